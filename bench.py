@@ -10,7 +10,13 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): the same frame is s
 puts them at their frame rows with one indexed copy.  Total work is fixed, so scaling = "strong".
 N = 1: the rows go through rt3_gather_rows (the C ABI's device-to-device gather), no collective.
 
-Prints one JSON line (rank 0).  Beside the driver's fields:
+Prints one JSON line (rank 0).  A plain run sets up, warms up, times --steps steps (ms_per_step = wall time of one), writes the
+last step's frame if --dump-outputs DIR is given, and prints the line.  --dump-outputs writes DIR/frame_rgba.npy: the frame rank 0
+holds after the last timed step, float32 (height, width, 4), R, G, B, A channel values 0..255 of its RGBA8 words; the scene, camera
+and seeds are fixed, so two builds given the same arguments can be compared pixel for pixel.
+--full adds what takes runs of its own: `cpu_baseline` (and `gpu_over_cpu`) and `extra_workloads` (below).
+
+Beside the driver's fields:
   roofline         the dominant kernel (k_trace_mfma32) against the unit it saturates.  `bound` names that unit: "valu_busy" — the vector ALU:
                    SQ_ACTIVE_INST_VALU x 4 cycles over the SIMD-cycles of the launch, ONE definition everywhere (README, DESIGN, profiles/README.md,
                    extra_workloads).  The counter advances once per issued vector instruction and once more per further 4-cycle pass of a multi-pass
@@ -24,8 +30,8 @@ Prints one JSON line (rank 0).  Beside the driver's fields:
                    achieved / peak / frac are the live matrix figures (the counters are then null, never reused on other code)
   algorithmic_equiv  SURVEY.md §8d's per-test figure (20 f32 FLOP per ray-sphere test) priced against the f32 peak — the
                    work a scalar formulation would do; NOT a roofline fraction of this kernel (it exceeds 1)
-  cpu_baseline     the CPU oracle timed on this host's cores on a bounded sample of the same workload
-  extra_workloads  short runs of the other BASELINE.json configs and of the Mode-R fixture (the only workload with a
+  cpu_baseline     (--full) the CPU oracle timed on this host's cores on a bounded sample of the same workload
+  extra_workloads  (--full) short runs of the other BASELINE.json configs and of the Mode-R fixture (the only workload with a
                    reference CPU time behind it), each with its own executed-MFMA fraction
 """
 import argparse
@@ -293,13 +299,19 @@ def main():
     ap.add_argument("--height", type=int, default=HEIGHT)
     ap.add_argument("--spp", type=int, default=SPP)
     ap.add_argument("--depth", type=int, default=DEPTH)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget (0 disables)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_workloads runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline and the extra_workloads (off: only the headline)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget with --full (0 disables)")
+    ap.add_argument("--no-extra", action="store_true", help="skip the extra_workloads runs of --full")
     ap.add_argument("--save-ppm", default="", help="rank 0 writes the last frame here")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the last timed step's frame as DIR/frame_rgba.npy (float32, height x width x RGBA, 0..255)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N > 1 ranks that ALL render on cuda:0 and gather over gloo through host memory: exercises this file's multi-rank control flow "
                          "(sharding, gather, stat reduction, the JSON line) where only one GPU is present; its numbers are not a measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -342,6 +354,7 @@ def main():
     # One explicit stream for the render, the gather and everything torch queues around them: the C ABI is handed its handle (never NULL,
     # which include/rt3.h defines as "the context's own stream"), RCCL orders its kernels behind torch's CURRENT stream, which is this one
     stream = torch.cuda.Stream(device=dev)
+    stream.wait_stream(torch.cuda.current_stream(dev))                  # the buffers' zero-fills come first, even with --warmup 0
 
     def step():
         with torch.cuda.stream(stream):
@@ -439,14 +452,20 @@ def main():
                     "note": "the figure north_star asks for: 12 B radiance record per sample; the 7.7 KB scene streams through LDS; "
                             "a high fraction here would mean lost reuse, not success"},
         }
-        if world == 1 and args.cpu_seconds > 0:
-            out["cpu_baseline"] = cpu_baseline(rt3, cr, mats, cam, args.cpu_seconds)
-            out["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
+        if args.dump_outputs or args.save_ppm:
+            frame = g.frame.cpu().numpy().view(np.uint32)               # the last timed step's frame (nothing has rendered since)
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            rgba = np.stack([(frame >> s) & 0xFF for s in (24, 16, 8, 0)], axis=-1).astype(np.float32)
+            np.save(os.path.join(args.dump_outputs, "frame_rgba.npy"), rgba)
         if args.save_ppm:
             f = rt3.Frame(W, H)
-            f.data[:] = g.frame.cpu().numpy().view(np.uint32)
+            f.data[:] = frame
             f.to_ppm(args.save_ppm)
-        if world == 1 and full_workload and not args.no_extra:
+        if args.full and world == 1 and args.cpu_seconds > 0:
+            out["cpu_baseline"] = cpu_baseline(rt3, cr, mats, cam, args.cpu_seconds)
+            out["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
+        if args.full and world == 1 and full_workload and not args.no_extra:
             out["extra_workloads"] = extra_workloads(rt3, r, np, fingerprint)
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -15,7 +15,7 @@ for p in (ROOT, HERE):
 import oracle_lib as O  # noqa: E402
 
 rt3 = importlib.import_module("raytracer-3_amd")
-TEDDY = "/root/reference/bin/objects/teddy.obj"
+TEDDY = os.path.join(GOLDEN, "teddy.obj")             # the reference's bin/objects/teddy.obj, as data
 
 
 def load_builtin_scene():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/*.npz.  Run in the build container (needs /root/reference for teddy.obj — read as DATA,
+"""Regenerates tests/golden/*.npz.  Reads tests/golden/teddy.obj (the reference's bin/objects/teddy.obj, kept here as DATA;
 nothing from the reference is executed):
 
     python tests/golden/make_golden.py

@@ -1,9 +1,10 @@
-"""bench.py's output contract: one JSON line with the fields the driver reads, plus the `roofline` and `cpu_baseline` objects."""
+"""bench.py's output contract: one JSON line with the fields the driver reads, plus the `roofline` object, and `cpu_baseline` with --full."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,7 +56,7 @@ def test_counter_provenance_follows_the_kernel_code_not_its_comments(tmp_path, m
 
 @pytest.mark.gpu
 def test_bench_line_has_every_field_of_the_contract():
-    p = run_bench("--spp", "8", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1")
+    p = run_bench("--spp", "8", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                         # ONE JSON line
@@ -127,10 +128,10 @@ def test_the_line_names_what_binds_with_one_definition(tmp_path, monkeypatch):
 
 @pytest.mark.gpu
 def test_full_workload_line_carries_the_binding_unit_and_the_extra_workloads(tmp_path):
-    """The default command (what the driver runs) at reduced steps: extra_workloads are there with the two-level filter's executed / equivalent counts,
+    """The --full command at reduced steps: extra_workloads are there with the two-level filter's executed / equivalent counts,
     and `roofline` follows the fingerprint rule — "valu_busy" with counter figures when profiles/r03_bench_pmc_k_trace.json belongs to this build, the
     live matrix figures otherwise."""
-    p = run_bench("--steps", "1", "--warmup", "1", "--cpu-seconds", "1")
+    p = run_bench("--steps", "1", "--warmup", "1", "--cpu-seconds", "1", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     r = d["roofline"]
@@ -148,3 +149,35 @@ def test_full_workload_line_carries_the_binding_unit_and_the_extra_workloads(tmp
         assert f["levels"] == 3 and f["filter_tests_executed"] * 50 < w["prim_tests"] and w["tests_per_s"] > 5e13       # brute-force equivalent
         assert "valu_busy" in w and "mfma_busy" in w and "counters_source" in w
     assert ew["config 5"]["filter"]["bound_tests_per_cast"] > 0 and ew["config 4"]["exact_tests_per_cast"] > 100
+
+
+def test_bench_offers_full_and_dump_outputs_and_refuses_zero_steps():
+    p = run_bench("--help")
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+    p = run_bench("--steps", "0")
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_and_dumps_the_last_frame(tmp_path, rt3):
+    """Without --full the line carries no baseline or extra workload; --dump-outputs writes the frame of the last timed step (the one
+    --save-ppm writes), and the same arguments give the same frame whatever the number of steps and warm-ups."""
+    p = run_bench("--spp", "8", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a"), "--save-ppm", str(tmp_path / "a.ppm"))
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert "cpu_baseline" not in d and "gpu_over_cpu" not in d and "extra_workloads" not in d
+    a = np.load(tmp_path / "a" / "frame_rgba.npy")
+    assert a.dtype == np.float32 and a.shape == (1080, 1920, 4)
+    assert np.array_equal(a, np.round(a)) and a.min() >= 0 and a.max() <= 255 and (a[..., 3] == 255).all() and a[..., :3].max() > 0
+    u = a.astype(np.uint32)
+    f = rt3.Frame(1920, 1080)
+    f.data[:] = (u[..., 0] << 24) | (u[..., 1] << 16) | (u[..., 2] << 8) | u[..., 3]
+    assert f.ppm_bytes() == (tmp_path / "a.ppm").read_bytes()
+    p = run_bench("--spp", "8", "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "b"))
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert np.array_equal(np.load(tmp_path / "b" / "frame_rgba.npy"), a)

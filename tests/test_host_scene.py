@@ -86,8 +86,6 @@ def test_malformed_object_indices_are_fatal_not_out_of_bounds(rt3, tmp_path, bod
 
 
 def test_teddy_matches_oracle(rt3, oracle):
-    if not os.path.exists(TEDDY):
-        pytest.skip("/root/reference not present (GPU box)")
     args = ((0.0, 0.0, -3.0), np.float32(1.0) / np.float32(17.0), (1.0, 0.0, 0.0))
     f, v = rt3.pre_render_entity(rt3.create_object(TEDDY, *args))
     of, ov = oracle.prerender_object(TEDDY, *args)

@@ -37,7 +37,7 @@ PY
 # checks its source fingerprint)
 cp $out/pmc_k_trace.json profiles/${RT3_PROFILE_TAG}_bench_pmc_k_trace.json
 fi   # RT3_TRACE_ONLY=1: only the traced run below, with the committed counter profiles (its JSON line then carries the tiled kernels' counters too)
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py > $out/bench_stdout.log 2>$out/bench_stderr.log || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full > $out/bench_stdout.log 2>$out/bench_stderr.log || exit 1
 echo "trace pass done"
 grep '^{' $out/bench_stdout.log | tail -1 > $out/bench_line.json
 cp $(ls $out/trace/*/*_kernel_stats.csv | head -1) $out/kernel_stats.csv
