@@ -243,6 +243,55 @@ uint32_t rt3_row_of_local(const rt3_params* params, uint32_t local_row);
 int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Batched ray queries   (the Mode-X nearest-hit engine for rays the caller makes)
+ * ------------------------------------------------------------------------------------------------- */
+/* One ray: 32 bytes, two 16-byte halves (origin, t_max | direction, pad).  The direction must be a unit vector (below). */
+typedef struct rt3_ray {
+    float    origin[3];
+    float    t_max;              /* hits count only for t < t_max; +inf: no limit */
+    float    direction[3];
+    uint32_t _pad;
+} rt3_ray;
+/* One result: 16 bytes. */
+typedef struct rt3_hit {
+    float    t;                  /* in units of the direction as given; +inf on a miss, NaN for an invalid ray */
+    uint32_t kind;               /* RT3_HIT_* */
+    uint32_t index;              /* the primitive's position in the caller's arrays (rt3_set_mesh / rt3_mesh_commit face order,
+                                    rt3_set_spheres order); 0xFFFFFFFF on a miss or an invalid ray */
+    uint32_t _pad;               /* 0 */
+} rt3_hit;
+#define RT3_HIT_NONE     0u
+#define RT3_HIT_FACE     1u
+#define RT3_HIT_SPHERE   2u
+#define RT3_HIT_INVALID  3u
+/* rt3_intersect*: for each ray, against the scene on the context (faces and spheres together), exactly what the Mode-X nearest-hit rule
+ * returns when its running best starts at t_max instead of +inf: faces first, then spheres; a face is accepted for t_min <= t, a sphere for
+ * t > t_min with the far-root rule; a hit counts only with t < t_max (a hit at exactly t_max is a miss); on equal t the earlier primitive
+ * wins, faces before spheres.  Equivalently: the nearest hit with t_max = +inf, kept only if t < t_max.  A miss is {+inf, RT3_HIT_NONE,
+ * 0xFFFFFFFF, 0}.
+ * rt3_occluded*: one uint32 per ray, 1 where such a hit exists, 0 where none does (exactly kind != RT3_HIT_NONE of rt3_intersect*),
+ * 0xFFFFFFFF for an invalid ray.
+ * A ray is INVALID when its origin or direction is not finite, when |d.d - 1| > 2^-20 (d.d as the fused chain fma(dz, dz, fma(dy, dy,
+ * dx * dx))), when t_max is NaN or when t_max <= t_min: it gets RT3_HIT_INVALID {NaN, 3, 0xFFFFFFFF, 0}, is not traced, not counted, and
+ * changes nothing for the other rays.
+ * Arguments: t_min finite and >= 0 (as in rt3_params); n <= 2^30; n == 0 does nothing and returns 0; device pointers 16-byte aligned
+ * (4-byte for the occlusion words); RT3_E_ARG otherwise; RT3_E_STATE without a scene.
+ * Streams follow the convention above: a query waits for the event the previous render or query recorded and records its own, so a
+ * later render, rt3_accum_download or query on the same context is ordered after it.  A query does not touch the accumulation of a
+ * progressive render (rt3_render_path_range continues bit-exactly across it).  rt3_get_stats afterwards: ray_casts = valid rays,
+ * prim_tests = ray_casts * (n_spheres + n_faces), samples = 0, launches, trace_ms and the filter counters.
+ * Kernel choice is Mode X's: k_trace_mfma32 for <= 512 spheres, the resident / tiled three-level form while the rows fit in LDS,
+ * k_trace_levels beyond, k_trace_brute under rt3_debug_force_brute / RT3_BRUTE; RT3_LEVELS, RT3_NO_RESIDENT, RT3_OLD_GROUPS and
+ * RT3_FORCE_TILED act as for renders.  Queries ignore the switches of forms they have none of: RT3_NO_MFMA (VALU k_trace), RT3_MFMA_K64,
+ * the flat filter (rt3_debug_force_flat_filter / RT3_NO_GROUPS) and RT3_FLAG_REFERENCE_PRIMARY. */
+/* Host arrays, synchronous. */
+int rt3_intersect(rt3_ctx* ctx, const rt3_ray* rays, uint32_t n, float t_min, rt3_hit* hits);
+int rt3_occluded(rt3_ctx* ctx, const rt3_ray* rays, uint32_t n, float t_min, uint32_t* out);
+/* Device arrays (n rt3_ray in, n rt3_hit | n uint32 out), asynchronous on `stream` (NULL = the context's own stream). */
+int rt3_intersect_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_min, void* d_hits, void* stream);
+int rt3_occluded_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_min, void* d_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side scene API   (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)
  * ------------------------------------------------------------------------------------------------- */
 /* cpu_pre_render_triangle (src/lib/entities/Triangle.cpp:28-76): 1 face, 3 vertices (xyzw). */

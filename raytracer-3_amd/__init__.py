@@ -37,6 +37,11 @@ GFACE = np.dtype([("v1", "<u4"), ("v2", "<u4"), ("v3", "<u4"), ("_p0", "<u4"),
 MATERIAL = np.dtype([("rgb", "<f4", 3), ("param", "<f4"), ("kind", "<u4")])
 
 MAT_FLAT, MAT_LAMBERT, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2, 3
+# batched ray queries (rt3_intersect / rt3_occluded): rt3_ray (32 bytes) and rt3_hit (16 bytes)
+RAY = np.dtype([("origin", "<f4", 3), ("t_max", "<f4"), ("direction", "<f4", 3), ("_pad", "<u4")])
+HIT = np.dtype([("t", "<f4"), ("kind", "<u4"), ("index", "<u4"), ("_pad", "<u4")])
+HIT_NONE, HIT_FACE, HIT_SPHERE, HIT_INVALID = 0, 1, 2, 3
+OCCLUDED_INVALID = 0xFFFFFFFF      # rt3_occluded's word for an invalid ray
 FLAG_GAMMA2, FLAG_BLACK_BACKGROUND, FLAG_REFERENCE_PRIMARY, FLAG_VARIANCE = 1, 2, 4, 8
 
 
@@ -56,6 +61,31 @@ class rt3_stats(C.Structure):
                 ("trace_ms", C.c_float), ("total_ms", C.c_float), ("launches", C.c_uint32),
                 ("n_spheres", C.c_uint32), ("n_faces", C.c_uint32), ("mfma_flop_per_instruction", C.c_uint32), ("mfma_instructions", C.c_uint64),
                 ("exact_tests", C.c_uint64), ("filter_tests", C.c_uint64), ("bound_tests", C.c_uint64)]
+
+
+class rt3_ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("direction", C.c_float * 3), ("_pad", C.c_uint32)]
+
+
+class rt3_hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("kind", C.c_uint32), ("index", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+def make_rays(origins, directions, t_max=np.inf):
+    """Packs rays for HipRenderer.intersect / occluded: (N, 3) origins and directions (any length; each direction is
+    normalised in float32) and t_max (a scalar or (N,)).  A zero or non-finite direction stays invalid."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError("origins and directions differ in length")
+    rays = np.zeros(len(o), RAY)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        dd = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        inv = np.float32(1.0) / np.sqrt(dd)
+        rays["direction"] = d * inv[:, None]
+    rays["origin"] = o
+    rays["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), (len(o),))
+    return rays
 
 
 class rt3_gather_copy(C.Structure):
@@ -89,6 +119,7 @@ EXPORTS = [
     "rt3_render_path_range", "rt3_render_path_range_device", "rt3_accum_download", "rt3_accum_upload", "rt3_gather_rows",
     "rt3_stream", "rt3_synchronize", "rt3_device_alloc_words", "rt3_device_free", "rt3_device_read_words", "rt3_debug_force_brute",
     "rt3_abi_version", "rt3_debug_force_flat_filter", "rt3_gather_plan",
+    "rt3_intersect", "rt3_occluded", "rt3_intersect_device", "rt3_occluded_device",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -142,6 +173,8 @@ def lib():
         "rt3_device_alloc_words": (vp, [vp, u64]), "rt3_device_free": (None, [vp, vp]),
         "rt3_device_read_words": (i32, [vp, vp, u64, vp]), "rt3_debug_force_brute": (i32, [vp, i32]),
         "rt3_abi_version": (u32, []), "rt3_debug_force_flat_filter": (i32, [vp, i32]), "rt3_gather_plan": (i32, [vp, vp]),
+        "rt3_intersect": (i32, [vp, vp, u32, f32, vp]), "rt3_occluded": (i32, [vp, vp, u32, f32, vp]),
+        "rt3_intersect_device": (i32, [vp, vp, u32, f32, vp, vp]), "rt3_occluded_device": (i32, [vp, vp, u32, f32, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -595,6 +628,54 @@ class HipRenderer(Renderer):
     def render_device(self, camera_c, width, height, d_out_ptr, stream_ptr=None):
         self._check(lib().rt3_render_device(self._ctx, C.byref(camera_c), width, height, C.c_void_p(d_out_ptr),
                                             C.c_void_p(stream_ptr or 0)))
+
+    # -- batched ray queries (rt3_intersect* / rt3_occluded*) ------------------------------------
+    @staticmethod
+    def _torch_rays(rays):
+        """A torch tensor of rays on the GPU, or None for host rays."""
+        mod = type(rays).__module__
+        if not mod.startswith("torch"):
+            return None
+        if not rays.is_cuda or str(rays.dtype) != "torch.float32" or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise Fatal("device rays must be a contiguous (N, 8) float32 tensor on the GPU")
+        return rays
+
+    @staticmethod
+    def _host_rays(rays):
+        a = np.asarray(rays)
+        if a.dtype == RAY:
+            return np.ascontiguousarray(a).reshape(-1)
+        if a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 8:
+            return np.ascontiguousarray(a).view(RAY).reshape(-1)
+        raise Fatal("rays must be a RAY array or an (N, 8) float32 array")
+
+    def _query(self, rays, t_min, occluded):
+        t = self._torch_rays(rays)
+        if t is not None:
+            import torch
+            n = t.shape[0]
+            out = torch.empty((n,) if occluded else (n, 4), dtype=torch.int32, device=t.device)
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+            fn = lib().rt3_occluded_device if occluded else lib().rt3_intersect_device
+            self._check(fn(self._ctx, C.c_void_p(t.data_ptr()), n, np.float32(t_min), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+            if occluded:
+                return out
+            return out[:, 0].view(torch.float32), out[:, 1], out[:, 2]
+        r = self._host_rays(rays)
+        out = np.zeros(len(r), np.uint32 if occluded else HIT)
+        fn = lib().rt3_occluded if occluded else lib().rt3_intersect
+        self._check(fn(self._ctx, _p(r), len(r), np.float32(t_min), _p(out)))
+        return out
+
+    def intersect(self, rays, t_min=0.001):
+        """Nearest hit of every ray (rt3_intersect).  numpy RAY / (N, 8) float32 -> numpy HIT array; a contiguous (N, 8) float32 torch
+        tensor on the GPU -> (t, kind, index), views of one (N, 4) int32 tensor, computed on torch.cuda.current_stream()."""
+        return self._query(rays, t_min, False)
+
+    def occluded(self, rays, t_min=0.001):
+        """1 where a ray hits something before its t_max, 0 where not, 0xFFFFFFFF for an invalid ray (rt3_occluded): numpy uint32 for host
+        rays, an (N,) int32 tensor for device rays."""
+        return self._query(rays, t_min, True)
 
     def set_sample_storage_cap(self, nbytes):
         self._check(lib().rt3_set_sample_storage_cap(self._ctx, nbytes))

@@ -75,6 +75,8 @@ struct rt3_ctx {
     float4* d_accum = nullptr; size_t accum_entries = 0;
     float4* d_accum_sq = nullptr; size_t accum_sq_entries = 0;      // RT3_FLAG_VARIANCE: per-pixel sums of squares
     uint32_t* d_out = nullptr; size_t out_entries = 0;
+    float4* d_qrays = nullptr; size_t qrays_entries = 0;           // batched ray queries, host forms: the rays and the results on the device
+    uint4* d_qout = nullptr; size_t qout_entries = 0;
     uint32_t* d_work = nullptr;                                     // [0] work counter
     unsigned long long* d_casts = nullptr;
     uint64_t rad_cap_bytes = 16ull << 30;
@@ -395,6 +397,148 @@ int check_params(rt3_ctx* ctx, const rt3_params* p) {
     return 0;
 }
 
+// The scene half of TraceArgs (what renders and queries share): records, filter centres, direct spheres, counters.
+TraceArgs scene_args(const rt3_ctx* ctx) {
+    TraceArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.sph = ctx->d_sph; A.sph_invr = ctx->d_sph_invr; A.sph_mat = ctx->d_sph_mat; A.sph_kind = ctx->d_sph_kind; A.n_sph = ctx->n_sph;
+    A.tri = ctx->d_tri; A.tri_mat = ctx->d_tri_mat; A.tri_kind = ctx->d_tri_kind; A.tri_bound = ctx->d_tri_bound; A.n_tri = ctx->n_faces;
+    A.work_counter = ctx->d_work; A.cast_counter = ctx->d_casts;
+    A.fcx = ctx->sph_centre[0]; A.fcy = ctx->sph_centre[1]; A.fcz = ctx->sph_centre[2];
+    A.tcx = ctx->tri_centre[0]; A.tcy = ctx->tri_centre[1]; A.tcz = ctx->tri_centre[2];
+    A.n_direct = ctx->n_direct;
+    for (int i = 0; i < 4; i++) A.direct[i] = ctx->direct[i];
+    return A;
+}
+
+bool cam_at_origin(const rt3_camera* cam) { return cam->origin[0] == 0.0f && cam->origin[1] == 0.0f && cam->origin[2] == 0.0f; }
+
+// ---- which trace kernel: ONE rule for Mode-X renders and batched ray queries (QUERY: the query form of the same kernel)
+//   brute         every ray against every primitive (debug switch / RT3_BRUTE=1; REFERENCE_PRIMARY with a camera off the origin or a lens)
+//   mfma_single   sphere scenes of <= 512 spheres, everything in LDS (the bench kernel)
+//   mfma tiled    every other scene
+//   valu          RT3_NO_MFMA=1: the vector-ALU scans (A/B reference; renders only)
+// Queries have no form of the VALU kernels, of K = 64, of the flat filter or of REF: they ignore those switches (rt3.h).
+using TraceKernel = void (*)(const TraceArgs);
+using TiledKernel = void (*)(const TraceArgs, const u32x4*, const u32x4*);
+using SingleKernel = void (*)(const TraceArgs, const u32x4*, uint32_t);
+struct TracePlan {
+    TraceKernel plain = nullptr;
+    TiledKernel tiled = nullptr;
+    SingleKernel single = nullptr;                                  // k_trace_mfma32 | k_trace_mfma (RT3_MFMA_K64)
+    const u32x4* frag_a = nullptr; const u32x4* frag_b = nullptr;   // tiled: faces' and spheres' rows; single: the spheres' fragments in frag_a
+    uint32_t mfma_blocks = 0;
+    size_t lds = 0;
+    int block = kBlock;
+    int per_cu = 0;                                                 // workgroups per CU the launch configuration allows (<= 8)
+    bool mfma16 = false;                                            // rt3_stats::mfma_flop_per_instruction: 16x16x32 (tiled kernels, k_trace_mfma32)
+    uint64_t filter_rows = 0;                                       // rows the matrix filter scans per ray cast
+};
+template <bool Q, uint32_t L, bool R>
+TiledKernel levels_kernel(bool has_tri, bool has_sph, bool ref) {
+    if constexpr (Q) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, true> : k_trace_levels<true, false, false, L, R, true>) : k_trace_levels<false, true, false, L, R, true>;
+    else return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R> : (ref ? k_trace_levels<true, false, true, L, R> : k_trace_levels<true, false, false, L, R>))
+                        : k_trace_levels<false, true, false, L, R>;
+}
+template <bool Q, bool RES>
+TiledKernel grouped_kernel(bool has_tri, bool has_sph, bool ref) {
+    constexpr uint32_t GT = kGroupTri, GS = kGroupSph, SUP = kSuper;
+    if constexpr (Q) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, true>)
+                                    : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES, true>;
+    else return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES> : (ref ? k_trace_mfma_tiled<true, false, true, GT, 1, SUP, RES> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES>))
+                        : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES>;
+}
+// Fills A's filter fields and T.  ref: RT3_FLAG_REFERENCE_PRIMARY (renders); ref_brute: REF with a camera only the brute-force kernel serves.
+int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query, TracePlan& T) {
+    const bool has_tri = ctx->n_faces > 0, has_sph = ctx->n_sph > 0;
+    const bool brute = ctx->force_brute || getenv("RT3_BRUTE") || ref_brute;
+    const bool use_mfma = !brute && (query || !getenv("RT3_NO_MFMA"));
+    const bool mfma_single = use_mfma && !has_tri && has_sph && ctx->n_sph <= kMfmaSphMax && !getenv("RT3_FORCE_TILED");   // (A/B knob)
+    const bool single_k64 = !query && mfma_single && getenv("RT3_MFMA_K64") != nullptr;
+    const bool sph_lds = has_sph && ctx->n_sph <= kSphLdsMax;
+    const bool grouped = kGroupTri > 1 && kGroupSph > 1 && (query || (!ctx->force_flat && !getenv("RT3_NO_GROUPS")));
+    A.n_tri_rows = grouped ? ctx->n_tri_groups : ctx->n_faces;
+    A.n_sph_rows = grouped ? ctx->n_sph_groups : ctx->n_sph;
+    A.sph_grp = ctx->d_sph_grp; A.sph_perm = ctx->d_sph_perm; A.tri_grp = ctx->d_tri_grp; A.tri_perm = ctx->d_tri_perm; A.tri_rec = ctx->d_tri_rec;
+    A.tri_leaf = ctx->d_tri_leaf; A.sph_leaf = ctx->d_sph_leaf; A.n_tri_leaves = ctx->n_tri_leaves; A.n_sph_leaves = ctx->n_sph_leaves;
+    A.tri_rowb = ctx->d_tri_rowb; A.sph_rowb = ctx->d_sph_rowb;
+    T.mfma_blocks = (ctx->n_sph + 31u) / 32u;
+    bool resident = false;
+    uint32_t levels = 0;                                            // k_trace_levels: 3 | 4
+    if (brute) {
+        T.plain = query ? k_trace_brute<false, true> : ref ? k_trace_brute<true> : k_trace_brute<false>;
+    } else if (mfma_single) {
+        // k_trace_mfma32 (K = 32 form, pair list); RT3_MFMA_K64=1: k_trace_mfma, round 1's K = 64 form on v_mfma_f32_32x32x16_bf16 (A/B reference)
+        T.lds = single_k64 ? (size_t)T.mfma_blocks * (4096 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes
+                           : (size_t)T.mfma_blocks * (2048 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes + (size_t)kMB * 8 + (size_t)(kMB / 64) * kPairCap * 4;
+        T.block = kMB;
+        T.single = single_k64 ? k_trace_mfma : query ? k_trace_mfma32<true> : k_trace_mfma32<>;
+        T.frag_a = (const u32x4*)(single_k64 ? (const void*)ctx->d_sph_frag : (const void*)ctx->d_sph_frag32);
+    } else if (use_mfma) {
+        // the two-level filter (rows = groups of primitives, DESIGN.md 5.2e) unless RT3_NO_GROUPS=1 asks for the flat one (A/B reference, tests)
+        constexpr uint32_t SUP = kSuper;
+        const uint32_t row_blocks = (has_tri ? (A.n_tri_rows + 31u) / 32u : 0u) + (has_sph ? (A.n_sph_rows + 31u) / 32u : 0u);
+        const uint32_t super_blocks = (has_tri ? (ctx->n_tri_super + 31u) / 32u : 0u) + (has_sph ? (ctx->n_sph_super + 31u) / 32u : 0u);
+        // While the rows of 64 fit in LDS (<= kResidentBlocks row blocks, 112 000 primitives: both BASELINE scenes) k_trace_mfma_tiled's resident three-level
+        // form runs; beyond, k_trace_levels (rt3_level_filter.hpp) with FOUR levels — the matrix cores scan super-rows of 512, resident up to 570 000
+        // primitives, through a tile after that.  RT3_LEVELS=3|4 forces k_trace_levels with that many levels, RT3_OLD_GROUPS=1 the nested form (A/B, tests)
+        const char* force_levels = getenv("RT3_LEVELS");
+        const bool no_res_env = getenv("RT3_NO_RESIDENT") != nullptr;
+        const bool lev_kernel = grouped && SUP > 1 && !getenv("RT3_OLD_GROUPS") && (force_levels != nullptr || row_blocks > kResidentBlocks);
+        if (lev_kernel) {
+            levels = force_levels ? (atoi(force_levels) == 4 ? 4u : 3u) : 4u;
+            const uint32_t top_blocks = levels == 4 ? super_blocks : row_blocks;
+            resident = !no_res_env && top_blocks <= lev_resident_blocks(levels);
+            A.n_tri_top = levels == 4 ? ctx->n_tri_super : ctx->n_tri_groups; A.n_sph_top = levels == 4 ? ctx->n_sph_super : ctx->n_sph_groups;
+            A.tri_topb = levels == 4 ? ctx->d_tri_srowb : ctx->d_tri_rowb; A.sph_topb = levels == 4 ? ctx->d_sph_srowb : ctx->d_sph_rowb;
+            if (query) T.tiled = levels == 4 ? (resident ? levels_kernel<true, 4, true>(has_tri, has_sph, ref) : levels_kernel<true, 4, false>(has_tri, has_sph, ref))
+                                             : (resident ? levels_kernel<true, 3, true>(has_tri, has_sph, ref) : levels_kernel<true, 3, false>(has_tri, has_sph, ref));
+            else T.tiled = levels == 4 ? (resident ? levels_kernel<false, 4, true>(has_tri, has_sph, ref) : levels_kernel<false, 4, false>(has_tri, has_sph, ref))
+                                       : (resident ? levels_kernel<false, 3, true>(has_tri, has_sph, ref) : levels_kernel<false, 3, false>(has_tri, has_sph, ref));
+            T.lds = lev_lds_fixed(levels, resident) + (resident ? (size_t)top_blocks * 2048u : 0u);
+        } else {
+            resident = grouped && SUP > 1 && row_blocks <= kResidentBlocks && !getenv("RT3_NO_RESIDENT");      // all rows fit in LDS: no tiles, no barriers
+            if (resident) T.tiled = query ? grouped_kernel<true, true>(has_tri, has_sph, ref) : grouped_kernel<false, true>(has_tri, has_sph, ref);
+            else if (grouped) T.tiled = query ? grouped_kernel<true, false>(has_tri, has_sph, ref) : grouped_kernel<false, false>(has_tri, has_sph, ref);
+            else T.tiled = has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false> : (ref ? k_trace_mfma_tiled<true, false, true> : k_trace_mfma_tiled<true, false, false>))
+                                   : k_trace_mfma_tiled<false, true, false>;
+            T.lds = resident ? (size_t)row_blocks * 2048u + (size_t)kBmBlocksRes * kTB * 4u + (size_t)kTB * 8u + (size_t)(kTB / 64u) * kPairCap * 4u * 3u : kTraceTiledLdsBytes;
+        }
+        T.block = kTB;
+        if (levels == 4) { T.frag_a = ctx->d_tri_sfrag; T.frag_b = ctx->d_sph_sfrag; }
+        else { T.frag_a = grouped ? ctx->d_tri_gfrag : ctx->d_tri_frag; T.frag_b = grouped ? ctx->d_sph_gfrag : (const u32x4*)ctx->d_sph_frag32; }
+    } else {
+        T.lds = sph_lds ? (size_t)ctx->n_sph * sizeof(float4) : 0;
+        T.plain = has_tri ? (has_sph ? (sph_lds ? k_trace<true, true, true> : k_trace<true, true, false>)
+                                     : (ref ? k_trace<true, false, false, true> : k_trace<true, false, false>))
+                          : (sph_lds ? k_trace<false, true, true> : k_trace<false, true, false>);
+    }
+    const void* kptr = T.single ? (const void*)T.single : T.tiled ? (const void*)T.tiled : (const void*)T.plain;
+    int rc;
+    if ((rc = blocks_per_cu(ctx, kptr, T.block, T.lds, &T.per_cu))) return rc;
+    if (T.per_cu < 1) return fail(ctx, RT3_E_DEVICE, "the trace kernel does not fit on a CU");
+    T.per_cu = std::min(T.per_cu, 8);
+    if (T.tiled && grouped) {                                       // one strip per wave of the largest grid this launch configuration can have
+        if ((rc = ensure(ctx, &ctx->d_strips, &ctx->strip_entries, (size_t)ctx->num_cu * T.per_cu * (kTB / 64u) * kStripPairs))) return rc;
+        A.pair_strips = ctx->d_strips;
+    }
+    T.mfma16 = T.tiled != nullptr || (mfma_single && !single_k64);
+    T.filter_rows = levels ? (uint64_t)(has_tri ? A.n_tri_top : 0u) + (has_sph ? A.n_sph_top : 0u) : T.tiled ? (uint64_t)A.n_tri_rows + A.n_sph_rows
+                  : mfma_single ? ctx->n_sph : 0;
+    return 0;
+}
+// Workgroups for `total` work items: enough for kWorkChunk items per wave, at most what fits on the device at once.
+uint32_t trace_grid(const rt3_ctx* ctx, const TracePlan& T, uint32_t total) {
+    const uint32_t waves_per_block = (uint32_t)T.block / 64u;
+    const uint32_t want_blocks = (total + kWorkChunk * waves_per_block - 1) / (kWorkChunk * waves_per_block);
+    return std::max(1u, std::min<uint32_t>((uint32_t)(ctx->num_cu * T.per_cu), want_blocks));
+}
+void launch_trace(const TracePlan& T, const TraceArgs& A, uint32_t grid, hipStream_t stream) {
+    if (T.single) hipLaunchKernelGGL(T.single, dim3(grid), dim3(kMB), T.lds, stream, A, T.frag_a, T.mfma_blocks);
+    else if (T.tiled) hipLaunchKernelGGL(T.tiled, dim3(grid), dim3(kTB), T.lds, stream, A, T.frag_a, T.frag_b);
+    else hipLaunchKernelGGL(T.plain, dim3(grid), dim3(kBlock), T.lds, stream, A);
+}
+
 }  // namespace
 
 extern "C" {
@@ -443,7 +587,7 @@ void rt3_destroy(rt3_ctx* ctx) {
     void* bufs[] = { ctx->d_gfaces, ctx->d_verts, ctx->d_face_mats_in, ctx->d_error, ctx->d_tri, ctx->d_tri_mat, ctx->d_tri_kind, ctx->d_tri_bound, ctx->d_tri_frag, ctx->d_sph, ctx->d_sph_frag, ctx->d_sph_frag32, ctx->d_sph_invr, ctx->d_sph_mat, ctx->d_sph_kind,
                      ctx->d_rad, ctx->d_accum, ctx->d_accum_sq, ctx->d_out, ctx->d_work, ctx->d_casts, ctx->d_box, ctx->d_tri_frag_r,
                      ctx->d_tri_gfrag, ctx->d_sph_gfrag, ctx->d_sph_grp, ctx->d_sph_perm, ctx->d_strips, ctx->d_tri_grp, ctx->d_tri_perm, ctx->d_tri_leaf, ctx->d_sph_leaf, ctx->d_tri_rowb, ctx->d_sph_rowb,
-                     ctx->d_tri_sfrag, ctx->d_sph_sfrag, ctx->d_tri_srowb, ctx->d_sph_srowb, ctx->d_tri_rec };
+                     ctx->d_tri_sfrag, ctx->d_sph_sfrag, ctx->d_tri_srowb, ctx->d_sph_srowb, ctx->d_tri_rec, ctx->d_qrays, ctx->d_qout };
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (auto& p : ctx->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
@@ -861,10 +1005,7 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
         if (var && (rc = ensure(ctx, &ctx->d_accum_sq, &ctx->accum_sq_entries, (size_t)npix))) return rc;
     }
 
-    TraceArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.sph = ctx->d_sph; A.sph_invr = ctx->d_sph_invr; A.sph_mat = ctx->d_sph_mat; A.sph_kind = ctx->d_sph_kind; A.n_sph = ctx->n_sph;
-    A.tri = ctx->d_tri; A.tri_mat = ctx->d_tri_mat; A.tri_kind = ctx->d_tri_kind; A.tri_bound = ctx->d_tri_bound; A.n_tri = ctx->n_faces;
+    TraceArgs A = scene_args(ctx);
     A.cam = cam_dev(cam);
     A.lens_radius = p->lens_radius;
     {
@@ -889,102 +1030,10 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     if (!fastdiv_ok(npix, 0x7FFFFFFFu) || !fastdiv_ok(p->width, 0x7FFFFFFFu) || !fastdiv_ok(A.edge ? A.edge : 1, p->spp) ||
         !fastdiv_ok(p->tile_count > 1 ? p->tile_rows : 1, p->height))
         return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
-    A.rad = ctx->d_rad; A.work_counter = ctx->d_work; A.cast_counter = ctx->d_casts;
-    A.fcx = ctx->sph_centre[0]; A.fcy = ctx->sph_centre[1]; A.fcz = ctx->sph_centre[2];
-    A.tcx = ctx->tri_centre[0]; A.tcy = ctx->tri_centre[1]; A.tcz = ctx->tri_centre[2];
-    A.n_direct = ctx->n_direct;
-    for (int i = 0; i < 4; i++) A.direct[i] = ctx->direct[i];
+    A.rad = ctx->d_rad;
 
-    // ---- which kernel
-    //   brute         every ray against every primitive (debug switch / RT3_BRUTE=1; REFERENCE_PRIMARY with a camera off the origin or a lens)
-    //   mfma_single   sphere scenes of <= 512 spheres, everything in LDS (the bench kernel)
-    //   mfma tiled    every other scene
-    //   valu          RT3_NO_MFMA=1: the vector-ALU scans (A/B reference)
-    using TraceKernel = void (*)(const TraceArgs);
-    using TiledKernel = void (*)(const TraceArgs, const u32x4*, const u32x4*);
-    const bool has_tri = ctx->n_faces > 0, has_sph = ctx->n_sph > 0;
-    const bool cam_at_origin = cam->origin[0] == 0.0f && cam->origin[1] == 0.0f && cam->origin[2] == 0.0f;
-    const bool brute = ctx->force_brute || getenv("RT3_BRUTE") || (ref && !(cam_at_origin && !(p->lens_radius > 0.0f)));
-    const bool use_mfma = !brute && !getenv("RT3_NO_MFMA");
-    const bool mfma_single = use_mfma && !has_tri && has_sph && ctx->n_sph <= kMfmaSphMax && !getenv("RT3_FORCE_TILED");   // (A/B knob)
-    const bool single_k64 = mfma_single && getenv("RT3_MFMA_K64") != nullptr;
-    const bool sph_lds = has_sph && ctx->n_sph <= kSphLdsMax;
-    const bool grouped = kGroupTri > 1 && kGroupSph > 1 && !ctx->force_flat && !getenv("RT3_NO_GROUPS");
-    A.n_tri_rows = grouped ? ctx->n_tri_groups : ctx->n_faces;
-    A.n_sph_rows = grouped ? ctx->n_sph_groups : ctx->n_sph;
-    A.sph_grp = ctx->d_sph_grp; A.sph_perm = ctx->d_sph_perm; A.tri_grp = ctx->d_tri_grp; A.tri_perm = ctx->d_tri_perm; A.tri_rec = ctx->d_tri_rec;
-    A.tri_leaf = ctx->d_tri_leaf; A.sph_leaf = ctx->d_sph_leaf; A.n_tri_leaves = ctx->n_tri_leaves; A.n_sph_leaves = ctx->n_sph_leaves;
-    A.tri_rowb = ctx->d_tri_rowb; A.sph_rowb = ctx->d_sph_rowb;
-    const uint32_t mfma_blocks = (ctx->n_sph + 31u) / 32u;
-    TraceKernel plain = nullptr;
-    TiledKernel tiled = nullptr;
-    bool resident = false;
-    uint32_t levels = 0;                                            // k_trace_levels: 3 | 4
-    size_t lds = 0;
-    int block = kBlock;
-    const void* kptr = nullptr;
-    if (brute) {
-        plain = ref ? k_trace_brute<true> : k_trace_brute<false>;
-        kptr = (const void*)plain;
-    } else if (mfma_single) {
-        // k_trace_mfma32 (K = 32 form, pair list); RT3_MFMA_K64=1: k_trace_mfma, round 1's K = 64 form on v_mfma_f32_32x32x16_bf16 (A/B reference)
-        lds = single_k64 ? (size_t)mfma_blocks * (4096 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes
-                         : (size_t)mfma_blocks * (2048 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes + (size_t)kMB * 8 + (size_t)(kMB / 64) * kPairCap * 4;
-        block = kMB;
-        kptr = single_k64 ? (const void*)k_trace_mfma : (const void*)k_trace_mfma32;
-    } else if (use_mfma) {
-        // the two-level filter (rows = groups of primitives, DESIGN.md 5.2e) unless RT3_NO_GROUPS=1 asks for the flat one (A/B reference, tests)
-        constexpr uint32_t GT = kGroupTri, GS = kGroupSph, SUP = kSuper;
-        const uint32_t row_blocks = (has_tri ? (A.n_tri_rows + 31u) / 32u : 0u) + (has_sph ? (A.n_sph_rows + 31u) / 32u : 0u);
-        const uint32_t super_blocks = (has_tri ? (ctx->n_tri_super + 31u) / 32u : 0u) + (has_sph ? (ctx->n_sph_super + 31u) / 32u : 0u);
-        // While the rows of 64 fit in LDS (<= kResidentBlocks row blocks, 112 000 primitives: both BASELINE scenes) k_trace_mfma_tiled's resident three-level
-        // form runs; beyond, k_trace_levels (rt3_level_filter.hpp) with FOUR levels — the matrix cores scan super-rows of 512, resident up to 570 000
-        // primitives, through a tile after that.  RT3_LEVELS=3|4 forces k_trace_levels with that many levels, RT3_OLD_GROUPS=1 the nested form (A/B, tests)
-        const char* force_levels = getenv("RT3_LEVELS");
-        const bool no_res_env = getenv("RT3_NO_RESIDENT") != nullptr;
-        const bool lev_kernel = grouped && SUP > 1 && !getenv("RT3_OLD_GROUPS") && (force_levels != nullptr || row_blocks > kResidentBlocks);
-        if (lev_kernel) {
-            levels = force_levels ? (atoi(force_levels) == 4 ? 4u : 3u) : 4u;
-            const uint32_t top_blocks = levels == 4 ? super_blocks : row_blocks;
-            resident = !no_res_env && top_blocks <= lev_resident_blocks(levels);
-            A.n_tri_top = levels == 4 ? ctx->n_tri_super : ctx->n_tri_groups; A.n_sph_top = levels == 4 ? ctx->n_sph_super : ctx->n_sph_groups;
-            A.tri_topb = levels == 4 ? ctx->d_tri_srowb : ctx->d_tri_rowb; A.sph_topb = levels == 4 ? ctx->d_sph_srowb : ctx->d_sph_rowb;
-#define RT3_LEV(L, R) (has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R> : (ref ? k_trace_levels<true, false, true, L, R> : k_trace_levels<true, false, false, L, R>)) \
-                               : k_trace_levels<false, true, false, L, R>)
-            tiled = levels == 4 ? (resident ? RT3_LEV(4, true) : RT3_LEV(4, false)) : (resident ? RT3_LEV(3, true) : RT3_LEV(3, false));
-#undef RT3_LEV
-            lds = lev_lds_fixed(levels, resident) + (resident ? (size_t)top_blocks * 2048u : 0u);
-        } else {
-        resident = grouped && SUP > 1 && row_blocks <= kResidentBlocks && !getenv("RT3_NO_RESIDENT");      // all rows fit in LDS: no tiles, no barriers
-        if (resident)
-            tiled = has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, true> : (ref ? k_trace_mfma_tiled<true, false, true, GT, 1, SUP, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, true>))
-                            : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, true>;
-        else if (grouped)
-            tiled = has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP> : (ref ? k_trace_mfma_tiled<true, false, true, GT, 1, SUP> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP>))
-                            : k_trace_mfma_tiled<false, true, false, 1, GS, SUP>;
-        else
-            tiled = has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false> : (ref ? k_trace_mfma_tiled<true, false, true> : k_trace_mfma_tiled<true, false, false>))
-                            : k_trace_mfma_tiled<false, true, false>;
-        lds = resident ? (size_t)row_blocks * 2048u + (size_t)kBmBlocksRes * kTB * 4u + (size_t)kTB * 8u + (size_t)(kTB / 64u) * kPairCap * 4u * 3u : kTraceTiledLdsBytes;
-        }
-        block = kTB;
-        kptr = (const void*)tiled;
-
-    } else {
-        lds = sph_lds ? (size_t)ctx->n_sph * sizeof(float4) : 0;
-        plain = has_tri ? (has_sph ? (sph_lds ? k_trace<true, true, true> : k_trace<true, true, false>)
-                                   : (ref ? k_trace<true, false, false, true> : k_trace<true, false, false>))
-                        : (sph_lds ? k_trace<false, true, true> : k_trace<false, true, false>);
-        kptr = (const void*)plain;
-    }
-    int per_cu = 0;
-    if ((rc = blocks_per_cu(ctx, kptr, block, lds, &per_cu))) return rc;
-    if (per_cu < 1) return fail(ctx, RT3_E_DEVICE, "the trace kernel does not fit on a CU");
-    per_cu = std::min(per_cu, 8);
-    if (tiled && grouped) {                                         // one strip per wave of the largest grid this launch configuration can have
-        if ((rc = ensure(ctx, &ctx->d_strips, &ctx->strip_entries, (size_t)ctx->num_cu * per_cu * (kTB / 64u) * kStripPairs))) return rc;
-        A.pair_strips = ctx->d_strips;
-    }
+    TracePlan T;
+    if ((rc = plan_trace(ctx, A, ref, ref && !(cam_at_origin(cam) && !(p->lens_radius > 0.0f)), false, T))) return rc;
 
     RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
     RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 128, stream));
@@ -996,19 +1045,12 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
         const uint32_t ns = std::min(batch, sample_begin + sample_count - s0);
         A.s0 = s0;
         A.total = npix * ns;
-        const uint32_t waves_per_block = (uint32_t)block / 64u;
-        const uint32_t want_blocks = (A.total + kWorkChunk * waves_per_block - 1) / (kWorkChunk * waves_per_block);
-        const uint32_t grid = std::max(1u, std::min<uint32_t>((uint32_t)(ctx->num_cu * per_cu), want_blocks));
+        const uint32_t grid = trace_grid(ctx, T, A.total);
         hipEvent_t a, b;
         if ((rc = take_event_pair(ctx, &a, &b))) return rc;
         RT3_HIP(hipMemsetAsync(ctx->d_work, 0, 4, stream));
         RT3_HIP(hipEventRecord(a, stream));
-        if (mfma_single && single_k64) hipLaunchKernelGGL(k_trace_mfma, dim3(grid), dim3(kMB), lds, stream, A, (const u32x4*)ctx->d_sph_frag, mfma_blocks);
-        else if (mfma_single) hipLaunchKernelGGL(k_trace_mfma32, dim3(grid), dim3(kMB), lds, stream, A, (const u32x4*)ctx->d_sph_frag32, mfma_blocks);
-        else if (tiled && levels == 4) hipLaunchKernelGGL(tiled, dim3(grid), dim3(kTB), lds, stream, A, (const u32x4*)ctx->d_tri_sfrag, (const u32x4*)ctx->d_sph_sfrag);
-        else if (tiled) hipLaunchKernelGGL(tiled, dim3(grid), dim3(kTB), lds, stream, A, (const u32x4*)(grouped ? ctx->d_tri_gfrag : ctx->d_tri_frag),
-                                           (const u32x4*)(grouped ? ctx->d_sph_gfrag : (u32x4*)ctx->d_sph_frag32));
-        else hipLaunchKernelGGL(plain, dim3(grid), dim3(kBlock), lds, stream, A);
+        launch_trace(T, A, grid, stream);
         RT3_HIP(hipGetLastError());
         RT3_HIP(hipEventRecord(b, stream));
         const dim3 ag((npix + kBlock - 1) / kBlock), ab(kBlock);
@@ -1024,8 +1066,8 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     ctx->last_stream = stream;
     ctx->last_samples = (uint64_t)npix * sample_count;
     ctx->last_was_path = true;
-    ctx->last_mfma16 = tiled != nullptr || (mfma_single && !single_k64);
-    ctx->last_filter_rows = levels ? (uint64_t)(has_tri ? A.n_tri_top : 0u) + (has_sph ? A.n_sph_top : 0u) : tiled ? (uint64_t)A.n_tri_rows + A.n_sph_rows : mfma_single ? ctx->n_sph : 0;
+    ctx->last_mfma16 = T.mfma16;
+    ctx->last_filter_rows = T.filter_rows;
     ctx->rendered = true;
     ctx->acc_valid = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = sample_begin + sample_count; ctx->acc_npix = npix;
     return 0;
@@ -1153,6 +1195,75 @@ int rt3_gather_rows(rt3_ctx* root, void* d_frame, rt3_ctx* shard, const void* d_
         else RT3_HIP(hipMemcpy2DAsync(frame + c.dst_offset, c.dst_pitch, tile + c.src_offset, c.src_pitch, c.row_bytes, c.rows, hipMemcpyDeviceToDevice, stream));
     }
     return 0;
+}
+
+// Batched ray queries: the query form of the kernel Mode X would take for the scene, one launch, one item per ray.
+static int query_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_min, void* d_out, void* stream_, bool occluded) {
+    if (!ctx) return RT3_E_ARG;
+    if (!(t_min >= 0.0f) || !(t_min < __builtin_inff())) return fail(ctx, RT3_E_ARG, "t_min must be finite and >= 0");
+    if (n > (1u << 30)) return fail(ctx, RT3_E_ARG, "at most 2^30 rays per query");
+    if (n == 0) return 0;
+    if (!d_rays || !d_out) return fail(ctx, RT3_E_ARG, "rays / results buffer is NULL");
+    if ((uintptr_t)d_rays % 16u != 0 || (uintptr_t)d_out % (occluded ? 4u : 16u) != 0)
+        return fail(ctx, RT3_E_ARG, occluded ? "rays must be 16-byte and occlusion words 4-byte aligned" : "rays and hits must be 16-byte aligned");
+    if (ctx->n_sph == 0 && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "no scene: call rt3_set_spheres / rt3_set_mesh first");
+    if (ctx->n_faces >= (1u << kPairLaneShift) - 32u || ctx->n_sph >= (1u << kPairLaneShift) - 32u) return fail(ctx, RT3_E_ARG, "too many primitives");
+    RT3_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
+    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));    // the counters, the work queue and the strips are the context's
+    ctx->rendered = false;
+    ctx->ev_used = 0;
+    TraceArgs A = scene_args(ctx);
+    A.t_min = t_min;
+    A.total = n;
+    A.q_rays = (const float4*)d_rays; A.q_out = d_out; A.q_occluded = occluded ? 1u : 0u;
+    TracePlan T;
+    int rc;
+    if ((rc = plan_trace(ctx, A, false, false, true, T))) return rc;
+    hipEvent_t a, b;
+    if ((rc = take_event_pair(ctx, &a, &b))) return rc;
+    RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
+    RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 128, stream));
+    RT3_HIP(hipMemsetAsync(ctx->d_work, 0, 4, stream));
+    RT3_HIP(hipEventRecord(a, stream));
+    launch_trace(T, A, trace_grid(ctx, T, n), stream);
+    RT3_HIP(hipGetLastError());
+    RT3_HIP(hipEventRecord(b, stream));
+    RT3_HIP(hipEventRecord(ctx->ev_end, stream));
+    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
+    ctx->last_stream = stream;
+    ctx->last_samples = 0;
+    ctx->last_was_path = true;
+    ctx->last_mfma16 = T.mfma16;
+    ctx->last_filter_rows = T.filter_rows;
+    ctx->rendered = true;
+    return 0;
+}
+static int query_host(rt3_ctx* ctx, const rt3_ray* rays, uint32_t n, float t_min, void* out, bool occluded) {
+    if (!ctx) return RT3_E_ARG;
+    if (!(t_min >= 0.0f) || !(t_min < __builtin_inff())) return fail(ctx, RT3_E_ARG, "t_min must be finite and >= 0");
+    if (n > (1u << 30)) return fail(ctx, RT3_E_ARG, "at most 2^30 rays per query");
+    if (n == 0) return 0;
+    if (!rays || !out) return fail(ctx, RT3_E_ARG, "rays / results array is NULL");
+    if (ctx->n_sph == 0 && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "no scene: call rt3_set_spheres / rt3_set_mesh first");
+    RT3_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = ensure(ctx, &ctx->d_qrays, &ctx->qrays_entries, (size_t)n * 2u)) || (rc = ensure(ctx, &ctx->d_qout, &ctx->qout_entries, (size_t)n))) return rc;
+    RT3_HIP(hipMemcpyAsync(ctx->d_qrays, rays, (size_t)n * sizeof(rt3_ray), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = query_device(ctx, ctx->d_qrays, n, t_min, ctx->d_qout, ctx->stream, occluded))) return rc;
+    RT3_HIP(hipMemcpyAsync(out, ctx->d_qout, (size_t)n * (occluded ? 4u : sizeof(rt3_hit)), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+static_assert(sizeof(rt3_ray) == 32 && sizeof(rt3_hit) == 16, "rt3.h: query wire structs");
+
+int rt3_intersect(rt3_ctx* ctx, const rt3_ray* rays, uint32_t n, float t_min, rt3_hit* hits) { return query_host(ctx, rays, n, t_min, hits, false); }
+int rt3_occluded(rt3_ctx* ctx, const rt3_ray* rays, uint32_t n, float t_min, uint32_t* out) { return query_host(ctx, rays, n, t_min, out, true); }
+int rt3_intersect_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_min, void* d_hits, void* stream) {
+    return query_device(ctx, d_rays, n, t_min, d_hits, stream, false);
+}
+int rt3_occluded_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_min, void* d_out, void* stream) {
+    return query_device(ctx, d_rays, n, t_min, d_out, stream, true);
 }
 
 int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {

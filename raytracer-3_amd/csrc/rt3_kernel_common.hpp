@@ -109,19 +109,27 @@ __device__ __forceinline__ void unit_vector(float xi0, float xi1, float& x, floa
 // Mode X
 // ------------------------------------------------------------------------------------------------------
 struct Rgb { float r, g, b; };   // one radiance record of the sample storage (three dwords: a quarter less HBM traffic than float4)
+// Batched ray queries (the QUERY forms of the trace kernels; rt3_intersect* / rt3_occluded*): item k of a launch is ray k
+// of the caller's rt3_ray[] (q_rays: two float4 per ray, origin, t_max | direction, pad); its result goes to q_out[k], an rt3_hit (16 bytes), or with
+// q_occluded one word.  They share the places of fields only the path kernels read (the VALU scan's face bounds, the sample storage, the render
+// flags), so that the layout of the struct — and with it the code of every path kernel — stays what it was.
 struct TraceArgs {
     const float4* sph;       const float* sph_invr;  const float4* sph_mat;  const uint32_t* sph_kind;  uint32_t n_sph;
-    const float4* tri;       const float4* tri_mat;  const uint32_t* tri_kind;  const float4* tri_bound; uint32_t n_tri;
+    const float4* tri;       const float4* tri_mat;  const uint32_t* tri_kind;
+    union { const float4* tri_bound; const float4* q_rays; };
+    uint32_t n_tri;
     CamDev cam;
     float lens_radius, lux, luy, luz, lvx, lvy, lvz;
-    uint32_t width, height, spp, max_depth, seed, flags, edge;
+    uint32_t width, height, spp, max_depth, seed;
+    union { uint32_t flags; uint32_t q_occluded; };
+    uint32_t edge;
     FastDiv div_npix, div_width, div_edge, div_tile_rows;
     float t_min;
     uint32_t tile_rows, tile_index, tile_count;
     uint32_t npix;           // pixels owned by this shard
     uint32_t s0;             // first sample of this batch
     uint32_t total;          // npix * samples in this batch
-    Rgb* rad;                // per-sample radiance, [sample in batch][owned pixel], 12 B each
+    union { Rgb* rad; void* q_out; };   // per-sample radiance, [sample in batch][owned pixel], 12 B each | QUERY: the results
     // Centres the matrix filter's coordinates are taken about: the filter's margin is eps (|C|^2 + r^2 + |o|^2), so a scene far from the
     // world origin would otherwise drown in candidates.  Spheres: the median of their centres; faces: the centre of the vertices' box.
     float fcx, fcy, fcz;     // spheres (k_trace_mfma, the K = 32 pass of k_trace_mfma_tiled)
@@ -150,6 +158,7 @@ struct Path {
     float ox, oy, oz, dx, dy, dz;
     float tr, tg, tb, lr, lg, lb;
     uint32_t slot, base, depth;
+    float tmax;              // QUERY forms: the ray's t_max (the path kernels never touch it)
 };
 
 // The reference's plane + three-edge test of one face (SequentialRenderer.cpp:53-98; hit_vertex, raytracer_v4.glsl:116-153), in

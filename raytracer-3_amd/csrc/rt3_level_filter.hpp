@@ -36,7 +36,8 @@ __host__ __device__ constexpr uint32_t lev_resident_blocks(uint32_t levels) { re
 static_assert(lev_lds_fixed(3, true) + lev_resident_blocks(3) * 2048u < 160u * 1024u && lev_lds_fixed(4, true) + lev_resident_blocks(4) * 2048u < 160u * 1024u &&
               lev_lds_fixed(3, false) < 160u * 1024u && lev_lds_fixed(4, false) < 160u * 1024u, "k_trace_levels: LDS");
 
-template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t LEVELS, bool RES>
+// QUERY: the batched ray queries' form (REF false; the nearest-hit key goes to query_sink instead of shading).
+template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t LEVELS, bool RES, bool QUERY = false>
 __global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
     static_assert(LEVELS == 3 || LEVELS == 4, "three or four levels");
     static_assert(kGroupTri == kLevFan && kGroupSph == kLevFan && kSuper == kLevFan, "k_trace_levels: 8 children per node");
@@ -63,14 +64,15 @@ __global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u
 
     Path P;
     P.ox = P.oy = P.oz = 0.0f; P.dx = P.dy = 0.0f; P.dz = 1.0f;
-    P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0;
+    P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0; P.tmax = __builtin_inff();
     bool alive = false;
     uint32_t chunk_next = 0, chunk_end = 0;
     bool exhausted = false;
     unsigned long long casts = 0, mfmas = 0, exact = 0, bound_tests = 0;
 
     for (;;) {
-        refill_lanes<REF>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else refill_lanes<REF>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         const unsigned long long live = __ballot(alive);
         if constexpr (RES) { if (live == 0ull) break; }
         else if (!__syncthreads_or(live != 0ull ? 1 : 0)) break;
@@ -78,7 +80,10 @@ __global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u
         const LaneRay ray = { P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, REF && P.depth == 0 };
         float ux = ray.dx, uy = ray.dy, uz = ray.dz;                            // what the filter and the bounds see: a unit direction
         if (REF && ray.literal) { const float inv = 1.0f / __builtin_sqrtf(dot3(ux, uy, uz, ux, uy, uz)); ux = ux * inv; uy = uy * inv; uz = uz * inv; }
-        keys[lane] = HAS_SPH ? direct_tests(A, ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, [&](uint32_t j) { return A.sph[j]; }) : kKeyNone;
+        {
+            const unsigned long long k0 = HAS_SPH ? direct_tests(A, ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, [&](uint32_t j) { return A.sph[j]; }) : kKeyNone;
+            keys[lane] = QUERY && query_start_key(P) < k0 ? query_start_key(P) : k0;
+        }
         uint32_t n_pairs = 0, n_s = 0, n_l = 0, n_f = 0, n_strip = 0, spos = 0;
 
         // A batch of (ray lane, parent) pairs, two lanes per pair, each lane four of the parent's eight children (its own 64 contiguous bytes of
@@ -302,8 +307,11 @@ __global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u
         __builtin_amdgcn_wave_barrier();
         uint32_t kind, ibest;
         float tbest;
-        key_decode(keys[lane], kind, ibest, tbest);
-        shade_lane<HAS_TRI, HAS_SPH, REF>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
+        if constexpr (QUERY) query_sink(A, P, alive, keys[lane]);
+        else {
+            key_decode(keys[lane], kind, ibest, tbest);
+            shade_lane<HAS_TRI, HAS_SPH, REF>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
+        }
     }
     if (lane == 0 && casts != 0) { atomicAdd(A.cast_counter, casts); atomicAdd(A.cast_counter + 1, mfmas); atomicAdd(A.cast_counter + 2, exact); atomicAdd(A.cast_counter + 3, bound_tests); }
 }

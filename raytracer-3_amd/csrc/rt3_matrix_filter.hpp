@@ -585,6 +585,18 @@ __device__ __forceinline__ void key_decode(unsigned long long key, uint32_t& kin
     idx = (lo & 0x7FFFFFFFu) >> 1;
     t = __uint_as_float(hi | (lo << 31));
 }
+// Batched ray queries: a ray's record starts from hit_key(t_max, face, 0) — below every key of a hit at t >= t_max, above every key of a hit at
+// t < t_max — so the BEYOND prunes and the exact tests' t <= t_best cut at t_max unchanged, and a record that still holds its start key missed.
+__device__ __forceinline__ unsigned long long query_start_key(const Path& P) { return hit_key(P.tmax, 0u, 0u); }
+__device__ __forceinline__ void query_sink(const TraceArgs& A, const Path& P, bool& alive, unsigned long long key) {
+    if (!alive) return;
+    uint32_t kind, idx;
+    float t;
+    key_decode(key, kind, idx, t);
+    if (key == query_start_key(P)) query_store(A, P.slot, RT3_HIT_NONE, 0xFFFFFFFFu, __builtin_inff());
+    else query_store(A, P.slot, kind, idx, t);
+    alive = false;
+}
 // The direct spheres (TraceArgs::direct): every lane tests its own ray; returns the key the ray's record starts from.
 template <class SphereAt>
 __device__ __forceinline__ unsigned long long direct_tests(const TraceArgs& A, float ox, float oy, float oz, float dx, float dy, float dz, SphereAt&& sphere_at) {
@@ -840,6 +852,8 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma(const TraceArgs A, const u32
 // The vector-ALU instruction count per ray cast is that of k_trace_mfma (the K = 32 margin brings more candidates, the pair list tests them
 // at full lane utilisation, the ray operands cost half), but the matrix pipe does half the work and the chip, which throttles under
 // k_trace_mfma's load (2.0-2.2 GHz), holds 2.3-2.4 GHz here — and a kernel bound by vector-ALU issue runs at the clock.
+// QUERY: the batched ray queries' form (refill from the caller's rays, no ray stock; the nearest-hit key goes to query_sink instead of shading).
+template <bool QUERY = false>
 __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u32x4* __restrict__ frags, uint32_t n_blocks) {
     extern __shared__ u32x4 lds_dyn[];
     u32x4* s_frag = lds_dyn;                                                   // [n_blocks][2][64]
@@ -865,7 +879,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
 
     Path P;
     P.ox = P.oy = P.oz = 0.0f; P.dx = P.dy = 0.0f; P.dz = 1.0f;
-    P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0;
+    P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0; P.tmax = __builtin_inff();
     bool alive = false;
     uint32_t chunk_next = 0, chunk_end = 0;
     bool exhausted = false;
@@ -880,7 +894,8 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
 #endif
 
     for (;;) {
-        refill_from_stock(A, lane, alive, P, Q, chunk_next, chunk_end, exhausted);
+        if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else refill_from_stock(A, lane, alive, P, Q, chunk_next, chunk_end, exhausted);
         RT3_SPHASE(ph_refill)
         const unsigned long long live = __ballot(alive);
         if (live == 0ull) break;
@@ -889,7 +904,10 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
         const LaneRay ray = { P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, false };
         RayOperands32 R;
         build_ray_operands32(ray.ox - A.fcx, ray.oy - A.fcy, ray.oz - A.fcz, ray.dx, ray.dy, ray.dz, alive, R);
-        keys[lane] = direct_tests(A, ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, [&](uint32_t j) { return s_sph[j]; });
+        {
+            const unsigned long long k0 = direct_tests(A, ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, [&](uint32_t j) { return s_sph[j]; });
+            keys[lane] = QUERY && query_start_key(P) < k0 ? query_start_key(P) : k0;
+        }
         uint32_t n_pairs = 0;
         auto test = [&](uint32_t pair, bool valid) {
             const uint32_t src = pair >> kPairLaneShift, j = pair & ((1u << kPairLaneShift) - 1u);
@@ -908,8 +926,11 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
         __builtin_amdgcn_wave_barrier();
         uint32_t kind, ibest;
         float tbest;
-        key_decode(keys[lane], kind, ibest, tbest);
-        shade_lane<false, true>(A, P, alive, kind, ibest, tbest, s_sph, s_invr, s_mat, s_kind);
+        if constexpr (QUERY) query_sink(A, P, alive, keys[lane]);
+        else {
+            key_decode(keys[lane], kind, ibest, tbest);
+            shade_lane<false, true>(A, P, alive, kind, ibest, tbest, s_sph, s_invr, s_mat, s_kind);
+        }
         RT3_SPHASE(ph_shade)
     }
 #ifdef RT3_PROFILE_PHASES
@@ -975,7 +996,8 @@ constexpr uint32_t kBmBlocksRes = 4;
 constexpr uint32_t kResidentBlocks = (160u * 1024u - kTB * 8u - (kTB / 64u) * kPairCap * 4u * 3u - kBmBlocksRes * kTB * 4u) / 2048u - 1u;   // row blocks of 2 KiB: 55
 // (one block of headroom: a kernel with any static LDS beside the dynamic request — __syncthreads_or's word, say — is refused at exactly 160 KiB;
 // this variant has none and did launch with 56, profiles/README.md)
-template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t GT = 1, uint32_t GS = 1, uint32_t SUP = 1, bool RES = false>
+// QUERY: the batched ray queries' form (REF false; the nearest-hit key goes to query_sink instead of shading).
+template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t GT = 1, uint32_t GS = 1, uint32_t SUP = 1, bool RES = false, bool QUERY = false>
 __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
     static_assert(64 % GT == 0 && 64 % GS == 0, "group sizes must divide the wave");
     static_assert(!RES || (SUP > 1 && RT3_FACE_K32), "resident rows: three-level filter only");
@@ -1000,7 +1022,7 @@ __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, con
 
     Path P;
     P.ox = P.oy = P.oz = 0.0f; P.dx = P.dy = 0.0f; P.dz = 1.0f;
-    P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0;
+    P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0; P.tmax = __builtin_inff();
     bool alive = false;
     uint32_t chunk_next = 0, chunk_end = 0;
     bool exhausted = false;
@@ -1014,7 +1036,8 @@ __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, con
 
     for (;;) {
         // (no ray stock here: a ray cast costs at least one tile scan, start_path is noise beside it, and the stock's 8 registers are needed)
-        refill_lanes<REF>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else refill_lanes<REF>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         const unsigned long long live = __ballot(alive);
         if constexpr (RES) { if (live == 0ull) break; }                           // every wave for itself
         else if (!__syncthreads_or(live != 0ull ? 1 : 0)) break;                 // tiles: the workgroup ends together
@@ -1030,7 +1053,10 @@ __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, con
         if (HAS_TRI) build_ray_operands16(ray.ox - A.tcx, ray.oy - A.tcy, ray.oz - A.tcz, ux, uy, uz, alive, R);
 #endif
         if (HAS_SPH && !HAS_TRI) build_ray_operands32(ray.ox - A.fcx, ray.oy - A.fcy, ray.oz - A.fcz, ux, uy, uz, alive, R32);
-        keys[lane] = HAS_SPH ? direct_tests(A, ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, [&](uint32_t j) { return A.sph[j]; }) : kKeyNone;
+        {
+            const unsigned long long k0 = HAS_SPH ? direct_tests(A, ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, [&](uint32_t j) { return A.sph[j]; }) : kKeyNone;
+            keys[lane] = QUERY && query_start_key(P) < k0 ? query_start_key(P) : k0;
+        }
         uint32_t n_pairs = 0, n_fpairs = 0, n_lpairs = 0, n_strip = 0;
         // SUP > 1: the middle level.  A batch of (ray lane, row) pairs, LPP lanes per pair, each lane SUP / LPP leaf bounds (its own contiguous bytes);
         // survivors are appended to lpairs and handed, 64 / LPP at a time, to `leaf_fn` (the members' tests of the two-level filter).
@@ -1314,8 +1340,11 @@ __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, con
         __builtin_amdgcn_wave_barrier();
         uint32_t kind, ibest;
         float tbest;
-        key_decode(keys[lane], kind, ibest, tbest);
-        shade_lane<HAS_TRI, HAS_SPH, REF>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
+        if constexpr (QUERY) query_sink(A, P, alive, keys[lane]);
+        else {
+            key_decode(keys[lane], kind, ibest, tbest);
+            shade_lane<HAS_TRI, HAS_SPH, REF>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
+        }
     }
     if (lane == 0 && casts != 0) { atomicAdd(A.cast_counter, casts); atomicAdd(A.cast_counter + 1, mfmas); atomicAdd(A.cast_counter + 2, exact); atomicAdd(A.cast_counter + 3, bound_tests); }
 #ifdef RT3_PROFILE

@@ -4,11 +4,34 @@
 
 namespace {
 
+// Batched ray queries: the QUERY form of a trace kernel takes its rays from the caller's buffer instead of the camera
+// and stores the nearest hit (or the occlusion word) instead of shading.  One result per ray, written with one vector store.
+__device__ __forceinline__ void query_store(const TraceArgs& A, uint32_t slot, uint32_t kind, uint32_t idx, float t) {
+    if (A.q_occluded) reinterpret_cast<uint32_t*>(A.q_out)[slot] = kind == RT3_HIT_INVALID ? 0xFFFFFFFFu : (kind != RT3_HIT_NONE ? 1u : 0u);
+    else reinterpret_cast<uint4*>(A.q_out)[slot] = make_uint4(__float_as_uint(t), kind, idx, 0u);
+}
+// Ray `item` of the caller's buffer (two 16-byte loads).  An invalid ray — non-finite origin or direction, |d.d - 1| > 2^-20 (the sphere test's
+// a = 1 and the filter's bound of DESIGN.md 5.2c need a unit direction), t_max NaN or <= t_min — gets RT3_HIT_INVALID here and is never traced.
+__device__ __forceinline__ bool query_ray(const TraceArgs& A, uint32_t item, Path& P) {
+    const float4* r = A.q_rays + 2 * (size_t)item;
+    const float4 a = r[0], b = r[1];
+    P.ox = a.x; P.oy = a.y; P.oz = a.z; P.tmax = a.w;
+    P.dx = b.x; P.dy = b.y; P.dz = b.z;
+    P.slot = item; P.depth = 0;
+    const float dd = dotf(b.x, b.y, b.z, b.x, b.y, b.z);
+    const bool finite = __builtin_isfinite(a.x) & __builtin_isfinite(a.y) & __builtin_isfinite(a.z) &
+                        __builtin_isfinite(b.x) & __builtin_isfinite(b.y) & __builtin_isfinite(b.z);
+    const bool ok = finite && __builtin_fabsf(dd - 1.0f) <= 0x1p-20f && a.w > A.t_min;      // (a NaN t_max fails the last test)
+    if (!ok) query_store(A, item, RT3_HIT_INVALID, 0xFFFFFFFFu, __builtin_nanf(""));
+    return ok;
+}
+
 // HAS_TRI / HAS_SPH compile the face loop / sphere loop (and the matching shading) in or out, so that a sphere-only
 // scene does not pay registers or code for the triangle path.
 // Refill: lanes whose path ended take the next samples of the wave's chunk (ballot + prefix count); a chunk of
 // kWorkChunk samples is fetched from the global queue with one atomic when the wave runs dry.
-template <bool REF = false>
+// QUERY: the items are the caller's rays (query_ray); an invalid one leaves its lane empty (refill_queries fills it again).
+template <bool REF = false, bool QUERY = false>
 __device__ __forceinline__ void refill_lanes(const TraceArgs& A, uint32_t lane, bool& alive, Path& P, uint32_t& chunk_next,
                                              uint32_t& chunk_end, bool& exhausted) {
     const unsigned long long need = __ballot(!alive);
@@ -30,8 +53,18 @@ __device__ __forceinline__ void refill_lanes(const TraceArgs& A, uint32_t lane, 
             chunk_next += k;
             taken += k;
         }
-        if (item != 0xFFFFFFFFu) { start_path<REF>(A, item, P); alive = true; }
+        if (item != 0xFFFFFFFFu) {
+            if constexpr (QUERY) alive = query_ray(A, item, P);
+            else { start_path<REF>(A, item, P); alive = true; }
+        }
     }
+}
+// The query forms' refill: until every lane holds a valid ray or the queue is dry, so that invalid rays neither end a wave early (a wave leaves
+// when no lane is alive after a refill) nor leave holes in it.
+__device__ __forceinline__ void refill_queries(const TraceArgs& A, uint32_t lane, bool& alive, Path& P, uint32_t& chunk_next, uint32_t& chunk_end,
+                                               bool& exhausted) {
+    do refill_lanes<false, true>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+    while (__ballot(!alive) != 0ull && !exhausted);
 }
 
 // Refill through a wave-wide stock of primary rays: start_path() runs for all 64 lanes at once (lane k of the stock holds sample

@@ -258,12 +258,13 @@ __global__ __launch_bounds__(kBlock) void k_trace(const TraceArgs A) {
 // tools/fuzz_filter.py; rt3_debug_force_brute / RT3_BRUTE=1) and the only kernel that can serve RT3_FLAG_REFERENCE_PRIMARY with a
 // camera off the origin (the reference's literal formula then puts the "hit point" off the face's plane, where no bound holds).
 // Scene records are wave-uniform loads through the constant address space (scalar cache); one path per lane, refill by ballot.
-template <bool REF>
+// QUERY: the batched ray queries' arbiter (rt3_intersect* / rt3_occluded* under the same switch): the running best starts at the ray's t_max.
+template <bool REF, bool QUERY = false>
 __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
     const uint32_t lane = lane_id();
     Path P;
     P.ox = P.oy = P.oz = 0.0f; P.dx = P.dy = 0.0f; P.dz = 1.0f;
-    P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0;
+    P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0; P.tmax = __builtin_inff();
     bool alive = false;
     uint32_t chunk_next = 0, chunk_end = 0;
     bool exhausted = false;
@@ -272,10 +273,11 @@ __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
     auto f4 = [](const f32x4 v) { return make_float4(v.x, v.y, v.z, v.w); };
 
     for (;;) {
-        refill_lanes<REF>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else refill_lanes<REF>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         if (__ballot(alive) == 0ull) break;
         casts += (unsigned long long)__popcll(__ballot(alive));
-        float tbest = __builtin_inff();
+        float tbest = QUERY ? P.tmax : __builtin_inff();
         uint32_t ibest = 0, kind = 0;
         const float ox = P.ox, oy = P.oy, oz = P.oz, dx = P.dx, dy = P.dy, dz = P.dz;
         const bool ref0 = REF && P.depth == 0;
@@ -292,7 +294,10 @@ __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
             float t;
             if (alive && sphere_root(s, ox, oy, oz, dx, dy, dz, A.t_min, t) && t < tbest) { tbest = t; ibest = j; kind = 2; }
         }
-        shade_lane<true, true, REF>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);   // kind says which arrays to read
+        if constexpr (QUERY) {
+            if (alive) query_store(A, P.slot, kind, kind != 0u ? ibest : 0xFFFFFFFFu, kind != 0u ? tbest : __builtin_inff());
+            alive = false;
+        } else shade_lane<true, true, REF>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);   // kind says which arrays to read
     }
     if (lane == 0 && casts != 0) atomicAdd(A.cast_counter, casts);
 }

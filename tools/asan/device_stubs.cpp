@@ -38,6 +38,10 @@ int rt3_debug_force_plain_mode_r(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_force_brute(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_force_flat_filter(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_arith(rt3_ctx*, const float*, const float*, uint32_t, float*, float*, float*, float*, float*, float*, uint32_t*) { return RT3_E_DEVICE; }
+int rt3_intersect(rt3_ctx*, const rt3_ray*, uint32_t, float, rt3_hit*) { return RT3_E_DEVICE; }
+int rt3_occluded(rt3_ctx*, const rt3_ray*, uint32_t, float, uint32_t*) { return RT3_E_DEVICE; }
+int rt3_intersect_device(rt3_ctx*, const void*, uint32_t, float, void*, void*) { return RT3_E_DEVICE; }
+int rt3_occluded_device(rt3_ctx*, const void*, uint32_t, float, void*, void*) { return RT3_E_DEVICE; }
 // (rt3_rows_owned / rt3_row_of_local are pure host arithmetic that happens to live in rt3_device.hip)
 uint32_t rt3_rows_owned(const rt3_params* p) {
     uint32_t n = 0;
