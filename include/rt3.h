@@ -292,6 +292,42 @@ int rt3_intersect_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_m
 int rt3_occluded_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_min, void* d_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Camera rays, first-hit AOVs and the linear frame   (what a denoiser or compositor reads)
+ * ------------------------------------------------------------------------------------------------- */
+/* One pixel's first-hit AOVs: 48 bytes, three 16-byte halves.  Averages over the pixel's spp primary rays (summed in sample order, then
+ * divided by spp), except depth (over the samples that hit) and kind / index (sample 0's hit). */
+typedef struct rt3_aov {
+    float    albedo[3];          /* FLAT / LAMBERT / METAL: the material's rgb; DIELECTRIC: (1, 1, 1); miss: sky(d), or 0 under
+                                    RT3_FLAG_BLACK_BACKGROUND (the render's miss radiance); invalid ray: 0 */
+    float    coverage;           /* samples that hit / spp */
+    float    normal[3];          /* the shading normal of the hit, flipped to face the ray (d.n < 0); 0 on a miss */
+    float    depth;              /* mean t of the samples that hit (distance from the lens point); +inf when none did */
+    uint32_t kind, index;        /* sample 0's hit, as in rt3_hit (RT3_HIT_INVALID if its ray was invalid) */
+    uint32_t _pad[2];            /* 0 */
+} rt3_aov;
+/* Mode X's primary rays as rt3_ray records: for samples [sample_begin, sample_begin + sample_count) of params->spp, record
+ * (s - sample_begin) * npix + pix, npix = rt3_rows_owned(params) * width (the render's item order, compact tile rows).  Bit for bit the ray
+ * that ray cast 0 of rt3_render_path* traces (jitter, strata, thin lens), unit direction, t_max = +inf, _pad = 0.  No scene needed.
+ * RT3_FLAG_REFERENCE_PRIMARY is refused (RT3_E_ARG): its directions are not unit vectors.  Owned pixels x samples <= 2^31 - 2^16. */
+int rt3_camera_rays(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* params, uint32_t sample_begin, uint32_t sample_count,
+                    rt3_ray* out_rays);
+int rt3_camera_rays_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* params, uint32_t sample_begin, uint32_t sample_count,
+                           void* d_out_rays, void* stream);
+/* First-hit AOVs of every owned pixel (compact tile rows, as rt3_render_path writes them): the camera rays above, each traced with
+ * rt3_intersect's rule (t_min from params, t_max = +inf), reduced per pixel as rt3_aov describes.  AOVs are linear: RT3_FLAG_GAMMA2 does
+ * not apply; max_depth is not used; RT3_FLAG_REFERENCE_PRIMARY is refused (RT3_E_ARG).  The call never touches the accumulation of a
+ * progressive render.  Streams as for queries.  rt3_get_stats afterwards: ray_casts = valid primary rays, samples = pixels x spp,
+ * launches / trace_ms / filter counters summed over the sample batches (sized by rt3_set_sample_storage_cap at 48 bytes per pixel and
+ * sample).  RT3_E_STATE without a scene; device pointers 16-byte aligned. */
+int rt3_render_aov(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* params, rt3_aov* out_aov);
+int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* params, void* d_out_aov, void* stream);
+/* The accumulation as a linear float frame: (sum.r / n, sum.g / n, sum.b / n, 0) per owned pixel, n = samples accumulated — the division
+ * the RGBA8 resolve does, before any gamma (packing it gives the frame of a render without RT3_FLAG_GAMMA2).  Compact tile rows of the
+ * last rt3_render_path* / rt3_accum_upload; RT3_E_STATE without an accumulation; d_out_rgba 16-byte aligned. */
+int rt3_accum_resolve(rt3_ctx* ctx, float* out_rgba);
+int rt3_accum_resolve_device(rt3_ctx* ctx, void* d_out_rgba, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side scene API   (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)
  * ------------------------------------------------------------------------------------------------- */
 /* cpu_pre_render_triangle (src/lib/entities/Triangle.cpp:28-76): 1 face, 3 vertices (xyzw). */
@@ -323,6 +359,13 @@ void     rt3_camera_look_at(rt3_camera* cam, const float from[3], const float at
  * `out` (capacity cap) or the required size when out == NULL. */
 uint64_t rt3_frame_ppm_bytes(const uint32_t* pixels, uint32_t width, uint32_t height, uint8_t* out, uint64_t cap);
 int      rt3_frame_to_ppm(const uint32_t* pixels, uint32_t width, uint32_t height, const char* path);
+/* Portable float map of a float image: "PF" (channels 3) or "Pf" (channels 1) header, scale -1.0 (little-endian), rows bottom to top.
+ * Pixel (x, y), row 0 on top, is data[(y * width + x) * stride_floats + c]; stride_floats >= channels (an rt3_aov frame is read with
+ * stride 12: albedo at offset 0, normal at 4, depth at 7).  Returns the bytes written to `out` (capacity cap), the required size when
+ * out == NULL, 0 for bad arguments or a short buffer.  rt3_frame_to_pfm: RT3_E_ARG / RT3_E_IO. */
+uint64_t rt3_frame_pfm_bytes(const float* data, uint32_t width, uint32_t height, uint32_t channels, uint32_t stride_floats,
+                             uint8_t* out, uint64_t cap);
+int      rt3_frame_to_pfm(const float* data, uint32_t width, uint32_t height, uint32_t channels, uint32_t stride_floats, const char* path);
 
 /* Benchmark scenes (build-owned).  Each returns the sphere count of the scene — the count REQUIRED, whatever
  * cap is (snprintf convention) — and writes at most cap spheres; NULL outputs write nothing.  All randomness comes from the reference's hash RNG

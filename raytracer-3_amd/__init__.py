@@ -41,6 +41,9 @@ MAT_FLAT, MAT_LAMBERT, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2, 3
 RAY = np.dtype([("origin", "<f4", 3), ("t_max", "<f4"), ("direction", "<f4", 3), ("_pad", "<u4")])
 HIT = np.dtype([("t", "<f4"), ("kind", "<u4"), ("index", "<u4"), ("_pad", "<u4")])
 HIT_NONE, HIT_FACE, HIT_SPHERE, HIT_INVALID = 0, 1, 2, 3
+# first-hit AOVs (rt3_render_aov): rt3_aov (48 bytes)
+AOV = np.dtype([("albedo", "<f4", 3), ("coverage", "<f4"), ("normal", "<f4", 3), ("depth", "<f4"), ("kind", "<u4"), ("index", "<u4"),
+                ("_pad", "<u4", 2)])
 OCCLUDED_INVALID = 0xFFFFFFFF      # rt3_occluded's word for an invalid ray
 FLAG_GAMMA2, FLAG_BLACK_BACKGROUND, FLAG_REFERENCE_PRIMARY, FLAG_VARIANCE = 1, 2, 4, 8
 
@@ -120,6 +123,8 @@ EXPORTS = [
     "rt3_stream", "rt3_synchronize", "rt3_device_alloc_words", "rt3_device_free", "rt3_device_read_words", "rt3_debug_force_brute",
     "rt3_abi_version", "rt3_debug_force_flat_filter", "rt3_gather_plan",
     "rt3_intersect", "rt3_occluded", "rt3_intersect_device", "rt3_occluded_device",
+    "rt3_camera_rays", "rt3_camera_rays_device", "rt3_render_aov", "rt3_render_aov_device", "rt3_accum_resolve", "rt3_accum_resolve_device",
+    "rt3_frame_pfm_bytes", "rt3_frame_to_pfm",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -175,6 +180,10 @@ def lib():
         "rt3_abi_version": (u32, []), "rt3_debug_force_flat_filter": (i32, [vp, i32]), "rt3_gather_plan": (i32, [vp, vp]),
         "rt3_intersect": (i32, [vp, vp, u32, f32, vp]), "rt3_occluded": (i32, [vp, vp, u32, f32, vp]),
         "rt3_intersect_device": (i32, [vp, vp, u32, f32, vp, vp]), "rt3_occluded_device": (i32, [vp, vp, u32, f32, vp, vp]),
+        "rt3_camera_rays": (i32, [vp, vp, vp, u32, u32, vp]), "rt3_camera_rays_device": (i32, [vp, vp, vp, u32, u32, vp, vp]),
+        "rt3_render_aov": (i32, [vp, vp, vp, vp]), "rt3_render_aov_device": (i32, [vp, vp, vp, vp, vp]),
+        "rt3_accum_resolve": (i32, [vp, vp]), "rt3_accum_resolve_device": (i32, [vp, vp, vp]),
+        "rt3_frame_pfm_bytes": (u64, [vp, u32, u32, u32, u32, vp, u64]), "rt3_frame_to_pfm": (i32, [vp, u32, u32, u32, u32, C.c_char_p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -229,6 +238,28 @@ class Frame:
         """(h, w, 3) uint8 view of the frame as PPM/PNG would show it."""
         d = self.data
         return np.stack([(d >> 24) & 0xFF, (d >> 16) & 0xFF, (d >> 8) & 0xFF], axis=-1).astype(np.uint8)
+
+
+def pfm_bytes(image):
+    """rt3_frame_pfm_bytes of a float32 image, row 0 on top: (h, w) -> "Pf", (h, w, 3) -> "PF".  The image may be a strided view of a wider
+    record (e.g. ``aov["albedo"]`` of an AOV frame) as long as its pixels are evenly spaced and its rows contiguous."""
+    a = np.asarray(image)
+    if a.dtype != np.float32 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+        raise ValueError("pfm_bytes: a float32 (h, w) or (h, w, 3) image")
+    h, w = a.shape[:2]
+    ch = 1 if a.ndim == 2 else 3
+    if a.ndim == 3 and a.strides[2] != 4:
+        a = np.ascontiguousarray(a)
+    stride = a.strides[1] // 4
+    if a.strides[1] % 4 or stride < ch or a.strides[0] != w * a.strides[1]:
+        a = np.ascontiguousarray(a)
+        stride = ch
+    need = lib().rt3_frame_pfm_bytes(a.ctypes.data_as(C.c_void_p), w, h, ch, stride, None, 0)
+    buf = np.zeros(need, np.uint8)
+    got = lib().rt3_frame_pfm_bytes(a.ctypes.data_as(C.c_void_p), w, h, ch, stride, _p(buf), need)
+    if need == 0 or got != need:
+        raise ValueError("pfm_bytes: bad image")
+    return buf.tobytes()
 
 
 class Camera:
@@ -676,6 +707,43 @@ class HipRenderer(Renderer):
         """1 where a ray hits something before its t_max, 0 where not, 0xFFFFFFFF for an invalid ray (rt3_occluded): numpy uint32 for host
         rays, an (N,) int32 tensor for device rays."""
         return self._query(rays, t_min, True)
+
+    # -- camera rays, first-hit AOVs, the linear frame (DESIGN.md 4.10) -----------------------------------------------
+    def camera_rays(self, camera_c, params, sample_begin=0, sample_count=None):
+        """Mode X's primary rays for samples [begin, begin + count) (default: all spp) as a RAY array, sample-major: record
+        (s - begin) * npix + pix over the owned pixels (compact tile rows).  Feed them to intersect() to shade or pick."""
+        if sample_count is None:
+            sample_count = params.spp - sample_begin
+        n = lib().rt3_rows_owned(C.byref(params)) * params.width * max(int(sample_count), 0)
+        out = np.zeros(n, RAY)
+        self._check(lib().rt3_camera_rays(self._ctx, C.byref(camera_c), C.byref(params), sample_begin, sample_count, _p(out)))
+        return out
+
+    def camera_rays_device(self, camera_c, params, sample_begin, sample_count, d_out_ptr, stream_ptr=None):
+        self._check(lib().rt3_camera_rays_device(self._ctx, C.byref(camera_c), C.byref(params), sample_begin, sample_count,
+                                                 C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def render_aov(self, camera_c, params):
+        """First-hit AOVs (rt3_render_aov): an AOV array of shape (rows_owned, width)."""
+        rows = lib().rt3_rows_owned(C.byref(params))
+        out = np.zeros((rows, params.width), AOV)
+        self._check(lib().rt3_render_aov(self._ctx, C.byref(camera_c), C.byref(params), _p(out)))
+        return out
+
+    def render_aov_device(self, camera_c, params, d_out_ptr, stream_ptr=None):
+        """Asynchronous AOVs into a device buffer of rows_owned * width * 48 bytes (e.g. a torch tensor's data_ptr())."""
+        self._check(lib().rt3_render_aov_device(self._ctx, C.byref(camera_c), C.byref(params), C.c_void_p(d_out_ptr),
+                                                C.c_void_p(stream_ptr or 0)))
+
+    def accum_resolve(self, params):
+        """The accumulation as a linear float frame (rt3_accum_resolve): float32 (rows_owned, width, 4), (r, g, b, 0)."""
+        rows = lib().rt3_rows_owned(C.byref(params))
+        out = np.zeros((rows, params.width, 4), np.float32)
+        self._check(lib().rt3_accum_resolve(self._ctx, _p(out)))
+        return out
+
+    def accum_resolve_device(self, d_out_ptr, stream_ptr=None):
+        self._check(lib().rt3_accum_resolve_device(self._ctx, C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
 
     def set_sample_storage_cap(self, nbytes):
         self._check(lib().rt3_set_sample_storage_cap(self._ctx, nbytes))

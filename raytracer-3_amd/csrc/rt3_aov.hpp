@@ -1,0 +1,99 @@
+// rt3_aov.hpp — first-hit AOVs (rt3_render_aov*), Mode X's camera rays as rt3_ray records (rt3_camera_rays*) and the
+// linear float resolve of the accumulation (rt3_accum_resolve*).  None of these kernels traces: the AOV pass runs k_camera_rays, then the
+// query form of the trace kernel Mode X would take (plan_trace(..., query = true)) on that buffer, then k_aov_accumulate.
+// Part of rt3_device.hip (one translation unit, gfx950 only); included from there, in this order.
+#pragma once
+
+namespace {
+
+// Item k of the batch (sample s0 + k / npix, owned pixel k % npix) -> its primary ray, bit for bit the ray Mode X casts first
+// (start_path<false>): rays[2 k] = (origin, +inf), rays[2 k + 1] = (unit direction, 0).  Two 16-byte stores per ray.
+__global__ __launch_bounds__(kBlock) void k_camera_rays(const TraceArgs A, float4* __restrict__ rays) {
+    const uint32_t item = blockIdx.x * kBlock + threadIdx.x;
+    if (item >= A.total) return;
+    Path P;
+    start_path<false>(A, item, P);
+    float4* r = rays + 2 * (size_t)item;
+    r[0] = make_float4(P.ox, P.oy, P.oz, __builtin_inff());
+    r[1] = make_float4(P.dx, P.dy, P.dz, 0.0f);
+}
+
+// Running sums of one pixel's AOVs, three planes of npix float4 each:
+//   acc[pix]            albedo sum (rgb), sum of t over the samples that hit
+//   acc[npix + pix]     normal sum (xyz), 0
+//   acc[2 npix + pix]   as uint4: kind and index of sample 0's hit, samples that hit, 0
+// One thread per pixel; the samples of the batch are added in sample order, as k_accumulate adds radiance.  `first`: the batch
+// starts at sample 0 (the sums start from zero and sample 0's hit is recorded).  Material and sphere records are read in the caller's primitive
+// order — the order of a hit's index — through the fields scene_args() fills in; hit point and normal are computed as shade_lane() does.
+__global__ __launch_bounds__(kBlock) void k_aov_accumulate(const TraceArgs A, const float4* __restrict__ rays, const uint4* __restrict__ hits,
+                                                          float4* __restrict__ acc, uint32_t npix, uint32_t ns, int first) {
+    const uint32_t pix = blockIdx.x * kBlock + threadIdx.x;
+    if (pix >= npix) return;
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 a = first ? zero : acc[pix];
+    float4 n = first ? zero : acc[(size_t)npix + pix];
+    uint4* const acc_u = reinterpret_cast<uint4*>(acc) + 2 * (size_t)npix + pix;
+    uint4 k = first ? make_uint4(0u, 0u, 0u, 0u) : *acc_u;
+    for (uint32_t s = 0; s < ns; s++) {
+        const size_t item = (size_t)s * npix + pix;
+        const uint4 h = hits[item];
+        const float4 ro = rays[2 * item], rd = rays[2 * item + 1];
+        const uint32_t kind = h.y, idx = h.z;
+        const float t = __uint_as_float(h.x);
+        float ar = 0.0f, ag = 0.0f, ab = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+        if (kind == RT3_HIT_NONE) {
+            if (!(A.flags & RT3_FLAG_BLACK_BACKGROUND)) sky(rd.x, rd.y, rd.z, ar, ag, ab);
+        } else if (kind == RT3_HIT_FACE || kind == RT3_HIT_SPHERE) {
+            float4 m; uint32_t mk;
+            if (kind == RT3_HIT_FACE) {
+                m = A.tri_mat[idx]; mk = A.tri_kind[idx];
+                const float4 fn = A.tri[(size_t)idx * 4];
+                nx = fn.x; ny = fn.y; nz = fn.z;
+            } else {
+                m = A.sph_mat[idx]; mk = A.sph_kind[idx];
+                const float4 c = A.sph[idx];
+                const float invr = A.sph_invr[idx];
+                const float px = fma_(t, rd.x, ro.x), py = fma_(t, rd.y, ro.y), pz = fma_(t, rd.z, ro.z);
+                nx = (px - c.x) * invr; ny = (py - c.y) * invr; nz = (pz - c.z) * invr;
+            }
+            if (!(dotf(rd.x, rd.y, rd.z, nx, ny, nz) < 0.0f)) { nx = -nx; ny = -ny; nz = -nz; }
+            // a dielectric's device record holds (1/ior, r0, r0', ior), not a colour: its albedo is its attenuation, 1
+            if (mk == RT3_MAT_DIELECTRIC) { ar = ag = ab = 1.0f; }
+            else { ar = m.x; ag = m.y; ab = m.z; }
+            a.w = a.w + t;
+            k.z += 1u;
+        }                                                           // (RT3_HIT_INVALID: a miss with albedo 0)
+        a.x = a.x + ar; a.y = a.y + ag; a.z = a.z + ab;
+        n.x = n.x + nx; n.y = n.y + ny; n.z = n.z + nz;
+        if (first && s == 0) { k.x = kind; k.y = idx; }
+    }
+    acc[pix] = a;
+    acc[(size_t)npix + pix] = n;
+    *acc_u = k;
+}
+
+// The sums -> rt3_aov records (48 bytes: three 16-byte stores), spp samples per pixel.
+__global__ __launch_bounds__(kBlock) void k_aov_resolve(const float4* __restrict__ acc, uint32_t npix, uint32_t spp, float4* __restrict__ out) {
+    const uint32_t pix = blockIdx.x * kBlock + threadIdx.x;
+    if (pix >= npix) return;
+    const float4 a = acc[pix], n = acc[(size_t)npix + pix];
+    const uint4 k = reinterpret_cast<const uint4*>(acc)[2 * (size_t)npix + pix];
+    const float fs = (float)spp;
+    const uint32_t n_hit = k.z;
+    const float depth = n_hit ? a.w / (float)n_hit : __builtin_inff();
+    float4* o = out + 3 * (size_t)pix;
+    o[0] = make_float4(a.x / fs, a.y / fs, a.z / fs, (float)n_hit / fs);
+    o[1] = make_float4(n.x / fs, n.y / fs, n.z / fs, depth);
+    reinterpret_cast<uint4*>(o)[2] = make_uint4(k.x, k.y, 0u, 0u);
+}
+
+// Linear resolve of the accumulation: (sum / n, 0) per owned pixel, n = samples accumulated — k_resolve's division, before any gamma.
+__global__ __launch_bounds__(kBlock) void k_resolve_float(const float4* __restrict__ accum, uint32_t npix, uint32_t spp, float4* __restrict__ out) {
+    const uint32_t pix = blockIdx.x * kBlock + threadIdx.x;
+    if (pix >= npix) return;
+    const float4 a = accum[pix];
+    const float n = (float)spp;
+    out[pix] = make_float4(a.x / n, a.y / n, a.z / n, 0.0f);
+}
+
+}  // namespace

@@ -13,6 +13,7 @@
 //                           matrix cores (the default; RT3_NO_MFMA=1 selects the VALU scans)
 //   rt3_reduce.hpp          per-sample radiance (SampleStorage of raytracer_v4.glsl:107-111) summed in sample order and resolved
 //                           (the reduce pass reduce_v1.glsl never got) — the image is bitwise independent of scheduling and GPU count
+//   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
 //   below                   the device context and the extern "C" entry points
 //
@@ -39,6 +40,7 @@
 #include "rt3_matrix_filter.hpp"
 #include "rt3_level_filter.hpp"
 #include "rt3_reduce.hpp"
+#include "rt3_aov.hpp"
 #include "rt3_scene_kernels.hpp"
 
 // ======================================================================================================
@@ -77,6 +79,10 @@ struct rt3_ctx {
     uint32_t* d_out = nullptr; size_t out_entries = 0;
     float4* d_qrays = nullptr; size_t qrays_entries = 0;           // batched ray queries, host forms: the rays and the results on the device
     uint4* d_qout = nullptr; size_t qout_entries = 0;
+    float4* d_arays = nullptr; size_t arays_entries = 0;           // first-hit AOVs (rt3_render_aov*): one batch's camera rays and their hits,
+    uint4* d_ahits = nullptr; size_t ahits_entries = 0;            // and the per-pixel running sums (three planes; not d_accum, which belongs to
+    float4* d_aacc = nullptr; size_t aacc_entries = 0;             // the progressive render)
+    float4* d_hout = nullptr; size_t hout_entries = 0;             // host forms of rt3_camera_rays / rt3_render_aov / rt3_accum_resolve: the results on the device
     uint32_t* d_work = nullptr;                                     // [0] work counter
     unsigned long long* d_casts = nullptr;
     uint64_t rad_cap_bytes = 16ull << 30;
@@ -413,6 +419,37 @@ TraceArgs scene_args(const rt3_ctx* ctx) {
 
 bool cam_at_origin(const rt3_camera* cam) { return cam->origin[0] == 0.0f && cam->origin[1] == 0.0f && cam->origin[2] == 0.0f; }
 
+// The camera and params half of TraceArgs (on top of scene_args): what start_path() reads to turn an item (sample in batch, owned pixel) into
+// Mode X's primary ray.  Renders and the camera-ray / AOV passes (rt3_aov.hpp) share it; s0 and total are set per batch by the caller.
+int path_args(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t npix, TraceArgs& A) {
+    A = scene_args(ctx);
+    A.cam = cam_dev(cam);
+    A.lens_radius = p->lens_radius;
+    {
+        const float* h = cam->horizontal; const float* v = cam->vertical;
+        const float lh = std::sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
+        const float lv = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        A.lux = h[0] / lh; A.luy = h[1] / lh; A.luz = h[2] / lh;
+        A.lvx = v[0] / lv; A.lvy = v[1] / lv; A.lvz = v[2] / lv;
+    }
+    A.width = p->width; A.height = p->height; A.spp = p->spp; A.max_depth = p->max_depth; A.seed = p->seed; A.flags = p->flags;
+    {
+        uint32_t e = (uint32_t)std::sqrt((double)p->spp);
+        while (e * e > p->spp) e--;
+        while ((e + 1) * (e + 1) <= p->spp) e++;
+        A.edge = (e * e == p->spp && p->spp > 1) ? e : 0;          // stratified only for perfect squares (v4:199)
+    }
+    A.t_min = p->t_min;
+    A.tile_rows = p->tile_rows; A.tile_index = p->tile_index; A.tile_count = p->tile_count;
+    A.npix = npix;
+    A.div_npix = make_fastdiv(npix); A.div_width = make_fastdiv(p->width);
+    A.div_edge = make_fastdiv(A.edge ? A.edge : 1); A.div_tile_rows = make_fastdiv(p->tile_count > 1 ? p->tile_rows : 1);
+    if (!fastdiv_ok(npix, 0x7FFFFFFFu) || !fastdiv_ok(p->width, 0x7FFFFFFFu) || !fastdiv_ok(A.edge ? A.edge : 1, p->spp) ||
+        !fastdiv_ok(p->tile_count > 1 ? p->tile_rows : 1, p->height))
+        return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
+    return 0;
+}
+
 // ---- which trace kernel: ONE rule for Mode-X renders and batched ray queries (QUERY: the query form of the same kernel)
 //   brute         every ray against every primitive (debug switch / RT3_BRUTE=1; REFERENCE_PRIMARY with a camera off the origin or a lens)
 //   mfma_single   sphere scenes of <= 512 spheres, everything in LDS (the bench kernel)
@@ -539,6 +576,21 @@ void launch_trace(const TracePlan& T, const TraceArgs& A, uint32_t grid, hipStre
     else hipLaunchKernelGGL(T.plain, dim3(grid), dim3(kBlock), T.lds, stream, A);
 }
 
+// The launch half of a batched query: the query form of T over the n rays A.q_rays points to, as one timed launch of the call.
+// rt3_intersect* / rt3_occluded* issue it once, the AOV pass once per sample batch; the caller records ev_begin, clears the counters before
+// the first one and finishes the call (ev_end, ev_acc, the stats fields).
+int issue_query(rt3_ctx* ctx, const TraceArgs& A, const TracePlan& T, uint32_t n, hipStream_t stream) {
+    hipEvent_t a, b;
+    int rc;
+    if ((rc = take_event_pair(ctx, &a, &b))) return rc;
+    RT3_HIP(hipMemsetAsync(ctx->d_work, 0, 4, stream));
+    RT3_HIP(hipEventRecord(a, stream));
+    launch_trace(T, A, trace_grid(ctx, T, n), stream);
+    RT3_HIP(hipGetLastError());
+    RT3_HIP(hipEventRecord(b, stream));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -587,7 +639,8 @@ void rt3_destroy(rt3_ctx* ctx) {
     void* bufs[] = { ctx->d_gfaces, ctx->d_verts, ctx->d_face_mats_in, ctx->d_error, ctx->d_tri, ctx->d_tri_mat, ctx->d_tri_kind, ctx->d_tri_bound, ctx->d_tri_frag, ctx->d_sph, ctx->d_sph_frag, ctx->d_sph_frag32, ctx->d_sph_invr, ctx->d_sph_mat, ctx->d_sph_kind,
                      ctx->d_rad, ctx->d_accum, ctx->d_accum_sq, ctx->d_out, ctx->d_work, ctx->d_casts, ctx->d_box, ctx->d_tri_frag_r,
                      ctx->d_tri_gfrag, ctx->d_sph_gfrag, ctx->d_sph_grp, ctx->d_sph_perm, ctx->d_strips, ctx->d_tri_grp, ctx->d_tri_perm, ctx->d_tri_leaf, ctx->d_sph_leaf, ctx->d_tri_rowb, ctx->d_sph_rowb,
-                     ctx->d_tri_sfrag, ctx->d_sph_sfrag, ctx->d_tri_srowb, ctx->d_sph_srowb, ctx->d_tri_rec, ctx->d_qrays, ctx->d_qout };
+                     ctx->d_tri_sfrag, ctx->d_sph_sfrag, ctx->d_tri_srowb, ctx->d_sph_srowb, ctx->d_tri_rec, ctx->d_qrays, ctx->d_qout,
+                     ctx->d_arays, ctx->d_ahits, ctx->d_aacc, ctx->d_hout };
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (auto& p : ctx->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
@@ -1005,31 +1058,8 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
         if (var && (rc = ensure(ctx, &ctx->d_accum_sq, &ctx->accum_sq_entries, (size_t)npix))) return rc;
     }
 
-    TraceArgs A = scene_args(ctx);
-    A.cam = cam_dev(cam);
-    A.lens_radius = p->lens_radius;
-    {
-        const float* h = cam->horizontal; const float* v = cam->vertical;
-        const float lh = std::sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
-        const float lv = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        A.lux = h[0] / lh; A.luy = h[1] / lh; A.luz = h[2] / lh;
-        A.lvx = v[0] / lv; A.lvy = v[1] / lv; A.lvz = v[2] / lv;
-    }
-    A.width = p->width; A.height = p->height; A.spp = p->spp; A.max_depth = p->max_depth; A.seed = p->seed; A.flags = p->flags;
-    {
-        uint32_t e = (uint32_t)std::sqrt((double)p->spp);
-        while (e * e > p->spp) e--;
-        while ((e + 1) * (e + 1) <= p->spp) e++;
-        A.edge = (e * e == p->spp && p->spp > 1) ? e : 0;          // stratified only for perfect squares (v4:199)
-    }
-    A.t_min = p->t_min;
-    A.tile_rows = p->tile_rows; A.tile_index = p->tile_index; A.tile_count = p->tile_count;
-    A.npix = npix;
-    A.div_npix = make_fastdiv(npix); A.div_width = make_fastdiv(p->width);
-    A.div_edge = make_fastdiv(A.edge ? A.edge : 1); A.div_tile_rows = make_fastdiv(p->tile_count > 1 ? p->tile_rows : 1);
-    if (!fastdiv_ok(npix, 0x7FFFFFFFu) || !fastdiv_ok(p->width, 0x7FFFFFFFu) || !fastdiv_ok(A.edge ? A.edge : 1, p->spp) ||
-        !fastdiv_ok(p->tile_count > 1 ? p->tile_rows : 1, p->height))
-        return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
+    TraceArgs A;
+    if ((rc = path_args(ctx, cam, p, npix, A))) return rc;
     A.rad = ctx->d_rad;
 
     TracePlan T;
@@ -1220,15 +1250,9 @@ static int query_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_mi
     TracePlan T;
     int rc;
     if ((rc = plan_trace(ctx, A, false, false, true, T))) return rc;
-    hipEvent_t a, b;
-    if ((rc = take_event_pair(ctx, &a, &b))) return rc;
     RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
     RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 128, stream));
-    RT3_HIP(hipMemsetAsync(ctx->d_work, 0, 4, stream));
-    RT3_HIP(hipEventRecord(a, stream));
-    launch_trace(T, A, trace_grid(ctx, T, n), stream);
-    RT3_HIP(hipGetLastError());
-    RT3_HIP(hipEventRecord(b, stream));
+    if ((rc = issue_query(ctx, A, T, n, stream))) return rc;
     RT3_HIP(hipEventRecord(ctx->ev_end, stream));
     RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
     ctx->last_stream = stream;
@@ -1265,6 +1289,165 @@ int rt3_intersect_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_m
 int rt3_occluded_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_min, void* d_out, void* stream) {
     return query_device(ctx, d_rays, n, t_min, d_out, stream, true);
 }
+
+// ---- Camera rays, first-hit AOVs and the linear resolve
+static int aov_common_checks(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, const void* d_out, const char* what) {
+    if (!cam || !d_out) return fail(ctx, RT3_E_ARG, std::string("cam / ") + what + " is NULL");
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    if (p->flags & RT3_FLAG_REFERENCE_PRIMARY)
+        return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY: its primary directions are not unit vectors, which the query engine needs");
+    if ((uintptr_t)d_out % 16u != 0) return fail(ctx, RT3_E_ARG, std::string(what) + " must be 16-byte aligned");
+    return 0;
+}
+
+int rt3_camera_rays_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t sample_begin, uint32_t sample_count, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = aov_common_checks(ctx, cam, p, d_out, "rays");
+    if (rc) return rc;
+    if (sample_count == 0 || (uint64_t)sample_begin + sample_count > p->spp) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
+    const uint32_t npix = rt3_rows_owned(p) * p->width;
+    if ((uint64_t)npix * sample_count > 0x7FFF0000ull) return fail(ctx, RT3_E_ARG, "too many rays for one call (owned pixels x samples > 2^31 - 2^16)");
+    RT3_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
+    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));
+    if (npix != 0) {
+        TraceArgs A;
+        if ((rc = path_args(ctx, cam, p, npix, A))) return rc;
+        A.s0 = sample_begin;
+        A.total = npix * sample_count;
+        hipLaunchKernelGGL(k_camera_rays, dim3((A.total + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, (float4*)d_out);
+        RT3_HIP(hipGetLastError());
+    }
+    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
+    return 0;
+}
+
+int rt3_camera_rays(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t sample_begin, uint32_t sample_count, rt3_ray* out) {
+    if (!ctx) return RT3_E_ARG;
+    if (!out) return fail(ctx, RT3_E_ARG, "out_rays is NULL");
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    if (sample_count == 0 || (uint64_t)sample_begin + sample_count > p->spp) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
+    const uint64_t n = (uint64_t)rt3_rows_owned(p) * p->width * sample_count;
+    if (n > 0x7FFF0000ull) return fail(ctx, RT3_E_ARG, "too many rays for one call (owned pixels x samples > 2^31 - 2^16)");
+    RT3_HIP(hipSetDevice(ctx->device));
+    if ((rc = ensure(ctx, &ctx->d_hout, &ctx->hout_entries, std::max<size_t>(2 * n, 1)))) return rc;
+    if ((rc = rt3_camera_rays_device(ctx, cam, p, sample_begin, sample_count, ctx->d_hout, ctx->stream))) return rc;
+    if (n) RT3_HIP(hipMemcpyAsync(out, ctx->d_hout, n * sizeof(rt3_ray), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// Per sample batch: k_camera_rays -> the query form of the scene's trace kernel on that buffer -> k_aov_accumulate; then one k_aov_resolve.
+// The batches share one ev_begin / ev_end and one counter reset, as the render's batch loop does.
+int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = aov_common_checks(ctx, cam, p, d_out, "d_out_aov");
+    if (rc) return rc;
+    if (ctx->n_sph == 0 && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "no scene: call rt3_set_spheres / rt3_set_mesh first");
+    if (ctx->n_faces >= (1u << kPairLaneShift) - 32u || ctx->n_sph >= (1u << kPairLaneShift) - 32u) return fail(ctx, RT3_E_ARG, "too many primitives");
+    RT3_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
+    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));    // the counters, the work queue and the strips are the context's
+    const uint32_t npix = rt3_rows_owned(p) * p->width;
+    ctx->rendered = false;
+    ctx->ev_used = 0;
+    if (npix == 0) {
+        RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
+        RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 64, stream));
+        RT3_HIP(hipEventRecord(ctx->ev_end, stream));
+        RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
+        ctx->last_stream = stream; ctx->last_samples = 0; ctx->last_was_path = true; ctx->rendered = true;
+        return 0;
+    }
+    // batch size: 48 B per (pixel, sample) — the ray (32) and its hit (16) — under the sample storage cap
+    const uint64_t per_spp = (uint64_t)npix * (sizeof(rt3_ray) + sizeof(rt3_hit));
+    uint32_t batch = (uint32_t)std::min<uint64_t>(p->spp, std::max<uint64_t>(1, ctx->rad_cap_bytes / per_spp));
+    batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / npix);
+    if (batch == 0) return fail(ctx, RT3_E_ARG, "frame too large for one sample batch");
+    if ((rc = ensure(ctx, &ctx->d_arays, &ctx->arays_entries, (size_t)npix * batch * 2u)) ||
+        (rc = ensure(ctx, &ctx->d_ahits, &ctx->ahits_entries, (size_t)npix * batch)) ||
+        (rc = ensure(ctx, &ctx->d_aacc, &ctx->aacc_entries, (size_t)npix * 3u)))
+        return rc;
+    TraceArgs A;                                                    // camera rays and the accumulation
+    if ((rc = path_args(ctx, cam, p, npix, A))) return rc;
+    TraceArgs Q = scene_args(ctx);                                  // the query launches, as query_device sets them up
+    Q.t_min = p->t_min;
+    Q.q_rays = ctx->d_arays; Q.q_out = ctx->d_ahits; Q.q_occluded = 0u;
+    TracePlan T;
+    if ((rc = plan_trace(ctx, Q, false, false, true, T))) return rc;
+    RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
+    RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 128, stream));
+    for (uint32_t s0 = 0; s0 < p->spp; s0 += batch) {
+        const uint32_t ns = std::min(batch, p->spp - s0);
+        A.s0 = s0;
+        A.total = Q.total = npix * ns;
+        hipLaunchKernelGGL(k_camera_rays, dim3((A.total + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, ctx->d_arays);
+        RT3_HIP(hipGetLastError());
+        if ((rc = issue_query(ctx, Q, T, Q.total, stream))) return rc;
+        hipLaunchKernelGGL(k_aov_accumulate, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, (const float4*)ctx->d_arays,
+                           (const uint4*)ctx->d_ahits, ctx->d_aacc, npix, ns, s0 == 0 ? 1 : 0);
+        RT3_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_aov_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_aacc, npix, p->spp, (float4*)d_out);
+    RT3_HIP(hipGetLastError());
+    RT3_HIP(hipEventRecord(ctx->ev_end, stream));
+    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
+    ctx->last_stream = stream;
+    ctx->last_samples = (uint64_t)npix * p->spp;
+    ctx->last_was_path = true;
+    ctx->last_mfma16 = T.mfma16;
+    ctx->last_filter_rows = T.filter_rows;
+    ctx->rendered = true;
+    return 0;
+}
+
+int rt3_render_aov(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, rt3_aov* out) {
+    if (!ctx) return RT3_E_ARG;
+    if (!out) return fail(ctx, RT3_E_ARG, "out_aov is NULL");
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
+    if ((rc = ensure(ctx, &ctx->d_hout, &ctx->hout_entries, std::max<size_t>(3 * npix, 1)))) return rc;
+    if ((rc = rt3_render_aov_device(ctx, cam, p, ctx->d_hout, ctx->stream))) return rc;
+    if (npix) RT3_HIP(hipMemcpyAsync(out, ctx->d_hout, npix * sizeof(rt3_aov), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int rt3_accum_resolve_device(rt3_ctx* ctx, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    if (!d_out) return fail(ctx, RT3_E_ARG, "d_out_rgba is NULL");
+    if ((uintptr_t)d_out % 16u != 0) return fail(ctx, RT3_E_ARG, "d_out_rgba must be 16-byte aligned");
+    if (!ctx->acc_valid) return fail(ctx, RT3_E_STATE, "no accumulation on this context");
+    RT3_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
+    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));    // behind the render that wrote d_accum
+    if (ctx->acc_npix) {
+        hipLaunchKernelGGL(k_resolve_float, dim3((ctx->acc_npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_accum,
+                           ctx->acc_npix, ctx->acc_done, (float4*)d_out);
+        RT3_HIP(hipGetLastError());
+    }
+    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;       // a later render that overwrites d_accum waits for this
+    return 0;
+}
+
+int rt3_accum_resolve(rt3_ctx* ctx, float* rgba) {
+    if (!ctx) return RT3_E_ARG;
+    if (!rgba) return fail(ctx, RT3_E_ARG, "rgba is NULL");
+    if (!ctx->acc_valid) return fail(ctx, RT3_E_STATE, "no accumulation on this context");
+    RT3_HIP(hipSetDevice(ctx->device));
+    const size_t npix = ctx->acc_npix;
+    int rc;
+    if ((rc = ensure(ctx, &ctx->d_hout, &ctx->hout_entries, std::max<size_t>(npix, 1)))) return rc;
+    if ((rc = rt3_accum_resolve_device(ctx, ctx->d_hout, ctx->stream))) return rc;
+    if (npix) RT3_HIP(hipMemcpyAsync(rgba, ctx->d_hout, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+static_assert(sizeof(rt3_aov) == 48, "rt3.h: rt3_aov");
 
 int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {
     if (!ctx || !out) return RT3_E_ARG;

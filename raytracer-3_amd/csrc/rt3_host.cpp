@@ -244,6 +244,42 @@ int rt3_frame_to_ppm(const uint32_t* pixels, uint32_t width, uint32_t height, co
     return n == bytes.size() ? 0 : RT3_E_IO;
 }
 
+// Portable float map (PF: 3 channels, Pf: 1), scale -1.0 = little-endian floats, rows from the bottom of the image up.  The floats are copied
+// bit for bit (inf and NaN included).
+uint64_t rt3_frame_pfm_bytes(const float* data, uint32_t width, uint32_t height, uint32_t channels, uint32_t stride_floats, uint8_t* out,
+                             uint64_t cap) {
+    if ((channels != 1 && channels != 3) || stride_floats < channels || width == 0 || height == 0) return 0;
+    const std::string header = std::string(channels == 3 ? "PF" : "Pf") + "\n" + std::to_string(width) + " " + std::to_string(height) + "\n-1.0\n";
+    const uint64_t total = header.size() + 4ull * channels * width * height;
+    if (out == nullptr) return total;
+    if (cap < total || data == nullptr) return 0;
+    std::memcpy(out, header.data(), header.size());
+    uint8_t* p = out + header.size();
+    for (uint32_t r = 0; r < height; r++) {
+        const float* row = data + (uint64_t)(height - 1 - r) * width * stride_floats;
+        for (uint32_t x = 0; x < width; x++)
+            for (uint32_t c = 0; c < channels; c++) {
+                const float v = row[(uint64_t)x * stride_floats + c];
+                uint32_t bits;
+                std::memcpy(&bits, &v, 4);
+                *p++ = (uint8_t)bits; *p++ = (uint8_t)(bits >> 8); *p++ = (uint8_t)(bits >> 16); *p++ = (uint8_t)(bits >> 24);
+            }
+    }
+    return total;
+}
+
+int rt3_frame_to_pfm(const float* data, uint32_t width, uint32_t height, uint32_t channels, uint32_t stride_floats, const char* path) {
+    const uint64_t need = rt3_frame_pfm_bytes(data, width, height, channels, stride_floats, nullptr, 0);
+    if (need == 0 || data == nullptr || path == nullptr) return RT3_E_ARG;
+    std::vector<uint8_t> bytes(need);
+    rt3_frame_pfm_bytes(data, width, height, channels, stride_floats, bytes.data(), bytes.size());
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return RT3_E_IO;
+    const size_t n = std::fwrite(bytes.data(), 1, bytes.size(), f);
+    std::fclose(f);
+    return n == bytes.size() ? 0 : RT3_E_IO;
+}
+
 // random_v1.glsl:22-29 and :37-52.
 uint32_t rt3_hash_u32(uint32_t x) {
     x += x << 10; x ^= x >> 6; x += x << 3; x ^= x >> 11; x += x << 15;

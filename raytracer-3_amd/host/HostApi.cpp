@@ -259,8 +259,9 @@ void HipRenderer::render(Camera& camera) const {
     // a device that finishes early ships its rows while the others still trace) and the assembled frame leaves device 0 in one copy.
     // No pixel passes through host memory before that.  One host thread per device only issues the (asynchronous) work.
     const uint32_t n = (uint32_t)ctx.size();
+    last_w = w; last_h = h;
     if (n == 1) {
-        rt3_params p{ w, h, path.spp, path.max_depth, path.seed, path.flags, path.lens_radius, path.t_min, path.tile_rows, 0, 1 };
+        const rt3_params p = shard_params(w, h, 0);
         if (rt3_render_path(ctx[0], &cam, &p, out) != 0) throw Fatal(rt3_last_error(ctx[0]));
         return;
     }
@@ -274,7 +275,7 @@ void HipRenderer::render(Camera& camera) const {
     std::vector<std::thread> workers;
     for (uint32_t i = 0; i < n; i++) {
         workers.emplace_back([&, i]() {
-            rt3_params p{ w, h, path.spp, path.max_depth, path.seed, path.flags, path.lens_radius, path.t_min, path.tile_rows, i, n };
+            const rt3_params p = shard_params(w, h, i);
             const uint32_t rows = rt3_rows_owned(&p);
             if (rows == 0) return;
             DeviceBuffer tile{ ctx[i], rt3_device_alloc_words(ctx[i], (uint64_t)rows * w) };
@@ -288,6 +289,62 @@ void HipRenderer::render(Camera& camera) const {
     for (std::thread& t : workers) t.join();
     for (const std::string& e : errors) if (!e.empty()) throw Fatal(e);
     if (rt3_device_read_words(ctx[0], frame.p, (uint64_t)w * h, out) != 0) throw Fatal(rt3_last_error(ctx[0]));
+}
+
+rt3_params HipRenderer::shard_params(uint32_t w, uint32_t h, uint32_t i) const {
+    return rt3_params{ w, h, path.spp, path.max_depth, path.seed, path.flags, path.lens_radius, path.t_min, path.tile_rows, i, (uint32_t)ctx.size() };
+}
+
+namespace {
+// Runs fetch(i, params, rows, tile) for every device shard on a host thread of its own — tile: rows_owned * width records — and places the
+// tile's rows at their frame rows (rt3_row_of_local).  T: one record per pixel.
+template <class T, class ParamsOf, class Fetch>
+void gather_shards(uint32_t n, uint32_t w, ParamsOf params_of, Fetch fetch, T* frame) {
+    std::vector<std::string> errors(n);
+    std::vector<std::thread> workers;
+    for (uint32_t i = 0; i < n; i++) {
+        workers.emplace_back([&, i]() {
+            const rt3_params p = params_of(i);
+            const uint32_t rows = rt3_rows_owned(&p);
+            if (rows == 0) return;
+            std::vector<T> tile((size_t)rows * w);
+            if (!fetch(i, p, tile.data(), errors[i])) return;
+            for (uint32_t r = 0; r < rows; r++)
+                std::copy(tile.begin() + (size_t)r * w, tile.begin() + (size_t)(r + 1) * w, frame + (size_t)rt3_row_of_local(&p, r) * w);
+        });
+    }
+    for (std::thread& t : workers) t.join();
+    for (const std::string& e : errors) if (!e.empty()) throw Fatal(e);
+}
+}  // namespace
+
+std::vector<rt3_aov> HipRenderer::aov(Camera& camera) const {
+    if (path.spp == 0) throw Fatal("first-hit AOVs need the path tracer (Mode X)");
+    const rt3_camera cam = camera.wire();
+    const uint32_t w = camera.w(), h = camera.h();
+    std::vector<rt3_aov> frame((size_t)w * h);
+    gather_shards<rt3_aov>((uint32_t)ctx.size(), w, [&](uint32_t i) { return shard_params(w, h, i); },
+                           [&](uint32_t i, const rt3_params& p, rt3_aov* tile, std::string& err) {
+                               if (rt3_render_aov(ctx[i], &cam, &p, tile) == 0) return true;
+                               err = rt3_last_error(ctx[i]);
+                               return false;
+                           }, frame.data());
+    return frame;
+}
+
+std::vector<float> HipRenderer::hdr() const {
+    if (path.spp == 0 || last_w == 0) throw Fatal("the linear frame needs a Mode-X render first");
+    struct Rgba { float v[4]; };
+    std::vector<Rgba> frame((size_t)last_w * last_h);
+    gather_shards<Rgba>((uint32_t)ctx.size(), last_w, [&](uint32_t i) { return shard_params(last_w, last_h, i); },
+                        [&](uint32_t i, const rt3_params&, Rgba* tile, std::string& err) {
+                            if (rt3_accum_resolve(ctx[i], tile[0].v) == 0) return true;
+                            err = rt3_last_error(ctx[i]);
+                            return false;
+                        }, frame.data());
+    std::vector<float> out(4 * frame.size());
+    std::memcpy(out.data(), frame.data(), out.size() * sizeof(float));
+    return out;
 }
 
 rt3_stats HipRenderer::stats() const {

@@ -5,7 +5,7 @@
 // Kept: -f/--format png|ppm (default png), -W/--width (800), -H/--height (600), -h/--help, first positional =
 // output path (later ones ignored), value forms `-W 400`, `-W400`, `--width 400`; exit code 0 after help, -1 on a
 // usage error, -1 on a fatal backend error.  Fixed: `--key=value`, which the reference mis-parses (Main.cpp:110).
-// Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus.
+// Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr (PFM files).
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -28,6 +28,7 @@ struct Options {
     std::string scene = "builtin";
     uint32_t spp = 0, depth = 50, seed = 1, gpus = 1;
     bool gpu_prerender = false, dump_scene = false;
+    std::string aov_prefix, hdr_path;                              // Mode X: first-hit AOVs / the linear beauty as PFM files
 };
 
 void print_usage(const char* exe) {
@@ -43,6 +44,8 @@ void print_usage(const char* exe) {
               << "\t   --gpus\tNumber of GPUs to shard the frame over (default: 1).\n"
               << "\t   --gpu-prerender\tTessellate spheres on the GPU instead of the host (same arrays).\n"
               << "\t   --dump-scene\tParse the --scene file, print its entities and exit.\n"
+              << "\t   --aov\tMode X: also write the first-hit AOVs as PREFIX.albedo.pfm, PREFIX.normal.pfm and PREFIX.depth.pfm.\n"
+              << "\t   --hdr\tMode X: also write the linear (float) frame to this path as a 3-channel PFM.\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -80,7 +83,8 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         if (key == "--gpu-prerender") { opt.gpu_prerender = true; continue; }
         if (key == "--dump-scene") { opt.dump_scene = true; continue; }
         const bool known = key == "-f" || key == "--format" || key == "-W" || key == "--width" || key == "-H" || key == "--height" ||
-                           key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus";
+                           key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
+                           key == "--aov" || key == "--hdr";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -99,9 +103,17 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         else if (key == "--depth") { if (!parse_u32(value, "depth", "Depth", &opt.depth)) return -1; }
         else if (key == "--seed") { if (!parse_u32(value, "seed", "Seed", &opt.seed)) return -1; }
         else if (key == "--gpus") { if (!parse_u32(value, "gpus", "Gpus", &opt.gpus)) return -1; }
+        else if (key == "--aov") opt.aov_prefix = value;
+        else if (key == "--hdr") opt.hdr_path = value;
         else opt.scene = value;
     }
     if (opt.output_path.empty() && !opt.dump_scene) { std::cerr << "No output path given." << std::endl; return -1; }
+    // the builtin scene and .scene files render in Mode R unless --spp is given; the analytic scenes always run Mode X
+    const bool mode_r = opt.spp == 0 && (opt.scene == "builtin" || (opt.scene.size() > 6 && opt.scene.compare(opt.scene.size() - 6, 6, ".scene") == 0));
+    if (mode_r && (!opt.aov_prefix.empty() || !opt.hdr_path.empty())) {
+        std::cerr << "--aov and --hdr need the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
     return 1;
 }
 
@@ -205,6 +217,21 @@ int main(int argc, const char** argv) {
                   << " in " << st.total_ms << " ms on device 0: " << st.ray_casts << " rays, " << st.prim_tests << " ray-primitive tests\n";
         if (opt.png) cam.get_frame().to_png(opt.output_path);
         else cam.get_frame().to_ppm(opt.output_path);
+        const uint32_t w = cam.w(), h = cam.h();
+        if (!opt.hdr_path.empty()) {
+            const std::vector<float> hdr = renderer.hdr();
+            if (rt3_frame_to_pfm(hdr.data(), w, h, 3, 4, opt.hdr_path.c_str()) != 0) throw Fatal("Could not write '" + opt.hdr_path + "'");
+        }
+        if (!opt.aov_prefix.empty()) {
+            const std::vector<rt3_aov> aov = renderer.aov(cam);
+            const float* base = reinterpret_cast<const float*>(aov.data());          // (rt3_aov: 12 floats and words, 48 bytes)
+            const struct { const char* name; size_t offset; uint32_t channels; } planes[] = { { ".albedo.pfm", 0, 3 }, { ".normal.pfm", 4, 3 }, { ".depth.pfm", 7, 1 } };
+            for (const auto& pl : planes) {
+                const std::string out = opt.aov_prefix + pl.name;
+                if (rt3_frame_to_pfm(base + pl.offset, w, h, pl.channels, sizeof(rt3_aov) / sizeof(float), out.c_str()) != 0)
+                    throw Fatal("Could not write '" + out + "'");
+            }
+        }
     } catch (Fatal& e) {
         std::cerr << "fatal: " << e.what() << std::endl;            // the reference logs and returns -1 (Main.cpp:305-308)
         return -1;

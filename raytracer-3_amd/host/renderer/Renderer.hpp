@@ -38,6 +38,10 @@ public:
     void set_spheres(const std::vector<float>& center_radius, const std::vector<rt3_material>& materials);
     void set_mesh(const std::vector<rt3_gface>& faces, const std::vector<float>& vertices_xyzw, const std::vector<rt3_material>& face_materials);
     rt3_stats stats() const;                                                     // of device 0's last render
+    // Mode X only, full frames (row 0 on top) assembled from the device shards: the first-hit AOVs of the current options (rt3_render_aov),
+    // and the linear (r, g, b, 0) frame of the last render (rt3_accum_resolve)
+    std::vector<rt3_aov> aov(Camera& camera) const;
+    std::vector<float> hdr() const;
     size_t faces() const { return n_faces; }
     size_t spheres() const { return n_spheres; }
 
@@ -46,6 +50,8 @@ private:
     PathOptions path;
     bool gpu_prerender = false;
     size_t n_faces = 0, n_spheres = 0;
+    mutable uint32_t last_w = 0, last_h = 0;        // frame size of the last Mode-X render (hdr())
+    rt3_params shard_params(uint32_t w, uint32_t h, uint32_t i) const;
 };
 
 Renderer* initialize_renderer();                    // Renderer.hpp:63 — always the HIP backend here

@@ -42,6 +42,12 @@ int rt3_intersect(rt3_ctx*, const rt3_ray*, uint32_t, float, rt3_hit*) { return 
 int rt3_occluded(rt3_ctx*, const rt3_ray*, uint32_t, float, uint32_t*) { return RT3_E_DEVICE; }
 int rt3_intersect_device(rt3_ctx*, const void*, uint32_t, float, void*, void*) { return RT3_E_DEVICE; }
 int rt3_occluded_device(rt3_ctx*, const void*, uint32_t, float, void*, void*) { return RT3_E_DEVICE; }
+int rt3_camera_rays(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t, uint32_t, rt3_ray*) { return RT3_E_DEVICE; }
+int rt3_camera_rays_device(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t, uint32_t, void*, void*) { return RT3_E_DEVICE; }
+int rt3_render_aov(rt3_ctx*, const rt3_camera*, const rt3_params*, rt3_aov*) { return RT3_E_DEVICE; }
+int rt3_render_aov_device(rt3_ctx*, const rt3_camera*, const rt3_params*, void*, void*) { return RT3_E_DEVICE; }
+int rt3_accum_resolve(rt3_ctx*, float*) { return RT3_E_DEVICE; }
+int rt3_accum_resolve_device(rt3_ctx*, void*, void*) { return RT3_E_DEVICE; }
 // (rt3_rows_owned / rt3_row_of_local are pure host arithmetic that happens to live in rt3_device.hip)
 uint32_t rt3_rows_owned(const rt3_params* p) {
     uint32_t n = 0;
