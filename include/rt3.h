@@ -328,6 +328,26 @@ int rt3_accum_resolve(rt3_ctx* ctx, float* out_rgba);
 int rt3_accum_resolve_device(rt3_ctx* ctx, void* d_out_rgba, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Denoiser   (the spatial part of SVGF: an edge-avoiding a-trous filter guided by the AOVs)
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rt3_denoise_params {      /* 16 bytes */
+    uint32_t iterations;                 /* a-trous passes N, 1..8 (steps 1, 2, 4, ...); default 5 */
+    uint32_t normal_power;               /* exponent P of the normal weight, a power of two in 1..1024; default 128 */
+    float    sigma_luminance;            /* sigma_l, finite and > 0; default 4 */
+    float    sigma_depth;                /* sigma_z, finite and > 0; default 1 */
+} rt3_denoise_params;
+/* One whole frame of width x height pixels, row 0 on top: colour_rgba is (r, g, b, ignored) per pixel as rt3_accum_resolve writes it,
+ * aov one rt3_aov per pixel as rt3_render_aov writes it; out_rgba gets (r, g, b, 0) per pixel and must not overlap either input.  No scene
+ * is needed.  The call never touches the accumulation of a progressive render and leaves rt3_get_stats as it was.  Streams as for
+ * queries; the host form is synchronous.  RT3_E_ARG for a NULL pointer, width or height 0, width x height > 2^26, a parameter outside
+ * the ranges above, a device pointer that is not 16-byte aligned, or a device output that overlaps an input.  Scratch (52 bytes per
+ * pixel) belongs to the context. */
+int rt3_denoise(rt3_ctx* ctx, uint32_t width, uint32_t height, const float* colour_rgba, const rt3_aov* aov,
+                const rt3_denoise_params* p, float* out_rgba);
+int rt3_denoise_device(rt3_ctx* ctx, uint32_t width, uint32_t height, const void* d_colour_rgba, const void* d_aov,
+                       const rt3_denoise_params* p, void* d_out_rgba, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side scene API   (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)
  * ------------------------------------------------------------------------------------------------- */
 /* cpu_pre_render_triangle (src/lib/entities/Triangle.cpp:28-76): 1 face, 3 vertices (xyzw). */

@@ -105,6 +105,11 @@ def gather_plan(params):
     return [out[i] for i in range(n)]
 
 
+class DENOISE_PARAMS(C.Structure):
+    """rt3_denoise_params (16 bytes): a-trous passes, normal exponent, sigma_l, sigma_z."""
+    _fields_ = [("iterations", C.c_uint32), ("normal_power", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_depth", C.c_float)]
+
+
 class Fatal(RuntimeError):
     """Mirror of CppDebugger::Fatal: every backend error is fatal (Main.cpp:305-308)."""
 
@@ -124,7 +129,7 @@ EXPORTS = [
     "rt3_abi_version", "rt3_debug_force_flat_filter", "rt3_gather_plan",
     "rt3_intersect", "rt3_occluded", "rt3_intersect_device", "rt3_occluded_device",
     "rt3_camera_rays", "rt3_camera_rays_device", "rt3_render_aov", "rt3_render_aov_device", "rt3_accum_resolve", "rt3_accum_resolve_device",
-    "rt3_frame_pfm_bytes", "rt3_frame_to_pfm",
+    "rt3_frame_pfm_bytes", "rt3_frame_to_pfm", "rt3_denoise", "rt3_denoise_device",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -184,6 +189,7 @@ def lib():
         "rt3_render_aov": (i32, [vp, vp, vp, vp]), "rt3_render_aov_device": (i32, [vp, vp, vp, vp, vp]),
         "rt3_accum_resolve": (i32, [vp, vp]), "rt3_accum_resolve_device": (i32, [vp, vp, vp]),
         "rt3_frame_pfm_bytes": (u64, [vp, u32, u32, u32, u32, vp, u64]), "rt3_frame_to_pfm": (i32, [vp, u32, u32, u32, u32, C.c_char_p]),
+        "rt3_denoise": (i32, [vp, u32, u32, vp, vp, vp, vp]), "rt3_denoise_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -744,6 +750,36 @@ class HipRenderer(Renderer):
 
     def accum_resolve_device(self, d_out_ptr, stream_ptr=None):
         self._check(lib().rt3_accum_resolve_device(self._ctx, C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
+
+    # -- the denoiser -----------------------------------------------------------------------------------
+    def denoise(self, colour, aov, iterations=5, normal_power=128, sigma_luminance=4.0, sigma_depth=1.0):
+        """The AOV-guided a-trous denoiser (rt3_denoise) of one whole frame, row 0 on top.  numpy: colour float32 (H, W, 4) as accum_resolve
+        returns it, aov an (H, W) AOV array -> float32 (H, W, 4), (r, g, b, 0).  torch: a contiguous (H, W, 4) float32 tensor on the GPU and a
+        contiguous tensor of the frame's 48-byte rt3_aov records whose first two dimensions are (H, W) (e.g. (H, W, 12) float32) -> a new
+        (H, W, 4) float32 tensor, computed on torch.cuda.current_stream()."""
+        p = DENOISE_PARAMS(iterations, normal_power, sigma_luminance, sigma_depth)
+        if type(colour).__module__.startswith("torch"):
+            import torch
+            if (not colour.is_cuda or colour.dtype != torch.float32 or colour.dim() != 3 or colour.shape[2] != 4
+                    or not colour.is_contiguous()):
+                raise Fatal("device colour must be a contiguous (H, W, 4) float32 tensor on the GPU")
+            h, w = colour.shape[:2]
+            if (not type(aov).__module__.startswith("torch") or not aov.is_cuda or aov.dim() < 2 or tuple(aov.shape[:2]) != (h, w)
+                    or aov.numel() * aov.element_size() != h * w * AOV.itemsize or not aov.is_contiguous()):
+                raise Fatal("device AOVs must be a contiguous tensor of (H, W) 48-byte records on the GPU")
+            out = torch.empty_like(colour)
+            stream = torch.cuda.current_stream(colour.device).cuda_stream
+            self._check(lib().rt3_denoise_device(self._ctx, w, h, C.c_void_p(colour.data_ptr()), C.c_void_p(aov.data_ptr()), C.byref(p),
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+            return out
+        c = np.ascontiguousarray(colour, np.float32)
+        a = np.ascontiguousarray(aov)
+        if c.ndim != 3 or c.shape[2] != 4 or a.dtype != AOV or a.shape != c.shape[:2]:
+            raise Fatal("denoise: colour must be float32 (H, W, 4) and aov an (H, W) AOV array")
+        h, w = c.shape[:2]
+        out = np.zeros((h, w, 4), np.float32)
+        self._check(lib().rt3_denoise(self._ctx, w, h, _p(c), _p(a), C.byref(p), _p(out)))
+        return out
 
     def set_sample_storage_cap(self, nbytes):
         self._check(lib().rt3_set_sample_storage_cap(self._ctx, nbytes))

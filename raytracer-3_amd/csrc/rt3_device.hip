@@ -14,6 +14,7 @@
 //   rt3_reduce.hpp          per-sample radiance (SampleStorage of raytracer_v4.glsl:107-111) summed in sample order and resolved
 //                           (the reduce pass reduce_v1.glsl never got) — the image is bitwise independent of scheduling and GPU count
 //   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve
+//   rt3_denoise.hpp         the launcher of the AOV-guided a-trous denoiser (its kernels: rt3_denoise.hip)
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
 //   below                   the device context and the extern "C" entry points
 //
@@ -41,6 +42,7 @@
 #include "rt3_level_filter.hpp"
 #include "rt3_reduce.hpp"
 #include "rt3_aov.hpp"
+#include "rt3_denoise.hpp"
 #include "rt3_scene_kernels.hpp"
 
 // ======================================================================================================
@@ -83,6 +85,8 @@ struct rt3_ctx {
     uint4* d_ahits = nullptr; size_t ahits_entries = 0;            // and the per-pixel running sums (three planes; not d_accum, which belongs to
     float4* d_aacc = nullptr; size_t aacc_entries = 0;             // the progressive render)
     float4* d_hout = nullptr; size_t hout_entries = 0;             // host forms of rt3_camera_rays / rt3_render_aov / rt3_accum_resolve: the results on the device
+    float4* d_dn = nullptr; size_t dn_entries = 0;                 // denoiser scratch (rt3_denoise*): two (I, v) planes, the guide plane, the depth slopes
+    float4* d_dnh = nullptr; size_t dnh_entries = 0;               // host form of rt3_denoise: colour, AOVs and the result on the device
     uint32_t* d_work = nullptr;                                     // [0] work counter
     unsigned long long* d_casts = nullptr;
     uint64_t rad_cap_bytes = 16ull << 30;
@@ -640,7 +644,7 @@ void rt3_destroy(rt3_ctx* ctx) {
                      ctx->d_rad, ctx->d_accum, ctx->d_accum_sq, ctx->d_out, ctx->d_work, ctx->d_casts, ctx->d_box, ctx->d_tri_frag_r,
                      ctx->d_tri_gfrag, ctx->d_sph_gfrag, ctx->d_sph_grp, ctx->d_sph_perm, ctx->d_strips, ctx->d_tri_grp, ctx->d_tri_perm, ctx->d_tri_leaf, ctx->d_sph_leaf, ctx->d_tri_rowb, ctx->d_sph_rowb,
                      ctx->d_tri_sfrag, ctx->d_sph_sfrag, ctx->d_tri_srowb, ctx->d_sph_srowb, ctx->d_tri_rec, ctx->d_qrays, ctx->d_qout,
-                     ctx->d_arays, ctx->d_ahits, ctx->d_aacc, ctx->d_hout };
+                     ctx->d_arays, ctx->d_ahits, ctx->d_aacc, ctx->d_hout, ctx->d_dn, ctx->d_dnh };
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (auto& p : ctx->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
@@ -1448,6 +1452,63 @@ int rt3_accum_resolve(rt3_ctx* ctx, float* rgba) {
     return 0;
 }
 static_assert(sizeof(rt3_aov) == 48, "rt3.h: rt3_aov");
+
+// ---- The denoiser
+static int denoise_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* colour, const void* aov, const rt3_denoise_params* p,
+                          const void* out) {
+    if (!p) return fail(ctx, RT3_E_ARG, "p is NULL");
+    if (!colour || !aov || !out) return fail(ctx, RT3_E_ARG, "colour / aov / out is NULL");
+    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must have 1 .. 2^26 pixels");
+    if (p->iterations < 1 || p->iterations > 8) return fail(ctx, RT3_E_ARG, "iterations must be 1 .. 8");
+    if (p->normal_power < 1 || p->normal_power > 1024 || (p->normal_power & (p->normal_power - 1)))
+        return fail(ctx, RT3_E_ARG, "normal_power must be a power of two in 1 .. 1024");
+    if (!std::isfinite(p->sigma_luminance) || !(p->sigma_luminance > 0.0f) || !std::isfinite(p->sigma_depth) || !(p->sigma_depth > 0.0f))
+        return fail(ctx, RT3_E_ARG, "sigma_luminance and sigma_depth must be finite and > 0");
+    return 0;
+}
+
+// k_denoise_prepare -> k_denoise_moments -> k_denoise_atrous per pass, ping-ponging two (I, v) planes of the scratch; the last pass writes
+// d_out.  Scratch layout (float4 entries): [0, n) and [n, 2n) the (I, v) planes, [2n, 3n) the guide, then n floats of depth slope.
+int rt3_denoise_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_colour, const void* d_aov, const rt3_denoise_params* p, void* d_out,
+                       void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = denoise_checks(ctx, w, h, d_colour, d_aov, p, d_out);
+    if (rc) return rc;
+    if (((uintptr_t)d_colour | (uintptr_t)d_aov | (uintptr_t)d_out) % 16u != 0)
+        return fail(ctx, RT3_E_ARG, "d_colour_rgba, d_aov and d_out_rgba must be 16-byte aligned");
+    const size_t npix = (size_t)w * h;
+    const uintptr_t o = (uintptr_t)d_out, oe = o + npix * sizeof(float4);
+    const uintptr_t c = (uintptr_t)d_colour, a = (uintptr_t)d_aov;
+    if ((o < c + npix * sizeof(float4) && c < oe) || (o < a + npix * sizeof(rt3_aov) && a < oe))
+        return fail(ctx, RT3_E_ARG, "d_out_rgba overlaps an input");
+    RT3_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
+    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));    // the scratch is the context's
+    if ((rc = ensure(ctx, &ctx->d_dn, &ctx->dn_entries, 3 * npix + (npix + 3) / 4))) return rc;
+    const DenoiseLaunch L{ w, h, p->iterations, p->normal_power, p->sigma_luminance, p->sigma_depth, d_colour, d_aov, d_out, ctx->d_dn };
+    RT3_HIP(denoise_launch(L, stream));
+    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
+    return 0;
+}
+
+int rt3_denoise(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* colour, const rt3_aov* aov, const rt3_denoise_params* p, float* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = denoise_checks(ctx, w, h, colour, aov, p, out);
+    if (rc) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)w * h;
+    if ((rc = ensure(ctx, &ctx->d_dnh, &ctx->dnh_entries, 5 * npix))) return rc;
+    float4* const dc = ctx->d_dnh;
+    float4* const da = dc + npix;
+    float4* const dout = da + 3 * npix;
+    RT3_HIP(hipMemcpyAsync(dc, colour, npix * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    RT3_HIP(hipMemcpyAsync(da, aov, npix * sizeof(rt3_aov), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = rt3_denoise_device(ctx, w, h, dc, da, p, dout, ctx->stream))) return rc;
+    RT3_HIP(hipMemcpyAsync(out, dout, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+static_assert(sizeof(rt3_denoise_params) == 16, "rt3.h: rt3_denoise_params");
 
 int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {
     if (!ctx || !out) return RT3_E_ARG;

@@ -347,6 +347,15 @@ std::vector<float> HipRenderer::hdr() const {
     return out;
 }
 
+std::vector<float> HipRenderer::denoise(Camera& camera, const rt3_denoise_params& params) const {
+    const std::vector<float> colour = hdr();
+    if (camera.w() != last_w || camera.h() != last_h) throw Fatal("denoise: the camera's frame size differs from the last render's");
+    const std::vector<rt3_aov> guides = aov(camera);
+    std::vector<float> out(colour.size());
+    if (rt3_denoise(ctx[0], last_w, last_h, colour.data(), guides.data(), &params, out.data()) != 0) throw Fatal(rt3_last_error(ctx[0]));
+    return out;
+}
+
 rt3_stats HipRenderer::stats() const {
     rt3_stats s;
     if (rt3_get_stats(ctx[0], &s) != 0) throw Fatal(rt3_last_error(ctx[0]));

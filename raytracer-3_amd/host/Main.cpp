@@ -5,7 +5,7 @@
 // Kept: -f/--format png|ppm (default png), -W/--width (800), -H/--height (600), -h/--help, first positional =
 // output path (later ones ignored), value forms `-W 400`, `-W400`, `--width 400`; exit code 0 after help, -1 on a
 // usage error, -1 on a fatal backend error.  Fixed: `--key=value`, which the reference mis-parses (Main.cpp:110).
-// Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr (PFM files).
+// Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr, --denoise (PFM files).
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -29,6 +29,7 @@ struct Options {
     uint32_t spp = 0, depth = 50, seed = 1, gpus = 1;
     bool gpu_prerender = false, dump_scene = false;
     std::string aov_prefix, hdr_path;                              // Mode X: first-hit AOVs / the linear beauty as PFM files
+    std::string denoise_path;                                      // Mode X: the denoised linear frame as a PFM file
 };
 
 void print_usage(const char* exe) {
@@ -46,6 +47,7 @@ void print_usage(const char* exe) {
               << "\t   --dump-scene\tParse the --scene file, print its entities and exit.\n"
               << "\t   --aov\tMode X: also write the first-hit AOVs as PREFIX.albedo.pfm, PREFIX.normal.pfm and PREFIX.depth.pfm.\n"
               << "\t   --hdr\tMode X: also write the linear (float) frame to this path as a 3-channel PFM.\n"
+              << "\t   --denoise\tMode X: also write the denoised linear frame (a-trous, AOV-guided) to this path as a 3-channel PFM.\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -84,7 +86,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         if (key == "--dump-scene") { opt.dump_scene = true; continue; }
         const bool known = key == "-f" || key == "--format" || key == "-W" || key == "--width" || key == "-H" || key == "--height" ||
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
-                           key == "--aov" || key == "--hdr";
+                           key == "--aov" || key == "--hdr" || key == "--denoise";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -105,6 +107,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         else if (key == "--gpus") { if (!parse_u32(value, "gpus", "Gpus", &opt.gpus)) return -1; }
         else if (key == "--aov") opt.aov_prefix = value;
         else if (key == "--hdr") opt.hdr_path = value;
+        else if (key == "--denoise") opt.denoise_path = value;
         else opt.scene = value;
     }
     if (opt.output_path.empty() && !opt.dump_scene) { std::cerr << "No output path given." << std::endl; return -1; }
@@ -112,6 +115,10 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     const bool mode_r = opt.spp == 0 && (opt.scene == "builtin" || (opt.scene.size() > 6 && opt.scene.compare(opt.scene.size() - 6, 6, ".scene") == 0));
     if (mode_r && (!opt.aov_prefix.empty() || !opt.hdr_path.empty())) {
         std::cerr << "--aov and --hdr need the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
+    if (mode_r && !opt.denoise_path.empty()) {
+        std::cerr << "--denoise needs the path tracer (Mode X): pass --spp." << std::endl;
         return -1;
     }
     return 1;
@@ -231,6 +238,11 @@ int main(int argc, const char** argv) {
                 if (rt3_frame_to_pfm(base + pl.offset, w, h, pl.channels, sizeof(rt3_aov) / sizeof(float), out.c_str()) != 0)
                     throw Fatal("Could not write '" + out + "'");
             }
+        }
+        if (!opt.denoise_path.empty()) {
+            const rt3_denoise_params dp{ 5, 128, 4.0f, 1.0f };                     // the defaults of DESIGN.md 4.11
+            const std::vector<float> out = renderer.denoise(cam, dp);
+            if (rt3_frame_to_pfm(out.data(), w, h, 3, 4, opt.denoise_path.c_str()) != 0) throw Fatal("Could not write '" + opt.denoise_path + "'");
         }
     } catch (Fatal& e) {
         std::cerr << "fatal: " << e.what() << std::endl;            // the reference logs and returns -1 (Main.cpp:305-308)

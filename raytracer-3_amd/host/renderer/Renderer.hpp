@@ -42,6 +42,8 @@ public:
     // and the linear (r, g, b, 0) frame of the last render (rt3_accum_resolve)
     std::vector<rt3_aov> aov(Camera& camera) const;
     std::vector<float> hdr() const;
+    // Mode X only: the linear frame of the last render denoised on device 0 (rt3_denoise), guided by aov(camera); (r, g, b, 0) per pixel
+    std::vector<float> denoise(Camera& camera, const rt3_denoise_params& params) const;
     size_t faces() const { return n_faces; }
     size_t spheres() const { return n_spheres; }
 

@@ -48,6 +48,8 @@ int rt3_render_aov(rt3_ctx*, const rt3_camera*, const rt3_params*, rt3_aov*) { r
 int rt3_render_aov_device(rt3_ctx*, const rt3_camera*, const rt3_params*, void*, void*) { return RT3_E_DEVICE; }
 int rt3_accum_resolve(rt3_ctx*, float*) { return RT3_E_DEVICE; }
 int rt3_accum_resolve_device(rt3_ctx*, void*, void*) { return RT3_E_DEVICE; }
+int rt3_denoise(rt3_ctx*, uint32_t, uint32_t, const float*, const rt3_aov*, const rt3_denoise_params*, float*) { return RT3_E_DEVICE; }
+int rt3_denoise_device(rt3_ctx*, uint32_t, uint32_t, const void*, const void*, const rt3_denoise_params*, void*, void*) { return RT3_E_DEVICE; }
 // (rt3_rows_owned / rt3_row_of_local are pure host arithmetic that happens to live in rt3_device.hip)
 uint32_t rt3_rows_owned(const rt3_params* p) {
     uint32_t n = 0;
