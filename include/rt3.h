@@ -348,6 +348,40 @@ int rt3_denoise_device(rt3_ctx* ctx, uint32_t width, uint32_t height, const void
                        const rt3_denoise_params* p, void* d_out_rgba, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Temporal denoiser   (SVGF's temporal half: reprojected history, blended, temporal variance)
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rt3_history {             /* 48 bytes, one per pixel, row 0 on top */
+    float colour[3];                     /* demodulated colour after the first a-trous pass */
+    float length;                        /* frames integrated (1 = no usable history) */
+    float moments[2];                    /* integrated L and L*L */
+    float depth;                         /* this frame's depth (+inf = miss) */
+    float _pad0;
+    float normal[3];                     /* this frame's normal (the AOV's) */
+    float _pad1;
+} rt3_history;
+typedef struct rt3_temporal_params {     /* 32 bytes */
+    rt3_denoise_params spatial;          /* the a-trous passes, as for rt3_denoise */
+    float alpha;                         /* blend floor of the colour, in (0, 1]; default 0.2 */
+    float moments_alpha;                 /* blend floor of the moments, in (0, 1]; default 0.2 */
+    float depth_tolerance;               /* finite and > 0; default 2 */
+    float normal_tolerance;              /* in [-1, 1]; default 0.9 */
+} rt3_temporal_params;
+/* One frame of a sequence: colour_rgba and aov as for rt3_denoise, cam the camera they were rendered with; prev_cam and prev_history the
+ * previous frame's camera and the history the previous call wrote (both NULL for the first frame of a sequence, or both non-NULL).  Writes
+ * the denoised frame to out_rgba ((r, g, b, 0) per pixel) and the history for the next frame to out_history.  The caller owns the history:
+ * the context keeps no state between calls.  The call never touches the accumulation and leaves rt3_get_stats as it was; streams as for
+ * queries; the host form is synchronous.  RT3_E_ARG for a NULL pointer that is not allowed, width or height below 2, width x height > 2^26,
+ * a parameter outside the ranges above, a non-finite camera field, a degenerate camera (horizontal x vertical = 0, or an image plane through
+ * its origin), a device pointer that is not 16-byte aligned, or an output that overlaps an input or the other output (prev_history and
+ * out_history are two buffers, used ping-pong). */
+int rt3_denoise_temporal(rt3_ctx* ctx, uint32_t width, uint32_t height, const rt3_camera* cam, const float* colour_rgba, const rt3_aov* aov,
+                         const rt3_camera* prev_cam, const rt3_history* prev_history, const rt3_temporal_params* p,
+                         float* out_rgba, rt3_history* out_history);
+int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t width, uint32_t height, const rt3_camera* cam, const void* d_colour_rgba,
+                                const void* d_aov, const rt3_camera* prev_cam, const void* d_prev_history, const rt3_temporal_params* p,
+                                void* d_out_rgba, void* d_out_history, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side scene API   (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)
  * ------------------------------------------------------------------------------------------------- */
 /* cpu_pre_render_triangle (src/lib/entities/Triangle.cpp:28-76): 1 face, 3 vertices (xyzw). */

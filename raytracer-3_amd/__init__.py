@@ -44,6 +44,9 @@ HIT_NONE, HIT_FACE, HIT_SPHERE, HIT_INVALID = 0, 1, 2, 3
 # first-hit AOVs (rt3_render_aov): rt3_aov (48 bytes)
 AOV = np.dtype([("albedo", "<f4", 3), ("coverage", "<f4"), ("normal", "<f4", 3), ("depth", "<f4"), ("kind", "<u4"), ("index", "<u4"),
                 ("_pad", "<u4", 2)])
+# the temporal denoiser's per-pixel history (rt3_denoise_temporal): rt3_history (48 bytes)
+HISTORY = np.dtype([("colour", "<f4", 3), ("length", "<f4"), ("moments", "<f4", 2), ("depth", "<f4"), ("_pad0", "<f4"),
+                    ("normal", "<f4", 3), ("_pad1", "<f4")])
 OCCLUDED_INVALID = 0xFFFFFFFF      # rt3_occluded's word for an invalid ray
 FLAG_GAMMA2, FLAG_BLACK_BACKGROUND, FLAG_REFERENCE_PRIMARY, FLAG_VARIANCE = 1, 2, 4, 8
 
@@ -110,6 +113,12 @@ class DENOISE_PARAMS(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("normal_power", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class TEMPORAL_PARAMS(C.Structure):
+    """rt3_temporal_params (32 bytes): the a-trous passes, the blend floors and the consistency tolerances."""
+    _fields_ = [("spatial", DENOISE_PARAMS), ("alpha", C.c_float), ("moments_alpha", C.c_float), ("depth_tolerance", C.c_float),
+                ("normal_tolerance", C.c_float)]
+
+
 class Fatal(RuntimeError):
     """Mirror of CppDebugger::Fatal: every backend error is fatal (Main.cpp:305-308)."""
 
@@ -129,7 +138,7 @@ EXPORTS = [
     "rt3_abi_version", "rt3_debug_force_flat_filter", "rt3_gather_plan",
     "rt3_intersect", "rt3_occluded", "rt3_intersect_device", "rt3_occluded_device",
     "rt3_camera_rays", "rt3_camera_rays_device", "rt3_render_aov", "rt3_render_aov_device", "rt3_accum_resolve", "rt3_accum_resolve_device",
-    "rt3_frame_pfm_bytes", "rt3_frame_to_pfm", "rt3_denoise", "rt3_denoise_device",
+    "rt3_frame_pfm_bytes", "rt3_frame_to_pfm", "rt3_denoise", "rt3_denoise_device", "rt3_denoise_temporal", "rt3_denoise_temporal_device",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -190,6 +199,8 @@ def lib():
         "rt3_accum_resolve": (i32, [vp, vp]), "rt3_accum_resolve_device": (i32, [vp, vp, vp]),
         "rt3_frame_pfm_bytes": (u64, [vp, u32, u32, u32, u32, vp, u64]), "rt3_frame_to_pfm": (i32, [vp, u32, u32, u32, u32, C.c_char_p]),
         "rt3_denoise": (i32, [vp, u32, u32, vp, vp, vp, vp]), "rt3_denoise_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp]),
+        "rt3_denoise_temporal": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rt3_denoise_temporal_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -780,6 +791,52 @@ class HipRenderer(Renderer):
         out = np.zeros((h, w, 4), np.float32)
         self._check(lib().rt3_denoise(self._ctx, w, h, _p(c), _p(a), C.byref(p), _p(out)))
         return out
+
+    def denoise_temporal(self, colour, aov, camera_c, prev=None, iterations=5, normal_power=128, sigma_luminance=4.0, sigma_depth=1.0,
+                         alpha=0.2, moments_alpha=0.2, depth_tolerance=2.0, normal_tolerance=0.9):
+        """One frame of a sequence through the temporal denoiser (rt3_denoise_temporal) -> (out, history).  colour and aov
+        as for denoise, camera_c the rt3_camera they were rendered with; prev None for the first frame, else the history of the previous
+        call; history = (records, camera): an (H, W) HISTORY array (numpy) or a contiguous (H, W, 12) float32 GPU tensor (torch), and a copy
+        of camera_c.  torch inputs run on torch.cuda.current_stream()."""
+        p = TEMPORAL_PARAMS(DENOISE_PARAMS(iterations, normal_power, sigma_luminance, sigma_depth), alpha, moments_alpha, depth_tolerance,
+                            normal_tolerance)
+        cam = rt3_camera.from_buffer_copy(bytes(camera_c))
+        prev_rec, prev_cam = prev if prev is not None else (None, None)
+        pc = C.byref(prev_cam) if prev_cam is not None else None
+        if type(colour).__module__.startswith("torch"):
+            import torch
+            if (not colour.is_cuda or colour.dtype != torch.float32 or colour.dim() != 3 or colour.shape[2] != 4
+                    or not colour.is_contiguous()):
+                raise Fatal("device colour must be a contiguous (H, W, 4) float32 tensor on the GPU")
+            h, w = colour.shape[:2]
+            for t, what in ((aov, "AOVs"), (prev_rec, "history")):
+                if t is None:
+                    continue
+                if (not type(t).__module__.startswith("torch") or not t.is_cuda or t.dim() < 2 or tuple(t.shape[:2]) != (h, w)
+                        or t.numel() * t.element_size() != h * w * 48 or not t.is_contiguous()):
+                    raise Fatal("device %s must be a contiguous tensor of (H, W) 48-byte records on the GPU" % what)
+            out = torch.empty_like(colour)
+            hist = torch.empty((h, w, 12), dtype=torch.float32, device=colour.device)
+            stream = torch.cuda.current_stream(colour.device).cuda_stream
+            self._check(lib().rt3_denoise_temporal_device(
+                self._ctx, w, h, C.byref(cam), C.c_void_p(colour.data_ptr()), C.c_void_p(aov.data_ptr()), pc,
+                C.c_void_p(prev_rec.data_ptr()) if prev_rec is not None else None, C.byref(p), C.c_void_p(out.data_ptr()),
+                C.c_void_p(hist.data_ptr()), C.c_void_p(stream)))
+            return out, (hist, cam)
+        c = np.ascontiguousarray(colour, np.float32)
+        a = np.ascontiguousarray(aov)
+        if c.ndim != 3 or c.shape[2] != 4 or a.dtype != AOV or a.shape != c.shape[:2]:
+            raise Fatal("denoise_temporal: colour must be float32 (H, W, 4) and aov an (H, W) AOV array")
+        h, w = c.shape[:2]
+        pr = None
+        if prev_rec is not None:
+            pr = np.ascontiguousarray(prev_rec)
+            if pr.dtype != HISTORY or pr.shape != (h, w):
+                raise Fatal("denoise_temporal: the previous history must be an (H, W) HISTORY array")
+        out = np.zeros((h, w, 4), np.float32)
+        hist = np.zeros((h, w), HISTORY)
+        self._check(lib().rt3_denoise_temporal(self._ctx, w, h, C.byref(cam), _p(c), _p(a), pc, _p(pr), C.byref(p), _p(out), _p(hist)))
+        return out, (hist, cam)
 
     def set_sample_storage_cap(self, nbytes):
         self._check(lib().rt3_set_sample_storage_cap(self._ctx, nbytes))

@@ -98,13 +98,20 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_denoise_prepare(const Den
     gz[p] = g;
 }
 
-// The spatial variance estimate: il (I, L) -> iv (I, v), v from the w_g-weighted moments of L over the 7 x 7 window.
+// The spatial variance estimate: il (I, L) -> iv (I, v), v from the w_g-weighted moments of L over the 7 x 7 window.  TEMPORAL (DESIGN.md
+// 4.12 step 6): where the history record's length is at least 4, v = max(0, M2 - M1 * M1) of its moments instead.
+template <bool TEMPORAL>
 __global__ __launch_bounds__(kDnTile * kDnTile) void k_denoise_moments(const DenoiseArgs D, const float4* __restrict__ il,
-                                                                      float4* __restrict__ iv) {
+                                                                      float4* __restrict__ iv, const float4* __restrict__ hist) {
     int x, y;
     if (!dn_pixel(D, x, y)) return;
     const int W = (int)D.width, H = (int)D.height;
     const uint32_t p = (uint32_t)(y * W + x);
+    if (TEMPORAL && hist[3 * (size_t)p].w >= 4.0f) {
+        const float4 m = hist[3 * (size_t)p + 1], c = il[p];
+        iv[p] = make_float4(c.x, c.y, c.z, fmaxf(0.0f, m.y - m.x * m.x));
+        return;
+    }
     const float4 gp = D.guide[p];
     const float gzp = D.gz[p];
     float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
@@ -130,10 +137,12 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_denoise_moments(const Den
 }
 
 // One a-trous pass at step `step` over (I, v): the edge-stopped 3 x 3 blur of v, then the 25 taps.  LAST: remodulate with the albedo of
-// the rt3_aov records and write (r, g, b, 0) to the caller's frame instead of (I', v').
-template <bool LAST>
+// the rt3_aov records and write (r, g, b, 0) to the caller's frame instead of (I', v').  HIST (pass 0 of the temporal call): also write
+// (I'.rgb, length) to the first float4 of the pixel's history record, whose length k_temporal_reproject left there.
+template <bool LAST, bool HIST>
 __global__ __launch_bounds__(kDnTile * kDnTile) void k_denoise_atrous(const DenoiseArgs D, const float4* __restrict__ in,
-                                                                     float4* __restrict__ out, int step, const float4* __restrict__ aov) {
+                                                                     float4* __restrict__ out, int step, const float4* __restrict__ aov,
+                                                                     float4* __restrict__ hist) {
     int x, y;
     if (!dn_pixel(D, x, y)) return;
     const int W = (int)D.width, H = (int)D.height;
@@ -197,12 +206,128 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_denoise_atrous(const Deno
         }
     }
     const float ir = sr / sw, ig = sg / sw, ib = sb / sw;
+    if (HIST) hist[3 * (size_t)p] = make_float4(ir, ig, ib, hist[3 * (size_t)p].w);
     if (LAST) {
         const float4 a = aov[3 * (size_t)p];
         out[p] = make_float4(a.x > 0x1p-10f ? ir * a.x : ir, a.y > 0x1p-10f ? ig * a.y : ig, a.z > 0x1p-10f ? ib * a.z : ib, 0.0f);
     } else {
         out[p] = make_float4(ir, ig, ib, sv / (sw * sw));
     }
+}
+
+// What k_temporal_reproject reads besides DenoiseArgs: this frame's camera, the previous camera's constants, the parameters.
+struct TemporalArgs {
+    float ox, oy, oz, hx, hy, hz, vx, vy, vz, lx, ly, lz;      // this frame's camera
+    float pox, poy, poz, plx, ply, plz;                        // o' and L = llc' - o'
+    float nx, ny, nz, aux, auy, auz, avx, avy, avz, ln;        // n = h x v, a_u, a_v, L . n
+    uint32_t has_prev, same_cam;
+    float alpha, moments_alpha, depth_tolerance, normal_tolerance;
+};
+
+__device__ __forceinline__ float dn_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+// DESIGN.md 4.12 steps 1-5 (in place of k_denoise_prepare): colour, rt3_aov records and the previous history -> il = (I.rgb, L(I)) of the
+// blended I, the guide and gz planes as k_denoise_prepare writes them, and the history record of the pixel with (I, length) in its first
+// float4 (pass 0 replaces I), (M1, M2, depth, 0) and (normal, 0).
+__global__ __launch_bounds__(kDnTile * kDnTile) void k_temporal_reproject(const DenoiseArgs D, const TemporalArgs T,
+                                                                         const float4* __restrict__ colour, const float4* __restrict__ aov,
+                                                                         const float4* __restrict__ prev, float4* __restrict__ il,
+                                                                         float4* __restrict__ guide, float* __restrict__ gz,
+                                                                         float4* __restrict__ hist) {
+    int x, y;
+    if (!dn_pixel(D, x, y)) return;
+    const int W = (int)D.width, H = (int)D.height;
+    const uint32_t p = (uint32_t)(y * W + x);
+    // 1: demodulate, guides and depth slope exactly as k_denoise_prepare
+    const float4 c = colour[p], a = aov[3 * (size_t)p], n = aov[3 * (size_t)p + 1];
+    const float ir = dn_demod(c.x, a.x), ig = dn_demod(c.y, a.y), ib = dn_demod(c.z, a.z);
+    const float lc = dn_lum(ir, ig, ib);
+    guide[p] = n;
+    float g = 0.0f;
+    if (!__builtin_isinf(n.w)) {
+        const int nx[4] = { x - 1, x + 1, x, x }, ny[4] = { y, y, y - 1, y + 1 };
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (nx[k] < 0 || nx[k] >= W || ny[k] < 0 || ny[k] >= H) continue;
+            const float zq = aov[3 * (size_t)(ny[k] * W + nx[k]) + 1].w;
+            if (!__builtin_isinf(zq)) g = fmaxf(g, __builtin_fabsf(zq - n.w));
+        }
+    }
+    gz[p] = g;
+
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, s1 = 0.0f, s2 = 0.0f, nmin = __builtin_inff();
+    if (T.has_prev) {
+        // 2: the world point of the pixel-centre ray, relative to the previous origin (the sky: the direction)
+        const float u = (float)x / ((float)W - 1.0f), v = (float)(H - 1 - y) / ((float)H - 1.0f);
+        const float dx = ((T.lx + u * T.hx) + v * T.vx) - T.ox;
+        const float dy = ((T.ly + u * T.hy) + v * T.vy) - T.oy;
+        const float dz = ((T.lz + u * T.hz) + v * T.vz) - T.oz;
+        const float inv = 1.0f / __builtin_sqrtf(dn_dot(dx, dy, dz, dx, dy, dz));
+        const float ux = dx * inv, uy = dy * inv, uz = dz * inv;
+        const bool hit = !__builtin_isinf(n.w);
+        const float rx = hit ? (T.ox + n.w * ux) - T.pox : ux;
+        const float ry = hit ? (T.oy + n.w * uy) - T.poy : uy;
+        const float rz = hit ? (T.oz + n.w * uz) - T.poz : uz;
+        // 3: project into the previous camera (skipped for a byte-equal camera: every pixel maps to itself)
+        float xp = (float)x, yp = (float)y;
+        bool ok = true;
+        if (!T.same_cam) {
+            const float sc = T.ln / dn_dot(rx, ry, rz, T.nx, T.ny, T.nz);
+            ok = __builtin_isfinite(sc) && sc > 0.0f;
+            const float px = sc * rx - T.plx, py = sc * ry - T.ply, pz = sc * rz - T.plz;
+            xp = dn_dot(px, py, pz, T.aux, T.auy, T.auz) * ((float)W - 1.0f);
+            yp = ((float)H - 1.0f) - dn_dot(px, py, pz, T.avx, T.avy, T.avz) * ((float)H - 1.0f);
+        }
+        // 4: the bilinear taps that lie in the frame and are consistent (no tap can when x' or y' is outside (-1, W) x (-1, H), or NaN)
+        if (ok && xp > -1.0f && xp < (float)W && yp > -1.0f && yp < (float)H) {
+            const float zhat = __builtin_sqrtf(dn_dot(rx, ry, rz, rx, ry, rz));
+            const float bound = T.depth_tolerance * (g + 1e-3f * zhat);
+            const float x0 = __builtin_floorf(xp), y0 = __builtin_floorf(yp);
+            const float fx = xp - x0, fy = yp - y0;
+            const int ix = (int)x0, iy = (int)y0;
+            const float wt[4] = { (1.0f - fx) * (1.0f - fy), fx * (1.0f - fy), (1.0f - fx) * fy, fx * fy };
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int qx = ix + (k & 1), qy = iy + (k >> 1);
+                if (wt[k] == 0.0f || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                const size_t q = 3 * (size_t)(qy * W + qx);
+                const float4 hm = prev[q + 1], hn = prev[q + 2];
+                bool consistent;
+                if (!hit || __builtin_isinf(hm.z)) consistent = !hit && __builtin_isinf(hm.z);
+                else consistent = __builtin_fabsf(hm.z - zhat) <= bound && dn_dot(n.x, n.y, n.z, hn.x, hn.y, hn.z) >= T.normal_tolerance;
+                if (!consistent) continue;
+                const float4 hc = prev[q];
+                const float w = wt[k];
+                sw = sw + w;
+                sr = sr + w * hc.x;
+                sg = sg + w * hc.y;
+                sb = sb + w * hc.z;
+                s1 = s1 + w * hm.x;
+                s2 = s2 + w * hm.y;
+                nmin = fminf(nmin, hc.w);
+            }
+        }
+    }
+    // 5: blend, or start afresh
+    float4 o;
+    float len, m1, m2;
+    if (sw >= 0.01f) {
+        len = fminf(nmin + 1.0f, 65535.0f);
+        const float a1 = fmaxf(T.alpha, 1.0f / len), a2 = fmaxf(T.moments_alpha, 1.0f / len);
+        const float r = (1.0f - a1) * (sr / sw) + a1 * ir, gg = (1.0f - a1) * (sg / sw) + a1 * ig, b = (1.0f - a1) * (sb / sw) + a1 * ib;
+        o = make_float4(r, gg, b, dn_lum(r, gg, b));
+        m1 = (1.0f - a2) * (s1 / sw) + a2 * lc;
+        m2 = (1.0f - a2) * (s2 / sw) + a2 * (lc * lc);
+    } else {
+        len = 1.0f;
+        o = make_float4(ir, ig, ib, lc);
+        m1 = lc;
+        m2 = lc * lc;
+    }
+    il[p] = o;
+    hist[3 * (size_t)p] = make_float4(o.x, o.y, o.z, len);
+    hist[3 * (size_t)p + 1] = make_float4(m1, m2, n.w, 0.0f);
+    hist[3 * (size_t)p + 2] = make_float4(n.x, n.y, n.z, 0.0f);
 }
 
 }  // namespace
@@ -226,13 +351,64 @@ hipError_t denoise_launch(const DenoiseLaunch& L, hipStream_t stream) {
     hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, stream, D, (const float4*)L.colour, aov, pa, guide, gz);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_denoise_moments, grid, block, 0, stream, D, (const float4*)pa, pb);
+    hipLaunchKernelGGL(k_denoise_moments<false>, grid, block, 0, stream, D, (const float4*)pa, pb, nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     float4* src = pb;
     float4* dst = pa;
     for (uint32_t i = 0; i < L.iterations; i++) {
-        if (i + 1 == L.iterations) hipLaunchKernelGGL(k_denoise_atrous<true>, grid, block, 0, stream, D, (const float4*)src, (float4*)L.out, 1 << i, aov);
-        else hipLaunchKernelGGL(k_denoise_atrous<false>, grid, block, 0, stream, D, (const float4*)src, dst, 1 << i, aov);
+        if (i + 1 == L.iterations) hipLaunchKernelGGL((k_denoise_atrous<true, false>), grid, block, 0, stream, D, (const float4*)src, (float4*)L.out, 1 << i, aov, nullptr);
+        else hipLaunchKernelGGL((k_denoise_atrous<false, false>), grid, block, 0, stream, D, (const float4*)src, dst, 1 << i, aov, nullptr);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        float4* t = src; src = dst; dst = t;
+    }
+    return hipSuccess;
+}
+
+hipError_t temporal_launch(const TemporalLaunch& T, hipStream_t stream) {
+    const DenoiseLaunch& L = T.base;
+    const uint32_t w = L.width, h = L.height;
+    const size_t npix = (size_t)w * h;
+    float4* const pa = L.scratch;
+    float4* const pb = pa + npix;
+    float4* const guide = pb + npix;
+    float* const gz = reinterpret_cast<float*>(guide + npix);
+    DenoiseArgs D;
+    D.width = w; D.height = h;
+    D.tiles_x = (w + kDnTile - 1) / kDnTile;
+    D.squarings = 0;
+    while ((1u << D.squarings) < L.normal_power) D.squarings++;
+    D.sigma_l = L.sigma_l; D.sigma_z = L.sigma_z;
+    D.guide = guide; D.gz = gz;
+    TemporalArgs A;
+    A.ox = T.cam[0]; A.oy = T.cam[1]; A.oz = T.cam[2];
+    A.hx = T.cam[3]; A.hy = T.cam[4]; A.hz = T.cam[5];
+    A.vx = T.cam[6]; A.vy = T.cam[7]; A.vz = T.cam[8];
+    A.lx = T.cam[9]; A.ly = T.cam[10]; A.lz = T.cam[11];
+    A.pox = T.prev_o[0]; A.poy = T.prev_o[1]; A.poz = T.prev_o[2];
+    A.plx = T.prev_l[0]; A.ply = T.prev_l[1]; A.plz = T.prev_l[2];
+    A.nx = T.prev_n[0]; A.ny = T.prev_n[1]; A.nz = T.prev_n[2];
+    A.aux = T.a_u[0]; A.auy = T.a_u[1]; A.auz = T.a_u[2];
+    A.avx = T.a_v[0]; A.avy = T.a_v[1]; A.avz = T.a_v[2];
+    A.ln = T.ln;
+    A.has_prev = T.has_prev; A.same_cam = T.same_cam;
+    A.alpha = T.alpha; A.moments_alpha = T.moments_alpha; A.depth_tolerance = T.depth_tolerance; A.normal_tolerance = T.normal_tolerance;
+    const dim3 grid(D.tiles_x * ((h + kDnTile - 1) / kDnTile)), block(kDnTile, kDnTile);
+    const float4* aov = (const float4*)L.aov;
+    float4* const hist = (float4*)T.out_history;
+    hipLaunchKernelGGL(k_temporal_reproject, grid, block, 0, stream, D, A, (const float4*)L.colour, aov, (const float4*)T.prev_history, pa,
+                       guide, gz, hist);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_denoise_moments<true>, grid, block, 0, stream, D, (const float4*)pa, pb, (const float4*)hist);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    float4* src = pb;
+    float4* dst = pa;
+    for (uint32_t i = 0; i < L.iterations; i++) {
+        const bool last = i + 1 == L.iterations;
+        if (i == 0 && last) hipLaunchKernelGGL((k_denoise_atrous<true, true>), grid, block, 0, stream, D, (const float4*)src, (float4*)L.out, 1, aov, hist);
+        else if (i == 0) hipLaunchKernelGGL((k_denoise_atrous<false, true>), grid, block, 0, stream, D, (const float4*)src, dst, 1, aov, hist);
+        else if (last) hipLaunchKernelGGL((k_denoise_atrous<true, false>), grid, block, 0, stream, D, (const float4*)src, (float4*)L.out, 1 << i, aov, nullptr);
+        else hipLaunchKernelGGL((k_denoise_atrous<false, false>), grid, block, 0, stream, D, (const float4*)src, dst, 1 << i, aov, nullptr);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         float4* t = src; src = dst; dst = t;
     }

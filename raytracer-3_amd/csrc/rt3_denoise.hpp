@@ -1,4 +1,4 @@
-// rt3_denoise.hpp — what rt3_device.hip needs of the denoiser (rt3_denoise.hip): its launcher.
+// rt3_denoise.hpp — what rt3_device.hip needs of the denoiser (rt3_denoise.hip): its launchers.
 #pragma once
 
 // One rt3_denoise_device call once its arguments have been checked: k_denoise_prepare, k_denoise_moments and `iterations` a-trous passes on
@@ -12,3 +12,19 @@ struct DenoiseLaunch {
     float4* scratch;
 };
 hipError_t denoise_launch(const DenoiseLaunch& L, hipStream_t stream);
+
+// One rt3_denoise_temporal_device call once its arguments have been checked: k_temporal_reproject, k_denoise_moments<true> and the passes,
+// pass 0 also writing the history colour.  The same scratch as denoise_launch.  The per-call constants of the projection into the previous
+// camera are computed by the caller in f32 in the order given there.
+struct TemporalLaunch {
+    DenoiseLaunch base;
+    float cam[12];                          // this frame's rt3_camera: origin, horizontal, vertical, lower_left_corner
+    float prev_o[3], prev_l[3];             // o' and L = llc' - o'
+    float prev_n[3], a_u[3], a_v[3];        // n = h x v, a_u, a_v
+    float ln;                               // L . n
+    uint32_t has_prev, same_cam;            // a previous frame; *prev_cam == *cam byte for byte
+    float alpha, moments_alpha, depth_tolerance, normal_tolerance;
+    const void* prev_history;               // width * height rt3_history (3 float4 each), or nullptr without has_prev
+    void* out_history;                      // width * height rt3_history
+};
+hipError_t temporal_launch(const TemporalLaunch& L, hipStream_t stream);

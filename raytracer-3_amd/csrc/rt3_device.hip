@@ -14,7 +14,7 @@
 //   rt3_reduce.hpp          per-sample radiance (SampleStorage of raytracer_v4.glsl:107-111) summed in sample order and resolved
 //                           (the reduce pass reduce_v1.glsl never got) — the image is bitwise independent of scheduling and GPU count
 //   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve
-//   rt3_denoise.hpp         the launcher of the AOV-guided a-trous denoiser (its kernels: rt3_denoise.hip)
+//   rt3_denoise.hpp         the launchers of the AOV-guided a-trous denoiser and its temporal form (kernels: rt3_denoise.hip)
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
 //   below                   the device context and the extern "C" entry points
 //
@@ -86,7 +86,7 @@ struct rt3_ctx {
     float4* d_aacc = nullptr; size_t aacc_entries = 0;             // the progressive render)
     float4* d_hout = nullptr; size_t hout_entries = 0;             // host forms of rt3_camera_rays / rt3_render_aov / rt3_accum_resolve: the results on the device
     float4* d_dn = nullptr; size_t dn_entries = 0;                 // denoiser scratch (rt3_denoise*): two (I, v) planes, the guide plane, the depth slopes
-    float4* d_dnh = nullptr; size_t dnh_entries = 0;               // host form of rt3_denoise: colour, AOVs and the result on the device
+    float4* d_dnh = nullptr; size_t dnh_entries = 0;               // host forms of rt3_denoise*: colour, AOVs, histories and the results on the device
     uint32_t* d_work = nullptr;                                     // [0] work counter
     unsigned long long* d_casts = nullptr;
     uint64_t rad_cap_bytes = 16ull << 30;
@@ -1509,6 +1509,129 @@ int rt3_denoise(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* colour, const
     return 0;
 }
 static_assert(sizeof(rt3_denoise_params) == 16, "rt3.h: rt3_denoise_params");
+
+// ---- The temporal denoiser
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+// h x v, written out: (hy vz - hz vy, hz vx - hx vz, hx vy - hy vx)
+static void cross3(const float* h, const float* v, float* out) {
+    out[0] = h[1] * v[2] - h[2] * v[1];
+    out[1] = h[2] * v[0] - h[0] * v[2];
+    out[2] = h[0] * v[1] - h[1] * v[0];
+}
+
+static float dot3h(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// A camera the reprojection can use: finite fields, horizontal x vertical != 0, and an image plane that misses the origin.
+static bool camera_ok(const rt3_camera* c) {
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(c->origin[i]) || !std::isfinite(c->horizontal[i]) || !std::isfinite(c->vertical[i]) || !std::isfinite(c->lower_left_corner[i]))
+            return false;
+    float n[3], l[3];
+    cross3(c->horizontal, c->vertical, n);
+    if (n[0] == 0.0f && n[1] == 0.0f && n[2] == 0.0f) return false;
+    for (int i = 0; i < 3; i++) l[i] = c->lower_left_corner[i] - c->origin[i];
+    return dot3h(l, n) != 0.0f;
+}
+
+static int temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* colour, const void* aov,
+                           const rt3_camera* prev_cam, const void* prev_history, const rt3_temporal_params* p, const void* out,
+                           const void* out_history) {
+    if (!p || !cam) return fail(ctx, RT3_E_ARG, "p / cam is NULL");
+    if (!colour || !aov || !out || !out_history) return fail(ctx, RT3_E_ARG, "colour / aov / out / out_history is NULL");
+    if (!prev_cam != !prev_history) return fail(ctx, RT3_E_ARG, "prev_cam and prev_history must both be NULL or both be non-NULL");
+    if (w < 2 || h < 2 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must be at least 2 x 2 and have at most 2^26 pixels");
+    int rc = denoise_checks(ctx, w, h, colour, aov, &p->spatial, out);
+    if (rc) return rc;
+    if (!(p->alpha > 0.0f && p->alpha <= 1.0f) || !(p->moments_alpha > 0.0f && p->moments_alpha <= 1.0f))
+        return fail(ctx, RT3_E_ARG, "alpha and moments_alpha must be in (0, 1]");
+    if (!std::isfinite(p->depth_tolerance) || !(p->depth_tolerance > 0.0f)) return fail(ctx, RT3_E_ARG, "depth_tolerance must be finite and > 0");
+    if (!(p->normal_tolerance >= -1.0f && p->normal_tolerance <= 1.0f)) return fail(ctx, RT3_E_ARG, "normal_tolerance must be in [-1, 1]");
+    if (!camera_ok(cam) || (prev_cam && !camera_ok(prev_cam)))
+        return fail(ctx, RT3_E_ARG, "a camera has a non-finite field, horizontal x vertical = 0, or an image plane through its origin");
+    const size_t npix = (size_t)w * h, nf = npix * sizeof(float4), nh = npix * sizeof(rt3_history);
+    const struct { const void* ptr; size_t n; } in[3] = { { colour, nf }, { aov, npix * sizeof(rt3_aov) }, { prev_history, nh } };
+    for (const auto& i : in)
+        if (i.ptr && (ranges_overlap(out, nf, i.ptr, i.n) || ranges_overlap(out_history, nh, i.ptr, i.n)))
+            return fail(ctx, RT3_E_ARG, "an output overlaps an input");
+    if (ranges_overlap(out, nf, out_history, nh)) return fail(ctx, RT3_E_ARG, "out_rgba and out_history overlap");
+    return 0;
+}
+
+// k_temporal_reproject -> k_denoise_moments<true> -> the passes (pass 0 also writes the history colour); the same scratch as rt3_denoise.
+// The projection constants of DESIGN.md 4.12 step 3, in f32 in this order: L = llc' - o', n = h x v, a_u = (v x n) / (h . (v x n)),
+// a_v = (n x h) / (v . (n x h)) component by component, then L . n.
+int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_colour, const void* d_aov,
+                                const rt3_camera* prev_cam, const void* d_prev_history, const rt3_temporal_params* p, void* d_out,
+                                void* d_out_history, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = temporal_checks(ctx, w, h, cam, d_colour, d_aov, prev_cam, d_prev_history, p, d_out, d_out_history);
+    if (rc) return rc;
+    if (((uintptr_t)d_colour | (uintptr_t)d_aov | (uintptr_t)d_prev_history | (uintptr_t)d_out | (uintptr_t)d_out_history) % 16u != 0)
+        return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
+    const size_t npix = (size_t)w * h;
+    TemporalLaunch T{};
+    T.base = DenoiseLaunch{ w, h, p->spatial.iterations, p->spatial.normal_power, p->spatial.sigma_luminance, p->spatial.sigma_depth,
+                            d_colour, d_aov, d_out, nullptr };
+    std::memcpy(T.cam, cam, sizeof(rt3_camera));
+    if (prev_cam) {
+        const float* hh = prev_cam->horizontal;
+        const float* vv = prev_cam->vertical;
+        float vn[3], nh[3];
+        for (int i = 0; i < 3; i++) { T.prev_o[i] = prev_cam->origin[i]; T.prev_l[i] = prev_cam->lower_left_corner[i] - prev_cam->origin[i]; }
+        cross3(hh, vv, T.prev_n);
+        cross3(vv, T.prev_n, vn);
+        const float du = dot3h(hh, vn);
+        for (int i = 0; i < 3; i++) T.a_u[i] = vn[i] / du;
+        cross3(T.prev_n, hh, nh);
+        const float dv = dot3h(vv, nh);
+        for (int i = 0; i < 3; i++) T.a_v[i] = nh[i] / dv;
+        T.ln = dot3h(T.prev_l, T.prev_n);
+        T.has_prev = 1;
+        T.same_cam = std::memcmp(prev_cam, cam, sizeof(rt3_camera)) == 0;
+    }
+    T.alpha = p->alpha; T.moments_alpha = p->moments_alpha; T.depth_tolerance = p->depth_tolerance; T.normal_tolerance = p->normal_tolerance;
+    T.prev_history = d_prev_history;
+    T.out_history = d_out_history;
+    RT3_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
+    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));    // the scratch is the context's
+    if ((rc = ensure(ctx, &ctx->d_dn, &ctx->dn_entries, 3 * npix + (npix + 3) / 4))) return rc;
+    T.base.scratch = ctx->d_dn;
+    RT3_HIP(temporal_launch(T, stream));
+    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
+    return 0;
+}
+
+// The host form: colour, AOVs, both histories and the result on the device in d_dnh (11 float4 per pixel).
+int rt3_denoise_temporal(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
+                         const rt3_camera* prev_cam, const rt3_history* prev_history, const rt3_temporal_params* p, float* out,
+                         rt3_history* out_history) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = temporal_checks(ctx, w, h, cam, colour, aov, prev_cam, prev_history, p, out, out_history);
+    if (rc) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)w * h;
+    if ((rc = ensure(ctx, &ctx->d_dnh, &ctx->dnh_entries, 11 * npix))) return rc;
+    float4* const dc = ctx->d_dnh;
+    float4* const da = dc + npix;
+    float4* const dprev = da + 3 * npix;
+    float4* const dhist = dprev + 3 * npix;
+    float4* const dout = dhist + 3 * npix;
+    RT3_HIP(hipMemcpyAsync(dc, colour, npix * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    RT3_HIP(hipMemcpyAsync(da, aov, npix * sizeof(rt3_aov), hipMemcpyHostToDevice, ctx->stream));
+    if (prev_history) RT3_HIP(hipMemcpyAsync(dprev, prev_history, npix * sizeof(rt3_history), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = rt3_denoise_temporal_device(ctx, w, h, cam, dc, da, prev_cam, prev_history ? dprev : nullptr, p, dout, dhist, ctx->stream))) return rc;
+    RT3_HIP(hipMemcpyAsync(out, dout, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipMemcpyAsync(out_history, dhist, npix * sizeof(rt3_history), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+static_assert(sizeof(rt3_history) == 48, "rt3.h: rt3_history");
+static_assert(sizeof(rt3_temporal_params) == 32, "rt3.h: rt3_temporal_params");
 
 int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {
     if (!ctx || !out) return RT3_E_ARG;

@@ -356,6 +356,24 @@ std::vector<float> HipRenderer::denoise(Camera& camera, const rt3_denoise_params
     return out;
 }
 
+std::vector<float> HipRenderer::denoise_temporal(Camera& camera, const rt3_temporal_params& params, History& history) const {
+    const std::vector<float> colour = hdr();
+    if (camera.w() != last_w || camera.h() != last_h) throw Fatal("denoise_temporal: the camera's frame size differs from the last render's");
+    const std::vector<rt3_aov> guides = aov(camera);
+    const size_t npix = (size_t)last_w * last_h;
+    const bool have = !history.records.empty();
+    if (have && history.records.size() != npix) throw Fatal("denoise_temporal: the history's frame size differs from the last render's");
+    const rt3_camera cam = camera.wire();
+    std::vector<float> out(colour.size());
+    std::vector<rt3_history> next(npix);
+    if (rt3_denoise_temporal(ctx[0], last_w, last_h, &cam, colour.data(), guides.data(), have ? &history.camera : nullptr,
+                             have ? history.records.data() : nullptr, &params, out.data(), next.data()) != 0)
+        throw Fatal(rt3_last_error(ctx[0]));
+    history.records.swap(next);
+    history.camera = cam;
+    return out;
+}
+
 rt3_stats HipRenderer::stats() const {
     rt3_stats s;
     if (rt3_get_stats(ctx[0], &s) != 0) throw Fatal(rt3_last_error(ctx[0]));

@@ -5,7 +5,9 @@
 // Kept: -f/--format png|ppm (default png), -W/--width (800), -H/--height (600), -h/--help, first positional =
 // output path (later ones ignored), value forms `-W 400`, `-W400`, `--width 400`; exit code 0 after help, -1 on a
 // usage error, -1 on a fatal backend error.  Fixed: `--key=value`, which the reference mis-parses (Main.cpp:110).
-// Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr, --denoise (PFM files).
+// Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr, --denoise (PFM files),
+// --frames and --orbit (a sequence, denoised temporally).
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -30,6 +32,9 @@ struct Options {
     bool gpu_prerender = false, dump_scene = false;
     std::string aov_prefix, hdr_path;                              // Mode X: first-hit AOVs / the linear beauty as PFM files
     std::string denoise_path;                                      // Mode X: the denoised linear frame as a PFM file
+    uint32_t frames = 1;                                           // Mode X: frames of a sequence (frame k renders with seed + k)
+    float orbit = 0.0f;                                            // look-at scenes: degrees the look-from point turns per frame
+    bool have_orbit = false;
 };
 
 void print_usage(const char* exe) {
@@ -47,7 +52,10 @@ void print_usage(const char* exe) {
               << "\t   --dump-scene\tParse the --scene file, print its entities and exit.\n"
               << "\t   --aov\tMode X: also write the first-hit AOVs as PREFIX.albedo.pfm, PREFIX.normal.pfm and PREFIX.depth.pfm.\n"
               << "\t   --hdr\tMode X: also write the linear (float) frame to this path as a 3-channel PFM.\n"
-              << "\t   --denoise\tMode X: also write the denoised linear frame (a-trous, AOV-guided) to this path as a 3-channel PFM.\n"
+              << "\t   --denoise\tMode X: also write the denoised linear frame (a-trous, AOV-guided) to this path as a 3-channel PFM;\n"
+              << "\t\t\twith --frames N > 1, write PREFIX.<k>.pfm for every frame k, denoised temporally.\n"
+              << "\t   --frames\tMode X: render a sequence of N frames, frame k with seed + k; the image written is the last (default: 1).\n"
+              << "\t   --orbit\tweekend / stress100k: turn the look-from point by k * DEG degrees about the vertical axis through the look-at point.\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -86,7 +94,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         if (key == "--dump-scene") { opt.dump_scene = true; continue; }
         const bool known = key == "-f" || key == "--format" || key == "-W" || key == "--width" || key == "-H" || key == "--height" ||
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
-                           key == "--aov" || key == "--hdr" || key == "--denoise";
+                           key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -108,6 +116,16 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         else if (key == "--aov") opt.aov_prefix = value;
         else if (key == "--hdr") opt.hdr_path = value;
         else if (key == "--denoise") opt.denoise_path = value;
+        else if (key == "--frames") { if (!parse_u32(value, "frames", "Frames", &opt.frames)) return -1; }
+        else if (key == "--orbit") {
+            char* end = nullptr;
+            const double deg = std::strtod(value.c_str(), &end);
+            if (end == value.c_str() || *end != '\0' || !std::isfinite(deg) || !std::isfinite((float)deg)) {
+                std::cerr << "Invalid orbit '" << value << "'" << std::endl;
+                return -1;
+            }
+            opt.orbit = (float)deg; opt.have_orbit = true;
+        }
         else opt.scene = value;
     }
     if (opt.output_path.empty() && !opt.dump_scene) { std::cerr << "No output path given." << std::endl; return -1; }
@@ -119,6 +137,15 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     }
     if (mode_r && !opt.denoise_path.empty()) {
         std::cerr << "--denoise needs the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
+    if (opt.frames == 0) { std::cerr << "--frames must be at least 1." << std::endl; return -1; }
+    if (mode_r && opt.frames > 1) {
+        std::cerr << "--frames needs the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
+    if (opt.have_orbit && opt.scene != "weekend" && opt.scene != "stress100k") {
+        std::cerr << "--orbit needs a look-at camera (--scene weekend or stress100k)." << std::endl;
         return -1;
     }
     return 1;
@@ -176,6 +203,7 @@ int main(int argc, const char** argv) {
         PathOptions path;
         path.spp = opt.spp; path.max_depth = opt.depth ? opt.depth : 1; path.seed = opt.seed;
         const float aspect = (float)opt.width / (float)opt.height;
+        struct { bool on = false; glm::vec3 from, at, vup; float vfov = 0.0f, focus = 0.0f; } la;     // the look-at scenes' camera
 
         if (opt.scene == "builtin") {                               // Main.cpp:272, :280-283
             cam.update(opt.width, opt.height, 2.0f, aspect * 2.0f, 2.0f);
@@ -189,11 +217,11 @@ int main(int argc, const char** argv) {
             sphere_scene(renderer, [](float* c, rt3_material* m, uint32_t cap) { return rt3_scene_three_spheres(c, m, cap); });
             path.flags = RT3_FLAG_GAMMA2;
         } else if (opt.scene == "weekend") {
-            cam.look_at(opt.width, opt.height, { 13.0f, 2.0f, 3.0f }, { 0.0f, 0.0f, 0.0f }, { 0.0f, 1.0f, 0.0f }, 20.0f, 10.0f);
+            la.on = true; la.from = { 13.0f, 2.0f, 3.0f }; la.at = { 0.0f, 0.0f, 0.0f }; la.vup = { 0.0f, 1.0f, 0.0f }; la.vfov = 20.0f; la.focus = 10.0f;
             sphere_scene(renderer, [](float* c, rt3_material* m, uint32_t cap) { return rt3_scene_weekend(42, c, m, cap); });
             path.flags = RT3_FLAG_GAMMA2; path.lens_radius = 0.05f;
         } else if (opt.scene == "stress100k") {
-            cam.look_at(opt.width, opt.height, { 0.0f, 8.0f, 12.0f }, { 0.0f, 6.0f, -50.0f }, { 0.0f, 1.0f, 0.0f }, 45.0f, 1.0f);
+            la.on = true; la.from = { 0.0f, 8.0f, 12.0f }; la.at = { 0.0f, 6.0f, -50.0f }; la.vup = { 0.0f, 1.0f, 0.0f }; la.vfov = 45.0f; la.focus = 1.0f;
             sphere_scene(renderer, [](float* c, rt3_material* m, uint32_t cap) { return rt3_scene_stress(100000, 43, c, m, cap); });
             path.flags = RT3_FLAG_GAMMA2;
         } else if (opt.scene == "cornell") {
@@ -216,8 +244,26 @@ int main(int argc, const char** argv) {
         }
         const bool from_file = opt.scene.size() > 6 && opt.scene.compare(opt.scene.size() - 6, 6, ".scene") == 0;
         if (opt.scene != "builtin" && !from_file && path.spp == 0) path.spp = 16;   // the analytic scenes only exist in Mode X
-        renderer.configure(path);
-        renderer.render(cam);
+        const uint32_t seed0 = path.seed;
+        const bool temporal = opt.frames > 1 && !opt.denoise_path.empty();
+        const rt3_temporal_params tp{ { 5, 128, 4.0f, 1.0f }, 0.2f, 0.2f, 2.0f, 0.9f };       // the defaults of DESIGN.md 4.11 and 4.12
+        History history;
+        for (uint32_t k = 0; k < opt.frames; k++) {
+            if (la.on) {                                             // frame k: the look-from point turned by k * orbit about the vertical axis
+                const double a = (double)k * (double)opt.orbit * 3.14159265358979323846 / 180.0, c = std::cos(a), sn = std::sin(a);
+                const double dx = (double)la.from.x - la.at.x, dz = (double)la.from.z - la.at.z;
+                const glm::vec3 from(la.at.x + (c * dx + sn * dz), (double)la.from.y, la.at.z + (c * dz - sn * dx));
+                cam.look_at(opt.width, opt.height, k == 0 ? la.from : from, la.at, la.vup, la.vfov, la.focus);
+            }
+            path.seed = seed0 + k;
+            renderer.configure(path);
+            renderer.render(cam);
+            if (temporal) {
+                const std::vector<float> out = renderer.denoise_temporal(cam, tp, history);
+                const std::string name = opt.denoise_path + "." + std::to_string(k) + ".pfm";
+                if (rt3_frame_to_pfm(out.data(), cam.w(), cam.h(), 3, 4, name.c_str()) != 0) throw Fatal("Could not write '" + name + "'");
+            }
+        }
 
         const rt3_stats st = renderer.stats();
         std::cerr << "rendered " << opt.width << "x" << opt.height << (path.spp ? " x " + std::to_string(path.spp) + " spp" : " (mode R)")
@@ -239,7 +285,7 @@ int main(int argc, const char** argv) {
                     throw Fatal("Could not write '" + out + "'");
             }
         }
-        if (!opt.denoise_path.empty()) {
+        if (!opt.denoise_path.empty() && !temporal) {
             const rt3_denoise_params dp{ 5, 128, 4.0f, 1.0f };                     // the defaults of DESIGN.md 4.11
             const std::vector<float> out = renderer.denoise(cam, dp);
             if (rt3_frame_to_pfm(out.data(), w, h, 3, 4, opt.denoise_path.c_str()) != 0) throw Fatal("Could not write '" + opt.denoise_path + "'");

@@ -19,6 +19,13 @@ public:
     virtual void render(Camera& camera) const = 0;
 };
 
+// The caller-owned state of a temporal denoising sequence (rt3_denoise_temporal): the last frame's history records and camera; empty
+// records = the first frame.
+struct History {
+    std::vector<rt3_history> records;
+    rt3_camera camera{};
+};
+
 // Mode-X knobs the reference API has no place for (spp / depth / seed ...); spp == 0 means Mode R.
 struct PathOptions {
     uint32_t spp = 0, max_depth = 50, seed = 1, flags = 0;
@@ -44,6 +51,9 @@ public:
     std::vector<float> hdr() const;
     // Mode X only: the linear frame of the last render denoised on device 0 (rt3_denoise), guided by aov(camera); (r, g, b, 0) per pixel
     std::vector<float> denoise(Camera& camera, const rt3_denoise_params& params) const;
+    // Mode X only: the same frame through the temporal denoiser (rt3_denoise_temporal) with `history` as the previous frame's, which the
+    // call replaces by this frame's; (r, g, b, 0) per pixel
+    std::vector<float> denoise_temporal(Camera& camera, const rt3_temporal_params& params, History& history) const;
     size_t faces() const { return n_faces; }
     size_t spheres() const { return n_spheres; }
 
