@@ -48,6 +48,36 @@
 // ======================================================================================================
 // Host side of the device context
 // ======================================================================================================
+// A device buffer of n elements of T that the context owns: freed when it is replaced and when the context is deleted.  A failed allocation
+// leaves it null with capacity 0 and reports through ctx->err (alloc / upload below).
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept { swap(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept { swap(o); return *this; }      // (what this held leaves with o)
+    ~DevBuf() { reset(); }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t size() const { return n_; }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }
+    int alloc(rt3_ctx* ctx, size_t n);                              // exactly n elements (n = 0: none)
+    int ensure(rt3_ctx* ctx, size_t n) { return n_ >= n && p_ ? 0 : alloc(ctx, n); }     // grows only
+    int upload(rt3_ctx* ctx, const std::vector<T>& v);              // exactly v (empty: none)
+private:
+    void swap(DevBuf& o) { std::swap(p_, o.p_); std::swap(n_, o.n_); }
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// The rows of the multi-level filter of one primitive class, built by build_rows: the members' (cx, cy, cz, r^2) records in
+// group order and the primitive index of each, the leaf groups' bounds, the rows' bounds in f32 (rows behind a ray are dropped before their
+// leaves are tested) and as fragments, and the super-rows of kSuper rows (four levels) as f32 records and as fragments.
+struct FilterRows {
+    DevBuf<float4> grp; DevBuf<uint32_t> perm; DevBuf<float4> leaf; DevBuf<float4> rowb; DevBuf<u32x4> gfrag; DevBuf<float4> srowb; DevBuf<u32x4> sfrag;
+    uint32_t n_groups = 0, n_leaves = 0, n_super = 0;              // rows the matrix filter scans, leaf groups, super-rows
+};
+
 struct rt3_ctx {
     int device = 0;
     int num_cu = 0;
@@ -56,39 +86,32 @@ struct rt3_ctx {
 
     // mesh
     uint32_t n_faces = 0;
-    float4* d_tri = nullptr; float4* d_tri_mat = nullptr; uint32_t* d_tri_kind = nullptr; float4* d_tri_bound = nullptr; u32x4* d_tri_frag = nullptr;
-    // merged entity buffers on the device (GFace[] / vec4[] as the reference keeps them), filled by rt3_mesh_*
-    rt3_gface* d_gfaces = nullptr; float4* d_verts = nullptr; uint32_t cap_gfaces = 0, cap_verts = 0;
-    rt3_material* d_face_mats_in = nullptr; uint32_t* d_error = nullptr;
+    DevBuf<float4> d_tri, d_tri_mat, d_tri_bound; DevBuf<uint32_t> d_tri_kind; DevBuf<u32x4> d_tri_frag;
+    // merged entity buffers on the device (GFace[] / vec4[] as the reference keeps them), filled by rt3_mesh_*; their sizes bound rt3_mesh_put
+    DevBuf<rt3_gface> d_gfaces; DevBuf<float4> d_verts;
+    DevBuf<rt3_material> d_face_mats_in; DevBuf<uint32_t> d_error;
     // spheres
     uint32_t n_sph = 0;
-    float4* d_sph = nullptr; uint32_t* d_sph_frag = nullptr; uint32_t* d_sph_frag32 = nullptr; float sph_centre[3] = { 0.0f, 0.0f, 0.0f }; uint32_t n_direct = 0; uint32_t direct[4] = { 0, 0, 0, 0 }; float tri_centre[3] = { 0.0f, 0.0f, 0.0f }; uint32_t* d_box = nullptr; uint32_t* d_tri_frag_r = nullptr; float* d_sph_invr = nullptr; float4* d_sph_mat = nullptr; uint32_t* d_sph_kind = nullptr;
+    DevBuf<float4> d_sph; DevBuf<uint32_t> d_sph_frag, d_sph_frag32; float sph_centre[3] = { 0.0f, 0.0f, 0.0f }; uint32_t n_direct = 0; uint32_t direct[4] = { 0, 0, 0, 0 }; float tri_centre[3] = { 0.0f, 0.0f, 0.0f }; DevBuf<uint32_t> d_box; DevBuf<u32x4> d_tri_frag_r; DevBuf<float> d_sph_invr; DevBuf<float4> d_sph_mat; DevBuf<uint32_t> d_sph_kind;
 
-    // group rows of the two-level filter: faces in face order, spheres in the order of a spatial median split
-    u32x4* d_tri_gfrag = nullptr; float4* d_tri_grp = nullptr; uint32_t* d_tri_perm = nullptr; uint32_t n_tri_groups = 0;
-    u32x4* d_sph_gfrag = nullptr; float4* d_sph_grp = nullptr; uint32_t* d_sph_perm = nullptr; uint32_t n_sph_groups = 0;
-    float4* d_tri_leaf = nullptr; float4* d_sph_leaf = nullptr; uint32_t n_tri_leaves = 0, n_sph_leaves = 0;      // three-level filter: the leaf groups' bounds
-    float4* d_tri_rowb = nullptr; float4* d_sph_rowb = nullptr;    // ... and the rows' own bounds in f32 (rows behind a ray are dropped before their leaves are tested)
-    float4* d_tri_rec = nullptr;                                   // the faces' records in group order (the exact test of the multi-level filter reads these)
-    u32x4* d_tri_sfrag = nullptr; u32x4* d_sph_sfrag = nullptr; float4* d_tri_srowb = nullptr; float4* d_sph_srowb = nullptr;   // four levels: super-rows of kSuper rows
-    uint32_t n_tri_super = 0, n_sph_super = 0;
-    uint32_t* d_strips = nullptr; size_t strip_entries = 0;          // deferred member tests: kStripPairs pairs per wave of the grid
+    // rows of the multi-level filter: faces and spheres, each in the order of a spatial median split
+    FilterRows tri, sph;
+    DevBuf<float4> d_tri_rec;                                       // the faces' records in group order (the exact test of the multi-level filter reads these)
+    DevBuf<uint32_t> d_strips;                                      // deferred member tests: kStripPairs pairs per wave of the grid
 
     // work buffers
-    Rgb* d_rad = nullptr; size_t rad_entries = 0;
-    float4* d_accum = nullptr; size_t accum_entries = 0;
-    float4* d_accum_sq = nullptr; size_t accum_sq_entries = 0;      // RT3_FLAG_VARIANCE: per-pixel sums of squares
-    uint32_t* d_out = nullptr; size_t out_entries = 0;
-    float4* d_qrays = nullptr; size_t qrays_entries = 0;           // batched ray queries, host forms: the rays and the results on the device
-    uint4* d_qout = nullptr; size_t qout_entries = 0;
-    float4* d_arays = nullptr; size_t arays_entries = 0;           // first-hit AOVs (rt3_render_aov*): one batch's camera rays and their hits,
-    uint4* d_ahits = nullptr; size_t ahits_entries = 0;            // and the per-pixel running sums (three planes; not d_accum, which belongs to
-    float4* d_aacc = nullptr; size_t aacc_entries = 0;             // the progressive render)
-    float4* d_hout = nullptr; size_t hout_entries = 0;             // host forms of rt3_camera_rays / rt3_render_aov / rt3_accum_resolve: the results on the device
-    float4* d_dn = nullptr; size_t dn_entries = 0;                 // denoiser scratch (rt3_denoise*): two (I, v) planes, the guide plane, the depth slopes
-    float4* d_dnh = nullptr; size_t dnh_entries = 0;               // host forms of rt3_denoise*: colour, AOVs, histories and the results on the device
-    uint32_t* d_work = nullptr;                                     // [0] work counter
-    unsigned long long* d_casts = nullptr;
+    DevBuf<Rgb> d_rad;
+    DevBuf<float4> d_accum;
+    DevBuf<float4> d_accum_sq;                                      // RT3_FLAG_VARIANCE: per-pixel sums of squares
+    DevBuf<float4> d_arays;                                         // first-hit AOVs (rt3_render_aov*): one batch's camera rays and their hits,
+    DevBuf<uint4> d_ahits;                                          // and the per-pixel running sums (three planes; not d_accum, which belongs to
+    DevBuf<float4> d_aacc;                                          // the progressive render)
+    DevBuf<float4> d_dn;                                            // denoiser scratch (rt3_denoise*): two (I, v) planes, the guide plane, the depth slopes
+    // The host forms' inputs and results on the device, each carved out at float4 offsets.  Shared by all of them: each one ends in
+    // hipStreamSynchronize(ctx->stream), and no device form touches it.
+    DevBuf<float4> stage;
+    DevBuf<uint32_t> d_work;                                        // [0] work counter
+    DevBuf<unsigned long long> d_casts;
     uint64_t rad_cap_bytes = 16ull << 30;
     bool force_plain_mode_r = false;                                // tests: compare the two Mode-R kernels
     bool force_brute = false;                                       // tests / fuzzers: unfiltered Mode-X kernel
@@ -113,10 +136,6 @@ struct rt3_ctx {
     // what the render in flight will report once its last launch has been issued (committed only then)
 };
 
-namespace {
-
-thread_local std::string g_create_error;
-
 #define RT3_HIP(call)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (call);                                                                         \
@@ -126,24 +145,26 @@ thread_local std::string g_create_error;
         }                                                                                               \
     } while (0)
 
-int fail(rt3_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
+template <typename T>
+int DevBuf<T>::alloc(rt3_ctx* ctx, size_t n) {
+    reset();
+    if (n) RT3_HIP(hipMalloc((void**)&p_, n * sizeof(T)));
+    n_ = n;
+    return 0;
+}
+template <typename T>
+int DevBuf<T>::upload(rt3_ctx* ctx, const std::vector<T>& v) {
+    const int rc = alloc(ctx, v.size());
+    if (rc) return rc;
+    if (!v.empty()) RT3_HIP(hipMemcpy(p_, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
 
-template <typename T>
-int upload(rt3_ctx* ctx, T** dst, const std::vector<T>& src) {
-    if (*dst) { RT3_HIP(hipFree(*dst)); *dst = nullptr; }
-    if (src.empty()) return 0;
-    RT3_HIP(hipMalloc((void**)dst, src.size() * sizeof(T)));
-    RT3_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-template <typename T>
-int ensure(rt3_ctx* ctx, T** buf, size_t* have, size_t want) {
-    if (*have >= want && *buf) return 0;
-    if (*buf) { RT3_HIP(hipFree(*buf)); *buf = nullptr; *have = 0; }
-    RT3_HIP(hipMalloc((void**)buf, want * sizeof(T)));
-    *have = want;
-    return 0;
-}
+namespace {
+
+thread_local std::string g_create_error;
+
+int fail(rt3_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
 
 CamDev cam_dev(const rt3_camera* c) {
     return CamDev{ c->origin[0], c->origin[1], c->origin[2], c->horizontal[0], c->horizontal[1], c->horizontal[2],
@@ -374,6 +395,53 @@ std::vector<uint32_t> face_group_order(const float4* bounds, uint32_t n, uint32_
     return ids;
 }
 
+// The rows of the multi-level filter over `members` ((cx, cy, cz, r^2) per primitive) in the group order `order`, groups of
+// `group`: leaf bounds, row fragments, row bounds, super-row fragments and bounds.  Filter coordinates are about the centre of the vertex box
+// `box` (faces) or, box = nullptr, about `centre` (spheres).  R is emptied first and its counts are set after the last launch has been issued,
+// so a failure leaves no rows.  The launches are on ctx->stream; the caller synchronises.
+int build_rows(rt3_ctx* ctx, FilterRows& R, const float4* members, const std::vector<uint32_t>& order, uint32_t group, const uint32_t* box,
+               const float centre[3]) {
+    R = FilterRows();
+    std::vector<float4> grp(order.size(), kPadSphere);
+    for (size_t k = 0; k < order.size(); k++) if (order[k] != 0xFFFFFFFFu) grp[k] = members[order[k]];
+    int rc;
+    if ((rc = R.grp.upload(ctx, grp)) || (rc = R.perm.upload(ctx, order))) return rc;
+    const uint32_t n_leaves = (uint32_t)(order.size() / group), n_groups = n_leaves / kSuper;
+    if (n_groups == 0) return 0;                                    // (spheres: every one is on the direct list or unusable)
+    const float cx = centre[0], cy = centre[1], cz = centre[2];
+    const float4* row_members = R.grp;
+    uint32_t row_entries = (uint32_t)order.size(), row_group = group, n_super = 0;
+    if (kSuper > 1) {                                               // three levels: the leaves' bounds are records of their own, a row bounds kSuper of them
+        if ((rc = R.leaf.alloc(ctx, n_leaves))) return rc;
+        hipLaunchKernelGGL(k_group_bounds, dim3((n_leaves + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, row_members, row_entries, group,
+                           n_leaves, box, cx, cy, cz, R.leaf.get());
+        RT3_HIP(hipGetLastError());
+        row_members = R.leaf; row_entries = n_leaves; row_group = kSuper;
+    }
+    const uint32_t n_group_rows = (n_groups + 31u) / 32u * 32u;
+    if ((rc = R.gfrag.alloc(ctx, (size_t)n_group_rows * 4))) return rc;
+    hipLaunchKernelGGL(k_group_frags, dim3((n_group_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, row_members, row_entries, row_group,
+                       n_group_rows, box, cx, cy, cz, R.gfrag.get());
+    RT3_HIP(hipGetLastError());
+    if (kSuper > 1) {                                               // the same rows as f32 records
+        if ((rc = R.rowb.alloc(ctx, n_group_rows))) return rc;
+        hipLaunchKernelGGL(k_group_bounds, dim3((n_group_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, row_members, row_entries, row_group,
+                           n_group_rows, box, cx, cy, cz, R.rowb.get());
+        RT3_HIP(hipGetLastError());
+        // four levels: super-rows of kSuper rows, as fragments for the matrix filter and as f32 records
+        n_super = (n_groups + kSuper - 1u) / kSuper;
+        const uint32_t n_super_rows = (n_super + 31u) / 32u * 32u;
+        if ((rc = R.sfrag.alloc(ctx, (size_t)n_super_rows * 4)) || (rc = R.srowb.alloc(ctx, n_super_rows))) return rc;
+        hipLaunchKernelGGL(k_group_frags, dim3((n_super_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, R.rowb.get(), n_group_rows,
+                           kSuper, n_super_rows, box, cx, cy, cz, R.sfrag.get());
+        hipLaunchKernelGGL(k_group_bounds, dim3((n_super_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, R.rowb.get(), n_group_rows,
+                           kSuper, n_super_rows, box, cx, cy, cz, R.srowb.get());
+        RT3_HIP(hipGetLastError());
+    }
+    R.n_leaves = n_leaves; R.n_groups = n_groups; R.n_super = n_super;
+    return 0;
+}
+
 bool row_owned(const rt3_params* p, uint32_t y) {
     if (p->tile_count <= 1) return true;
     return ((y / p->tile_rows) % p->tile_count) == p->tile_index;
@@ -404,6 +472,13 @@ int check_params(rt3_ctx* ctx, const rt3_params* p) {
     if (p->spp < 1 || p->max_depth < 1) return fail(ctx, RT3_E_ARG, "spp and max_depth must be >= 1");
     if (p->tile_count > 1 && (p->tile_rows == 0 || p->tile_index >= p->tile_count))
         return fail(ctx, RT3_E_ARG, "bad tile_rows / tile_index / tile_count");
+    return 0;
+}
+
+// A scene the trace kernels can take: renders and queries need one, and the pair lists address at most 2^kPairLaneShift - 32 rows.
+int check_scene(rt3_ctx* ctx) {
+    if (ctx->n_sph == 0 && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "no scene: call rt3_set_spheres / rt3_set_mesh first");
+    if (ctx->n_faces >= (1u << kPairLaneShift) - 32u || ctx->n_sph >= (1u << kPairLaneShift) - 32u) return fail(ctx, RT3_E_ARG, "too many primitives");
     return 0;
 }
 
@@ -498,11 +573,11 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
     const bool single_k64 = !query && mfma_single && getenv("RT3_MFMA_K64") != nullptr;
     const bool sph_lds = has_sph && ctx->n_sph <= kSphLdsMax;
     const bool grouped = kGroupTri > 1 && kGroupSph > 1 && (query || (!ctx->force_flat && !getenv("RT3_NO_GROUPS")));
-    A.n_tri_rows = grouped ? ctx->n_tri_groups : ctx->n_faces;
-    A.n_sph_rows = grouped ? ctx->n_sph_groups : ctx->n_sph;
-    A.sph_grp = ctx->d_sph_grp; A.sph_perm = ctx->d_sph_perm; A.tri_grp = ctx->d_tri_grp; A.tri_perm = ctx->d_tri_perm; A.tri_rec = ctx->d_tri_rec;
-    A.tri_leaf = ctx->d_tri_leaf; A.sph_leaf = ctx->d_sph_leaf; A.n_tri_leaves = ctx->n_tri_leaves; A.n_sph_leaves = ctx->n_sph_leaves;
-    A.tri_rowb = ctx->d_tri_rowb; A.sph_rowb = ctx->d_sph_rowb;
+    A.n_tri_rows = grouped ? ctx->tri.n_groups : ctx->n_faces;
+    A.n_sph_rows = grouped ? ctx->sph.n_groups : ctx->n_sph;
+    A.sph_grp = ctx->sph.grp; A.sph_perm = ctx->sph.perm; A.tri_grp = ctx->tri.grp; A.tri_perm = ctx->tri.perm; A.tri_rec = ctx->d_tri_rec;
+    A.tri_leaf = ctx->tri.leaf; A.sph_leaf = ctx->sph.leaf; A.n_tri_leaves = ctx->tri.n_leaves; A.n_sph_leaves = ctx->sph.n_leaves;
+    A.tri_rowb = ctx->tri.rowb; A.sph_rowb = ctx->sph.rowb;
     T.mfma_blocks = (ctx->n_sph + 31u) / 32u;
     bool resident = false;
     uint32_t levels = 0;                                            // k_trace_levels: 3 | 4
@@ -514,12 +589,12 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
                            : (size_t)T.mfma_blocks * (2048 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes + (size_t)kMB * 8 + (size_t)(kMB / 64) * kPairCap * 4;
         T.block = kMB;
         T.single = single_k64 ? k_trace_mfma : query ? k_trace_mfma32<true> : k_trace_mfma32<>;
-        T.frag_a = (const u32x4*)(single_k64 ? (const void*)ctx->d_sph_frag : (const void*)ctx->d_sph_frag32);
+        T.frag_a = (const u32x4*)(single_k64 ? ctx->d_sph_frag.get() : ctx->d_sph_frag32.get());
     } else if (use_mfma) {
         // the two-level filter (rows = groups of primitives) unless RT3_NO_GROUPS=1 asks for the flat one (A/B reference, tests)
         constexpr uint32_t SUP = kSuper;
         const uint32_t row_blocks = (has_tri ? (A.n_tri_rows + 31u) / 32u : 0u) + (has_sph ? (A.n_sph_rows + 31u) / 32u : 0u);
-        const uint32_t super_blocks = (has_tri ? (ctx->n_tri_super + 31u) / 32u : 0u) + (has_sph ? (ctx->n_sph_super + 31u) / 32u : 0u);
+        const uint32_t super_blocks = (has_tri ? (ctx->tri.n_super + 31u) / 32u : 0u) + (has_sph ? (ctx->sph.n_super + 31u) / 32u : 0u);
         // While the rows of 64 fit in LDS (<= kResidentBlocks row blocks, 112 000 primitives: both BASELINE scenes) k_trace_mfma_tiled's resident three-level
         // form runs; beyond, k_trace_levels (rt3_level_filter.hpp) with FOUR levels — the matrix cores scan super-rows of 512, resident up to 570 000
         // primitives, through a tile after that.  RT3_LEVELS=3|4 forces k_trace_levels with that many levels, RT3_OLD_GROUPS=1 the nested form (A/B, tests)
@@ -530,8 +605,8 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
             levels = force_levels ? (atoi(force_levels) == 4 ? 4u : 3u) : 4u;
             const uint32_t top_blocks = levels == 4 ? super_blocks : row_blocks;
             resident = !no_res_env && top_blocks <= lev_resident_blocks(levels);
-            A.n_tri_top = levels == 4 ? ctx->n_tri_super : ctx->n_tri_groups; A.n_sph_top = levels == 4 ? ctx->n_sph_super : ctx->n_sph_groups;
-            A.tri_topb = levels == 4 ? ctx->d_tri_srowb : ctx->d_tri_rowb; A.sph_topb = levels == 4 ? ctx->d_sph_srowb : ctx->d_sph_rowb;
+            A.n_tri_top = levels == 4 ? ctx->tri.n_super : ctx->tri.n_groups; A.n_sph_top = levels == 4 ? ctx->sph.n_super : ctx->sph.n_groups;
+            A.tri_topb = levels == 4 ? ctx->tri.srowb : ctx->tri.rowb; A.sph_topb = levels == 4 ? ctx->sph.srowb : ctx->sph.rowb;
             if (query) T.tiled = levels == 4 ? (resident ? levels_kernel<true, 4, true>(has_tri, has_sph, ref) : levels_kernel<true, 4, false>(has_tri, has_sph, ref))
                                              : (resident ? levels_kernel<true, 3, true>(has_tri, has_sph, ref) : levels_kernel<true, 3, false>(has_tri, has_sph, ref));
             else T.tiled = levels == 4 ? (resident ? levels_kernel<false, 4, true>(has_tri, has_sph, ref) : levels_kernel<false, 4, false>(has_tri, has_sph, ref))
@@ -546,8 +621,8 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
             T.lds = resident ? (size_t)row_blocks * 2048u + (size_t)kBmBlocksRes * kTB * 4u + (size_t)kTB * 8u + (size_t)(kTB / 64u) * kPairCap * 4u * 3u : kTraceTiledLdsBytes;
         }
         T.block = kTB;
-        if (levels == 4) { T.frag_a = ctx->d_tri_sfrag; T.frag_b = ctx->d_sph_sfrag; }
-        else { T.frag_a = grouped ? ctx->d_tri_gfrag : ctx->d_tri_frag; T.frag_b = grouped ? ctx->d_sph_gfrag : (const u32x4*)ctx->d_sph_frag32; }
+        if (levels == 4) { T.frag_a = ctx->tri.sfrag; T.frag_b = ctx->sph.sfrag; }
+        else { T.frag_a = grouped ? ctx->tri.gfrag : ctx->d_tri_frag; T.frag_b = grouped ? ctx->sph.gfrag.get() : (const u32x4*)ctx->d_sph_frag32.get(); }
     } else {
         T.lds = sph_lds ? (size_t)ctx->n_sph * sizeof(float4) : 0;
         T.plain = has_tri ? (has_sph ? (sph_lds ? k_trace<true, true, true> : k_trace<true, true, false>)
@@ -560,7 +635,7 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
     if (T.per_cu < 1) return fail(ctx, RT3_E_DEVICE, "the trace kernel does not fit on a CU");
     T.per_cu = std::min(T.per_cu, 8);
     if (T.tiled && grouped) {                                       // one strip per wave of the largest grid this launch configuration can have
-        if ((rc = ensure(ctx, &ctx->d_strips, &ctx->strip_entries, (size_t)ctx->num_cu * T.per_cu * (kTB / 64u) * kStripPairs))) return rc;
+        if ((rc = ctx->d_strips.ensure(ctx, (size_t)ctx->num_cu * T.per_cu * (kTB / 64u) * kStripPairs))) return rc;
         A.pair_strips = ctx->d_strips;
     }
     T.mfma16 = T.tiled != nullptr || (mfma_single && !single_k64);
@@ -592,6 +667,43 @@ int issue_query(rt3_ctx* ctx, const TraceArgs& A, const TracePlan& T, uint32_t n
     launch_trace(T, A, trace_grid(ctx, T, n), stream);
     RT3_HIP(hipGetLastError());
     RT3_HIP(hipEventRecord(b, stream));
+    return 0;
+}
+
+// ---- What the entry points share.  rt3.h: a NULL stream is the context's own.
+hipStream_t stream_of(const rt3_ctx* ctx, void* stream_) { return stream_ ? (hipStream_t)stream_ : ctx->stream; }
+
+// d_rad, d_accum, the scratch and the counters belong to the context, not to a stream: whatever stream the previous call ran on, this one
+// starts behind it (a wait on the device; nothing if it is the same stream).  leave() marks where the next call starts.
+int enter(rt3_ctx* ctx, void* stream_, hipStream_t* stream) {
+    RT3_HIP(hipSetDevice(ctx->device));
+    *stream = stream_of(ctx, stream_);
+    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(*stream, ctx->ev_acc, 0));
+    return 0;
+}
+int leave(rt3_ctx* ctx, hipStream_t stream) {
+    RT3_HIP(hipEventRecord(ctx->ev_acc, stream));
+    ctx->ev_acc_recorded = true;
+    return 0;
+}
+
+// The calls rt3_get_stats reports on (Mode-X renders, queries, AOVs) issue their launches between these two; each clears ctx->rendered before
+// anything that can fail, and end_timed sets it once the last launch has been issued.  plan: nullptr when nothing was traced (no owned pixels).
+int begin_timed(rt3_ctx* ctx, hipStream_t stream) {
+    ctx->ev_used = 0;
+    RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
+    RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 128, stream));
+    return 0;
+}
+int end_timed(rt3_ctx* ctx, hipStream_t stream, uint64_t samples, const TracePlan* plan) {
+    RT3_HIP(hipEventRecord(ctx->ev_end, stream));
+    const int rc = leave(ctx, stream);
+    if (rc) return rc;
+    ctx->last_stream = stream;
+    ctx->last_samples = samples;
+    ctx->last_was_path = true;
+    if (plan) { ctx->last_mfma16 = plan->mfma16; ctx->last_filter_rows = plan->filter_rows; }
+    ctx->rendered = true;
     return 0;
 }
 
@@ -627,8 +739,8 @@ rt3_ctx* rt3_create(int device_id) {
     if ((e = hipSetDevice(device_id)) != hipSuccess || (e = hipGetDeviceProperties(&prop, device_id)) != hipSuccess ||
         (e = hipStreamCreate(&ctx->stream)) != hipSuccess || (e = hipEventCreate(&ctx->ev_begin)) != hipSuccess ||
         (e = hipEventCreate(&ctx->ev_end)) != hipSuccess || (e = hipEventCreateWithFlags(&ctx->ev_acc, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipMalloc((void**)&ctx->d_work, 64)) != hipSuccess || (e = hipMalloc((void**)&ctx->d_casts, 128)) != hipSuccess) {
-        g_create_error = std::string("rt3_create: ") + hipGetErrorString(e);
+        ctx->d_work.alloc(ctx, 16) || ctx->d_casts.alloc(ctx, 16)) {
+        g_create_error = "rt3_create: " + (e != hipSuccess ? std::string(hipGetErrorString(e)) : ctx->err);
         delete ctx;
         return nullptr;
     }
@@ -639,13 +751,7 @@ rt3_ctx* rt3_create(int device_id) {
 void rt3_destroy(rt3_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();
-    void* bufs[] = { ctx->d_gfaces, ctx->d_verts, ctx->d_face_mats_in, ctx->d_error, ctx->d_tri, ctx->d_tri_mat, ctx->d_tri_kind, ctx->d_tri_bound, ctx->d_tri_frag, ctx->d_sph, ctx->d_sph_frag, ctx->d_sph_frag32, ctx->d_sph_invr, ctx->d_sph_mat, ctx->d_sph_kind,
-                     ctx->d_rad, ctx->d_accum, ctx->d_accum_sq, ctx->d_out, ctx->d_work, ctx->d_casts, ctx->d_box, ctx->d_tri_frag_r,
-                     ctx->d_tri_gfrag, ctx->d_sph_gfrag, ctx->d_sph_grp, ctx->d_sph_perm, ctx->d_strips, ctx->d_tri_grp, ctx->d_tri_perm, ctx->d_tri_leaf, ctx->d_sph_leaf, ctx->d_tri_rowb, ctx->d_sph_rowb,
-                     ctx->d_tri_sfrag, ctx->d_sph_sfrag, ctx->d_tri_srowb, ctx->d_sph_srowb, ctx->d_tri_rec, ctx->d_qrays, ctx->d_qout,
-                     ctx->d_arays, ctx->d_ahits, ctx->d_aacc, ctx->d_hout, ctx->d_dn, ctx->d_dnh };
-    for (void* b : bufs) if (b) (void)hipFree(b);
+    (void)hipDeviceSynchronize();                                   // (the buffers are freed with the context)
     for (auto& p : ctx->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
@@ -672,14 +778,10 @@ int rt3_debug_force_plain_mode_r(rt3_ctx* ctx, int on) {
 int rt3_mesh_begin(rt3_ctx* ctx, uint32_t n_faces, uint32_t n_vertices) {
     if (!ctx) return RT3_E_ARG;
     RT3_HIP(hipSetDevice(ctx->device));
-    if (ctx->d_gfaces) { RT3_HIP(hipFree(ctx->d_gfaces)); ctx->d_gfaces = nullptr; }
-    if (ctx->d_verts) { RT3_HIP(hipFree(ctx->d_verts)); ctx->d_verts = nullptr; }
-    if (n_faces) RT3_HIP(hipMalloc((void**)&ctx->d_gfaces, (size_t)n_faces * sizeof(rt3_gface)));
-    if (n_vertices) RT3_HIP(hipMalloc((void**)&ctx->d_verts, (size_t)n_vertices * sizeof(float4)));
+    int rc;
+    if ((rc = ctx->d_gfaces.alloc(ctx, n_faces)) || (rc = ctx->d_verts.alloc(ctx, n_vertices))) return rc;
     if (n_faces) RT3_HIP(hipMemsetAsync(ctx->d_gfaces, 0, (size_t)n_faces * sizeof(rt3_gface), ctx->stream));
     if (n_vertices) RT3_HIP(hipMemsetAsync(ctx->d_verts, 0, (size_t)n_vertices * sizeof(float4), ctx->stream));
-    ctx->cap_gfaces = n_faces;
-    ctx->cap_verts = n_vertices;
     return 0;
 }
 
@@ -687,7 +789,7 @@ int rt3_mesh_put(rt3_ctx* ctx, const rt3_gface* faces, uint32_t n_faces, const f
                  uint32_t face_offset, uint32_t vertex_offset) {
     if (!ctx) return RT3_E_ARG;
     if ((n_faces && !faces) || (n_vertices && !vertices)) return fail(ctx, RT3_E_ARG, "faces / vertices is NULL");
-    if ((uint64_t)face_offset + n_faces > ctx->cap_gfaces || (uint64_t)vertex_offset + n_vertices > ctx->cap_verts)
+    if ((uint64_t)face_offset + n_faces > ctx->d_gfaces.size() || (uint64_t)vertex_offset + n_vertices > ctx->d_verts.size())
         return fail(ctx, RT3_E_ARG, "rt3_mesh_put: entity does not fit in the buffers sized by rt3_mesh_begin");
     RT3_HIP(hipSetDevice(ctx->device));
     std::vector<rt3_gface> rebased(faces, faces + n_faces);         // transfer_entity: indices += running vertex count
@@ -703,7 +805,7 @@ int rt3_mesh_sphere(rt3_ctx* ctx, const float center[3], float radius, uint32_t 
     if (!ctx) return RT3_E_ARG;
     if (!center || !color || n_meridians < 3 || n_parallels < 3) return fail(ctx, RT3_E_ARG, "rt3_mesh_sphere: need >= 3 meridians and parallels");
     const uint32_t nf = 2 * n_meridians * (n_parallels - 2), nv = 2 + (n_parallels - 2) * n_meridians;
-    if ((uint64_t)face_offset + nf > ctx->cap_gfaces || (uint64_t)vertex_offset + nv > ctx->cap_verts)
+    if ((uint64_t)face_offset + nf > ctx->d_gfaces.size() || (uint64_t)vertex_offset + nv > ctx->d_verts.size())
         return fail(ctx, RT3_E_ARG, "rt3_mesh_sphere: entity does not fit in the buffers sized by rt3_mesh_begin");
     RT3_HIP(hipSetDevice(ctx->device));
     const SphereGen g{ center[0], center[1], center[2], radius, n_meridians, n_parallels, color[0], color[1], color[2], face_offset, vertex_offset };
@@ -719,39 +821,38 @@ int rt3_mesh_sphere(rt3_ctx* ctx, const float center[3], float radius, uint32_t 
 int rt3_mesh_commit(rt3_ctx* ctx, const rt3_material* face_materials) {
     if (!ctx) return RT3_E_ARG;
     RT3_HIP(hipSetDevice(ctx->device));
-    const uint32_t n = ctx->cap_gfaces, n_pad = (n + 3u) / 4u * 4u;
-    for (void** b : { (void**)&ctx->d_tri, (void**)&ctx->d_tri_mat, (void**)&ctx->d_tri_kind, (void**)&ctx->d_tri_bound, (void**)&ctx->d_tri_frag, (void**)&ctx->d_face_mats_in,
-                      (void**)&ctx->d_tri_frag_r, (void**)&ctx->d_tri_gfrag, (void**)&ctx->d_tri_grp, (void**)&ctx->d_tri_perm, (void**)&ctx->d_tri_leaf, (void**)&ctx->d_tri_rowb, (void**)&ctx->d_tri_sfrag, (void**)&ctx->d_tri_srowb, (void**)&ctx->d_tri_rec })
-        if (*b) { RT3_HIP(hipFree(*b)); *b = nullptr; }
-    ctx->n_faces = 0; ctx->n_tri_groups = 0; ctx->n_tri_super = 0;
+    const uint32_t n = (uint32_t)ctx->d_gfaces.size(), n_pad = (n + 3u) / 4u * 4u, n_verts = (uint32_t)ctx->d_verts.size();
+    ctx->n_faces = 0;
+    ctx->tri = FilterRows();
+    for (DevBuf<float4>* b : { &ctx->d_tri, &ctx->d_tri_mat, &ctx->d_tri_bound, &ctx->d_tri_rec }) b->reset();
+    ctx->d_tri_kind.reset(); ctx->d_tri_frag.reset(); ctx->d_tri_frag_r.reset(); ctx->d_face_mats_in.reset();
     if (n == 0) return 0;
     if (face_materials)
         for (uint32_t i = 0; i < n; i++)
             if (face_materials[i].kind > RT3_MAT_DIELECTRIC) return fail(ctx, RT3_E_ARG, "unknown material kind");
-    if (!ctx->d_error) RT3_HIP(hipMalloc((void**)&ctx->d_error, 4));
+    int rc;
+    if ((rc = ctx->d_error.ensure(ctx, 1))) return rc;
     RT3_HIP(hipMemsetAsync(ctx->d_error, 0, 4, ctx->stream));
-    RT3_HIP(hipMalloc((void**)&ctx->d_tri, (size_t)n * 4 * sizeof(float4)));
-    RT3_HIP(hipMalloc((void**)&ctx->d_tri_mat, (size_t)n * sizeof(float4)));
-    RT3_HIP(hipMalloc((void**)&ctx->d_tri_kind, (size_t)n * sizeof(uint32_t)));
-    RT3_HIP(hipMalloc((void**)&ctx->d_tri_bound, (size_t)n_pad * sizeof(float4)));
     const uint32_t n_frag_rows = (n + 31u) / 32u * 32u;
-    RT3_HIP(hipMalloc((void**)&ctx->d_tri_frag, (size_t)n_frag_rows * 8 * sizeof(u32x4)));      // 4 operands x 2 lane halves per row
+    if ((rc = ctx->d_tri.alloc(ctx, (size_t)n * 4)) || (rc = ctx->d_tri_mat.alloc(ctx, n)) || (rc = ctx->d_tri_kind.alloc(ctx, n)) ||
+        (rc = ctx->d_tri_bound.alloc(ctx, n_pad)) || (rc = ctx->d_tri_frag.alloc(ctx, (size_t)n_frag_rows * 8)))      // 4 operands x 2 lane halves per row
+        return rc;
     if (face_materials) {
-        RT3_HIP(hipMalloc((void**)&ctx->d_face_mats_in, (size_t)n * sizeof(rt3_material)));
+        if ((rc = ctx->d_face_mats_in.alloc(ctx, n))) return rc;
         RT3_HIP(hipMemcpyAsync(ctx->d_face_mats_in, face_materials, (size_t)n * sizeof(rt3_material), hipMemcpyHostToDevice, ctx->stream));
     }
     // the box of the vertices: its centre is what the faces' filter coordinates are taken about (k_commit_mesh and the ray side agree on it
     // through box_centre())
-    if (!ctx->d_box) RT3_HIP(hipMalloc((void**)&ctx->d_box, 6 * sizeof(uint32_t)));
+    if ((rc = ctx->d_box.ensure(ctx, 6))) return rc;
     RT3_HIP(hipMemsetAsync(ctx->d_box, 0xFF, 3 * sizeof(uint32_t), ctx->stream));
     RT3_HIP(hipMemsetAsync(ctx->d_box + 3, 0, 3 * sizeof(uint32_t), ctx->stream));
-    if (ctx->cap_verts) {
-        hipLaunchKernelGGL(k_vertex_box, dim3(std::min<uint32_t>(256u, (ctx->cap_verts + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                           (const float4*)ctx->d_verts, ctx->cap_verts, ctx->d_box);
+    if (n_verts) {
+        hipLaunchKernelGGL(k_vertex_box, dim3(std::min<uint32_t>(256u, (n_verts + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
+                           (const float4*)ctx->d_verts, n_verts, ctx->d_box);
         RT3_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_commit_mesh, dim3((n_frag_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, ctx->d_gfaces, ctx->d_verts, n, n_pad,
-                       ctx->cap_verts, ctx->d_face_mats_in, ctx->d_tri, ctx->d_tri_bound, ctx->d_tri_mat, ctx->d_tri_kind, ctx->d_error,
+                       n_verts, ctx->d_face_mats_in, ctx->d_tri, ctx->d_tri_bound, ctx->d_tri_mat, ctx->d_tri_kind, ctx->d_error,
                        ctx->d_tri_frag, n_frag_rows, (const uint32_t*)ctx->d_box, 1.0f);
     RT3_HIP(hipGetLastError());
     // Mode R's rays all start at the world origin, the path tracer's mostly ON the scene: the filter's margin eps (|C - c|^2 + r^2 +
@@ -759,9 +860,9 @@ int rt3_mesh_commit(rt3_ctx* ctx, const rt3_material* face_materials) {
     // fragments of its own, built here by the same kernel (with centre_scale 0.5 it writes nothing else) while the merged entity
     // buffers are known to be the ones these faces came from: a render never reads d_gfaces / d_verts, so an rt3_mesh_begin without a
     // commit leaves the committed scene renderable.
-    RT3_HIP(hipMalloc((void**)&ctx->d_tri_frag_r, (size_t)n_frag_rows * 8 * sizeof(u32x4)));
+    if ((rc = ctx->d_tri_frag_r.alloc(ctx, (size_t)n_frag_rows * 8))) return rc;
     hipLaunchKernelGGL(k_commit_mesh, dim3((n_frag_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, ctx->d_gfaces, ctx->d_verts, n, n_pad,
-                       ctx->cap_verts, ctx->d_face_mats_in, ctx->d_tri, ctx->d_tri_bound, ctx->d_tri_mat, ctx->d_tri_kind, ctx->d_error,
+                       n_verts, ctx->d_face_mats_in, ctx->d_tri, ctx->d_tri_bound, ctx->d_tri_mat, ctx->d_tri_kind, ctx->d_error,
                        (u32x4*)ctx->d_tri_frag_r, n_frag_rows, (const uint32_t*)ctx->d_box, 0.5f);
     RT3_HIP(hipGetLastError());
     uint32_t err = 0, box[6];
@@ -770,54 +871,18 @@ int rt3_mesh_commit(rt3_ctx* ctx, const rt3_material* face_materials) {
     RT3_HIP(hipStreamSynchronize(ctx->stream));
     box_centre(box, ctx->tri_centre);
     if (err) return fail(ctx, RT3_E_ARG, "a face references a vertex out of range");
-    // rows of the two-level filter: groups of kGroupTri faces in the order of a spatial median split of their bounds (read back once per commit:
-    // 16 bytes per face); the members' bounds in group order + the face index of each
-    {
-        std::vector<float4> bounds(n);
-        RT3_HIP(hipMemcpy(bounds.data(), ctx->d_tri_bound, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
-        const std::vector<uint32_t> order = face_group_order(bounds.data(), n, kGroupTri, kSuper);
-        std::vector<float4> grp(order.size(), kPadSphere);
-        for (size_t k = 0; k < order.size(); k++) if (order[k] != 0xFFFFFFFFu) grp[k] = bounds[order[k]];
-        int rc;
-        if ((rc = upload(ctx, &ctx->d_tri_grp, grp)) || (rc = upload(ctx, &ctx->d_tri_perm, order))) return rc;
-        RT3_HIP(hipMalloc((void**)&ctx->d_tri_rec, order.size() * 4 * sizeof(float4)));
-        hipLaunchKernelGGL(k_gather_face_records, dim3(((uint32_t)order.size() * 4u + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->d_tri,
-                           (const uint32_t*)ctx->d_tri_perm, (uint32_t)order.size(), ctx->d_tri_rec);
-        RT3_HIP(hipGetLastError());
-        ctx->n_tri_leaves = (uint32_t)(order.size() / kGroupTri);
-        ctx->n_tri_groups = ctx->n_tri_leaves / kSuper;                // rows the matrix filter scans
-        const float4* row_members = ctx->d_tri_grp;
-        uint32_t row_entries = (uint32_t)order.size(), row_group = kGroupTri;
-        if (kSuper > 1) {                                           // three levels: the leaves' bounds are records of their own, a row bounds kSuper of them
-            RT3_HIP(hipMalloc((void**)&ctx->d_tri_leaf, (size_t)ctx->n_tri_leaves * sizeof(float4)));
-            hipLaunchKernelGGL(k_group_bounds, dim3((ctx->n_tri_leaves + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->d_tri_grp, (uint32_t)order.size(),
-                               kGroupTri, ctx->n_tri_leaves, (const uint32_t*)ctx->d_box, 0.0f, 0.0f, 0.0f, ctx->d_tri_leaf);
-            RT3_HIP(hipGetLastError());
-            row_members = ctx->d_tri_leaf; row_entries = ctx->n_tri_leaves; row_group = kSuper;
-        }
-        const uint32_t n_group_rows = (ctx->n_tri_groups + 31u) / 32u * 32u;
-        RT3_HIP(hipMalloc((void**)&ctx->d_tri_gfrag, (size_t)n_group_rows * 4 * sizeof(u32x4)));
-        hipLaunchKernelGGL(k_group_frags, dim3((n_group_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, row_members, row_entries,
-                           row_group, n_group_rows, (const uint32_t*)ctx->d_box, 0.0f, 0.0f, 0.0f, ctx->d_tri_gfrag);
-        RT3_HIP(hipGetLastError());
-        if (kSuper > 1) {                                           // the same rows as f32 records
-            RT3_HIP(hipMalloc((void**)&ctx->d_tri_rowb, (size_t)n_group_rows * sizeof(float4)));
-            hipLaunchKernelGGL(k_group_bounds, dim3((n_group_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, row_members, row_entries,
-                               row_group, n_group_rows, (const uint32_t*)ctx->d_box, 0.0f, 0.0f, 0.0f, ctx->d_tri_rowb);
-            RT3_HIP(hipGetLastError());
-            // four levels: super-rows of kSuper rows, as fragments for the matrix filter and as f32 records
-            ctx->n_tri_super = (ctx->n_tri_groups + kSuper - 1u) / kSuper;
-            const uint32_t n_super_rows = (ctx->n_tri_super + 31u) / 32u * 32u;
-            RT3_HIP(hipMalloc((void**)&ctx->d_tri_sfrag, (size_t)n_super_rows * 4 * sizeof(u32x4)));
-            RT3_HIP(hipMalloc((void**)&ctx->d_tri_srowb, (size_t)n_super_rows * sizeof(float4)));
-            hipLaunchKernelGGL(k_group_frags, dim3((n_super_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->d_tri_rowb, n_group_rows,
-                               kSuper, n_super_rows, (const uint32_t*)ctx->d_box, 0.0f, 0.0f, 0.0f, ctx->d_tri_sfrag);
-            hipLaunchKernelGGL(k_group_bounds, dim3((n_super_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->d_tri_rowb, n_group_rows,
-                               kSuper, n_super_rows, (const uint32_t*)ctx->d_box, 0.0f, 0.0f, 0.0f, ctx->d_tri_srowb);
-            RT3_HIP(hipGetLastError());
-        }
-        RT3_HIP(hipStreamSynchronize(ctx->stream));                 // a render may come on another stream
-    }
+    // rows of the multi-level filter: groups of kGroupTri faces in the order of a spatial median split of their bounds (read back once per
+    // commit: 16 bytes per face); then the faces' records in group order
+    std::vector<float4> bounds(n);
+    RT3_HIP(hipMemcpy(bounds.data(), ctx->d_tri_bound, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
+    const std::vector<uint32_t> order = face_group_order(bounds.data(), n, kGroupTri, kSuper);
+    const float no_centre[3] = { 0.0f, 0.0f, 0.0f };
+    if ((rc = build_rows(ctx, ctx->tri, bounds.data(), order, kGroupTri, ctx->d_box, no_centre))) return rc;
+    if ((rc = ctx->d_tri_rec.alloc(ctx, order.size() * 4))) return rc;
+    hipLaunchKernelGGL(k_gather_face_records, dim3(((uint32_t)order.size() * 4u + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->d_tri,
+                       (const uint32_t*)ctx->tri.perm, (uint32_t)order.size(), ctx->d_tri_rec.get());
+    RT3_HIP(hipGetLastError());
+    RT3_HIP(hipStreamSynchronize(ctx->stream));                     // a render may come on another stream
     ctx->n_faces = n;
     return 0;
 }
@@ -826,8 +891,8 @@ int rt3_mesh_download(rt3_ctx* ctx, rt3_gface* faces, float* vertices) {
     if (!ctx) return RT3_E_ARG;
     RT3_HIP(hipSetDevice(ctx->device));
     RT3_HIP(hipStreamSynchronize(ctx->stream));
-    if (faces && ctx->cap_gfaces) RT3_HIP(hipMemcpy(faces, ctx->d_gfaces, (size_t)ctx->cap_gfaces * sizeof(rt3_gface), hipMemcpyDeviceToHost));
-    if (vertices && ctx->cap_verts) RT3_HIP(hipMemcpy(vertices, ctx->d_verts, (size_t)ctx->cap_verts * sizeof(float4), hipMemcpyDeviceToHost));
+    if (faces && ctx->d_gfaces.size()) RT3_HIP(hipMemcpy(faces, ctx->d_gfaces, ctx->d_gfaces.size() * sizeof(rt3_gface), hipMemcpyDeviceToHost));
+    if (vertices && ctx->d_verts.size()) RT3_HIP(hipMemcpy(vertices, ctx->d_verts, ctx->d_verts.size() * sizeof(float4), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -857,59 +922,19 @@ int rt3_set_spheres(rt3_ctx* ctx, const float* center_radius, const rt3_material
         mat[i] = pack_material(materials[i]);
         kind[i] = materials[i].kind;
     }
+    ctx->n_sph = 0;                                                 // (no spheres until everything below has been issued)
     int rc;
     sphere_filter_centre(center_radius, n, ctx->sph_centre);
     ctx->n_direct = sphere_direct_list(center_radius, n, ctx->sph_centre, ctx->direct);
-    if ((rc = upload(ctx, &ctx->d_sph_frag, build_sphere_frags(center_radius, n, ctx->sph_centre, ctx->direct, ctx->n_direct)))) return rc;      // k_trace_mfma (K = 64, 32x32x16)
-    if ((rc = upload(ctx, &ctx->d_sph_frag32, build_sphere_frags32(center_radius, n, ctx->sph_centre, ctx->direct, ctx->n_direct)))) return rc;  // K = 32 form
-    if ((rc = upload(ctx, &ctx->d_sph, sph)) || (rc = upload(ctx, &ctx->d_sph_invr, invr)) ||
-        (rc = upload(ctx, &ctx->d_sph_mat, mat)) || (rc = upload(ctx, &ctx->d_sph_kind, kind)))
+    if ((rc = ctx->d_sph_frag.upload(ctx, build_sphere_frags(center_radius, n, ctx->sph_centre, ctx->direct, ctx->n_direct)))) return rc;      // k_trace_mfma (K = 64, 32x32x16)
+    if ((rc = ctx->d_sph_frag32.upload(ctx, build_sphere_frags32(center_radius, n, ctx->sph_centre, ctx->direct, ctx->n_direct)))) return rc;  // K = 32 form
+    if ((rc = ctx->d_sph.upload(ctx, sph)) || (rc = ctx->d_sph_invr.upload(ctx, invr)) || (rc = ctx->d_sph_mat.upload(ctx, mat)) ||
+        (rc = ctx->d_sph_kind.upload(ctx, kind)))
         return rc;
-    // rows of the two-level filter: groups of kGroupSph spheres in the order of a spatial median split
-    {
-        const std::vector<uint32_t> order = sphere_group_order(center_radius, n, ctx->direct, ctx->n_direct, kGroupSph, kSuper);
-        std::vector<float4> grp(order.size(), kPadSphere);
-        for (size_t k = 0; k < order.size(); k++) if (order[k] != 0xFFFFFFFFu) grp[k] = sph[order[k]];
-        if ((rc = upload(ctx, &ctx->d_sph_grp, grp)) || (rc = upload(ctx, &ctx->d_sph_perm, order))) return rc;
-        for (void** b : { (void**)&ctx->d_sph_gfrag, (void**)&ctx->d_sph_leaf, (void**)&ctx->d_sph_rowb, (void**)&ctx->d_sph_sfrag, (void**)&ctx->d_sph_srowb })
-            if (*b) { RT3_HIP(hipFree(*b)); *b = nullptr; }
-        ctx->n_sph_leaves = (uint32_t)(order.size() / kGroupSph);
-        ctx->n_sph_groups = ctx->n_sph_leaves / kSuper;                // rows the matrix filter scans
-        ctx->n_sph_super = 0;                                          // (no groups: every sphere is on the direct list or unusable)
-        if (ctx->n_sph_groups) {
-            const float4* row_members = ctx->d_sph_grp;
-            uint32_t row_entries = (uint32_t)order.size(), row_group = kGroupSph;
-            if (kSuper > 1) {
-                RT3_HIP(hipMalloc((void**)&ctx->d_sph_leaf, (size_t)ctx->n_sph_leaves * sizeof(float4)));
-                hipLaunchKernelGGL(k_group_bounds, dim3((ctx->n_sph_leaves + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->d_sph_grp,
-                                   (uint32_t)order.size(), kGroupSph, ctx->n_sph_leaves, (const uint32_t*)nullptr, ctx->sph_centre[0], ctx->sph_centre[1], ctx->sph_centre[2],
-                                   ctx->d_sph_leaf);
-                RT3_HIP(hipGetLastError());
-                row_members = ctx->d_sph_leaf; row_entries = ctx->n_sph_leaves; row_group = kSuper;
-            }
-            const uint32_t n_group_rows = (ctx->n_sph_groups + 31u) / 32u * 32u;
-            RT3_HIP(hipMalloc((void**)&ctx->d_sph_gfrag, (size_t)n_group_rows * 4 * sizeof(u32x4)));
-            hipLaunchKernelGGL(k_group_frags, dim3((n_group_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, row_members, row_entries, row_group,
-                               n_group_rows, (const uint32_t*)nullptr, ctx->sph_centre[0], ctx->sph_centre[1], ctx->sph_centre[2], ctx->d_sph_gfrag);
-            RT3_HIP(hipGetLastError());
-            if (kSuper > 1) {
-                RT3_HIP(hipMalloc((void**)&ctx->d_sph_rowb, (size_t)n_group_rows * sizeof(float4)));
-                hipLaunchKernelGGL(k_group_bounds, dim3((n_group_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, row_members, row_entries, row_group,
-                                   n_group_rows, (const uint32_t*)nullptr, ctx->sph_centre[0], ctx->sph_centre[1], ctx->sph_centre[2], ctx->d_sph_rowb);
-                RT3_HIP(hipGetLastError());
-                ctx->n_sph_super = (ctx->n_sph_groups + kSuper - 1u) / kSuper;
-                const uint32_t n_super_rows = (ctx->n_sph_super + 31u) / 32u * 32u;
-                RT3_HIP(hipMalloc((void**)&ctx->d_sph_sfrag, (size_t)n_super_rows * 4 * sizeof(u32x4)));
-                RT3_HIP(hipMalloc((void**)&ctx->d_sph_srowb, (size_t)n_super_rows * sizeof(float4)));
-                hipLaunchKernelGGL(k_group_frags, dim3((n_super_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->d_sph_rowb, n_group_rows, kSuper,
-                                   n_super_rows, (const uint32_t*)nullptr, ctx->sph_centre[0], ctx->sph_centre[1], ctx->sph_centre[2], ctx->d_sph_sfrag);
-                hipLaunchKernelGGL(k_group_bounds, dim3((n_super_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->d_sph_rowb, n_group_rows, kSuper,
-                                   n_super_rows, (const uint32_t*)nullptr, ctx->sph_centre[0], ctx->sph_centre[1], ctx->sph_centre[2], ctx->d_sph_srowb);
-                RT3_HIP(hipGetLastError());
-            }
-            RT3_HIP(hipStreamSynchronize(ctx->stream));             // a render may come on another stream
-        }
-    }
+    // rows of the multi-level filter: groups of kGroupSph spheres in the order of a spatial median split
+    const std::vector<uint32_t> order = sphere_group_order(center_radius, n, ctx->direct, ctx->n_direct, kGroupSph, kSuper);
+    if ((rc = build_rows(ctx, ctx->sph, sph.data(), order, kGroupSph, nullptr, ctx->sph_centre))) return rc;
+    RT3_HIP(hipStreamSynchronize(ctx->stream));                     // a render may come on another stream
     ctx->n_sph = n;
     return 0;
 }
@@ -960,7 +985,7 @@ int rt3_render_device(rt3_ctx* ctx, const rt3_camera* cam, uint32_t width, uint3
     if (!cam || !d_out) return fail(ctx, RT3_E_ARG, "cam / d_out_pixels is NULL");
     if (width < 2 || height < 2 || (uint64_t)width * height > 0x7FFFFFFFull) return fail(ctx, RT3_E_ARG, "bad frame size");
     RT3_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
+    const hipStream_t stream = stream_of(ctx, stream_);            // (Mode R's buffers are the caller's: no wait for ev_acc)
     ctx->rendered = false;                                          // stats are valid again once every launch below has been issued
     ctx->ev_used = 0;
     hipEvent_t a, b;
@@ -981,7 +1006,7 @@ int rt3_render_device(rt3_ctx* ctx, const rt3_camera* cam, uint32_t width, uint3
     RT3_HIP(hipEventRecord(a, stream));
     if (use_mfma)
         hipLaunchKernelGGL(k_mode_r_mfma, dim3((npix + kMB - 1) / kMB), dim3(kMB), kTiledLdsBytes, stream,
-                           ctx->d_tri, (const u32x4*)ctx->d_tri_frag_r, ctx->d_tri_mat, ctx->n_faces, cam_dev(cam), width, height, (uint32_t*)d_out,
+                           ctx->d_tri, ctx->d_tri_frag_r, ctx->d_tri_mat, ctx->n_faces, cam_dev(cam), width, height, (uint32_t*)d_out,
                            0.5f * ctx->tri_centre[0], 0.5f * ctx->tri_centre[1], 0.5f * ctx->tri_centre[2]);
     else if (at_origin && !ctx->force_plain_mode_r)
         hipLaunchKernelGGL(k_mode_r_fast, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
@@ -1005,10 +1030,11 @@ int rt3_render(rt3_ctx* ctx, const rt3_camera* cam, uint32_t width, uint32_t hei
     if (width < 2 || height < 2 || (uint64_t)width * height > 0x7FFFFFFFull) return fail(ctx, RT3_E_ARG, "bad frame size");
     RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)width * height;
-    int rc = ensure(ctx, &ctx->d_out, &ctx->out_entries, npix);
+    int rc = ctx->stage.ensure(ctx, (npix + 3) / 4);
     if (rc) return rc;
-    if ((rc = rt3_render_device(ctx, cam, width, height, ctx->d_out, ctx->stream))) return rc;
-    RT3_HIP(hipMemcpyAsync(out_pixels, ctx->d_out, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
+    uint32_t* const d_out = (uint32_t*)ctx->stage.get();
+    if ((rc = rt3_render_device(ctx, cam, width, height, d_out, ctx->stream))) return rc;
+    RT3_HIP(hipMemcpyAsync(out_pixels, d_out, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
     RT3_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -1020,15 +1046,11 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     int rc = check_params(ctx, p);
     if (rc) return rc;
     if (sample_count == 0 || (uint64_t)sample_begin + sample_count > p->spp) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
-    if (ctx->n_sph == 0 && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "no scene: call rt3_set_spheres / rt3_set_mesh first");
+    if ((rc = check_scene(ctx))) return rc;
     const bool ref = (p->flags & RT3_FLAG_REFERENCE_PRIMARY) != 0, var = (p->flags & RT3_FLAG_VARIANCE) != 0;
     if (ref && ctx->n_sph != 0) return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY needs a triangle-only scene");
-    if (ctx->n_faces >= (1u << kPairLaneShift) - 32u || ctx->n_sph >= (1u << kPairLaneShift) - 32u) return fail(ctx, RT3_E_ARG, "too many primitives");
-    RT3_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
-    // d_rad, d_accum and the counters belong to the context, not to a stream: whatever stream the previous render ran on, this one
-    // starts behind it (a wait on the device; nothing if it is the same stream)
-    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
 
     const uint32_t rows = rt3_rows_owned(p);
     const uint32_t npix = rows * p->width;
@@ -1040,13 +1062,8 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     }
     ctx->rendered = false;                                          // stats: valid again once every launch below has been issued
     ctx->acc_valid = false;                                         // accumulation: valid again once this call has been issued completely
-    ctx->ev_used = 0;
     if (npix == 0) {
-        RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
-        RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 64, stream));
-        RT3_HIP(hipEventRecord(ctx->ev_end, stream));
-        RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
-        ctx->last_stream = stream; ctx->last_samples = 0; ctx->last_was_path = true; ctx->rendered = true;
+        if ((rc = begin_timed(ctx, stream)) || (rc = end_timed(ctx, stream, 0, nullptr))) return rc;
         ctx->acc_valid = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = sample_begin + sample_count; ctx->acc_npix = 0;
         return 0;
     }
@@ -1056,10 +1073,10 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     uint32_t batch = (uint32_t)std::min<uint64_t>(sample_count, std::max<uint64_t>(1, ctx->rad_cap_bytes / per_spp));
     batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / npix);
     if (batch == 0) return fail(ctx, RT3_E_ARG, "frame too large for one sample batch");
-    if ((rc = ensure(ctx, &ctx->d_rad, &ctx->rad_entries, (size_t)npix * batch))) return rc;
+    if ((rc = ctx->d_rad.ensure(ctx, (size_t)npix * batch))) return rc;
     if (sample_begin == 0) {
-        if ((rc = ensure(ctx, &ctx->d_accum, &ctx->accum_entries, (size_t)npix))) return rc;
-        if (var && (rc = ensure(ctx, &ctx->d_accum_sq, &ctx->accum_sq_entries, (size_t)npix))) return rc;
+        if ((rc = ctx->d_accum.ensure(ctx, npix))) return rc;
+        if (var && (rc = ctx->d_accum_sq.ensure(ctx, npix))) return rc;
     }
 
     TraceArgs A;
@@ -1069,8 +1086,7 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     TracePlan T;
     if ((rc = plan_trace(ctx, A, ref, ref && !(cam_at_origin(cam) && !(p->lens_radius > 0.0f)), false, T))) return rc;
 
-    RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
-    RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 128, stream));
+    if ((rc = begin_timed(ctx, stream))) return rc;
 #ifdef RT3_PROFILE
     RT3_HIP(hipMemsetAsync(ctx->d_casts + 6, 0xFF, 8, stream));
     RT3_HIP(hipMemsetAsync(ctx->d_casts + 8, 0xFF, 16, stream));       // [8] first wave start, [9] first time a wave found the queue empty
@@ -1095,14 +1111,7 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     hipLaunchKernelGGL(k_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
                        ctx->d_accum, npix, sample_begin + sample_count, p->flags, (uint32_t*)d_out);
     RT3_HIP(hipGetLastError());
-    RT3_HIP(hipEventRecord(ctx->ev_end, stream));
-    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
-    ctx->last_stream = stream;
-    ctx->last_samples = (uint64_t)npix * sample_count;
-    ctx->last_was_path = true;
-    ctx->last_mfma16 = T.mfma16;
-    ctx->last_filter_rows = T.filter_rows;
-    ctx->rendered = true;
+    if ((rc = end_timed(ctx, stream, (uint64_t)npix * sample_count, &T))) return rc;
     ctx->acc_valid = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = sample_begin + sample_count; ctx->acc_npix = npix;
     return 0;
 }
@@ -1120,9 +1129,10 @@ int rt3_render_path_range(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
     if (rc) return rc;
     RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
-    if ((rc = ensure(ctx, &ctx->d_out, &ctx->out_entries, std::max<size_t>(npix, 1)))) return rc;
-    if ((rc = rt3_render_path_range_device(ctx, cam, p, sample_begin, sample_count, ctx->d_out, ctx->stream))) return rc;
-    if (npix) RT3_HIP(hipMemcpyAsync(out_pixels, ctx->d_out, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ctx->stage.ensure(ctx, (std::max<size_t>(npix, 1) + 3) / 4))) return rc;
+    uint32_t* const d_out = (uint32_t*)ctx->stage.get();
+    if ((rc = rt3_render_path_range_device(ctx, cam, p, sample_begin, sample_count, d_out, ctx->stream))) return rc;
+    if (npix) RT3_HIP(hipMemcpyAsync(out_pixels, d_out, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
     RT3_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -1162,10 +1172,10 @@ int rt3_accum_upload(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, c
     ctx->acc_valid = false;
     if (ctx->ev_acc_recorded) RT3_HIP(hipEventSynchronize(ctx->ev_acc));        // a render still in flight reads and writes what is overwritten here
     if (npix) {
-        if ((rc = ensure(ctx, &ctx->d_accum, &ctx->accum_entries, (size_t)npix))) return rc;
+        if ((rc = ctx->d_accum.ensure(ctx, npix))) return rc;
         RT3_HIP(hipMemcpy(ctx->d_accum, sum, (size_t)npix * sizeof(float4), hipMemcpyHostToDevice));
         if (var) {
-            if ((rc = ensure(ctx, &ctx->d_accum_sq, &ctx->accum_sq_entries, (size_t)npix))) return rc;
+            if ((rc = ctx->d_accum_sq.ensure(ctx, npix))) return rc;
             RT3_HIP(hipMemcpy(ctx->d_accum_sq, sum_sq, (size_t)npix * sizeof(float4), hipMemcpyHostToDevice));
         }
     }
@@ -1208,7 +1218,7 @@ int rt3_gather_rows(rt3_ctx* root, void* d_frame, rt3_ctx* shard, const void* d_
     int rc = check_params(ctx, p);
     if (rc) return rc;
     RT3_HIP(hipSetDevice(shard->device));
-    hipStream_t stream = stream_ ? (hipStream_t)stream_ : shard->stream;
+    const hipStream_t stream = stream_of(shard, stream_);           // (d_frame and d_tile are the caller's: no wait for ev_acc)
     if (root->device != shard->device && !shard->peers_enabled.count(root->device)) {
         int can = 0;
         RT3_HIP(hipDeviceCanAccessPeer(&can, shard->device, root->device));
@@ -1240,32 +1250,18 @@ static int query_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_mi
     if (!d_rays || !d_out) return fail(ctx, RT3_E_ARG, "rays / results buffer is NULL");
     if ((uintptr_t)d_rays % 16u != 0 || (uintptr_t)d_out % (occluded ? 4u : 16u) != 0)
         return fail(ctx, RT3_E_ARG, occluded ? "rays must be 16-byte and occlusion words 4-byte aligned" : "rays and hits must be 16-byte aligned");
-    if (ctx->n_sph == 0 && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "no scene: call rt3_set_spheres / rt3_set_mesh first");
-    if (ctx->n_faces >= (1u << kPairLaneShift) - 32u || ctx->n_sph >= (1u << kPairLaneShift) - 32u) return fail(ctx, RT3_E_ARG, "too many primitives");
-    RT3_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
-    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));    // the counters, the work queue and the strips are the context's
+    int rc = check_scene(ctx);
+    if (rc) return rc;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
     ctx->rendered = false;
-    ctx->ev_used = 0;
     TraceArgs A = scene_args(ctx);
     A.t_min = t_min;
     A.total = n;
     A.q_rays = (const float4*)d_rays; A.q_out = d_out; A.q_occluded = occluded ? 1u : 0u;
     TracePlan T;
-    int rc;
-    if ((rc = plan_trace(ctx, A, false, false, true, T))) return rc;
-    RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
-    RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 128, stream));
-    if ((rc = issue_query(ctx, A, T, n, stream))) return rc;
-    RT3_HIP(hipEventRecord(ctx->ev_end, stream));
-    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
-    ctx->last_stream = stream;
-    ctx->last_samples = 0;
-    ctx->last_was_path = true;
-    ctx->last_mfma16 = T.mfma16;
-    ctx->last_filter_rows = T.filter_rows;
-    ctx->rendered = true;
-    return 0;
+    if ((rc = plan_trace(ctx, A, false, false, true, T)) || (rc = begin_timed(ctx, stream)) || (rc = issue_query(ctx, A, T, n, stream))) return rc;
+    return end_timed(ctx, stream, 0, &T);
 }
 static int query_host(rt3_ctx* ctx, const rt3_ray* rays, uint32_t n, float t_min, void* out, bool occluded) {
     if (!ctx) return RT3_E_ARG;
@@ -1273,13 +1269,15 @@ static int query_host(rt3_ctx* ctx, const rt3_ray* rays, uint32_t n, float t_min
     if (n > (1u << 30)) return fail(ctx, RT3_E_ARG, "at most 2^30 rays per query");
     if (n == 0) return 0;
     if (!rays || !out) return fail(ctx, RT3_E_ARG, "rays / results array is NULL");
-    if (ctx->n_sph == 0 && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "no scene: call rt3_set_spheres / rt3_set_mesh first");
+    int rc = check_scene(ctx);
+    if (rc) return rc;
     RT3_HIP(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = ensure(ctx, &ctx->d_qrays, &ctx->qrays_entries, (size_t)n * 2u)) || (rc = ensure(ctx, &ctx->d_qout, &ctx->qout_entries, (size_t)n))) return rc;
-    RT3_HIP(hipMemcpyAsync(ctx->d_qrays, rays, (size_t)n * sizeof(rt3_ray), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = query_device(ctx, ctx->d_qrays, n, t_min, ctx->d_qout, ctx->stream, occluded))) return rc;
-    RT3_HIP(hipMemcpyAsync(out, ctx->d_qout, (size_t)n * (occluded ? 4u : sizeof(rt3_hit)), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ctx->stage.ensure(ctx, (size_t)n * 3u))) return rc;
+    float4* const d_rays = ctx->stage.get();                        // two float4 per ray, then one per result
+    float4* const d_out = d_rays + (size_t)n * 2u;
+    RT3_HIP(hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(rt3_ray), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = query_device(ctx, d_rays, n, t_min, d_out, ctx->stream, occluded))) return rc;
+    RT3_HIP(hipMemcpyAsync(out, d_out, (size_t)n * (occluded ? 4u : sizeof(rt3_hit)), hipMemcpyDeviceToHost, ctx->stream));
     RT3_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -1312,9 +1310,8 @@ int rt3_camera_rays_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params
     if (sample_count == 0 || (uint64_t)sample_begin + sample_count > p->spp) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
     const uint32_t npix = rt3_rows_owned(p) * p->width;
     if ((uint64_t)npix * sample_count > 0x7FFF0000ull) return fail(ctx, RT3_E_ARG, "too many rays for one call (owned pixels x samples > 2^31 - 2^16)");
-    RT3_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
-    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
     if (npix != 0) {
         TraceArgs A;
         if ((rc = path_args(ctx, cam, p, npix, A))) return rc;
@@ -1323,8 +1320,7 @@ int rt3_camera_rays_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params
         hipLaunchKernelGGL(k_camera_rays, dim3((A.total + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, (float4*)d_out);
         RT3_HIP(hipGetLastError());
     }
-    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
-    return 0;
+    return leave(ctx, stream);
 }
 
 int rt3_camera_rays(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t sample_begin, uint32_t sample_count, rt3_ray* out) {
@@ -1336,9 +1332,9 @@ int rt3_camera_rays(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, ui
     const uint64_t n = (uint64_t)rt3_rows_owned(p) * p->width * sample_count;
     if (n > 0x7FFF0000ull) return fail(ctx, RT3_E_ARG, "too many rays for one call (owned pixels x samples > 2^31 - 2^16)");
     RT3_HIP(hipSetDevice(ctx->device));
-    if ((rc = ensure(ctx, &ctx->d_hout, &ctx->hout_entries, std::max<size_t>(2 * n, 1)))) return rc;
-    if ((rc = rt3_camera_rays_device(ctx, cam, p, sample_begin, sample_count, ctx->d_hout, ctx->stream))) return rc;
-    if (n) RT3_HIP(hipMemcpyAsync(out, ctx->d_hout, n * sizeof(rt3_ray), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(2 * n, 1)))) return rc;
+    if ((rc = rt3_camera_rays_device(ctx, cam, p, sample_begin, sample_count, ctx->stage, ctx->stream))) return rc;
+    if (n) RT3_HIP(hipMemcpyAsync(out, ctx->stage, n * sizeof(rt3_ray), hipMemcpyDeviceToHost, ctx->stream));
     RT3_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -1349,30 +1345,19 @@ int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
     if (!ctx) return RT3_E_ARG;
     int rc = aov_common_checks(ctx, cam, p, d_out, "d_out_aov");
     if (rc) return rc;
-    if (ctx->n_sph == 0 && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "no scene: call rt3_set_spheres / rt3_set_mesh first");
-    if (ctx->n_faces >= (1u << kPairLaneShift) - 32u || ctx->n_sph >= (1u << kPairLaneShift) - 32u) return fail(ctx, RT3_E_ARG, "too many primitives");
-    RT3_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
-    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));    // the counters, the work queue and the strips are the context's
+    if ((rc = check_scene(ctx))) return rc;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
     const uint32_t npix = rt3_rows_owned(p) * p->width;
     ctx->rendered = false;
-    ctx->ev_used = 0;
-    if (npix == 0) {
-        RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
-        RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 64, stream));
-        RT3_HIP(hipEventRecord(ctx->ev_end, stream));
-        RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
-        ctx->last_stream = stream; ctx->last_samples = 0; ctx->last_was_path = true; ctx->rendered = true;
-        return 0;
-    }
+    if (npix == 0) return (rc = begin_timed(ctx, stream)) ? rc : end_timed(ctx, stream, 0, nullptr);
     // batch size: 48 B per (pixel, sample) — the ray (32) and its hit (16) — under the sample storage cap
     const uint64_t per_spp = (uint64_t)npix * (sizeof(rt3_ray) + sizeof(rt3_hit));
     uint32_t batch = (uint32_t)std::min<uint64_t>(p->spp, std::max<uint64_t>(1, ctx->rad_cap_bytes / per_spp));
     batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / npix);
     if (batch == 0) return fail(ctx, RT3_E_ARG, "frame too large for one sample batch");
-    if ((rc = ensure(ctx, &ctx->d_arays, &ctx->arays_entries, (size_t)npix * batch * 2u)) ||
-        (rc = ensure(ctx, &ctx->d_ahits, &ctx->ahits_entries, (size_t)npix * batch)) ||
-        (rc = ensure(ctx, &ctx->d_aacc, &ctx->aacc_entries, (size_t)npix * 3u)))
+    if ((rc = ctx->d_arays.ensure(ctx, (size_t)npix * batch * 2u)) || (rc = ctx->d_ahits.ensure(ctx, (size_t)npix * batch)) ||
+        (rc = ctx->d_aacc.ensure(ctx, (size_t)npix * 3u)))
         return rc;
     TraceArgs A;                                                    // camera rays and the accumulation
     if ((rc = path_args(ctx, cam, p, npix, A))) return rc;
@@ -1380,9 +1365,7 @@ int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
     Q.t_min = p->t_min;
     Q.q_rays = ctx->d_arays; Q.q_out = ctx->d_ahits; Q.q_occluded = 0u;
     TracePlan T;
-    if ((rc = plan_trace(ctx, Q, false, false, true, T))) return rc;
-    RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
-    RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 128, stream));
+    if ((rc = plan_trace(ctx, Q, false, false, true, T)) || (rc = begin_timed(ctx, stream))) return rc;
     for (uint32_t s0 = 0; s0 < p->spp; s0 += batch) {
         const uint32_t ns = std::min(batch, p->spp - s0);
         A.s0 = s0;
@@ -1396,15 +1379,7 @@ int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
     }
     hipLaunchKernelGGL(k_aov_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_aacc, npix, p->spp, (float4*)d_out);
     RT3_HIP(hipGetLastError());
-    RT3_HIP(hipEventRecord(ctx->ev_end, stream));
-    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
-    ctx->last_stream = stream;
-    ctx->last_samples = (uint64_t)npix * p->spp;
-    ctx->last_was_path = true;
-    ctx->last_mfma16 = T.mfma16;
-    ctx->last_filter_rows = T.filter_rows;
-    ctx->rendered = true;
-    return 0;
+    return end_timed(ctx, stream, (uint64_t)npix * p->spp, &T);
 }
 
 int rt3_render_aov(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, rt3_aov* out) {
@@ -1414,9 +1389,9 @@ int rt3_render_aov(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, rt3
     if (rc) return rc;
     RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
-    if ((rc = ensure(ctx, &ctx->d_hout, &ctx->hout_entries, std::max<size_t>(3 * npix, 1)))) return rc;
-    if ((rc = rt3_render_aov_device(ctx, cam, p, ctx->d_hout, ctx->stream))) return rc;
-    if (npix) RT3_HIP(hipMemcpyAsync(out, ctx->d_hout, npix * sizeof(rt3_aov), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(3 * npix, 1)))) return rc;
+    if ((rc = rt3_render_aov_device(ctx, cam, p, ctx->stage, ctx->stream))) return rc;
+    if (npix) RT3_HIP(hipMemcpyAsync(out, ctx->stage, npix * sizeof(rt3_aov), hipMemcpyDeviceToHost, ctx->stream));
     RT3_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -1426,16 +1401,15 @@ int rt3_accum_resolve_device(rt3_ctx* ctx, void* d_out, void* stream_) {
     if (!d_out) return fail(ctx, RT3_E_ARG, "d_out_rgba is NULL");
     if ((uintptr_t)d_out % 16u != 0) return fail(ctx, RT3_E_ARG, "d_out_rgba must be 16-byte aligned");
     if (!ctx->acc_valid) return fail(ctx, RT3_E_STATE, "no accumulation on this context");
-    RT3_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
-    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));    // behind the render that wrote d_accum
+    hipStream_t stream;
+    const int rc = enter(ctx, stream_, &stream);                    // behind the render that wrote d_accum
+    if (rc) return rc;
     if (ctx->acc_npix) {
         hipLaunchKernelGGL(k_resolve_float, dim3((ctx->acc_npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_accum,
                            ctx->acc_npix, ctx->acc_done, (float4*)d_out);
         RT3_HIP(hipGetLastError());
     }
-    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;       // a later render that overwrites d_accum waits for this
-    return 0;
+    return leave(ctx, stream);                                      // a later render that overwrites d_accum waits for this
 }
 
 int rt3_accum_resolve(rt3_ctx* ctx, float* rgba) {
@@ -1445,9 +1419,9 @@ int rt3_accum_resolve(rt3_ctx* ctx, float* rgba) {
     RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = ctx->acc_npix;
     int rc;
-    if ((rc = ensure(ctx, &ctx->d_hout, &ctx->hout_entries, std::max<size_t>(npix, 1)))) return rc;
-    if ((rc = rt3_accum_resolve_device(ctx, ctx->d_hout, ctx->stream))) return rc;
-    if (npix) RT3_HIP(hipMemcpyAsync(rgba, ctx->d_hout, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(npix, 1)))) return rc;
+    if ((rc = rt3_accum_resolve_device(ctx, ctx->stage, ctx->stream))) return rc;
+    if (npix) RT3_HIP(hipMemcpyAsync(rgba, ctx->stage, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     RT3_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -1481,14 +1455,11 @@ int rt3_denoise_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_colou
     const uintptr_t c = (uintptr_t)d_colour, a = (uintptr_t)d_aov;
     if ((o < c + npix * sizeof(float4) && c < oe) || (o < a + npix * sizeof(rt3_aov) && a < oe))
         return fail(ctx, RT3_E_ARG, "d_out_rgba overlaps an input");
-    RT3_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
-    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));    // the scratch is the context's
-    if ((rc = ensure(ctx, &ctx->d_dn, &ctx->dn_entries, 3 * npix + (npix + 3) / 4))) return rc;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream)) || (rc = ctx->d_dn.ensure(ctx, 3 * npix + (npix + 3) / 4))) return rc;     // the scratch is the context's
     const DenoiseLaunch L{ w, h, p->iterations, p->normal_power, p->sigma_luminance, p->sigma_depth, d_colour, d_aov, d_out, ctx->d_dn };
     RT3_HIP(denoise_launch(L, stream));
-    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
-    return 0;
+    return leave(ctx, stream);
 }
 
 int rt3_denoise(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* colour, const rt3_aov* aov, const rt3_denoise_params* p, float* out) {
@@ -1497,8 +1468,8 @@ int rt3_denoise(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* colour, const
     if (rc) return rc;
     RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)w * h;
-    if ((rc = ensure(ctx, &ctx->d_dnh, &ctx->dnh_entries, 5 * npix))) return rc;
-    float4* const dc = ctx->d_dnh;
+    if ((rc = ctx->stage.ensure(ctx, 5 * npix))) return rc;
+    float4* const dc = ctx->stage;
     float4* const da = dc + npix;
     float4* const dout = da + 3 * npix;
     RT3_HIP(hipMemcpyAsync(dc, colour, npix * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
@@ -1596,17 +1567,14 @@ int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_
     T.alpha = p->alpha; T.moments_alpha = p->moments_alpha; T.depth_tolerance = p->depth_tolerance; T.normal_tolerance = p->normal_tolerance;
     T.prev_history = d_prev_history;
     T.out_history = d_out_history;
-    RT3_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;     // rt3.h: NULL = the context's own stream
-    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));    // the scratch is the context's
-    if ((rc = ensure(ctx, &ctx->d_dn, &ctx->dn_entries, 3 * npix + (npix + 3) / 4))) return rc;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream)) || (rc = ctx->d_dn.ensure(ctx, 3 * npix + (npix + 3) / 4))) return rc;     // the scratch is the context's
     T.base.scratch = ctx->d_dn;
     RT3_HIP(temporal_launch(T, stream));
-    RT3_HIP(hipEventRecord(ctx->ev_acc, stream)); ctx->ev_acc_recorded = true;
-    return 0;
+    return leave(ctx, stream);
 }
 
-// The host form: colour, AOVs, both histories and the result on the device in d_dnh (11 float4 per pixel).
+// The host form: colour, AOVs, both histories and the result on the device in ctx->stage (11 float4 per pixel).
 int rt3_denoise_temporal(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
                          const rt3_camera* prev_cam, const rt3_history* prev_history, const rt3_temporal_params* p, float* out,
                          rt3_history* out_history) {
@@ -1615,8 +1583,8 @@ int rt3_denoise_temporal(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera*
     if (rc) return rc;
     RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)w * h;
-    if ((rc = ensure(ctx, &ctx->d_dnh, &ctx->dnh_entries, 11 * npix))) return rc;
-    float4* const dc = ctx->d_dnh;
+    if ((rc = ctx->stage.ensure(ctx, 11 * npix))) return rc;
+    float4* const dc = ctx->stage;
     float4* const da = dc + npix;
     float4* const dprev = da + 3 * npix;
     float4* const dhist = dprev + 3 * npix;

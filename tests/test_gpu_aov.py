@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from test_denoise_abi import synthetic
 from test_gpu_brute import random_soup
 from test_gpu_ray_query import FORMS
 
@@ -331,6 +332,29 @@ def test_device_forms_equal_the_host_forms(rt3, renderer):
     assert d_aov.cpu().numpy().tobytes() == aov.tobytes()
     assert d_rays.cpu().numpy().tobytes() == rays.tobytes()
     assert d_lin.cpu().numpy().tobytes() == lin.tobytes()
+
+
+def test_host_forms_share_one_staging_buffer(rt3, renderer):
+    """The host forms copy through one device buffer of the context: interleaved on one context with different sizes, each call returns
+    what it returns on a context of its own."""
+    kw, cam, lens = scene(rt3, "soup", False)
+    big = rt3.make_params(4 * W, 4 * H, spp=2, max_depth=1, seed=3, lens_radius=lens)
+    small = rt3.make_params(W // 2, H // 2, spp=3, max_depth=1, seed=4, lens_radius=lens)
+    p = rt3.make_params(W, H, spp=4, max_depth=4, seed=5, lens_radius=lens)
+    g = np.linspace(-0.3, 0.3, 3, dtype=np.float32)
+    rays = rt3.make_rays(np.zeros((9, 3), np.float32), np.stack([np.repeat(g, 3), np.tile(g, 3), -np.ones(9, np.float32)], axis=-1))
+    colour, aov = synthetic(rt3, 12, 16, 5)
+    calls = [lambda r: r.render_aov(cam.c, big), lambda r: r.intersect(rays), lambda r: r.denoise(colour, aov),
+             lambda r: r.render_aov(cam.c, small), lambda r: r.render_path_range(cam.c, p, 0, 3)]
+    set_scene(rt3, renderer, **kw)
+    together = [call(renderer) for call in calls]
+    for i, call in enumerate(calls):
+        alone = rt3.initialize_renderer(0)
+        try:
+            set_scene(rt3, alone, **kw)
+            assert call(alone).tobytes() == together[i].tobytes(), "call %d" % i
+        finally:
+            alone.close()
 
 
 def test_argument_errors(rt3, renderer):

@@ -323,6 +323,7 @@ def test_single_gpu_gather_path(rt3, renderer):
 def test_errors(rt3, renderer):
     case = mode_x_cases()["three_spheres_64x36x16_d8"]
     hip_upload(renderer, case)
+    frame = hip_render(renderer, case, upload=False)
     with pytest.raises(rt3.Fatal):
         hip_render(renderer, case, upload=False, spp=0)
     with pytest.raises(rt3.Fatal):
@@ -331,6 +332,7 @@ def test_errors(rt3, renderer):
     bad[1, 3] = 0.0
     with pytest.raises(rt3.Fatal, match="radius"):
         renderer.set_spheres(bad, case["smats"])
+    assert np.array_equal(hip_render(renderer, case, upload=False), frame)     # the rejected upload left the scene as it was
     renderer.set_mesh(np.zeros(0, rt3.GFACE), np.zeros((0, 4), np.float32))
     renderer.set_spheres(np.zeros((0, 4), np.float32), np.zeros(0, rt3.MATERIAL))
     with pytest.raises(rt3.Fatal, match="no scene"):
