@@ -382,6 +382,40 @@ int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t width, uint32_t height, c
                                 void* d_out_rgba, void* d_out_history, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Motion plane   (per-pixel world-space motion of the scene's primitives for the temporal denoiser)
+ * ------------------------------------------------------------------------------------------------- */
+/* One float4 per pixel of a whole frame, row 0 on top: (mx, my, mz, moved).  m is the world-space displacement from the point the pixel
+ * shows now to where that surface point was in the previous frame; moved is 1.0f or 0.0f ((0, 0, 0, 0): a miss, a primitive that is byte
+ * for byte where it was, a class without a previous array, a degenerate face).  The scene on the context is THIS frame's, the one aov was
+ * rendered from with cam.  The previous frame's geometry comes from the caller, in the caller's order and layout: 4 floats per sphere as
+ * rt3_set_spheres takes them, vec4 vertices as rt3_set_mesh takes them (same topology: the face list is the context's).  Either pointer
+ * may be NULL with a count of 0: that class of primitive did not move.  A non-NULL array's count must equal the context's (the sphere
+ * count; the vertex count of the merged entity buffers that rt3_mesh_download returns), else RT3_E_ARG.  RT3_E_STATE when a non-NULL
+ * array names a class the context has no committed scene of, or when the merged entity buffers were changed after the last commit
+ * (rt3_mesh_begin / rt3_mesh_put / rt3_mesh_sphere without an rt3_mesh_commit).  The previous arrays' values are not validated: a non-finite m
+ * is written as it comes and costs that pixel its history in rt3_denoise_temporal_motion.  Spheres move by translation and uniform
+ * scaling about the centre; a face carries the point's barycentric coordinates to its previous vertices, whatever moved them.
+ * The call never touches the accumulation and leaves rt3_get_stats as it was; streams as for queries; the host form is synchronous.
+ * RT3_E_ARG also for a NULL cam / aov / out_motion, width or height below 2, width x height > 2^26, a camera rt3_denoise_temporal would
+ * refuse, a device pointer that is not 16-byte aligned, or an output that overlaps an input. */
+int rt3_motion(rt3_ctx* ctx, uint32_t width, uint32_t height, const rt3_camera* cam, const rt3_aov* aov,
+               const float* prev_center_radius, uint32_t n_prev_spheres,
+               const float* prev_vertices_xyzw, uint32_t n_prev_vertices, float* out_motion);
+int rt3_motion_device(rt3_ctx* ctx, uint32_t width, uint32_t height, const rt3_camera* cam, const void* d_aov,
+                      const void* d_prev_center_radius, uint32_t n_prev_spheres,
+                      const void* d_prev_vertices_xyzw, uint32_t n_prev_vertices, void* d_out_motion, void* stream);
+/* rt3_denoise_temporal with one more input: motion, the plane rt3_motion wrote for this frame (width x height float4), or NULL.  A pixel
+ * that hit and whose moved is not 0 is reprojected from its previous position (the world point plus m) and is always projected into the
+ * previous camera, also when *prev_cam equals *cam; every other pixel comes out bit for bit as from rt3_denoise_temporal, which is this
+ * call with motion == NULL.  motion takes part in the alignment and overlap checks; without a previous frame it is not read. */
+int rt3_denoise_temporal_motion(rt3_ctx* ctx, uint32_t width, uint32_t height, const rt3_camera* cam, const float* colour_rgba,
+                                const rt3_aov* aov, const rt3_camera* prev_cam, const rt3_history* prev_history, const float* motion,
+                                const rt3_temporal_params* p, float* out_rgba, rt3_history* out_history);
+int rt3_denoise_temporal_motion_device(rt3_ctx* ctx, uint32_t width, uint32_t height, const rt3_camera* cam, const void* d_colour_rgba,
+                                       const void* d_aov, const rt3_camera* prev_cam, const void* d_prev_history, const void* d_motion,
+                                       const rt3_temporal_params* p, void* d_out_rgba, void* d_out_history, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side scene API   (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)
  * ------------------------------------------------------------------------------------------------- */
 /* cpu_pre_render_triangle (src/lib/entities/Triangle.cpp:28-76): 1 face, 3 vertices (xyzw). */

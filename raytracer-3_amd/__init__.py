@@ -139,6 +139,7 @@ EXPORTS = [
     "rt3_intersect", "rt3_occluded", "rt3_intersect_device", "rt3_occluded_device",
     "rt3_camera_rays", "rt3_camera_rays_device", "rt3_render_aov", "rt3_render_aov_device", "rt3_accum_resolve", "rt3_accum_resolve_device",
     "rt3_frame_pfm_bytes", "rt3_frame_to_pfm", "rt3_denoise", "rt3_denoise_device", "rt3_denoise_temporal", "rt3_denoise_temporal_device",
+    "rt3_motion", "rt3_motion_device", "rt3_denoise_temporal_motion", "rt3_denoise_temporal_motion_device",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -201,6 +202,10 @@ def lib():
         "rt3_denoise": (i32, [vp, u32, u32, vp, vp, vp, vp]), "rt3_denoise_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp]),
         "rt3_denoise_temporal": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "rt3_denoise_temporal_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rt3_motion": (i32, [vp, u32, u32, vp, vp, vp, u32, vp, u32, vp]),
+        "rt3_motion_device": (i32, [vp, u32, u32, vp, vp, vp, u32, vp, u32, vp, vp]),
+        "rt3_denoise_temporal_motion": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rt3_denoise_temporal_motion_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -793,11 +798,13 @@ class HipRenderer(Renderer):
         return out
 
     def denoise_temporal(self, colour, aov, camera_c, prev=None, iterations=5, normal_power=128, sigma_luminance=4.0, sigma_depth=1.0,
-                         alpha=0.2, moments_alpha=0.2, depth_tolerance=2.0, normal_tolerance=0.9):
+                         alpha=0.2, moments_alpha=0.2, depth_tolerance=2.0, normal_tolerance=0.9, motion=None):
         """One frame of a sequence through the temporal denoiser (rt3_denoise_temporal) -> (out, history).  colour and aov
         as for denoise, camera_c the rt3_camera they were rendered with; prev None for the first frame, else the history of the previous
         call; history = (records, camera): an (H, W) HISTORY array (numpy) or a contiguous (H, W, 12) float32 GPU tensor (torch), and a copy
-        of camera_c.  torch inputs run on torch.cuda.current_stream()."""
+        of camera_c.  motion: None, or the plane motion() returned for this frame ((H, W, 4) float32, numpy or torch as colour is): pixels of
+        primitives that moved are reprojected from where they were (rt3_denoise_temporal_motion).  torch inputs run on
+        torch.cuda.current_stream()."""
         p = TEMPORAL_PARAMS(DENOISE_PARAMS(iterations, normal_power, sigma_luminance, sigma_depth), alpha, moments_alpha, depth_tolerance,
                             normal_tolerance)
         cam = rt3_camera.from_buffer_copy(bytes(camera_c))
@@ -815,12 +822,16 @@ class HipRenderer(Renderer):
                 if (not type(t).__module__.startswith("torch") or not t.is_cuda or t.dim() < 2 or tuple(t.shape[:2]) != (h, w)
                         or t.numel() * t.element_size() != h * w * 48 or not t.is_contiguous()):
                     raise Fatal("device %s must be a contiguous tensor of (H, W) 48-byte records on the GPU" % what)
+            if motion is not None and (not type(motion).__module__.startswith("torch") or not motion.is_cuda or motion.dtype != torch.float32
+                                       or tuple(motion.shape) != (h, w, 4) or not motion.is_contiguous()):
+                raise Fatal("device motion must be a contiguous (H, W, 4) float32 tensor on the GPU")
             out = torch.empty_like(colour)
             hist = torch.empty((h, w, 12), dtype=torch.float32, device=colour.device)
             stream = torch.cuda.current_stream(colour.device).cuda_stream
-            self._check(lib().rt3_denoise_temporal_device(
+            self._check(lib().rt3_denoise_temporal_motion_device(
                 self._ctx, w, h, C.byref(cam), C.c_void_p(colour.data_ptr()), C.c_void_p(aov.data_ptr()), pc,
-                C.c_void_p(prev_rec.data_ptr()) if prev_rec is not None else None, C.byref(p), C.c_void_p(out.data_ptr()),
+                C.c_void_p(prev_rec.data_ptr()) if prev_rec is not None else None,
+                C.c_void_p(motion.data_ptr()) if motion is not None else None, C.byref(p), C.c_void_p(out.data_ptr()),
                 C.c_void_p(hist.data_ptr()), C.c_void_p(stream)))
             return out, (hist, cam)
         c = np.ascontiguousarray(colour, np.float32)
@@ -833,10 +844,53 @@ class HipRenderer(Renderer):
             pr = np.ascontiguousarray(prev_rec)
             if pr.dtype != HISTORY or pr.shape != (h, w):
                 raise Fatal("denoise_temporal: the previous history must be an (H, W) HISTORY array")
+        mo = None
+        if motion is not None:
+            mo = np.ascontiguousarray(motion, np.float32)
+            if mo.shape != (h, w, 4):
+                raise Fatal("denoise_temporal: motion must be float32 (H, W, 4)")
         out = np.zeros((h, w, 4), np.float32)
         hist = np.zeros((h, w), HISTORY)
-        self._check(lib().rt3_denoise_temporal(self._ctx, w, h, C.byref(cam), _p(c), _p(a), pc, _p(pr), C.byref(p), _p(out), _p(hist)))
+        self._check(lib().rt3_denoise_temporal_motion(self._ctx, w, h, C.byref(cam), _p(c), _p(a), pc, _p(pr), _p(mo), C.byref(p), _p(out),
+                                                      _p(hist)))
         return out, (hist, cam)
+
+    def motion(self, aov, camera_c, prev_center_radius=None, prev_vertices=None):
+        """The motion plane of one frame (rt3_motion) -> (H, W, 4) float32, (mx, my, mz, moved) per pixel.  The scene on this
+        renderer is the frame's own, aov its AOVs and camera_c its camera; prev_center_radius ((n_spheres, 4)) and prev_vertices
+        ((n_vertices, 4), the merged vertices as mesh_download returns them) are the previous frame's, None for a class that did not move.
+        numpy: aov an (H, W) AOV array.  torch: a contiguous tensor of (H, W) 48-byte records and contiguous float32 GPU tensors for the
+        previous arrays -> a new tensor, computed on torch.cuda.current_stream()."""
+        cam = rt3_camera.from_buffer_copy(bytes(camera_c))
+        if type(aov).__module__.startswith("torch"):
+            import torch
+            if not aov.is_cuda or aov.dim() < 2 or aov.numel() * aov.element_size() != aov.shape[0] * aov.shape[1] * 48 or not aov.is_contiguous():
+                raise Fatal("device AOVs must be a contiguous tensor of (H, W) 48-byte records on the GPU")
+            h, w = aov.shape[:2]
+            ptrs = []
+            for t, what in ((prev_center_radius, "prev_center_radius"), (prev_vertices, "prev_vertices")):
+                if t is None:
+                    ptrs += [None, 0]
+                    continue
+                if (not type(t).__module__.startswith("torch") or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 4
+                        or not t.is_contiguous()):
+                    raise Fatal("device %s must be a contiguous (N, 4) float32 tensor on the GPU" % what)
+                ptrs += [C.c_void_p(t.data_ptr()), t.shape[0]]
+            out = torch.empty((h, w, 4), dtype=torch.float32, device=aov.device)
+            stream = torch.cuda.current_stream(aov.device).cuda_stream
+            self._check(lib().rt3_motion_device(self._ctx, w, h, C.byref(cam), C.c_void_p(aov.data_ptr()), *ptrs, C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(stream)))
+            return out
+        a = np.ascontiguousarray(aov)
+        if a.dtype != AOV or a.ndim != 2:
+            raise Fatal("motion: aov must be an (H, W) AOV array")
+        h, w = a.shape
+        ps = None if prev_center_radius is None else np.ascontiguousarray(prev_center_radius, np.float32).reshape(-1, 4)
+        pv = None if prev_vertices is None else np.ascontiguousarray(prev_vertices, np.float32).reshape(-1, 4)
+        out = np.zeros((h, w, 4), np.float32)
+        self._check(lib().rt3_motion(self._ctx, w, h, C.byref(cam), _p(a), _p(ps), 0 if ps is None else len(ps), _p(pv),
+                                     0 if pv is None else len(pv), _p(out)))
+        return out
 
     def set_sample_storage_cap(self, nbytes):
         self._check(lib().rt3_set_sample_storage_cap(self._ctx, nbytes))

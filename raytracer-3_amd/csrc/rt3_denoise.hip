@@ -228,12 +228,15 @@ __device__ __forceinline__ float dn_dot(float ax, float ay, float az, float bx, 
 
 // DESIGN.md 4.12 steps 1-5 (in place of k_denoise_prepare): colour, rt3_aov records and the previous history -> il = (I.rgb, L(I)) of the
 // blended I, the guide and gz planes as k_denoise_prepare writes them, and the history record of the pixel with (I, length) in its first
-// float4 (pass 0 replaces I), (M1, M2, depth, 0) and (normal, 0).
+// float4 (pass 0 replaces I), (M1, M2, depth, 0) and (normal, 0).  MOTION: a pixel that hit and whose motion record
+// (m, moved) has moved != 0 adds m to its world point and is projected even under a byte-equal camera; every other pixel takes the
+// operations of the MOTION = false kernel.
+template <bool MOTION>
 __global__ __launch_bounds__(kDnTile * kDnTile) void k_temporal_reproject(const DenoiseArgs D, const TemporalArgs T,
                                                                          const float4* __restrict__ colour, const float4* __restrict__ aov,
                                                                          const float4* __restrict__ prev, float4* __restrict__ il,
                                                                          float4* __restrict__ guide, float* __restrict__ gz,
-                                                                         float4* __restrict__ hist) {
+                                                                         float4* __restrict__ hist, const float4* __restrict__ motion) {
     int x, y;
     if (!dn_pixel(D, x, y)) return;
     const int W = (int)D.width, H = (int)D.height;
@@ -265,13 +268,23 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_temporal_reproject(const 
         const float inv = 1.0f / __builtin_sqrtf(dn_dot(dx, dy, dz, dx, dy, dz));
         const float ux = dx * inv, uy = dy * inv, uz = dz * inv;
         const bool hit = !__builtin_isinf(n.w);
-        const float rx = hit ? (T.ox + n.w * ux) - T.pox : ux;
-        const float ry = hit ? (T.oy + n.w * uy) - T.poy : uy;
-        const float rz = hit ? (T.oz + n.w * uz) - T.poz : uz;
-        // 3: project into the previous camera (skipped for a byte-equal camera: every pixel maps to itself)
+        float rx = hit ? (T.ox + n.w * ux) - T.pox : ux;
+        float ry = hit ? (T.oy + n.w * uy) - T.poy : uy;
+        float rz = hit ? (T.oz + n.w * uz) - T.poz : uz;
+        bool moved = false;
+        if (MOTION && hit) {
+            const float4 m = motion[p];
+            moved = m.w != 0.0f;
+            if (moved) {
+                rx = ((T.ox + n.w * ux) + m.x) - T.pox;
+                ry = ((T.oy + n.w * uy) + m.y) - T.poy;
+                rz = ((T.oz + n.w * uz) + m.z) - T.poz;
+            }
+        }
+        // 3: project into the previous camera (skipped for a byte-equal camera: every pixel that has not moved maps to itself)
         float xp = (float)x, yp = (float)y;
         bool ok = true;
-        if (!T.same_cam) {
+        if (!T.same_cam || moved) {
             const float sc = T.ln / dn_dot(rx, ry, rz, T.nx, T.ny, T.nz);
             ok = __builtin_isfinite(sc) && sc > 0.0f;
             const float px = sc * rx - T.plx, py = sc * ry - T.ply, pz = sc * rz - T.plz;
@@ -328,6 +341,86 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_temporal_reproject(const 
     hist[3 * (size_t)p] = make_float4(o.x, o.y, o.z, len);
     hist[3 * (size_t)p + 1] = make_float4(m1, m2, n.w, 0.0f);
     hist[3 * (size_t)p + 2] = make_float4(n.x, n.y, n.z, 0.0f);
+}
+
+// What k_motion reads: this frame's camera, the context's current primitives in the caller's order and the caller's
+// previous ones (nullptr: that class did not move).
+struct MotionArgs {
+    uint32_t width, height, tiles_x;
+    uint32_t n_sph, n_faces, n_verts;
+    float ox, oy, oz, hx, hy, hz, vx, vy, vz, lx, ly, lz;      // this frame's camera
+    const float4* __restrict__ aov;                            // rt3_aov records (3 float4 each)
+    const float4* __restrict__ sph;                            // (C, r) as rt3_set_spheres took them
+    const float* __restrict__ sph_invr;                        // 1 / r
+    const float4* __restrict__ prev_sph;                       // (C', r'), or nullptr
+    const uint4* __restrict__ gfaces;                          // rt3_gface records (3 x 16 bytes each; the first holds v1, v2, v3)
+    const float4* __restrict__ verts;                          // the merged vertices
+    const float4* __restrict__ prev_verts;                     // the previous vertices, or nullptr
+};
+
+// per pixel the world-space displacement from the point it shows to where that surface point was in the previous frame,
+// (mx, my, mz, 1), or (0, 0, 0, 0) where nothing moved or nothing is known.  Every gather index is checked against its buffer first.
+__global__ __launch_bounds__(kDnTile * kDnTile) void k_motion(const MotionArgs M, float4* __restrict__ out) {
+    const uint32_t ty = blockIdx.x / M.tiles_x, tx = blockIdx.x - ty * M.tiles_x;
+    const int x = (int)(tx * kDnTile + threadIdx.x), y = (int)(ty * kDnTile + threadIdx.y);
+    const int W = (int)M.width, H = (int)M.height;
+    if (x >= W || y >= H) return;
+    const uint32_t p = (uint32_t)(y * W + x);
+    const float z = M.aov[3 * (size_t)p + 1].w;
+    const float4 ki = M.aov[3 * (size_t)p + 2];
+    const uint32_t kind = __float_as_uint(ki.x), index = __float_as_uint(ki.y);
+    float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const bool sphere = kind == 2u && M.prev_sph && index < M.n_sph;            // RT3_HIT_SPHERE
+    const bool face = kind == 1u && M.prev_verts && index < M.n_faces;          // RT3_HIT_FACE
+    if (!__builtin_isinf(z) && (sphere || face)) {
+        // 2: the shown point on the pixel-centre ray (4.12 step 2)
+        const float u = (float)x / ((float)W - 1.0f), v = (float)(H - 1 - y) / ((float)H - 1.0f);
+        const float dx = ((M.lx + u * M.hx) + v * M.vx) - M.ox;
+        const float dy = ((M.ly + u * M.hy) + v * M.vy) - M.oy;
+        const float dz = ((M.lz + u * M.hz) + v * M.vz) - M.oz;
+        const float inv = 1.0f / __builtin_sqrtf(dn_dot(dx, dy, dz, dx, dy, dz));
+        const float px = M.ox + z * (dx * inv), py = M.oy + z * (dy * inv), pz = M.oz + z * (dz * inv);
+        if (sphere) {
+            // 3: translation and uniform scaling about the centre
+            const float4 c = M.sph[index], q = M.prev_sph[index];
+            const bool same = __float_as_uint(c.x) == __float_as_uint(q.x) && __float_as_uint(c.y) == __float_as_uint(q.y) &&
+                              __float_as_uint(c.z) == __float_as_uint(q.z) && __float_as_uint(c.w) == __float_as_uint(q.w);
+            if (!same) {
+                const float k = q.w * M.sph_invr[index];
+                const float qx = q.x + (px - c.x) * k, qy = q.y + (py - c.y) * k, qz = q.z + (pz - c.z) * k;
+                o = make_float4(qx - px, qy - py, qz - pz, 1.0f);
+            }
+        } else {
+            // 4: the barycentrics of P in the current triangle, applied to the previous one
+            const uint4 f = M.gfaces[3 * (size_t)index];
+            if (f.x < M.n_verts && f.y < M.n_verts && f.z < M.n_verts) {
+                const float4 a = M.verts[f.x], b = M.verts[f.y], c = M.verts[f.z];
+                const float4 a1 = M.prev_verts[f.x], b1 = M.prev_verts[f.y], c1 = M.prev_verts[f.z];
+                const bool same = __float_as_uint(a.x) == __float_as_uint(a1.x) && __float_as_uint(a.y) == __float_as_uint(a1.y) &&
+                                  __float_as_uint(a.z) == __float_as_uint(a1.z) && __float_as_uint(b.x) == __float_as_uint(b1.x) &&
+                                  __float_as_uint(b.y) == __float_as_uint(b1.y) && __float_as_uint(b.z) == __float_as_uint(b1.z) &&
+                                  __float_as_uint(c.x) == __float_as_uint(c1.x) && __float_as_uint(c.y) == __float_as_uint(c1.y) &&
+                                  __float_as_uint(c.z) == __float_as_uint(c1.z);
+                if (!same) {
+                    const float e1x = b.x - a.x, e1y = b.y - a.y, e1z = b.z - a.z;
+                    const float e2x = c.x - a.x, e2y = c.y - a.y, e2z = c.z - a.z;
+                    const float wx = px - a.x, wy = py - a.y, wz = pz - a.z;
+                    const float d00 = dn_dot(e1x, e1y, e1z, e1x, e1y, e1z), d01 = dn_dot(e1x, e1y, e1z, e2x, e2y, e2z);
+                    const float d11 = dn_dot(e2x, e2y, e2z, e2x, e2y, e2z);
+                    const float d20 = dn_dot(wx, wy, wz, e1x, e1y, e1z), d21 = dn_dot(wx, wy, wz, e2x, e2y, e2z);
+                    const float den = d00 * d11 - d01 * d01;
+                    if (den != 0.0f) {
+                        const float b2 = (d11 * d20 - d01 * d21) / den, b3 = (d00 * d21 - d01 * d20) / den;
+                        const float qx = (a1.x + b2 * (b1.x - a1.x)) + b3 * (c1.x - a1.x);
+                        const float qy = (a1.y + b2 * (b1.y - a1.y)) + b3 * (c1.y - a1.y);
+                        const float qz = (a1.z + b2 * (b1.z - a1.z)) + b3 * (c1.z - a1.z);
+                        o = make_float4(qx - px, qy - py, qz - pz, 1.0f);
+                    }
+                }
+            }
+        }
+    }
+    out[p] = o;
 }
 
 }  // namespace
@@ -395,8 +488,10 @@ hipError_t temporal_launch(const TemporalLaunch& T, hipStream_t stream) {
     const dim3 grid(D.tiles_x * ((h + kDnTile - 1) / kDnTile)), block(kDnTile, kDnTile);
     const float4* aov = (const float4*)L.aov;
     float4* const hist = (float4*)T.out_history;
-    hipLaunchKernelGGL(k_temporal_reproject, grid, block, 0, stream, D, A, (const float4*)L.colour, aov, (const float4*)T.prev_history, pa,
-                       guide, gz, hist);
+    if (T.motion) hipLaunchKernelGGL(k_temporal_reproject<true>, grid, block, 0, stream, D, A, (const float4*)L.colour, aov,
+                                     (const float4*)T.prev_history, pa, guide, gz, hist, (const float4*)T.motion);
+    else hipLaunchKernelGGL(k_temporal_reproject<false>, grid, block, 0, stream, D, A, (const float4*)L.colour, aov,
+                            (const float4*)T.prev_history, pa, guide, gz, hist, nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_denoise_moments<true>, grid, block, 0, stream, D, (const float4*)pa, pb, (const float4*)hist);
@@ -413,4 +508,21 @@ hipError_t temporal_launch(const TemporalLaunch& T, hipStream_t stream) {
         float4* t = src; src = dst; dst = t;
     }
     return hipSuccess;
+}
+
+hipError_t motion_launch(const MotionLaunch& L, hipStream_t stream) {
+    MotionArgs M;
+    M.width = L.width; M.height = L.height;
+    M.tiles_x = (L.width + kDnTile - 1) / kDnTile;
+    M.n_sph = L.n_sph; M.n_faces = L.n_faces; M.n_verts = L.n_verts;
+    M.ox = L.cam[0]; M.oy = L.cam[1]; M.oz = L.cam[2];
+    M.hx = L.cam[3]; M.hy = L.cam[4]; M.hz = L.cam[5];
+    M.vx = L.cam[6]; M.vy = L.cam[7]; M.vz = L.cam[8];
+    M.lx = L.cam[9]; M.ly = L.cam[10]; M.lz = L.cam[11];
+    M.aov = (const float4*)L.aov;
+    M.sph = (const float4*)L.sph; M.sph_invr = L.sph_invr; M.prev_sph = (const float4*)L.prev_sph;
+    M.gfaces = (const uint4*)L.gfaces; M.verts = (const float4*)L.verts; M.prev_verts = (const float4*)L.prev_verts;
+    const dim3 grid(M.tiles_x * ((L.height + kDnTile - 1) / kDnTile)), block(kDnTile, kDnTile);
+    hipLaunchKernelGGL(k_motion, grid, block, 0, stream, M, (float4*)L.out);
+    return hipGetLastError();
 }

@@ -1,4 +1,4 @@
-// rt3_denoise.hpp — what rt3_device.hip needs of the denoiser (rt3_denoise.hip, DESIGN.md 4.11, 4.12, 5.2h and 5.2i): its launchers.
+// rt3_denoise.hpp — what rt3_device.hip needs of the denoiser (rt3_denoise.hip, DESIGN.md 4.11 to 4.13, 5.2h to 5.2j): its launchers.
 #pragma once
 
 // One rt3_denoise_device call once its arguments have been checked: k_denoise_prepare, k_denoise_moments and `iterations` a-trous passes on
@@ -26,5 +26,24 @@ struct TemporalLaunch {
     float alpha, moments_alpha, depth_tolerance, normal_tolerance;
     const void* prev_history;               // width * height rt3_history (3 float4 each), or nullptr without has_prev
     void* out_history;                      // width * height rt3_history
+    const void* motion;                     // width * height float4 (m, moved) as motion_launch writes them, or nullptr
 };
 hipError_t temporal_launch(const TemporalLaunch& L, hipStream_t stream);
+
+// One rt3_motion_device call once its arguments have been checked: k_motion on `stream`.  A class whose prev_* pointer is
+// nullptr did not move; the counts bound every gather (a face index >= n_faces, a sphere index >= n_sph and a vertex index >= n_verts are
+// never followed).
+struct MotionLaunch {
+    uint32_t width, height;
+    float cam[12];                          // this frame's rt3_camera
+    const void* aov;                        // width * height rt3_aov
+    const void* sph;                        // n_sph float4 (C, r): the records rt3_set_spheres took
+    const float* sph_invr;                  // n_sph reciprocal radii
+    const void* prev_sph;                   // n_sph float4 (C', r'), or nullptr
+    const void* gfaces;                     // n_faces rt3_gface: the merged faces
+    const void* verts;                      // n_verts float4: the merged vertices
+    const void* prev_verts;                 // n_verts float4, or nullptr
+    uint32_t n_sph, n_faces, n_verts;
+    void* out;                              // width * height float4
+};
+hipError_t motion_launch(const MotionLaunch& L, hipStream_t stream);

@@ -14,7 +14,7 @@
 //   rt3_reduce.hpp          per-sample radiance (SampleStorage of raytracer_v4.glsl:107-111) summed in sample order and resolved
 //                           (the reduce pass reduce_v1.glsl never got) — the image is bitwise independent of scheduling and GPU count
 //   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve
-//   rt3_denoise.hpp         the launchers of the AOV-guided a-trous denoiser and its temporal form (kernels: rt3_denoise.hip)
+//   rt3_denoise.hpp         the launchers of the AOV-guided a-trous denoiser, its temporal form and the motion plane (kernels: rt3_denoise.hip)
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
 //   below                   the device context and the extern "C" entry points
 //
@@ -89,10 +89,13 @@ struct rt3_ctx {
     DevBuf<float4> d_tri, d_tri_mat, d_tri_bound; DevBuf<uint32_t> d_tri_kind; DevBuf<u32x4> d_tri_frag;
     // merged entity buffers on the device (GFace[] / vec4[] as the reference keeps them), filled by rt3_mesh_*; their sizes bound rt3_mesh_put
     DevBuf<rt3_gface> d_gfaces; DevBuf<float4> d_verts;
+    bool mesh_in_sync = false;                                      // d_gfaces / d_verts are what the committed faces were built from (rt3_motion reads them)
     DevBuf<rt3_material> d_face_mats_in; DevBuf<uint32_t> d_error;
     // spheres
     uint32_t n_sph = 0;
     DevBuf<float4> d_sph; DevBuf<uint32_t> d_sph_frag, d_sph_frag32; float sph_centre[3] = { 0.0f, 0.0f, 0.0f }; uint32_t n_direct = 0; uint32_t direct[4] = { 0, 0, 0, 0 }; float tri_centre[3] = { 0.0f, 0.0f, 0.0f }; DevBuf<uint32_t> d_box; DevBuf<u32x4> d_tri_frag_r; DevBuf<float> d_sph_invr; DevBuf<float4> d_sph_mat; DevBuf<uint32_t> d_sph_kind;
+
+    DevBuf<float4> d_sph_cr;                                        // (C, r) as the caller gave them, in the caller's order (rt3_motion compares and scales by them)
 
     // rows of the multi-level filter: faces and spheres, each in the order of a spatial median split
     FilterRows tri, sph;
@@ -778,6 +781,7 @@ int rt3_debug_force_plain_mode_r(rt3_ctx* ctx, int on) {
 int rt3_mesh_begin(rt3_ctx* ctx, uint32_t n_faces, uint32_t n_vertices) {
     if (!ctx) return RT3_E_ARG;
     RT3_HIP(hipSetDevice(ctx->device));
+    ctx->mesh_in_sync = false;
     int rc;
     if ((rc = ctx->d_gfaces.alloc(ctx, n_faces)) || (rc = ctx->d_verts.alloc(ctx, n_vertices))) return rc;
     if (n_faces) RT3_HIP(hipMemsetAsync(ctx->d_gfaces, 0, (size_t)n_faces * sizeof(rt3_gface), ctx->stream));
@@ -792,6 +796,7 @@ int rt3_mesh_put(rt3_ctx* ctx, const rt3_gface* faces, uint32_t n_faces, const f
     if ((uint64_t)face_offset + n_faces > ctx->d_gfaces.size() || (uint64_t)vertex_offset + n_vertices > ctx->d_verts.size())
         return fail(ctx, RT3_E_ARG, "rt3_mesh_put: entity does not fit in the buffers sized by rt3_mesh_begin");
     RT3_HIP(hipSetDevice(ctx->device));
+    ctx->mesh_in_sync = false;
     std::vector<rt3_gface> rebased(faces, faces + n_faces);         // transfer_entity: indices += running vertex count
     for (rt3_gface& f : rebased) { f.v1 += vertex_offset; f.v2 += vertex_offset; f.v3 += vertex_offset; }
     if (n_faces) RT3_HIP(hipMemcpyAsync(ctx->d_gfaces + face_offset, rebased.data(), (size_t)n_faces * sizeof(rt3_gface), hipMemcpyHostToDevice, ctx->stream));
@@ -808,6 +813,7 @@ int rt3_mesh_sphere(rt3_ctx* ctx, const float center[3], float radius, uint32_t 
     if ((uint64_t)face_offset + nf > ctx->d_gfaces.size() || (uint64_t)vertex_offset + nv > ctx->d_verts.size())
         return fail(ctx, RT3_E_ARG, "rt3_mesh_sphere: entity does not fit in the buffers sized by rt3_mesh_begin");
     RT3_HIP(hipSetDevice(ctx->device));
+    ctx->mesh_in_sync = false;
     const SphereGen g{ center[0], center[1], center[2], radius, n_meridians, n_parallels, color[0], color[1], color[2], face_offset, vertex_offset };
     const dim3 blk(32, 8);
     hipLaunchKernelGGL(k_prerender_sphere_vertices, dim3((n_meridians + 31) / 32, (n_parallels + 7) / 8), blk, 0, ctx->stream, g, ctx->d_verts);
@@ -823,6 +829,7 @@ int rt3_mesh_commit(rt3_ctx* ctx, const rt3_material* face_materials) {
     RT3_HIP(hipSetDevice(ctx->device));
     const uint32_t n = (uint32_t)ctx->d_gfaces.size(), n_pad = (n + 3u) / 4u * 4u, n_verts = (uint32_t)ctx->d_verts.size();
     ctx->n_faces = 0;
+    ctx->mesh_in_sync = false;
     ctx->tri = FilterRows();
     for (DevBuf<float4>* b : { &ctx->d_tri, &ctx->d_tri_mat, &ctx->d_tri_bound, &ctx->d_tri_rec }) b->reset();
     ctx->d_tri_kind.reset(); ctx->d_tri_frag.reset(); ctx->d_tri_frag_r.reset(); ctx->d_face_mats_in.reset();
@@ -884,6 +891,7 @@ int rt3_mesh_commit(rt3_ctx* ctx, const rt3_material* face_materials) {
     RT3_HIP(hipGetLastError());
     RT3_HIP(hipStreamSynchronize(ctx->stream));                     // a render may come on another stream
     ctx->n_faces = n;
+    ctx->mesh_in_sync = true;
     return 0;
 }
 
@@ -910,7 +918,7 @@ int rt3_set_spheres(rt3_ctx* ctx, const float* center_radius, const rt3_material
     if (!ctx) return RT3_E_ARG;
     if (n != 0 && (!center_radius || !materials)) return fail(ctx, RT3_E_ARG, "center_radius / materials is NULL");
     RT3_HIP(hipSetDevice(ctx->device));
-    std::vector<float4> sph(((size_t)n + 3) / 4 * 4, kPadSphere), mat(n);                 // scan works in groups of 4
+    std::vector<float4> sph(((size_t)n + 3) / 4 * 4, kPadSphere), mat(n), cr(n);          // scan works in groups of 4
     std::vector<float> invr(n);
     std::vector<uint32_t> kind(n);
     for (uint32_t i = 0; i < n; i++) {
@@ -918,6 +926,7 @@ int rt3_set_spheres(rt3_ctx* ctx, const float* center_radius, const rt3_material
         if (!(s[3] > 0.0f)) return fail(ctx, RT3_E_ARG, "sphere " + std::to_string(i) + " has a non-positive radius");
         if (materials[i].kind > RT3_MAT_DIELECTRIC) return fail(ctx, RT3_E_ARG, "unknown material kind");
         sph[i] = make_float4(s[0], s[1], s[2], s[3] * s[3]);
+        cr[i] = make_float4(s[0], s[1], s[2], s[3]);
         invr[i] = 1.0f / s[3];
         mat[i] = pack_material(materials[i]);
         kind[i] = materials[i].kind;
@@ -929,7 +938,7 @@ int rt3_set_spheres(rt3_ctx* ctx, const float* center_radius, const rt3_material
     if ((rc = ctx->d_sph_frag.upload(ctx, build_sphere_frags(center_radius, n, ctx->sph_centre, ctx->direct, ctx->n_direct)))) return rc;      // k_trace_mfma (K = 64, 32x32x16)
     if ((rc = ctx->d_sph_frag32.upload(ctx, build_sphere_frags32(center_radius, n, ctx->sph_centre, ctx->direct, ctx->n_direct)))) return rc;  // K = 32 form
     if ((rc = ctx->d_sph.upload(ctx, sph)) || (rc = ctx->d_sph_invr.upload(ctx, invr)) || (rc = ctx->d_sph_mat.upload(ctx, mat)) ||
-        (rc = ctx->d_sph_kind.upload(ctx, kind)))
+        (rc = ctx->d_sph_kind.upload(ctx, kind)) || (rc = ctx->d_sph_cr.upload(ctx, cr)))
         return rc;
     // rows of the multi-level filter: groups of kGroupSph spheres in the order of a spatial median split
     const std::vector<uint32_t> order = sphere_group_order(center_radius, n, ctx->direct, ctx->n_direct, kGroupSph, kSuper);
@@ -1509,8 +1518,8 @@ static bool camera_ok(const rt3_camera* c) {
 }
 
 static int temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* colour, const void* aov,
-                           const rt3_camera* prev_cam, const void* prev_history, const rt3_temporal_params* p, const void* out,
-                           const void* out_history) {
+                           const rt3_camera* prev_cam, const void* prev_history, const void* motion, const rt3_temporal_params* p,
+                           const void* out, const void* out_history) {
     if (!p || !cam) return fail(ctx, RT3_E_ARG, "p / cam is NULL");
     if (!colour || !aov || !out || !out_history) return fail(ctx, RT3_E_ARG, "colour / aov / out / out_history is NULL");
     if (!prev_cam != !prev_history) return fail(ctx, RT3_E_ARG, "prev_cam and prev_history must both be NULL or both be non-NULL");
@@ -1524,7 +1533,7 @@ static int temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camer
     if (!camera_ok(cam) || (prev_cam && !camera_ok(prev_cam)))
         return fail(ctx, RT3_E_ARG, "a camera has a non-finite field, horizontal x vertical = 0, or an image plane through its origin");
     const size_t npix = (size_t)w * h, nf = npix * sizeof(float4), nh = npix * sizeof(rt3_history);
-    const struct { const void* ptr; size_t n; } in[3] = { { colour, nf }, { aov, npix * sizeof(rt3_aov) }, { prev_history, nh } };
+    const struct { const void* ptr; size_t n; } in[4] = { { colour, nf }, { aov, npix * sizeof(rt3_aov) }, { prev_history, nh }, { motion, nf } };
     for (const auto& i : in)
         if (i.ptr && (ranges_overlap(out, nf, i.ptr, i.n) || ranges_overlap(out_history, nh, i.ptr, i.n)))
             return fail(ctx, RT3_E_ARG, "an output overlaps an input");
@@ -1535,13 +1544,14 @@ static int temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camer
 // k_temporal_reproject -> k_denoise_moments<true> -> the passes (pass 0 also writes the history colour); the same scratch as rt3_denoise.
 // The projection constants of DESIGN.md 4.12 step 3, in f32 in this order: L = llc' - o', n = h x v, a_u = (v x n) / (h . (v x n)),
 // a_v = (n x h) / (v . (n x h)) component by component, then L . n.
-int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_colour, const void* d_aov,
-                                const rt3_camera* prev_cam, const void* d_prev_history, const rt3_temporal_params* p, void* d_out,
-                                void* d_out_history, void* stream_) {
+// d_motion: the plane rt3_motion wrote, or NULL; without a previous frame it is checked and not read.
+int rt3_denoise_temporal_motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_colour, const void* d_aov,
+                                       const rt3_camera* prev_cam, const void* d_prev_history, const void* d_motion,
+                                       const rt3_temporal_params* p, void* d_out, void* d_out_history, void* stream_) {
     if (!ctx) return RT3_E_ARG;
-    int rc = temporal_checks(ctx, w, h, cam, d_colour, d_aov, prev_cam, d_prev_history, p, d_out, d_out_history);
+    int rc = temporal_checks(ctx, w, h, cam, d_colour, d_aov, prev_cam, d_prev_history, d_motion, p, d_out, d_out_history);
     if (rc) return rc;
-    if (((uintptr_t)d_colour | (uintptr_t)d_aov | (uintptr_t)d_prev_history | (uintptr_t)d_out | (uintptr_t)d_out_history) % 16u != 0)
+    if (((uintptr_t)d_colour | (uintptr_t)d_aov | (uintptr_t)d_prev_history | (uintptr_t)d_motion | (uintptr_t)d_out | (uintptr_t)d_out_history) % 16u != 0)
         return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
     const size_t npix = (size_t)w * h;
     TemporalLaunch T{};
@@ -1567,6 +1577,7 @@ int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_
     T.alpha = p->alpha; T.moments_alpha = p->moments_alpha; T.depth_tolerance = p->depth_tolerance; T.normal_tolerance = p->normal_tolerance;
     T.prev_history = d_prev_history;
     T.out_history = d_out_history;
+    T.motion = prev_cam ? d_motion : nullptr;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream)) || (rc = ctx->d_dn.ensure(ctx, 3 * npix + (npix + 3) / 4))) return rc;     // the scratch is the context's
     T.base.scratch = ctx->d_dn;
@@ -1574,32 +1585,118 @@ int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_
     return leave(ctx, stream);
 }
 
-// The host form: colour, AOVs, both histories and the result on the device in ctx->stage (11 float4 per pixel).
-int rt3_denoise_temporal(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
-                         const rt3_camera* prev_cam, const rt3_history* prev_history, const rt3_temporal_params* p, float* out,
-                         rt3_history* out_history) {
+int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_colour, const void* d_aov,
+                                const rt3_camera* prev_cam, const void* d_prev_history, const rt3_temporal_params* p, void* d_out,
+                                void* d_out_history, void* stream_) {
+    return rt3_denoise_temporal_motion_device(ctx, w, h, cam, d_colour, d_aov, prev_cam, d_prev_history, nullptr, p, d_out, d_out_history, stream_);
+}
+
+// The host form: colour, AOVs, both histories, the result and the motion plane on the device in ctx->stage (12 float4 per pixel).
+int rt3_denoise_temporal_motion(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
+                                const rt3_camera* prev_cam, const rt3_history* prev_history, const float* motion,
+                                const rt3_temporal_params* p, float* out, rt3_history* out_history) {
     if (!ctx) return RT3_E_ARG;
-    int rc = temporal_checks(ctx, w, h, cam, colour, aov, prev_cam, prev_history, p, out, out_history);
+    int rc = temporal_checks(ctx, w, h, cam, colour, aov, prev_cam, prev_history, motion, p, out, out_history);
     if (rc) return rc;
     RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)w * h;
-    if ((rc = ctx->stage.ensure(ctx, 11 * npix))) return rc;
+    if ((rc = ctx->stage.ensure(ctx, (motion ? 12 : 11) * npix))) return rc;
     float4* const dc = ctx->stage;
     float4* const da = dc + npix;
     float4* const dprev = da + 3 * npix;
     float4* const dhist = dprev + 3 * npix;
     float4* const dout = dhist + 3 * npix;
+    float4* const dmot = dout + npix;
+    if (motion) RT3_HIP(hipMemcpyAsync(dmot, motion, npix * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
     RT3_HIP(hipMemcpyAsync(dc, colour, npix * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
     RT3_HIP(hipMemcpyAsync(da, aov, npix * sizeof(rt3_aov), hipMemcpyHostToDevice, ctx->stream));
     if (prev_history) RT3_HIP(hipMemcpyAsync(dprev, prev_history, npix * sizeof(rt3_history), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = rt3_denoise_temporal_device(ctx, w, h, cam, dc, da, prev_cam, prev_history ? dprev : nullptr, p, dout, dhist, ctx->stream))) return rc;
+    if ((rc = rt3_denoise_temporal_motion_device(ctx, w, h, cam, dc, da, prev_cam, prev_history ? dprev : nullptr, motion ? dmot : nullptr, p, dout,
+                                                 dhist, ctx->stream)))
+        return rc;
     RT3_HIP(hipMemcpyAsync(out, dout, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     RT3_HIP(hipMemcpyAsync(out_history, dhist, npix * sizeof(rt3_history), hipMemcpyDeviceToHost, ctx->stream));
     RT3_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
+
+int rt3_denoise_temporal(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
+                         const rt3_camera* prev_cam, const rt3_history* prev_history, const rt3_temporal_params* p, float* out,
+                         rt3_history* out_history) {
+    return rt3_denoise_temporal_motion(ctx, w, h, cam, colour, aov, prev_cam, prev_history, nullptr, p, out, out_history);
+}
 static_assert(sizeof(rt3_history) == 48, "rt3.h: rt3_history");
 static_assert(sizeof(rt3_temporal_params) == 32, "rt3.h: rt3_temporal_params");
+
+// ---- The motion plane
+// What both forms check: the frame, the camera, and the previous arrays against the scene on the context.
+static int motion_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* aov, const void* prev_sph, uint32_t n_prev_sph,
+                         const void* prev_verts, uint32_t n_prev_verts, const void* out) {
+    if (!cam || !aov || !out) return fail(ctx, RT3_E_ARG, "cam / aov / out_motion is NULL");
+    if (w < 2 || h < 2 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must be at least 2 x 2 and have at most 2^26 pixels");
+    if (!camera_ok(cam))
+        return fail(ctx, RT3_E_ARG, "the camera has a non-finite field, horizontal x vertical = 0, or an image plane through its origin");
+    if ((!prev_sph && n_prev_sph) || (!prev_verts && n_prev_verts)) return fail(ctx, RT3_E_ARG, "a NULL previous array must have a count of 0");
+    if (prev_sph && ctx->n_sph == 0) return fail(ctx, RT3_E_STATE, "previous spheres were given, but the context has no spheres");
+    if (prev_verts && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "previous vertices were given, but the context has no committed mesh");
+    if (prev_verts && !ctx->mesh_in_sync)
+        return fail(ctx, RT3_E_STATE, "the merged entity buffers were changed after the last rt3_mesh_commit (rt3_mesh_begin / rt3_mesh_put without a commit)");
+    if (prev_sph && n_prev_sph != ctx->n_sph) return fail(ctx, RT3_E_ARG, "n_prev_spheres must equal the context's sphere count");
+    if (prev_verts && n_prev_verts != ctx->d_verts.size()) return fail(ctx, RT3_E_ARG, "n_prev_vertices must equal the vertex count of the merged entity buffers");
+    const size_t npix = (size_t)w * h, no = npix * sizeof(float4);
+    const struct { const void* ptr; size_t n; } in[3] = { { aov, npix * sizeof(rt3_aov) }, { prev_sph, (size_t)n_prev_sph * sizeof(float4) },
+                                                          { prev_verts, (size_t)n_prev_verts * sizeof(float4) } };
+    for (const auto& i : in)
+        if (i.ptr && ranges_overlap(out, no, i.ptr, i.n)) return fail(ctx, RT3_E_ARG, "out_motion overlaps an input");
+    return 0;
+}
+
+int rt3_motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_aov, const void* d_prev_sph, uint32_t n_prev_sph,
+                      const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = motion_checks(ctx, w, h, cam, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out);
+    if (rc) return rc;
+    if (((uintptr_t)d_aov | (uintptr_t)d_prev_sph | (uintptr_t)d_prev_verts | (uintptr_t)d_out) % 16u != 0)
+        return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
+    MotionLaunch L{};
+    L.width = w; L.height = h;
+    std::memcpy(L.cam, cam, sizeof(rt3_camera));
+    L.aov = d_aov;
+    // a class without a previous array is never gathered: its buffers and counts stay out of the launch
+    if (d_prev_sph) { L.sph = ctx->d_sph_cr; L.sph_invr = ctx->d_sph_invr; L.prev_sph = d_prev_sph; L.n_sph = ctx->n_sph; }
+    if (d_prev_verts) {
+        L.gfaces = ctx->d_gfaces; L.verts = ctx->d_verts; L.prev_verts = d_prev_verts;
+        L.n_faces = ctx->n_faces; L.n_verts = (uint32_t)ctx->d_verts.size();
+    }
+    L.out = d_out;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    RT3_HIP(motion_launch(L, stream));
+    return leave(ctx, stream);
+}
+
+// The host form: the AOVs, the plane and the previous arrays on the device in ctx->stage (4 float4 per pixel, one per sphere and vertex).
+int rt3_motion(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_aov* aov, const float* prev_sph, uint32_t n_prev_sph,
+               const float* prev_verts, uint32_t n_prev_verts, float* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = motion_checks(ctx, w, h, cam, aov, prev_sph, n_prev_sph, prev_verts, n_prev_verts, out);
+    if (rc) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)w * h;
+    if ((rc = ctx->stage.ensure(ctx, 4 * npix + n_prev_sph + n_prev_verts))) return rc;
+    float4* const da = ctx->stage;
+    float4* const dout = da + 3 * npix;
+    float4* const dsph = dout + npix;
+    float4* const dverts = dsph + n_prev_sph;
+    RT3_HIP(hipMemcpyAsync(da, aov, npix * sizeof(rt3_aov), hipMemcpyHostToDevice, ctx->stream));
+    if (prev_sph) RT3_HIP(hipMemcpyAsync(dsph, prev_sph, (size_t)n_prev_sph * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    if (prev_verts) RT3_HIP(hipMemcpyAsync(dverts, prev_verts, (size_t)n_prev_verts * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = rt3_motion_device(ctx, w, h, cam, da, prev_sph ? dsph : nullptr, n_prev_sph, prev_verts ? dverts : nullptr, n_prev_verts, dout, ctx->stream)))
+        return rc;
+    RT3_HIP(hipMemcpyAsync(out, dout, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
 
 int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {
     if (!ctx || !out) return RT3_E_ARG;

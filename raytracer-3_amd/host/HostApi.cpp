@@ -356,21 +356,36 @@ std::vector<float> HipRenderer::denoise(Camera& camera, const rt3_denoise_params
     return out;
 }
 
-std::vector<float> HipRenderer::denoise_temporal(Camera& camera, const rt3_temporal_params& params, History& history) const {
+std::vector<float> HipRenderer::denoise_temporal(Camera& camera, const rt3_temporal_params& params, History& history,
+                                                 const std::vector<float>& motion) const {
     const std::vector<float> colour = hdr();
     if (camera.w() != last_w || camera.h() != last_h) throw Fatal("denoise_temporal: the camera's frame size differs from the last render's");
     const std::vector<rt3_aov> guides = aov(camera);
     const size_t npix = (size_t)last_w * last_h;
     const bool have = !history.records.empty();
     if (have && history.records.size() != npix) throw Fatal("denoise_temporal: the history's frame size differs from the last render's");
+    if (!motion.empty() && motion.size() != 4 * npix) throw Fatal("denoise_temporal: the motion plane's frame size differs from the last render's");
     const rt3_camera cam = camera.wire();
     std::vector<float> out(colour.size());
     std::vector<rt3_history> next(npix);
-    if (rt3_denoise_temporal(ctx[0], last_w, last_h, &cam, colour.data(), guides.data(), have ? &history.camera : nullptr,
-                             have ? history.records.data() : nullptr, &params, out.data(), next.data()) != 0)
+    if (rt3_denoise_temporal_motion(ctx[0], last_w, last_h, &cam, colour.data(), guides.data(), have ? &history.camera : nullptr,
+                                    have ? history.records.data() : nullptr, motion.empty() ? nullptr : motion.data(), &params, out.data(),
+                                    next.data()) != 0)
         throw Fatal(rt3_last_error(ctx[0]));
     history.records.swap(next);
     history.camera = cam;
+    return out;
+}
+
+std::vector<float> HipRenderer::motion(Camera& camera, const std::vector<float>& prev_center_radius,
+                                       const std::vector<float>& prev_vertices_xyzw) const {
+    const std::vector<rt3_aov> guides = aov(camera);
+    const rt3_camera cam = camera.wire();
+    std::vector<float> out(4 * guides.size());
+    if (rt3_motion(ctx[0], camera.w(), camera.h(), &cam, guides.data(), prev_center_radius.empty() ? nullptr : prev_center_radius.data(),
+                   (uint32_t)(prev_center_radius.size() / 4), prev_vertices_xyzw.empty() ? nullptr : prev_vertices_xyzw.data(),
+                   (uint32_t)(prev_vertices_xyzw.size() / 4), out.data()) != 0)
+        throw Fatal(rt3_last_error(ctx[0]));
     return out;
 }
 

@@ -6,7 +6,8 @@
 // output path (later ones ignored), value forms `-W 400`, `-W400`, `--width 400`; exit code 0 after help, -1 on a
 // usage error, -1 on a fatal backend error.  Fixed: `--key=value`, which the reference mis-parses (Main.cpp:110).
 // Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr, --denoise (PFM files),
-// --frames and --orbit (a sequence, denoised temporally).
+// --frames, --orbit and --slide (a sequence, denoised temporally).
+#include <cctype>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -35,6 +36,8 @@ struct Options {
     uint32_t frames = 1;                                           // Mode X: frames of a sequence (frame k renders with seed + k)
     float orbit = 0.0f;                                            // look-at scenes: degrees the look-from point turns per frame
     bool have_orbit = false;
+    float slide[3] = { 0.0f, 0.0f, 0.0f };                         // sphere scenes: what every sphere of odd index moves by per frame
+    bool have_slide = false;
 };
 
 void print_usage(const char* exe) {
@@ -56,6 +59,8 @@ void print_usage(const char* exe) {
               << "\t\t\twith --frames N > 1, write PREFIX.<k>.pfm for every frame k, denoised temporally.\n"
               << "\t   --frames\tMode X: render a sequence of N frames, frame k with seed + k; the image written is the last (default: 1).\n"
               << "\t   --orbit\tweekend / stress100k: turn the look-from point by k * DEG degrees about the vertical axis through the look-at point.\n"
+              << "\t   --slide\tthree / weekend / stress100k with --frames: translate every sphere of odd index by k * (DX,DY,DZ) in frame k;\n"
+              << "\t\t\twith --denoise PREFIX the temporal filter follows them (the motion plane).\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -94,13 +99,17 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         if (key == "--dump-scene") { opt.dump_scene = true; continue; }
         const bool known = key == "-f" || key == "--format" || key == "-W" || key == "--width" || key == "-H" || key == "--height" ||
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
-                           key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit";
+                           key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
+                           key == "--slide";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
         }
         if (value.empty()) {
-            if (i == argc - 1 || argv[i + 1][0] == '-') { std::cerr << key << " has no value." << std::endl; return -1; }
+            // (a --slide value may start with a minus sign: "-0.1,0,0")
+            const bool negative_number = key == "--slide" && i < argc - 1 && argv[i + 1][0] == '-' &&
+                                         (std::isdigit((unsigned char)argv[i + 1][1]) || argv[i + 1][1] == '.');
+            if (i == argc - 1 || (argv[i + 1][0] == '-' && !negative_number)) { std::cerr << key << " has no value." << std::endl; return -1; }
             value = argv[++i];
         }
         if (key == "-f" || key == "--format") {
@@ -126,6 +135,19 @@ int parse_cli(Options& opt, int argc, const char** argv) {
             }
             opt.orbit = (float)deg; opt.have_orbit = true;
         }
+        else if (key == "--slide") {                                 // three finite numbers, comma-separated
+            const char* at = value.c_str();
+            bool ok = true;
+            for (int c = 0; c < 3 && ok; c++) {
+                char* end = nullptr;
+                const double v = std::strtod(at, &end);
+                ok = end != at && std::isfinite(v) && std::isfinite((float)v) && *end == (c < 2 ? ',' : '\0');
+                opt.slide[c] = (float)v;
+                at = end + 1;
+            }
+            if (!ok) { std::cerr << "Invalid slide '" << value << "'" << std::endl; return -1; }
+            opt.have_slide = true;
+        }
         else opt.scene = value;
     }
     if (opt.output_path.empty() && !opt.dump_scene) { std::cerr << "No output path given." << std::endl; return -1; }
@@ -148,14 +170,28 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         std::cerr << "--orbit needs a look-at camera (--scene weekend or stress100k)." << std::endl;
         return -1;
     }
+    if (opt.have_slide && opt.scene != "three" && opt.scene != "weekend" && opt.scene != "stress100k") {
+        std::cerr << "--slide needs a sphere scene (--scene three, weekend or stress100k)." << std::endl;
+        return -1;
+    }
+    if (opt.have_slide && opt.frames < 2) {
+        std::cerr << "--slide needs a sequence: pass --frames N with N of at least 2." << std::endl;
+        return -1;
+    }
     return 1;
 }
+
+// The spheres of the scene on the renderer (--slide moves them from frame to frame).
+std::vector<float> scene_cr;
+std::vector<rt3_material> scene_mats;
 
 template <class Fn>
 void sphere_scene(HipRenderer& r, Fn generate) {
     const uint32_t n = generate(nullptr, nullptr, 0);
-    std::vector<float> cr(4 * (size_t)n);
-    std::vector<rt3_material> mats(n);
+    std::vector<float>& cr = scene_cr;
+    std::vector<rt3_material>& mats = scene_mats;
+    cr.assign(4 * (size_t)n, 0.0f);
+    mats.assign(n, rt3_material{});
     generate(cr.data(), mats.data(), n);
     r.prerender(Tools::Array<ECS::RenderEntity*>());
     r.set_spheres(cr, mats);
@@ -248,7 +284,14 @@ int main(int argc, const char** argv) {
         const bool temporal = opt.frames > 1 && !opt.denoise_path.empty();
         const rt3_temporal_params tp{ { 5, 128, 4.0f, 1.0f }, 0.2f, 0.2f, 2.0f, 0.9f };       // the defaults of DESIGN.md 4.11 and 4.12
         History history;
+        std::vector<float> shown_cr = scene_cr, prev_cr;             // --slide: the spheres of this frame and of the one before
         for (uint32_t k = 0; k < opt.frames; k++) {
+            if (opt.have_slide && k > 0) {                           // frame k: every sphere of odd index translated by k * slide
+                prev_cr = shown_cr;
+                for (size_t i = 1; i < scene_mats.size(); i += 2)
+                    for (int c = 0; c < 3; c++) shown_cr[4 * i + c] = scene_cr[4 * i + c] + (float)k * opt.slide[c];
+                renderer.set_spheres(shown_cr, scene_mats);
+            }
             if (la.on) {                                             // frame k: the look-from point turned by k * orbit about the vertical axis
                 const double a = (double)k * (double)opt.orbit * 3.14159265358979323846 / 180.0, c = std::cos(a), sn = std::sin(a);
                 const double dx = (double)la.from.x - la.at.x, dz = (double)la.from.z - la.at.z;
@@ -259,7 +302,9 @@ int main(int argc, const char** argv) {
             renderer.configure(path);
             renderer.render(cam);
             if (temporal) {
-                const std::vector<float> out = renderer.denoise_temporal(cam, tp, history);
+                std::vector<float> motion;
+                if (opt.have_slide && k > 0) motion = renderer.motion(cam, prev_cr, {});
+                const std::vector<float> out = renderer.denoise_temporal(cam, tp, history, motion);
                 const std::string name = opt.denoise_path + "." + std::to_string(k) + ".pfm";
                 if (rt3_frame_to_pfm(out.data(), cam.w(), cam.h(), 3, 4, name.c_str()) != 0) throw Fatal("Could not write '" + name + "'");
             }

@@ -19,7 +19,7 @@ public:
     virtual void render(Camera& camera) const = 0;
 };
 
-// The caller-owned state of a temporal denoising sequence (rt3_denoise_temporal): the last frame's history records and camera; empty
+// The caller-owned state of a temporal denoising sequence (rt3_denoise_temporal*): the last frame's history records and camera; empty
 // records = the first frame.
 struct History {
     std::vector<rt3_history> records;
@@ -53,7 +53,12 @@ public:
     std::vector<float> denoise(Camera& camera, const rt3_denoise_params& params) const;
     // Mode X only: the same frame through the temporal denoiser (rt3_denoise_temporal) with `history` as the previous frame's, which the
     // call replaces by this frame's; (r, g, b, 0) per pixel
-    std::vector<float> denoise_temporal(Camera& camera, const rt3_temporal_params& params, History& history) const;
+    // motion: empty, or the plane motion() returned for this frame (rt3_denoise_temporal_motion): what moved keeps its history
+    std::vector<float> denoise_temporal(Camera& camera, const rt3_temporal_params& params, History& history,
+                                        const std::vector<float>& motion = {}) const;
+    // Mode X only: the motion plane of the current scene on device 0 (rt3_motion), (mx, my, mz, moved) per pixel of aov(camera); the previous
+    // frame's spheres (4 floats each) and merged vertices (xyzw), an empty vector for a class that did not move
+    std::vector<float> motion(Camera& camera, const std::vector<float>& prev_center_radius, const std::vector<float>& prev_vertices_xyzw) const;
     size_t faces() const { return n_faces; }
     size_t spheres() const { return n_spheres; }
 
