@@ -31,7 +31,8 @@ extern "C" {
  * it loaded reports before it passes any struct (rt3_stats grew from 56 to 64 bytes between versions 1 and 2; rt3_get_stats writes
  * sizeof(rt3_stats) bytes of THIS version).  History: 1 = round 1; 2 = + mfma_instructions / exact_tests in rt3_stats, progressive
  * accumulation, rt3_gather_rows; 3 = + rt3_abi_version itself, one stream convention (below),
- * filter_tests / bound_tests in rt3_stats (80 bytes). */
+ * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh*: functions were only added,
+ * no struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
 
@@ -168,6 +169,36 @@ int rt3_mesh_download(rt3_ctx* ctx, rt3_gface* faces, float* vertices_xyzw);
 /* center_radius: 4 floats per sphere (cx,cy,cz,r), r > 0.  (Sphere{vec3 center; float radius; vec3 color},
  * raytracer_v4.glsl:42-49.) */
 int rt3_set_spheres(rt3_ctx* ctx, const float* center_radius, const rt3_material* materials, uint32_t n);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Scene update   (new positions for the scene that is there: a refit on the device)
+ * ------------------------------------------------------------------------------------------------- */
+/* rt3_update_spheres*: after the call every entry point (render, range render, query, AOV, motion, Mode R) returns bit for bit what it
+ * would return after rt3_set_spheres(center_radius, <the materials of the last rt3_set_spheres>, n).  rt3_update_mesh*: the same against
+ * rt3_set_mesh(faces', vertices_xyzw, n_vertices, <the face materials of the last commit>), faces' = `faces`, or with faces == NULL the
+ * context's own GFace[]: indices, stored normals and colours are kept and only the positions change.  A non-NULL `faces` holds the
+ * context's face count of records and is how a caller supplies new normals (the render layout takes the STORED normal, so a deforming mesh
+ * that wants correct shading passes them).  Materials, counts and the grouping do not change; only performance may differ from a full
+ * upload.  What is kept from the last full upload: the group order and the sphere permutation, the direct-sphere list, and the centres the
+ * filter's coordinates are taken about (the spheres' median centre, the vertex box of the mesh) — each affects only how many candidates
+ * the filter passes, never the result; re-upload in full when the scene has drifted far.
+ * Counts: n must equal the context's sphere count, n_vertices the vertex count of the merged entity buffers (rt3_mesh_download), else
+ * RT3_E_ARG.  RT3_E_STATE without a committed scene of that class; while the merged entity buffers are out of sync with the commit
+ * (rt3_mesh_begin / rt3_mesh_put / rt3_mesh_sphere without an rt3_mesh_commit); and when the last rt3_set_spheres left a sphere with a
+ * non-finite record out of the grouping (an update could make it finite again, and it has no place in the rows).
+ * The device forms (16-byte aligned pointers, RT3_E_ARG otherwise) allocate nothing, never wait for the device and cannot refuse a bad
+ * record: a sphere record that is not finite, or whose radius is not positive, becomes a sphere nothing can hit (rt3_motion still reports
+ * the record as it was passed); a face of a supplied `faces` with a vertex index out of range becomes a face nothing can hit, and the
+ * next rt3_synchronize on the context returns RT3_E_ARG for it, once (rt3_get_stats does not report it).  The host forms are synchronous
+ * and refuse instead: RT3_E_ARG for a radius that is not positive, with the scene untouched; RT3_E_ARG for a face index out of range, which
+ * leaves the context without a mesh, as rt3_set_mesh would.
+ * Streams follow the convention above: an update waits for the event the previous render, query or update recorded and records its own,
+ * so the next call on any stream sees the new scene.  The accumulation of a progressive render is treated as a full upload treats it: it
+ * is left alone, and what continuing it over a changed scene means is the caller's business. */
+int rt3_update_spheres(rt3_ctx* ctx, const float* center_radius, uint32_t n);
+int rt3_update_spheres_device(rt3_ctx* ctx, const void* d_center_radius, uint32_t n, void* stream);
+int rt3_update_mesh(rt3_ctx* ctx, const rt3_gface* faces, const float* vertices_xyzw, uint32_t n_vertices);
+int rt3_update_mesh_device(rt3_ctx* ctx, const void* d_faces, const void* d_vertices_xyzw, uint32_t n_vertices, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Render   (replaces Renderer::render, Renderer.hpp:50)

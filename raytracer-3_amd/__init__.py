@@ -140,6 +140,7 @@ EXPORTS = [
     "rt3_camera_rays", "rt3_camera_rays_device", "rt3_render_aov", "rt3_render_aov_device", "rt3_accum_resolve", "rt3_accum_resolve_device",
     "rt3_frame_pfm_bytes", "rt3_frame_to_pfm", "rt3_denoise", "rt3_denoise_device", "rt3_denoise_temporal", "rt3_denoise_temporal_device",
     "rt3_motion", "rt3_motion_device", "rt3_denoise_temporal_motion", "rt3_denoise_temporal_motion_device",
+    "rt3_update_spheres", "rt3_update_spheres_device", "rt3_update_mesh", "rt3_update_mesh_device",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -206,6 +207,8 @@ def lib():
         "rt3_motion_device": (i32, [vp, u32, u32, vp, vp, vp, u32, vp, u32, vp, vp]),
         "rt3_denoise_temporal_motion": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "rt3_denoise_temporal_motion_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rt3_update_spheres": (i32, [vp, vp, u32]), "rt3_update_spheres_device": (i32, [vp, vp, u32, vp]),
+        "rt3_update_mesh": (i32, [vp, vp, vp, u32]), "rt3_update_mesh_device": (i32, [vp, vp, vp, u32, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -611,6 +614,61 @@ class HipRenderer(Renderer):
         assert materials.dtype == MATERIAL and len(materials) == len(cr)
         self._check(lib().rt3_set_spheres(self._ctx, _p(cr), _p(materials), len(cr)))
         self.n_spheres = len(cr)
+
+    # -- refit: new positions for the scene that is there (rt3_update_*) -----------------------------
+    @staticmethod
+    def _torch_rows(t, what, row_bytes):
+        """A torch tensor on the GPU holding rows of row_bytes bytes each -> its row count, or None for a host array."""
+        if not type(t).__module__.startswith("torch"):
+            return None
+        if not t.is_cuda or not t.is_contiguous() or t.dim() < 1 or (t.numel() * t.element_size()) % row_bytes:
+            raise Fatal("device %s must be a contiguous GPU tensor of %d-byte records" % (what, row_bytes))
+        return t.numel() * t.element_size() // row_bytes
+
+    def update_spheres(self, center_radius):
+        """New (cx, cy, cz, r) for every sphere of the scene (rt3_update_spheres): the result of set_spheres(center_radius, <the same
+        materials>) without the host-side rebuild; the grouping of the last set_spheres is kept.  numpy (n, 4): synchronous.  A contiguous
+        (n, 4) float32 torch tensor on the GPU is read in place, queued on torch.cuda.current_stream() (rt3_update_spheres_device)."""
+        n = self._torch_rows(center_radius, "center_radius", 16)
+        if n is not None:
+            import torch
+            if center_radius.dtype != torch.float32:
+                raise Fatal("device center_radius must be float32")
+            stream = torch.cuda.current_stream(center_radius.device).cuda_stream
+            self._check(lib().rt3_update_spheres_device(self._ctx, C.c_void_p(center_radius.data_ptr()), n, C.c_void_p(stream)))
+            return
+        cr = np.ascontiguousarray(center_radius, np.float32).reshape(-1, 4)
+        self._check(lib().rt3_update_spheres(self._ctx, _p(cr), len(cr)))
+
+    def update_mesh(self, vertices, faces=None):
+        """New merged vertices ((n_vertices, 4), as mesh_download returns them) for the committed mesh (rt3_update_mesh); faces None keeps
+        the indices, stored normals and colours, a GFACE array of the mesh's face count replaces them (new normals).  numpy: synchronous.
+        torch: contiguous GPU tensors (vertices float32 (n, 4); faces any tensor of n_faces 48-byte records), read in place and queued on
+        torch.cuda.current_stream() (rt3_update_mesh_device)."""
+        n = self._torch_rows(vertices, "vertices", 16)
+        if n is not None:
+            import torch
+            if vertices.dtype != torch.float32:
+                raise Fatal("device vertices must be float32")
+            fptr = None
+            if faces is not None:
+                if self._torch_rows(faces, "faces", GFACE.itemsize) != self.n_faces or faces.device != vertices.device:
+                    raise Fatal("device faces must hold the mesh's %d faces, on the vertices' device" % self.n_faces)
+                fptr = C.c_void_p(faces.data_ptr())
+            stream = torch.cuda.current_stream(vertices.device).cuda_stream
+            self._check(lib().rt3_update_mesh_device(self._ctx, fptr, C.c_void_p(vertices.data_ptr()), n, C.c_void_p(stream)))
+            return
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
+        f = None
+        if faces is not None:
+            f = np.ascontiguousarray(faces)
+            if f.dtype != GFACE or len(f) != self.n_faces:
+                raise Fatal("update_mesh: faces must be a GFACE array of the mesh's %d faces" % self.n_faces)
+        self._check(lib().rt3_update_mesh(self._ctx, _p(f), _p(v), len(v)))
+
+    def synchronize(self):
+        """rt3_synchronize: waits for the context's own stream; reports a face index out of range of a device-form update_mesh."""
+        self._check(lib().rt3_synchronize(self._ctx))
 
     # -- render --------------------------------------------------------------------------------------
     def configure(self, spp=None, max_depth=None, seed=1, flags=0, lens_radius=0.0, t_min=0.001):

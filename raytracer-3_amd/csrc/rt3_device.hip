@@ -96,6 +96,10 @@ struct rt3_ctx {
     DevBuf<float4> d_sph; DevBuf<uint32_t> d_sph_frag, d_sph_frag32; float sph_centre[3] = { 0.0f, 0.0f, 0.0f }; uint32_t n_direct = 0; uint32_t direct[4] = { 0, 0, 0, 0 }; float tri_centre[3] = { 0.0f, 0.0f, 0.0f }; DevBuf<uint32_t> d_box; DevBuf<u32x4> d_tri_frag_r; DevBuf<float> d_sph_invr; DevBuf<float4> d_sph_mat; DevBuf<uint32_t> d_sph_kind;
 
     DevBuf<float4> d_sph_cr;                                        // (C, r) as the caller gave them, in the caller's order (rt3_motion compares and scales by them)
+    // what rt3_update_spheres* needs from the last rt3_set_spheres: every sphere's position in sph.grp (0xFFFFFFFF: a direct sphere), and whether
+    // a sphere was left out of the group order for a non-finite record (an update could make it finite again, and it has no slot)
+    DevBuf<uint32_t> d_sph_slot; bool sph_left_out = false;
+    bool update_error_pending = false;                              // a device-form rt3_update_mesh_device with faces: d_error is read by the next rt3_synchronize
 
     // rows of the multi-level filter: faces and spheres, each in the order of a spatial median split
     FilterRows tri, sph;
@@ -442,6 +446,31 @@ int build_rows(rt3_ctx* ctx, FilterRows& R, const float4* members, const std::ve
         RT3_HIP(hipGetLastError());
     }
     R.n_leaves = n_leaves; R.n_groups = n_groups; R.n_super = n_super;
+    return 0;
+}
+
+// The same rows again for members that moved (rt3_update_*): R.grp holds the new member records, every bound above them is
+// recomputed into the buffers build_rows allocated — k_refit_rows, one launch per level (leaves, rows, super-rows), each bound evaluated once.
+// RT3_REFIT_SIMPLE=1 issues build_rows' own five launches instead (A/B reference: the same bits).  Nothing is allocated, nothing waits.
+int refit_rows(rt3_ctx* ctx, const FilterRows& R, const uint32_t* box, const float centre[3], hipStream_t stream) {
+    static_assert(kSuper == kLevFan && kGroupTri == kLevFan && kGroupSph == kLevFan, "refit_rows: the three-level rows, 8 children per node");
+    if (R.n_groups == 0) return 0;
+    const uint32_t n_entries = (uint32_t)R.grp.size(), n_leaves = R.n_leaves, n_group_rows = (uint32_t)R.rowb.size(), n_super_rows = (uint32_t)R.srowb.size();
+    const float cx = centre[0], cy = centre[1], cz = centre[2];
+    const dim3 blk(kBlock);
+    auto grid = [](uint32_t threads) { return dim3((threads + kBlock - 1) / kBlock); };
+    if (getenv("RT3_REFIT_SIMPLE")) {
+        hipLaunchKernelGGL(k_group_bounds, grid(n_leaves), blk, 0, stream, R.grp.get(), n_entries, kLevFan, n_leaves, box, cx, cy, cz, R.leaf.get());
+        hipLaunchKernelGGL(k_group_frags, grid(n_group_rows), blk, 0, stream, R.leaf.get(), n_leaves, kLevFan, n_group_rows, box, cx, cy, cz, R.gfrag.get());
+        hipLaunchKernelGGL(k_group_bounds, grid(n_group_rows), blk, 0, stream, R.leaf.get(), n_leaves, kLevFan, n_group_rows, box, cx, cy, cz, R.rowb.get());
+        hipLaunchKernelGGL(k_group_frags, grid(n_super_rows), blk, 0, stream, R.rowb.get(), n_group_rows, kLevFan, n_super_rows, box, cx, cy, cz, R.sfrag.get());
+        hipLaunchKernelGGL(k_group_bounds, grid(n_super_rows), blk, 0, stream, R.rowb.get(), n_group_rows, kLevFan, n_super_rows, box, cx, cy, cz, R.srowb.get());
+    } else {
+        hipLaunchKernelGGL(k_refit_rows, grid(n_leaves * kLevFan), blk, 0, stream, R.grp.get(), n_entries, n_leaves, box, cx, cy, cz, R.leaf.get(), (u32x4*)nullptr);
+        hipLaunchKernelGGL(k_refit_rows, grid(n_group_rows * kLevFan), blk, 0, stream, R.leaf.get(), n_leaves, n_group_rows, box, cx, cy, cz, R.rowb.get(), R.gfrag.get());
+        hipLaunchKernelGGL(k_refit_rows, grid(n_super_rows * kLevFan), blk, 0, stream, R.rowb.get(), n_group_rows, n_super_rows, box, cx, cy, cz, R.srowb.get(), R.sfrag.get());
+    }
+    RT3_HIP(hipGetLastError());
     return 0;
 }
 
@@ -830,6 +859,7 @@ int rt3_mesh_commit(rt3_ctx* ctx, const rt3_material* face_materials) {
     const uint32_t n = (uint32_t)ctx->d_gfaces.size(), n_pad = (n + 3u) / 4u * 4u, n_verts = (uint32_t)ctx->d_verts.size();
     ctx->n_faces = 0;
     ctx->mesh_in_sync = false;
+    ctx->update_error_pending = false;
     ctx->tri = FilterRows();
     for (DevBuf<float4>* b : { &ctx->d_tri, &ctx->d_tri_mat, &ctx->d_tri_bound, &ctx->d_tri_rec }) b->reset();
     ctx->d_tri_kind.reset(); ctx->d_tri_frag.reset(); ctx->d_tri_frag_r.reset(); ctx->d_face_mats_in.reset();
@@ -943,8 +973,132 @@ int rt3_set_spheres(rt3_ctx* ctx, const float* center_radius, const rt3_material
     // rows of the multi-level filter: groups of kGroupSph spheres in the order of a spatial median split
     const std::vector<uint32_t> order = sphere_group_order(center_radius, n, ctx->direct, ctx->n_direct, kGroupSph, kSuper);
     if ((rc = build_rows(ctx, ctx->sph, sph.data(), order, kGroupSph, nullptr, ctx->sph_centre))) return rc;
+    std::vector<uint32_t> slot(n, 0xFFFFFFFFu);                     // the inverse of the order (rt3_update_spheres*)
+    uint32_t placed = 0;
+    for (size_t k = 0; k < order.size(); k++) if (order[k] != 0xFFFFFFFFu) { slot[order[k]] = (uint32_t)k; placed++; }
+    if ((rc = ctx->d_sph_slot.upload(ctx, slot))) return rc;
+    ctx->sph_left_out = placed + ctx->n_direct != n;
     RT3_HIP(hipStreamSynchronize(ctx->stream));                     // a render may come on another stream
     ctx->n_sph = n;
+    return 0;
+}
+
+// ---- Refit: new positions for the scene on the context, every derived buffer recomputed in place on the device
+static int update_spheres_checks(rt3_ctx* ctx, const void* center_radius, uint32_t n) {
+    if (!center_radius) return fail(ctx, RT3_E_ARG, "center_radius is NULL");
+    if (ctx->n_sph == 0) return fail(ctx, RT3_E_STATE, "no spheres to update: call rt3_set_spheres first");
+    if (ctx->sph_left_out)
+        return fail(ctx, RT3_E_STATE, "the last rt3_set_spheres left a non-finite sphere out of the group order: it has no slot an update could fill");
+    if (n != ctx->n_sph) return fail(ctx, RT3_E_ARG, "n must equal the context's sphere count");
+    return 0;
+}
+
+int rt3_update_spheres_device(rt3_ctx* ctx, const void* d_center_radius, uint32_t n, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = update_spheres_checks(ctx, d_center_radius, n);
+    if (rc) return rc;
+    if ((uintptr_t)d_center_radius % 16u != 0) return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    ctx->n_sph = 0;                                                 // (no spheres until everything below has been issued)
+    hipLaunchKernelGGL(k_refit_spheres, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)d_center_radius, n,
+                       (const uint32_t*)ctx->d_sph_slot, ctx->sph_centre[0], ctx->sph_centre[1], ctx->sph_centre[2], ctx->d_sph.get(),
+                       ctx->d_sph_cr.get(), ctx->d_sph_invr.get(), (u32x4*)ctx->d_sph_frag.get(), (u32x4*)ctx->d_sph_frag32.get(), ctx->sph.grp.get());
+    RT3_HIP(hipGetLastError());
+    if ((rc = refit_rows(ctx, ctx->sph, nullptr, ctx->sph_centre, stream)) || (rc = leave(ctx, stream))) return rc;
+    ctx->n_sph = n;
+    return 0;
+}
+
+int rt3_update_spheres(rt3_ctx* ctx, const float* center_radius, uint32_t n) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = update_spheres_checks(ctx, center_radius, n);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n; i++)                                // rt3_set_spheres' check; the scene is untouched
+        if (!(center_radius[4 * (size_t)i + 3] > 0.0f)) return fail(ctx, RT3_E_ARG, "sphere " + std::to_string(i) + " has a non-positive radius");
+    RT3_HIP(hipSetDevice(ctx->device));
+    if ((rc = ctx->stage.ensure(ctx, n))) return rc;
+    RT3_HIP(hipMemcpyAsync(ctx->stage, center_radius, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = rt3_update_spheres_device(ctx, ctx->stage.get(), n, ctx->stream))) return rc;
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// The launches of a mesh update, after the new vertices (and faces) have been queued into d_verts / d_gfaces on `stream`.
+static int refit_mesh(rt3_ctx* ctx, hipStream_t stream) {
+    const uint32_t n = ctx->n_faces, n_pad = (n + 3u) / 4u * 4u, n_verts = (uint32_t)ctx->d_verts.size(), n_frag_rows = (n + 31u) / 32u * 32u;
+    const uint32_t n_pos = (uint32_t)ctx->tri.perm.size();
+    for (const float scale : { 1.0f, 0.5f }) {                      // as rt3_mesh_commit: everything, then Mode R's fragments
+        hipLaunchKernelGGL(k_commit_mesh, dim3((n_frag_rows + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, ctx->d_gfaces, ctx->d_verts, n, n_pad,
+                           n_verts, ctx->d_face_mats_in, ctx->d_tri, ctx->d_tri_bound, ctx->d_tri_mat, ctx->d_tri_kind, ctx->d_error,
+                           scale == 1.0f ? ctx->d_tri_frag.get() : ctx->d_tri_frag_r.get(), n_frag_rows, (const uint32_t*)ctx->d_box, scale);
+        RT3_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_gather_members, dim3((n_pos + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_tri_bound,
+                       (const uint32_t*)ctx->tri.perm, n_pos, ctx->tri.grp.get());
+    hipLaunchKernelGGL(k_gather_face_records, dim3((n_pos * 4u + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_tri,
+                       (const uint32_t*)ctx->tri.perm, n_pos, ctx->d_tri_rec.get());
+    RT3_HIP(hipGetLastError());
+    const float no_centre[3] = { 0.0f, 0.0f, 0.0f };
+    return refit_rows(ctx, ctx->tri, ctx->d_box, no_centre, stream);
+}
+static int update_mesh_checks(rt3_ctx* ctx, const void* vertices, uint32_t n_vertices) {
+    if (!vertices) return fail(ctx, RT3_E_ARG, "vertices is NULL");
+    if (ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "no committed mesh to update: call rt3_set_mesh / rt3_mesh_commit first");
+    if (!ctx->mesh_in_sync)
+        return fail(ctx, RT3_E_STATE, "the merged entity buffers were changed after the last rt3_mesh_commit (rt3_mesh_begin / rt3_mesh_put without a commit)");
+    if (n_vertices != ctx->d_verts.size()) return fail(ctx, RT3_E_ARG, "n_vertices must equal the vertex count of the merged entity buffers");
+    return 0;
+}
+// clear_error: the host form reads the error word itself; the device form leaves it to the next rt3_synchronize.
+static int update_mesh_issue(rt3_ctx* ctx, const void* d_faces, const void* d_verts, void* stream_, bool clear_error) {
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    const uint32_t n = ctx->n_faces;
+    ctx->n_faces = 0;                                               // (no mesh until everything below has been issued)
+    ctx->mesh_in_sync = false;
+    if (clear_error || !ctx->update_error_pending) RT3_HIP(hipMemsetAsync(ctx->d_error, 0, 4, stream));
+    RT3_HIP(hipMemcpyAsync(ctx->d_verts, d_verts, ctx->d_verts.size() * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+    if (d_faces) RT3_HIP(hipMemcpyAsync(ctx->d_gfaces, d_faces, (size_t)n * sizeof(rt3_gface), hipMemcpyDeviceToDevice, stream));
+    ctx->n_faces = n;                                               // (refit_mesh reads the count; taken back below if it fails)
+    rc = refit_mesh(ctx, stream);
+    if (!rc) rc = leave(ctx, stream);
+    if (rc) { ctx->n_faces = 0; return rc; }
+    ctx->mesh_in_sync = true;
+    return 0;
+}
+
+int rt3_update_mesh_device(rt3_ctx* ctx, const void* d_faces, const void* d_vertices, uint32_t n_vertices, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = update_mesh_checks(ctx, d_vertices, n_vertices);
+    if (rc) return rc;
+    if (((uintptr_t)d_faces | (uintptr_t)d_vertices) % 16u != 0) return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
+    if ((rc = update_mesh_issue(ctx, d_faces, d_vertices, stream_, false))) return rc;
+    if (d_faces) ctx->update_error_pending = true;
+    return 0;
+}
+
+int rt3_update_mesh(rt3_ctx* ctx, const rt3_gface* faces, const float* vertices, uint32_t n_vertices) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = update_mesh_checks(ctx, vertices, n_vertices);
+    if (rc) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    const size_t nf = faces ? ctx->n_faces : 0;
+    if ((rc = ctx->stage.ensure(ctx, (size_t)n_vertices + 3 * nf))) return rc;
+    float4* const dv = ctx->stage;
+    float4* const df = dv + n_vertices;
+    RT3_HIP(hipMemcpyAsync(dv, vertices, (size_t)n_vertices * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    if (faces) RT3_HIP(hipMemcpyAsync(df, faces, nf * sizeof(rt3_gface), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = update_mesh_issue(ctx, faces ? df : nullptr, dv, ctx->stream, true))) return rc;
+    uint32_t err = 0;
+    RT3_HIP(hipMemcpyAsync(&err, ctx->d_error, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->update_error_pending = false;
+    if (err) {                                                      // as after rt3_set_mesh with such a face: no mesh
+        ctx->n_faces = 0; ctx->mesh_in_sync = false;
+        return fail(ctx, RT3_E_ARG, "a face references a vertex out of range");
+    }
     return 0;
 }
 
@@ -966,6 +1120,16 @@ int rt3_synchronize(rt3_ctx* ctx) {
     if (!ctx) return RT3_E_ARG;
     RT3_HIP(hipSetDevice(ctx->device));
     RT3_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->update_error_pending) {                                // rt3_update_mesh_device with faces: a face index out of range is reported here, once
+        ctx->update_error_pending = false;
+        uint32_t err = 0;
+        if (ctx->ev_acc_recorded) RT3_HIP(hipEventSynchronize(ctx->ev_acc));    // (the update may have run on a caller's stream)
+        RT3_HIP(hipMemcpy(&err, ctx->d_error, 4, hipMemcpyDeviceToHost));
+        if (err) {
+            RT3_HIP(hipMemset(ctx->d_error, 0, 4));
+            return fail(ctx, RT3_E_ARG, "rt3_update_mesh_device: a face references a vertex out of range (that face cannot be hit)");
+        }
+    }
     return 0;
 }
 
@@ -994,7 +1158,8 @@ int rt3_render_device(rt3_ctx* ctx, const rt3_camera* cam, uint32_t width, uint3
     if (!cam || !d_out) return fail(ctx, RT3_E_ARG, "cam / d_out_pixels is NULL");
     if (width < 2 || height < 2 || (uint64_t)width * height > 0x7FFFFFFFull) return fail(ctx, RT3_E_ARG, "bad frame size");
     RT3_HIP(hipSetDevice(ctx->device));
-    const hipStream_t stream = stream_of(ctx, stream_);            // (Mode R's buffers are the caller's: no wait for ev_acc)
+    const hipStream_t stream = stream_of(ctx, stream_);            // (Mode R's buffers are the caller's; the scene's are not: an update may be in flight)
+    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));
     ctx->rendered = false;                                          // stats are valid again once every launch below has been issued
     ctx->ev_used = 0;
     hipEvent_t a, b;
@@ -1026,6 +1191,7 @@ int rt3_render_device(rt3_ctx* ctx, const rt3_camera* cam, uint32_t width, uint3
     RT3_HIP(hipGetLastError());
     RT3_HIP(hipEventRecord(b, stream));
     RT3_HIP(hipEventRecord(ctx->ev_end, stream));
+    if ((rc = leave(ctx, stream))) return rc;                      // (an update on another stream starts behind this render)
     ctx->last_stream = stream;
     ctx->last_samples = npix;
     ctx->last_was_path = false;

@@ -116,7 +116,11 @@ __global__ void k_commit_mesh(const rt3_gface* __restrict__ faces, const float4*
     if (i >= n_pad && i >= n_frag_rows) return;
     if (i >= n_faces) { if (all && i < n_pad) bound[i] = kPadSphere; write_frag(0.0f, 0.0f, 0.0f, kNeverCandidate); return; }
     const rt3_gface f = faces[i];
-    if (f.v1 >= n_verts || f.v2 >= n_verts || f.v3 >= n_verts) { if (all) { atomicOr(error_flag, 1u); bound[i] = kPadSphere; } write_frag(0.0f, 0.0f, 0.0f, kNeverCandidate); return; }
+    if (f.v1 >= n_verts || f.v2 >= n_verts || f.v3 >= n_verts) {     // a pad, and a record no test accepts (n = 0): an update keeps the scene (rt3_update_mesh_device)
+        if (all) { atomicOr(error_flag, 1u); bound[i] = kPadSphere; for (int q = 0; q < 4; q++) tri[4 * (size_t)i + q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+        write_frag(0.0f, 0.0f, 0.0f, kNeverCandidate);
+        return;
+    }
     const float4 p1 = verts[f.v1], p2 = verts[f.v2], p3 = verts[f.v3];
     if (all) {
         tri[4 * (size_t)i] = make_float4(f.normal[0], f.normal[1], f.normal[2], dot3(f.normal[0], f.normal[1], f.normal[2], p1.x, p1.y, p1.z));
@@ -286,6 +290,143 @@ __global__ void k_group_frags(const float4* __restrict__ bounds, uint32_t n_entr
     uint32_t fr[4][4];
     bound_frag32_row(fx, fy, fz, kj, fr);
     for (uint32_t q = 0; q < 4; q++) frag[frag32_index(g / 32, g % 32, q)] = u32x4{ fr[q][0], fr[q][1], fr[q][2], fr[q][3] };
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Refit (rt3_update_spheres* / rt3_update_mesh*): every derived value again, in place, for the group order, the
+// filter centre and the direct list of the last full upload
+// ------------------------------------------------------------------------------------------------------
+// One thread per sphere of the caller's (cx, cy, cz, r)[]: what rt3_set_spheres derives from record i on the host, with the same operations —
+// (C, r^2), 1 / r, the record as given, the sphere's rows of the two flat filters (K = 64: build_sphere_frags, K = 32: build_sphere_frags32)
+// and its member record in the rows of the multi-level filter.  slot[i] is the sphere's position in group order, 0xFFFFFFFF for a direct
+// sphere: it is in no group and its flat rows can never be candidates.  A record that is not finite or whose radius is not positive (the
+// device form cannot refuse it) becomes a sphere nothing can hit: kPadSphere where the kernels look, never-candidate rows.
+__global__ void k_refit_spheres(const float4* __restrict__ in, uint32_t n, const uint32_t* __restrict__ slot, float ecx, float ecy, float ecz,
+                                float4* __restrict__ sph, float4* __restrict__ cr, float* __restrict__ invr, u32x4* __restrict__ frag,
+                                u32x4* __restrict__ frag32, float4* __restrict__ grp) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 s = in[i];
+    const float r2f = s.w * s.w;
+    const bool good = s.w > 0.0f && s.x - s.x == 0.0f && s.y - s.y == 0.0f && s.z - s.z == 0.0f && r2f - r2f == 0.0f;
+    const float4 rec = good ? make_float4(s.x, s.y, s.z, r2f) : kPadSphere;
+    const uint32_t k = slot[i];
+    sph[i] = rec;
+    cr[i] = s;
+    invr[i] = 1.0f / s.w;
+    if (k != 0xFFFFFFFFu) grp[k] = rec;
+    float fx = 0.0f, fy = 0.0f, fz = 0.0f, kj = kNeverCandidate, kj32 = kNeverCandidate;
+    if (good && k != 0xFFFFFFFFu) {
+        fx = (float)((double)s.x - ecx); fy = (float)((double)s.y - ecy); fz = (float)((double)s.z - ecz);
+        const double c2 = (double)fx * fx + (double)fy * fy + (double)fz * fz, r2 = (double)s.w * s.w;
+        kj = filter_kj(c2, r2); kj32 = filter_kj32(c2, r2);
+    }
+    uint32_t fr[4][2][4], fr32[4][4];
+    bound_frag_row(fx, fy, fz, kj, fr);
+    bound_frag32_row(fx, fy, fz, kj32, fr32);
+    for (uint32_t q = 0; q < 4; q++)
+        for (uint32_t hh = 0; hh < 2; hh++)
+            frag[((size_t)(i / 32) * 4 + q) * 64 + hh * 32 + frag_row_of(i % 32)] = u32x4{ fr[q][hh][0], fr[q][hh][1], fr[q][hh][2], fr[q][hh][3] };
+    for (uint32_t g = 0; g < 4; g++) frag32[frag32_index(i / 32, i % 32, g)] = u32x4{ fr32[g][0], fr32[g][1], fr32[g][2], fr32[g][3] };
+}
+
+// The members' records of one class in group order: grp[k] = bound[perm[k]], kPadSphere where the position holds no primitive (what build_rows
+// gathers on the host).
+__global__ void k_gather_members(const float4* __restrict__ bound, const uint32_t* __restrict__ perm, uint32_t n_pos, float4* __restrict__ grp) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_pos) return;
+    const uint32_t j = perm[k];
+    grp[k] = j == 0xFFFFFFFFu ? kPadSphere : bound[j];
+}
+
+// One level of the rows: the bounds of n_out groups of kLevFan consecutive entries of `members`, each evaluated ONCE and written as the f32
+// record (rec, or null) and as the row of the matrix filter (frag, or null) — k_group_bounds and k_group_frags evaluate it once each, one
+// thread per group.  Here a group has kLevFan lanes, one per member (8 groups per wave), and group_bound above is the specification: the
+// result is the same bits.
+//   mean       every lane adds the members in index order (the serial loop's order)
+//   farthest   a butterfly over the group's lanes on (d, member index): the larger d wins, on equal d the lower index — what the serial
+//              `d > far` keeps; lanes without a usable member carry d = -1, the serial loop's start value
+//   radius     the same butterfly with fmax (every term is >= 0 and none is a NaN: max is exact in any order)
+// Everything after the radius is computed by every lane of the group; lane 0 writes the record, lanes 0..3 one quarter of the row each.
+template <typename T>
+__device__ __forceinline__ T group_lane(T v, uint32_t lane) { return __shfl(v, (int)lane); }
+__global__ void k_refit_rows(const float4* __restrict__ members, uint32_t n_entries, uint32_t n_out, const uint32_t* __restrict__ box,
+                             float ecx, float ecy, float ecz, float4* __restrict__ rec, u32x4* __restrict__ frag) {
+    static_assert(kLevFan == 8 && kBlock % 64 == 0, "k_refit_rows: 8 lanes per group, whole waves");
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, g = t / kLevFan, m = t % kLevFan;
+    const uint32_t lane = lane_id(), base = lane & ~(kLevFan - 1u);
+    float centre[3] = { ecx, ecy, ecz };
+    if (box) box_centre(box, centre);
+    const uint64_t j = (uint64_t)g * kLevFan + m;
+    const bool valid = g < n_out && j < n_entries;                  // (every lane stays for the cross-lane steps)
+    const float4 b = valid ? members[j] : kPadSphere;
+    const bool alw = valid && b.w >= 3e38f;
+    const bool use = valid && b.w >= 0.0f && b.w < 3e38f && b.x - b.x == 0.0f && b.y - b.y == 0.0f && b.z - b.z == 0.0f;
+    const bool always = ((__ballot(alw) >> base) & 0xFFull) != 0ull;
+    const uint32_t um = (uint32_t)((__ballot(use) >> base) & 0xFFull), n_use = (uint32_t)__popc(um);
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+#pragma unroll
+    for (uint32_t q = 0; q < kLevFan; q++) {
+        const float x = group_lane(b.x, base + q), y = group_lane(b.y, base + q), z = group_lane(b.z, base + q);
+        if ((um >> q) & 1u) { sx += x; sy += y; sz += z; }
+    }
+    float4 out = kPadSphere;
+    if (always) out = make_float4(0.0f, 0.0f, 0.0f, 3e38f);
+    // (the branches below are uniform over a group, not over a wave: the shuffles stay outside them)
+    const bool live = !always && n_use != 0u;
+    double cx = live ? sx / n_use : 0.0, cy = live ? sy / n_use : 0.0, cz = live ? sz / n_use : 0.0;
+    const double rm = use ? sqrt((double)b.w) : 0.0;
+    // a wave leaves the loop when none of its groups has a step left (members > 1); a group without one keeps its centre
+    const bool steps = live && n_use > 1u;
+    if (__ballot(steps) != 0ull) {
+        for (int it = 1; it <= 32; it++) {
+            const double ddx = b.x - cx, ddy = b.y - cy, ddz = b.z - cz;
+            double d = use ? sqrt(ddx * ddx + ddy * ddy + ddz * ddz) + rm : -1.0;
+            uint32_t idx = m;
+#pragma unroll
+            for (int o = 1; o < (int)kLevFan; o <<= 1) {
+                const double od = __shfl_xor(d, o);
+                const uint32_t oi = (uint32_t)__shfl_xor((int)idx, o);
+                if (od > d || (od == d && oi < idx)) { d = od; idx = oi; }
+            }
+            const float tx = group_lane(b.x, base + idx), ty = group_lane(b.y, base + idx), tz = group_lane(b.z, base + idx);
+            const double step = 1.0 / (it + 1);
+            if (steps) { cx += ((double)tx - cx) * step; cy += ((double)ty - cy) * step; cz += ((double)tz - cz) * step; }
+        }
+    }
+    const float fcx = (float)cx, fcy = (float)cy, fcz = (float)cz;
+    double R = 0.0;
+    {
+        const double ddx = (double)b.x - fcx, ddy = (double)b.y - fcy, ddz = (double)b.z - fcz;
+        if (use) R = fmax(R, sqrt(ddx * ddx + ddy * ddy + ddz * ddz) + rm);
+#pragma unroll
+        for (int o = 1; o < (int)kLevFan; o <<= 1) R = fmax(R, __shfl_xor(R, o));
+    }
+    if (live) {
+        const double qx = (double)fcx - centre[0], qy = (double)fcy - centre[1], qz = (double)fcz - centre[2];
+        const double rho = sqrt(qx * qx + qy * qy + qz * qz) + R;
+        const double r2 = (1.04 * R * R + 2e-3 * R * rho + 4e-6 * rho * rho) * (1.0 + 1e-6) + 1e-30;
+        if (!(r2 < 1e30)) out = make_float4(0.0f, 0.0f, 0.0f, 3e38f);
+        else {
+            float r2f = (float)r2;
+            if ((double)r2f < r2) r2f = __uint_as_float(__float_as_uint(r2f) + 1u);
+            out = make_float4(fcx, fcy, fcz, r2f);
+        }
+    }
+    if (g >= n_out) return;
+    if (rec && m == 0u) rec[g] = out;
+    if (frag && m < 4u) {
+        float fx = 0.0f, fy = 0.0f, fz = 0.0f, kj = kNeverCandidate;
+        if (out.w >= 3e38f) kj = kAlwaysCandidate;
+        else if (out.w >= 0.0f) {
+            fx = (float)((double)out.x - (double)centre[0]); fy = (float)((double)out.y - (double)centre[1]); fz = (float)((double)out.z - (double)centre[2]);
+            const double c2 = (double)fx * fx + (double)fy * fy + (double)fz * fz;
+            kj = filter_kj32(c2, (double)out.w);
+        }
+        uint32_t fr[4][4];
+        bound_frag32_row(fx, fy, fz, kj, fr);
+        frag[frag32_index(g / 32, g % 32, m)] = u32x4{ fr[m][0], fr[m][1], fr[m][2], fr[m][3] };
+    }
 }
 
 }  // namespace

@@ -245,6 +245,19 @@ void HipRenderer::set_mesh(const std::vector<rt3_gface>& faces, const std::vecto
     n_faces = faces.size();
 }
 
+// New positions for the scene that is there (rt3_update_spheres / rt3_update_mesh): a refit on every device, no rebuild on the host.
+void HipRenderer::update_spheres(const std::vector<float>& center_radius) {
+    for (rt3_ctx* c : ctx)
+        if (rt3_update_spheres(c, center_radius.data(), (uint32_t)(center_radius.size() / 4)) != 0) throw Fatal(rt3_last_error(c));
+}
+
+void HipRenderer::update_mesh(const std::vector<float>& vertices, const std::vector<rt3_gface>& faces) {
+    if (!faces.empty() && faces.size() != n_faces) throw Fatal("update_mesh: faces must hold the mesh's face count, or be empty");
+    for (rt3_ctx* c : ctx)
+        if (rt3_update_mesh(c, faces.empty() ? nullptr : faces.data(), vertices.data(), (uint32_t)(vertices.size() / 4)) != 0)
+            throw Fatal(rt3_last_error(c));
+}
+
 void HipRenderer::render(Camera& camera) const {
     const rt3_camera cam = camera.wire();
     const uint32_t w = camera.w(), h = camera.h();

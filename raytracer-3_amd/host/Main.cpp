@@ -38,6 +38,7 @@ struct Options {
     bool have_orbit = false;
     float slide[3] = { 0.0f, 0.0f, 0.0f };                         // sphere scenes: what every sphere of odd index moves by per frame
     bool have_slide = false;
+    bool refit = false;                                            // --slide: frames after the first update the spheres in place (rt3_update_spheres)
 };
 
 void print_usage(const char* exe) {
@@ -61,6 +62,7 @@ void print_usage(const char* exe) {
               << "\t   --orbit\tweekend / stress100k: turn the look-from point by k * DEG degrees about the vertical axis through the look-at point.\n"
               << "\t   --slide\tthree / weekend / stress100k with --frames: translate every sphere of odd index by k * (DX,DY,DZ) in frame k;\n"
               << "\t\t\twith --denoise PREFIX the temporal filter follows them (the motion plane).\n"
+              << "\t   --refit\tWith --slide: frames after the first move the spheres by an update on the device instead of a full upload (same frames).\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -97,6 +99,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         if (key == "-h" || key == "--help") { print_usage(argv[0]); return 0; }
         if (key == "--gpu-prerender") { opt.gpu_prerender = true; continue; }
         if (key == "--dump-scene") { opt.dump_scene = true; continue; }
+        if (key == "--refit") { opt.refit = true; continue; }
         const bool known = key == "-f" || key == "--format" || key == "-W" || key == "--width" || key == "-H" || key == "--height" ||
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
@@ -176,6 +179,10 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     }
     if (opt.have_slide && opt.frames < 2) {
         std::cerr << "--slide needs a sequence: pass --frames N with N of at least 2." << std::endl;
+        return -1;
+    }
+    if (opt.refit && !opt.have_slide) {
+        std::cerr << "--refit needs --slide: it is how the moved spheres reach the device." << std::endl;
         return -1;
     }
     return 1;
@@ -290,7 +297,8 @@ int main(int argc, const char** argv) {
                 prev_cr = shown_cr;
                 for (size_t i = 1; i < scene_mats.size(); i += 2)
                     for (int c = 0; c < 3; c++) shown_cr[4 * i + c] = scene_cr[4 * i + c] + (float)k * opt.slide[c];
-                renderer.set_spheres(shown_cr, scene_mats);
+                if (opt.refit) renderer.update_spheres(shown_cr);
+                else renderer.set_spheres(shown_cr, scene_mats);
             }
             if (la.on) {                                             // frame k: the look-from point turned by k * orbit about the vertical axis
                 const double a = (double)k * (double)opt.orbit * 3.14159265358979323846 / 180.0, c = std::cos(a), sn = std::sin(a);

@@ -44,6 +44,10 @@ public:
     // scenes that are not entity lists (benchmark sphere fields)
     void set_spheres(const std::vector<float>& center_radius, const std::vector<rt3_material>& materials);
     void set_mesh(const std::vector<rt3_gface>& faces, const std::vector<float>& vertices_xyzw, const std::vector<rt3_material>& face_materials);
+    // the same scene with new positions (rt3_update_spheres / rt3_update_mesh): counts, materials and the grouping stay; faces: empty keeps
+    // the indices, normals and colours, else the mesh's face count of records (new normals)
+    void update_spheres(const std::vector<float>& center_radius);
+    void update_mesh(const std::vector<float>& vertices_xyzw, const std::vector<rt3_gface>& faces = {});
     rt3_stats stats() const;                                                     // of device 0's last render
     // Mode X only, full frames (row 0 on top) assembled from the device shards: the first-hit AOVs of the current options (rt3_render_aov),
     // and the linear (r, g, b, 0) frame of the last render (rt3_accum_resolve)
