@@ -112,7 +112,7 @@ typedef struct rt3_params {
 
 /* Counters of the last render on a context (device-side counts, HIP-event timings on the render stream). */
 typedef struct rt3_stats {
-    uint64_t ray_casts;          /* rays traced (primary + scattered)                                */
+    uint64_t ray_casts;          /* rays traced (primary + scattered; primary rays traced against the strip lists included) */
     uint64_t prim_tests;         /* ray-primitive tests = ray_casts * (n_spheres + n_faces)          */
     uint64_t samples;            /* pixels * spp rendered by this call                               */
     float    trace_ms;           /* dominant kernel (trace / mode-R) duration, summed over launches  */
@@ -122,8 +122,13 @@ typedef struct rt3_stats {
     uint32_t mfma_flop_per_instruction;   /* 32768 (v_mfma_f32_32x32x16_bf16: k_trace_mfma) or 16384 (v_mfma_f32_16x16x32_bf16: tiled kernels) */
     uint64_t mfma_instructions;  /* bf16 MFMA wave-instructions issued by the candidate filter (0: VALU scan / brute force) */
     uint64_t exact_tests;        /* (ray, primitive) pairs that survived the filter(s) and went through the exact test
-                                    (counted by the pair-list kernels; 0 elsewhere)                                      */
-    uint64_t filter_tests;       /* (ray, row) pairs the matrix filter evaluated = ray_casts * rows; a row is one primitive in the
+                                    (counted by the pair-list kernels; 0 elsewhere); the tests of primary rays against their
+                                    strip lists (below) are counted here too                                             */
+    uint64_t filter_tests;       /* (ray, row) pairs the matrix filter evaluated = (ray casts that took the filter) * rows.  Every
+                                    cast takes it, except in sphere scenes of <= 512 spheres: there the primary rays of 64
+                                    consecutive pixels are traced against a short list of the spheres their beam can meet and
+                                    skip the filter (RT3_PRIMARY_LISTS=0 turns that off, RT3_PRIMARY_LIST_MAX=n sets the longest
+                                    list still traced that way), so filter_tests < ray_casts * rows.  A row is one primitive in the
                                     flat filter and a group of primitives in the two-level filter, so this is what
                                     the matrix cores executed, while prim_tests is the brute-force-equivalent count              */
     uint64_t bound_tests;        /* two-level filter, faces: members of candidate groups checked against their own bounding sphere */
@@ -517,6 +522,11 @@ int      rt3_debug_force_brute(rt3_ctx* ctx, int on);
 int      rt3_debug_force_flat_filter(rt3_ctx* ctx, int on);
 int      rt3_debug_arith(rt3_ctx* ctx, const float* a, const float* b, uint32_t n, float* div, float* sq, float* fm,
                          float* cs, float* sn, float* sk3, uint32_t* pk);
+/* Debug probe used by the tests only: builds the strip lists of the current scene (sphere-only, <= 512 spheres) for this camera and
+ * these params and downloads them: n_groups x n_blocks words, group g = owned pixels 64 g .. 64 g + 63, bit b of word k of a group =
+ * sphere 32 k + b may be met by a primary ray of the group.  RT3_E_ARG (with n_groups / n_blocks set) if capacity_words is too small. */
+int      rt3_debug_primary_lists(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t* out_masks, uint64_t capacity_words,
+                                 uint32_t* n_groups, uint32_t* n_blocks);
 
 #ifdef __cplusplus
 }

@@ -141,6 +141,7 @@ EXPORTS = [
     "rt3_frame_pfm_bytes", "rt3_frame_to_pfm", "rt3_denoise", "rt3_denoise_device", "rt3_denoise_temporal", "rt3_denoise_temporal_device",
     "rt3_motion", "rt3_motion_device", "rt3_denoise_temporal_motion", "rt3_denoise_temporal_motion_device",
     "rt3_update_spheres", "rt3_update_spheres_device", "rt3_update_mesh", "rt3_update_mesh_device",
+    "rt3_debug_primary_lists",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -184,6 +185,7 @@ def lib():
         "rt3_hash_u32": (u32, [u32]), "rt3_random_float": (f32, [u32]),
         "rt3_debug_arith": (i32, [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "rt3_debug_force_plain_mode_r": (i32, [vp, i32]),
+        "rt3_debug_primary_lists": (i32, [vp, vp, vp, vp, u64, vp, vp]),
         "rt3_mesh_begin": (i32, [vp, u32, u32]), "rt3_mesh_put": (i32, [vp, vp, u32, vp, u32, u32, u32]),
         "rt3_mesh_sphere": (i32, [vp, vp, f32, u32, u32, vp, u32, u32]), "rt3_mesh_commit": (i32, [vp, vp]),
         "rt3_mesh_download": (i32, [vp, vp, vp]),
@@ -968,6 +970,16 @@ class HipRenderer(Renderer):
         outs = [np.zeros(n, np.float32) for _ in range(5)] + [np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)]
         self._check(lib().rt3_debug_arith(self._ctx, _p(a), _p(b), n, *[_p(o) for o in outs]))
         return outs
+
+
+    def debug_primary_lists(self, cam, params):
+        """The strip lists of the current sphere scene for (cam, params): a (groups of 64 owned pixels, row blocks) uint32 array, bit b of
+        word k = sphere 32 k + b (tests only)."""
+        ng, nb = C.c_uint32(0), C.c_uint32(0)
+        npix = rows_owned(params) * params.width
+        out = np.zeros((-(-npix // 64), 16), np.uint32)
+        self._check(lib().rt3_debug_primary_lists(self._ctx, C.byref(cam), C.byref(params), _p(out), out.size, C.byref(ng), C.byref(nb)))
+        return out.reshape(-1)[:ng.value * nb.value].reshape(ng.value, nb.value).copy()
 
 
 def initialize_renderer(device=0):

@@ -44,6 +44,7 @@
 #include "rt3_aov.hpp"
 #include "rt3_denoise.hpp"
 #include "rt3_scene_kernels.hpp"
+#include "rt3_primary_lists.hpp"
 
 // ======================================================================================================
 // Host side of the device context
@@ -105,6 +106,7 @@ struct rt3_ctx {
     FilterRows tri, sph;
     DevBuf<float4> d_tri_rec;                                       // the faces' records in group order (the exact test of the multi-level filter reads these)
     DevBuf<uint32_t> d_strips;                                      // deferred member tests: kStripPairs pairs per wave of the grid
+    DevBuf<uint32_t> d_prim_masks;                                  // strip lists of the last k_trace_mfma32 render: [group of 64 owned pixels][row block]
 
     // work buffers
     DevBuf<Rgb> d_rad;
@@ -124,6 +126,7 @@ struct rt3_ctx {
     bool force_brute = false;                                       // tests / fuzzers: unfiltered Mode-X kernel
     bool force_flat = false;                                        // tests / A-B: one filter row per primitive (no groups)
     uint64_t last_filter_rows = 0;                                  // rows the matrix filter scanned per ray cast in the last Mode-X render
+    bool last_filter_counted = false;                               // ... and the kernel counted the casts that took the filter itself (d_casts[16])
     // the accumulation a progressive render continues (rt3_render_path_range): what it belongs to and how far it got
     bool acc_valid = false; rt3_params acc_params{}; rt3_camera acc_cam{}; uint32_t acc_done = 0; uint32_t acc_npix = 0;
     // launch configuration per (kernel, dynamic LDS): max dynamic LDS attribute set, workgroups per CU
@@ -581,7 +584,17 @@ struct TracePlan {
     int per_cu = 0;                                                 // workgroups per CU the launch configuration allows (<= 8)
     bool mfma16 = false;                                            // rt3_stats::mfma_flop_per_instruction: 16x16x32 (tiled kernels, k_trace_mfma32)
     uint64_t filter_rows = 0;                                       // rows the matrix filter scans per ray cast
+    bool filter_counted = false;                                    // the kernel counts the casts that take the filter (k_trace_mfma32's render form)
+    uint32_t list_groups = 0;                                       // strip lists to build before the first batch (k_primary_lists): groups of 64 owned pixels, 0: none
 };
+// Strip lists (rt3_primary_lists.hpp): RT3_PRIMARY_LISTS=0 turns them off (the A/B reference: every primary ray takes the matrix filter),
+// RT3_PRIMARY_LIST_MAX=n sets the longest list a restock still traces itself.  The default is the best of a sweep on the bench frame at 1080p (short
+// lists) and at 400x225 (long ones): profiles/primary_lists_mi355x.log.
+constexpr uint32_t kPrimaryListMax = 32;
+void launch_primary_lists(const rt3_ctx* ctx, const TraceArgs& A, uint32_t n_groups, uint32_t n_blocks, hipStream_t stream) {
+    constexpr uint32_t per_block = kBlock / 64;
+    hipLaunchKernelGGL(k_primary_lists, dim3((n_groups + per_block - 1) / per_block), dim3(kBlock), 0, stream, A, n_groups, n_blocks, ctx->d_prim_masks.get());
+}
 template <bool Q, uint32_t L, bool R>
 TiledKernel levels_kernel(bool has_tri, bool has_sph, bool ref) {
     if constexpr (Q) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, true> : k_trace_levels<true, false, false, L, R, true>) : k_trace_levels<false, true, false, L, R, true>;
@@ -622,6 +635,19 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
         T.block = kMB;
         T.single = single_k64 ? k_trace_mfma : query ? k_trace_mfma32<true> : k_trace_mfma32<>;
         T.frag_a = (const u32x4*)(single_k64 ? ctx->d_sph_frag.get() : ctx->d_sph_frag32.get());
+        if (!query && !single_k64) {
+            T.filter_counted = true;
+            const char* on = getenv("RT3_PRIMARY_LISTS"); const char* cap = getenv("RT3_PRIMARY_LIST_MAX");
+            A.prim_masks = nullptr;                                 // (the slot held the face bounds' address: none in a sphere-only scene)
+            A.prim_list_max = 0;
+            if (!(on && atoi(on) == 0)) {
+                T.list_groups = (A.npix + 63u) / 64u;
+                int rc_;
+                if ((rc_ = ctx->d_prim_masks.ensure(ctx, (size_t)T.list_groups * T.mfma_blocks))) return rc_;
+                A.prim_masks = ctx->d_prim_masks;
+                A.prim_list_max = cap ? (uint32_t)std::min<long>(std::max<long>(atol(cap), 0), (long)kMfmaSphMax) : kPrimaryListMax;
+            }
+        }
     } else if (use_mfma) {
         // the two-level filter (rows = groups of primitives) unless RT3_NO_GROUPS=1 asks for the flat one (A/B reference, tests)
         constexpr uint32_t SUP = kSuper;
@@ -721,10 +747,11 @@ int leave(rt3_ctx* ctx, hipStream_t stream) {
 
 // The calls rt3_get_stats reports on (Mode-X renders, queries, AOVs) issue their launches between these two; each clears ctx->rendered before
 // anything that can fail, and end_timed sets it once the last launch has been issued.  plan: nullptr when nothing was traced (no owned pixels).
+constexpr size_t kCastSlots = 32;                                   // d_casts: [0..15] as the kernels' comments say, [16] casts through the filter, [17] restock phase
 int begin_timed(rt3_ctx* ctx, hipStream_t stream) {
     ctx->ev_used = 0;
     RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
-    RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, 128, stream));
+    RT3_HIP(hipMemsetAsync(ctx->d_casts, 0, kCastSlots * 8, stream));
     return 0;
 }
 int end_timed(rt3_ctx* ctx, hipStream_t stream, uint64_t samples, const TracePlan* plan) {
@@ -734,7 +761,7 @@ int end_timed(rt3_ctx* ctx, hipStream_t stream, uint64_t samples, const TracePla
     ctx->last_stream = stream;
     ctx->last_samples = samples;
     ctx->last_was_path = true;
-    if (plan) { ctx->last_mfma16 = plan->mfma16; ctx->last_filter_rows = plan->filter_rows; }
+    if (plan) { ctx->last_mfma16 = plan->mfma16; ctx->last_filter_rows = plan->filter_rows; ctx->last_filter_counted = plan->filter_counted; }
     ctx->rendered = true;
     return 0;
 }
@@ -771,7 +798,7 @@ rt3_ctx* rt3_create(int device_id) {
     if ((e = hipSetDevice(device_id)) != hipSuccess || (e = hipGetDeviceProperties(&prop, device_id)) != hipSuccess ||
         (e = hipStreamCreate(&ctx->stream)) != hipSuccess || (e = hipEventCreate(&ctx->ev_begin)) != hipSuccess ||
         (e = hipEventCreate(&ctx->ev_end)) != hipSuccess || (e = hipEventCreateWithFlags(&ctx->ev_acc, hipEventDisableTiming)) != hipSuccess ||
-        ctx->d_work.alloc(ctx, 16) || ctx->d_casts.alloc(ctx, 16)) {
+        ctx->d_work.alloc(ctx, 16) || ctx->d_casts.alloc(ctx, kCastSlots)) {
         g_create_error = "rt3_create: " + (e != hipSuccess ? std::string(hipGetErrorString(e)) : ctx->err);
         delete ctx;
         return nullptr;
@@ -1266,6 +1293,10 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     RT3_HIP(hipMemsetAsync(ctx->d_casts + 6, 0xFF, 8, stream));
     RT3_HIP(hipMemsetAsync(ctx->d_casts + 8, 0xFF, 16, stream));       // [8] first wave start, [9] first time a wave found the queue empty
 #endif
+    if (T.list_groups) {                                            // camera, params and scene may all have changed since the last call: built every time
+        launch_primary_lists(ctx, A, T.list_groups, T.mfma_blocks, stream);
+        RT3_HIP(hipGetLastError());
+    }
     for (uint32_t s0 = sample_begin; s0 < sample_begin + sample_count; s0 += batch) {
         const uint32_t ns = std::min(batch, sample_begin + sample_count - s0);
         A.s0 = s0;
@@ -1883,14 +1914,15 @@ int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {
     out->n_spheres = ctx->n_sph;
     out->n_faces = ctx->n_faces;
     if (ctx->last_was_path) {
-        unsigned long long counters[16] = { 0 };
-        RT3_HIP(hipMemcpy(counters, ctx->d_casts, 128, hipMemcpyDeviceToHost));
+        unsigned long long counters[kCastSlots] = { 0 };
+        RT3_HIP(hipMemcpy(counters, ctx->d_casts, sizeof counters, hipMemcpyDeviceToHost));
 #ifdef RT3_PROFILE_PHASES
         if (counters[13] != 0) {                                     // k_trace_mfma: where its waves spend their time
-            const double all = (double)(counters[11] + counters[12] + counters[13] + counters[14] + counters[15]);
+            const double all = (double)(counters[11] + counters[12] + counters[13] + counters[14] + counters[15] + counters[17]);
             fprintf(stderr, "[rt3 profile] k_trace_mfma32 / k_trace_mfma, share of wave time: refill %.1f %%, ray operands (+ direct spheres) %.1f %%, scan %.1f %%, "
-                            "push + exact tests %.1f %%, decode + shade %.1f %%\n",
-                    100.0 * counters[11] / all, 100.0 * counters[12] / all, 100.0 * counters[13] / all, 100.0 * counters[14] / all, 100.0 * counters[15] / all);
+                            "push + exact tests %.1f %%, decode + shade %.1f %%, restock (primary pass) %.1f %%\n",
+                    100.0 * counters[11] / all, 100.0 * counters[12] / all, 100.0 * counters[13] / all, 100.0 * counters[14] / all, 100.0 * counters[15] / all,
+                    100.0 * counters[17] / all);
         }
 #endif
 #ifdef RT3_PROFILE
@@ -1918,7 +1950,7 @@ int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {
         out->exact_tests = counters[2];
         out->bound_tests = counters[3];
 #endif
-        out->filter_tests = counters[0] * ctx->last_filter_rows;
+        out->filter_tests = (ctx->last_filter_counted ? counters[16] : counters[0]) * ctx->last_filter_rows;
     } else {
         out->ray_casts = ctx->last_samples;
         out->prim_tests = ctx->last_samples * (uint64_t)ctx->n_faces;
@@ -1949,6 +1981,31 @@ int rt3_debug_arith(rt3_ctx* ctx, const float* a, const float* b, uint32_t n, fl
     RT3_HIP(hipMemcpy(sn, dsn, N * 4, hipMemcpyDeviceToHost));
     RT3_HIP(hipMemcpy(sk3, dsk, N * 12, hipMemcpyDeviceToHost));
     RT3_HIP(hipMemcpy(pk, dpk, N * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Debug probe (tests only): the strip lists k_trace_mfma32's render form would use for this camera and these params, see tests/test_gpu_primary_lists.py.
+int rt3_debug_primary_lists(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t* out_masks, uint64_t capacity_words, uint32_t* n_groups,
+                            uint32_t* n_blocks) {
+    if (!ctx) return RT3_E_ARG;
+    if (!cam || !n_groups || !n_blocks) return fail(ctx, RT3_E_ARG, "cam / n_groups / n_blocks is NULL");
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    if (ctx->n_sph == 0 || ctx->n_faces != 0 || ctx->n_sph > kMfmaSphMax) return fail(ctx, RT3_E_STATE, "strip lists need a sphere-only scene of <= 512 spheres");
+    hipStream_t stream;
+    if ((rc = enter(ctx, nullptr, &stream))) return rc;
+    const uint32_t npix = rt3_rows_owned(p) * p->width;
+    *n_groups = (npix + 63u) / 64u;
+    *n_blocks = (ctx->n_sph + 31u) / 32u;
+    const size_t words = (size_t)*n_groups * *n_blocks;
+    if (!out_masks || capacity_words < words) return fail(ctx, RT3_E_ARG, "out_masks holds fewer than n_groups * n_blocks words");
+    if (words == 0) return 0;
+    TraceArgs A;
+    if ((rc = path_args(ctx, cam, p, npix, A)) || (rc = ctx->d_prim_masks.ensure(ctx, words))) return rc;
+    launch_primary_lists(ctx, A, *n_groups, *n_blocks, stream);
+    RT3_HIP(hipGetLastError());
+    RT3_HIP(hipMemcpyAsync(out_masks, ctx->d_prim_masks.get(), words * 4, hipMemcpyDeviceToHost, stream));
+    RT3_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 

@@ -116,7 +116,7 @@ struct Rgb { float r, g, b; };   // one radiance record of the sample storage (t
 struct TraceArgs {
     const float4* sph;       const float* sph_invr;  const float4* sph_mat;  const uint32_t* sph_kind;  uint32_t n_sph;
     const float4* tri;       const float4* tri_mat;  const uint32_t* tri_kind;
-    union { const float4* tri_bound; const float4* q_rays; };
+    union { const float4* tri_bound; const float4* q_rays; const uint32_t* prim_masks; };   // prim_masks: k_trace_mfma32's render form (sphere-only: no face bounds), below
     uint32_t n_tri;
     CamDev cam;
     float lens_radius, lux, luy, luz, lvx, lvy, lvz;
@@ -148,7 +148,11 @@ struct TraceArgs {
     const float4* sph_leaf; const float4* tri_leaf; uint32_t n_sph_leaves, n_tri_leaves;
     const float4* sph_rowb; const float4* tri_rowb;                 // three-level filter: the rows' own bounds (C, R_eff^2) in f32, or null
     const float4* tri_rec;                                          // the faces' 64-byte records once more, in GROUP order (a leaf's 8 faces: 512 contiguous bytes)
-    const float4* sph_topb; const float4* tri_topb; uint32_t n_sph_top, n_tri_top;   // k_trace_levels: what the matrix cores scan (rows, or super-rows of 8 rows) and its bounds in f32
+    const float4* sph_topb; const float4* tri_topb; uint32_t n_sph_top;              // k_trace_levels: what the matrix cores scan (rows, or super-rows of 8 rows) and its bounds in f32
+    // Strip lists of k_trace_mfma32's render form (rt3_primary_lists.hpp; they share the places of fields that kernel never reads): prim_masks holds, per
+    // aligned group of 64 owned pixels, one bit per sphere row ([group][row block] dwords) — the spheres a primary ray of the group can meet — or null
+    // (lists off); a restock whose groups list more than prim_list_max spheres sends its primary rays through the matrix filter instead.
+    union { uint32_t n_tri_top; uint32_t prim_list_max; };
     uint32_t* pair_strips;   // [wave of the grid][kStripPairs]: candidate (ray lane, row) pairs set aside for the end of a pass (deferred member tests)
     uint32_t* work_counter;
     unsigned long long* cast_counter;

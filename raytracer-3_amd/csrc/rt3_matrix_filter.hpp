@@ -847,6 +847,108 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma(const TraceArgs A, const u32
 #endif
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Primary rays traced at restock time, against the strip lists (lists: rt3_primary_lists.hpp)
+// ------------------------------------------------------------------------------------------------------
+// 37 % of the bench frame's ray casts are primary rays, and which spheres a primary ray can meet is all but fixed by its pixel: the stock
+// makes them 64 at a time for 64 consecutive owned pixels of one sample — a thin beam that meets two listed spheres on average.  So the restock
+// itself traces them: every lane tests its own ray against the spheres k_primary_lists listed for the pixel group(s) the 64 items fall into —
+// sphere_root on the LDS mirror, folded into a key that starts from the direct spheres' tests, which is the main loop's rule — shades them,
+// lets the finished paths (sky, flat material, depth 1) write their radiance there, and stocks the survivors, compacted into lanes [0, n), with
+// their throughput and depth.  A trip of the main loop (ray operands, 512 filter rows on the matrix cores, decode, push) is then spent on
+// bounce rays only.  Same functions, same inputs, same per-path order, same RNG counters: the frame does not depend on the schedule.
+// A restock whose groups list more than A.prim_list_max spheres (or have no list: every bit set) stocks its rays untraced; they take the filter.
+// casts: primary casts traced here; exact: their (ray, sphere) tests.  ph_restock (RT3_PROFILE_PHASES): wave time of the primary pass.
+struct SphereMirror { const float4* sph; const float* invr; const float4* mat; const uint32_t* kind; uint32_t n_blocks; };     // LDS
+__device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, const SphereMirror& S, uint32_t lane, bool& alive, Path& P, TracedStock& Q,
+                                                         uint32_t& chunk_next, uint32_t& chunk_end, bool& exhausted, unsigned long long& casts,
+                                                         unsigned long long& exact, unsigned long long& ph_restock) {
+    const unsigned long long need = __ballot(!alive);
+    if (need == 0ull) return;
+    const uint32_t n_need = (uint32_t)__popcll(need), rank = prefix_count(need);
+    uint32_t served = 0;
+    for (;;) {
+        const uint32_t k = min(Q.n, n_need - served);
+        if (k != 0) {
+            const bool take = !alive && rank >= served && rank < served + k;
+            stock_pop(Q, Q.n - 1u - (rank - served), take, P, alive);       // (the index only matters where take is set)
+            Q.n -= k;
+            served += k;
+        }
+        if (served == n_need || exhausted) return;
+        // the stock is empty: restock from the wave's chunk (one atomic per kWorkChunk samples)
+        if (chunk_next == chunk_end) {
+            uint32_t b = 0;
+            if (lane == 0) b = atomicAdd(A.work_counter, kWorkChunk);
+            b = __builtin_amdgcn_readfirstlane(b);
+            if (b >= A.total) { exhausted = true; return; }
+            chunk_next = b;
+            chunk_end = min(b + kWorkChunk, A.total);
+        }
+#ifdef RT3_PROFILE_PHASES
+        const unsigned long long ph_t0 = clock64();
+#endif
+        const uint32_t n_new = min(64u, chunk_end - chunk_next);
+        const uint32_t item = min(chunk_next + lane, chunk_end - 1u);
+        bool live = lane < n_new;                                           // (the lanes beyond repeat the last item: they take no part)
+        Path T;
+        start_path<false>(A, item, T);
+        chunk_next += n_new;
+        // the union of the lists of the pixel groups these items fall into (one or two; more only where a sample block is shorter than 64
+        // pixels): lane b holds the word of row block b
+        uint32_t word = 0, listed = 0xFFFFFFFFu;
+        if (A.prim_masks != nullptr) {
+            const uint32_t grp = (item - fdiv(item, A.div_npix) * A.npix) >> 6;
+            unsigned long long rest = __ballot(live);
+            while (rest != 0ull) {
+                const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)grp, (int)(__ffsll((long long)rest) - 1));
+                if (lane < S.n_blocks) word |= A.prim_masks[(size_t)g * S.n_blocks + lane];
+                rest &= ~__ballot(grp == g);
+            }
+            listed = 0;
+            for (uint32_t b = 0; b < S.n_blocks; b++) listed += (uint32_t)__popc((uint32_t)__builtin_amdgcn_readlane((int)word, (int)b));
+        }
+        if (listed <= A.prim_list_max) {                                    // (wave-uniform)
+            casts += n_new;
+            unsigned long long key = direct_tests(A, T.ox, T.oy, T.oz, T.dx, T.dy, T.dz, [&](uint32_t j) { return S.sph[j]; });
+            for (uint32_t b = 0; b < S.n_blocks; b++) {
+                uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)word, (int)b);
+                while (m != 0u) {
+                    const uint32_t j = b * 32u + ((uint32_t)__ffs((int)m) - 1u);
+                    m &= m - 1u;
+                    float t;
+                    if (sphere_root(S.sph[j], T.ox, T.oy, T.oz, T.dx, T.dy, T.dz, A.t_min, t) && t < __builtin_inff()) {
+                        const unsigned long long kk = hit_key(t, 1u, j);
+                        key = kk < key ? kk : key;
+                    }
+                    exact += n_new;
+                }
+            }
+            uint32_t kind, ibest;
+            float tbest;
+            key_decode(key, kind, ibest, tbest);
+            shade_lane<false, true>(A, T, live, kind, ibest, tbest, S.sph, S.invr, S.mat, S.kind);
+            // the survivors move to lanes [0, n), the rest behind them: a permutation of the wave (ds_permute: every lane sends)
+            const unsigned long long surv = __ballot(live);
+            const uint32_t n = (uint32_t)__popcll(surv), before = prefix_count(surv);
+            const int to = (int)((live ? before : n + (lane - before)) * 4u);
+            auto send = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_permute(to, (int)v); };
+            auto sendf = [&](float v) { return __uint_as_float(send(__float_as_uint(v))); };
+            Q.ox = sendf(T.ox); Q.oy = sendf(T.oy); Q.oz = sendf(T.oz); Q.dx = sendf(T.dx); Q.dy = sendf(T.dy); Q.dz = sendf(T.dz);
+            Q.tr = sendf(T.tr); Q.tg = sendf(T.tg); Q.tb = sendf(T.tb);
+            Q.slot = send(T.slot); Q.base = send(T.base); Q.depth = send(T.depth);
+            Q.n = n;
+        } else {
+            Q.ox = T.ox; Q.oy = T.oy; Q.oz = T.oz; Q.dx = T.dx; Q.dy = T.dy; Q.dz = T.dz; Q.slot = T.slot; Q.base = T.base;
+            Q.tr = Q.tg = Q.tb = 1.0f; Q.depth = 0;
+            Q.n = n_new;
+        }
+#ifdef RT3_PROFILE_PHASES
+        ph_restock += clock64() - ph_t0;
+#endif
+    }
+}
+
 // The same scene class (<= 512 spheres, everything in LDS, no barrier after the prologue) on the K = 32 form: ONE v_mfma_f32_16x16x32_bf16
 // per 16 x 16 tests, 64 B of fragments per sphere, candidates through the pair list, exact tests on the LDS mirror of the spheres.
 // The vector-ALU instruction count per ray cast is that of k_trace_mfma (the K = 32 margin brings more candidates, the pair list tests them
@@ -883,9 +985,11 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
     bool alive = false;
     uint32_t chunk_next = 0, chunk_end = 0;
     bool exhausted = false;
-    RayStock Q;
-    Q.ox = Q.oy = Q.oz = 0.0f; Q.dx = Q.dy = 0.0f; Q.dz = 1.0f; Q.slot = 0; Q.base = 0; Q.n = 0;
+    TracedStock Q;
+    Q.ox = Q.oy = Q.oz = 0.0f; Q.dx = Q.dy = 0.0f; Q.dz = 1.0f; Q.tr = Q.tg = Q.tb = 0.0f; Q.slot = 0; Q.base = 0; Q.depth = 0; Q.n = 0;
+    const SphereMirror mirror = { s_sph, s_invr, s_mat, s_kind, n_blocks };
     unsigned long long casts = 0, iters = 0, exact = 0;
+    unsigned long long primary_casts = 0, ph_restock = 0;                       // render form: ray casts traced at restock time, wave time spent on them
 #ifdef RT3_PROFILE_PHASES                                                       // wave time (s_memtime) per part of a trip: tools/README.md
     unsigned long long ph_refill = 0, ph_operands = 0, ph_scan = 0, ph_flush = 0, ph_shade = 0, ph_mark = clock64();
 #define RT3_SPHASE(acc) { const unsigned long long now_ = clock64(); acc += now_ - ph_mark; ph_mark = now_; }
@@ -895,7 +999,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
 
     for (;;) {
         if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else refill_from_stock(A, lane, alive, P, Q, chunk_next, chunk_end, exhausted);
+        else refill_from_traced_stock(A, mirror, lane, alive, P, Q, chunk_next, chunk_end, exhausted, primary_casts, exact, ph_restock);
         RT3_SPHASE(ph_refill)
         const unsigned long long live = __ballot(alive);
         if (live == 0ull) break;
@@ -935,12 +1039,17 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
     }
 #ifdef RT3_PROFILE_PHASES
     if (lane == 0) {
-        atomicAdd(A.cast_counter + 11, ph_refill); atomicAdd(A.cast_counter + 12, ph_operands); atomicAdd(A.cast_counter + 13, ph_scan);
-        atomicAdd(A.cast_counter + 14, ph_flush); atomicAdd(A.cast_counter + 15, ph_shade);
+        atomicAdd(A.cast_counter + 11, ph_refill - ph_restock); atomicAdd(A.cast_counter + 12, ph_operands); atomicAdd(A.cast_counter + 13, ph_scan);
+        atomicAdd(A.cast_counter + 14, ph_flush); atomicAdd(A.cast_counter + 15, ph_shade); atomicAdd(A.cast_counter + 17, ph_restock);
     }
 #endif
 #undef RT3_SPHASE
-    if (lane == 0 && casts != 0) { atomicAdd(A.cast_counter, casts); atomicAdd(A.cast_counter + 1, iters * n_blocks * 8ull); atomicAdd(A.cast_counter + 2, exact); }
+    if constexpr (QUERY) {
+        if (lane == 0 && casts != 0) { atomicAdd(A.cast_counter, casts); atomicAdd(A.cast_counter + 1, iters * n_blocks * 8ull); atomicAdd(A.cast_counter + 2, exact); }
+    } else if (lane == 0 && casts + primary_casts != 0) {                       // [16]: the casts that went through the matrix filter (rt3_stats::filter_tests)
+        atomicAdd(A.cast_counter, casts + primary_casts); atomicAdd(A.cast_counter + 1, iters * n_blocks * 8ull); atomicAdd(A.cast_counter + 2, exact);
+        atomicAdd(A.cast_counter + 16, casts);
+    }
 }
 
 // Any scene: faces (through their bounding spheres) and spheres, streamed through LDS in 64-KiB tiles of 1024 rows.  The 16 waves of the

@@ -115,6 +115,21 @@ __device__ __forceinline__ void refill_from_stock(const TraceArgs& A, uint32_t l
     }
 }
 
+// The stock of k_trace_mfma32's render form (refill_from_traced_stock, rt3_matrix_filter.hpp): its entries are paths whose primary ray may already have
+// been traced and shaded when the stock was filled, so an entry carries throughput and depth too (an untraced one: throughput 1, depth 0).
+struct TracedStock { float ox, oy, oz, dx, dy, dz, tr, tg, tb; uint32_t slot, base, depth; uint32_t n; };   // n: wave-uniform count, entries in lanes [0, n)
+__device__ __forceinline__ void stock_pop(const TracedStock& Q, uint32_t src, bool take, Path& P, bool& alive) {
+    const int s = (int)src;
+    const float ox = __shfl(Q.ox, s), oy = __shfl(Q.oy, s), oz = __shfl(Q.oz, s), dx = __shfl(Q.dx, s), dy = __shfl(Q.dy, s), dz = __shfl(Q.dz, s);
+    const float tr = __shfl(Q.tr, s), tg = __shfl(Q.tg, s), tb = __shfl(Q.tb, s);
+    const uint32_t slot = (uint32_t)__shfl((int)Q.slot, s), base = (uint32_t)__shfl((int)Q.base, s), depth = (uint32_t)__shfl((int)Q.depth, s);
+    if (take) {
+        P.ox = ox; P.oy = oy; P.oz = oz; P.dx = dx; P.dy = dy; P.dz = dz; P.slot = slot; P.base = base;
+        P.tr = tr; P.tg = tg; P.tb = tb; P.lr = P.lg = P.lb = 0.0f; P.depth = depth;        // (a path that goes on has gathered no light yet: shade_lane)
+        alive = true;
+    }
+}
+
 // Shade / scatter one ray cast of every live lane (book materials).  kind: 0 miss, 1 face, 2 sphere.
 // The four per-sphere arrays read at a hit are parameters: global memory in k_trace, LDS copies in k_trace_mfma.
 // REF (RT3_FLAG_REFERENCE_PRIMARY): at ray cast 0 the direction is the reference's unnormalised one — the sky and the hit point use

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved A/B timing of two builds of librt3hip.so in ONE process on ONE device (cdna_hip_programming.md §5.4 rule 24):
-    python tools/ab.py libA.so libB.so [spp] [rounds]
-Renders BASELINE config 2 (1920x1080, depth 50, thin lens) at `spp` with each library alternately; prints the k_trace time
+    python tools/ab.py libA.so libB.so [spp] [rounds] [width height]
+Renders BASELINE config 2 (1920x1080 unless given, depth 50, thin lens) at `spp` with each library alternately; prints the k_trace time
 (HIP events) per round and the medians.  Also checks that both builds produce the same frame."""
 import ctypes as C
 import importlib
@@ -28,7 +28,7 @@ def main():
     paths = sys.argv[1:3]
     spp = int(sys.argv[3]) if len(sys.argv) > 3 else 128
     rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 5
-    W, H = 1920, 1080
+    W, H = (int(sys.argv[5]), int(sys.argv[6])) if len(sys.argv) > 6 else (1920, 1080)
     cr, mats = rt3.scene_weekend(42)
     cam = rt3.weekend_camera(W, H)
     p = rt3.make_params(W, H, spp=spp, max_depth=50, seed=1, flags=1, lens_radius=0.05)

@@ -42,6 +42,7 @@ int rt3_debug_force_plain_mode_r(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_force_brute(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_force_flat_filter(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_arith(rt3_ctx*, const float*, const float*, uint32_t, float*, float*, float*, float*, float*, float*, uint32_t*) { return RT3_E_DEVICE; }
+int rt3_debug_primary_lists(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t*, uint64_t, uint32_t*, uint32_t*) { return RT3_E_DEVICE; }
 int rt3_intersect(rt3_ctx*, const rt3_ray*, uint32_t, float, rt3_hit*) { return RT3_E_DEVICE; }
 int rt3_occluded(rt3_ctx*, const rt3_ray*, uint32_t, float, uint32_t*) { return RT3_E_DEVICE; }
 int rt3_intersect_device(rt3_ctx*, const void*, uint32_t, float, void*, void*) { return RT3_E_DEVICE; }

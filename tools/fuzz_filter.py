@@ -96,7 +96,8 @@ def run(count, first, r=None, log=print):
         ref = r.render_path(cam.c, p).copy()
         del os.environ["RT3_NO_MFMA"]
         img = r.render_path(cam.c, p)
-        assert r.stats().mfma_instructions > 0
+        st = r.stats()                                               # the matrix-filter kernel ran: it issued MFMAs, unless no ray needed the filter — every
+        assert st.mfma_instructions > 0 or st.ray_casts == st.samples    # path ended at its primary ray, and k_trace_mfma32 traced those against its strip lists
         bad = int((img != ref).sum())
         if bad:
             bad_total += 1
