@@ -31,8 +31,8 @@ extern "C" {
  * it loaded reports before it passes any struct (rt3_stats grew from 56 to 64 bytes between versions 1 and 2; rt3_get_stats writes
  * sizeof(rt3_stats) bytes of THIS version).  History: 1 = round 1; 2 = + mfma_instructions / exact_tests in rt3_stats, progressive
  * accumulation, rt3_gather_rows; 3 = + rt3_abi_version itself, one stream convention (below),
- * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh*: functions were only added,
- * no struct changed. */
+ * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh* and with
+ * rt3_render_path_adaptive* (one new struct of its own): functions were only added, no existing struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
 
@@ -233,6 +233,41 @@ int rt3_render_path_range(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
                           uint32_t sample_begin, uint32_t sample_count, uint32_t* out_pixels);
 int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* params,
                                  uint32_t sample_begin, uint32_t sample_count, void* d_out_pixels, void* stream);
+/* Adaptive sampling: params->spp is a BUDGET; a pixel stops receiving samples once it and its neighbours have converged.
+ *   Rounds.  Round 0 renders samples [0, min_spp) of the spp-sample law of rt3_render_path (same jitter strata, same RNG keys) for every owned pixel;
+ *     round r >= 1 renders the next min(step_spp, spp - done) samples for the ACTIVE pixels only; it ends when done == spp or no pixel is active.  A
+ *     pixel that left never returns, so all active pixels share one count.
+ *   A pixel's value is the prefix of its own sample law: sums and squares over samples [0, n) in sample order, resolved as sum / (float)n, gamma
+ *     and packing as for rt3_render_path.  A pixel with count n therefore equals, bit for bit, the same pixel of
+ *     rt3_render_path_range(cam, params, 0, n).
+ *   unconverged(q), owned pixel q with count n, sums S and squares Q; all in f32, every operation rounded on its own, in this order:
+ *     m_c = S_c / n;  v_c = Q_c / n - m_c * m_c, v_c = v_c > 0 ? v_c : 0;  e2 = ((v_r + v_g) + v_b) / n;  d = ((m_r + m_g) + m_b) + dark;
+ *     lim = threshold * d;  unconverged <=> e2 > lim * lim.
+ *   After a round p stays active <=> p was active and some pixel q is unconverged, q owned by this shard, inside the frame, |x_q - x_p| <= 1 and
+ *     |framerow_q - framerow_p| <= 1 (p itself is such a q).  Pixels of other shards are ignored: with tile_count > 1 the count map may differ from
+ *     the whole frame's along row-block edges; the prefix property holds for every pixel regardless.
+ * The squares are always kept: RT3_FLAG_VARIANCE in params->flags changes nothing.  min_spp == spp is exactly rt3_render_path.
+ * Outputs, both in compact tile rows as rt3_render_path writes them: the pixels, and (out_counts may be NULL) the samples each pixel received.
+ * RT3_E_ARG: a NULL pointer that is not allowed; min_spp outside [2, spp], step_spp == 0, a threshold that is not finite and > 0, a dark that is
+ * not finite and >= 0; RT3_FLAG_REFERENCE_PRIMARY; a device pointer that is not 16-byte (pixels) / 4-byte (counts) aligned.  RT3_E_STATE without a
+ * scene.
+ * The call replaces the context's accumulation with an adaptive one: rt3_accum_resolve* then divides each pixel by its own count (what a denoiser
+ * reads); rt3_accum_download and a following rt3_render_path_range with sample_begin != 0 return RT3_E_STATE (no checkpoint form); any later
+ * ordinary render starts over.
+ * Streams follow the convention above.  The device form is NOT fully asynchronous: it waits for the device once per round, to read back one
+ * word, the length of the active list.  rt3_get_stats afterwards: samples = the sum of the counts; ray_casts, launches, trace_ms and the filter
+ * counters are summed over the rounds.  In sphere scenes of <= 512 spheres only round 0 traces its primary rays against the strip lists: the
+ * active pixels of later rounds are not runs of 64 consecutive pixels, and their primary rays take the matrix filter. */
+typedef struct rt3_adaptive_params {   /* 16 bytes */
+    uint32_t min_spp;     /* samples every owned pixel gets first; 2 <= min_spp <= params->spp */
+    uint32_t step_spp;    /* samples per later round, >= 1 */
+    float    threshold;   /* relative standard error of the mean at which a pixel stops; finite, > 0 */
+    float    dark;        /* added to the mean r+g+b it is relative to; finite, >= 0 (0.01 is a good default) */
+} rt3_adaptive_params;
+int rt3_render_path_adaptive(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* params, const rt3_adaptive_params* adaptive,
+                             uint32_t* out_pixels, uint32_t* out_counts);
+int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* params, const rt3_adaptive_params* adaptive,
+                                    void* d_out_pixels, void* d_out_counts, void* stream);
 /* Checkpoint / resume of that accumulation.  Download: sum (and, when the accumulation runs with
  * RT3_FLAG_VARIANCE and sum_sq != NULL, the sums of squares) as 4 floats per owned pixel (r, g, b, 0), compact tile
  * rows as rt3_render_path writes them; *samples_done = samples accumulated.  Upload: restores such a state for

@@ -119,6 +119,12 @@ class TEMPORAL_PARAMS(C.Structure):
                 ("normal_tolerance", C.c_float)]
 
 
+class ADAPTIVE_PARAMS(C.Structure):
+    """rt3_adaptive_params (16 bytes): first-round samples, samples per later round, the relative standard error at which a pixel stops and
+    the floor added to the mean it is relative to."""
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("threshold", C.c_float), ("dark", C.c_float)]
+
+
 class Fatal(RuntimeError):
     """Mirror of CppDebugger::Fatal: every backend error is fatal (Main.cpp:305-308)."""
 
@@ -142,6 +148,7 @@ EXPORTS = [
     "rt3_motion", "rt3_motion_device", "rt3_denoise_temporal_motion", "rt3_denoise_temporal_motion_device",
     "rt3_update_spheres", "rt3_update_spheres_device", "rt3_update_mesh", "rt3_update_mesh_device",
     "rt3_debug_primary_lists",
+    "rt3_render_path_adaptive", "rt3_render_path_adaptive_device",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -211,6 +218,7 @@ def lib():
         "rt3_denoise_temporal_motion_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "rt3_update_spheres": (i32, [vp, vp, u32]), "rt3_update_spheres_device": (i32, [vp, vp, u32, vp]),
         "rt3_update_mesh": (i32, [vp, vp, vp, u32]), "rt3_update_mesh_device": (i32, [vp, vp, vp, u32, vp]),
+        "rt3_render_path_adaptive": (i32, [vp, vp, vp, vp, vp, vp]), "rt3_render_path_adaptive_device": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -705,6 +713,38 @@ class HipRenderer(Renderer):
     def render_path_range_device(self, camera_c, params, sample_begin, sample_count, d_out_ptr, stream_ptr=None):
         self._check(lib().rt3_render_path_range_device(self._ctx, C.byref(camera_c), C.byref(params), sample_begin, sample_count,
                                                        C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
+
+    # -- adaptive sampling (rt3_render_path_adaptive*) ------------------------------------------------
+    def render_adaptive(self, camera_c, params, threshold=0.05, min_spp=16, step_spp=16, dark=0.01):
+        """Mode X with params.spp as a budget: min_spp samples for every pixel, then step_spp at a time for the pixels whose 3 x 3
+        neighbourhood has not reached a relative standard error of `threshold`.  Returns (pixels, counts), both uint32 (rows_owned, width):
+        a pixel with count n is the pixel of render_path_range(camera_c, params, 0, n), bit for bit.  accum_resolve() afterwards gives the
+        linear frame (each pixel over its own count) for the denoiser."""
+        rows = lib().rt3_rows_owned(C.byref(params))
+        out = np.zeros((rows, params.width), np.uint32)
+        counts = np.zeros((rows, params.width), np.uint32)
+        ap = ADAPTIVE_PARAMS(min_spp, step_spp, threshold, dark)
+        self._check(lib().rt3_render_path_adaptive(self._ctx, C.byref(camera_c), C.byref(params), C.byref(ap), _p(out), _p(counts)))
+        return out, counts
+
+    def render_adaptive_device(self, camera_c, params, d_out, d_counts=None, stream_ptr=None, threshold=0.05, min_spp=16, step_spp=16, dark=0.01):
+        """The same into device memory (rt3_render_path_adaptive_device).  d_out / d_counts: raw device pointers (ints; the work is queued
+        on stream_ptr, None = the renderer's own stream) or contiguous 4-byte torch tensors of rows_owned * width elements on the GPU (queued
+        on torch.cuda.current_stream() unless stream_ptr is given); d_counts may be None.  The call waits for the device once per round."""
+        n = lib().rt3_rows_owned(C.byref(params)) * params.width
+        ptrs = []
+        for t, what in ((d_out, "d_out"), (d_counts, "d_counts")):
+            if t is not None and type(t).__module__.startswith("torch"):
+                if self._torch_rows(t, what, 4) != n:
+                    raise Fatal("device %s must hold rows_owned * width = %d 4-byte elements" % (what, n))
+                if stream_ptr is None:
+                    import torch
+                    stream_ptr = torch.cuda.current_stream(t.device).cuda_stream
+                t = t.data_ptr()
+            ptrs.append(C.c_void_p(t or 0))
+        ap = ADAPTIVE_PARAMS(min_spp, step_spp, threshold, dark)
+        self._check(lib().rt3_render_path_adaptive_device(self._ctx, C.byref(camera_c), C.byref(params), C.byref(ap), ptrs[0], ptrs[1],
+                                                          C.c_void_p(stream_ptr or 0)))
 
     def accum_download(self, params, want_sq=False):
         """Checkpoint of the accumulation: (sum[rows, w, 4], sum_sq or None, samples_done)."""

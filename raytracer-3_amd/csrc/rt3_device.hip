@@ -13,6 +13,8 @@
 //                           matrix cores (the default; RT3_NO_MFMA=1 selects the VALU scans)
 //   rt3_reduce.hpp          per-sample radiance (SampleStorage of raytracer_v4.glsl:107-111) summed in sample order and resolved
 //                           (the reduce pass reduce_v1.glsl never got) — the image is bitwise independent of scheduling and GPU count
+//   rt3_adaptive.hpp        adaptive sampling (rt3_render_path_adaptive*): the reduce pass over an active list, the convergence rule, the
+//                           ordered compaction of the pixels that stay active, the resolves by a pixel's own count
 //   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve
 //   rt3_denoise.hpp         the launchers of the AOV-guided a-trous denoiser, its temporal form and the motion plane (kernels: rt3_denoise.hip)
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
@@ -41,6 +43,7 @@
 #include "rt3_matrix_filter.hpp"
 #include "rt3_level_filter.hpp"
 #include "rt3_reduce.hpp"
+#include "rt3_adaptive.hpp"
 #include "rt3_aov.hpp"
 #include "rt3_denoise.hpp"
 #include "rt3_scene_kernels.hpp"
@@ -129,6 +132,10 @@ struct rt3_ctx {
     bool last_filter_counted = false;                               // ... and the kernel counted the casts that took the filter itself (d_casts[16])
     // the accumulation a progressive render continues (rt3_render_path_range): what it belongs to and how far it got
     bool acc_valid = false; rt3_params acc_params{}; rt3_camera acc_cam{}; uint32_t acc_done = 0; uint32_t acc_npix = 0;
+    // adaptive sampling (rt3_render_path_adaptive*): the accumulation holds a different number of samples per pixel, d_counts[pix]; the two
+    // active lists (ping-pong), the rule's verdict per pixel, the compaction's block counts and, behind them, the length of the new list
+    bool acc_adaptive = false;
+    DevBuf<uint32_t> d_counts, d_active[2], d_block_counts; DevBuf<uint8_t> d_unconverged;
     // launch configuration per (kernel, dynamic LDS): max dynamic LDS attribute set, workgroups per CU
     std::map<std::pair<const void*, size_t>, int> occupancy;
     std::set<int> peers_enabled;                                    // devices this context's device may already write to
@@ -595,22 +602,28 @@ void launch_primary_lists(const rt3_ctx* ctx, const TraceArgs& A, uint32_t n_gro
     constexpr uint32_t per_block = kBlock / 64;
     hipLaunchKernelGGL(k_primary_lists, dim3((n_groups + per_block - 1) / per_block), dim3(kBlock), 0, stream, A, n_groups, n_blocks, ctx->d_prim_masks.get());
 }
-template <bool Q, uint32_t L, bool R>
+// (LI: the list form of a render kernel, TraceArgs::active — non-REF renders only)
+template <bool Q, uint32_t L, bool R, bool LI = false>
 TiledKernel levels_kernel(bool has_tri, bool has_sph, bool ref) {
-    if constexpr (Q) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, true> : k_trace_levels<true, false, false, L, R, true>) : k_trace_levels<false, true, false, L, R, true>;
+    if constexpr (LI) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, false, true> : k_trace_levels<true, false, false, L, R, false, true>)
+                                     : k_trace_levels<false, true, false, L, R, false, true>;
+    else if constexpr (Q) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, true> : k_trace_levels<true, false, false, L, R, true>) : k_trace_levels<false, true, false, L, R, true>;
     else return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R> : (ref ? k_trace_levels<true, false, true, L, R> : k_trace_levels<true, false, false, L, R>))
                         : k_trace_levels<false, true, false, L, R>;
 }
-template <bool Q, bool RES>
+template <bool Q, bool RES, bool LI = false>
 TiledKernel grouped_kernel(bool has_tri, bool has_sph, bool ref) {
     constexpr uint32_t GT = kGroupTri, GS = kGroupSph, SUP = kSuper;
-    if constexpr (Q) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, true>)
+    if constexpr (LI) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, false, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, false, true>)
+                                     : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES, false, true>;
+    else if constexpr (Q) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, true>)
                                     : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES, true>;
     else return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES> : (ref ? k_trace_mfma_tiled<true, false, true, GT, 1, SUP, RES> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES>))
                         : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES>;
 }
 // Fills A's filter fields and T.  ref: RT3_FLAG_REFERENCE_PRIMARY (renders); ref_brute: REF with a camera only the brute-force kernel serves.
-int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query, TracePlan& T) {
+// list: the list form of the kernel a plain render (no ref, no query) would take, strip lists off (the later rounds of an adaptive render).
+int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query, TracePlan& T, bool list = false) {
     const bool has_tri = ctx->n_faces > 0, has_sph = ctx->n_sph > 0;
     const bool brute = ctx->force_brute || getenv("RT3_BRUTE") || ref_brute;
     const bool use_mfma = !brute && (query || !getenv("RT3_NO_MFMA"));
@@ -627,20 +640,20 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
     bool resident = false;
     uint32_t levels = 0;                                            // k_trace_levels: 3 | 4
     if (brute) {
-        T.plain = query ? k_trace_brute<false, true> : ref ? k_trace_brute<true> : k_trace_brute<false>;
+        T.plain = query ? k_trace_brute<false, true> : ref ? k_trace_brute<true> : list ? k_trace_brute<false, false, true> : k_trace_brute<false>;
     } else if (mfma_single) {
         // k_trace_mfma32 (K = 32 form, pair list); RT3_MFMA_K64=1: k_trace_mfma, round 1's K = 64 form on v_mfma_f32_32x32x16_bf16 (A/B reference)
         T.lds = single_k64 ? (size_t)T.mfma_blocks * (4096 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes
                            : (size_t)T.mfma_blocks * (2048 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes + (size_t)kMB * 8 + (size_t)(kMB / 64) * kPairCap * 4;
         T.block = kMB;
-        T.single = single_k64 ? k_trace_mfma : query ? k_trace_mfma32<true> : k_trace_mfma32<>;
+        T.single = single_k64 ? (list ? k_trace_mfma<true> : k_trace_mfma<>) : query ? k_trace_mfma32<true> : list ? k_trace_mfma32<false, true> : k_trace_mfma32<>;
         T.frag_a = (const u32x4*)(single_k64 ? ctx->d_sph_frag.get() : ctx->d_sph_frag32.get());
         if (!query && !single_k64) {
             T.filter_counted = true;
             const char* on = getenv("RT3_PRIMARY_LISTS"); const char* cap = getenv("RT3_PRIMARY_LIST_MAX");
             A.prim_masks = nullptr;                                 // (the slot held the face bounds' address: none in a sphere-only scene)
             A.prim_list_max = 0;
-            if (!(on && atoi(on) == 0)) {
+            if (!list && !(on && atoi(on) == 0)) {             // (a list's groups of 64 are not consecutive pixels: no strip lists)
                 T.list_groups = (A.npix + 63u) / 64u;
                 int rc_;
                 if ((rc_ = ctx->d_prim_masks.ensure(ctx, (size_t)T.list_groups * T.mfma_blocks))) return rc_;
@@ -667,13 +680,17 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
             A.tri_topb = levels == 4 ? ctx->tri.srowb : ctx->tri.rowb; A.sph_topb = levels == 4 ? ctx->sph.srowb : ctx->sph.rowb;
             if (query) T.tiled = levels == 4 ? (resident ? levels_kernel<true, 4, true>(has_tri, has_sph, ref) : levels_kernel<true, 4, false>(has_tri, has_sph, ref))
                                              : (resident ? levels_kernel<true, 3, true>(has_tri, has_sph, ref) : levels_kernel<true, 3, false>(has_tri, has_sph, ref));
+            else if (list) T.tiled = levels == 4 ? (resident ? levels_kernel<false, 4, true, true>(has_tri, has_sph, ref) : levels_kernel<false, 4, false, true>(has_tri, has_sph, ref))
+                                                 : (resident ? levels_kernel<false, 3, true, true>(has_tri, has_sph, ref) : levels_kernel<false, 3, false, true>(has_tri, has_sph, ref));
             else T.tiled = levels == 4 ? (resident ? levels_kernel<false, 4, true>(has_tri, has_sph, ref) : levels_kernel<false, 4, false>(has_tri, has_sph, ref))
                                        : (resident ? levels_kernel<false, 3, true>(has_tri, has_sph, ref) : levels_kernel<false, 3, false>(has_tri, has_sph, ref));
             T.lds = lev_lds_fixed(levels, resident) + (resident ? (size_t)top_blocks * 2048u : 0u);
         } else {
             resident = grouped && SUP > 1 && row_blocks <= kResidentBlocks && !getenv("RT3_NO_RESIDENT");      // all rows fit in LDS: no tiles, no barriers
-            if (resident) T.tiled = query ? grouped_kernel<true, true>(has_tri, has_sph, ref) : grouped_kernel<false, true>(has_tri, has_sph, ref);
-            else if (grouped) T.tiled = query ? grouped_kernel<true, false>(has_tri, has_sph, ref) : grouped_kernel<false, false>(has_tri, has_sph, ref);
+            if (resident) T.tiled = query ? grouped_kernel<true, true>(has_tri, has_sph, ref) : list ? grouped_kernel<false, true, true>(has_tri, has_sph, ref) : grouped_kernel<false, true>(has_tri, has_sph, ref);
+            else if (grouped) T.tiled = query ? grouped_kernel<true, false>(has_tri, has_sph, ref) : list ? grouped_kernel<false, false, true>(has_tri, has_sph, ref) : grouped_kernel<false, false>(has_tri, has_sph, ref);
+            else if (list) T.tiled = has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, 1, 1, 1, false, false, true> : k_trace_mfma_tiled<true, false, false, 1, 1, 1, false, false, true>)
+                                             : k_trace_mfma_tiled<false, true, false, 1, 1, 1, false, false, true>;
             else T.tiled = has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false> : (ref ? k_trace_mfma_tiled<true, false, true> : k_trace_mfma_tiled<true, false, false>))
                                    : k_trace_mfma_tiled<false, true, false>;
             T.lds = resident ? (size_t)row_blocks * 2048u + (size_t)kBmBlocksRes * kTB * 4u + (size_t)kTB * 8u + (size_t)(kTB / 64u) * kPairCap * 4u * 3u : kTraceTiledLdsBytes;
@@ -683,7 +700,9 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
         else { T.frag_a = grouped ? ctx->tri.gfrag : ctx->d_tri_frag; T.frag_b = grouped ? ctx->sph.gfrag.get() : (const u32x4*)ctx->d_sph_frag32.get(); }
     } else {
         T.lds = sph_lds ? (size_t)ctx->n_sph * sizeof(float4) : 0;
-        T.plain = has_tri ? (has_sph ? (sph_lds ? k_trace<true, true, true> : k_trace<true, true, false>)
+        if (list) T.plain = has_tri ? (has_sph ? (sph_lds ? k_trace<true, true, true, false, true> : k_trace<true, true, false, false, true>) : k_trace<true, false, false, false, true>)
+                                    : (sph_lds ? k_trace<false, true, true, false, true> : k_trace<false, true, false, false, true>);
+        else T.plain = has_tri ? (has_sph ? (sph_lds ? k_trace<true, true, true> : k_trace<true, true, false>)
                                      : (ref ? k_trace<true, false, false, true> : k_trace<true, false, false>))
                           : (sph_lds ? k_trace<false, true, true> : k_trace<false, true, false>);
     }
@@ -1257,6 +1276,8 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     const uint32_t rows = rt3_rows_owned(p);
     const uint32_t npix = rows * p->width;
     if (sample_begin != 0) {                                        // a continuation: of this very accumulation?
+        if (ctx->acc_valid && ctx->acc_adaptive)
+            return fail(ctx, RT3_E_STATE, "the accumulation held by this context is an adaptive one: it cannot be continued (start with sample_begin = 0)");
         if (!ctx->acc_valid || ctx->acc_done != sample_begin || ctx->acc_npix != npix || !same_bytes(&ctx->acc_params, p, sizeof *p) ||
             !same_bytes(&ctx->acc_cam, cam, sizeof *cam))
             return fail(ctx, RT3_E_STATE, "sample_begin does not continue the accumulation held by this context (same camera, params and "
@@ -1264,6 +1285,7 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     }
     ctx->rendered = false;                                          // stats: valid again once every launch below has been issued
     ctx->acc_valid = false;                                         // accumulation: valid again once this call has been issued completely
+    ctx->acc_adaptive = false;
     if (npix == 0) {
         if ((rc = begin_timed(ctx, stream)) || (rc = end_timed(ctx, stream, 0, nullptr))) return rc;
         ctx->acc_valid = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = sample_begin + sample_count; ctx->acc_npix = 0;
@@ -1349,10 +1371,154 @@ int rt3_render_path(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, ui
     return rt3_render_path_range(ctx, cam, p, 0, p->spp, out_pixels);
 }
 
+// Adaptive sampling: round 0 is the dense launch of rt3_render_path_range_device over samples [0, min_spp); every later round
+// traces the next samples of the pixels on the active list (the trace kernels' list form: TraceArgs::active), adds them with k_accumulate_list,
+// applies the rule and compacts the pixels that stay.  The host reads one word per round, the length of the new list.
+static_assert(sizeof(rt3_adaptive_params) == 16, "rt3.h: rt3_adaptive_params");
+int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, const rt3_adaptive_params* ap, void* d_out,
+                                    void* d_out_counts, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    if (!cam || !ap || !d_out) return fail(ctx, RT3_E_ARG, "cam / adaptive params / d_out_pixels is NULL");
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    if (p->flags & RT3_FLAG_REFERENCE_PRIMARY) return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY is not available to the adaptive render");
+    if (ap->min_spp < 2 || ap->min_spp > p->spp) return fail(ctx, RT3_E_ARG, "min_spp must lie in [2, spp]");
+    if (ap->step_spp < 1) return fail(ctx, RT3_E_ARG, "step_spp must be >= 1");
+    if (!(ap->threshold > 0.0f) || !(ap->threshold < __builtin_inff())) return fail(ctx, RT3_E_ARG, "threshold must be finite and > 0");
+    if (!(ap->dark >= 0.0f) || !(ap->dark < __builtin_inff())) return fail(ctx, RT3_E_ARG, "dark must be finite and >= 0");
+    if ((uintptr_t)d_out % 16u != 0) return fail(ctx, RT3_E_ARG, "d_out_pixels must be 16-byte aligned");
+    if ((uintptr_t)d_out_counts % 4u != 0) return fail(ctx, RT3_E_ARG, "d_out_counts must be 4-byte aligned");
+    if ((rc = check_scene(ctx))) return rc;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+
+    const uint32_t rows = rt3_rows_owned(p);
+    const uint32_t npix = rows * p->width;
+    ctx->rendered = false;
+    ctx->acc_valid = false;
+    ctx->acc_adaptive = false;
+    if (npix == 0) {
+        if ((rc = begin_timed(ctx, stream)) || (rc = end_timed(ctx, stream, 0, nullptr))) return rc;
+        ctx->acc_valid = true; ctx->acc_adaptive = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = p->spp; ctx->acc_npix = 0;
+        return 0;
+    }
+
+    // sample storage: sized once, for the dense round or the longest later round over every pixel; a list round takes as many samples per batch
+    // as fit in it (n_active in the place of npix)
+    const uint64_t per_spp = (uint64_t)npix * sizeof(Rgb);
+    const uint32_t longest = std::max(ap->min_spp, std::min(ap->step_spp, p->spp));
+    uint32_t batch = (uint32_t)std::min<uint64_t>(longest, std::max<uint64_t>(1, ctx->rad_cap_bytes / per_spp));
+    batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / npix);
+    if (batch == 0) return fail(ctx, RT3_E_ARG, "frame too large for one sample batch");
+    const size_t rad_items = (size_t)npix * batch;
+    const uint32_t n_blocks = (npix + kBlock - 1) / kBlock;
+    if ((rc = ctx->d_rad.ensure(ctx, rad_items)) || (rc = ctx->d_accum.ensure(ctx, npix)) || (rc = ctx->d_accum_sq.ensure(ctx, npix)) ||
+        (rc = ctx->d_counts.ensure(ctx, npix)) || (rc = ctx->d_active[0].ensure(ctx, npix)) || (rc = ctx->d_active[1].ensure(ctx, npix)) ||
+        (rc = ctx->d_unconverged.ensure(ctx, npix)) || (rc = ctx->d_block_counts.ensure(ctx, (size_t)n_blocks + 1)))
+        return rc;
+    uint32_t* const d_n_active = ctx->d_block_counts.get() + n_blocks;
+
+    TraceArgs A;
+    if ((rc = path_args(ctx, cam, p, npix, A))) return rc;
+    A.rad = ctx->d_rad;
+    TracePlan T, TL;                                                // the dense launch of round 0, the list form of the same kernel for the later rounds
+    if ((rc = plan_trace(ctx, A, false, false, false, T))) return rc;
+    TraceArgs AL = A;
+    if ((rc = plan_trace(ctx, AL, false, false, false, TL, true))) return rc;
+    AdaptiveGeom G{ p->width, rows, p->tile_rows, p->tile_index, p->tile_count, A.div_width, A.div_tile_rows };
+
+    if ((rc = begin_timed(ctx, stream))) return rc;
+    if (T.list_groups) {
+        launch_primary_lists(ctx, A, T.list_groups, T.mfma_blocks, stream);
+        RT3_HIP(hipGetLastError());
+    }
+    // one round: samples [s_begin, s_begin + s_count) of the n_items pixels the arguments B address, in batches of at most rad_items records
+    auto render_round = [&](const TracePlan& P, TraceArgs& B, uint32_t n_items, const uint32_t* active, uint32_t s_begin, uint32_t s_count) -> int {
+        const uint32_t per = (uint32_t)std::min<uint64_t>(s_count, std::min<uint64_t>(rad_items / n_items, 0x7FFF0000ull / n_items));
+        for (uint32_t s0 = s_begin; s0 < s_begin + s_count; s0 += per) {
+            const uint32_t ns = std::min(per, s_begin + s_count - s0);
+            B.s0 = s0;
+            B.total = n_items * ns;
+            hipEvent_t a, b;
+            int rc_;
+            if ((rc_ = take_event_pair(ctx, &a, &b))) return rc_;
+            RT3_HIP(hipMemsetAsync(ctx->d_work, 0, 4, stream));
+            RT3_HIP(hipEventRecord(a, stream));
+            launch_trace(P, B, trace_grid(ctx, P, B.total), stream);
+            RT3_HIP(hipGetLastError());
+            RT3_HIP(hipEventRecord(b, stream));
+            const dim3 ag((n_items + kBlock - 1) / kBlock), ab(kBlock);
+            if (active) hipLaunchKernelGGL(k_accumulate_list<true>, ag, ab, 0, stream, ctx->d_rad, active, n_items, ctx->d_accum, ctx->d_accum_sq,
+                                           ctx->d_counts, ns, s0 + ns);
+            else hipLaunchKernelGGL(k_accumulate<true>, ag, ab, 0, stream, ctx->d_rad, ctx->d_accum, ctx->d_accum_sq, npix, ns, s0 == 0 ? 1 : 0);
+            RT3_HIP(hipGetLastError());
+        }
+        return 0;
+    };
+    if ((rc = render_round(T, A, npix, nullptr, 0, ap->min_spp))) return rc;
+    hipLaunchKernelGGL(k_fill_words, dim3(n_blocks), dim3(kBlock), 0, stream, ctx->d_counts, npix, ap->min_spp);
+    RT3_HIP(hipGetLastError());
+
+    uint64_t samples = (uint64_t)npix * ap->min_spp;
+    uint32_t done = ap->min_spp, cur = 0;
+    while (done < p->spp) {
+        // who stays active after the round that ended at `done`: the rule, then the ordered compaction into the other list
+        hipLaunchKernelGGL(k_adaptive_flags, dim3(n_blocks), dim3(kBlock), 0, stream, (const float4*)ctx->d_accum, (const float4*)ctx->d_accum_sq,
+                           (const uint32_t*)ctx->d_counts, npix, ap->threshold, ap->dark, ctx->d_unconverged.get());
+        hipLaunchKernelGGL(k_adaptive_count, dim3(n_blocks), dim3(kBlock), 0, stream, G, (const uint32_t*)ctx->d_counts,
+                           (const uint8_t*)ctx->d_unconverged, npix, done, ctx->d_block_counts.get());
+        hipLaunchKernelGGL(k_adaptive_select, dim3(n_blocks), dim3(kBlock), 0, stream, G, (const uint32_t*)ctx->d_counts,
+                           (const uint8_t*)ctx->d_unconverged, npix, done, (const uint32_t*)ctx->d_block_counts, ctx->d_active[cur].get(), d_n_active);
+        RT3_HIP(hipGetLastError());
+        uint32_t n_active = 0;
+        RT3_HIP(hipMemcpyAsync(&n_active, d_n_active, 4, hipMemcpyDeviceToHost, stream));
+        RT3_HIP(hipStreamSynchronize(stream));
+        if (n_active == 0) break;
+        if (n_active > npix) return fail(ctx, RT3_E_DEVICE, "internal: the active list is longer than the frame");
+        TraceArgs B = AL;
+        B.active = ctx->d_active[cur];
+        B.npix = n_active;
+        B.div_npix = make_fastdiv(n_active);
+        if (!fastdiv_ok(n_active, 0x7FFFFFFFu)) return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
+        const uint32_t ns = std::min(ap->step_spp, p->spp - done);
+        if ((rc = render_round(TL, B, n_active, ctx->d_active[cur], done, ns))) return rc;
+        samples += (uint64_t)n_active * ns;
+        done += ns;
+        cur ^= 1u;
+    }
+    hipLaunchKernelGGL(k_resolve_counts, dim3(n_blocks), dim3(kBlock), 0, stream, (const float4*)ctx->d_accum, (const uint32_t*)ctx->d_counts, npix,
+                       p->flags, (uint32_t*)d_out);
+    RT3_HIP(hipGetLastError());
+    if (d_out_counts) RT3_HIP(hipMemcpyAsync(d_out_counts, ctx->d_counts, (size_t)npix * 4, hipMemcpyDeviceToDevice, stream));
+    if ((rc = end_timed(ctx, stream, samples, &T))) return rc;
+    ctx->acc_valid = true; ctx->acc_adaptive = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = p->spp; ctx->acc_npix = npix;
+    return 0;
+}
+
+int rt3_render_path_adaptive(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, const rt3_adaptive_params* ap, uint32_t* out_pixels,
+                             uint32_t* out_counts) {
+    if (!ctx) return RT3_E_ARG;
+    if (!out_pixels) return fail(ctx, RT3_E_ARG, "out_pixels is NULL");
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
+    const size_t quads = (std::max<size_t>(npix, 1) + 3) / 4;        // pixels, then counts, each at a float4 offset of the staging buffer
+    if ((rc = ctx->stage.ensure(ctx, 2 * quads))) return rc;
+    uint32_t* const d_out = (uint32_t*)ctx->stage.get();
+    uint32_t* const d_counts = (uint32_t*)(ctx->stage.get() + quads);
+    if ((rc = rt3_render_path_adaptive_device(ctx, cam, p, ap, d_out, out_counts ? d_counts : nullptr, ctx->stream))) return rc;
+    if (npix) RT3_HIP(hipMemcpyAsync(out_pixels, d_out, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (npix && out_counts) RT3_HIP(hipMemcpyAsync(out_counts, d_counts, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 // Checkpoint of the accumulation: what rt3_render_path_range keeps between calls, 4 floats per owned pixel.
 int rt3_accum_download(rt3_ctx* ctx, float* sum, float* sum_sq, uint32_t* samples_done) {
     if (!ctx) return RT3_E_ARG;
     if (!ctx->acc_valid) return fail(ctx, RT3_E_STATE, "no accumulation on this context");
+    if (ctx->acc_adaptive) return fail(ctx, RT3_E_STATE, "the accumulation is an adaptive one (per-pixel sample counts): it has no checkpoint form");
     RT3_HIP(hipSetDevice(ctx->device));
     if (ctx->ev_acc_recorded) RT3_HIP(hipEventSynchronize(ctx->ev_acc));        // the render may have run on a caller's stream (which may be gone by now)
     const size_t bytes = (size_t)ctx->acc_npix * sizeof(float4);
@@ -1376,6 +1542,7 @@ int rt3_accum_upload(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, c
     RT3_HIP(hipSetDevice(ctx->device));
     const uint32_t npix = rt3_rows_owned(p) * p->width;
     ctx->acc_valid = false;
+    ctx->acc_adaptive = false;
     if (ctx->ev_acc_recorded) RT3_HIP(hipEventSynchronize(ctx->ev_acc));        // a render still in flight reads and writes what is overwritten here
     if (npix) {
         if ((rc = ctx->d_accum.ensure(ctx, npix))) return rc;
@@ -1611,8 +1778,10 @@ int rt3_accum_resolve_device(rt3_ctx* ctx, void* d_out, void* stream_) {
     const int rc = enter(ctx, stream_, &stream);                    // behind the render that wrote d_accum
     if (rc) return rc;
     if (ctx->acc_npix) {
-        hipLaunchKernelGGL(k_resolve_float, dim3((ctx->acc_npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_accum,
-                           ctx->acc_npix, ctx->acc_done, (float4*)d_out);
+        const dim3 grid((ctx->acc_npix + kBlock - 1) / kBlock);
+        if (ctx->acc_adaptive) hipLaunchKernelGGL(k_resolve_float_counts, grid, dim3(kBlock), 0, stream, (const float4*)ctx->d_accum,
+                                                  (const uint32_t*)ctx->d_counts, ctx->acc_npix, (float4*)d_out);
+        else hipLaunchKernelGGL(k_resolve_float, grid, dim3(kBlock), 0, stream, (const float4*)ctx->d_accum, ctx->acc_npix, ctx->acc_done, (float4*)d_out);
         RT3_HIP(hipGetLastError());
     }
     return leave(ctx, stream);                                      // a later render that overwrites d_accum waits for this

@@ -156,6 +156,10 @@ struct TraceArgs {
     uint32_t* pair_strips;   // [wave of the grid][kStripPairs]: candidate (ray lane, row) pairs set aside for the end of a pass (deferred member tests)
     uint32_t* work_counter;
     unsigned long long* cast_counter;
+    // List form of a work item (the later rounds of rt3_render_path_adaptive*): non-null, item j is (sample s0 + j / npix, pixel
+    // active[j % npix]) with npix = the length of the list, and the strip lists are off (prim_masks null).  Only the LIST instantiations of the trace
+    // kernels read it.  It is the LAST field: every slot above is read by some render form, and a field behind them moves none of them.
+    const uint32_t* active;
 };
 
 struct Path {
@@ -225,9 +229,13 @@ __device__ __forceinline__ uint32_t frame_row(const TraceArgs& A, uint32_t local
 
 // sample -> primary ray (raytracer_v4.glsl:190-214 with the jitter in pixel units), unit direction.
 // REF (RT3_FLAG_REFERENCE_PRIMARY): the direction stays unnormalised, as SequentialRenderer.cpp:293 leaves it.
-template <bool REF = false>
+// LIST: the list form of a work item (TraceArgs::active).  A compile-time flag, not a test of the pointer: the dense kernels' code stays what it was
+// (a wave-uniform test cost two of them scratch, profiles/adaptive_kernel_resources.log).
+template <bool REF = false, bool LIST = false>
 __device__ __forceinline__ void start_path(const TraceArgs& A, uint32_t item, Path& P) {
-    const uint32_t sb = fdiv(item, A.div_npix), pix = item - sb * A.npix;
+    const uint32_t sb = fdiv(item, A.div_npix);
+    uint32_t pix = item - sb * A.npix;
+    if constexpr (LIST) pix = A.active[pix];
     const uint32_t s = A.s0 + sb;
     const uint32_t lrow = fdiv(pix, A.div_width), x = pix - lrow * A.width;
     const uint32_t y = frame_row(A, lrow);

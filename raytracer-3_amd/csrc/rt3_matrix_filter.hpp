@@ -727,6 +727,7 @@ __device__ __forceinline__ void drain_strip(uint32_t lane, const uint32_t* strip
 }
 
 // Sphere scenes of <= 512 spheres: everything the loop touches lives in LDS, waves never synchronise after the prologue.
+template <bool LIST = false>
 __global__ __launch_bounds__(kMB) void k_trace_mfma(const TraceArgs A, const u32x4* __restrict__ frags, uint32_t n_blocks) {
     extern __shared__ u32x4 lds_dyn[];
     u32x4* s_frag = lds_dyn;                                                   // [n_blocks][4][64]
@@ -768,7 +769,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma(const TraceArgs A, const u32
 #define RT3_SPHASE(acc)
 #endif
     for (;;) {
-        refill_from_stock(A, lane, alive, P, Q, chunk_next, chunk_end, exhausted);
+        refill_from_stock<false, LIST>(A, lane, alive, P, Q, chunk_next, chunk_end, exhausted);
         RT3_SPHASE(ph_refill)
 #ifdef RT3_PROFILE
         if (exhausted && !prof_dry_seen) {
@@ -860,6 +861,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma(const TraceArgs A, const u32
 // A restock whose groups list more than A.prim_list_max spheres (or have no list: every bit set) stocks its rays untraced; they take the filter.
 // casts: primary casts traced here; exact: their (ray, sphere) tests.  ph_restock (RT3_PROFILE_PHASES): wave time of the primary pass.
 struct SphereMirror { const float4* sph; const float* invr; const float4* mat; const uint32_t* kind; uint32_t n_blocks; };     // LDS
+template <bool LIST = false>
 __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, const SphereMirror& S, uint32_t lane, bool& alive, Path& P, TracedStock& Q,
                                                          uint32_t& chunk_next, uint32_t& chunk_end, bool& exhausted, unsigned long long& casts,
                                                          unsigned long long& exact, unsigned long long& ph_restock) {
@@ -892,7 +894,7 @@ __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, con
         const uint32_t item = min(chunk_next + lane, chunk_end - 1u);
         bool live = lane < n_new;                                           // (the lanes beyond repeat the last item: they take no part)
         Path T;
-        start_path<false>(A, item, T);
+        start_path<false, LIST>(A, item, T);
         chunk_next += n_new;
         // the union of the lists of the pixel groups these items fall into (one or two; more only where a sample block is shorter than 64
         // pixels): lane b holds the word of row block b
@@ -955,7 +957,7 @@ __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, con
 // at full lane utilisation, the ray operands cost half), but the matrix pipe does half the work and the chip, which throttles under
 // k_trace_mfma's load (2.0-2.2 GHz), holds 2.3-2.4 GHz here — and a kernel bound by vector-ALU issue runs at the clock.
 // QUERY: the batched ray queries' form (refill from the caller's rays, no ray stock; the nearest-hit key goes to query_sink instead of shading).
-template <bool QUERY = false>
+template <bool QUERY = false, bool LIST = false>
 __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u32x4* __restrict__ frags, uint32_t n_blocks) {
     extern __shared__ u32x4 lds_dyn[];
     u32x4* s_frag = lds_dyn;                                                   // [n_blocks][2][64]
@@ -999,7 +1001,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
 
     for (;;) {
         if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else refill_from_traced_stock(A, mirror, lane, alive, P, Q, chunk_next, chunk_end, exhausted, primary_casts, exact, ph_restock);
+        else refill_from_traced_stock<LIST>(A, mirror, lane, alive, P, Q, chunk_next, chunk_end, exhausted, primary_casts, exact, ph_restock);
         RT3_SPHASE(ph_refill)
         const unsigned long long live = __ballot(alive);
         if (live == 0ull) break;
@@ -1106,7 +1108,7 @@ constexpr uint32_t kResidentBlocks = (160u * 1024u - kTB * 8u - (kTB / 64u) * kP
 // (one block of headroom: a kernel with any static LDS beside the dynamic request — __syncthreads_or's word, say — is refused at exactly 160 KiB;
 // this variant has none and did launch with 56, profiles/README.md)
 // QUERY: the batched ray queries' form (REF false; the nearest-hit key goes to query_sink instead of shading).
-template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t GT = 1, uint32_t GS = 1, uint32_t SUP = 1, bool RES = false, bool QUERY = false>
+template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t GT = 1, uint32_t GS = 1, uint32_t SUP = 1, bool RES = false, bool QUERY = false, bool LIST = false>
 __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
     static_assert(64 % GT == 0 && 64 % GS == 0, "group sizes must divide the wave");
     static_assert(!RES || (SUP > 1 && RT3_FACE_K32), "resident rows: three-level filter only");
@@ -1146,7 +1148,7 @@ __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, con
     for (;;) {
         // (no ray stock here: a ray cast costs at least one tile scan, start_path is noise beside it, and the stock's 8 registers are needed)
         if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else refill_lanes<REF>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else refill_lanes<REF, false, LIST>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         const unsigned long long live = __ballot(alive);
         if constexpr (RES) { if (live == 0ull) break; }                           // every wave for itself
         else if (!__syncthreads_or(live != 0ull ? 1 : 0)) break;                 // tiles: the workgroup ends together

@@ -31,7 +31,7 @@ __device__ __forceinline__ bool query_ray(const TraceArgs& A, uint32_t item, Pat
 // Refill: lanes whose path ended take the next samples of the wave's chunk (ballot + prefix count); a chunk of
 // kWorkChunk samples is fetched from the global queue with one atomic when the wave runs dry.
 // QUERY: the items are the caller's rays (query_ray); an invalid one leaves its lane empty (refill_queries fills it again).
-template <bool REF = false, bool QUERY = false>
+template <bool REF = false, bool QUERY = false, bool LIST = false>
 __device__ __forceinline__ void refill_lanes(const TraceArgs& A, uint32_t lane, bool& alive, Path& P, uint32_t& chunk_next,
                                              uint32_t& chunk_end, bool& exhausted) {
     const unsigned long long need = __ballot(!alive);
@@ -55,7 +55,7 @@ __device__ __forceinline__ void refill_lanes(const TraceArgs& A, uint32_t lane, 
         }
         if (item != 0xFFFFFFFFu) {
             if constexpr (QUERY) alive = query_ray(A, item, P);
-            else { start_path<REF>(A, item, P); alive = true; }
+            else { start_path<REF, LIST>(A, item, P); alive = true; }
         }
     }
 }
@@ -81,7 +81,7 @@ __device__ __forceinline__ void stock_pop(const RayStock& Q, uint32_t src, bool 
         alive = true;
     }
 }
-template <bool REF = false>
+template <bool REF = false, bool LIST = false>
 __device__ __forceinline__ void refill_from_stock(const TraceArgs& A, uint32_t lane, bool& alive, Path& P, RayStock& Q, uint32_t& chunk_next,
                                                   uint32_t& chunk_end, bool& exhausted) {
     const unsigned long long need = __ballot(!alive);
@@ -108,7 +108,7 @@ __device__ __forceinline__ void refill_from_stock(const TraceArgs& A, uint32_t l
         }
         const uint32_t n_new = min(64u, chunk_end - chunk_next);
         Path T;
-        start_path<REF>(A, min(chunk_next + lane, chunk_end - 1u), T);
+        start_path<REF, LIST>(A, min(chunk_next + lane, chunk_end - 1u), T);
         Q.ox = T.ox; Q.oy = T.oy; Q.oz = T.oz; Q.dx = T.dx; Q.dy = T.dy; Q.dz = T.dz; Q.slot = T.slot; Q.base = T.base;
         Q.n = n_new;
         chunk_next += n_new;

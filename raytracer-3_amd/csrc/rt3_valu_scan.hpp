@@ -189,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void k_mode_r_fast(const float4* __restrict
 
 // SPH_LDS: the sphere array (<= kSphLdsMax entries) is also copied to LDS once per block, for the per-lane gathers of
 // the exact evaluation (an LDS gather costs ~64 cycles, a global one an L2 round trip per candidate).
-template <bool HAS_TRI, bool HAS_SPH, bool SPH_LDS, bool REF = false>
+template <bool HAS_TRI, bool HAS_SPH, bool SPH_LDS, bool REF = false, bool LIST = false>
 __global__ __launch_bounds__(kBlock) void k_trace(const TraceArgs A) {
     __shared__ uint32_t cand[kCandSlots * kBlock];                  // per-lane candidate queues, [slot][thread]
     extern __shared__ float4 s_sph[];                               // SPH_LDS only
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void k_trace(const TraceArgs A) {
     unsigned long long casts = 0;                                   // wave-uniform
 
     for (;;) {
-        refill_lanes<REF>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        refill_lanes<REF, false, LIST>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         if (__ballot(alive) == 0ull) break;                         // waves are independent: no block-level barrier anywhere
         casts += (unsigned long long)__popcll(__ballot(alive));
 
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(kBlock) void k_trace(const TraceArgs A) {
 // camera off the origin (the reference's literal formula then puts the "hit point" off the face's plane, where no bound holds).
 // Scene records are wave-uniform loads through the constant address space (scalar cache); one path per lane, refill by ballot.
 // QUERY: the batched ray queries' arbiter (rt3_intersect* / rt3_occluded* under the same switch): the running best starts at the ray's t_max.
-template <bool REF, bool QUERY = false>
+template <bool REF, bool QUERY = false, bool LIST = false>
 __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
     const uint32_t lane = lane_id();
     Path P;
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
 
     for (;;) {
         if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else refill_lanes<REF>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else refill_lanes<REF, false, LIST>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         if (__ballot(alive) == 0ull) break;
         casts += (unsigned long long)__popcll(__ballot(alive));
         float tbest = QUERY ? P.tmax : __builtin_inff();

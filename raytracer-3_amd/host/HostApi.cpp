@@ -331,6 +331,30 @@ void gather_shards(uint32_t n, uint32_t w, ParamsOf params_of, Fetch fetch, T* f
 }
 }  // namespace
 
+std::vector<uint32_t> HipRenderer::render_adaptive(Camera& camera, const rt3_adaptive_params& adaptive) const {
+    if (path.spp == 0) throw Fatal("adaptive sampling needs the path tracer (Mode X)");
+    const rt3_camera cam = camera.wire();
+    const uint32_t w = camera.w(), h = camera.h();
+    struct Sampled { uint32_t pixel, count; };
+    std::vector<Sampled> frame((size_t)w * h);
+    last_w = w; last_h = h;
+    gather_shards<Sampled>((uint32_t)ctx.size(), w, [&](uint32_t i) { return shard_params(w, h, i); },
+                           [&](uint32_t i, const rt3_params& p, Sampled* tile, std::string& err) {
+                               const size_t n = (size_t)rt3_rows_owned(&p) * w;
+                               std::vector<uint32_t> pixels(n), counts(n);
+                               if (rt3_render_path_adaptive(ctx[i], &cam, &p, &adaptive, pixels.data(), counts.data()) != 0) {
+                                   err = rt3_last_error(ctx[i]);
+                                   return false;
+                               }
+                               for (size_t k = 0; k < n; k++) tile[k] = Sampled{ pixels[k], counts[k] };
+                               return true;
+                           }, frame.data());
+    uint32_t* out = camera.get_frame().d();
+    std::vector<uint32_t> counts(frame.size());
+    for (size_t k = 0; k < frame.size(); k++) { out[k] = frame[k].pixel; counts[k] = frame[k].count; }
+    return counts;
+}
+
 std::vector<rt3_aov> HipRenderer::aov(Camera& camera) const {
     if (path.spp == 0) throw Fatal("first-hit AOVs need the path tracer (Mode X)");
     const rt3_camera cam = camera.wire();

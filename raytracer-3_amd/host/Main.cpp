@@ -6,7 +6,7 @@
 // output path (later ones ignored), value forms `-W 400`, `-W400`, `--width 400`; exit code 0 after help, -1 on a
 // usage error, -1 on a fatal backend error.  Fixed: `--key=value`, which the reference mis-parses (Main.cpp:110).
 // Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr, --denoise (PFM files),
-// --frames, --orbit and --slide (a sequence, denoised temporally).
+// --frames, --orbit and --slide (a sequence, denoised temporally), --adaptive and --counts (--spp as a budget).
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -39,6 +39,10 @@ struct Options {
     float slide[3] = { 0.0f, 0.0f, 0.0f };                         // sphere scenes: what every sphere of odd index moves by per frame
     bool have_slide = false;
     bool refit = false;                                            // --slide: frames after the first update the spheres in place (rt3_update_spheres)
+    bool adaptive = false;                                         // Mode X: --spp is a budget (rt3_render_path_adaptive)
+    float adaptive_threshold = 0.05f;
+    uint32_t adaptive_min = 0, adaptive_step = 16;                 // (min 0: not given = min(16, spp))
+    std::string counts_path;                                       // --adaptive: the samples per pixel as a 1-channel PFM
 };
 
 void print_usage(const char* exe) {
@@ -63,6 +67,9 @@ void print_usage(const char* exe) {
               << "\t   --slide\tthree / weekend / stress100k with --frames: translate every sphere of odd index by k * (DX,DY,DZ) in frame k;\n"
               << "\t\t\twith --denoise PREFIX the temporal filter follows them (the motion plane).\n"
               << "\t   --refit\tWith --slide: frames after the first move the spheres by an update on the device instead of a full upload (same frames).\n"
+              << "\t   --adaptive\tMode X: T[,MIN[,STEP]]: --spp is a budget; MIN samples for every pixel (default: 16), then STEP at a time (default: 16)\n"
+              << "\t\t\tfor the pixels whose neighbourhood has not reached a relative standard error of T. Combines with --hdr, --aov, --denoise.\n"
+              << "\t   --counts\tWith --adaptive: also write the samples every pixel received to this path as a 1-channel PFM.\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -103,7 +110,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         const bool known = key == "-f" || key == "--format" || key == "-W" || key == "--width" || key == "-H" || key == "--height" ||
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
-                           key == "--slide";
+                           key == "--slide" || key == "--adaptive" || key == "--counts";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -151,6 +158,22 @@ int parse_cli(Options& opt, int argc, const char** argv) {
             if (!ok) { std::cerr << "Invalid slide '" << value << "'" << std::endl; return -1; }
             opt.have_slide = true;
         }
+        else if (key == "--adaptive") {                              // T[,MIN[,STEP]]: a finite T > 0, MIN >= 2, STEP >= 1
+            char* end = nullptr;
+            const double t = std::strtod(value.c_str(), &end);
+            bool ok = end != value.c_str() && std::isfinite(t) && (float)t > 0.0f && std::isfinite((float)t) && (*end == ',' || *end == '\0');
+            uint32_t* const fields[2] = { &opt.adaptive_min, &opt.adaptive_step };
+            for (int c = 0; c < 2 && ok && *end == ','; c++) {
+                const char* at = end + 1;
+                ok = std::isdigit((unsigned char)*at) != 0;
+                const unsigned long long v = ok ? std::strtoull(at, &end, 10) : 0ull;
+                ok = ok && v <= std::numeric_limits<uint32_t>::max() && v >= (c == 0 ? 2ull : 1ull) && (*end == '\0' || (c == 0 && *end == ','));
+                *fields[c] = (uint32_t)v;
+            }
+            if (!ok || *end != '\0') { std::cerr << "Invalid adaptive '" << value << "'" << std::endl; return -1; }
+            opt.adaptive = true; opt.adaptive_threshold = (float)t;
+        }
+        else if (key == "--counts") opt.counts_path = value;
         else opt.scene = value;
     }
     if (opt.output_path.empty() && !opt.dump_scene) { std::cerr << "No output path given." << std::endl; return -1; }
@@ -162,6 +185,14 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     }
     if (mode_r && !opt.denoise_path.empty()) {
         std::cerr << "--denoise needs the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
+    if (mode_r && opt.adaptive) {
+        std::cerr << "--adaptive needs the path tracer (Mode X): pass --spp, the budget." << std::endl;
+        return -1;
+    }
+    if (!opt.counts_path.empty() && !opt.adaptive) {
+        std::cerr << "--counts needs --adaptive: a uniform render gives every pixel --spp samples." << std::endl;
         return -1;
     }
     if (opt.frames == 0) { std::cerr << "--frames must be at least 1." << std::endl; return -1; }
@@ -292,6 +323,7 @@ int main(int argc, const char** argv) {
         const rt3_temporal_params tp{ { 5, 128, 4.0f, 1.0f }, 0.2f, 0.2f, 2.0f, 0.9f };       // the defaults of DESIGN.md 4.11 and 4.12
         History history;
         std::vector<float> shown_cr = scene_cr, prev_cr;             // --slide: the spheres of this frame and of the one before
+        std::vector<uint32_t> counts;                                // --adaptive: the samples every pixel of the last frame received
         for (uint32_t k = 0; k < opt.frames; k++) {
             if (opt.have_slide && k > 0) {                           // frame k: every sphere of odd index translated by k * slide
                 prev_cr = shown_cr;
@@ -308,7 +340,10 @@ int main(int argc, const char** argv) {
             }
             path.seed = seed0 + k;
             renderer.configure(path);
-            renderer.render(cam);
+            if (opt.adaptive) {
+                const uint32_t min_spp = opt.adaptive_min ? opt.adaptive_min : (path.spp < 16u ? path.spp : 16u);
+                counts = renderer.render_adaptive(cam, rt3_adaptive_params{ min_spp, opt.adaptive_step, opt.adaptive_threshold, 0.01f });
+            } else renderer.render(cam);
             if (temporal) {
                 std::vector<float> motion;
                 if (opt.have_slide && k > 0) motion = renderer.motion(cam, prev_cr, {});
@@ -324,6 +359,15 @@ int main(int argc, const char** argv) {
         if (opt.png) cam.get_frame().to_png(opt.output_path);
         else cam.get_frame().to_ppm(opt.output_path);
         const uint32_t w = cam.w(), h = cam.h();
+        if (opt.adaptive) {
+            uint64_t total = 0;
+            for (const uint32_t c : counts) total += c;
+            std::cerr << "adaptive: " << total << " samples, " << (double)total / ((double)w * h * path.spp) << " of the uniform " << path.spp << " spp\n";
+            if (!opt.counts_path.empty()) {
+                const std::vector<float> as_float(counts.begin(), counts.end());
+                if (rt3_frame_to_pfm(as_float.data(), w, h, 1, 1, opt.counts_path.c_str()) != 0) throw Fatal("Could not write '" + opt.counts_path + "'");
+            }
+        }
         if (!opt.hdr_path.empty()) {
             const std::vector<float> hdr = renderer.hdr();
             if (rt3_frame_to_pfm(hdr.data(), w, h, 3, 4, opt.hdr_path.c_str()) != 0) throw Fatal("Could not write '" + opt.hdr_path + "'");

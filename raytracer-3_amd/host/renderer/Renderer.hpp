@@ -40,6 +40,10 @@ public:
     void prerender(const Tools::Array<ECS::RenderEntity*>& entities) override;   // flatten in entity order + upload
     void render(Camera& camera) const override;                                  // fills camera.get_frame().d()
     void configure(const PathOptions& options) { path = options; }
+    // Mode X only: render() with path.spp as a budget (rt3_render_path_adaptive on every device shard).  Fills
+    // camera.get_frame().d() and returns the samples each pixel received, a full frame, row 0 on top.  hdr(), aov() and the denoisers follow it
+    // as they follow render().  With several devices every shard decides over its own rows (the count map may differ along row-block edges).
+    std::vector<uint32_t> render_adaptive(Camera& camera, const rt3_adaptive_params& adaptive) const;
     void set_gpu_prerender(bool on) { gpu_prerender = on; }         // tessellate eprmf_gpu entities on the device (default: host)
     // scenes that are not entity lists (benchmark sphere fields)
     void set_spheres(const std::vector<float>& center_radius, const std::vector<rt3_material>& materials);

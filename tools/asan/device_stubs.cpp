@@ -28,6 +28,8 @@ int rt3_render_path(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t*) {
 int rt3_render_path_device(rt3_ctx*, const rt3_camera*, const rt3_params*, void*, void*) { return RT3_E_DEVICE; }
 int rt3_render_path_range(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t, uint32_t, uint32_t*) { return RT3_E_DEVICE; }
 int rt3_render_path_range_device(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t, uint32_t, void*, void*) { return RT3_E_DEVICE; }
+int rt3_render_path_adaptive(rt3_ctx*, const rt3_camera*, const rt3_params*, const rt3_adaptive_params*, uint32_t*, uint32_t*) { return RT3_E_DEVICE; }
+int rt3_render_path_adaptive_device(rt3_ctx*, const rt3_camera*, const rt3_params*, const rt3_adaptive_params*, void*, void*, void*) { return RT3_E_DEVICE; }
 int rt3_accum_download(rt3_ctx*, float*, float*, uint32_t*) { return RT3_E_DEVICE; }
 int rt3_accum_upload(rt3_ctx*, const rt3_camera*, const rt3_params*, const float*, const float*, uint32_t) { return RT3_E_DEVICE; }
 int rt3_gather_rows(rt3_ctx*, void*, rt3_ctx*, const void*, const rt3_params*, void*) { return RT3_E_DEVICE; }

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Before/after table of the kernels' resource usage, from two logs of
+
+    hipcc --offload-arch=gfx950 <the Makefile's HIPFLAGS> -Rpass-analysis=kernel-resource-usage ... 2> LOG
+
+(one of the parent commit, one of this tree).  Kernels are matched by their demangled names; where this tree gave a kernel template one more
+trailing parameter whose value `false` selects the parent's kernel (the LIST flag of the trace kernels), that argument is dropped first, so the
+dense instantiation is compared with the kernel it was.  Prints one line per kernel, `a -> b` where a figure changed, NEW for kernels the parent
+does not have, and ends with the number of existing kernels that gained scratch or lost occupancy (exit code 1 if there is one).
+
+    python tools/kernel_resources.py PARENT.log TREE.log > profiles/adaptive_kernel_resources.log
+"""
+import re
+import shutil
+import subprocess
+import sys
+
+KEYS = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]"]
+# template arguments of the trace kernels in the parent: one more, `false`, is this tree's LIST flag
+PARENT_ARGS = {"k_trace_mfma32": 1, "k_trace_mfma_tiled": 8, "k_trace_levels": 6, "k_trace": 4, "k_trace_brute": 2, "k_trace_mfma": 0}
+
+
+def parse(path):
+    out, cur = {}, None
+    for line in open(path, errors="replace"):
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            cur = out.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+([A-Za-z \[\]/]+): (\S+) \[-Rpass", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = m.group(2)
+    return out
+
+
+def demangled(names):
+    tool = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
+    if not tool:
+        return list(names)
+    return subprocess.run([tool] + list(names), capture_output=True, text=True, check=True).stdout.splitlines()
+
+
+def key(d):
+    d = re.sub(r"\(anonymous namespace\)::", "", d)
+    d = re.sub(r"^void ", "", re.sub(r"\(.*$", "", d))
+    m = re.match(r"(\w+)<(.*)>$", d)
+    if not m or m.group(1) not in PARENT_ARGS:
+        return d
+    args = [x.strip() for x in m.group(2).split(",")]
+    if len(args) == PARENT_ARGS[m.group(1)] + 1 and args[-1] == "false":
+        args = args[:-1]
+    return "%s<%s>" % (m.group(1), ", ".join(args)) if args else m.group(1)
+
+
+def table(path):
+    raw = parse(path)
+    return {key(d): raw[n] for n, d in zip(raw, demangled(raw))}
+
+
+def main():
+    a, b = table(sys.argv[1]), table(sys.argv[2])
+    print("kernel | " + " | ".join(KEYS) + "     (parent -> this tree; one figure: unchanged)")
+    worse = []
+    for n in sorted(set(a) | set(b)):
+        if n not in b:
+            print("GONE %s" % n)
+            continue
+        x, y = a.get(n, b[n]), b[n]
+        cells = [y.get(k, "?") if x.get(k) == y.get(k) else "%s -> %s" % (x.get(k), y.get(k)) for k in KEYS]
+        tag = "" if n in a else "NEW "
+        if n in a and (int(y[KEYS[3]]) > int(x[KEYS[3]]) or int(y[KEYS[4]]) < int(x[KEYS[4]])):
+            worse.append(n)
+            tag = "WORSE "
+        print("%s%s | %s" % (tag, n, " | ".join(cells)))
+    print("existing kernels: %d, new kernels: %d, existing kernels with a changed figure: %d, with new scratch or lower occupancy: %d"
+          % (len(set(a) & set(b)), len(set(b) - set(a)), sum(1 for n in set(a) & set(b) if any(a[n].get(k) != b[n].get(k) for k in KEYS)), len(worse)))
+    return 1 if worse else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
