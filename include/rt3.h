@@ -31,8 +31,8 @@ extern "C" {
  * it loaded reports before it passes any struct (rt3_stats grew from 56 to 64 bytes between versions 1 and 2; rt3_get_stats writes
  * sizeof(rt3_stats) bytes of THIS version).  History: 1 = round 1; 2 = + mfma_instructions / exact_tests in rt3_stats, progressive
  * accumulation, rt3_gather_rows; 3 = + rt3_abi_version itself, one stream convention (below),
- * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh* and with
- * rt3_render_path_adaptive* (one new struct of its own): functions were only added, no existing struct changed. */
+ * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh*, with
+ * rt3_render_path_adaptive* (one new struct of its own) and with rt3_regroup*: functions were only added, no existing struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
 
@@ -204,6 +204,29 @@ int rt3_update_spheres(rt3_ctx* ctx, const float* center_radius, uint32_t n);
 int rt3_update_spheres_device(rt3_ctx* ctx, const void* d_center_radius, uint32_t n, void* stream);
 int rt3_update_mesh(rt3_ctx* ctx, const rt3_gface* faces, const float* vertices_xyzw, uint32_t n_vertices);
 int rt3_update_mesh_device(rt3_ctx* ctx, const void* d_faces, const void* d_vertices_xyzw, uint32_t n_vertices, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Regroup   (the group order of the candidate filter again, from the positions on the device)
+ * ------------------------------------------------------------------------------------------------- */
+/* Updates keep the group order of the last full upload, and a scene whose neighbours have scattered pays for it in candidates.
+ * rt3_regroup* reorders the primitives among the positions they already occupy — the median split of a full upload, as a stable sort
+ * per part, on the device — and runs the refit's tail.  After it every entry point returns bit for bit what it returned before (and so
+ * what it returns after a full upload of the same arrays); only the filter counters of rt3_stats and the time may change.  Counts,
+ * materials, the direct-sphere list, the filter centres, every buffer size, the set of primitives in the split region (the spheres that
+ * had a slot at rt3_set_spheres; the faces with a bounded hit region at commit), the pads and the unbounded faces' tail are kept.
+ * `what`: RT3_REGROUP_SPHERES | RT3_REGROUP_MESH, at least one.  rt3_regroup is synchronous; rt3_regroup_device is queued on `stream`
+ * (convention above), takes part in the event chain as an update does, and after its first call for a scene size allocates nothing and
+ * never waits for the device.  The accumulation of a progressive render is left alone.
+ * Errors: RT3_E_ARG for a NULL ctx, what == 0 or unknown bits; RT3_E_STATE without a committed scene of a named class, with merged
+ * entity buffers out of sync with the commit, and when the last rt3_set_spheres left a non-finite sphere out of the group order.  A
+ * class without rows (every sphere on the direct list) is a successful no-op. */
+#define RT3_REGROUP_SPHERES 1u
+#define RT3_REGROUP_MESH    2u
+int rt3_regroup(rt3_ctx* ctx, uint32_t what);
+int rt3_regroup_device(rt3_ctx* ctx, uint32_t what, void* stream);
+/* Tests only: downloads the group order of one class (what = exactly one RT3_REGROUP_* bit): the primitive index at every position,
+ * 0xFFFFFFFF for a pad.  n_positions is set whenever a scene of that class exists; RT3_E_ARG if capacity_words is smaller. */
+int rt3_debug_group_order(rt3_ctx* ctx, uint32_t what, uint32_t* out, uint64_t capacity_words, uint32_t* n_positions);
 
 /* ---------------------------------------------------------------------------------------------------
  * Render   (replaces Renderer::render, Renderer.hpp:50)

@@ -49,6 +49,7 @@ HISTORY = np.dtype([("colour", "<f4", 3), ("length", "<f4"), ("moments", "<f4", 
                     ("normal", "<f4", 3), ("_pad1", "<f4")])
 OCCLUDED_INVALID = 0xFFFFFFFF      # rt3_occluded's word for an invalid ray
 FLAG_GAMMA2, FLAG_BLACK_BACKGROUND, FLAG_REFERENCE_PRIMARY, FLAG_VARIANCE = 1, 2, 4, 8
+REGROUP_SPHERES, REGROUP_MESH = 1, 2      # rt3_regroup's `what`
 
 
 class rt3_camera(C.Structure):
@@ -148,6 +149,7 @@ EXPORTS = [
     "rt3_motion", "rt3_motion_device", "rt3_denoise_temporal_motion", "rt3_denoise_temporal_motion_device",
     "rt3_update_spheres", "rt3_update_spheres_device", "rt3_update_mesh", "rt3_update_mesh_device",
     "rt3_debug_primary_lists",
+    "rt3_regroup", "rt3_regroup_device", "rt3_debug_group_order",
     "rt3_render_path_adaptive", "rt3_render_path_adaptive_device",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
@@ -218,6 +220,7 @@ def lib():
         "rt3_denoise_temporal_motion_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "rt3_update_spheres": (i32, [vp, vp, u32]), "rt3_update_spheres_device": (i32, [vp, vp, u32, vp]),
         "rt3_update_mesh": (i32, [vp, vp, vp, u32]), "rt3_update_mesh_device": (i32, [vp, vp, vp, u32, vp]),
+        "rt3_regroup": (i32, [vp, u32]), "rt3_regroup_device": (i32, [vp, u32, vp]), "rt3_debug_group_order": (i32, [vp, u32, vp, u64, vp]),
         "rt3_render_path_adaptive": (i32, [vp, vp, vp, vp, vp, vp]), "rt3_render_path_adaptive_device": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
@@ -532,6 +535,7 @@ class HipRenderer(Renderer):
         self.n_faces = 0
         self.n_spheres = 0
         self._mesh_counts = (0, 0)
+        self._torch_device = None    # set by a device-form update: regroup() then queues on torch's current stream as well
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -614,6 +618,7 @@ class HipRenderer(Renderer):
         if face_materials is not None:
             face_materials = np.ascontiguousarray(face_materials)
             assert face_materials.dtype == MATERIAL and len(face_materials) == len(faces)
+        self._torch_device = None
         self._check(lib().rt3_set_mesh(self._ctx, _p(faces), len(faces), _p(verts), len(verts), _p(face_materials)))
         self.n_faces = len(faces)
         self._mesh_counts = (len(faces), len(verts))
@@ -622,6 +627,7 @@ class HipRenderer(Renderer):
         cr = np.ascontiguousarray(center_radius, np.float32).reshape(-1, 4)
         materials = np.ascontiguousarray(materials)
         assert materials.dtype == MATERIAL and len(materials) == len(cr)
+        self._torch_device = None
         self._check(lib().rt3_set_spheres(self._ctx, _p(cr), _p(materials), len(cr)))
         self.n_spheres = len(cr)
 
@@ -645,9 +651,11 @@ class HipRenderer(Renderer):
             if center_radius.dtype != torch.float32:
                 raise Fatal("device center_radius must be float32")
             stream = torch.cuda.current_stream(center_radius.device).cuda_stream
+            self._torch_device = center_radius.device
             self._check(lib().rt3_update_spheres_device(self._ctx, C.c_void_p(center_radius.data_ptr()), n, C.c_void_p(stream)))
             return
         cr = np.ascontiguousarray(center_radius, np.float32).reshape(-1, 4)
+        self._torch_device = None
         self._check(lib().rt3_update_spheres(self._ctx, _p(cr), len(cr)))
 
     def update_mesh(self, vertices, faces=None):
@@ -666,15 +674,43 @@ class HipRenderer(Renderer):
                     raise Fatal("device faces must hold the mesh's %d faces, on the vertices' device" % self.n_faces)
                 fptr = C.c_void_p(faces.data_ptr())
             stream = torch.cuda.current_stream(vertices.device).cuda_stream
+            self._torch_device = vertices.device
             self._check(lib().rt3_update_mesh_device(self._ctx, fptr, C.c_void_p(vertices.data_ptr()), n, C.c_void_p(stream)))
             return
         v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
+        self._torch_device = None
         f = None
         if faces is not None:
             f = np.ascontiguousarray(faces)
             if f.dtype != GFACE or len(f) != self.n_faces:
                 raise Fatal("update_mesh: faces must be a GFACE array of the mesh's %d faces" % self.n_faces)
         self._check(lib().rt3_update_mesh(self._ctx, _p(f), _p(v), len(v)))
+
+    def regroup(self, spheres=True, mesh=True):
+        """The group order of the candidate filter again, from the positions on the device (rt3_regroup): what repeated
+        updates let go stale, without a full upload.  Results do not change, only the filter's work.  Regroups the named classes that
+        have a committed scene.  Synchronous, unless the last upload or update of the scene was an update from torch tensors: then
+        it is queued on torch.cuda.current_stream() like that update (rt3_regroup_device)."""
+        what = (REGROUP_SPHERES if spheres and self.n_spheres else 0) | (REGROUP_MESH if mesh and self.n_faces else 0)
+        if not what:
+            return
+        if self._torch_device is not None:
+            import torch
+            stream = torch.cuda.current_stream(self._torch_device).cuda_stream
+            self._check(lib().rt3_regroup_device(self._ctx, what, C.c_void_p(stream)))
+            return
+        self._check(lib().rt3_regroup(self._ctx, what))
+
+    def group_order(self, what):
+        """Tests: the group order of one class (REGROUP_SPHERES or REGROUP_MESH) as rt3_debug_group_order downloads it: the primitive
+        index at every position, 0xFFFFFFFF for a pad."""
+        n = C.c_uint32(0)
+        rc = lib().rt3_debug_group_order(self._ctx, what, None, 0, C.byref(n))
+        if rc != 0 and n.value == 0:
+            self._check(rc)
+        out = np.zeros(n.value, np.uint32)
+        self._check(lib().rt3_debug_group_order(self._ctx, what, _p(out), len(out), C.byref(n)))
+        return out
 
     def synchronize(self):
         """rt3_synchronize: waits for the context's own stream; reports a face index out of range of a device-form update_mesh."""

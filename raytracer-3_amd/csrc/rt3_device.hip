@@ -18,11 +18,14 @@
 //   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve
 //   rt3_denoise.hpp         the launchers of the AOV-guided a-trous denoiser, its temporal form and the motion plane (kernels: rt3_denoise.hip)
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
+//   rt3_regroup.hpp         the group order of the multi-level filter again on the device (rt3_regroup*): the median split as stable sorts,
+//                           in LDS for parts of up to 4096 primitives
 //   below                   the device context and the extern "C" entry points
 //
 // Compiled with -ffp-contract=off: a*b+c is two roundings unless written __builtin_fmaf.  Division and sqrt are
 // the correctly rounded forms (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt), f32 denormals are kept.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -47,6 +50,7 @@
 #include "rt3_aov.hpp"
 #include "rt3_denoise.hpp"
 #include "rt3_scene_kernels.hpp"
+#include "rt3_regroup.hpp"
 #include "rt3_primary_lists.hpp"
 
 // ======================================================================================================
@@ -82,6 +86,17 @@ struct FilterRows {
     uint32_t n_groups = 0, n_leaves = 0, n_super = 0;              // rows the matrix filter scans, leaf groups, super-rows
 };
 
+// What rt3_regroup* keeps per primitive class: the parts of every level above the LDS limit and of the level k_split_lds
+// starts from, as begins[0 .. n_parts] one after the other — they depend on the count alone — built with the first regroup of a scene size.
+struct RegroupPlan {
+    struct Level { uint32_t offset, n_parts; };
+    bool ready = false;
+    uint32_t n_reg = 0, n_region = 0, max_parts = 0;                // primitives in the split region, its positions (pads included), parts of the widest global level
+    size_t temp_bytes = 0;                                          // the radix sorts' temporary storage
+    std::vector<Level> levels;
+    DevBuf<uint32_t> table;
+};
+
 struct rt3_ctx {
     int device = 0;
     int num_cu = 0;
@@ -103,6 +118,11 @@ struct rt3_ctx {
     // what rt3_update_spheres* needs from the last rt3_set_spheres: every sphere's position in sph.grp (0xFFFFFFFF: a direct sphere), and whether
     // a sphere was left out of the group order for a non-finite record (an update could make it finite again, and it has no slot)
     DevBuf<uint32_t> d_sph_slot; bool sph_left_out = false;
+    // rt3_regroup*: the faces face_group_order put in the bounded part at commit; the plans; scratch (centres, ping-pong ids and keys, the
+    // parts' boxes, sort temporaries), grown by the first regroup of a scene size and kept
+    uint32_t tri_bounded = 0;
+    RegroupPlan rg_sph, rg_tri;
+    DevBuf<float4> d_rg_cen; DevBuf<uint32_t> d_rg_ids[2], d_rg_box; DevBuf<uint64_t> d_rg_keys[2]; DevBuf<uint8_t> d_rg_temp;
     bool update_error_pending = false;                              // a device-form rt3_update_mesh_device with faces: d_error is read by the next rt3_synchronize
 
     // rows of the multi-level filter: faces and spheres, each in the order of a spatial median split
@@ -959,6 +979,8 @@ int rt3_mesh_commit(rt3_ctx* ctx, const rt3_material* face_materials) {
     std::vector<float4> bounds(n);
     RT3_HIP(hipMemcpy(bounds.data(), ctx->d_tri_bound, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
     const std::vector<uint32_t> order = face_group_order(bounds.data(), n, kGroupTri, kSuper);
+    ctx->tri_bounded = 0;                                           // the region rt3_regroup* reorders: face_group_order's own condition
+    for (const float4& b : bounds) ctx->tri_bounded += std::isfinite(b.x) && std::isfinite(b.y) && std::isfinite(b.z) && b.w >= 0.0f && b.w < 3e38f;
     const float no_centre[3] = { 0.0f, 0.0f, 0.0f };
     if ((rc = build_rows(ctx, ctx->tri, bounds.data(), order, kGroupTri, ctx->d_box, no_centre))) return rc;
     if ((rc = ctx->d_tri_rec.alloc(ctx, order.size() * 4))) return rc;
@@ -1145,6 +1167,172 @@ int rt3_update_mesh(rt3_ctx* ctx, const rt3_gface* faces, const float* vertices,
         ctx->n_faces = 0; ctx->mesh_in_sync = false;
         return fail(ctx, RT3_E_ARG, "a face references a vertex out of range");
     }
+    return 0;
+}
+
+// ---- Regroup: the group order again from the records on the device, then the refit's tail
+static uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
+static int regroup_plan(rt3_ctx* ctx, RegroupPlan& P, uint32_t n_reg, uint32_t n_region, uint32_t n_prims) {
+    int rc;
+    if (!P.ready || P.n_reg != n_reg || P.n_region != n_region) {
+        P = RegroupPlan();
+        std::vector<uint32_t> parts{ 0u, n_reg }, table;
+        for (;;) {
+            uint32_t largest = 0;
+            for (size_t k = 0; k + 1 < parts.size(); k++) largest = std::max(largest, parts[k + 1] - parts[k]);
+            P.levels.push_back({ (uint32_t)table.size(), (uint32_t)parts.size() - 1u });
+            table.insert(table.end(), parts.begin(), parts.end());
+            if (largest <= kSplitCap) break;
+            P.max_parts = std::max(P.max_parts, (uint32_t)parts.size() - 1u);
+            std::vector<uint32_t> next;
+            for (size_t k = 0; k + 1 < parts.size(); k++) {
+                const uint32_t count = parts[k + 1] - parts[k];
+                next.push_back(parts[k]);
+                if (count > kLevFan) next.push_back(parts[k] + split_half(count, kLevFan, kSuper));
+            }
+            next.push_back(n_reg);
+            parts.swap(next);
+        }
+        // what k_split_lds relies on: the parts of the last level tile [0, n_reg) and none exceeds its LDS
+        const uint32_t* last = table.data() + P.levels.back().offset;
+        for (uint32_t k = 0; k < P.levels.back().n_parts; k++)
+            if (last[k + 1] <= last[k] || last[k + 1] - last[k] > kSplitCap) return fail(ctx, RT3_E_DEVICE, "rt3_regroup: the part table does not fit k_split_lds");
+        if (last[0] != 0 || last[P.levels.back().n_parts] != n_reg) return fail(ctx, RT3_E_DEVICE, "rt3_regroup: the part table does not cover the region");
+        if ((rc = P.table.upload(ctx, table))) return rc;
+        size_t a = 0, b = 0;
+        RT3_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr, n_region, 0, 32, ctx->stream));
+        RT3_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                   n_reg, 0, 64, ctx->stream));
+        P.temp_bytes = std::max<size_t>(std::max(a, b), 16);
+        RT3_HIP(hipFuncSetAttribute((const void*)k_split_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSplitLds));
+        P.n_reg = n_reg; P.n_region = n_region; P.ready = true;
+    }
+    // (grow only: nothing happens here once both classes have been regrouped at their sizes)
+    if ((rc = ctx->d_rg_cen.ensure(ctx, n_prims)) || (rc = ctx->d_rg_ids[0].ensure(ctx, n_region)) || (rc = ctx->d_rg_ids[1].ensure(ctx, n_region)) ||
+        (rc = ctx->d_rg_keys[0].ensure(ctx, n_reg)) || (rc = ctx->d_rg_keys[1].ensure(ctx, n_reg)) ||
+        (rc = ctx->d_rg_box.ensure(ctx, (size_t)std::max(P.max_parts, 1u) * 6)) || (rc = ctx->d_rg_temp.ensure(ctx, P.temp_bytes)))
+        return rc;
+    return 0;
+}
+// The split of one class: R.perm[0 .. n_reg) becomes the specified order of the primitives it holds; pads and whatever follows stay.
+static int regroup_order(rt3_ctx* ctx, const RegroupPlan& P, FilterRows& R, hipStream_t stream) {
+    const dim3 blk(kBlock);
+    auto grid = [](uint32_t threads) { return dim3((threads + kBlock - 1) / kBlock); };
+    size_t temp = P.temp_bytes;
+    // the region's primitive ids in ascending order (pads are 0xFFFFFFFF: they sort behind the n_reg ids)
+    RT3_HIP(hipcub::DeviceRadixSort::SortKeys(ctx->d_rg_temp.get(), temp, (const uint32_t*)R.perm.get(), ctx->d_rg_ids[0].get(), P.n_region, 0, 32, stream));
+    int cur = 0;
+    for (size_t l = 0; l + 1 < P.levels.size(); l++) {
+        const uint32_t* begins = P.table.get() + P.levels[l].offset;
+        const uint32_t n_parts = P.levels[l].n_parts;
+        hipLaunchKernelGGL(k_part_box_clear, grid(n_parts * 6), blk, 0, stream, n_parts, ctx->d_rg_box.get());
+        hipLaunchKernelGGL(k_part_box, grid((P.n_reg + kBoxPerThread - 1) / kBoxPerThread), blk, 0, stream, begins, n_parts, (const uint32_t*)ctx->d_rg_ids[cur].get(),
+                           (const float4*)ctx->d_rg_cen.get(), P.n_reg, ctx->d_rg_box.get());
+        hipLaunchKernelGGL(k_part_keys, grid(P.n_reg), blk, 0, stream, begins, n_parts, (const uint32_t*)ctx->d_rg_ids[cur].get(),
+                           (const float4*)ctx->d_rg_cen.get(), P.n_reg, (const uint32_t*)ctx->d_rg_box.get(), kLevFan, ctx->d_rg_keys[0].get());
+        RT3_HIP(hipGetLastError());
+        int part_bits = 0;                                          // only the bits in use are sorted
+        while ((1u << part_bits) < n_parts) part_bits++;
+        temp = P.temp_bytes;
+        RT3_HIP(hipcub::DeviceRadixSort::SortPairs(ctx->d_rg_temp.get(), temp, (const uint64_t*)ctx->d_rg_keys[0].get(), ctx->d_rg_keys[1].get(),
+                                                   (const uint32_t*)ctx->d_rg_ids[cur].get(), ctx->d_rg_ids[cur ^ 1].get(), P.n_reg, 0, 32 + part_bits, stream));
+        cur ^= 1;
+    }
+    const RegroupPlan::Level& last = P.levels.back();
+    hipLaunchKernelGGL(k_split_lds, dim3(last.n_parts), dim3(kSplitThreads), kSplitLds, stream, (const uint32_t*)(P.table.get() + last.offset),
+                       (const uint32_t*)ctx->d_rg_ids[cur].get(), (const float4*)ctx->d_rg_cen.get(), kLevFan, kSuper, R.perm.get());
+    RT3_HIP(hipGetLastError());
+    return 0;
+}
+static int regroup_spheres(rt3_ctx* ctx, hipStream_t stream) {
+    const uint32_t n = ctx->n_sph, n_pos = (uint32_t)ctx->sph.perm.size(), n_reg = n - ctx->n_direct;
+    if (n_pos == 0 || n_reg == 0) return 0;                         // every sphere is on the direct list: no rows
+    int rc;
+    if ((rc = regroup_plan(ctx, ctx->rg_sph, n_reg, n_pos, n))) return rc;
+    const dim3 blk(kBlock);
+    auto grid = [](uint32_t threads) { return dim3((threads + kBlock - 1) / kBlock); };
+    ctx->n_sph = 0;                                                 // (no spheres until everything below has been issued)
+    hipLaunchKernelGGL(k_regroup_centres_sph, grid(n), blk, 0, stream, (const float4*)ctx->d_sph_cr.get(), n, ctx->sph_centre[0], ctx->sph_centre[1],
+                       ctx->sph_centre[2], ctx->d_rg_cen.get());
+    RT3_HIP(hipGetLastError());
+    if ((rc = regroup_order(ctx, ctx->rg_sph, ctx->sph, stream))) return rc;
+    hipLaunchKernelGGL(k_inverse_slots, grid(n_pos), blk, 0, stream, (const uint32_t*)ctx->sph.perm.get(), n_pos, ctx->d_sph_slot.get());
+    hipLaunchKernelGGL(k_gather_members, grid(n_pos), blk, 0, stream, (const float4*)ctx->d_sph.get(), (const uint32_t*)ctx->sph.perm.get(), n_pos,
+                       ctx->sph.grp.get());
+    RT3_HIP(hipGetLastError());
+    return refit_rows(ctx, ctx->sph, nullptr, ctx->sph_centre, stream);
+}
+static int regroup_mesh(rt3_ctx* ctx, hipStream_t stream) {
+    const uint32_t n = ctx->n_faces, n_pos = (uint32_t)ctx->tri.perm.size(), n_reg = ctx->tri_bounded;
+    if (n_pos == 0 || n_reg == 0) return 0;                         // no face with a bounded hit region: nothing to order
+    int rc;
+    if ((rc = regroup_plan(ctx, ctx->rg_tri, n_reg, round_up(n_reg, kGroupTri * kSuper), n))) return rc;
+    const dim3 blk(kBlock);
+    auto grid = [](uint32_t threads) { return dim3((threads + kBlock - 1) / kBlock); };
+    ctx->n_faces = 0;                                               // (no mesh until everything below has been issued)
+    hipLaunchKernelGGL(k_regroup_centres_tri, grid(n), blk, 0, stream, (const float4*)ctx->d_tri_bound.get(), n, (const uint32_t*)ctx->d_box.get(),
+                       ctx->d_rg_cen.get());
+    RT3_HIP(hipGetLastError());
+    if ((rc = regroup_order(ctx, ctx->rg_tri, ctx->tri, stream))) return rc;
+    hipLaunchKernelGGL(k_gather_members, grid(n_pos), blk, 0, stream, (const float4*)ctx->d_tri_bound.get(), (const uint32_t*)ctx->tri.perm.get(), n_pos,
+                       ctx->tri.grp.get());
+    hipLaunchKernelGGL(k_gather_face_records, grid(n_pos * 4u), blk, 0, stream, (const float4*)ctx->d_tri.get(), (const uint32_t*)ctx->tri.perm.get(),
+                       n_pos, ctx->d_tri_rec.get());
+    RT3_HIP(hipGetLastError());
+    const float no_centre[3] = { 0.0f, 0.0f, 0.0f };
+    return refit_rows(ctx, ctx->tri, ctx->d_box, no_centre, stream);
+}
+static int regroup_checks(rt3_ctx* ctx, uint32_t what) {
+    if (what == 0 || (what & ~(RT3_REGROUP_SPHERES | RT3_REGROUP_MESH))) return fail(ctx, RT3_E_ARG, "what must name RT3_REGROUP_SPHERES and / or RT3_REGROUP_MESH");
+    if (what & RT3_REGROUP_SPHERES) {
+        if (ctx->n_sph == 0) return fail(ctx, RT3_E_STATE, "no spheres to regroup: call rt3_set_spheres first");
+        if (ctx->sph_left_out)
+            return fail(ctx, RT3_E_STATE, "the last rt3_set_spheres left a non-finite sphere out of the group order: it has no position a regroup could give it");
+    }
+    if (what & RT3_REGROUP_MESH) {
+        if (ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "no committed mesh to regroup: call rt3_set_mesh / rt3_mesh_commit first");
+        if (!ctx->mesh_in_sync)
+            return fail(ctx, RT3_E_STATE, "the merged entity buffers were changed after the last rt3_mesh_commit (rt3_mesh_begin / rt3_mesh_put without a commit)");
+    }
+    return 0;
+}
+
+int rt3_regroup_device(rt3_ctx* ctx, uint32_t what, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = regroup_checks(ctx, what);
+    if (rc) return rc;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    // a class's count is cleared before its first launch (regroup_spheres / regroup_mesh) and published only once the event behind the last
+    // launch has been recorded: a failure anywhere leaves no scene of the classes that were touched, never new counts over old buffers
+    const uint32_t n_sph = ctx->n_sph, n_faces = ctx->n_faces;
+    if ((what & RT3_REGROUP_SPHERES) && (rc = regroup_spheres(ctx, stream))) return rc;
+    if ((what & RT3_REGROUP_MESH) && (rc = regroup_mesh(ctx, stream))) return rc;
+    if ((rc = leave(ctx, stream))) return rc;
+    ctx->n_sph = n_sph; ctx->n_faces = n_faces;
+    return 0;
+}
+
+int rt3_regroup(rt3_ctx* ctx, uint32_t what) {
+    if (!ctx) return RT3_E_ARG;
+    const int rc = rt3_regroup_device(ctx, what, ctx->stream);
+    if (rc) return rc;
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int rt3_debug_group_order(rt3_ctx* ctx, uint32_t what, uint32_t* out, uint64_t capacity_words, uint32_t* n_positions) {
+    if (!ctx) return RT3_E_ARG;
+    if (what != RT3_REGROUP_SPHERES && what != RT3_REGROUP_MESH) return fail(ctx, RT3_E_ARG, "what must be exactly one of RT3_REGROUP_SPHERES, RT3_REGROUP_MESH");
+    if (!n_positions) return fail(ctx, RT3_E_ARG, "n_positions is NULL");
+    const bool sph = what == RT3_REGROUP_SPHERES;
+    if ((sph ? ctx->n_sph : ctx->n_faces) == 0) return fail(ctx, RT3_E_STATE, "no committed scene of that class");
+    const FilterRows& R = sph ? ctx->sph : ctx->tri;
+    *n_positions = (uint32_t)R.perm.size();
+    if (capacity_words < R.perm.size() || (!out && R.perm.size())) return fail(ctx, RT3_E_ARG, "capacity_words is too small for the group order");
+    RT3_HIP(hipSetDevice(ctx->device));
+    if (ctx->ev_acc_recorded) RT3_HIP(hipEventSynchronize(ctx->ev_acc));    // (a regroup may have run on a caller's stream)
+    if (R.perm.size()) RT3_HIP(hipMemcpy(out, R.perm.get(), R.perm.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

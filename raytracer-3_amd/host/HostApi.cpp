@@ -251,6 +251,14 @@ void HipRenderer::update_spheres(const std::vector<float>& center_radius) {
         if (rt3_update_spheres(c, center_radius.data(), (uint32_t)(center_radius.size() / 4)) != 0) throw Fatal(rt3_last_error(c));
 }
 
+// The group order of the candidate filter again, from the positions on the device (rt3_regroup): same results, less filter work.
+void HipRenderer::regroup(bool spheres, bool mesh) {
+    const uint32_t what = (spheres && n_spheres ? RT3_REGROUP_SPHERES : 0u) | (mesh && n_faces ? RT3_REGROUP_MESH : 0u);
+    if (what == 0) return;
+    for (rt3_ctx* c : ctx)
+        if (rt3_regroup(c, what) != 0) throw Fatal(rt3_last_error(c));
+}
+
 void HipRenderer::update_mesh(const std::vector<float>& vertices, const std::vector<rt3_gface>& faces) {
     if (!faces.empty() && faces.size() != n_faces) throw Fatal("update_mesh: faces must hold the mesh's face count, or be empty");
     for (rt3_ctx* c : ctx)

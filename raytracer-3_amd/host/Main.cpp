@@ -39,6 +39,8 @@ struct Options {
     float slide[3] = { 0.0f, 0.0f, 0.0f };                         // sphere scenes: what every sphere of odd index moves by per frame
     bool have_slide = false;
     bool refit = false;                                            // --slide: frames after the first update the spheres in place (rt3_update_spheres)
+    uint32_t regroup = 0;                                          // --refit: every regroup-th refit frame is followed by rt3_regroup (0: never)
+    bool have_regroup = false;
     bool adaptive = false;                                         // Mode X: --spp is a budget (rt3_render_path_adaptive)
     float adaptive_threshold = 0.05f;
     uint32_t adaptive_min = 0, adaptive_step = 16;                 // (min 0: not given = min(16, spp))
@@ -67,6 +69,7 @@ void print_usage(const char* exe) {
               << "\t   --slide\tthree / weekend / stress100k with --frames: translate every sphere of odd index by k * (DX,DY,DZ) in frame k;\n"
               << "\t\t\twith --denoise PREFIX the temporal filter follows them (the motion plane).\n"
               << "\t   --refit\tWith --slide: frames after the first move the spheres by an update on the device instead of a full upload (same frames).\n"
+              << "\t   --regroup\tWith --refit: K: after every K-th refit frame the group order is rebuilt on the device (rt3_regroup; same frames).\n"
               << "\t   --adaptive\tMode X: T[,MIN[,STEP]]: --spp is a budget; MIN samples for every pixel (default: 16), then STEP at a time (default: 16)\n"
               << "\t\t\tfor the pixels whose neighbourhood has not reached a relative standard error of T. Combines with --hdr, --aov, --denoise.\n"
               << "\t   --counts\tWith --adaptive: also write the samples every pixel received to this path as a 1-channel PFM.\n"
@@ -110,7 +113,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         const bool known = key == "-f" || key == "--format" || key == "-W" || key == "--width" || key == "-H" || key == "--height" ||
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
-                           key == "--slide" || key == "--adaptive" || key == "--counts";
+                           key == "--slide" || key == "--adaptive" || key == "--counts" || key == "--regroup";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -174,6 +177,11 @@ int parse_cli(Options& opt, int argc, const char** argv) {
             opt.adaptive = true; opt.adaptive_threshold = (float)t;
         }
         else if (key == "--counts") opt.counts_path = value;
+        else if (key == "--regroup") {
+            if (!parse_u32(value, "regroup", "Regroup", &opt.regroup)) return -1;
+            if (opt.regroup == 0) { std::cerr << "--regroup must be at least 1." << std::endl; return -1; }
+            opt.have_regroup = true;
+        }
         else opt.scene = value;
     }
     if (opt.output_path.empty() && !opt.dump_scene) { std::cerr << "No output path given." << std::endl; return -1; }
@@ -214,6 +222,10 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     }
     if (opt.refit && !opt.have_slide) {
         std::cerr << "--refit needs --slide: it is how the moved spheres reach the device." << std::endl;
+        return -1;
+    }
+    if (opt.have_regroup && !opt.refit) {
+        std::cerr << "--regroup needs --refit: a full upload sorts the groups itself." << std::endl;
         return -1;
     }
     return 1;
@@ -329,7 +341,10 @@ int main(int argc, const char** argv) {
                 prev_cr = shown_cr;
                 for (size_t i = 1; i < scene_mats.size(); i += 2)
                     for (int c = 0; c < 3; c++) shown_cr[4 * i + c] = scene_cr[4 * i + c] + (float)k * opt.slide[c];
-                if (opt.refit) renderer.update_spheres(shown_cr);
+                if (opt.refit) {
+                    renderer.update_spheres(shown_cr);
+                    if (opt.regroup != 0 && k % opt.regroup == 0) renderer.regroup(true, false);
+                }
                 else renderer.set_spheres(shown_cr, scene_mats);
             }
             if (la.on) {                                             // frame k: the look-from point turned by k * orbit about the vertical axis

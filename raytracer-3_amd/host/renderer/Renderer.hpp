@@ -52,6 +52,8 @@ public:
     // the indices, normals and colours, else the mesh's face count of records (new normals)
     void update_spheres(const std::vector<float>& center_radius);
     void update_mesh(const std::vector<float>& vertices_xyzw, const std::vector<rt3_gface>& faces = {});
+    // the classes that have a scene get the group order of a full upload back after updates (rt3_regroup): nothing a render returns changes
+    void regroup(bool spheres = true, bool mesh = true);
     rt3_stats stats() const;                                                     // of device 0's last render
     // Mode X only, full frames (row 0 on top) assembled from the device shards: the first-hit AOVs of the current options (rt3_render_aov),
     // and the linear (r, g, b, 0) frame of the last render (rt3_accum_resolve)
