@@ -585,6 +585,10 @@ int      rt3_debug_arith(rt3_ctx* ctx, const float* a, const float* b, uint32_t 
  * sphere 32 k + b may be met by a primary ray of the group.  RT3_E_ARG (with n_groups / n_blocks set) if capacity_words is too small. */
 int      rt3_debug_primary_lists(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t* out_masks, uint64_t capacity_words,
                                  uint32_t* n_groups, uint32_t* n_blocks);
+/* Debug probe used by the tests only (no device needed): the counter-hash table k_trace_mfma32's render form builds in LDS, computed on the host by the
+ * function the kernel fills it with.  Writes min(rows, capacity_rows) rows of 4 words — row d, word k = hash(1 + 8 (d + 1) + k), the inner hash of
+ * the random numbers a path of depth d draws when it scatters — and returns rows, the depth below which shade_lane reads the table. */
+uint32_t rt3_debug_ctr_table(uint32_t* out, uint32_t capacity_rows);
 
 #ifdef __cplusplus
 }

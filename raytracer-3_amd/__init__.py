@@ -148,7 +148,7 @@ EXPORTS = [
     "rt3_frame_pfm_bytes", "rt3_frame_to_pfm", "rt3_denoise", "rt3_denoise_device", "rt3_denoise_temporal", "rt3_denoise_temporal_device",
     "rt3_motion", "rt3_motion_device", "rt3_denoise_temporal_motion", "rt3_denoise_temporal_motion_device",
     "rt3_update_spheres", "rt3_update_spheres_device", "rt3_update_mesh", "rt3_update_mesh_device",
-    "rt3_debug_primary_lists",
+    "rt3_debug_primary_lists", "rt3_debug_ctr_table",
     "rt3_regroup", "rt3_regroup_device", "rt3_debug_group_order",
     "rt3_render_path_adaptive", "rt3_render_path_adaptive_device",
 ]
@@ -194,7 +194,7 @@ def lib():
         "rt3_hash_u32": (u32, [u32]), "rt3_random_float": (f32, [u32]),
         "rt3_debug_arith": (i32, [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "rt3_debug_force_plain_mode_r": (i32, [vp, i32]),
-        "rt3_debug_primary_lists": (i32, [vp, vp, vp, vp, u64, vp, vp]),
+        "rt3_debug_primary_lists": (i32, [vp, vp, vp, vp, u64, vp, vp]), "rt3_debug_ctr_table": (u32, [vp, u32]),
         "rt3_mesh_begin": (i32, [vp, u32, u32]), "rt3_mesh_put": (i32, [vp, vp, u32, vp, u32, u32, u32]),
         "rt3_mesh_sphere": (i32, [vp, vp, f32, u32, u32, vp, u32, u32]), "rt3_mesh_commit": (i32, [vp, vp]),
         "rt3_mesh_download": (i32, [vp, vp, vp]),
@@ -1061,6 +1061,14 @@ class HipRenderer(Renderer):
 def initialize_renderer(device=0):
     """RayTracer::initialize_renderer (Renderer.hpp:63): the link-time factory; here it always builds the HIP backend."""
     return HipRenderer(device)
+
+
+def debug_ctr_table():
+    """The counter-hash table of k_trace_mfma32's render form as the library computes it on the host: (rows, 4) uint32 (tests only; no device)."""
+    rows = lib().rt3_debug_ctr_table(None, 0)
+    out = np.zeros((rows, 4), np.uint32)
+    lib().rt3_debug_ctr_table(_p(out), rows)
+    return out
 
 
 def rows_owned(params):

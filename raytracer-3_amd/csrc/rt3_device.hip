@@ -665,6 +665,7 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
         // k_trace_mfma32 (K = 32 form, pair list); RT3_MFMA_K64=1: k_trace_mfma, round 1's K = 64 form on v_mfma_f32_32x32x16_bf16 (A/B reference)
         T.lds = single_k64 ? (size_t)T.mfma_blocks * (4096 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes
                            : (size_t)T.mfma_blocks * (2048 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes + (size_t)kMB * 8 + (size_t)(kMB / 64) * kPairCap * 4;
+        if (!single_k64 && !query && RT3_CTR_TABLE) T.lds += kCtrTableBytes;       // the render forms' counter-hash table (shade_lane)
         T.block = kMB;
         T.single = single_k64 ? (list ? k_trace_mfma<true> : k_trace_mfma<>) : query ? k_trace_mfma32<true> : list ? k_trace_mfma32<false, true> : k_trace_mfma32<>;
         T.frag_a = (const u32x4*)(single_k64 ? ctx->d_sph_frag.get() : ctx->d_sph_frag32.get());
@@ -786,7 +787,7 @@ int leave(rt3_ctx* ctx, hipStream_t stream) {
 
 // The calls rt3_get_stats reports on (Mode-X renders, queries, AOVs) issue their launches between these two; each clears ctx->rendered before
 // anything that can fail, and end_timed sets it once the last launch has been issued.  plan: nullptr when nothing was traced (no owned pixels).
-constexpr size_t kCastSlots = 32;                                   // d_casts: [0..15] as the kernels' comments say, [16] casts through the filter, [17] restock phase
+constexpr size_t kCastSlots = 32;                                   // d_casts: [0..15] as the kernels' comments say, [16] casts through the filter, [17] restock phase, [18..22] its parts
 int begin_timed(rt3_ctx* ctx, hipStream_t stream) {
     ctx->ev_used = 0;
     RT3_HIP(hipEventRecord(ctx->ev_begin, stream));
@@ -2280,6 +2281,10 @@ int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {
                             "push + exact tests %.1f %%, decode + shade %.1f %%, restock (primary pass) %.1f %%\n",
                     100.0 * counters[11] / all, 100.0 * counters[12] / all, 100.0 * counters[13] / all, 100.0 * counters[14] / all, 100.0 * counters[15] / all,
                     100.0 * counters[17] / all);
+            if (counters[17] != 0)                                   // k_trace_mfma32's render form: the parts of a restock
+                fprintf(stderr, "[rt3 profile] restock, share of its wave time: ray generation %.1f %%, list fetch %.1f %%, direct + listed tests %.1f %%, "
+                                "shade %.1f %%, compaction %.1f %%\n", 100.0 * counters[18] / counters[17], 100.0 * counters[19] / counters[17],
+                        100.0 * counters[20] / counters[17], 100.0 * counters[21] / counters[17], 100.0 * counters[22] / counters[17]);
         }
 #endif
 #ifdef RT3_PROFILE
@@ -2339,6 +2344,12 @@ int rt3_debug_arith(rt3_ctx* ctx, const float* a, const float* b, uint32_t n, fl
     RT3_HIP(hipMemcpy(sk3, dsk, N * 12, hipMemcpyDeviceToHost));
     RT3_HIP(hipMemcpy(pk, dpk, N * 4, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// Debug probe (tests only, host code): the counter-hash table as k_trace_mfma32's prologue fills it, see tests/test_restock_uniform.py.
+uint32_t rt3_debug_ctr_table(uint32_t* out, uint32_t capacity_rows) {
+    if (out) for (uint32_t k = 0; k < std::min(capacity_rows, kCtrDepthCap) * 4u; k++) out[k] = ctr_table_word(k);
+    return kCtrDepthCap;
 }
 
 // Debug probe (tests only): the strip lists k_trace_mfma32's render form would use for this camera and these params, see tests/test_gpu_primary_lists.py.

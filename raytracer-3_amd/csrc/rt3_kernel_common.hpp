@@ -45,13 +45,18 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, FastDiv f) {
 }
 
 // random_v1.glsl:22-31, :37-52
-__device__ __forceinline__ uint32_t hash_u32(uint32_t x) {
+__host__ __device__ __forceinline__ uint32_t hash_u32(uint32_t x) {
     x += x << 10; x ^= x >> 6; x += x << 3; x ^= x >> 11; x += x << 15;
     return x;
 }
 __device__ __forceinline__ uint32_t hash2(uint32_t a, uint32_t b) { return hash_u32(a ^ hash_u32(b)); }
 __device__ __forceinline__ float u01(uint32_t m) { return __uint_as_float((m & 0x007FFFFFu) | 0x3F800000u) - 1.0f; }
 __device__ __forceinline__ float rnd(uint32_t base, uint32_t ctr) { return u01(hash2(base, ctr)); }
+// Counter-hash table of k_trace_mfma32's render form (built in its prologue, read by shade_lane): row d holds hash_u32(1 + 8 (d + 1) + k), k = 0..3 —
+// the inner hashes of the rnd(base, ctr + k) a path of depth d draws when it scatters.  Paths at or beyond the cap compute them.
+constexpr uint32_t kCtrDepthCap = 64;
+constexpr uint32_t kCtrTableBytes = kCtrDepthCap * 16;
+__host__ __device__ __forceinline__ uint32_t ctr_table_word(uint32_t k) { return hash_u32(1u + 8u * ((k >> 2) + 1u) + (k & 3u)); }   // word k of the table: row k / 4, column k % 4
 
 // sky gradient, SequentialRenderer.cpp:105-107 (float form of raytracer_v3.glsl:139-141; same bits)
 __device__ __forceinline__ void sky(float dx, float dy, float dz, float& r, float& g, float& b) {
@@ -231,15 +236,11 @@ __device__ __forceinline__ uint32_t frame_row(const TraceArgs& A, uint32_t local
 // REF (RT3_FLAG_REFERENCE_PRIMARY): the direction stays unnormalised, as SequentialRenderer.cpp:293 leaves it.
 // LIST: the list form of a work item (TraceArgs::active).  A compile-time flag, not a test of the pointer: the dense kernels' code stays what it was
 // (a wave-uniform test cost two of them scratch, profiles/adaptive_kernel_resources.log).
-template <bool REF = false, bool LIST = false>
-__device__ __forceinline__ void start_path(const TraceArgs& A, uint32_t item, Path& P) {
-    const uint32_t sb = fdiv(item, A.div_npix);
-    uint32_t pix = item - sb * A.npix;
-    if constexpr (LIST) pix = A.active[pix];
-    const uint32_t s = A.s0 + sb;
-    const uint32_t lrow = fdiv(pix, A.div_width), x = pix - lrow * A.width;
-    const uint32_t y = frame_row(A, lrow);
-    const uint32_t base = hash2(y * A.width + x, hash2(s, A.seed));
+// start_path_at: the part behind the index arithmetic — item `item` is sample s of the pixel (x, y) of the frame.  HS: hs is hash2(s, A.seed), worked
+// out by the caller (refill_from_traced_stock, once per wave where the 64 items of a restock share their sample).
+template <bool REF = false, bool HS = false>
+__device__ __forceinline__ void start_path_at(const TraceArgs& A, uint32_t item, uint32_t s, uint32_t x, uint32_t y, uint32_t hs, Path& P) {
+    const uint32_t base = hash2(y * A.width + x, HS ? hs : hash2(s, A.seed));
     float jx = 0.0f, jy = 0.0f;
     if (A.spp > 1) {
         const float xi0 = rnd(base, 1), xi1 = rnd(base, 2);
@@ -275,6 +276,16 @@ __device__ __forceinline__ void start_path(const TraceArgs& A, uint32_t item, Pa
     P.tr = P.tg = P.tb = 1.0f;
     P.lr = P.lg = P.lb = 0.0f;
     P.slot = item; P.base = base; P.depth = 0;
+}
+template <bool REF = false, bool LIST = false>
+__device__ __forceinline__ void start_path(const TraceArgs& A, uint32_t item, Path& P) {
+    const uint32_t sb = fdiv(item, A.div_npix);
+    uint32_t pix = item - sb * A.npix;
+    if constexpr (LIST) pix = A.active[pix];
+    const uint32_t s = A.s0 + sb;
+    const uint32_t lrow = fdiv(pix, A.div_width), x = pix - lrow * A.width;
+    const uint32_t y = frame_row(A, lrow);
+    start_path_at<REF>(A, item, s, x, y, 0u, P);
 }
 
 }  // namespace

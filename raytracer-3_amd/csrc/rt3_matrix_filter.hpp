@@ -859,12 +859,37 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma(const TraceArgs A, const u32
 // their throughput and depth.  A trip of the main loop (ray operands, 512 filter rows on the matrix cores, decode, push) is then spent on
 // bounce rays only.  Same functions, same inputs, same per-path order, same RNG counters: the frame does not depend on the schedule.
 // A restock whose groups list more than A.prim_list_max spheres (or have no list: every bit set) stocks its rays untraced; they take the filter.
-// casts: primary casts traced here; exact: their (ray, sphere) tests.  ph_restock (RT3_PROFILE_PHASES): wave time of the primary pass.
-struct SphereMirror { const float4* sph; const float* invr; const float4* mat; const uint32_t* kind; uint32_t n_blocks; };     // LDS
+// casts: primary casts traced here; exact: their (ray, sphere) tests.  ph (RT3_PROFILE_PHASES): wave time of the primary pass and of its parts.
+// Wave-uniform bookkeeping (registers: profiles/restock_uniform_kernel_resources.log): the integer work of a restock that is the same for all 64 lanes, or a function
+// of a small integer, leaves the vector ALU.  Nothing here touches a floating-point expression, an RNG counter or the order of work in a path.  Each
+// piece has its switch (1: on), so that two builds can be compared in one process (tools/ab.py):
+//   RT3_CTR_TABLE       shade_lane reads hash_u32(ctr + k) from the counter-hash table in LDS (rt3_path.hpp), here and in the main loop
+//   RT3_UNIFORM_SAMPLE  the 64 items lie in one sample block (dense form): hash2(s, seed) and the first item's (pixel, row, x) are worked out once, on
+//                       the scalar unit; a lane adds its index and wraps rows
+//   RT3_UNIFORM_GROUP   the 64 items lie in one aligned pixel group: its list is read with scalar loads, counted and walked from scalar registers
+//   RT3_COMPACT_SKIP    no survivor, or 64 of them: the compaction would be the identity
+#ifndef RT3_CTR_TABLE
+#define RT3_CTR_TABLE 1
+#endif
+#ifndef RT3_UNIFORM_SAMPLE
+#define RT3_UNIFORM_SAMPLE 1
+#endif
+#ifndef RT3_UNIFORM_GROUP
+#define RT3_UNIFORM_GROUP 1
+#endif
+#ifndef RT3_COMPACT_SKIP
+#define RT3_COMPACT_SKIP 1
+#endif
+static_assert(kMfmaSphMax / 32u <= 32u, "refill_from_traced_stock keeps one bit per row block in a 32-bit word (blocks)");
+typedef const __attribute__((address_space(4))) uint32_t* ConstWords;        // constant address space: a wave-uniform address loads through the scalar cache
+__device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// wave time per part of a restock (RT3_PROFILE_PHASES; unused otherwise)
+struct RestockPhases { unsigned long long total = 0, raygen = 0, fetch = 0, tests = 0, shade = 0, compact = 0; };
+struct SphereMirror { const float4* sph; const float* invr; const float4* mat; const uint32_t* kind; uint32_t n_blocks; const uint4* ctr_tab; };     // LDS
 template <bool LIST = false>
 __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, const SphereMirror& S, uint32_t lane, bool& alive, Path& P, TracedStock& Q,
                                                          uint32_t& chunk_next, uint32_t& chunk_end, bool& exhausted, unsigned long long& casts,
-                                                         unsigned long long& exact, unsigned long long& ph_restock) {
+                                                         unsigned long long& exact, RestockPhases& ph) {
     const unsigned long long need = __ballot(!alive);
     if (need == 0ull) return;
     const uint32_t n_need = (uint32_t)__popcll(need), rank = prefix_count(need);
@@ -889,65 +914,128 @@ __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, con
         }
 #ifdef RT3_PROFILE_PHASES
         const unsigned long long ph_t0 = clock64();
+        unsigned long long ph_mark = ph_t0;
+#define RT3_RPHASE(acc) { const unsigned long long now_ = clock64(); acc += now_ - ph_mark; ph_mark = now_; }
+#else
+#define RT3_RPHASE(acc)
 #endif
         const uint32_t n_new = min(64u, chunk_end - chunk_next);
         const uint32_t item = min(chunk_next + lane, chunk_end - 1u);
         bool live = lane < n_new;                                           // (the lanes beyond repeat the last item: they take no part)
         Path T;
-        start_path<false, LIST>(A, item, T);
-        chunk_next += n_new;
-        // the union of the lists of the pixel groups these items fall into (one or two; more only where a sample block is shorter than 64
-        // pixels): lane b holds the word of row block b
-        uint32_t word = 0, listed = 0xFFFFFFFFu;
-        if (A.prim_masks != nullptr) {
-            const uint32_t grp = (item - fdiv(item, A.div_npix) * A.npix) >> 6;
-            unsigned long long rest = __ballot(live);
-            while (rest != 0ull) {
-                const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)grp, (int)(__ffsll((long long)rest) - 1));
-                if (lane < S.n_blocks) word |= A.prim_masks[(size_t)g * S.n_blocks + lane];
-                rest &= ~__ballot(grp == g);
-            }
-            listed = 0;
-            for (uint32_t b = 0; b < S.n_blocks; b++) listed += (uint32_t)__popc((uint32_t)__builtin_amdgcn_readlane((int)word, (int)b));
+        // the first item's place, on the scalar unit: sample block, owned pixel; one_sample: the last item lies in the same sample block (dense form only:
+        // a list's items are no consecutive pixels)
+        constexpr bool kFirstItem = !LIST && (RT3_UNIFORM_SAMPLE || RT3_UNIFORM_GROUP);     // some piece uses the first item's decomposition
+        uint32_t pix0 = 0, s_first = 0;
+        bool one_sample = false;
+        if constexpr (kFirstItem) {
+            const uint32_t first = uniform(chunk_next), sb0 = uniform(fdiv(first, A.div_npix));
+            one_sample = sb0 == uniform(fdiv(first + (n_new - 1u), A.div_npix));
+            pix0 = first - sb0 * A.npix;
+            s_first = A.s0 + sb0;
         }
+        const uint32_t step = min(lane, n_new - 1u);                        // item - first item
+        if (!LIST && RT3_UNIFORM_SAMPLE && one_sample) {                    // (wave-uniform)
+            const uint32_t hs = uniform(hash2(s_first, A.seed));
+            const uint32_t lrow0 = uniform(fdiv(pix0, A.div_width)), x0 = pix0 - lrow0 * A.width;
+            uint32_t x = x0 + step, lrow = lrow0;
+            while (__ballot(x >= A.width) != 0ull)                          // row wrap: once for a frame of 64 or more columns
+                if (x >= A.width) { x -= A.width; lrow += 1u; }
+            start_path_at<false, true>(A, item, s_first, x, frame_row(A, lrow), hs, T);
+        } else start_path<false, LIST>(A, item, T);
+        chunk_next += n_new;
+        RT3_RPHASE(ph.raygen)
+        // the union of the lists of the pixel groups these items fall into (one or two; more only where a sample block is shorter than 64
+        // pixels).  One group: its words stay in scalar registers (tab).  Otherwise lane b holds the word of row block b.
+        uint32_t word = 0, listed = 0xFFFFFFFFu, blocks = 0;               // blocks (one group): the row blocks with a listed sphere
+        const bool one_group = !LIST && RT3_UNIFORM_GROUP && one_sample && (pix0 >> 6) == ((pix0 + (n_new - 1u)) >> 6);
+        ConstWords tab = nullptr;
+        if (A.prim_masks != nullptr) {
+            listed = 0;
+            if (one_group) {
+                tab = (ConstWords)(A.prim_masks + (size_t)(pix0 >> 6) * S.n_blocks);
+#pragma unroll 4
+                for (uint32_t b = 0; b < S.n_blocks; b++) {
+                    const uint32_t w = tab[b];
+                    listed += (uint32_t)__popc(w);
+                    blocks |= (w != 0u ? 1u : 0u) << b;
+                }
+            } else {
+                const uint32_t grp = (kFirstItem && one_sample ? pix0 + step : item - fdiv(item, A.div_npix) * A.npix) >> 6;
+                unsigned long long rest = __ballot(live);
+                while (rest != 0ull) {
+                    const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)grp, (int)(__ffsll((long long)rest) - 1));
+                    if (lane < S.n_blocks) word |= A.prim_masks[(size_t)g * S.n_blocks + lane];
+                    rest &= ~__ballot(grp == g);
+                }
+                for (uint32_t b = 0; b < S.n_blocks; b++) listed += (uint32_t)__popc((uint32_t)__builtin_amdgcn_readlane((int)word, (int)b));
+            }
+        }
+        RT3_RPHASE(ph.fetch)
         if (listed <= A.prim_list_max) {                                    // (wave-uniform)
             casts += n_new;
             unsigned long long key = direct_tests(A, T.ox, T.oy, T.oz, T.dx, T.dy, T.dz, [&](uint32_t j) { return S.sph[j]; });
-            for (uint32_t b = 0; b < S.n_blocks; b++) {
-                uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)word, (int)b);
-                while (m != 0u) {
-                    const uint32_t j = b * 32u + ((uint32_t)__ffs((int)m) - 1u);
-                    m &= m - 1u;
-                    float t;
-                    if (sphere_root(S.sph[j], T.ox, T.oy, T.oz, T.dx, T.dy, T.dz, A.t_min, t) && t < __builtin_inff()) {
-                        const unsigned long long kk = hit_key(t, 1u, j);
-                        key = kk < key ? kk : key;
+            auto listed_sphere = [&](uint32_t j) {
+                float t;
+                if (sphere_root(S.sph[j], T.ox, T.oy, T.oz, T.dx, T.dy, T.dz, A.t_min, t) && t < __builtin_inff()) {
+                    const unsigned long long kk = hit_key(t, 1u, j);
+                    key = kk < key ? kk : key;
+                }
+                exact += n_new;
+            };
+            if (one_group) {
+                while (blocks != 0u) {                                      // (a traced list is never null: listed would be 0xFFFFFFFF)
+                    const uint32_t b = (uint32_t)__ffs((int)blocks) - 1u;
+                    blocks &= blocks - 1u;
+                    uint32_t m = tab[b];
+                    while (m != 0u) {
+                        listed_sphere(b * 32u + ((uint32_t)__ffs((int)m) - 1u));
+                        m &= m - 1u;
                     }
-                    exact += n_new;
+                }
+            } else {
+                for (uint32_t b = 0; b < S.n_blocks; b++) {
+                    uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)word, (int)b);
+                    while (m != 0u) {
+                        listed_sphere(b * 32u + ((uint32_t)__ffs((int)m) - 1u));
+                        m &= m - 1u;
+                    }
                 }
             }
+            RT3_RPHASE(ph.tests)
             uint32_t kind, ibest;
             float tbest;
             key_decode(key, kind, ibest, tbest);
-            shade_lane<false, true>(A, T, live, kind, ibest, tbest, S.sph, S.invr, S.mat, S.kind);
-            // the survivors move to lanes [0, n), the rest behind them: a permutation of the wave (ds_permute: every lane sends)
+            shade_lane<false, true, false, RT3_CTR_TABLE != 0>(A, T, live, kind, ibest, tbest, S.sph, S.invr, S.mat, S.kind, S.ctr_tab);
+            RT3_RPHASE(ph.shade)
+            // the survivors move to lanes [0, n), the rest behind them: a permutation of the wave (ds_permute: every lane sends) — the identity when no
+            // lane survives (a strip of sky) or all 64 do
             const unsigned long long surv = __ballot(live);
-            const uint32_t n = (uint32_t)__popcll(surv), before = prefix_count(surv);
-            const int to = (int)((live ? before : n + (lane - before)) * 4u);
-            auto send = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_permute(to, (int)v); };
-            auto sendf = [&](float v) { return __uint_as_float(send(__float_as_uint(v))); };
-            Q.ox = sendf(T.ox); Q.oy = sendf(T.oy); Q.oz = sendf(T.oz); Q.dx = sendf(T.dx); Q.dy = sendf(T.dy); Q.dz = sendf(T.dz);
-            Q.tr = sendf(T.tr); Q.tg = sendf(T.tg); Q.tb = sendf(T.tb);
-            Q.slot = send(T.slot); Q.base = send(T.base); Q.depth = send(T.depth);
+            const uint32_t n = (uint32_t)__popcll(surv);
+            if (RT3_COMPACT_SKIP && (n == 0u || n == 64u)) {
+                Q.ox = T.ox; Q.oy = T.oy; Q.oz = T.oz; Q.dx = T.dx; Q.dy = T.dy; Q.dz = T.dz;
+                Q.tr = T.tr; Q.tg = T.tg; Q.tb = T.tb;
+                Q.slot = T.slot; Q.base = T.base; Q.depth = T.depth;
+            } else {
+                const uint32_t before = prefix_count(surv);
+                const int to = (int)((live ? before : n + (lane - before)) * 4u);
+                auto send = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_permute(to, (int)v); };
+                auto sendf = [&](float v) { return __uint_as_float(send(__float_as_uint(v))); };
+                Q.ox = sendf(T.ox); Q.oy = sendf(T.oy); Q.oz = sendf(T.oz); Q.dx = sendf(T.dx); Q.dy = sendf(T.dy); Q.dz = sendf(T.dz);
+                Q.tr = sendf(T.tr); Q.tg = sendf(T.tg); Q.tb = sendf(T.tb);
+                Q.slot = send(T.slot); Q.base = send(T.base); Q.depth = send(T.depth);
+            }
             Q.n = n;
+            RT3_RPHASE(ph.compact)
         } else {
             Q.ox = T.ox; Q.oy = T.oy; Q.oz = T.oz; Q.dx = T.dx; Q.dy = T.dy; Q.dz = T.dz; Q.slot = T.slot; Q.base = T.base;
             Q.tr = Q.tg = Q.tb = 1.0f; Q.depth = 0;
             Q.n = n_new;
         }
 #ifdef RT3_PROFILE_PHASES
-        ph_restock += clock64() - ph_t0;
+        ph.total += clock64() - ph_t0;
 #endif
+#undef RT3_RPHASE
     }
 }
 
@@ -968,9 +1056,12 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
     uint32_t* s_bm = reinterpret_cast<uint32_t*>(s_kind + (size_t)n_blocks * 32); // [16][kMB] candidate words
     unsigned long long* s_key = reinterpret_cast<unsigned long long*>(s_bm + 16 * kMB);   // [kMB] nearest hit of every lane's ray
     uint32_t* s_pairs = reinterpret_cast<uint32_t*>(s_key + kMB);              // [16 waves][kPairCap]
+    constexpr bool CTR = !QUERY && RT3_CTR_TABLE != 0;                          // render forms: the counter-hash table (kCtrTableBytes more, sized by the host)
+    uint32_t* s_ctr = s_pairs + (kMB / 64u) * kPairCap;                        // [kCtrDepthCap][4]
     const uint32_t tid = threadIdx.x, lane = lane_id();
     uint32_t* pairs = s_pairs + (tid / 64u) * kPairCap;
     unsigned long long* keys = s_key + (tid & ~63u);
+    if constexpr (CTR) for (uint32_t k = tid; k < kCtrDepthCap * 4u; k += kMB) s_ctr[k] = ctr_table_word(k);
     for (uint32_t k = tid; k < n_blocks * 128; k += kMB) s_frag[k] = frags[k];
     for (uint32_t k = tid; k < n_blocks * 32; k += kMB) {
         const bool in = k < A.n_sph;
@@ -989,9 +1080,11 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
     bool exhausted = false;
     TracedStock Q;
     Q.ox = Q.oy = Q.oz = 0.0f; Q.dx = Q.dy = 0.0f; Q.dz = 1.0f; Q.tr = Q.tg = Q.tb = 0.0f; Q.slot = 0; Q.base = 0; Q.depth = 0; Q.n = 0;
-    const SphereMirror mirror = { s_sph, s_invr, s_mat, s_kind, n_blocks };
+    const uint4* ctr_tab = reinterpret_cast<const uint4*>(s_ctr);
+    const SphereMirror mirror = { s_sph, s_invr, s_mat, s_kind, n_blocks, ctr_tab };
     unsigned long long casts = 0, iters = 0, exact = 0;
-    unsigned long long primary_casts = 0, ph_restock = 0;                       // render form: ray casts traced at restock time, wave time spent on them
+    unsigned long long primary_casts = 0;                                       // render form: ray casts traced at restock time
+    RestockPhases ph_restock;                                                   // ... and the wave time spent on them
 #ifdef RT3_PROFILE_PHASES                                                       // wave time (s_memtime) per part of a trip: tools/README.md
     unsigned long long ph_refill = 0, ph_operands = 0, ph_scan = 0, ph_flush = 0, ph_shade = 0, ph_mark = clock64();
 #define RT3_SPHASE(acc) { const unsigned long long now_ = clock64(); acc += now_ - ph_mark; ph_mark = now_; }
@@ -1035,14 +1128,17 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
         if constexpr (QUERY) query_sink(A, P, alive, keys[lane]);
         else {
             key_decode(keys[lane], kind, ibest, tbest);
-            shade_lane<false, true>(A, P, alive, kind, ibest, tbest, s_sph, s_invr, s_mat, s_kind);
+            shade_lane<false, true, false, CTR>(A, P, alive, kind, ibest, tbest, s_sph, s_invr, s_mat, s_kind, ctr_tab);
         }
         RT3_SPHASE(ph_shade)
     }
 #ifdef RT3_PROFILE_PHASES
     if (lane == 0) {
-        atomicAdd(A.cast_counter + 11, ph_refill - ph_restock); atomicAdd(A.cast_counter + 12, ph_operands); atomicAdd(A.cast_counter + 13, ph_scan);
-        atomicAdd(A.cast_counter + 14, ph_flush); atomicAdd(A.cast_counter + 15, ph_shade); atomicAdd(A.cast_counter + 17, ph_restock);
+        atomicAdd(A.cast_counter + 11, ph_refill - ph_restock.total); atomicAdd(A.cast_counter + 12, ph_operands); atomicAdd(A.cast_counter + 13, ph_scan);
+        atomicAdd(A.cast_counter + 14, ph_flush); atomicAdd(A.cast_counter + 15, ph_shade); atomicAdd(A.cast_counter + 17, ph_restock.total);
+        // [18..22]: the restock's parts — ray generation, list fetch, listed + direct tests, shade, compaction
+        atomicAdd(A.cast_counter + 18, ph_restock.raygen); atomicAdd(A.cast_counter + 19, ph_restock.fetch); atomicAdd(A.cast_counter + 20, ph_restock.tests);
+        atomicAdd(A.cast_counter + 21, ph_restock.shade); atomicAdd(A.cast_counter + 22, ph_restock.compact);
     }
 #endif
 #undef RT3_SPHASE

@@ -134,9 +134,12 @@ __device__ __forceinline__ void stock_pop(const TracedStock& Q, uint32_t src, bo
 // The four per-sphere arrays read at a hit are parameters: global memory in k_trace, LDS copies in k_trace_mfma.
 // REF (RT3_FLAG_REFERENCE_PRIMARY): at ray cast 0 the direction is the reference's unnormalised one — the sky and the hit point use
 // it as it is (SequentialRenderer.cpp:77,105-107); the scatter formulas then get the unit direction.
-template <bool HAS_TRI, bool HAS_SPH, bool REF = false>
+// CTR: ctr_tab is the counter-hash table (rt3_kernel_common.hpp, kCtrDepthCap rows in LDS): the inner hash of rnd(base, ctr + k) depends on the
+// depth alone, so a lane below the cap reads its row instead of computing three hashes; at or beyond the cap it computes them as rnd() does.
+template <bool HAS_TRI, bool HAS_SPH, bool REF = false, bool CTR = false>
 __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& alive, uint32_t kind, uint32_t ibest, float tbest,
-                                           const float4* sph, const float* sph_invr, const float4* sph_mat, const uint32_t* sph_kind) {
+                                           const float4* sph, const float* sph_invr, const float4* sph_mat, const uint32_t* sph_kind,
+                                           const uint4* ctr_tab = nullptr) {
     const float ox = P.ox, oy = P.oy, oz = P.oz;
     float dx = P.dx, dy = P.dy, dz = P.dz;
     if (alive) {
@@ -176,6 +179,12 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
                 const bool front = dotf(dx, dy, dz, nx, ny, nz) < 0.0f;
                 if (!front) { nx = -nx; ny = -ny; nz = -nz; }           // (the dot product is recomputed with the flipped normal below:
                 const uint32_t ctr = 1u + 8u * (P.depth + 1u);
+                uint32_t h0 = 0, h1 = 0, h2 = 0;                // CTR: hash_u32(ctr + k)
+                if constexpr (CTR) {
+                    if (P.depth < kCtrDepthCap) { const uint4 row = ctr_tab[P.depth]; h0 = row.x; h1 = row.y; h2 = row.z; }
+                    else { h0 = hash_u32(ctr); h1 = hash_u32(ctr + 1u); h2 = hash_u32(ctr + 2u); }
+                }
+                auto xi = [&](uint32_t k, uint32_t h) { return CTR ? u01(hash_u32(P.base ^ h)) : rnd(P.base, ctr + k); };
                 float sx, sy, sz;                               // scattered direction before normalisation
                 float ar = m.x, ag = m.y, ab = m.z;
                 // work shared between material branches is done once for all lanes that need it: the random unit vector
@@ -184,7 +193,7 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
                 const float dn = dotf(dx, dy, dz, nx, ny, nz);
                 float vx = 0.0f, vy = 0.0f, vz = 0.0f;
                 if ((mk == RT3_MAT_LAMBERT) | ((mk == RT3_MAT_METAL) & (m.w > 0.0f)))
-                    unit_vector(rnd(P.base, ctr), rnd(P.base, ctr + 1), vx, vy, vz);
+                    unit_vector(xi(0, h0), xi(1, h1), vx, vy, vz);
                 const float k2 = 2.0f * dn;
                 const float mx = fma_(-k2, nx, dx), my = fma_(-k2, ny, dy), mz = fma_(-k2, nz, dz);   // reflect(d, n)
                 if (mk == RT3_MAT_LAMBERT) {
@@ -206,7 +215,7 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
                     const float r0 = front ? m.y : m.z;
                     const float xx = 1.0f - cosv, x2 = xx * xx, x5 = x2 * x2 * xx;
                     const float R = fma_(1.0f - r0, x5, r0);
-                    if (cannot || R > rnd(P.base, ctr + 2)) {
+                    if (cannot || R > xi(2, h2)) {
                         sx = mx; sy = my; sz = mz;
                     } else {
                         const float ex = fma_(cosv, nx, dx) * ri, ey = fma_(cosv, ny, dy) * ri, ez = fma_(cosv, nz, dz) * ri;

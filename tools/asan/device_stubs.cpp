@@ -48,6 +48,15 @@ int rt3_debug_force_brute(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_force_flat_filter(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_arith(rt3_ctx*, const float*, const float*, uint32_t, float*, float*, float*, float*, float*, float*, uint32_t*) { return RT3_E_DEVICE; }
 int rt3_debug_primary_lists(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t*, uint64_t, uint32_t*, uint32_t*) { return RT3_E_DEVICE; }
+uint32_t rt3_debug_ctr_table(uint32_t* out, uint32_t capacity_rows) {       // host code in the library too: the same table, from random_v1.glsl's hash
+    const uint32_t rows = 64;
+    for (uint32_t k = 0; out && k < (capacity_rows < rows ? capacity_rows : rows) * 4u; k++) {
+        uint32_t x = 1u + 8u * ((k >> 2) + 1u) + (k & 3u);
+        x += x << 10; x ^= x >> 6; x += x << 3; x ^= x >> 11; x += x << 15;
+        out[k] = x;
+    }
+    return rows;
+}
 int rt3_intersect(rt3_ctx*, const rt3_ray*, uint32_t, float, rt3_hit*) { return RT3_E_DEVICE; }
 int rt3_occluded(rt3_ctx*, const rt3_ray*, uint32_t, float, uint32_t*) { return RT3_E_DEVICE; }
 int rt3_intersect_device(rt3_ctx*, const void*, uint32_t, float, void*, void*) { return RT3_E_DEVICE; }
