@@ -176,6 +176,38 @@ int rt3_mesh_download(rt3_ctx* ctx, rt3_gface* faces, float* vertices_xyzw);
 int rt3_set_spheres(rt3_ctx* ctx, const float* center_radius, const rt3_material* materials, uint32_t n);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Scene upload from device arrays   (a scene that is made or changes its counts on the device)
+ * ------------------------------------------------------------------------------------------------- */
+/* rt3_set_spheres_device: after the call the context is in the state that rt3_set_spheres(<the same arrays>) followed by
+ * rt3_regroup(RT3_REGROUP_SPHERES) leaves, so every entry point (render, range render, adaptive, query, AOV, motion, Mode R) returns bit
+ * for bit what it returns after the host upload, rt3_debug_group_order returns the regroup order of the usable spheres (not on the direct
+ * list, a finite centre and a finite r^2), and rt3_update_spheres* / rt3_regroup* work on the result as after a host upload.  A sphere
+ * with a non-finite record is left out of the group order as on the host (an update then returns RT3_E_STATE); unlike rt3_regroup the
+ * build works with such spheres.  rt3_set_mesh_device: the same against rt3_set_mesh(...) followed by rt3_regroup(RT3_REGROUP_MESH);
+ * indices are taken as given (no rebasing), the merged entity buffers afterwards hold the caller's arrays (rt3_mesh_download,
+ * rt3_update_mesh* work) and d_face_materials may be NULL as in rt3_set_mesh.
+ * d_center_radius: n x (cx, cy, cz, r) floats; d_materials: n rt3_material; d_faces: n_faces rt3_gface; d_vertices_xyzw: n_vertices x 4
+ * floats.  The arrays are only read; they must stay valid until the work queued on `stream` has run.
+ * The filter centre is rt3_set_spheres' (the component-wise median of the finite coordinates), the direct list its set of at most four
+ * spheres whenever there are at most four candidates or the candidates' ratios are pairwise distinct; among more than four candidates
+ * with equal ratios any four of the largest are taken (any choice is correct: it changes the filter's work, never a result).
+ * Two phases, one wait: phase 1 reads the caller's arrays and writes scratch; the call then waits for the device ONCE, to read back a few
+ * dozen bytes (the buffer sizes depend on them); phase 2 allocates and queues the rest on `stream`.  So the device forms can refuse:
+ * RT3_E_ARG with the scene untouched for a radius that is not > 0 (NaN included; the message names the lowest such index), a material
+ * kind above RT3_MAT_DIELECTRIC, a NULL array with a non-zero count, a pointer that is not 16-byte aligned (4-byte for the material
+ * arrays) and a NULL ctx.  A face index out of range returns RT3_E_ARG and leaves the context without a mesh, as rt3_set_mesh does.
+ * n == 0 / n_faces == 0 clears that class (the pointers may then be NULL).  Streams follow the convention above and the event chain of
+ * the updates.  Not for graph capture (the wait). */
+int rt3_set_spheres_device(rt3_ctx* ctx, const void* d_center_radius, const void* d_materials, uint32_t n, void* stream);
+int rt3_set_mesh_device(rt3_ctx* ctx, const void* d_faces, uint32_t n_faces, const void* d_vertices_xyzw, uint32_t n_vertices,
+                        const void* d_face_materials, void* stream);
+/* Tests only.  rt3_debug_sphere_plan: what rt3_set_spheres decides for these records, on the host (no device, no context): the filter
+ * centre and the direct list (unused entries 0xFFFFFFFF); returns the length of the list.  rt3_debug_sphere_build: what the context
+ * holds after the last sphere upload of either form; RT3_E_STATE without spheres. */
+uint32_t rt3_debug_sphere_plan(const float* center_radius, uint32_t n, float centre[3], uint32_t direct[4]);
+int rt3_debug_sphere_build(rt3_ctx* ctx, float centre[3], uint32_t direct[4], uint32_t* n_direct);
+
+/* ---------------------------------------------------------------------------------------------------
  * Scene update   (new positions for the scene that is there: a refit on the device)
  * ------------------------------------------------------------------------------------------------- */
 /* rt3_update_spheres*: after the call every entry point (render, range render, query, AOV, motion, Mode R) returns bit for bit what it

@@ -151,6 +151,7 @@ EXPORTS = [
     "rt3_debug_primary_lists", "rt3_debug_ctr_table",
     "rt3_regroup", "rt3_regroup_device", "rt3_debug_group_order",
     "rt3_render_path_adaptive", "rt3_render_path_adaptive_device",
+    "rt3_set_spheres_device", "rt3_set_mesh_device", "rt3_debug_sphere_plan", "rt3_debug_sphere_build",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -222,6 +223,8 @@ def lib():
         "rt3_update_mesh": (i32, [vp, vp, vp, u32]), "rt3_update_mesh_device": (i32, [vp, vp, vp, u32, vp]),
         "rt3_regroup": (i32, [vp, u32]), "rt3_regroup_device": (i32, [vp, u32, vp]), "rt3_debug_group_order": (i32, [vp, u32, vp, u64, vp]),
         "rt3_render_path_adaptive": (i32, [vp, vp, vp, vp, vp, vp]), "rt3_render_path_adaptive_device": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "rt3_set_spheres_device": (i32, [vp, vp, vp, u32, vp]), "rt3_set_mesh_device": (i32, [vp, vp, u32, vp, u32, vp, vp]),
+        "rt3_debug_sphere_plan": (u32, [vp, u32, vp, vp]), "rt3_debug_sphere_build": (i32, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -535,7 +538,7 @@ class HipRenderer(Renderer):
         self.n_faces = 0
         self.n_spheres = 0
         self._mesh_counts = (0, 0)
-        self._torch_device = None    # set by a device-form update: regroup() then queues on torch's current stream as well
+        self._torch_device = None    # set by a device-form upload or update: regroup() then queues on torch's current stream as well
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -612,6 +615,30 @@ class HipRenderer(Renderer):
         return faces, verts
 
     def set_mesh(self, faces, verts, face_materials=None):
+        """The merged mesh (rt3_set_mesh).  numpy arrays: the host upload, synchronous.  Contiguous torch GPU tensors on one device — verts
+        float32 (n, 4), faces any tensor of n 48-byte records, face_materials None or n 20-byte records — are read in place and the scene is
+        built on the device, queued on torch.cuda.current_stream() (rt3_set_mesh_device): the state of the host upload
+        followed by regroup().  The call waits for the device once."""
+        nv = self._torch_rows(verts, "verts", 16)
+        if nv is not None:
+            import torch
+            if verts.dtype != torch.float32:
+                raise Fatal("device verts must be float32")
+            nf = self._torch_rows(faces, "faces", GFACE.itemsize)
+            if nf is None or faces.device != verts.device:
+                raise Fatal("device faces must be a GPU tensor on the verts' device")
+            mptr = None
+            if face_materials is not None:
+                if self._torch_rows(face_materials, "face_materials", MATERIAL.itemsize) != nf or face_materials.device != verts.device:
+                    raise Fatal("device face_materials must hold one 20-byte record per face, on the verts' device")
+                mptr = C.c_void_p(face_materials.data_ptr())
+            stream = torch.cuda.current_stream(verts.device).cuda_stream
+            self._torch_device = verts.device
+            self._check(lib().rt3_set_mesh_device(self._ctx, C.c_void_p(faces.data_ptr()) if nf else None, nf,
+                                                  C.c_void_p(verts.data_ptr()) if nv else None, nv, mptr, C.c_void_p(stream)))
+            self.n_faces = nf
+            self._mesh_counts = (nf, nv)
+            return
         faces = np.ascontiguousarray(faces)
         verts = np.ascontiguousarray(verts, np.float32)
         assert faces.dtype == GFACE
@@ -624,12 +651,38 @@ class HipRenderer(Renderer):
         self._mesh_counts = (len(faces), len(verts))
 
     def set_spheres(self, center_radius, materials):
+        """The analytic spheres (rt3_set_spheres).  numpy arrays: the host upload, synchronous.  Contiguous torch GPU tensors on one device —
+        center_radius float32 (n, 4), materials any tensor of n 20-byte records — are read in place and the scene is built on the device,
+        queued on torch.cuda.current_stream() (rt3_set_spheres_device): the state of the host upload followed by regroup().
+        The call waits for the device once; a radius that is not > 0 or an unknown material kind is refused with the scene untouched."""
+        n = self._torch_rows(center_radius, "center_radius", 16)
+        if n is not None:
+            import torch
+            if center_radius.dtype != torch.float32:
+                raise Fatal("device center_radius must be float32")
+            if self._torch_rows(materials, "materials", MATERIAL.itemsize) != n or materials.device != center_radius.device:
+                raise Fatal("device materials must hold one 20-byte record per sphere, on center_radius' device")
+            stream = torch.cuda.current_stream(center_radius.device).cuda_stream
+            self._torch_device = center_radius.device
+            self._check(lib().rt3_set_spheres_device(self._ctx, C.c_void_p(center_radius.data_ptr()) if n else None,
+                                                     C.c_void_p(materials.data_ptr()) if n else None, n, C.c_void_p(stream)))
+            self.n_spheres = n
+            return
         cr = np.ascontiguousarray(center_radius, np.float32).reshape(-1, 4)
         materials = np.ascontiguousarray(materials)
         assert materials.dtype == MATERIAL and len(materials) == len(cr)
         self._torch_device = None
         self._check(lib().rt3_set_spheres(self._ctx, _p(cr), _p(materials), len(cr)))
         self.n_spheres = len(cr)
+
+    def sphere_build(self):
+        """Tests: the filter centre (3 float32) and the direct list (sorted uint32) the context holds after the last sphere upload
+        (rt3_debug_sphere_build)."""
+        centre = np.zeros(3, np.float32)
+        direct = np.zeros(4, np.uint32)
+        n = C.c_uint32(0)
+        self._check(lib().rt3_debug_sphere_build(self._ctx, _p(centre), _p(direct), C.byref(n)))
+        return centre, np.sort(direct[:n.value])
 
     # -- refit: new positions for the scene that is there (rt3_update_*; DESIGN.md 4.14) -----------------------------
     @staticmethod
@@ -1056,6 +1109,16 @@ class HipRenderer(Renderer):
         out = np.zeros((-(-npix // 64), 16), np.uint32)
         self._check(lib().rt3_debug_primary_lists(self._ctx, C.byref(cam), C.byref(params), _p(out), out.size, C.byref(ng), C.byref(nb)))
         return out.reshape(-1)[:ng.value * nb.value].reshape(ng.value, nb.value).copy()
+
+
+def sphere_plan(center_radius):
+    """Tests: what the host upload decides for these (n, 4) records (rt3_debug_sphere_plan; no device): the filter centre (3 float32) and the
+    direct list (sorted uint32)."""
+    cr = np.ascontiguousarray(center_radius, np.float32).reshape(-1, 4)
+    centre = np.zeros(3, np.float32)
+    direct = np.zeros(4, np.uint32)
+    n = lib().rt3_debug_sphere_plan(_p(cr), len(cr), _p(centre), _p(direct))
+    return centre, np.sort(direct[:n])
 
 
 def initialize_renderer(device=0):

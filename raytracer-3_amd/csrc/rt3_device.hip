@@ -20,6 +20,9 @@
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
 //   rt3_regroup.hpp         the group order of the multi-level filter again on the device (rt3_regroup*): the median split as stable sorts,
 //                           in LDS for parts of up to 4096 primitives
+//   rt3_scene_build.hpp     a full upload from device arrays (rt3_set_spheres_device / rt3_set_mesh_device): validation, the medians, the direct
+//                           list and the ordered compaction into the initial group order
+//   rt3_sphere_plan.hpp     host: the filter centre and the direct list of a sphere upload (shared with rt3_host.cpp)
 //   below                   the device context and the extern "C" entry points
 //
 // Compiled with -ffp-contract=off: a*b+c is two roundings unless written __builtin_fmaf.  Division and sqrt are
@@ -40,6 +43,7 @@
 
 #include "rt3.h"
 
+#include "rt3_sphere_plan.hpp"
 #include "rt3_kernel_common.hpp"
 #include "rt3_path.hpp"
 #include "rt3_valu_scan.hpp"
@@ -51,6 +55,7 @@
 #include "rt3_denoise.hpp"
 #include "rt3_scene_kernels.hpp"
 #include "rt3_regroup.hpp"
+#include "rt3_scene_build.hpp"
 #include "rt3_primary_lists.hpp"
 
 // ======================================================================================================
@@ -123,6 +128,7 @@ struct rt3_ctx {
     uint32_t tri_bounded = 0;
     RegroupPlan rg_sph, rg_tri;
     DevBuf<float4> d_rg_cen; DevBuf<uint32_t> d_rg_ids[2], d_rg_box; DevBuf<uint64_t> d_rg_keys[2]; DevBuf<uint8_t> d_rg_temp;
+    DevBuf<uint32_t> d_sb;                                          // rt3_set_*_device: the build's header and the compaction's block counts (rt3_scene_build.hpp)
     bool update_error_pending = false;                              // a device-form rt3_update_mesh_device with faces: d_error is read by the next rt3_synchronize
 
     // rows of the multi-level filter: faces and spheres, each in the order of a spatial median split
@@ -317,59 +323,7 @@ std::vector<uint32_t> build_sphere_frags32(const float* center_radius, uint32_t 
     return out;
 }
 
-// The centre of the spheres' filter coordinates: the component-wise median of the centres — the middle of where the spheres are,
-// whatever a few far or huge ones do (the book scene's ground sphere, centre y = -1000, moves the mean by two units and the median not at
-// all; weights of 1 / r^2, the minimiser of the sum of margin / r^2, follow the few smallest spheres instead: 9 % more exact tests on the
-// 100 000-sphere scene).  Non-finite coordinates are skipped; (0, 0, 0) without any.
-void sphere_filter_centre(const float* center_radius, uint32_t n, float out[3]) {
-    std::vector<float> v;
-    v.reserve(n);
-    for (int a = 0; a < 3; a++) {
-        v.clear();
-        for (uint32_t i = 0; i < n; i++) { const float c = center_radius[4 * (size_t)i + a]; if (std::isfinite(c)) v.push_back(c); }
-        out[a] = 0.0f;
-        if (v.empty()) continue;
-        std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
-        out[a] = v[v.size() / 2];
-    }
-}
-
-// Spheres that (nearly) every ray is a candidate for: the line of a ray that starts somewhere in the scene meets a sphere whose radius is
-// comparable to its distance from there — the book scene's ground (r = 1000, its centre 1000 away).  The filter cannot reject such a sphere
-// and it costs the pair list one entry per ray, so the matrix-filter kernels test it directly instead (TraceArgs::direct).  Any choice is
-// correct; this one takes the (at most four) spheres with the largest r / max(|centre - c0|, R) above 1/2, R = the median distance of the
-// centres from c0, i.e. the scene's own size: a unit sphere in the middle of the book scene (candidate for a few per cent of the rays) stays
-// in the filter — a direct test costs every ray ~30 instructions.
-uint32_t sphere_direct_list(const float* center_radius, uint32_t n, const float c0[3], uint32_t out[4]) {
-    std::vector<double> dist(n);
-    for (uint32_t i = 0; i < n; i++) {
-        const float* s = center_radius + 4 * (size_t)i;
-        const double dx = (double)s[0] - c0[0], dy = (double)s[1] - c0[1], dz = (double)s[2] - c0[2];
-        dist[i] = std::sqrt(dx * dx + dy * dy + dz * dz);
-    }
-    double scene = 0.0;
-    if (n) {
-        std::vector<double> d(dist);
-        for (double& v : d) if (!std::isfinite(v)) v = 0.0;
-        std::nth_element(d.begin(), d.begin() + d.size() / 2, d.end());
-        scene = d[d.size() / 2];
-    }
-    float best[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    uint32_t count = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const float ratio = (float)((double)center_radius[4 * (size_t)i + 3] / std::max(std::max(dist[i], scene), 1e-30));
-        if (!(ratio >= 0.5f)) continue;                             // (NaN: not chosen)
-        uint32_t k = count < 4 ? count++ : 4;
-        if (k == 4) {                                               // replace the weakest if this one is stronger
-            uint32_t w = 0;
-            for (uint32_t q = 1; q < 4; q++) if (best[q] < best[w]) w = q;
-            if (!(ratio > best[w])) continue;
-            k = w;
-        }
-        best[k] = ratio; out[k] = i;
-    }
-    return count;
-}
+// sphere_filter_centre / sphere_direct_list (the filter's centre, the directly tested spheres): rt3_sphere_plan.hpp
 
 // Group order for the two-level filter: a median split of the centres along the longest axis of their box, repeated until a
 // part holds at most `group` primitives; the left part of every split is a multiple of `group`, so that only the very last group is short.
@@ -1334,6 +1288,244 @@ int rt3_debug_group_order(rt3_ctx* ctx, uint32_t what, uint32_t* out, uint64_t c
     RT3_HIP(hipSetDevice(ctx->device));
     if (ctx->ev_acc_recorded) RT3_HIP(hipEventSynchronize(ctx->ev_acc));    // (a regroup may have run on a caller's stream)
     if (R.perm.size()) RT3_HIP(hipMemcpy(out, R.perm.get(), R.perm.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- Full upload from device arrays: phase 1 looks at the caller's arrays and writes scratch only, one read-back of the
+// build's header follows, phase 2 allocates and queues the rest — the refit's kernels, regroup_order and the refit's tail
+// build_rows' buffers and counts for n_pos positions, without its host vectors; the caller fills grp and perm and runs refit_rows
+static int alloc_rows(rt3_ctx* ctx, FilterRows& R, uint32_t n_pos, uint32_t group) {
+    static_assert(kSuper > 1, "alloc_rows: the three- and four-level rows");
+    R = FilterRows();
+    int rc;
+    if ((rc = R.grp.alloc(ctx, n_pos)) || (rc = R.perm.alloc(ctx, n_pos))) return rc;
+    const uint32_t n_leaves = n_pos / group, n_groups = n_leaves / kSuper;
+    if (n_groups == 0) return 0;
+    const uint32_t n_group_rows = round_up(n_groups, 32u), n_super = (n_groups + kSuper - 1u) / kSuper, n_super_rows = round_up(n_super, 32u);
+    if ((rc = R.leaf.alloc(ctx, n_leaves)) || (rc = R.gfrag.alloc(ctx, (size_t)n_group_rows * 4)) || (rc = R.rowb.alloc(ctx, n_group_rows)) ||
+        (rc = R.sfrag.alloc(ctx, (size_t)n_super_rows * 4)) || (rc = R.srowb.alloc(ctx, n_super_rows))) {
+        R = FilterRows();
+        return rc;
+    }
+    R.n_leaves = n_leaves; R.n_groups = n_groups; R.n_super = n_super;
+    return 0;
+}
+static dim3 build_grid(uint32_t threads) { return dim3((threads + kBlock - 1) / kBlock); }
+// the header and the block counts of a build over n primitives; with sort_scratch the key buffers and the radix sorts' temporary storage of the
+// medians (the regroup's scratch: it belongs to the context, and a build's later regroup_plan only grows it)
+static int build_scratch(rt3_ctx* ctx, uint32_t n, bool sort_scratch, size_t* temp_bytes) {
+    int rc;
+    if ((rc = ctx->d_sb.ensure(ctx, (size_t)kSbWords + (n + kBlock - 1) / kBlock))) return rc;
+    if (!sort_scratch) return 0;
+    size_t a = 0, b = 0;
+    RT3_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 32, ctx->stream));
+    RT3_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, n, 0, 64, ctx->stream));
+    *temp_bytes = std::max<size_t>(std::max(a, b), 16);
+    if ((rc = ctx->d_rg_ids[0].ensure(ctx, n)) || (rc = ctx->d_rg_ids[1].ensure(ctx, n)) || (rc = ctx->d_rg_keys[0].ensure(ctx, n)) ||
+        (rc = ctx->d_rg_keys[1].ensure(ctx, n)) || (rc = ctx->d_rg_temp.ensure(ctx, *temp_bytes)))
+        return rc;
+    return 0;
+}
+static void clear_spheres(rt3_ctx* ctx) {                           // what rt3_set_spheres(n = 0) leaves
+    ctx->n_sph = 0; ctx->n_direct = 0; ctx->sph_left_out = false;
+    for (int a = 0; a < 3; a++) ctx->sph_centre[a] = 0.0f;
+    ctx->sph = FilterRows();
+    for (DevBuf<float4>* b : { &ctx->d_sph, &ctx->d_sph_mat, &ctx->d_sph_cr }) b->reset();
+    for (DevBuf<uint32_t>* b : { &ctx->d_sph_frag, &ctx->d_sph_frag32, &ctx->d_sph_kind, &ctx->d_sph_slot }) b->reset();
+    ctx->d_sph_invr.reset();
+}
+
+int rt3_set_spheres_device(rt3_ctx* ctx, const void* d_center_radius, const void* d_materials, uint32_t n, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    if (n != 0 && (!d_center_radius || !d_materials)) return fail(ctx, RT3_E_ARG, "center_radius / materials is NULL");
+    if ((uintptr_t)d_center_radius % 16u != 0 || (uintptr_t)d_materials % 4u != 0)
+        return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned (materials: 4-byte)");
+    if (n > 0x7FFFFFFFu) return fail(ctx, RT3_E_ARG, "too many primitives");
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    if (n == 0) { clear_spheres(ctx); return 0; }
+    const float4* const in = (const float4*)d_center_radius;
+    const rt3_material* const mats = (const rt3_material*)d_materials;
+    const dim3 blk(kBlock), one(1);
+    // ---- phase 1: nothing of the scene is touched
+    size_t temp_bytes = 0;
+    if ((rc = build_scratch(ctx, n, true, &temp_bytes))) return rc;
+    uint32_t* const hdr = ctx->d_sb.get();
+    uint32_t* const block_counts = hdr + kSbWords;
+    hipLaunchKernelGGL(k_sb_init, one, dim3(64), 0, stream, hdr);
+    hipLaunchKernelGGL(k_sb_check_radii, build_grid(n), blk, 0, stream, in, n, hdr);
+    hipLaunchKernelGGL(k_sb_check_kinds, build_grid(n), blk, 0, stream, mats, n, hdr);
+    RT3_HIP(hipGetLastError());
+    for (uint32_t axis = 0; axis < 3; axis++) {                     // the filter centre: three medians
+        hipLaunchKernelGGL(k_sb_axis_keys, build_grid(n), blk, 0, stream, in, n, axis, ctx->d_rg_ids[0].get(), hdr);
+        size_t temp = temp_bytes;
+        RT3_HIP(hipcub::DeviceRadixSort::SortKeys(ctx->d_rg_temp.get(), temp, (const uint32_t*)ctx->d_rg_ids[0].get(), ctx->d_rg_ids[1].get(), n, 0, 32, stream));
+        hipLaunchKernelGGL(k_sb_pick_centre, one, one, 0, stream, (const uint32_t*)ctx->d_rg_ids[1].get(), axis, hdr);
+        RT3_HIP(hipGetLastError());
+    }
+    {                                                               // the scene size, the candidates, the four strongest
+        hipLaunchKernelGGL(k_sb_dist_keys, build_grid(n), blk, 0, stream, in, n, (const uint32_t*)hdr, ctx->d_rg_keys[0].get());
+        size_t temp = temp_bytes;
+        RT3_HIP(hipcub::DeviceRadixSort::SortKeys(ctx->d_rg_temp.get(), temp, (const uint64_t*)ctx->d_rg_keys[0].get(), ctx->d_rg_keys[1].get(), n, 0, 64, stream));
+        hipLaunchKernelGGL(k_sb_pick_scene, one, one, 0, stream, (const uint64_t*)ctx->d_rg_keys[1].get(), n, hdr);
+        hipLaunchKernelGGL(k_sb_ratio_keys, build_grid(n), blk, 0, stream, in, n, hdr, ctx->d_rg_keys[0].get());
+        for (uint32_t k = 0; k < 4; k++) hipLaunchKernelGGL(k_sb_top, build_grid(n), blk, 0, stream, (const uint64_t*)ctx->d_rg_keys[0].get(), n, k, hdr);
+        RT3_HIP(hipGetLastError());
+    }
+    const SphInOrder in_order{ in, hdr };
+    hipLaunchKernelGGL(k_compact_count<SphInOrder>, build_grid(n), blk, 0, stream, in_order, n, block_counts, hdr + kSbInOrder);
+    RT3_HIP(hipGetLastError());
+    uint32_t h[kSbFaceError];                                       // the call's one wait for the device
+    RT3_HIP(hipMemcpyAsync(h, hdr, sizeof h, hipMemcpyDeviceToHost, stream));
+    RT3_HIP(hipStreamSynchronize(stream));
+    if (h[kSbBadRadius] != 0xFFFFFFFFu) return fail(ctx, RT3_E_ARG, "sphere " + std::to_string(h[kSbBadRadius]) + " has a non-positive radius");
+    if (h[kSbBadKind]) return fail(ctx, RT3_E_ARG, "unknown material kind");
+    // ---- phase 2
+    ctx->n_sph = 0;                                                 // (no spheres until everything below has been issued)
+    std::memcpy(ctx->sph_centre, h + kSbCentre, sizeof ctx->sph_centre);
+    ctx->n_direct = std::min(h[kSbCand], 4u);
+    for (uint32_t k = 0; k < ctx->n_direct; k++) ctx->direct[k] = 0xFFFFFFFFu - h[kSbBest + 2 * k];     // (the key's low word)
+    std::sort(ctx->direct, ctx->direct + ctx->n_direct);
+    const uint32_t n_in = h[kSbInOrder], n_pos = round_up(n_in, kGroupSph * kSuper), blocks = (n + 31u) / 32u;
+    ctx->sph_left_out = n_in + ctx->n_direct != n;
+    if ((rc = ctx->d_sph_frag.alloc(ctx, (size_t)blocks * 4 * 64 * 4)) || (rc = ctx->d_sph_frag32.alloc(ctx, (size_t)blocks * 2 * 64 * 4)) ||
+        (rc = ctx->d_sph.alloc(ctx, ((size_t)n + 3) / 4 * 4)) || (rc = ctx->d_sph_invr.alloc(ctx, n)) || (rc = ctx->d_sph_mat.alloc(ctx, n)) ||
+        (rc = ctx->d_sph_kind.alloc(ctx, n)) || (rc = ctx->d_sph_cr.alloc(ctx, n)) || (rc = ctx->d_sph_slot.alloc(ctx, n)) ||
+        (rc = alloc_rows(ctx, ctx->sph, n_pos, kGroupSph)))
+        return rc;
+    SphDirect direct{ ctx->n_direct, { 0u, 0u, 0u, 0u } };
+    for (uint32_t k = 0; k < ctx->n_direct; k++) direct.id[k] = ctx->direct[k];
+    hipLaunchKernelGGL(k_build_spheres, build_grid(blocks * 32u), blk, 0, stream, in, mats, n, blocks * 32u, ctx->sph_centre[0], ctx->sph_centre[1],
+                       ctx->sph_centre[2], direct, ctx->d_sph.get(), ctx->d_sph_cr.get(), ctx->d_sph_invr.get(), ctx->d_sph_mat.get(), ctx->d_sph_kind.get(),
+                       (u32x4*)ctx->d_sph_frag.get(), (u32x4*)ctx->d_sph_frag32.get());
+    hipLaunchKernelGGL(k_fill_words, build_grid(n), blk, 0, stream, ctx->d_sph_slot.get(), n, 0xFFFFFFFFu);
+    RT3_HIP(hipGetLastError());
+    if (n_pos) {
+        // the initial order: the usable ids in ascending order, pads behind them; then the regroup's split and the refit's tail
+        hipLaunchKernelGGL(k_fill_words, build_grid(n_pos), blk, 0, stream, ctx->sph.perm.get(), n_pos, 0xFFFFFFFFu);
+        hipLaunchKernelGGL(k_compact_select<SphInOrder>, build_grid(n), blk, 0, stream, in_order, n, (const uint32_t*)block_counts, ctx->sph.perm.get(),
+                           (uint32_t*)nullptr);
+        RT3_HIP(hipGetLastError());
+        if ((rc = regroup_plan(ctx, ctx->rg_sph, n_in, n_pos, n))) return rc;
+        hipLaunchKernelGGL(k_regroup_centres_sph, build_grid(n), blk, 0, stream, in, n, ctx->sph_centre[0], ctx->sph_centre[1], ctx->sph_centre[2],
+                           ctx->d_rg_cen.get());
+        RT3_HIP(hipGetLastError());
+        if ((rc = regroup_order(ctx, ctx->rg_sph, ctx->sph, stream))) return rc;
+        hipLaunchKernelGGL(k_inverse_slots, build_grid(n_pos), blk, 0, stream, (const uint32_t*)ctx->sph.perm.get(), n_pos, ctx->d_sph_slot.get());
+        hipLaunchKernelGGL(k_gather_members, build_grid(n_pos), blk, 0, stream, (const float4*)ctx->d_sph.get(), (const uint32_t*)ctx->sph.perm.get(), n_pos,
+                           ctx->sph.grp.get());
+        RT3_HIP(hipGetLastError());
+        if ((rc = refit_rows(ctx, ctx->sph, nullptr, ctx->sph_centre, stream))) return rc;
+    }
+    if ((rc = leave(ctx, stream))) return rc;
+    ctx->n_sph = n;
+    return 0;
+}
+
+static void clear_mesh(rt3_ctx* ctx) {                              // what rt3_mesh_commit drops before it builds
+    ctx->n_faces = 0; ctx->mesh_in_sync = false; ctx->update_error_pending = false; ctx->tri_bounded = 0;
+    ctx->tri = FilterRows();
+    for (DevBuf<float4>* b : { &ctx->d_tri, &ctx->d_tri_mat, &ctx->d_tri_bound, &ctx->d_tri_rec }) b->reset();
+    ctx->d_tri_kind.reset(); ctx->d_tri_frag.reset(); ctx->d_tri_frag_r.reset(); ctx->d_face_mats_in.reset();
+}
+
+int rt3_set_mesh_device(rt3_ctx* ctx, const void* d_faces, uint32_t n_faces, const void* d_vertices, uint32_t n_vertices, const void* d_face_materials,
+                        void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    if (n_faces != 0 && (!d_faces || !d_vertices)) return fail(ctx, RT3_E_ARG, "faces / vertices is NULL");
+    if (n_vertices != 0 && !d_vertices) return fail(ctx, RT3_E_ARG, "faces / vertices is NULL");
+    if (((uintptr_t)d_faces | (uintptr_t)d_vertices) % 16u != 0 || (uintptr_t)d_face_materials % 4u != 0)
+        return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned (materials: 4-byte)");
+    if (n_faces > 0x7FFFFFFFu) return fail(ctx, RT3_E_ARG, "too many primitives");
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    if (n_faces == 0) { clear_mesh(ctx); ctx->d_gfaces.reset(); ctx->d_verts.reset(); return 0; }
+    const uint32_t n = n_faces, n_pad = (n + 3u) / 4u * 4u, n_frag_rows = (n + 31u) / 32u * 32u;
+    const dim3 blk(kBlock);
+    // ---- phase 1: the new mesh is built in buffers the context does not hold yet — its own copy of the caller's arrays, the render layout, the
+    // vertex box — so that a refusal leaves the scene as it was
+    DevBuf<rt3_gface> gfaces; DevBuf<float4> verts, tri, tri_mat, tri_bound; DevBuf<rt3_material> mats_in; DevBuf<uint32_t> tri_kind, box;
+    DevBuf<u32x4> tri_frag, tri_frag_r;
+    if ((rc = build_scratch(ctx, n, false, nullptr)) || (rc = gfaces.alloc(ctx, n)) || (rc = verts.alloc(ctx, n_vertices)) ||
+        (rc = mats_in.alloc(ctx, d_face_materials ? n : 0)) || (rc = tri.alloc(ctx, (size_t)n * 4)) || (rc = tri_mat.alloc(ctx, n)) ||
+        (rc = tri_kind.alloc(ctx, n)) || (rc = tri_bound.alloc(ctx, n_pad)) || (rc = tri_frag.alloc(ctx, (size_t)n_frag_rows * 8)) ||
+        (rc = tri_frag_r.alloc(ctx, (size_t)n_frag_rows * 8)) || (rc = box.alloc(ctx, 6)))
+        return rc;
+    uint32_t* const hdr = ctx->d_sb.get();
+    uint32_t* const block_counts = hdr + kSbWords;
+    hipLaunchKernelGGL(k_sb_init, dim3(1), dim3(64), 0, stream, hdr);
+    RT3_HIP(hipMemcpyAsync(gfaces, d_faces, (size_t)n * sizeof(rt3_gface), hipMemcpyDeviceToDevice, stream));
+    RT3_HIP(hipMemcpyAsync(verts, d_vertices, (size_t)n_vertices * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+    if (d_face_materials) {
+        RT3_HIP(hipMemcpyAsync(mats_in, d_face_materials, (size_t)n * sizeof(rt3_material), hipMemcpyDeviceToDevice, stream));
+        hipLaunchKernelGGL(k_sb_check_kinds, build_grid(n), blk, 0, stream, (const rt3_material*)mats_in.get(), n, hdr);
+    }
+    RT3_HIP(hipMemsetAsync(box, 0xFF, 3 * sizeof(uint32_t), stream));                 // as rt3_mesh_commit
+    RT3_HIP(hipMemsetAsync(box + 3, 0, 3 * sizeof(uint32_t), stream));
+    if (n_vertices)
+        hipLaunchKernelGGL(k_vertex_box, dim3(std::min<uint32_t>(256u, (n_vertices + kBlock - 1) / kBlock)), blk, 0, stream, (const float4*)verts.get(),
+                           n_vertices, box.get());
+    RT3_HIP(hipGetLastError());
+    for (const float scale : { 1.0f, 0.5f }) {                      // everything, then Mode R's fragments
+        hipLaunchKernelGGL(k_commit_mesh, build_grid(n_frag_rows), blk, 0, stream, (const rt3_gface*)gfaces.get(), (const float4*)verts.get(), n, n_pad,
+                           n_vertices, (const rt3_material*)mats_in.get(), tri.get(), tri_bound.get(), tri_mat.get(), tri_kind.get(), hdr + kSbFaceError,
+                           scale == 1.0f ? tri_frag.get() : tri_frag_r.get(), n_frag_rows, (const uint32_t*)box.get(), scale);
+        RT3_HIP(hipGetLastError());
+    }
+    const FaceInOrder in_order{ tri_bound.get() };
+    hipLaunchKernelGGL(k_compact_count<FaceInOrder>, build_grid(n), blk, 0, stream, in_order, n, block_counts, hdr + kSbInOrder);
+    RT3_HIP(hipGetLastError());
+    uint32_t h[kSbWords], hbox[6];                                  // the call's one wait for the device
+    RT3_HIP(hipMemcpyAsync(h, hdr, sizeof h, hipMemcpyDeviceToHost, stream));
+    RT3_HIP(hipMemcpyAsync(hbox, box, sizeof hbox, hipMemcpyDeviceToHost, stream));
+    RT3_HIP(hipStreamSynchronize(stream));
+    if (h[kSbBadKind]) return fail(ctx, RT3_E_ARG, "unknown material kind");
+    // ---- phase 2: the context takes the new buffers
+    clear_mesh(ctx);
+    ctx->d_gfaces = std::move(gfaces); ctx->d_verts = std::move(verts); ctx->d_face_mats_in = std::move(mats_in);
+    if (h[kSbFaceError]) return fail(ctx, RT3_E_ARG, "a face references a vertex out of range");   // (no mesh, as after rt3_set_mesh)
+    ctx->d_tri = std::move(tri); ctx->d_tri_mat = std::move(tri_mat); ctx->d_tri_bound = std::move(tri_bound); ctx->d_tri_kind = std::move(tri_kind);
+    ctx->d_tri_frag = std::move(tri_frag); ctx->d_tri_frag_r = std::move(tri_frag_r); ctx->d_box = std::move(box);
+    box_centre(hbox, ctx->tri_centre);
+    if ((rc = ctx->d_error.ensure(ctx, 1))) return rc;
+    RT3_HIP(hipMemsetAsync(ctx->d_error, 0, 4, stream));
+    // face_group_order's layout: the bounded faces and their pads, then the others in ascending index order and theirs
+    const uint32_t n_in = h[kSbInOrder], row = kGroupTri * kSuper, pos_in = round_up(n_in, row), n_pos = pos_in + round_up(n - n_in, row);
+    if ((rc = alloc_rows(ctx, ctx->tri, n_pos, kGroupTri)) || (rc = ctx->d_tri_rec.alloc(ctx, (size_t)n_pos * 4))) return rc;
+    const FaceInOrder committed{ ctx->d_tri_bound.get() };
+    hipLaunchKernelGGL(k_fill_words, build_grid(n_pos), blk, 0, stream, ctx->tri.perm.get(), n_pos, 0xFFFFFFFFu);
+    hipLaunchKernelGGL(k_compact_select<FaceInOrder>, build_grid(n), blk, 0, stream, committed, n, (const uint32_t*)block_counts, ctx->tri.perm.get(),
+                       ctx->tri.perm.get() + pos_in);
+    RT3_HIP(hipGetLastError());
+    if (n_in) {
+        if ((rc = regroup_plan(ctx, ctx->rg_tri, n_in, pos_in, n))) return rc;
+        hipLaunchKernelGGL(k_regroup_centres_tri, build_grid(n), blk, 0, stream, (const float4*)ctx->d_tri_bound.get(), n, (const uint32_t*)ctx->d_box.get(),
+                           ctx->d_rg_cen.get());
+        RT3_HIP(hipGetLastError());
+        if ((rc = regroup_order(ctx, ctx->rg_tri, ctx->tri, stream))) return rc;
+    }
+    hipLaunchKernelGGL(k_gather_members, build_grid(n_pos), blk, 0, stream, (const float4*)ctx->d_tri_bound.get(), (const uint32_t*)ctx->tri.perm.get(), n_pos,
+                       ctx->tri.grp.get());
+    hipLaunchKernelGGL(k_gather_face_records, build_grid(n_pos * 4u), blk, 0, stream, (const float4*)ctx->d_tri.get(), (const uint32_t*)ctx->tri.perm.get(),
+                       n_pos, ctx->d_tri_rec.get());
+    RT3_HIP(hipGetLastError());
+    const float no_centre[3] = { 0.0f, 0.0f, 0.0f };
+    if ((rc = refit_rows(ctx, ctx->tri, ctx->d_box, no_centre, stream)) || (rc = leave(ctx, stream))) return rc;
+    ctx->tri_bounded = n_in;
+    ctx->n_faces = n;
+    ctx->mesh_in_sync = true;
+    return 0;
+}
+
+int rt3_debug_sphere_build(rt3_ctx* ctx, float centre[3], uint32_t direct[4], uint32_t* n_direct) {
+    if (!ctx) return RT3_E_ARG;
+    if (!centre || !direct || !n_direct) return fail(ctx, RT3_E_ARG, "centre / direct / n_direct is NULL");
+    if (ctx->n_sph == 0) return fail(ctx, RT3_E_STATE, "no spheres: call rt3_set_spheres first");
+    for (int a = 0; a < 3; a++) centre[a] = ctx->sph_centre[a];
+    for (int k = 0; k < 4; k++) direct[k] = (uint32_t)k < ctx->n_direct ? ctx->direct[k] : 0xFFFFFFFFu;
+    *n_direct = ctx->n_direct;
     return 0;
 }
 

@@ -5,6 +5,7 @@
 // the render path itself (rt3_render*, rt3_render_path*) lives in rt3_device.hip and has no CPU form.
 // Compiled with -ffp-contract=off: the reference's flattening is plain IEEE binary32 with libm double trig.
 #include "rt3.h"
+#include "rt3_sphere_plan.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -431,4 +432,12 @@ extern "C" uint32_t rt3_scene_cornell(uint32_t grid, rt3_gface* faces, float* ve
     out.box(Vec3(0.1f, -1.0f, -3.0f), Vec3(0.7f, -0.4f, -2.4f), gb, white);     // short box
     out.rect(Vec3(-0.25f, 0.998f, -3.25f), Vec3(0.5f, 0, 0), Vec3(0, 0, 0.5f), 1, light);
     return out.n;
+}
+
+// Tests only: what rt3_set_spheres decides before it builds anything (rt3_sphere_plan.hpp, unchanged) — no device, no context.
+extern "C" uint32_t rt3_debug_sphere_plan(const float* center_radius, uint32_t n, float centre[3], uint32_t direct[4]) {
+    if (!centre || !direct || (n != 0 && !center_radius)) return 0;
+    for (int k = 0; k < 4; k++) direct[k] = 0xFFFFFFFFu;
+    sphere_filter_centre(center_radius, n, centre);
+    return sphere_direct_list(center_radius, n, centre, direct);
 }

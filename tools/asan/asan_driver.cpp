@@ -197,6 +197,28 @@ void scenes() {
     CHECK(rt3_random_float(0x3F800000u) >= 0.0f && rt3_random_float(0xFFFFFFFFu) < 1.0f);
 }
 
+// rt3_debug_sphere_plan (csrc/rt3_sphere_plan.hpp): the median centre and the direct list over exact buffers, with the records the plan must
+// skip (non-finite coordinates, a NaN ratio) and the sizes at which its medians index differently
+void sphere_plans() {
+    float centre[3]; uint32_t direct[4];
+    CHECK(rt3_debug_sphere_plan(nullptr, 0, centre, direct) == 0 && centre[0] == 0.0f && centre[1] == 0.0f && centre[2] == 0.0f);
+    const uint32_t n = rt3_scene_weekend(42, nullptr, nullptr, 0);
+    Exact<float> cr(4 * (size_t)n); Exact<rt3_material> m(n);
+    rt3_scene_weekend(42, cr.p, m.p, n);
+    CHECK(rt3_debug_sphere_plan(cr.p, n, centre, direct) == 1 && direct[0] == 0 && direct[1] == 0xFFFFFFFFu);       // the ground sphere
+    for (uint32_t k = 1; k <= 6; k++) {                             // odd and even counts, one sphere
+        Exact<float> part(4 * (size_t)k);
+        std::memcpy(part.p, cr.p + 4, part.bytes());
+        const uint32_t nd = rt3_debug_sphere_plan(part.p, k, centre, direct);
+        CHECK(nd <= 4 && std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]));
+    }
+    Exact<float> odd(4 * 5);
+    const float bad[5][4] = { { NAN, 0, 0, 1 }, { INFINITY, -INFINITY, NAN, 1 }, { 1, 2, 3, INFINITY }, { 1, 2, 3, 0.25f }, { NAN, NAN, NAN, 1 } };
+    std::memcpy(odd.p, bad, odd.bytes());
+    const uint32_t nd = rt3_debug_sphere_plan(odd.p, 5, centre, direct);
+    CHECK(nd <= 4 && centre[0] == 1.0f && centre[1] == 2.0f && centre[2] == 3.0f);
+}
+
 void oracle_loops() {
     // Mode R: a tessellated sphere + a triangle, every row (the caller of the reference loop chooses the rows)
     const float center[3] = { -0.5f, 0.0f, -4.0f }, blue[3] = { 0, 0, 1 }, red[3] = { 1, 0, 0 };
@@ -256,6 +278,7 @@ int main(int argc, const char** argv) {
         tessellation();
         cameras_and_frames();
         scenes();
+        sphere_plans();
         oracle_loops();
         std::printf("rt3_asan selftest: %s (%d failed checks)\n", failures ? "FAILED" : "ok", failures);
         return failures ? 1 : 0;

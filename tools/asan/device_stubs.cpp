@@ -22,6 +22,9 @@ int rt3_update_spheres(rt3_ctx*, const float*, uint32_t) { return RT3_E_DEVICE; 
 int rt3_update_spheres_device(rt3_ctx*, const void*, uint32_t, void*) { return RT3_E_DEVICE; }
 int rt3_update_mesh(rt3_ctx*, const rt3_gface*, const float*, uint32_t) { return RT3_E_DEVICE; }
 int rt3_update_mesh_device(rt3_ctx*, const void*, const void*, uint32_t, void*) { return RT3_E_DEVICE; }
+int rt3_set_spheres_device(rt3_ctx*, const void*, const void*, uint32_t, void*) { return RT3_E_DEVICE; }
+int rt3_set_mesh_device(rt3_ctx*, const void*, uint32_t, const void*, uint32_t, const void*, void*) { return RT3_E_DEVICE; }
+int rt3_debug_sphere_build(rt3_ctx*, float*, uint32_t*, uint32_t*) { return RT3_E_DEVICE; }     // (rt3_debug_sphere_plan is host code: csrc/rt3_host.cpp)
 int rt3_regroup(rt3_ctx*, uint32_t) { return RT3_E_DEVICE; }
 int rt3_regroup_device(rt3_ctx*, uint32_t, void*) { return RT3_E_DEVICE; }
 int rt3_debug_group_order(rt3_ctx*, uint32_t, uint32_t*, uint64_t, uint32_t*) { return RT3_E_DEVICE; }
