@@ -542,7 +542,46 @@ int rt3_denoise_temporal_motion_device(rt3_ctx* ctx, uint32_t width, uint32_t he
                                        const rt3_temporal_params* p, void* d_out_rgba, void* d_out_history, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
- * Host-side scene API   (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)
+ * Radiance along caller-supplied rays   (the Mode-X path loop for rays the caller makes)
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rt3_radiance_params {   /* 24 bytes */
+    uint32_t max_depth;      /* ray casts per path, >= 1, as rt3_params */
+    uint32_t seed;
+    uint32_t flags;          /* 0 or RT3_FLAG_BLACK_BACKGROUND; any other bit: RT3_E_ARG */
+    uint32_t sample_begin;   /* first sample index */
+    uint32_t sample_count;   /* samples per ray, >= 1; sample_begin + sample_count <= 2^31 */
+    float    t_min;          /* finite, >= 0 */
+} rt3_radiance_params;
+/* Path law.  Ray i has key k_i = keys ? keys[i] : i.  For each sample s in [sample_begin, sample_begin + sample_count), one Mode-X path is
+ * traced: it starts at the ray's origin and direction with throughput 1, depth 0 and base = hash2(k_i, hash2(s, seed)); the rest is the path
+ * loop of DESIGN.md 4 with nothing changed: the nearest-hit rule, the materials, the RNG counters 1 + 8 (depth + 1) + k, max_depth, t_min, and
+ * the sky or black on a miss.  L(i, s) is the radiance record a render would store for that sample.
+ * Output.  16 bytes per ray: (S.r / n_s, S.g / n_s, S.b / n_s, 0), S the f32 sum of L(i, s) in sample order starting from +0,
+ * n_s = (float)sample_count, each operation rounded on its own (the render's accumulation followed by rt3_accum_resolve's division).
+ * Defining property.  Take any whole-frame rt3_params P, a pixel (x, y) and a sample s.  Query that (pixel, sample)'s ray from
+ * rt3_camera_rays(cam, P, s, 1) with key y * P.width + x, seed = P.seed, max_depth = P.max_depth, t_min = P.t_min, the BLACK_BACKGROUND bit
+ * of P.flags, sample_begin = s and sample_count = 1: the result is, bit for bit, the radiance rt3_render_path_range(cam, P, s, 1)
+ * accumulates for that pixel.  For a shard, the key is the frame pixel index and the ray is the shard's record.
+ * Valid rays.  rt3_intersect's rule, plus one more: t_max must be +inf.  A finite t_max is reserved and is not silently ignored.  An
+ * invalid ray gets (NaN, NaN, NaN, 0); it is not traced, is not counted in ray_casts, and changes nothing for any other ray.
+ * Arguments.  n <= 2^27 (keys make it seamless for a caller to split a larger batch); n == 0 returns 0 and does nothing; keys may be NULL;
+ * device pointers are 16-byte aligned (rays, output) and 4-byte aligned (keys); the output must not overlap the inputs; RT3_E_ARG and
+ * RT3_E_STATE are returned as for queries.
+ * Context state.  The call never touches the accumulation of a progressive or adaptive render: rt3_render_path_range continues bit-exactly
+ * across it.  Streams and the event chain work as for queries.  The device form never waits for the device and allocates only when the
+ * sample storage must grow.  Samples are batched by rt3_set_sample_storage_cap at 12 B per (ray, sample); the result does not depend on the
+ * batching.
+ * rt3_get_stats afterwards: samples = n * sample_count; ray_casts, prim_tests, launches, trace_ms and the filter counters are summed over
+ * the batches.
+ * Kernel choice is that of a query on the same scene (the RAYS form of that kernel); the switches queries ignore are ignored here too. */
+/* Host arrays, synchronous. */
+int rt3_radiance(rt3_ctx* ctx, const rt3_ray* rays, const uint32_t* keys, uint32_t n, const rt3_radiance_params* p, float* out_rgba);
+/* Device arrays (n rt3_ray and, or NULL, n uint32 in; n float4 out), asynchronous on `stream` (NULL = the context's own stream). */
+int rt3_radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, uint32_t n, const rt3_radiance_params* p, void* d_out_rgba,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Host-side scene API  (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)
  * ------------------------------------------------------------------------------------------------- */
 /* cpu_pre_render_triangle (src/lib/entities/Triangle.cpp:28-76): 1 face, 3 vertices (xyzw). */
 void     rt3_prerender_triangle(const float p1[3], const float p2[3], const float p3[3], const float color[3],

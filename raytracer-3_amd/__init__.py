@@ -126,6 +126,12 @@ class ADAPTIVE_PARAMS(C.Structure):
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("threshold", C.c_float), ("dark", C.c_float)]
 
 
+class RADIANCE_PARAMS(C.Structure):
+    """rt3_radiance_params (24 bytes): ray casts per path, seed, flags (0 or FLAG_BLACK_BACKGROUND), the sample range and t_min."""
+    _fields_ = [("max_depth", C.c_uint32), ("seed", C.c_uint32), ("flags", C.c_uint32), ("sample_begin", C.c_uint32),
+                ("sample_count", C.c_uint32), ("t_min", C.c_float)]
+
+
 class Fatal(RuntimeError):
     """Mirror of CppDebugger::Fatal: every backend error is fatal (Main.cpp:305-308)."""
 
@@ -152,6 +158,7 @@ EXPORTS = [
     "rt3_regroup", "rt3_regroup_device", "rt3_debug_group_order",
     "rt3_render_path_adaptive", "rt3_render_path_adaptive_device",
     "rt3_set_spheres_device", "rt3_set_mesh_device", "rt3_debug_sphere_plan", "rt3_debug_sphere_build",
+    "rt3_radiance", "rt3_radiance_device",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -225,6 +232,7 @@ def lib():
         "rt3_render_path_adaptive": (i32, [vp, vp, vp, vp, vp, vp]), "rt3_render_path_adaptive_device": (i32, [vp, vp, vp, vp, vp, vp, vp]),
         "rt3_set_spheres_device": (i32, [vp, vp, vp, u32, vp]), "rt3_set_mesh_device": (i32, [vp, vp, u32, vp, u32, vp, vp]),
         "rt3_debug_sphere_plan": (u32, [vp, u32, vp, vp]), "rt3_debug_sphere_build": (i32, [vp, vp, vp, vp]),
+        "rt3_radiance": (i32, [vp, vp, vp, u32, vp, vp]), "rt3_radiance_device": (i32, [vp, vp, vp, u32, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -918,6 +926,40 @@ class HipRenderer(Renderer):
         """1 where a ray hits something before its t_max, 0 where not, 0xFFFFFFFF for an invalid ray (rt3_occluded): numpy uint32 for host
         rays, an (N,) int32 tensor for device rays."""
         return self._query(rays, t_min, True)
+
+    # -- radiance along caller-supplied rays (rt3_radiance*; DESIGN.md 4.18) -----------------------------------------
+    def radiance(self, rays, keys=None, samples=1, sample_begin=0, max_depth=8, seed=1, flags=0, t_min=0.001):
+        """Path-traced radiance along every ray (rt3_radiance): the mean over samples [sample_begin, sample_begin + samples) of the Mode-X
+        path that starts with the ray, keyed by keys[i] (default: the ray's index) where a render keys by the pixel index.  numpy RAY /
+        (N, 8) float32 (keys: (N,) uint32) -> float32 (N, 4), (r, g, b, 0), NaN rgb for an invalid ray; a contiguous (N, 8) float32 torch
+        tensor on the GPU (keys: an (N,) int32 tensor on that device) -> an (N, 4) float32 tensor there, computed on
+        torch.cuda.current_stream()."""
+        rp = RADIANCE_PARAMS(max_depth, seed, flags, sample_begin, samples, np.float32(t_min))
+        t = self._torch_rays(rays)
+        if t is not None:
+            import torch
+            n = t.shape[0]
+            if keys is not None and (not type(keys).__module__.startswith("torch") or keys.device != t.device or keys.dtype != torch.int32 or
+                                     keys.dim() != 1 or keys.shape[0] != n or not keys.is_contiguous()):
+                raise Fatal("device keys must be a contiguous (N,) int32 tensor on the rays' device")
+            out = torch.empty((n, 4), dtype=torch.float32, device=t.device)
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+            self.radiance_device(t.data_ptr(), None if keys is None else keys.data_ptr(), n, rp, out.data_ptr(), stream)
+            return out
+        r = self._host_rays(rays)
+        k = None
+        if keys is not None:
+            k = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+            if len(k) != len(r):
+                raise Fatal("keys and rays differ in length")
+        out = np.zeros((len(r), 4), np.float32)
+        self._check(lib().rt3_radiance(self._ctx, _p(r), _p(k), len(r), C.byref(rp), _p(out)))
+        return out
+
+    def radiance_device(self, d_rays_ptr, d_keys_ptr, n, radiance_params, d_out_ptr, stream_ptr=None):
+        """Asynchronous rt3_radiance_device: n rt3_ray at d_rays_ptr, n uint32 keys at d_keys_ptr (or None), n float4 out at d_out_ptr."""
+        self._check(lib().rt3_radiance_device(self._ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_keys_ptr or 0), n, C.byref(radiance_params),
+                                              C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
 
     # -- camera rays, first-hit AOVs, the linear frame (DESIGN.md 4.10) -----------------------------------------------
     def camera_rays(self, camera_c, params, sample_begin=0, sample_count=None):

@@ -95,5 +95,13 @@ __global__ __launch_bounds__(kBlock) void k_resolve_float(const float4* __restri
     const float n = (float)spp;
     out[pix] = make_float4(a.x / n, a.y / n, a.z / n, 0.0f);
 }
+// The same division in place (rt3_radiance*: the caller's output is the sum buffer of its batches; k_resolve_float's __restrict__ forbids the aliasing).
+__global__ __launch_bounds__(kBlock) void k_resolve_float_inplace(float4* sums, uint32_t n_items, uint32_t spp) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_items) return;
+    const float4 a = sums[i];
+    const float n = (float)spp;
+    sums[i] = make_float4(a.x / n, a.y / n, a.z / n, 0.0f);
+}
 
 }  // namespace

@@ -1,7 +1,7 @@
 // rt3_device.hip — the render path on gfx950 (CDNA4): HIP kernels + the device half of the C ABI (include/rt3.h).
 //
 //   rt3_kernel_common.hpp   constants, arithmetic helpers, Mode-X launch arguments, start_path()
-//   rt3_path.hpp            refill (ballot + prefix count, ray stock) and shade_lane()
+//   rt3_path.hpp            refill (ballot + prefix count, ray stock; the caller's rays of queries and of rt3_radiance*) and shade_lane()
 //   rt3_valu_scan.hpp       k_mode_r      Mode R: SequentialRenderer::render + ray_color (src/lib/renderer/SequentialRenderer.cpp:47-109,
 //                                         269-308; GLSL twin src/lib/shaders/raytracer_v3.glsl:91-143,187-203), one thread per pixel,
 //                                         IEEE arithmetic in the reference's order
@@ -15,7 +15,7 @@
 //                           (the reduce pass reduce_v1.glsl never got) — the image is bitwise independent of scheduling and GPU count
 //   rt3_adaptive.hpp        adaptive sampling (rt3_render_path_adaptive*): the reduce pass over an active list, the convergence rule, the
 //                           ordered compaction of the pixels that stay active, the resolves by a pixel's own count
-//   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve
+//   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve (in place for 4.18)
 //   rt3_denoise.hpp         the launchers of the AOV-guided a-trous denoiser, its temporal form and the motion plane (kernels: rt3_denoise.hip)
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
 //   rt3_regroup.hpp         the group order of the multi-level filter again on the device (rt3_regroup*): the median split as stable sorts,
@@ -576,19 +576,23 @@ void launch_primary_lists(const rt3_ctx* ctx, const TraceArgs& A, uint32_t n_gro
     constexpr uint32_t per_block = kBlock / 64;
     hipLaunchKernelGGL(k_primary_lists, dim3((n_groups + per_block - 1) / per_block), dim3(kBlock), 0, stream, A, n_groups, n_blocks, ctx->d_prim_masks.get());
 }
-// (LI: the list form of a render kernel, TraceArgs::active — non-REF renders only)
-template <bool Q, uint32_t L, bool R, bool LI = false>
+// (LI: the list form of a render kernel, TraceArgs::active — non-REF renders only; RY: the rays form, rt3_radiance*)
+template <bool Q, uint32_t L, bool R, bool LI = false, bool RY = false>
 TiledKernel levels_kernel(bool has_tri, bool has_sph, bool ref) {
-    if constexpr (LI) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, false, true> : k_trace_levels<true, false, false, L, R, false, true>)
+    if constexpr (RY) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, false, false, true> : k_trace_levels<true, false, false, L, R, false, false, true>)
+                                     : k_trace_levels<false, true, false, L, R, false, false, true>;
+    else if constexpr (LI) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, false, true> : k_trace_levels<true, false, false, L, R, false, true>)
                                      : k_trace_levels<false, true, false, L, R, false, true>;
     else if constexpr (Q) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, true> : k_trace_levels<true, false, false, L, R, true>) : k_trace_levels<false, true, false, L, R, true>;
     else return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R> : (ref ? k_trace_levels<true, false, true, L, R> : k_trace_levels<true, false, false, L, R>))
                         : k_trace_levels<false, true, false, L, R>;
 }
-template <bool Q, bool RES, bool LI = false>
+template <bool Q, bool RES, bool LI = false, bool RY = false>
 TiledKernel grouped_kernel(bool has_tri, bool has_sph, bool ref) {
     constexpr uint32_t GT = kGroupTri, GS = kGroupSph, SUP = kSuper;
-    if constexpr (LI) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, false, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, false, true>)
+    if constexpr (RY) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, false, false, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, false, false, true>)
+                                     : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES, false, false, true>;
+    else if constexpr (LI) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, false, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, false, true>)
                                      : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES, false, true>;
     else if constexpr (Q) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, true>)
                                     : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES, true>;
@@ -597,14 +601,16 @@ TiledKernel grouped_kernel(bool has_tri, bool has_sph, bool ref) {
 }
 // Fills A's filter fields and T.  ref: RT3_FLAG_REFERENCE_PRIMARY (renders); ref_brute: REF with a camera only the brute-force kernel serves.
 // list: the list form of the kernel a plain render (no ref, no query) would take, strip lists off (the later rounds of an adaptive render).
-int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query, TracePlan& T, bool list = false) {
+// rays: the rays form (rt3_radiance*) of the kernel a QUERY would take on this scene — the switches queries ignore are ignored — shading as a render;
+// A.q_rays is the caller's to set (its slot is the strip lists': they are off).
+int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query, TracePlan& T, bool list = false, bool rays = false) {
     const bool has_tri = ctx->n_faces > 0, has_sph = ctx->n_sph > 0;
     const bool brute = ctx->force_brute || getenv("RT3_BRUTE") || ref_brute;
-    const bool use_mfma = !brute && (query || !getenv("RT3_NO_MFMA"));
+    const bool use_mfma = !brute && (query || rays || !getenv("RT3_NO_MFMA"));
     const bool mfma_single = use_mfma && !has_tri && has_sph && ctx->n_sph <= kMfmaSphMax && !getenv("RT3_FORCE_TILED");   // (A/B knob)
-    const bool single_k64 = !query && mfma_single && getenv("RT3_MFMA_K64") != nullptr;
+    const bool single_k64 = !query && !rays && mfma_single && getenv("RT3_MFMA_K64") != nullptr;
     const bool sph_lds = has_sph && ctx->n_sph <= kSphLdsMax;
-    const bool grouped = kGroupTri > 1 && kGroupSph > 1 && (query || (!ctx->force_flat && !getenv("RT3_NO_GROUPS")));
+    const bool grouped = kGroupTri > 1 && kGroupSph > 1 && (query || rays || (!ctx->force_flat && !getenv("RT3_NO_GROUPS")));
     A.n_tri_rows = grouped ? ctx->tri.n_groups : ctx->n_faces;
     A.n_sph_rows = grouped ? ctx->sph.n_groups : ctx->n_sph;
     A.sph_grp = ctx->sph.grp; A.sph_perm = ctx->sph.perm; A.tri_grp = ctx->tri.grp; A.tri_perm = ctx->tri.perm; A.tri_rec = ctx->d_tri_rec;
@@ -614,21 +620,21 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
     bool resident = false;
     uint32_t levels = 0;                                            // k_trace_levels: 3 | 4
     if (brute) {
-        T.plain = query ? k_trace_brute<false, true> : ref ? k_trace_brute<true> : list ? k_trace_brute<false, false, true> : k_trace_brute<false>;
+        T.plain = query ? k_trace_brute<false, true> : rays ? k_trace_brute<false, false, false, true> : ref ? k_trace_brute<true> : list ? k_trace_brute<false, false, true> : k_trace_brute<false>;
     } else if (mfma_single) {
         // k_trace_mfma32 (K = 32 form, pair list); RT3_MFMA_K64=1: k_trace_mfma, round 1's K = 64 form on v_mfma_f32_32x32x16_bf16 (A/B reference)
         T.lds = single_k64 ? (size_t)T.mfma_blocks * (4096 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes
                            : (size_t)T.mfma_blocks * (2048 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes + (size_t)kMB * 8 + (size_t)(kMB / 64) * kPairCap * 4;
         if (!single_k64 && !query && RT3_CTR_TABLE) T.lds += kCtrTableBytes;       // the render forms' counter-hash table (shade_lane)
         T.block = kMB;
-        T.single = single_k64 ? (list ? k_trace_mfma<true> : k_trace_mfma<>) : query ? k_trace_mfma32<true> : list ? k_trace_mfma32<false, true> : k_trace_mfma32<>;
+        T.single = single_k64 ? (list ? k_trace_mfma<true> : k_trace_mfma<>) : query ? k_trace_mfma32<true> : rays ? k_trace_mfma32<false, false, true> : list ? k_trace_mfma32<false, true> : k_trace_mfma32<>;
         T.frag_a = (const u32x4*)(single_k64 ? ctx->d_sph_frag.get() : ctx->d_sph_frag32.get());
         if (!query && !single_k64) {
             T.filter_counted = true;
             const char* on = getenv("RT3_PRIMARY_LISTS"); const char* cap = getenv("RT3_PRIMARY_LIST_MAX");
-            A.prim_masks = nullptr;                                 // (the slot held the face bounds' address: none in a sphere-only scene)
+            if (!rays) A.prim_masks = nullptr;                      // (the slot held the face bounds' address: none in a sphere-only scene; rays: it is q_rays' slot)
             A.prim_list_max = 0;
-            if (!list && !(on && atoi(on) == 0)) {             // (a list's groups of 64 are not consecutive pixels: no strip lists)
+            if (!list && !rays && !(on && atoi(on) == 0)) {             // (a list's groups of 64 are not consecutive pixels: no strip lists)
                 T.list_groups = (A.npix + 63u) / 64u;
                 int rc_;
                 if ((rc_ = ctx->d_prim_masks.ensure(ctx, (size_t)T.list_groups * T.mfma_blocks))) return rc_;
@@ -655,6 +661,8 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
             A.tri_topb = levels == 4 ? ctx->tri.srowb : ctx->tri.rowb; A.sph_topb = levels == 4 ? ctx->sph.srowb : ctx->sph.rowb;
             if (query) T.tiled = levels == 4 ? (resident ? levels_kernel<true, 4, true>(has_tri, has_sph, ref) : levels_kernel<true, 4, false>(has_tri, has_sph, ref))
                                              : (resident ? levels_kernel<true, 3, true>(has_tri, has_sph, ref) : levels_kernel<true, 3, false>(has_tri, has_sph, ref));
+            else if (rays) T.tiled = levels == 4 ? (resident ? levels_kernel<false, 4, true, false, true>(has_tri, has_sph, ref) : levels_kernel<false, 4, false, false, true>(has_tri, has_sph, ref))
+                                                 : (resident ? levels_kernel<false, 3, true, false, true>(has_tri, has_sph, ref) : levels_kernel<false, 3, false, false, true>(has_tri, has_sph, ref));
             else if (list) T.tiled = levels == 4 ? (resident ? levels_kernel<false, 4, true, true>(has_tri, has_sph, ref) : levels_kernel<false, 4, false, true>(has_tri, has_sph, ref))
                                                  : (resident ? levels_kernel<false, 3, true, true>(has_tri, has_sph, ref) : levels_kernel<false, 3, false, true>(has_tri, has_sph, ref));
             else T.tiled = levels == 4 ? (resident ? levels_kernel<false, 4, true>(has_tri, has_sph, ref) : levels_kernel<false, 4, false>(has_tri, has_sph, ref))
@@ -662,8 +670,8 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
             T.lds = lev_lds_fixed(levels, resident) + (resident ? (size_t)top_blocks * 2048u : 0u);
         } else {
             resident = grouped && SUP > 1 && row_blocks <= kResidentBlocks && !getenv("RT3_NO_RESIDENT");      // all rows fit in LDS: no tiles, no barriers
-            if (resident) T.tiled = query ? grouped_kernel<true, true>(has_tri, has_sph, ref) : list ? grouped_kernel<false, true, true>(has_tri, has_sph, ref) : grouped_kernel<false, true>(has_tri, has_sph, ref);
-            else if (grouped) T.tiled = query ? grouped_kernel<true, false>(has_tri, has_sph, ref) : list ? grouped_kernel<false, false, true>(has_tri, has_sph, ref) : grouped_kernel<false, false>(has_tri, has_sph, ref);
+            if (resident) T.tiled = query ? grouped_kernel<true, true>(has_tri, has_sph, ref) : rays ? grouped_kernel<false, true, false, true>(has_tri, has_sph, ref) : list ? grouped_kernel<false, true, true>(has_tri, has_sph, ref) : grouped_kernel<false, true>(has_tri, has_sph, ref);
+            else if (grouped) T.tiled = query ? grouped_kernel<true, false>(has_tri, has_sph, ref) : rays ? grouped_kernel<false, false, false, true>(has_tri, has_sph, ref) : list ? grouped_kernel<false, false, true>(has_tri, has_sph, ref) : grouped_kernel<false, false>(has_tri, has_sph, ref);
             else if (list) T.tiled = has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, 1, 1, 1, false, false, true> : k_trace_mfma_tiled<true, false, false, 1, 1, 1, false, false, true>)
                                              : k_trace_mfma_tiled<false, true, false, 1, 1, 1, false, false, true>;
             else T.tiled = has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false> : (ref ? k_trace_mfma_tiled<true, false, true> : k_trace_mfma_tiled<true, false, false>))
@@ -2443,6 +2451,92 @@ int rt3_motion(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, cons
     RT3_HIP(hipMemcpyAsync(out, dout, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     RT3_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+// ---- Radiance along caller-supplied rays: the rays form of the kernel a query would take on the scene, over the items
+// (sample in batch, ray); the batch loop is rt3_render_path_range_device's with the caller's output as the sum buffer — d_accum and the acc_* state of a
+// progressive or adaptive render are never touched — then the division in place.
+static_assert(sizeof(rt3_radiance_params) == 24, "rt3.h: rt3_radiance_params");
+static int radiance_checks(rt3_ctx* ctx, uint32_t n, const rt3_radiance_params* rp) {
+    if (!rp) return fail(ctx, RT3_E_ARG, "radiance params is NULL");
+    if (!(rp->t_min >= 0.0f) || !(rp->t_min < __builtin_inff())) return fail(ctx, RT3_E_ARG, "t_min must be finite and >= 0");
+    if (rp->flags & ~RT3_FLAG_BLACK_BACKGROUND) return fail(ctx, RT3_E_ARG, "rt3_radiance: flags may only hold RT3_FLAG_BLACK_BACKGROUND");
+    if (rp->max_depth < 1 || rp->sample_count < 1) return fail(ctx, RT3_E_ARG, "max_depth and sample_count must be >= 1");
+    if ((uint64_t)rp->sample_begin + rp->sample_count > (1ull << 31)) return fail(ctx, RT3_E_ARG, "sample_begin + sample_count must be <= 2^31");
+    if (n > (1u << 27)) return fail(ctx, RT3_E_ARG, "at most 2^27 rays per radiance call (split the batch and pass keys)");
+    return 0;
+}
+static int radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, uint32_t n, const rt3_radiance_params* rp, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = radiance_checks(ctx, n, rp);
+    if (rc) return rc;
+    if (n == 0) return 0;
+    if (!d_rays || !d_out) return fail(ctx, RT3_E_ARG, "rays / out_rgba buffer is NULL");
+    if ((uintptr_t)d_rays % 16u != 0 || (uintptr_t)d_out % 16u != 0 || (uintptr_t)d_keys % 4u != 0)
+        return fail(ctx, RT3_E_ARG, "rays and out_rgba must be 16-byte and keys 4-byte aligned");
+    if (ranges_overlap(d_out, (size_t)n * 16u, d_rays, (size_t)n * sizeof(rt3_ray)) || (d_keys && ranges_overlap(d_out, (size_t)n * 16u, d_keys, (size_t)n * 4u)))
+        return fail(ctx, RT3_E_ARG, "out_rgba overlaps the rays or the keys");
+    if ((rc = check_scene(ctx))) return rc;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    ctx->rendered = false;
+    // batch size: per-sample storage of 12 B per (ray, sample), capped (n <= 2^27: at least 15 samples fit the item index)
+    uint32_t batch = (uint32_t)std::min<uint64_t>(rp->sample_count, std::max<uint64_t>(1, ctx->rad_cap_bytes / ((uint64_t)n * sizeof(Rgb))));
+    batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / n);
+    if ((rc = ctx->d_rad.ensure(ctx, (size_t)n * batch))) return rc;
+    TraceArgs A = scene_args(ctx);
+    A.max_depth = rp->max_depth; A.seed = rp->seed; A.flags = rp->flags; A.t_min = rp->t_min;
+    A.npix = n; A.div_npix = make_fastdiv(n);
+    if (!fastdiv_ok(n, 0x7FFFFFFFu)) return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
+    A.rad = ctx->d_rad;
+    TracePlan T;
+    if ((rc = plan_trace(ctx, A, false, false, false, T, false, true))) return rc;
+    A.q_rays = (const float4*)d_rays; A.ray_keys = (const uint32_t*)d_keys;
+    if ((rc = begin_timed(ctx, stream))) return rc;
+    const uint32_t s_end = rp->sample_begin + rp->sample_count;
+    const dim3 ag((n + kBlock - 1) / kBlock), ab(kBlock);
+    for (uint32_t s0 = rp->sample_begin; s0 < s_end; s0 += batch) {
+        const uint32_t ns = std::min(batch, s_end - s0);
+        A.s0 = s0;
+        A.total = n * ns;
+        hipEvent_t a, b;
+        if ((rc = take_event_pair(ctx, &a, &b))) return rc;
+        RT3_HIP(hipMemsetAsync(ctx->d_work, 0, 4, stream));
+        RT3_HIP(hipEventRecord(a, stream));
+        launch_trace(T, A, trace_grid(ctx, T, A.total), stream);
+        RT3_HIP(hipGetLastError());
+        RT3_HIP(hipEventRecord(b, stream));
+        hipLaunchKernelGGL(k_accumulate<false>, ag, ab, 0, stream, ctx->d_rad, (float4*)d_out, (float4*)nullptr, n, ns, s0 == rp->sample_begin ? 1 : 0);
+        RT3_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_resolve_float_inplace, ag, ab, 0, stream, (float4*)d_out, n, rp->sample_count);
+    RT3_HIP(hipGetLastError());
+    return end_timed(ctx, stream, (uint64_t)n * rp->sample_count, &T);
+}
+static int radiance_host(rt3_ctx* ctx, const rt3_ray* rays, const uint32_t* keys, uint32_t n, const rt3_radiance_params* rp, float* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = radiance_checks(ctx, n, rp);
+    if (rc) return rc;
+    if (n == 0) return 0;
+    if (!rays || !out) return fail(ctx, RT3_E_ARG, "rays / out_rgba array is NULL");
+    if ((rc = check_scene(ctx))) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    if ((rc = ctx->stage.ensure(ctx, (size_t)n * 3u + ((size_t)n + 3u) / 4u))) return rc;
+    float4* const d_rays = ctx->stage.get();                        // two float4 per ray, one per result, then the keys
+    float4* const d_out = d_rays + (size_t)n * 2u;
+    uint32_t* const d_keys = keys ? (uint32_t*)(d_out + n) : nullptr;
+    RT3_HIP(hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(rt3_ray), hipMemcpyHostToDevice, ctx->stream));
+    if (keys) RT3_HIP(hipMemcpyAsync(d_keys, keys, (size_t)n * 4u, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = radiance_device(ctx, d_rays, d_keys, n, rp, d_out, ctx->stream))) return rc;
+    RT3_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 16u, hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+int rt3_radiance(rt3_ctx* ctx, const rt3_ray* rays, const uint32_t* keys, uint32_t n, const rt3_radiance_params* p, float* out_rgba) {
+    return radiance_host(ctx, rays, keys, n, p, out_rgba);
+}
+int rt3_radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, uint32_t n, const rt3_radiance_params* p, void* d_out_rgba, void* stream) {
+    return radiance_device(ctx, d_rays, d_keys, n, p, d_out_rgba, stream);
 }
 
 int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {

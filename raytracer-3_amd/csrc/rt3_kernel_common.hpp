@@ -164,7 +164,11 @@ struct TraceArgs {
     // List form of a work item (the later rounds of rt3_render_path_adaptive*): non-null, item j is (sample s0 + j / npix, pixel
     // active[j % npix]) with npix = the length of the list, and the strip lists are off (prim_masks null).  Only the LIST instantiations of the trace
     // kernels read it.  It is the LAST field: every slot above is read by some render form, and a field behind them moves none of them.
-    const uint32_t* active;
+    // Rays form of a work item (rt3_radiance*): item j is (sample s0 + j / npix, ray j % npix of q_rays) with npix = the number of rays;
+    // ray_keys[ray] — or, null, the ray's index — takes the pixel index's place in the path's RNG base.  Only the RAYS instantiations read it, and they
+    // have no list: it shares the list's place.  (A field of its own behind `active` moves no field either, but it moves the kernel arguments that follow
+    // the struct, and the list forms, which load `active` next to them, changed their scalar register allocation: DESIGN.md 5.2l.)
+    union { const uint32_t* active; const uint32_t* ray_keys; };
 };
 
 struct Path {

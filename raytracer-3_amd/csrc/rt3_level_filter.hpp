@@ -37,7 +37,8 @@ static_assert(lev_lds_fixed(3, true) + lev_resident_blocks(3) * 2048u < 160u * 1
               lev_lds_fixed(3, false) < 160u * 1024u && lev_lds_fixed(4, false) < 160u * 1024u, "k_trace_levels: LDS");
 
 // QUERY: the batched ray queries' form (REF false; the nearest-hit key goes to query_sink instead of shading).
-template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t LEVELS, bool RES, bool QUERY = false, bool LIST = false>
+// RAYS: rt3_radiance*'s form (REF false; the refill takes the caller's rays, rays_path, and everything behind it is the render's).
+template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t LEVELS, bool RES, bool QUERY = false, bool LIST = false, bool RAYS = false>
 __global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
     static_assert(LEVELS == 3 || LEVELS == 4, "three or four levels");
     static_assert(kGroupTri == kLevFan && kGroupSph == kLevFan && kSuper == kLevFan, "k_trace_levels: 8 children per node");
@@ -72,6 +73,7 @@ __global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u
 
     for (;;) {
         if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else if constexpr (RAYS) refill_queries<true>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         else refill_lanes<REF, false, LIST>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         const unsigned long long live = __ballot(alive);
         if constexpr (RES) { if (live == 0ull) break; }

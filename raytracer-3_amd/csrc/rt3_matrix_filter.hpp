@@ -1045,7 +1045,8 @@ __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, con
 // at full lane utilisation, the ray operands cost half), but the matrix pipe does half the work and the chip, which throttles under
 // k_trace_mfma's load (2.0-2.2 GHz), holds 2.3-2.4 GHz here — and a kernel bound by vector-ALU issue runs at the clock.
 // QUERY: the batched ray queries' form (refill from the caller's rays, no ray stock; the nearest-hit key goes to query_sink instead of shading).
-template <bool QUERY = false, bool LIST = false>
+// RAYS: rt3_radiance*'s form (the caller's rays through rays_path, no ray stock and no strip lists; shading as in the render form, counter-hash table included).
+template <bool QUERY = false, bool LIST = false, bool RAYS = false>
 __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u32x4* __restrict__ frags, uint32_t n_blocks) {
     extern __shared__ u32x4 lds_dyn[];
     u32x4* s_frag = lds_dyn;                                                   // [n_blocks][2][64]
@@ -1094,6 +1095,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
 
     for (;;) {
         if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else if constexpr (RAYS) refill_queries<true>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         else refill_from_traced_stock<LIST>(A, mirror, lane, alive, P, Q, chunk_next, chunk_end, exhausted, primary_casts, exact, ph_restock);
         RT3_SPHASE(ph_refill)
         const unsigned long long live = __ballot(alive);
@@ -1204,7 +1206,8 @@ constexpr uint32_t kResidentBlocks = (160u * 1024u - kTB * 8u - (kTB / 64u) * kP
 // (one block of headroom: a kernel with any static LDS beside the dynamic request — __syncthreads_or's word, say — is refused at exactly 160 KiB;
 // this variant has none and did launch with 56, profiles/README.md)
 // QUERY: the batched ray queries' form (REF false; the nearest-hit key goes to query_sink instead of shading).
-template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t GT = 1, uint32_t GS = 1, uint32_t SUP = 1, bool RES = false, bool QUERY = false, bool LIST = false>
+// RAYS: rt3_radiance*'s form (REF false; the refill takes the caller's rays, rays_path, and everything behind it is the render's).
+template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t GT = 1, uint32_t GS = 1, uint32_t SUP = 1, bool RES = false, bool QUERY = false, bool LIST = false, bool RAYS = false>
 __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
     static_assert(64 % GT == 0 && 64 % GS == 0, "group sizes must divide the wave");
     static_assert(!RES || (SUP > 1 && RT3_FACE_K32), "resident rows: three-level filter only");
@@ -1244,6 +1247,7 @@ __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, con
     for (;;) {
         // (no ray stock here: a ray cast costs at least one tile scan, start_path is noise beside it, and the stock's 8 registers are needed)
         if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else if constexpr (RAYS) refill_queries<true>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         else refill_lanes<REF, false, LIST>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         const unsigned long long live = __ballot(alive);
         if constexpr (RES) { if (live == 0ull) break; }                           // every wave for itself

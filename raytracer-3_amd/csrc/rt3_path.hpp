@@ -26,12 +26,34 @@ __device__ __forceinline__ bool query_ray(const TraceArgs& A, uint32_t item, Pat
     return ok;
 }
 
+// The rays form of a path kernel (rt3_radiance*): item `item` is sample A.s0 + item / n of ray item % n of the caller's buffer
+// (n = A.npix).  The loader fills the whole Path as start_path() does — origin and direction as they stand in the buffer, throughput 1, light 0, depth 0,
+// base = hash2(key, hash2(s, seed)) with the ray's key in the pixel index's place — so that everything behind the refill is the render's.  Valid rays:
+// query_ray's rule and t_max == +inf (a finite t_max is reserved); an invalid one gets a NaN record in the sample storage and is never traced.
+__device__ __forceinline__ bool rays_path(const TraceArgs& A, uint32_t item, Path& P) {
+    const uint32_t sb = fdiv(item, A.div_npix), ray = item - sb * A.npix;
+    const float4* r = A.q_rays + 2 * (size_t)ray;
+    const float4 a = r[0], b = r[1];
+    const uint32_t key = A.ray_keys ? A.ray_keys[ray] : ray;
+    P.ox = a.x; P.oy = a.y; P.oz = a.z;
+    P.dx = b.x; P.dy = b.y; P.dz = b.z;
+    P.tr = P.tg = P.tb = 1.0f;
+    P.lr = P.lg = P.lb = 0.0f;
+    P.slot = item; P.base = hash2(key, hash2(A.s0 + sb, A.seed)); P.depth = 0;
+    const float dd = dotf(b.x, b.y, b.z, b.x, b.y, b.z);
+    const bool finite = __builtin_isfinite(a.x) & __builtin_isfinite(a.y) & __builtin_isfinite(a.z) &
+                        __builtin_isfinite(b.x) & __builtin_isfinite(b.y) & __builtin_isfinite(b.z);
+    const bool ok = finite && __builtin_fabsf(dd - 1.0f) <= 0x1p-20f && a.w == __builtin_inff();       // (a NaN t_max fails the last test)
+    if (!ok) { const float nan = __builtin_nanf(""); A.rad[item] = Rgb{ nan, nan, nan }; }
+    return ok;
+}
+
 // HAS_TRI / HAS_SPH compile the face loop / sphere loop (and the matching shading) in or out, so that a sphere-only
 // scene does not pay registers or code for the triangle path.
 // Refill: lanes whose path ended take the next samples of the wave's chunk (ballot + prefix count); a chunk of
 // kWorkChunk samples is fetched from the global queue with one atomic when the wave runs dry.
-// QUERY: the items are the caller's rays (query_ray); an invalid one leaves its lane empty (refill_queries fills it again).
-template <bool REF = false, bool QUERY = false, bool LIST = false>
+// QUERY: the items are the caller's rays (query_ray); an invalid one leaves its lane empty (refill_queries fills it again).  RAYS: the same with rays_path.
+template <bool REF = false, bool QUERY = false, bool LIST = false, bool RAYS = false>
 __device__ __forceinline__ void refill_lanes(const TraceArgs& A, uint32_t lane, bool& alive, Path& P, uint32_t& chunk_next,
                                              uint32_t& chunk_end, bool& exhausted) {
     const unsigned long long need = __ballot(!alive);
@@ -55,15 +77,17 @@ __device__ __forceinline__ void refill_lanes(const TraceArgs& A, uint32_t lane, 
         }
         if (item != 0xFFFFFFFFu) {
             if constexpr (QUERY) alive = query_ray(A, item, P);
+            else if constexpr (RAYS) alive = rays_path(A, item, P);
             else { start_path<REF, LIST>(A, item, P); alive = true; }
         }
     }
 }
 // The query forms' refill: until every lane holds a valid ray or the queue is dry, so that invalid rays neither end a wave early (a wave leaves
-// when no lane is alive after a refill) nor leave holes in it.
+// when no lane is alive after a refill) nor leave holes in it.  RAYS: the rays forms' refill, the same loop around rays_path.
+template <bool RAYS = false>
 __device__ __forceinline__ void refill_queries(const TraceArgs& A, uint32_t lane, bool& alive, Path& P, uint32_t& chunk_next, uint32_t& chunk_end,
                                                bool& exhausted) {
-    do refill_lanes<false, true>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+    do refill_lanes<false, !RAYS, false, RAYS>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
     while (__ballot(!alive) != 0ull && !exhausted);
 }
 

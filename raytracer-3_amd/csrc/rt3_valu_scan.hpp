@@ -259,7 +259,8 @@ __global__ __launch_bounds__(kBlock) void k_trace(const TraceArgs A) {
 // camera off the origin (the reference's literal formula then puts the "hit point" off the face's plane, where no bound holds).
 // Scene records are wave-uniform loads through the constant address space (scalar cache); one path per lane, refill by ballot.
 // QUERY: the batched ray queries' arbiter (rt3_intersect* / rt3_occluded* under the same switch): the running best starts at the ray's t_max.
-template <bool REF, bool QUERY = false, bool LIST = false>
+// RAYS: rt3_radiance*'s arbiter (the caller's rays, shaded as a render's: rays_path).
+template <bool REF, bool QUERY = false, bool LIST = false, bool RAYS = false>
 __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
     const uint32_t lane = lane_id();
     Path P;
@@ -274,6 +275,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
 
     for (;;) {
         if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else if constexpr (RAYS) refill_queries<true>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         else refill_lanes<REF, false, LIST>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         if (__ballot(alive) == 0ull) break;
         casts += (unsigned long long)__popcll(__ballot(alive));

@@ -6,11 +6,13 @@
 // output path (later ones ignored), value forms `-W 400`, `-W400`, `--width 400`; exit code 0 after help, -1 on a
 // usage error, -1 on a fatal backend error.  Fixed: `--key=value`, which the reference mis-parses (Main.cpp:110).
 // Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr, --denoise (PFM files),
-// --frames, --orbit and --slide (a sequence, denoised temporally), --adaptive and --counts (--spp as a budget).
+// --frames, --orbit and --slide (a sequence, denoised temporally), --adaptive and --counts (--spp as a budget), --rays and --radiance
+// (path-traced radiance along rays read from a file).
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <limits>
 #include <sstream>
@@ -45,6 +47,7 @@ struct Options {
     float adaptive_threshold = 0.05f;
     uint32_t adaptive_min = 0, adaptive_step = 16;                 // (min 0: not given = min(16, spp))
     std::string counts_path;                                       // --adaptive: the samples per pixel as a 1-channel PFM
+    std::string rays_path, radiance_path;                          // Mode X: rt3_ray records in, their radiance out as a PFM of n x 1
 };
 
 void print_usage(const char* exe) {
@@ -73,6 +76,9 @@ void print_usage(const char* exe) {
               << "\t   --adaptive\tMode X: T[,MIN[,STEP]]: --spp is a budget; MIN samples for every pixel (default: 16), then STEP at a time (default: 16)\n"
               << "\t\t\tfor the pixels whose neighbourhood has not reached a relative standard error of T. Combines with --hdr, --aov, --denoise.\n"
               << "\t   --counts\tWith --adaptive: also write the samples every pixel received to this path as a 1-channel PFM.\n"
+              << "\t   --rays\tMode X, with --radiance: a file of raw little-endian rt3_ray records (32 bytes each: origin, t_max = +inf, unit direction, pad).\n"
+              << "\t   --radiance\tMode X, with --rays: write the path-traced radiance along those rays (--spp samples per ray, --depth, --seed) to this\n"
+              << "\t\t\tpath as a 3-channel PFM, n wide and 1 high.\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -113,7 +119,8 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         const bool known = key == "-f" || key == "--format" || key == "-W" || key == "--width" || key == "-H" || key == "--height" ||
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
-                           key == "--slide" || key == "--adaptive" || key == "--counts" || key == "--regroup";
+                           key == "--slide" || key == "--adaptive" || key == "--counts" || key == "--regroup" ||
+                           key == "--rays" || key == "--radiance";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -177,6 +184,8 @@ int parse_cli(Options& opt, int argc, const char** argv) {
             opt.adaptive = true; opt.adaptive_threshold = (float)t;
         }
         else if (key == "--counts") opt.counts_path = value;
+        else if (key == "--rays") opt.rays_path = value;
+        else if (key == "--radiance") opt.radiance_path = value;
         else if (key == "--regroup") {
             if (!parse_u32(value, "regroup", "Regroup", &opt.regroup)) return -1;
             if (opt.regroup == 0) { std::cerr << "--regroup must be at least 1." << std::endl; return -1; }
@@ -193,6 +202,14 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     }
     if (mode_r && !opt.denoise_path.empty()) {
         std::cerr << "--denoise needs the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
+    if (opt.rays_path.empty() != opt.radiance_path.empty()) {
+        std::cerr << "--rays and --radiance go together: the rays to trace and where their radiance is written." << std::endl;
+        return -1;
+    }
+    if (mode_r && !opt.rays_path.empty()) {
+        std::cerr << "--rays and --radiance need the path tracer (Mode X): pass --spp." << std::endl;
         return -1;
     }
     if (mode_r && opt.adaptive) {
@@ -401,6 +418,19 @@ int main(int argc, const char** argv) {
             const rt3_denoise_params dp{ 5, 128, 4.0f, 1.0f };                     // the defaults of DESIGN.md 4.11
             const std::vector<float> out = renderer.denoise(cam, dp);
             if (rt3_frame_to_pfm(out.data(), w, h, 3, 4, opt.denoise_path.c_str()) != 0) throw Fatal("Could not write '" + opt.denoise_path + "'");
+        }
+        if (!opt.rays_path.empty()) {                                // last: it replaces the render's stats, and touches nothing the outputs above read
+            std::ifstream in(opt.rays_path, std::ios::binary | std::ios::ate);
+            if (!in) throw Fatal("Could not open '" + opt.rays_path + "'");
+            const std::streamoff bytes = in.tellg();
+            if (bytes <= 0 || bytes % (std::streamoff)sizeof(rt3_ray) != 0 || bytes / (std::streamoff)sizeof(rt3_ray) > (std::streamoff)(1u << 27))
+                throw Fatal("'" + opt.rays_path + "' must hold between 1 and 2^27 rt3_ray records of 32 bytes");
+            std::vector<rt3_ray> rays((size_t)(bytes / (std::streamoff)sizeof(rt3_ray)));
+            in.seekg(0);
+            if (!in.read(reinterpret_cast<char*>(rays.data()), bytes)) throw Fatal("Could not read '" + opt.rays_path + "'");
+            const std::vector<float> out = renderer.radiance(rays);
+            if (rt3_frame_to_pfm(out.data(), (uint32_t)rays.size(), 1, 3, 4, opt.radiance_path.c_str()) != 0) throw Fatal("Could not write '" + opt.radiance_path + "'");
+            std::cerr << "radiance: " << rays.size() << " rays x " << path.spp << " samples, " << renderer.stats().ray_casts << " ray casts\n";
         }
     } catch (Fatal& e) {
         std::cerr << "fatal: " << e.what() << std::endl;            // the reference logs and returns -1 (Main.cpp:305-308)

@@ -64,6 +64,8 @@ int rt3_intersect(rt3_ctx*, const rt3_ray*, uint32_t, float, rt3_hit*) { return 
 int rt3_occluded(rt3_ctx*, const rt3_ray*, uint32_t, float, uint32_t*) { return RT3_E_DEVICE; }
 int rt3_intersect_device(rt3_ctx*, const void*, uint32_t, float, void*, void*) { return RT3_E_DEVICE; }
 int rt3_occluded_device(rt3_ctx*, const void*, uint32_t, float, void*, void*) { return RT3_E_DEVICE; }
+int rt3_radiance(rt3_ctx*, const rt3_ray*, const uint32_t*, uint32_t, const rt3_radiance_params*, float*) { return RT3_E_DEVICE; }
+int rt3_radiance_device(rt3_ctx*, const void*, const void*, uint32_t, const rt3_radiance_params*, void*, void*) { return RT3_E_DEVICE; }
 int rt3_camera_rays(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t, uint32_t, rt3_ray*) { return RT3_E_DEVICE; }
 int rt3_camera_rays_device(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t, uint32_t, void*, void*) { return RT3_E_DEVICE; }
 int rt3_render_aov(rt3_ctx*, const rt3_camera*, const rt3_params*, rt3_aov*) { return RT3_E_DEVICE; }

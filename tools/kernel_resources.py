@@ -4,11 +4,11 @@
     hipcc --offload-arch=gfx950 <the Makefile's HIPFLAGS> -Rpass-analysis=kernel-resource-usage ... 2> LOG
 
 (one of the parent commit, one of this tree).  Kernels are matched by their demangled names; where this tree gave a kernel template one more
-trailing parameter whose value `false` selects the parent's kernel (the LIST flag of the trace kernels), that argument is dropped first, so the
-dense instantiation is compared with the kernel it was.  Prints one line per kernel, `a -> b` where a figure changed, NEW for kernels the parent
+trailing parameter whose value `false` selects the parent's kernel (the RAYS flag of the trace kernels, as the LIST flag before it), that argument is
+dropped first, so the existing instantiation is compared with the kernel it was.  Prints one line per kernel, `a -> b` where a figure changed, NEW for kernels the parent
 does not have, and ends with the number of existing kernels that gained scratch or lost occupancy (exit code 1 if there is one).
 
-    python tools/kernel_resources.py PARENT.log TREE.log > profiles/adaptive_kernel_resources.log
+    python tools/kernel_resources.py PARENT.log TREE.log > profiles/radiance_kernel_resources.log
 """
 import re
 import shutil
@@ -16,18 +16,19 @@ import subprocess
 import sys
 
 KEYS = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]"]
-# template arguments of the trace kernels in the parent: one more, `false`, is this tree's LIST flag
-PARENT_ARGS = {"k_trace_mfma32": 1, "k_trace_mfma_tiled": 8, "k_trace_levels": 6, "k_trace": 4, "k_trace_brute": 2, "k_trace_mfma": 0}
+# template arguments of the trace kernels in the parent: one more, `false`, is this tree's RAYS flag (the kernels with a query twin; the VALU k_trace and
+# the K = 64 k_trace_mfma have no rays form and keep their parameter lists)
+PARENT_ARGS = {"k_trace_mfma32": 2, "k_trace_mfma_tiled": 9, "k_trace_levels": 7, "k_trace_brute": 3}
 
 
 def parse(path):
     out, cur = {}, None
     for line in open(path, errors="replace"):
-        m = re.search(r"remark: Function Name: (\S+)", line)
+        m = re.search(r"remark: (?:\S+:\d+:\d+: )?Function Name: (\S+)", line)       # (the location comes before or after "remark:", by compiler version)
         if m:
             cur = out.setdefault(m.group(1), {})
             continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+): (\S+) \[-Rpass", line)
+        m = re.search(r"remark:\s+(?:\S+:\d+:\d+:\s+)?([A-Za-z \[\]/]+): (\S+) \[-Rpass", line)
         if m and cur is not None:
             cur[m.group(1).strip()] = m.group(2)
     return out
