@@ -1,18 +1,18 @@
 // rt3_aov.hpp — first-hit AOVs (rt3_render_aov*), Mode X's camera rays as rt3_ray records (rt3_camera_rays*) and the
 // linear float resolve of the accumulation (rt3_accum_resolve*).  None of these kernels traces: the AOV pass runs k_camera_rays, then the
-// query form of the trace kernel Mode X would take (plan_trace(..., query = true)) on that buffer, then k_aov_accumulate.
+// query form of the trace kernel Mode X would take (plan_trace with Form::Query) on that buffer, then k_aov_accumulate.
 // Part of rt3_device.hip (one translation unit, gfx950 only); included from there, in this order.
 #pragma once
 
 namespace {
 
 // Item k of the batch (sample s0 + k / npix, owned pixel k % npix) -> its primary ray, bit for bit the ray Mode X casts first
-// (start_path<false>): rays[2 k] = (origin, +inf), rays[2 k + 1] = (unit direction, 0).  Two 16-byte stores per ray.
+// (start_path<Form::Render>): rays[2 k] = (origin, +inf), rays[2 k + 1] = (unit direction, 0).  Two 16-byte stores per ray.
 __global__ __launch_bounds__(kBlock) void k_camera_rays(const TraceArgs A, float4* __restrict__ rays) {
     const uint32_t item = blockIdx.x * kBlock + threadIdx.x;
     if (item >= A.total) return;
     Path P;
-    start_path<false>(A, item, P);
+    start_path<Form::Render>(A, item, P);
     float4* r = rays + 2 * (size_t)item;
     r[0] = make_float4(P.ox, P.oy, P.oz, __builtin_inff());
     r[1] = make_float4(P.dx, P.dy, P.dz, 0.0f);

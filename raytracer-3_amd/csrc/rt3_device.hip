@@ -545,12 +545,12 @@ int path_args(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t
     return 0;
 }
 
-// ---- which trace kernel: ONE rule for Mode-X renders and batched ray queries (QUERY: the query form of the same kernel)
+// ---- which trace kernel: ONE rule for every form (Form, rt3_kernel_common.hpp; the table of forms and families: DESIGN.md 5.2m)
 //   brute         every ray against every primitive (debug switch / RT3_BRUTE=1; REFERENCE_PRIMARY with a camera off the origin or a lens)
 //   mfma_single   sphere scenes of <= 512 spheres, everything in LDS (the bench kernel)
 //   mfma tiled    every other scene
 //   valu          RT3_NO_MFMA=1: the vector-ALU scans (A/B reference; renders only)
-// Queries have no form of the VALU kernels, of K = 64, of the flat filter or of REF: they ignore those switches (rt3.h).
+// Queries and rays have no form of the VALU kernels, of K = 64 or of the flat filter: they ignore those switches (rt3.h).
 using TraceKernel = void (*)(const TraceArgs);
 using TiledKernel = void (*)(const TraceArgs, const u32x4*, const u32x4*);
 using SingleKernel = void (*)(const TraceArgs, const u32x4*, uint32_t);
@@ -576,34 +576,63 @@ void launch_primary_lists(const rt3_ctx* ctx, const TraceArgs& A, uint32_t n_gro
     constexpr uint32_t per_block = kBlock / 64;
     hipLaunchKernelGGL(k_primary_lists, dim3((n_groups + per_block - 1) / per_block), dim3(kBlock), 0, stream, A, n_groups, n_blocks, ctx->d_prim_masks.get());
 }
-// (LI: the list form of a render kernel, TraceArgs::active — non-REF renders only; RY: the rays form, rt3_radiance*)
-template <bool Q, uint32_t L, bool R, bool LI = false, bool RY = false>
-TiledKernel levels_kernel(bool has_tri, bool has_sph, bool ref) {
-    if constexpr (RY) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, false, false, true> : k_trace_levels<true, false, false, L, R, false, false, true>)
-                                     : k_trace_levels<false, true, false, L, R, false, false, true>;
-    else if constexpr (LI) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, false, true> : k_trace_levels<true, false, false, L, R, false, true>)
-                                     : k_trace_levels<false, true, false, L, R, false, true>;
-    else if constexpr (Q) return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R, true> : k_trace_levels<true, false, false, L, R, true>) : k_trace_levels<false, true, false, L, R, true>;
-    else return has_tri ? (has_sph ? k_trace_levels<true, true, false, L, R> : (ref ? k_trace_levels<true, false, true, L, R> : k_trace_levels<true, false, false, L, R>))
-                        : k_trace_levels<false, true, false, L, R>;
+// The instantiation of each kernel family for a form and a scene.  by_scene writes the face / sphere choice once: pick(HAS_TRI, HAS_SPH) as
+// integral constants; RenderRef exists for face-only scenes alone.  A (form, family) pair that does not exist is not instantiated (the kernels'
+// static_asserts would refuse it): the answer is nullptr, which plan_trace reports as an internal error.
+template <Form F, class Pick>
+auto by_scene(bool has_tri, bool has_sph, Pick pick) -> decltype(pick(std::true_type{}, std::false_type{})) {
+    if constexpr (F == Form::RenderRef) return has_tri && !has_sph ? pick(std::true_type{}, std::false_type{}) : nullptr;
+    else return has_tri ? (has_sph ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{})) : pick(std::false_type{}, std::true_type{});
 }
-template <bool Q, bool RES, bool LI = false, bool RY = false>
-TiledKernel grouped_kernel(bool has_tri, bool has_sph, bool ref) {
-    constexpr uint32_t GT = kGroupTri, GS = kGroupSph, SUP = kSuper;
-    if constexpr (RY) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, false, false, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, false, false, true>)
-                                     : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES, false, false, true>;
-    else if constexpr (LI) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, false, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, false, true>)
-                                     : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES, false, true>;
-    else if constexpr (Q) return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES, true> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES, true>)
-                                    : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES, true>;
-    else return has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, GT, GS, SUP, RES> : (ref ? k_trace_mfma_tiled<true, false, true, GT, 1, SUP, RES> : k_trace_mfma_tiled<true, false, false, GT, 1, SUP, RES>))
-                        : k_trace_mfma_tiled<false, true, false, 1, GS, SUP, RES>;
+template <Form F>
+TiledKernel levels_kernel(uint32_t levels, bool resident, bool has_tri, bool has_sph) {
+    return by_scene<F>(has_tri, has_sph, [=](auto tri, auto sph) -> TiledKernel {
+        constexpr bool T = tri(), S = sph();
+        return levels == 4 ? (resident ? k_trace_levels<T, S, F, 4, true> : k_trace_levels<T, S, F, 4, false>)
+                           : (resident ? k_trace_levels<T, S, F, 3, true> : k_trace_levels<T, S, F, 3, false>);
+    });
 }
-// Fills A's filter fields and T.  ref: RT3_FLAG_REFERENCE_PRIMARY (renders); ref_brute: REF with a camera only the brute-force kernel serves.
-// list: the list form of the kernel a plain render (no ref, no query) would take, strip lists off (the later rounds of an adaptive render).
-// rays: the rays form (rt3_radiance*) of the kernel a QUERY would take on this scene — the switches queries ignore are ignored — shading as a render;
-// A.q_rays is the caller's to set (its slot is the strip lists': they are off).
-int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query, TracePlan& T, bool list = false, bool rays = false) {
+template <Form F>
+TiledKernel tiled_kernel(bool grouped, bool resident, bool has_tri, bool has_sph) {
+    return by_scene<F>(has_tri, has_sph, [=](auto tri, auto sph) -> TiledKernel {
+        constexpr bool T = tri(), S = sph();
+        constexpr uint32_t GT = T ? kGroupTri : 1u, GS = S ? kGroupSph : 1u;       // (a pass over one kind of primitive alone keeps the other's group size 1)
+        if (resident) return k_trace_mfma_tiled<T, S, F, GT, GS, kSuper, true>;
+        if (grouped) return k_trace_mfma_tiled<T, S, F, GT, GS, kSuper, false>;
+        if constexpr (F == Form::Query || F == Form::Rays) return nullptr;         // the flat filter
+        else return k_trace_mfma_tiled<T, S, F, 1, 1, 1, false>;
+    });
+}
+template <Form F>
+SingleKernel single_kernel(bool k64) {
+    if constexpr (F == Form::Render || F == Form::List) return k64 ? k_trace_mfma<F> : k_trace_mfma32<F>;
+    else if constexpr (F == Form::RenderRef) return nullptr;
+    else return k64 ? nullptr : k_trace_mfma32<F>;
+}
+template <Form F>
+TraceKernel valu_kernel(bool sph_lds, bool has_tri, bool has_sph) {
+    if constexpr (F == Form::Query || F == Form::Rays) return nullptr;
+    else return by_scene<F>(has_tri, has_sph, [=](auto tri, auto sph) -> TraceKernel {
+        constexpr bool T = tri(), S = sph();
+        return S && sph_lds ? k_trace<T, S, /* SPH_LDS */ S, F> : k_trace<T, S, false, F>;
+    });
+}
+// fn(std::integral_constant<Form, form>): the run-time form as a compile-time one.
+template <class Fn>
+void with_form(Form form, Fn fn) {
+    switch (form) {
+    case Form::Render: return fn(std::integral_constant<Form, Form::Render>{});
+    case Form::RenderRef: return fn(std::integral_constant<Form, Form::RenderRef>{});
+    case Form::Query: return fn(std::integral_constant<Form, Form::Query>{});
+    case Form::List: return fn(std::integral_constant<Form, Form::List>{});
+    case Form::Rays: return fn(std::integral_constant<Form, Form::Rays>{});
+    }
+}
+// Fills A's filter fields and T for the form `form` (rt3_kernel_common.hpp).  ref_brute: a RenderRef with a camera only the brute-force kernel serves.
+// List: the kernel a Render would take, strip lists off.  Rays: the kernel a Query would take on this scene — the switches queries ignore are ignored —
+// shading as a render; A.q_rays is the caller's to set (its slot is the strip lists': they are off).
+int plan_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, TracePlan& T) {
+    const bool query = form == Form::Query, list = form == Form::List, rays = form == Form::Rays;
     const bool has_tri = ctx->n_faces > 0, has_sph = ctx->n_sph > 0;
     const bool brute = ctx->force_brute || getenv("RT3_BRUTE") || ref_brute;
     const bool use_mfma = !brute && (query || rays || !getenv("RT3_NO_MFMA"));
@@ -619,15 +648,12 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
     T.mfma_blocks = (ctx->n_sph + 31u) / 32u;
     bool resident = false;
     uint32_t levels = 0;                                            // k_trace_levels: 3 | 4
-    if (brute) {
-        T.plain = query ? k_trace_brute<false, true> : rays ? k_trace_brute<false, false, false, true> : ref ? k_trace_brute<true> : list ? k_trace_brute<false, false, true> : k_trace_brute<false>;
-    } else if (mfma_single) {
+    if (mfma_single) {
         // k_trace_mfma32 (K = 32 form, pair list); RT3_MFMA_K64=1: k_trace_mfma, round 1's K = 64 form on v_mfma_f32_32x32x16_bf16 (A/B reference)
         T.lds = single_k64 ? (size_t)T.mfma_blocks * (4096 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes
                            : (size_t)T.mfma_blocks * (2048 + 32 * (16 + 16 + 4 + 4)) + (size_t)kBitmapBytes + (size_t)kMB * 8 + (size_t)(kMB / 64) * kPairCap * 4;
         if (!single_k64 && !query && RT3_CTR_TABLE) T.lds += kCtrTableBytes;       // the render forms' counter-hash table (shade_lane)
         T.block = kMB;
-        T.single = single_k64 ? (list ? k_trace_mfma<true> : k_trace_mfma<>) : query ? k_trace_mfma32<true> : rays ? k_trace_mfma32<false, false, true> : list ? k_trace_mfma32<false, true> : k_trace_mfma32<>;
         T.frag_a = (const u32x4*)(single_k64 ? ctx->d_sph_frag.get() : ctx->d_sph_frag32.get());
         if (!query && !single_k64) {
             T.filter_counted = true;
@@ -659,37 +685,27 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, bool ref, bool ref_brute, bool query,
             resident = !no_res_env && top_blocks <= lev_resident_blocks(levels);
             A.n_tri_top = levels == 4 ? ctx->tri.n_super : ctx->tri.n_groups; A.n_sph_top = levels == 4 ? ctx->sph.n_super : ctx->sph.n_groups;
             A.tri_topb = levels == 4 ? ctx->tri.srowb : ctx->tri.rowb; A.sph_topb = levels == 4 ? ctx->sph.srowb : ctx->sph.rowb;
-            if (query) T.tiled = levels == 4 ? (resident ? levels_kernel<true, 4, true>(has_tri, has_sph, ref) : levels_kernel<true, 4, false>(has_tri, has_sph, ref))
-                                             : (resident ? levels_kernel<true, 3, true>(has_tri, has_sph, ref) : levels_kernel<true, 3, false>(has_tri, has_sph, ref));
-            else if (rays) T.tiled = levels == 4 ? (resident ? levels_kernel<false, 4, true, false, true>(has_tri, has_sph, ref) : levels_kernel<false, 4, false, false, true>(has_tri, has_sph, ref))
-                                                 : (resident ? levels_kernel<false, 3, true, false, true>(has_tri, has_sph, ref) : levels_kernel<false, 3, false, false, true>(has_tri, has_sph, ref));
-            else if (list) T.tiled = levels == 4 ? (resident ? levels_kernel<false, 4, true, true>(has_tri, has_sph, ref) : levels_kernel<false, 4, false, true>(has_tri, has_sph, ref))
-                                                 : (resident ? levels_kernel<false, 3, true, true>(has_tri, has_sph, ref) : levels_kernel<false, 3, false, true>(has_tri, has_sph, ref));
-            else T.tiled = levels == 4 ? (resident ? levels_kernel<false, 4, true>(has_tri, has_sph, ref) : levels_kernel<false, 4, false>(has_tri, has_sph, ref))
-                                       : (resident ? levels_kernel<false, 3, true>(has_tri, has_sph, ref) : levels_kernel<false, 3, false>(has_tri, has_sph, ref));
             T.lds = lev_lds_fixed(levels, resident) + (resident ? (size_t)top_blocks * 2048u : 0u);
         } else {
             resident = grouped && SUP > 1 && row_blocks <= kResidentBlocks && !getenv("RT3_NO_RESIDENT");      // all rows fit in LDS: no tiles, no barriers
-            if (resident) T.tiled = query ? grouped_kernel<true, true>(has_tri, has_sph, ref) : rays ? grouped_kernel<false, true, false, true>(has_tri, has_sph, ref) : list ? grouped_kernel<false, true, true>(has_tri, has_sph, ref) : grouped_kernel<false, true>(has_tri, has_sph, ref);
-            else if (grouped) T.tiled = query ? grouped_kernel<true, false>(has_tri, has_sph, ref) : rays ? grouped_kernel<false, false, false, true>(has_tri, has_sph, ref) : list ? grouped_kernel<false, false, true>(has_tri, has_sph, ref) : grouped_kernel<false, false>(has_tri, has_sph, ref);
-            else if (list) T.tiled = has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false, 1, 1, 1, false, false, true> : k_trace_mfma_tiled<true, false, false, 1, 1, 1, false, false, true>)
-                                             : k_trace_mfma_tiled<false, true, false, 1, 1, 1, false, false, true>;
-            else T.tiled = has_tri ? (has_sph ? k_trace_mfma_tiled<true, true, false> : (ref ? k_trace_mfma_tiled<true, false, true> : k_trace_mfma_tiled<true, false, false>))
-                                   : k_trace_mfma_tiled<false, true, false>;
             T.lds = resident ? (size_t)row_blocks * 2048u + (size_t)kBmBlocksRes * kTB * 4u + (size_t)kTB * 8u + (size_t)(kTB / 64u) * kPairCap * 4u * 3u : kTraceTiledLdsBytes;
         }
         T.block = kTB;
         if (levels == 4) { T.frag_a = ctx->tri.sfrag; T.frag_b = ctx->sph.sfrag; }
         else { T.frag_a = grouped ? ctx->tri.gfrag : ctx->d_tri_frag; T.frag_b = grouped ? ctx->sph.gfrag.get() : (const u32x4*)ctx->d_sph_frag32.get(); }
-    } else {
+    } else if (!brute) {
         T.lds = sph_lds ? (size_t)ctx->n_sph * sizeof(float4) : 0;
-        if (list) T.plain = has_tri ? (has_sph ? (sph_lds ? k_trace<true, true, true, false, true> : k_trace<true, true, false, false, true>) : k_trace<true, false, false, false, true>)
-                                    : (sph_lds ? k_trace<false, true, true, false, true> : k_trace<false, true, false, false, true>);
-        else T.plain = has_tri ? (has_sph ? (sph_lds ? k_trace<true, true, true> : k_trace<true, true, false>)
-                                     : (ref ? k_trace<true, false, false, true> : k_trace<true, false, false>))
-                          : (sph_lds ? k_trace<false, true, true> : k_trace<false, true, false>);
     }
+    with_form(form, [&](auto f) {                                   // the one place a kernel is named: family x form
+        constexpr Form F = decltype(f)::value;
+        if (brute) T.plain = k_trace_brute<F>;
+        else if (mfma_single) T.single = single_kernel<F>(single_k64);
+        else if (levels) T.tiled = levels_kernel<F>(levels, resident, has_tri, has_sph);
+        else if (use_mfma) T.tiled = tiled_kernel<F>(grouped, resident, has_tri, has_sph);
+        else T.plain = valu_kernel<F>(sph_lds, has_tri, has_sph);
+    });
     const void* kptr = T.single ? (const void*)T.single : T.tiled ? (const void*)T.tiled : (const void*)T.plain;
+    if (!kptr) return fail(ctx, RT3_E_DEVICE, "internal: the trace kernel chosen has no such form");
     int rc;
     if ((rc = blocks_per_cu(ctx, kptr, T.block, T.lds, &T.per_cu))) return rc;
     if (T.per_cu < 1) return fail(ctx, RT3_E_DEVICE, "the trace kernel does not fit on a CU");
@@ -715,10 +731,10 @@ void launch_trace(const TracePlan& T, const TraceArgs& A, uint32_t grid, hipStre
     else hipLaunchKernelGGL(T.plain, dim3(grid), dim3(kBlock), T.lds, stream, A);
 }
 
-// The launch half of a batched query: the query form of T over the n rays A.q_rays points to, as one timed launch of the call.
-// rt3_intersect* / rt3_occluded* issue it once, the AOV pass once per sample batch; the caller records ev_begin, clears the counters before
-// the first one and finishes the call (ev_end, ev_acc, the stats fields).
-int issue_query(rt3_ctx* ctx, const TraceArgs& A, const TracePlan& T, uint32_t n, hipStream_t stream) {
+// One timed trace launch of a call: the kernel of T over the n work items A describes (a batch of samples; DESIGN.md 4.9: the rays A.q_rays points to).
+// Renders, the adaptive rounds, rt3_radiance* and the AOV pass issue it once per sample batch, rt3_intersect* / rt3_occluded* once; the caller records
+// ev_begin, clears the counters before the first one and finishes the call (ev_end, ev_acc, the stats fields).
+int issue_trace(rt3_ctx* ctx, const TraceArgs& A, const TracePlan& T, uint32_t n, hipStream_t stream) {
     hipEvent_t a, b;
     int rc;
     if ((rc = take_event_pair(ctx, &a, &b))) return rc;
@@ -1697,7 +1713,7 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     A.rad = ctx->d_rad;
 
     TracePlan T;
-    if ((rc = plan_trace(ctx, A, ref, ref && !(cam_at_origin(cam) && !(p->lens_radius > 0.0f)), false, T))) return rc;
+    if ((rc = plan_trace(ctx, A, ref ? Form::RenderRef : Form::Render, ref && !(cam_at_origin(cam) && !(p->lens_radius > 0.0f)), T))) return rc;
 
     if ((rc = begin_timed(ctx, stream))) return rc;
 #ifdef RT3_PROFILE
@@ -1712,14 +1728,7 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
         const uint32_t ns = std::min(batch, sample_begin + sample_count - s0);
         A.s0 = s0;
         A.total = npix * ns;
-        const uint32_t grid = trace_grid(ctx, T, A.total);
-        hipEvent_t a, b;
-        if ((rc = take_event_pair(ctx, &a, &b))) return rc;
-        RT3_HIP(hipMemsetAsync(ctx->d_work, 0, 4, stream));
-        RT3_HIP(hipEventRecord(a, stream));
-        launch_trace(T, A, grid, stream);
-        RT3_HIP(hipGetLastError());
-        RT3_HIP(hipEventRecord(b, stream));
+        if ((rc = issue_trace(ctx, A, T, A.total, stream))) return rc;
         const dim3 ag((npix + kBlock - 1) / kBlock), ab(kBlock);
         if (var) hipLaunchKernelGGL(k_accumulate<true>, ag, ab, 0, stream, ctx->d_rad, ctx->d_accum, ctx->d_accum_sq, npix, ns, s0 == 0 ? 1 : 0);
         else hipLaunchKernelGGL(k_accumulate<false>, ag, ab, 0, stream, ctx->d_rad, ctx->d_accum, (float4*)nullptr, npix, ns, s0 == 0 ? 1 : 0);
@@ -1811,9 +1820,9 @@ int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const r
     if ((rc = path_args(ctx, cam, p, npix, A))) return rc;
     A.rad = ctx->d_rad;
     TracePlan T, TL;                                                // the dense launch of round 0, the list form of the same kernel for the later rounds
-    if ((rc = plan_trace(ctx, A, false, false, false, T))) return rc;
+    if ((rc = plan_trace(ctx, A, Form::Render, false, T))) return rc;
     TraceArgs AL = A;
-    if ((rc = plan_trace(ctx, AL, false, false, false, TL, true))) return rc;
+    if ((rc = plan_trace(ctx, AL, Form::List, false, TL))) return rc;
     AdaptiveGeom G{ p->width, rows, p->tile_rows, p->tile_index, p->tile_count, A.div_width, A.div_tile_rows };
 
     if ((rc = begin_timed(ctx, stream))) return rc;
@@ -1828,14 +1837,8 @@ int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const r
             const uint32_t ns = std::min(per, s_begin + s_count - s0);
             B.s0 = s0;
             B.total = n_items * ns;
-            hipEvent_t a, b;
             int rc_;
-            if ((rc_ = take_event_pair(ctx, &a, &b))) return rc_;
-            RT3_HIP(hipMemsetAsync(ctx->d_work, 0, 4, stream));
-            RT3_HIP(hipEventRecord(a, stream));
-            launch_trace(P, B, trace_grid(ctx, P, B.total), stream);
-            RT3_HIP(hipGetLastError());
-            RT3_HIP(hipEventRecord(b, stream));
+            if ((rc_ = issue_trace(ctx, B, P, B.total, stream))) return rc_;
             const dim3 ag((n_items + kBlock - 1) / kBlock), ab(kBlock);
             if (active) hipLaunchKernelGGL(k_accumulate_list<true>, ag, ab, 0, stream, ctx->d_rad, active, n_items, ctx->d_accum, ctx->d_accum_sq,
                                            ctx->d_counts, ns, s0 + ns);
@@ -2022,7 +2025,7 @@ static int query_device(rt3_ctx* ctx, const void* d_rays, uint32_t n, float t_mi
     A.total = n;
     A.q_rays = (const float4*)d_rays; A.q_out = d_out; A.q_occluded = occluded ? 1u : 0u;
     TracePlan T;
-    if ((rc = plan_trace(ctx, A, false, false, true, T)) || (rc = begin_timed(ctx, stream)) || (rc = issue_query(ctx, A, T, n, stream))) return rc;
+    if ((rc = plan_trace(ctx, A, Form::Query, false, T)) || (rc = begin_timed(ctx, stream)) || (rc = issue_trace(ctx, A, T, n, stream))) return rc;
     return end_timed(ctx, stream, 0, &T);
 }
 static int query_host(rt3_ctx* ctx, const rt3_ray* rays, uint32_t n, float t_min, void* out, bool occluded) {
@@ -2127,14 +2130,14 @@ int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
     Q.t_min = p->t_min;
     Q.q_rays = ctx->d_arays; Q.q_out = ctx->d_ahits; Q.q_occluded = 0u;
     TracePlan T;
-    if ((rc = plan_trace(ctx, Q, false, false, true, T)) || (rc = begin_timed(ctx, stream))) return rc;
+    if ((rc = plan_trace(ctx, Q, Form::Query, false, T)) || (rc = begin_timed(ctx, stream))) return rc;
     for (uint32_t s0 = 0; s0 < p->spp; s0 += batch) {
         const uint32_t ns = std::min(batch, p->spp - s0);
         A.s0 = s0;
         A.total = Q.total = npix * ns;
         hipLaunchKernelGGL(k_camera_rays, dim3((A.total + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, ctx->d_arays);
         RT3_HIP(hipGetLastError());
-        if ((rc = issue_query(ctx, Q, T, Q.total, stream))) return rc;
+        if ((rc = issue_trace(ctx, Q, T, Q.total, stream))) return rc;
         hipLaunchKernelGGL(k_aov_accumulate, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, (const float4*)ctx->d_arays,
                            (const uint4*)ctx->d_ahits, ctx->d_aacc, npix, ns, s0 == 0 ? 1 : 0);
         RT3_HIP(hipGetLastError());
@@ -2490,7 +2493,7 @@ static int radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys,
     if (!fastdiv_ok(n, 0x7FFFFFFFu)) return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
     A.rad = ctx->d_rad;
     TracePlan T;
-    if ((rc = plan_trace(ctx, A, false, false, false, T, false, true))) return rc;
+    if ((rc = plan_trace(ctx, A, Form::Rays, false, T))) return rc;
     A.q_rays = (const float4*)d_rays; A.ray_keys = (const uint32_t*)d_keys;
     if ((rc = begin_timed(ctx, stream))) return rc;
     const uint32_t s_end = rp->sample_begin + rp->sample_count;
@@ -2499,13 +2502,7 @@ static int radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys,
         const uint32_t ns = std::min(batch, s_end - s0);
         A.s0 = s0;
         A.total = n * ns;
-        hipEvent_t a, b;
-        if ((rc = take_event_pair(ctx, &a, &b))) return rc;
-        RT3_HIP(hipMemsetAsync(ctx->d_work, 0, 4, stream));
-        RT3_HIP(hipEventRecord(a, stream));
-        launch_trace(T, A, trace_grid(ctx, T, A.total), stream);
-        RT3_HIP(hipGetLastError());
-        RT3_HIP(hipEventRecord(b, stream));
+        if ((rc = issue_trace(ctx, A, T, A.total, stream))) return rc;
         hipLaunchKernelGGL(k_accumulate<false>, ag, ab, 0, stream, ctx->d_rad, (float4*)d_out, (float4*)nullptr, n, ns, s0 == rp->sample_begin ? 1 : 0);
         RT3_HIP(hipGetLastError());
     }

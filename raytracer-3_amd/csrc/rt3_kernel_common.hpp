@@ -114,6 +114,14 @@ __device__ __forceinline__ void unit_vector(float xi0, float xi1, float& x, floa
 // Mode X
 // ------------------------------------------------------------------------------------------------------
 struct Rgb { float r, g, b; };   // one radiance record of the sample storage (three dwords: a quarter less HBM traffic than float4)
+// The form of a trace kernel: where its work items come from and where a finished one goes.  One template parameter of every trace kernel and of the
+// refill helpers; each kernel static_asserts the forms it has, plan_trace (rt3_device.hip) is the one place that picks one.
+//   Render     item = (sample, owned pixel) through the camera, shaded into the sample storage: rt3_render_path*, the first round of the adaptive render
+//   RenderRef  the same with RT3_FLAG_REFERENCE_PRIMARY (the reference's unnormalised primary direction; face-only scenes): rt3_render_path*
+//   Query      item = one of the caller's rays, the nearest hit or the occlusion word stored: rt3_intersect*, rt3_occluded*, the AOV pass
+//   List       Render over a list of pixels (TraceArgs::active): the later rounds of rt3_render_path_adaptive*
+//   Rays       item = (sample, one of the caller's rays), shaded as a render's (TraceArgs::ray_keys): rt3_radiance*
+enum class Form : uint32_t { Render, RenderRef, Query, List, Rays };
 // Batched ray queries (the QUERY forms of the trace kernels; rt3_intersect* / rt3_occluded*): item k of a launch is ray k
 // of the caller's rt3_ray[] (q_rays: two float4 per ray, origin, t_max | direction, pad); its result goes to q_out[k], an rt3_hit (16 bytes), or with
 // q_occluded one word.  They share the places of fields only the path kernels read (the VALU scan's face bounds, the sample storage, the render
@@ -238,7 +246,7 @@ __device__ __forceinline__ uint32_t frame_row(const TraceArgs& A, uint32_t local
 
 // sample -> primary ray (raytracer_v4.glsl:190-214 with the jitter in pixel units), unit direction.
 // REF (RT3_FLAG_REFERENCE_PRIMARY): the direction stays unnormalised, as SequentialRenderer.cpp:293 leaves it.
-// LIST: the list form of a work item (TraceArgs::active).  A compile-time flag, not a test of the pointer: the dense kernels' code stays what it was
+// Form::List: the list form of a work item (TraceArgs::active).  A compile-time choice, not a test of the pointer: the dense kernels' code stays what it was
 // (a wave-uniform test cost two of them scratch, profiles/adaptive_kernel_resources.log).
 // start_path_at: the part behind the index arithmetic — item `item` is sample s of the pixel (x, y) of the frame.  HS: hs is hash2(s, A.seed), worked
 // out by the caller (refill_from_traced_stock, once per wave where the 64 items of a restock share their sample).
@@ -281,15 +289,16 @@ __device__ __forceinline__ void start_path_at(const TraceArgs& A, uint32_t item,
     P.lr = P.lg = P.lb = 0.0f;
     P.slot = item; P.base = base; P.depth = 0;
 }
-template <bool REF = false, bool LIST = false>
+template <Form F>
 __device__ __forceinline__ void start_path(const TraceArgs& A, uint32_t item, Path& P) {
+    static_assert(F == Form::Render || F == Form::RenderRef || F == Form::List, "start_path: the forms whose items are samples of pixels");
     const uint32_t sb = fdiv(item, A.div_npix);
     uint32_t pix = item - sb * A.npix;
-    if constexpr (LIST) pix = A.active[pix];
+    if constexpr (F == Form::List) pix = A.active[pix];
     const uint32_t s = A.s0 + sb;
     const uint32_t lrow = fdiv(pix, A.div_width), x = pix - lrow * A.width;
     const uint32_t y = frame_row(A, lrow);
-    start_path_at<REF>(A, item, s, x, y, 0u, P);
+    start_path_at<F == Form::RenderRef>(A, item, s, x, y, 0u, P);
 }
 
 }  // namespace

@@ -36,10 +36,12 @@ __host__ __device__ constexpr uint32_t lev_resident_blocks(uint32_t levels) { re
 static_assert(lev_lds_fixed(3, true) + lev_resident_blocks(3) * 2048u < 160u * 1024u && lev_lds_fixed(4, true) + lev_resident_blocks(4) * 2048u < 160u * 1024u &&
               lev_lds_fixed(3, false) < 160u * 1024u && lev_lds_fixed(4, false) < 160u * 1024u, "k_trace_levels: LDS");
 
-// QUERY: the batched ray queries' form (REF false; the nearest-hit key goes to query_sink instead of shading).
-// RAYS: rt3_radiance*'s form (REF false; the refill takes the caller's rays, rays_path, and everything behind it is the render's).
-template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t LEVELS, bool RES, bool QUERY = false, bool LIST = false, bool RAYS = false>
+// Form::Query: the batched ray queries' form (the nearest-hit key goes to query_sink instead of shading).
+// Form::Rays: rt3_radiance*'s form (the refill takes the caller's rays, rays_path, and everything behind it is the render's).
+template <bool HAS_TRI, bool HAS_SPH, Form F, uint32_t LEVELS, bool RES>
 __global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
+    static_assert(F != Form::RenderRef || (HAS_TRI && !HAS_SPH), "RenderRef: face-only scenes");
+    constexpr bool REF = F == Form::RenderRef, QUERY = F == Form::Query;
     static_assert(LEVELS == 3 || LEVELS == 4, "three or four levels");
     static_assert(kGroupTri == kLevFan && kGroupSph == kLevFan && kSuper == kLevFan, "k_trace_levels: 8 children per node");
     constexpr uint32_t BM = RES ? kLevBmBlocks : kLevBmBlocksTiled;
@@ -72,9 +74,7 @@ __global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u
     unsigned long long casts = 0, mfmas = 0, exact = 0, bound_tests = 0;
 
     for (;;) {
-        if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else if constexpr (RAYS) refill_queries<true>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else refill_lanes<REF, false, LIST>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        refill<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         const unsigned long long live = __ballot(alive);
         if constexpr (RES) { if (live == 0ull) break; }
         else if (!__syncthreads_or(live != 0ull ? 1 : 0)) break;
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u
         if constexpr (QUERY) query_sink(A, P, alive, keys[lane]);
         else {
             key_decode(keys[lane], kind, ibest, tbest);
-            shade_lane<HAS_TRI, HAS_SPH, REF>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
+            shade_lane<HAS_TRI, HAS_SPH, F>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
         }
     }
     if (lane == 0 && casts != 0) { atomicAdd(A.cast_counter, casts); atomicAdd(A.cast_counter + 1, mfmas); atomicAdd(A.cast_counter + 2, exact); atomicAdd(A.cast_counter + 3, bound_tests); }

@@ -727,8 +727,9 @@ __device__ __forceinline__ void drain_strip(uint32_t lane, const uint32_t* strip
 }
 
 // Sphere scenes of <= 512 spheres: everything the loop touches lives in LDS, waves never synchronise after the prologue.
-template <bool LIST = false>
+template <Form F>
 __global__ __launch_bounds__(kMB) void k_trace_mfma(const TraceArgs A, const u32x4* __restrict__ frags, uint32_t n_blocks) {
+    static_assert(F == Form::Render || F == Form::List, "k_trace_mfma: Render and List only");
     extern __shared__ u32x4 lds_dyn[];
     u32x4* s_frag = lds_dyn;                                                   // [n_blocks][4][64]
     float4* s_sph = reinterpret_cast<float4*>(s_frag + (size_t)n_blocks * 256);   // [n_blocks * 32] (cx, cy, cz, r^2) for the exact test
@@ -769,7 +770,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma(const TraceArgs A, const u32
 #define RT3_SPHASE(acc)
 #endif
     for (;;) {
-        refill_from_stock<false, LIST>(A, lane, alive, P, Q, chunk_next, chunk_end, exhausted);
+        refill_from_stock<F>(A, lane, alive, P, Q, chunk_next, chunk_end, exhausted);
         RT3_SPHASE(ph_refill)
 #ifdef RT3_PROFILE
         if (exhausted && !prof_dry_seen) {
@@ -828,7 +829,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma(const TraceArgs A, const u32
         }
         RT3_SPHASE(ph_flush)
         kind = tbest < __builtin_inff() ? 2u : 0u;
-        shade_lane<false, true>(A, P, alive, kind, ibest, tbest, s_sph, s_invr, s_mat, s_kind);
+        shade_lane<false, true, F>(A, P, alive, kind, ibest, tbest, s_sph, s_invr, s_mat, s_kind);
         RT3_SPHASE(ph_shade)
     }
 #ifdef RT3_PROFILE_PHASES
@@ -886,10 +887,12 @@ __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__bui
 // wave time per part of a restock (RT3_PROFILE_PHASES; unused otherwise)
 struct RestockPhases { unsigned long long total = 0, raygen = 0, fetch = 0, tests = 0, shade = 0, compact = 0; };
 struct SphereMirror { const float4* sph; const float* invr; const float4* mat; const uint32_t* kind; uint32_t n_blocks; const uint4* ctr_tab; };     // LDS
-template <bool LIST = false>
+template <Form F>
 __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, const SphereMirror& S, uint32_t lane, bool& alive, Path& P, TracedStock& Q,
                                                          uint32_t& chunk_next, uint32_t& chunk_end, bool& exhausted, unsigned long long& casts,
                                                          unsigned long long& exact, RestockPhases& ph) {
+    static_assert(F == Form::Render || F == Form::List, "refill_from_traced_stock: k_trace_mfma32's render forms");
+    constexpr bool LIST = F == Form::List;
     const unsigned long long need = __ballot(!alive);
     if (need == 0ull) return;
     const uint32_t n_need = (uint32_t)__popcll(need), rank = prefix_count(need);
@@ -942,7 +945,7 @@ __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, con
             while (__ballot(x >= A.width) != 0ull)                          // row wrap: once for a frame of 64 or more columns
                 if (x >= A.width) { x -= A.width; lrow += 1u; }
             start_path_at<false, true>(A, item, s_first, x, frame_row(A, lrow), hs, T);
-        } else start_path<false, LIST>(A, item, T);
+        } else start_path<F>(A, item, T);
         chunk_next += n_new;
         RT3_RPHASE(ph.raygen)
         // the union of the lists of the pixel groups these items fall into (one or two; more only where a sample block is shorter than 64
@@ -1006,7 +1009,7 @@ __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, con
             uint32_t kind, ibest;
             float tbest;
             key_decode(key, kind, ibest, tbest);
-            shade_lane<false, true, false, RT3_CTR_TABLE != 0>(A, T, live, kind, ibest, tbest, S.sph, S.invr, S.mat, S.kind, S.ctr_tab);
+            shade_lane<false, true, F, RT3_CTR_TABLE != 0>(A, T, live, kind, ibest, tbest, S.sph, S.invr, S.mat, S.kind, S.ctr_tab);
             RT3_RPHASE(ph.shade)
             // the survivors move to lanes [0, n), the rest behind them: a permutation of the wave (ds_permute: every lane sends) — the identity when no
             // lane survives (a strip of sky) or all 64 do
@@ -1044,10 +1047,12 @@ __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, con
 // The vector-ALU instruction count per ray cast is that of k_trace_mfma (the K = 32 margin brings more candidates, the pair list tests them
 // at full lane utilisation, the ray operands cost half), but the matrix pipe does half the work and the chip, which throttles under
 // k_trace_mfma's load (2.0-2.2 GHz), holds 2.3-2.4 GHz here — and a kernel bound by vector-ALU issue runs at the clock.
-// QUERY: the batched ray queries' form (refill from the caller's rays, no ray stock; the nearest-hit key goes to query_sink instead of shading).
-// RAYS: rt3_radiance*'s form (the caller's rays through rays_path, no ray stock and no strip lists; shading as in the render form, counter-hash table included).
-template <bool QUERY = false, bool LIST = false, bool RAYS = false>
+// Form::Query: the batched ray queries' form (refill from the caller's rays, no ray stock; the nearest-hit key goes to query_sink instead of shading).
+// Form::Rays: rt3_radiance*'s form (the caller's rays through rays_path, no ray stock and no strip lists; shading as in the render form, counter-hash table included).
+template <Form F>
 __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u32x4* __restrict__ frags, uint32_t n_blocks) {
+    static_assert(F != Form::RenderRef, "k_trace_mfma32: sphere scenes, no RenderRef");
+    constexpr bool QUERY = F == Form::Query;
     extern __shared__ u32x4 lds_dyn[];
     u32x4* s_frag = lds_dyn;                                                   // [n_blocks][2][64]
     float4* s_sph = reinterpret_cast<float4*>(s_frag + (size_t)n_blocks * 128);   // [n_blocks * 32] (cx, cy, cz, r^2) for the exact test
@@ -1094,9 +1099,8 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
 #endif
 
     for (;;) {
-        if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else if constexpr (RAYS) refill_queries<true>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else refill_from_traced_stock<LIST>(A, mirror, lane, alive, P, Q, chunk_next, chunk_end, exhausted, primary_casts, exact, ph_restock);
+        if constexpr (F == Form::Query || F == Form::Rays) refill_queries<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        else refill_from_traced_stock<F>(A, mirror, lane, alive, P, Q, chunk_next, chunk_end, exhausted, primary_casts, exact, ph_restock);
         RT3_SPHASE(ph_refill)
         const unsigned long long live = __ballot(alive);
         if (live == 0ull) break;
@@ -1130,7 +1134,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
         if constexpr (QUERY) query_sink(A, P, alive, keys[lane]);
         else {
             key_decode(keys[lane], kind, ibest, tbest);
-            shade_lane<false, true, false, CTR>(A, P, alive, kind, ibest, tbest, s_sph, s_invr, s_mat, s_kind, ctr_tab);
+            shade_lane<false, true, F, CTR>(A, P, alive, kind, ibest, tbest, s_sph, s_invr, s_mat, s_kind, ctr_tab);
         }
         RT3_SPHASE(ph_shade)
     }
@@ -1205,10 +1209,14 @@ constexpr uint32_t kBmBlocksRes = 4;
 constexpr uint32_t kResidentBlocks = (160u * 1024u - kTB * 8u - (kTB / 64u) * kPairCap * 4u * 3u - kBmBlocksRes * kTB * 4u) / 2048u - 1u;   // row blocks of 2 KiB: 55
 // (one block of headroom: a kernel with any static LDS beside the dynamic request — __syncthreads_or's word, say — is refused at exactly 160 KiB;
 // this variant has none and did launch with 56, profiles/README.md)
-// QUERY: the batched ray queries' form (REF false; the nearest-hit key goes to query_sink instead of shading).
-// RAYS: rt3_radiance*'s form (REF false; the refill takes the caller's rays, rays_path, and everything behind it is the render's).
-template <bool HAS_TRI, bool HAS_SPH, bool REF, uint32_t GT = 1, uint32_t GS = 1, uint32_t SUP = 1, bool RES = false, bool QUERY = false, bool LIST = false, bool RAYS = false>
+// Form::Query: the batched ray queries' form (the nearest-hit key goes to query_sink instead of shading).
+// Form::Rays: rt3_radiance*'s form (the refill takes the caller's rays, rays_path, and everything behind it is the render's).
+// Neither has a flat (GT = GS = SUP = 1) form.
+template <bool HAS_TRI, bool HAS_SPH, Form F, uint32_t GT, uint32_t GS, uint32_t SUP, bool RES>
 __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
+    static_assert(F != Form::RenderRef || (HAS_TRI && !HAS_SPH), "RenderRef: face-only scenes");
+    static_assert(GT > 1 || GS > 1 || SUP > 1 || (F != Form::Query && F != Form::Rays), "the flat filter has no Query or Rays form");
+    constexpr bool REF = F == Form::RenderRef, QUERY = F == Form::Query;
     static_assert(64 % GT == 0 && 64 % GS == 0, "group sizes must divide the wave");
     static_assert(!RES || (SUP > 1 && RT3_FACE_K32), "resident rows: three-level filter only");
     constexpr uint32_t BM = RES ? kBmBlocksRes : kBmBlocks;                     // row blocks per push
@@ -1246,9 +1254,7 @@ __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, con
 
     for (;;) {
         // (no ray stock here: a ray cast costs at least one tile scan, start_path is noise beside it, and the stock's 8 registers are needed)
-        if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else if constexpr (RAYS) refill_queries<true>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else refill_lanes<REF, false, LIST>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        refill<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         const unsigned long long live = __ballot(alive);
         if constexpr (RES) { if (live == 0ull) break; }                           // every wave for itself
         else if (!__syncthreads_or(live != 0ull ? 1 : 0)) break;                 // tiles: the workgroup ends together
@@ -1554,7 +1560,7 @@ __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, con
         if constexpr (QUERY) query_sink(A, P, alive, keys[lane]);
         else {
             key_decode(keys[lane], kind, ibest, tbest);
-            shade_lane<HAS_TRI, HAS_SPH, REF>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
+            shade_lane<HAS_TRI, HAS_SPH, F>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
         }
     }
     if (lane == 0 && casts != 0) { atomicAdd(A.cast_counter, casts); atomicAdd(A.cast_counter + 1, mfmas); atomicAdd(A.cast_counter + 2, exact); atomicAdd(A.cast_counter + 3, bound_tests); }

@@ -52,8 +52,9 @@ __device__ __forceinline__ bool rays_path(const TraceArgs& A, uint32_t item, Pat
 // scene does not pay registers or code for the triangle path.
 // Refill: lanes whose path ended take the next samples of the wave's chunk (ballot + prefix count); a chunk of
 // kWorkChunk samples is fetched from the global queue with one atomic when the wave runs dry.
-// QUERY: the items are the caller's rays (query_ray); an invalid one leaves its lane empty (refill_queries fills it again).  RAYS: the same with rays_path.
-template <bool REF = false, bool QUERY = false, bool LIST = false, bool RAYS = false>
+// Form::Query: the items are the caller's rays (query_ray); an invalid one leaves its lane empty (refill_queries fills it again).  Form::Rays: the same
+// with rays_path.
+template <Form F>
 __device__ __forceinline__ void refill_lanes(const TraceArgs& A, uint32_t lane, bool& alive, Path& P, uint32_t& chunk_next,
                                              uint32_t& chunk_end, bool& exhausted) {
     const unsigned long long need = __ballot(!alive);
@@ -76,19 +77,26 @@ __device__ __forceinline__ void refill_lanes(const TraceArgs& A, uint32_t lane, 
             taken += k;
         }
         if (item != 0xFFFFFFFFu) {
-            if constexpr (QUERY) alive = query_ray(A, item, P);
-            else if constexpr (RAYS) alive = rays_path(A, item, P);
-            else { start_path<REF, LIST>(A, item, P); alive = true; }
+            if constexpr (F == Form::Query) alive = query_ray(A, item, P);
+            else if constexpr (F == Form::Rays) alive = rays_path(A, item, P);
+            else { start_path<F>(A, item, P); alive = true; }
         }
     }
 }
 // The query forms' refill: until every lane holds a valid ray or the queue is dry, so that invalid rays neither end a wave early (a wave leaves
-// when no lane is alive after a refill) nor leave holes in it.  RAYS: the rays forms' refill, the same loop around rays_path.
-template <bool RAYS = false>
+// when no lane is alive after a refill) nor leave holes in it.  The rays forms' refill is the same loop around rays_path.
+template <Form F>
 __device__ __forceinline__ void refill_queries(const TraceArgs& A, uint32_t lane, bool& alive, Path& P, uint32_t& chunk_next, uint32_t& chunk_end,
                                                bool& exhausted) {
-    do refill_lanes<false, !RAYS, false, RAYS>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+    static_assert(F == Form::Query || F == Form::Rays, "refill_queries: the forms whose items are the caller's rays");
+    do refill_lanes<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
     while (__ballot(!alive) != 0ull && !exhausted);
+}
+// The refill of every kernel without a ray stock: the one its form takes.
+template <Form F>
+__device__ __forceinline__ void refill(const TraceArgs& A, uint32_t lane, bool& alive, Path& P, uint32_t& chunk_next, uint32_t& chunk_end, bool& exhausted) {
+    if constexpr (F == Form::Query || F == Form::Rays) refill_queries<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+    else refill_lanes<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
 }
 
 // Refill through a wave-wide stock of primary rays: start_path() runs for all 64 lanes at once (lane k of the stock holds sample
@@ -105,7 +113,7 @@ __device__ __forceinline__ void stock_pop(const RayStock& Q, uint32_t src, bool 
         alive = true;
     }
 }
-template <bool REF = false, bool LIST = false>
+template <Form F>
 __device__ __forceinline__ void refill_from_stock(const TraceArgs& A, uint32_t lane, bool& alive, Path& P, RayStock& Q, uint32_t& chunk_next,
                                                   uint32_t& chunk_end, bool& exhausted) {
     const unsigned long long need = __ballot(!alive);
@@ -132,7 +140,7 @@ __device__ __forceinline__ void refill_from_stock(const TraceArgs& A, uint32_t l
         }
         const uint32_t n_new = min(64u, chunk_end - chunk_next);
         Path T;
-        start_path<REF, LIST>(A, min(chunk_next + lane, chunk_end - 1u), T);
+        start_path<F>(A, min(chunk_next + lane, chunk_end - 1u), T);
         Q.ox = T.ox; Q.oy = T.oy; Q.oz = T.oz; Q.dx = T.dx; Q.dy = T.dy; Q.dz = T.dz; Q.slot = T.slot; Q.base = T.base;
         Q.n = n_new;
         chunk_next += n_new;
@@ -156,14 +164,15 @@ __device__ __forceinline__ void stock_pop(const TracedStock& Q, uint32_t src, bo
 
 // Shade / scatter one ray cast of every live lane (book materials).  kind: 0 miss, 1 face, 2 sphere.
 // The four per-sphere arrays read at a hit are parameters: global memory in k_trace, LDS copies in k_trace_mfma.
-// REF (RT3_FLAG_REFERENCE_PRIMARY): at ray cast 0 the direction is the reference's unnormalised one — the sky and the hit point use
+// Form::RenderRef (RT3_FLAG_REFERENCE_PRIMARY): at ray cast 0 the direction is the reference's unnormalised one — the sky and the hit point use
 // it as it is (SequentialRenderer.cpp:77,105-107); the scatter formulas then get the unit direction.
 // CTR: ctr_tab is the counter-hash table (rt3_kernel_common.hpp, kCtrDepthCap rows in LDS): the inner hash of rnd(base, ctr + k) depends on the
 // depth alone, so a lane below the cap reads its row instead of computing three hashes; at or beyond the cap it computes them as rnd() does.
-template <bool HAS_TRI, bool HAS_SPH, bool REF = false, bool CTR = false>
+template <bool HAS_TRI, bool HAS_SPH, Form F, bool CTR = false>
 __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& alive, uint32_t kind, uint32_t ibest, float tbest,
                                            const float4* sph, const float* sph_invr, const float4* sph_mat, const uint32_t* sph_kind,
                                            const uint4* ctr_tab = nullptr) {
+    constexpr bool REF = F == Form::RenderRef;
     const float ox = P.ox, oy = P.oy, oz = P.oz;
     float dx = P.dx, dy = P.dy, dz = P.dz;
     if (alive) {

@@ -189,8 +189,10 @@ __global__ __launch_bounds__(kBlock) void k_mode_r_fast(const float4* __restrict
 
 // SPH_LDS: the sphere array (<= kSphLdsMax entries) is also copied to LDS once per block, for the per-lane gathers of
 // the exact evaluation (an LDS gather costs ~64 cycles, a global one an L2 round trip per candidate).
-template <bool HAS_TRI, bool HAS_SPH, bool SPH_LDS, bool REF = false, bool LIST = false>
+template <bool HAS_TRI, bool HAS_SPH, bool SPH_LDS, Form F>
 __global__ __launch_bounds__(kBlock) void k_trace(const TraceArgs A) {
+    static_assert(F == Form::Render || F == Form::List || (F == Form::RenderRef && HAS_TRI && !HAS_SPH), "k_trace: renders only, RenderRef of face-only scenes");
+    constexpr bool REF = F == Form::RenderRef;
     __shared__ uint32_t cand[kCandSlots * kBlock];                  // per-lane candidate queues, [slot][thread]
     extern __shared__ float4 s_sph[];                               // SPH_LDS only
     const uint32_t tid = threadIdx.x, lane = lane_id();
@@ -208,7 +210,7 @@ __global__ __launch_bounds__(kBlock) void k_trace(const TraceArgs A) {
     unsigned long long casts = 0;                                   // wave-uniform
 
     for (;;) {
-        refill_lanes<REF, false, LIST>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        refill<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         if (__ballot(alive) == 0ull) break;                         // waves are independent: no block-level barrier anywhere
         casts += (unsigned long long)__popcll(__ballot(alive));
 
@@ -248,7 +250,7 @@ __global__ __launch_bounds__(kBlock) void k_trace(const TraceArgs A) {
             }
         }
 
-        shade_lane<HAS_TRI, HAS_SPH, REF>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
+        shade_lane<HAS_TRI, HAS_SPH, F>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
     }
     if (lane == 0 && casts != 0) atomicAdd(A.cast_counter, casts);
 }
@@ -258,10 +260,11 @@ __global__ __launch_bounds__(kBlock) void k_trace(const TraceArgs A) {
 // tools/fuzz_filter.py; rt3_debug_force_brute / RT3_BRUTE=1) and the only kernel that can serve RT3_FLAG_REFERENCE_PRIMARY with a
 // camera off the origin (the reference's literal formula then puts the "hit point" off the face's plane, where no bound holds).
 // Scene records are wave-uniform loads through the constant address space (scalar cache); one path per lane, refill by ballot.
-// QUERY: the batched ray queries' arbiter (rt3_intersect* / rt3_occluded* under the same switch): the running best starts at the ray's t_max.
-// RAYS: rt3_radiance*'s arbiter (the caller's rays, shaded as a render's: rays_path).
-template <bool REF, bool QUERY = false, bool LIST = false, bool RAYS = false>
+// Form::Query: the batched ray queries' arbiter (rt3_intersect* / rt3_occluded* under the same switch): the running best starts at the ray's t_max.
+// Form::Rays: rt3_radiance*'s arbiter (the caller's rays, shaded as a render's: rays_path).  Every form exists.
+template <Form F>
 __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
+    constexpr bool REF = F == Form::RenderRef, QUERY = F == Form::Query;
     const uint32_t lane = lane_id();
     Path P;
     P.ox = P.oy = P.oz = 0.0f; P.dx = P.dy = 0.0f; P.dz = 1.0f;
@@ -274,9 +277,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
     auto f4 = [](const f32x4 v) { return make_float4(v.x, v.y, v.z, v.w); };
 
     for (;;) {
-        if constexpr (QUERY) refill_queries(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else if constexpr (RAYS) refill_queries<true>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else refill_lanes<REF, false, LIST>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
+        refill<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
         if (__ballot(alive) == 0ull) break;
         casts += (unsigned long long)__popcll(__ballot(alive));
         float tbest = QUERY ? P.tmax : __builtin_inff();
@@ -299,7 +300,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
         if constexpr (QUERY) {
             if (alive) query_store(A, P.slot, kind, kind != 0u ? ibest : 0xFFFFFFFFu, kind != 0u ? tbest : __builtin_inff());
             alive = false;
-        } else shade_lane<true, true, REF>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);   // kind says which arrays to read
+        } else shade_lane<true, true, F>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);   // kind says which arrays to read
     }
     if (lane == 0 && casts != 0) atomicAdd(A.cast_counter, casts);
 }

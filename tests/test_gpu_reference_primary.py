@@ -34,7 +34,7 @@ def ppm_hash(rt3, oracle, img):
 def test_mode_x_with_the_flag_reproduces_the_reference_ppm(rt3, renderer, oracle, size):
     w, h = map(int, size.split("x"))
     case = builtin_case(rt3, w, h)
-    img = hip_render(renderer, case)                        # rt3_render_path -> k_trace_mfma_tiled<faces, REF>
+    img = hip_render(renderer, case)                        # rt3_render_path -> k_trace_mfma_tiled<faces, Form::RenderRef>
     assert renderer.stats().ray_casts == w * h
     assert ppm_hash(rt3, oracle, img) == PINS["ppm_sha256"][size]
     # the Mode-R entry point gives the same frame, row H-1 included
@@ -48,12 +48,12 @@ def test_every_kernel_family_agrees_under_the_flag(rt3, renderer, oracle):
     case = builtin_case(rt3, 400, 225)
     want = PINS["ppm_sha256"]["400x225"]
     assert ppm_hash(rt3, oracle, hip_render(renderer, case)) == want
-    os.environ["RT3_NO_MFMA"] = "1"                         # vector-ALU scan, k_trace<faces, REF>
+    os.environ["RT3_NO_MFMA"] = "1"                         # vector-ALU scan, k_trace<faces, Form::RenderRef>
     try:
         assert ppm_hash(rt3, oracle, hip_render(renderer, case, upload=False)) == want
     finally:
         del os.environ["RT3_NO_MFMA"]
-    renderer.force_brute(True)                              # no filter at all, k_trace_brute<REF>
+    renderer.force_brute(True)                              # no filter at all, k_trace_brute<Form::RenderRef>
     try:
         assert ppm_hash(rt3, oracle, hip_render(renderer, case, upload=False)) == want
     finally:

@@ -3,9 +3,8 @@
 
     hipcc --offload-arch=gfx950 <the Makefile's HIPFLAGS> -Rpass-analysis=kernel-resource-usage ... 2> LOG
 
-(one of the parent commit, one of this tree).  Kernels are matched by their demangled names; where this tree gave a kernel template one more
-trailing parameter whose value `false` selects the parent's kernel (the RAYS flag of the trace kernels, as the LIST flag before it), that argument is
-dropped first, so the existing instantiation is compared with the kernel it was.  Prints one line per kernel, `a -> b` where a figure changed, NEW for kernels the parent
+(one of the parent commit, one of this tree).  Kernels are matched by their demangled names (a new form of a trace kernel is a new value of Form,
+rt3_kernel_common.hpp, and renames no existing kernel).  Prints one line per kernel, `a -> b` where a figure changed, NEW for kernels the parent
 does not have, and ends with the number of existing kernels that gained scratch or lost occupancy (exit code 1 if there is one).
 
     python tools/kernel_resources.py PARENT.log TREE.log > profiles/radiance_kernel_resources.log
@@ -16,9 +15,6 @@ import subprocess
 import sys
 
 KEYS = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]"]
-# template arguments of the trace kernels in the parent: one more, `false`, is this tree's RAYS flag (the kernels with a query twin; the VALU k_trace and
-# the K = 64 k_trace_mfma have no rays form and keep their parameter lists)
-PARENT_ARGS = {"k_trace_mfma32": 2, "k_trace_mfma_tiled": 9, "k_trace_levels": 7, "k_trace_brute": 3}
 
 
 def parse(path):
@@ -42,15 +38,13 @@ def demangled(names):
 
 
 def key(d):
-    d = re.sub(r"\(anonymous namespace\)::", "", d)
-    d = re.sub(r"^void ", "", re.sub(r"\(.*$", "", d))
-    m = re.match(r"(\w+)<(.*)>$", d)
-    if not m or m.group(1) not in PARENT_ARGS:
-        return d
-    args = [x.strip() for x in m.group(2).split(",")]
-    if len(args) == PARENT_ARGS[m.group(1)] + 1 and args[-1] == "false":
-        args = args[:-1]
-    return "%s<%s>" % (m.group(1), ", ".join(args)) if args else m.group(1)
+    d = re.sub(r"^void ", "", re.sub(r"\(anonymous namespace\)::", "", d))
+    depth = 0
+    for i in range(len(d) - 1, -1, -1):                               # drop the parameter list: the last balanced (...) — an enum argument, (Form)2, stays
+        depth += (d[i] == ")") - (d[i] == "(")
+        if depth == 0:
+            return d[:i] if d.endswith(")") else d
+    return d
 
 
 def table(path):
