@@ -32,7 +32,8 @@ extern "C" {
  * sizeof(rt3_stats) bytes of THIS version).  History: 1 = round 1; 2 = + mfma_instructions / exact_tests in rt3_stats, progressive
  * accumulation, rt3_gather_rows; 3 = + rt3_abi_version itself, one stream convention (below),
  * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh*, with
- * rt3_render_path_adaptive* (one new struct of its own) and with rt3_regroup*: functions were only added, no existing struct changed. */
+ * rt3_render_path_adaptive* (one new struct of its own), with rt3_regroup* and with the environment map (rt3_set_environment*): functions were
+ * only added, no existing struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
 
@@ -579,6 +580,52 @@ int rt3_radiance(rt3_ctx* ctx, const rt3_ray* rays, const uint32_t* keys, uint32
 /* Device arrays (n rt3_ray and, or NULL, n uint32 in; n float4 out), asynchronous on `stream` (NULL = the context's own stream). */
 int rt3_radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, uint32_t n, const rt3_radiance_params* p, void* d_out_rgba,
                         void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Environment map  (DESIGN.md 4.19, 5.2n): a cube map answers every Mode-X ray that leaves the scene
+ * ------------------------------------------------------------------------------------------------- */
+/* The map.  6 faces of N x N texels, 1 <= N <= RT3_ENV_MAX_FACE, each texel a float4 (r, g, b, ignored).  Faces in the order +X, -X, +Y, -Y, +Z, -Z,
+ * row 0 first: the texel of face f, row j, column i is at index (f * N + j) * N + i.
+ * The lookup law.  For a direction d = (x, y, z) with ax = |x|, ay = |y|, az = |z|, the face f, the major-axis length m and the in-face
+ * coordinates sc (columns) and tc (rows) are
+ *     if (ax >= ay && ax >= az)  f = x < 0 ? 1 : 0,  m = ax,  sc = x < 0 ? z : -z,  tc = -y
+ *     else if (ay >= az)         f = y < 0 ? 3 : 2,  m = ay,  sc = x,               tc = y < 0 ? -z : z
+ *     else                       f = z < 0 ? 5 : 4,  m = az,  sc = z < 0 ? -x : x,  tc = -y
+ * and then, for sc (giving x0, wx, i0, i1) and in the same way for tc (giving y0, wy, j0, j1), every operation an IEEE f32 one rounded on its
+ * own, nothing fused:
+ *     q = sc / m;  u = q * 0.5f + 0.5f;  fx = u * (float)N - 0.5f;  x0 = floorf(fx);  wx = fx - x0;
+ *     x0 = fminf(fmaxf(x0, -1), N - 1)      (in float, the NaN-dropping min / max: a NaN gives -1), only then converted to an integer
+ *     i0 = max(x0, 0);  i1 = min(x0 + 1, N - 1)
+ * With cAB the texel at column iA, row jB, per channel:
+ *     top = c00 + wx * (c10 - c00);  bot = c01 + wx * (c11 - c01);  c = top + wy * (bot - top)
+ * So: filtering stays inside one face (clamp to edge, no seam handling); a face of one colour returns that colour exactly; on the four side
+ * faces row 0 is up (+Y); and whatever d holds, non-finite values included, a lookup reads inside the map.
+ * The miss of the Mode-X path law, in this order: under RT3_FLAG_BLACK_BACKGROUND nothing; otherwise, when a map is set, L = fma(T, c, L) per
+ * channel with c = the lookup of the ray's direction; otherwise the sky.
+ * Who reads the map: rt3_render_path*, rt3_render_path_range*, rt3_render_path_adaptive* and rt3_radiance* (the defining property of
+ * rt3_radiance holds with a map set as without); rt3_render_aov* in its miss albedo (env(d) in place of sky(d)).  Mode R, queries, the denoisers
+ * and rt3_camera_rays do not.  A render with RT3_FLAG_REFERENCE_PRIMARY while a map is set returns RT3_E_ARG (its primary direction is not a
+ * unit vector, and it exists to reproduce the reference).  While a map is set the trace kernel is chosen as for a query: RT3_NO_MFMA,
+ * RT3_MFMA_K64 and the flat filter (RT3_NO_GROUPS, rt3_debug_force_flat_filter) are ignored.  With no map set every entry point returns what it
+ * returned before these functions existed, bit for bit.
+ * State.  The map belongs to the context: it survives every scene upload, update and regroup and never touches the accumulation (a progressive
+ * render continues across rt3_set_environment; what it continues WITH is the caller's business).
+ * Errors.  n_face == 0 clears the map (the pointer may then be NULL).  RT3_E_ARG, with the previous map left in place: a NULL ctx or array,
+ * n_face > RT3_ENV_MAX_FACE, a misaligned device pointer, and — host form only, the device form does not validate texels — a texel whose r, g
+ * or b is not finite (the message names the lowest such texel index).
+ * Out of scope: importance sampling of the map (a small bright sun is noisy), seamless filtering across face edges, mip levels, rotation. */
+#define RT3_ENV_MAX_FACE 2048u
+/* Host array of 6 * n_face * n_face float4; the context copies it and owns the copy.  Synchronous. */
+int      rt3_set_environment(rt3_ctx* ctx, const float* rgba, uint32_t n_face);
+/* The same from a device array (16-byte aligned), queued on `stream` (the stream convention above); it takes part in the event chain as an update
+ * does.  The caller's array is only read until the queued work has run. */
+int      rt3_set_environment_device(rt3_ctx* ctx, const void* d_rgba, uint32_t n_face, void* stream);
+int      rt3_clear_environment(rt3_ctx* ctx);
+/* N, or 0 when no map is set. */
+uint32_t rt3_environment_size(rt3_ctx* ctx);
+/* Host only, no device and no context: the lookup law above in C, out_rgb = env(d).  RT3_E_ARG for a NULL pointer, n_face == 0 or
+ * n_face > RT3_ENV_MAX_FACE.  The tests compare it and the device with tests/environment_ref.py bit for bit. */
+int      rt3_debug_environment_lookup(const float* rgba, uint32_t n_face, const float d[3], float out_rgb[3]);
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side scene API  (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)

@@ -159,6 +159,7 @@ EXPORTS = [
     "rt3_render_path_adaptive", "rt3_render_path_adaptive_device",
     "rt3_set_spheres_device", "rt3_set_mesh_device", "rt3_debug_sphere_plan", "rt3_debug_sphere_build",
     "rt3_radiance", "rt3_radiance_device",
+    "rt3_set_environment", "rt3_set_environment_device", "rt3_clear_environment", "rt3_environment_size", "rt3_debug_environment_lookup",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -233,6 +234,9 @@ def lib():
         "rt3_set_spheres_device": (i32, [vp, vp, vp, u32, vp]), "rt3_set_mesh_device": (i32, [vp, vp, u32, vp, u32, vp, vp]),
         "rt3_debug_sphere_plan": (u32, [vp, u32, vp, vp]), "rt3_debug_sphere_build": (i32, [vp, vp, vp, vp]),
         "rt3_radiance": (i32, [vp, vp, vp, u32, vp, vp]), "rt3_radiance_device": (i32, [vp, vp, vp, u32, vp, vp, vp]),
+        "rt3_set_environment": (i32, [vp, vp, u32]), "rt3_set_environment_device": (i32, [vp, vp, u32, vp]),
+        "rt3_clear_environment": (i32, [vp]), "rt3_environment_size": (u32, [vp]),
+        "rt3_debug_environment_lookup": (i32, [vp, u32, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -247,6 +251,57 @@ def lib():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _cube_rgba(cube):
+    """(6, N, N, 3 | 4) -> contiguous float32 (6, N, N, 4), the layout rt3_set_environment takes (the fourth channel is ignored: 0 when absent)."""
+    a = np.asarray(cube, np.float32)
+    if a.ndim != 4 or a.shape[0] != 6 or a.shape[1] != a.shape[2] or a.shape[3] not in (3, 4) or a.shape[1] < 1:
+        raise Fatal("an environment map is an array of shape (6, N, N, 3) or (6, N, N, 4)")
+    if a.shape[3] == 3:
+        a = np.concatenate([a, np.zeros(a.shape[:3] + (1,), np.float32)], axis=3)
+    return np.ascontiguousarray(a)
+
+
+def environment_lookup(cube, d):
+    """rt3_debug_environment_lookup, the environment map's lookup law in C on the host: float32 (3,) for one direction, (K, 3) for K."""
+    rgba = _cube_rgba(cube)
+    dirs = np.ascontiguousarray(np.asarray(d, np.float32).reshape(-1, 3))
+    out = np.zeros((len(dirs), 3), np.float32)
+    fn = lib().rt3_debug_environment_lookup
+    for k in range(len(dirs)):
+        if fn(_p(rgba), rgba.shape[1], C.c_void_p(dirs.ctypes.data + 12 * k), C.c_void_p(out.ctypes.data + 12 * k)) != 0:
+            raise Fatal("rt3_debug_environment_lookup refused its arguments (1 <= N <= 2048)")
+    return out[0] if np.ndim(d) == 1 else out
+
+
+def cube_from_equirect(image, n):
+    """A latitude-longitude image (H, W, 3 | 4; row 0 is +Y, the centre column is -Z, longitude grows towards +X) -> a cube map (6, n, n, 4)
+    float32 for set_environment: every texel centre's direction — the inverse of the lookup law's face coordinates — is looked up bilinearly in the
+    image (float64 inside; columns wrap around, rows clamp at the poles)."""
+    img = np.asarray(image, np.float64)
+    if img.ndim != 3 or img.shape[2] not in (3, 4) or img.shape[0] < 1 or img.shape[1] < 1 or n < 1:
+        raise Fatal("cube_from_equirect takes an image (H, W, 3 | 4) and n >= 1")
+    h, w = img.shape[:2]
+    c = (np.arange(n, dtype=np.float64) + 0.5) / n * 2.0 - 1.0          # sc / m (columns) and tc / m (rows) of the texel centres
+    sc, tc = np.meshgrid(c, c)                                           # [row j, column i]
+    one = np.ones_like(sc)
+    faces = [(one, -tc, -sc), (-one, -tc, sc), (sc, one, tc), (sc, -one, -tc), (sc, -tc, one), (-sc, -tc, -one)]
+    out = np.zeros((6, n, n, 4), np.float32)
+    for f, (x, y, z) in enumerate(faces):
+        r = np.sqrt(x * x + y * y + z * z)
+        lon = np.arctan2(x, -z)                                          # 0 at -Z, +pi/2 at +X
+        lat = np.arcsin(np.clip(y / r, -1.0, 1.0))                       # +pi/2 at +Y
+        fx = (lon / (2.0 * np.pi) + 0.5) * w - 0.5
+        fy = (0.5 - lat / np.pi) * h - 0.5
+        x0, y0 = np.floor(fx), np.floor(fy)
+        wx, wy = (fx - x0)[..., None], (fy - y0)[..., None]
+        xa, xb = x0.astype(np.int64) % w, (x0.astype(np.int64) + 1) % w
+        ya, yb = np.clip(y0.astype(np.int64), 0, h - 1), np.clip(y0.astype(np.int64) + 1, 0, h - 1)
+        top = img[ya, xa, :3] * (1.0 - wx) + img[ya, xb, :3] * wx
+        bot = img[yb, xa, :3] * (1.0 - wx) + img[yb, xb, :3] * wx
+        out[f, :, :, :3] = (top * (1.0 - wy) + bot * wy).astype(np.float32)
+    return out
 
 
 def _f3(v):
@@ -960,6 +1015,35 @@ class HipRenderer(Renderer):
         """Asynchronous rt3_radiance_device: n rt3_ray at d_rays_ptr, n uint32 keys at d_keys_ptr (or None), n float4 out at d_out_ptr."""
         self._check(lib().rt3_radiance_device(self._ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_keys_ptr or 0), n, C.byref(radiance_params),
                                               C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
+
+    # -- the environment map (rt3_set_environment*; DESIGN.md 4.19) -----------------------------------------------------
+    def set_environment(self, cube):
+        """Sets the cube map every Mode-X ray that leaves the scene reads (rt3_set_environment): a numpy array (6, N, N, 3 | 4), faces +X, -X,
+        +Y, -Y, +Z, -Z, row 0 first — the context copies it — or a contiguous (6, N, N, 4) float32 torch tensor on the GPU, copied on
+        torch.cuda.current_stream() (rt3_set_environment_device; its texels are not validated)."""
+        if type(cube).__module__.startswith("torch"):
+            import torch
+            if (not cube.is_cuda or cube.dtype != torch.float32 or cube.dim() != 4 or cube.shape[0] != 6 or cube.shape[1] != cube.shape[2] or
+                    cube.shape[3] != 4 or not cube.is_contiguous()):
+                raise Fatal("a device environment must be a contiguous (6, N, N, 4) float32 tensor on the GPU")
+            stream = torch.cuda.current_stream(cube.device).cuda_stream
+            self._check(lib().rt3_set_environment_device(self._ctx, C.c_void_p(cube.data_ptr()), int(cube.shape[1]), C.c_void_p(stream or 0)))
+            return
+        rgba = _cube_rgba(cube)
+        self._check(lib().rt3_set_environment(self._ctx, _p(rgba), rgba.shape[1]))
+
+    def clear_environment(self):
+        """Removes the map: a miss is the sky again (rt3_clear_environment)."""
+        self._check(lib().rt3_clear_environment(self._ctx))
+
+    def environment_size(self):
+        """N of the map that is set, 0 when none is (rt3_environment_size)."""
+        return int(lib().rt3_environment_size(self._ctx))
+
+    @staticmethod
+    def environment_lookup(cube, d):
+        """The lookup law on the host (rt3_debug_environment_lookup; no device): cube (6, N, N, 3 | 4), d (3,) or (K, 3) -> float32 (3,) or (K, 3)."""
+        return environment_lookup(cube, d)
 
     # -- camera rays, first-hit AOVs, the linear frame (DESIGN.md 4.10) -----------------------------------------------
     def camera_rays(self, camera_c, params, sample_begin=0, sample_count=None):

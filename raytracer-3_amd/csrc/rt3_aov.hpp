@@ -25,8 +25,11 @@ __global__ __launch_bounds__(kBlock) void k_camera_rays(const TraceArgs A, float
 // One thread per pixel; the samples of the batch are added in sample order, as k_accumulate adds radiance.  `first`: the batch
 // starts at sample 0 (the sums start from zero and sample 0's hit is recorded).  Material and sphere records are read in the caller's primitive
 // order — the order of a hit's index — through the fields scene_args() fills in; hit point and normal are computed as shade_lane() does.
+// env_n != 0: an environment map is set and a miss's albedo is its lookup, where it is the sky otherwise — a run-time test, this is no
+// trace kernel.
 __global__ __launch_bounds__(kBlock) void k_aov_accumulate(const TraceArgs A, const float4* __restrict__ rays, const uint4* __restrict__ hits,
-                                                          float4* __restrict__ acc, uint32_t npix, uint32_t ns, int first) {
+                                                          float4* __restrict__ acc, uint32_t npix, uint32_t ns, int first,
+                                                          const float4* __restrict__ env, uint32_t env_n) {
     const uint32_t pix = blockIdx.x * kBlock + threadIdx.x;
     if (pix >= npix) return;
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -42,7 +45,10 @@ __global__ __launch_bounds__(kBlock) void k_aov_accumulate(const TraceArgs A, co
         const float t = __uint_as_float(h.x);
         float ar = 0.0f, ag = 0.0f, ab = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
         if (kind == RT3_HIT_NONE) {
-            if (!(A.flags & RT3_FLAG_BLACK_BACKGROUND)) sky(rd.x, rd.y, rd.z, ar, ag, ab);
+            if (!(A.flags & RT3_FLAG_BLACK_BACKGROUND)) {
+                if (env_n != 0u) env_lookup(env, env_n, rd.x, rd.y, rd.z, ar, ag, ab);
+                else sky(rd.x, rd.y, rd.z, ar, ag, ab);
+            }
         } else if (kind == RT3_HIT_FACE || kind == RT3_HIT_SPHERE) {
             float4 m; uint32_t mk;
             if (kind == RT3_HIT_FACE) {

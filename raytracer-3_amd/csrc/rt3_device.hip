@@ -136,6 +136,9 @@ struct rt3_ctx {
     DevBuf<float4> d_tri_rec;                                       // the faces' records in group order (the exact test of the multi-level filter reads these)
     DevBuf<uint32_t> d_strips;                                      // deferred member tests: kStripPairs pairs per wave of the grid
     DevBuf<uint32_t> d_prim_masks;                                  // strip lists of the last k_trace_mfma32 render: [group of 64 owned pixels][row block]
+    // environment map (rt3_set_environment*): the context's copy, 6 faces of env_n x env_n float4 texels; env_n == 0: none.  Scene
+    // uploads, updates and regroups never touch it.
+    DevBuf<float4> d_env; uint32_t env_n = 0;
 
     // work buffers
     DevBuf<Rgb> d_rad;
@@ -554,6 +557,11 @@ int path_args(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t
 using TraceKernel = void (*)(const TraceArgs);
 using TiledKernel = void (*)(const TraceArgs, const u32x4*, const u32x4*);
 using SingleKernel = void (*)(const TraceArgs, const u32x4*, uint32_t);
+// The same three signatures by form: an environment form takes an EnvTraceArgs (rt3_kernel_common.hpp).  TracePlan keeps such a kernel under the
+// plain pointer type with env_n != 0; launch_trace casts it back before it launches.
+template <Form F> using TraceKernelOf = void (*)(const trace_args<F>);
+template <Form F> using TiledKernelOf = void (*)(const trace_args<F>, const u32x4*, const u32x4*);
+template <Form F> using SingleKernelOf = void (*)(const trace_args<F>, const u32x4*, uint32_t);
 struct TracePlan {
     TraceKernel plain = nullptr;
     TiledKernel tiled = nullptr;
@@ -567,6 +575,7 @@ struct TracePlan {
     uint64_t filter_rows = 0;                                       // rows the matrix filter scans per ray cast
     bool filter_counted = false;                                    // the kernel counts the casts that take the filter (k_trace_mfma32's render form)
     uint32_t list_groups = 0;                                       // strip lists to build before the first batch (k_primary_lists): groups of 64 owned pixels, 0: none
+    const float4* env = nullptr; uint32_t env_n = 0;                // environment forms: the map the launch hands over behind TraceArgs (env_n != 0)
 };
 // Strip lists (rt3_primary_lists.hpp): RT3_PRIMARY_LISTS=0 turns them off (the A/B reference: every primary ray takes the matrix filter),
 // RT3_PRIMARY_LIST_MAX=n sets the longest list a restock still traces itself.  The default is the best of a sweep on the bench frame at 1080p (short
@@ -585,34 +594,34 @@ auto by_scene(bool has_tri, bool has_sph, Pick pick) -> decltype(pick(std::true_
     else return has_tri ? (has_sph ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{})) : pick(std::false_type{}, std::true_type{});
 }
 template <Form F>
-TiledKernel levels_kernel(uint32_t levels, bool resident, bool has_tri, bool has_sph) {
-    return by_scene<F>(has_tri, has_sph, [=](auto tri, auto sph) -> TiledKernel {
+TiledKernelOf<F> levels_kernel(uint32_t levels, bool resident, bool has_tri, bool has_sph) {
+    return by_scene<F>(has_tri, has_sph, [=](auto tri, auto sph) -> TiledKernelOf<F> {
         constexpr bool T = tri(), S = sph();
         return levels == 4 ? (resident ? k_trace_levels<T, S, F, 4, true> : k_trace_levels<T, S, F, 4, false>)
                            : (resident ? k_trace_levels<T, S, F, 3, true> : k_trace_levels<T, S, F, 3, false>);
     });
 }
 template <Form F>
-TiledKernel tiled_kernel(bool grouped, bool resident, bool has_tri, bool has_sph) {
-    return by_scene<F>(has_tri, has_sph, [=](auto tri, auto sph) -> TiledKernel {
+TiledKernelOf<F> tiled_kernel(bool grouped, bool resident, bool has_tri, bool has_sph) {
+    return by_scene<F>(has_tri, has_sph, [=](auto tri, auto sph) -> TiledKernelOf<F> {
         constexpr bool T = tri(), S = sph();
         constexpr uint32_t GT = T ? kGroupTri : 1u, GS = S ? kGroupSph : 1u;       // (a pass over one kind of primitive alone keeps the other's group size 1)
         if (resident) return k_trace_mfma_tiled<T, S, F, GT, GS, kSuper, true>;
         if (grouped) return k_trace_mfma_tiled<T, S, F, GT, GS, kSuper, false>;
-        if constexpr (F == Form::Query || F == Form::Rays) return nullptr;         // the flat filter
+        if constexpr (F == Form::Query || F == Form::Rays || is_env(F)) return nullptr;   // the flat filter
         else return k_trace_mfma_tiled<T, S, F, 1, 1, 1, false>;
     });
 }
 template <Form F>
-SingleKernel single_kernel(bool k64) {
+SingleKernelOf<F> single_kernel(bool k64) {
     if constexpr (F == Form::Render || F == Form::List) return k64 ? k_trace_mfma<F> : k_trace_mfma32<F>;
     else if constexpr (F == Form::RenderRef) return nullptr;
     else return k64 ? nullptr : k_trace_mfma32<F>;
 }
 template <Form F>
-TraceKernel valu_kernel(bool sph_lds, bool has_tri, bool has_sph) {
-    if constexpr (F == Form::Query || F == Form::Rays) return nullptr;
-    else return by_scene<F>(has_tri, has_sph, [=](auto tri, auto sph) -> TraceKernel {
+TraceKernelOf<F> valu_kernel(bool sph_lds, bool has_tri, bool has_sph) {
+    if constexpr (F == Form::Query || F == Form::Rays || is_env(F)) return nullptr;
+    else return by_scene<F>(has_tri, has_sph, [=](auto tri, auto sph) -> TraceKernelOf<F> {
         constexpr bool T = tri(), S = sph();
         return S && sph_lds ? k_trace<T, S, /* SPH_LDS */ S, F> : k_trace<T, S, false, F>;
     });
@@ -626,20 +635,27 @@ void with_form(Form form, Fn fn) {
     case Form::Query: return fn(std::integral_constant<Form, Form::Query>{});
     case Form::List: return fn(std::integral_constant<Form, Form::List>{});
     case Form::Rays: return fn(std::integral_constant<Form, Form::Rays>{});
+    case Form::RenderEnv: return fn(std::integral_constant<Form, Form::RenderEnv>{});
+    case Form::ListEnv: return fn(std::integral_constant<Form, Form::ListEnv>{});
+    case Form::RaysEnv: return fn(std::integral_constant<Form, Form::RaysEnv>{});
     }
 }
 // Fills A's filter fields and T for the form `form` (rt3_kernel_common.hpp).  ref_brute: a RenderRef with a camera only the brute-force kernel serves.
 // List: the kernel a Render would take, strip lists off.  Rays: the kernel a Query would take on this scene — the switches queries ignore are ignored —
 // shading as a render; A.q_rays is the caller's to set (its slot is the strip lists': they are off).
+// While an environment map is set a Render, List or Rays becomes its environment twin: the same family — the families without such a
+// form (VALU, K = 64, the flat filter) are never chosen, their switches are ignored as queries ignore them — and T carries the map for launch_trace.
 int plan_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, TracePlan& T) {
     const bool query = form == Form::Query, list = form == Form::List, rays = form == Form::Rays;
+    const bool env = ctx->env_n != 0 && (form == Form::Render || list || rays);
+    if (env) { T.env = ctx->d_env; T.env_n = ctx->env_n; form = form == Form::Render ? Form::RenderEnv : list ? Form::ListEnv : Form::RaysEnv; }
     const bool has_tri = ctx->n_faces > 0, has_sph = ctx->n_sph > 0;
     const bool brute = ctx->force_brute || getenv("RT3_BRUTE") || ref_brute;
-    const bool use_mfma = !brute && (query || rays || !getenv("RT3_NO_MFMA"));
+    const bool use_mfma = !brute && (query || rays || env || !getenv("RT3_NO_MFMA"));
     const bool mfma_single = use_mfma && !has_tri && has_sph && ctx->n_sph <= kMfmaSphMax && !getenv("RT3_FORCE_TILED");   // (A/B knob)
-    const bool single_k64 = !query && !rays && mfma_single && getenv("RT3_MFMA_K64") != nullptr;
+    const bool single_k64 = !query && !rays && !env && mfma_single && getenv("RT3_MFMA_K64") != nullptr;
     const bool sph_lds = has_sph && ctx->n_sph <= kSphLdsMax;
-    const bool grouped = kGroupTri > 1 && kGroupSph > 1 && (query || rays || (!ctx->force_flat && !getenv("RT3_NO_GROUPS")));
+    const bool grouped = kGroupTri > 1 && kGroupSph > 1 && (query || rays || env || (!ctx->force_flat && !getenv("RT3_NO_GROUPS")));
     A.n_tri_rows = grouped ? ctx->tri.n_groups : ctx->n_faces;
     A.n_sph_rows = grouped ? ctx->sph.n_groups : ctx->n_sph;
     A.sph_grp = ctx->sph.grp; A.sph_perm = ctx->sph.perm; A.tri_grp = ctx->tri.grp; A.tri_perm = ctx->tri.perm; A.tri_rec = ctx->d_tri_rec;
@@ -698,11 +714,11 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, TracePlan&
     }
     with_form(form, [&](auto f) {                                   // the one place a kernel is named: family x form
         constexpr Form F = decltype(f)::value;
-        if (brute) T.plain = k_trace_brute<F>;
-        else if (mfma_single) T.single = single_kernel<F>(single_k64);
-        else if (levels) T.tiled = levels_kernel<F>(levels, resident, has_tri, has_sph);
-        else if (use_mfma) T.tiled = tiled_kernel<F>(grouped, resident, has_tri, has_sph);
-        else T.plain = valu_kernel<F>(sph_lds, has_tri, has_sph);
+        if (brute) T.plain = reinterpret_cast<TraceKernel>(TraceKernelOf<F>(k_trace_brute<F>));
+        else if (mfma_single) T.single = reinterpret_cast<SingleKernel>(single_kernel<F>(single_k64));
+        else if (levels) T.tiled = reinterpret_cast<TiledKernel>(levels_kernel<F>(levels, resident, has_tri, has_sph));
+        else if (use_mfma) T.tiled = reinterpret_cast<TiledKernel>(tiled_kernel<F>(grouped, resident, has_tri, has_sph));
+        else T.plain = reinterpret_cast<TraceKernel>(valu_kernel<F>(sph_lds, has_tri, has_sph));
     });
     const void* kptr = T.single ? (const void*)T.single : T.tiled ? (const void*)T.tiled : (const void*)T.plain;
     if (!kptr) return fail(ctx, RT3_E_DEVICE, "internal: the trace kernel chosen has no such form");
@@ -726,6 +742,16 @@ uint32_t trace_grid(const rt3_ctx* ctx, const TracePlan& T, uint32_t total) {
     return std::max(1u, std::min<uint32_t>((uint32_t)(ctx->num_cu * T.per_cu), want_blocks));
 }
 void launch_trace(const TracePlan& T, const TraceArgs& A, uint32_t grid, hipStream_t stream) {
+    if (T.env_n != 0) {                                             // an environment form: the same launch with the map behind the arguments
+        EnvTraceArgs E;
+        static_cast<TraceArgs&>(E) = A;
+        E.env = T.env; E.env_n = T.env_n; E.env_pad = 0u;
+        constexpr Form F = Form::RenderEnv;                         // (the three environment forms share their signatures)
+        if (T.single) hipLaunchKernelGGL(reinterpret_cast<SingleKernelOf<F>>(T.single), dim3(grid), dim3(kMB), T.lds, stream, E, T.frag_a, T.mfma_blocks);
+        else if (T.tiled) hipLaunchKernelGGL(reinterpret_cast<TiledKernelOf<F>>(T.tiled), dim3(grid), dim3(kTB), T.lds, stream, E, T.frag_a, T.frag_b);
+        else hipLaunchKernelGGL(reinterpret_cast<TraceKernelOf<F>>(T.plain), dim3(grid), dim3(kBlock), T.lds, stream, E);
+        return;
+    }
     if (T.single) hipLaunchKernelGGL(T.single, dim3(grid), dim3(kMB), T.lds, stream, A, T.frag_a, T.mfma_blocks);
     else if (T.tiled) hipLaunchKernelGGL(T.tiled, dim3(grid), dim3(kTB), T.lds, stream, A, T.frag_a, T.frag_b);
     else hipLaunchKernelGGL(T.plain, dim3(grid), dim3(kBlock), T.lds, stream, A);
@@ -1675,6 +1701,8 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     if ((rc = check_scene(ctx))) return rc;
     const bool ref = (p->flags & RT3_FLAG_REFERENCE_PRIMARY) != 0, var = (p->flags & RT3_FLAG_VARIANCE) != 0;
     if (ref && ctx->n_sph != 0) return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY needs a triangle-only scene");
+    if (ref && ctx->env_n != 0)
+        return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY is not available while an environment map is set (its primary direction is not a unit vector)");
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
 
@@ -2139,7 +2167,7 @@ int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
         RT3_HIP(hipGetLastError());
         if ((rc = issue_trace(ctx, Q, T, Q.total, stream))) return rc;
         hipLaunchKernelGGL(k_aov_accumulate, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, (const float4*)ctx->d_arays,
-                           (const uint4*)ctx->d_ahits, ctx->d_aacc, npix, ns, s0 == 0 ? 1 : 0);
+                           (const uint4*)ctx->d_ahits, ctx->d_aacc, npix, ns, s0 == 0 ? 1 : 0, (const float4*)ctx->d_env, ctx->env_n);
         RT3_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_aov_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_aacc, npix, p->spp, (float4*)d_out);
@@ -2534,6 +2562,64 @@ int rt3_radiance(rt3_ctx* ctx, const rt3_ray* rays, const uint32_t* keys, uint32
 }
 int rt3_radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, uint32_t n, const rt3_radiance_params* p, void* d_out_rgba, void* stream) {
     return radiance_device(ctx, d_rays, d_keys, n, p, d_out_rgba, stream);
+}
+
+// ---- Environment map: the context's own copy of a cube map, read by the miss of the environment forms (5.2n) and by k_aov_accumulate.
+// Replacing it allocates the new copy first and frees the old one behind the event chain, so that a failure leaves the previous map in place.
+static int environment_checks(rt3_ctx* ctx, const void* rgba, uint32_t n_face) {
+    if (!rgba) return fail(ctx, RT3_E_ARG, "environment array is NULL");
+    if (n_face > RT3_ENV_MAX_FACE) return fail(ctx, RT3_E_ARG, "n_face must be <= " + std::to_string(RT3_ENV_MAX_FACE));
+    return 0;
+}
+int rt3_clear_environment(rt3_ctx* ctx) {
+    if (!ctx) return RT3_E_ARG;
+    if (ctx->env_n == 0) return 0;
+    RT3_HIP(hipSetDevice(ctx->device));
+    if (ctx->ev_acc_recorded) RT3_HIP(hipEventSynchronize(ctx->ev_acc));       // a launch still in flight may read the map
+    ctx->d_env.reset();
+    ctx->env_n = 0;
+    return 0;
+}
+uint32_t rt3_environment_size(rt3_ctx* ctx) { return ctx ? ctx->env_n : 0u; }
+// The copy of both forms: `src` is a device array (kind device-to-device) or, for the host form, the caller's host array, queued on `stream_`.
+static int install_environment(rt3_ctx* ctx, const void* src, hipMemcpyKind kind, uint32_t n_face, void* stream_) {
+    const size_t texels = (size_t)6 * n_face * n_face;
+    hipStream_t stream;
+    int rc;
+    if (ctx->env_n == n_face) {                                     // the same size: into the copy the context has, behind whatever still reads it
+        if ((rc = enter(ctx, stream_, &stream))) return rc;
+        RT3_HIP(hipMemcpyAsync(ctx->d_env.get(), src, texels * sizeof(float4), kind, stream));
+        return leave(ctx, stream);
+    }
+    DevBuf<float4> fresh;
+    if ((rc = fresh.alloc(ctx, texels)) || (rc = enter(ctx, stream_, &stream))) return rc;
+    RT3_HIP(hipMemcpyAsync(fresh.get(), src, texels * sizeof(float4), kind, stream));
+    if ((rc = leave(ctx, stream))) return rc;
+    if (ctx->env_n != 0 && ctx->ev_acc_recorded) RT3_HIP(hipEventSynchronize(ctx->ev_acc));    // the old copy is freed: nothing may still read it
+    ctx->d_env = std::move(fresh);
+    ctx->env_n = n_face;
+    return 0;
+}
+int rt3_set_environment_device(rt3_ctx* ctx, const void* d_rgba, uint32_t n_face, void* stream) {
+    if (!ctx) return RT3_E_ARG;
+    if (n_face == 0) return rt3_clear_environment(ctx);
+    int rc = environment_checks(ctx, d_rgba, n_face);
+    if (rc) return rc;
+    if ((uintptr_t)d_rgba % 16u != 0) return fail(ctx, RT3_E_ARG, "d_rgba must be 16-byte aligned");
+    return install_environment(ctx, d_rgba, hipMemcpyDeviceToDevice, n_face, stream);
+}
+int rt3_set_environment(rt3_ctx* ctx, const float* rgba, uint32_t n_face) {
+    if (!ctx) return RT3_E_ARG;
+    if (n_face == 0) return rt3_clear_environment(ctx);
+    int rc = environment_checks(ctx, rgba, n_face);
+    if (rc) return rc;
+    const size_t texels = (size_t)6 * n_face * n_face;
+    for (size_t i = 0; i < texels; i++)
+        if (!std::isfinite(rgba[4 * i]) || !std::isfinite(rgba[4 * i + 1]) || !std::isfinite(rgba[4 * i + 2]))
+            return fail(ctx, RT3_E_ARG, "environment texel " + std::to_string(i) + " is not finite");
+    if ((rc = install_environment(ctx, rgba, hipMemcpyHostToDevice, n_face, ctx->stream))) return rc;      // (no staging buffer: a large map would stay in it)
+    RT3_HIP(hipStreamSynchronize(ctx->stream));                     // the caller's array is free again
+    return 0;
 }
 
 int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {

@@ -435,6 +435,42 @@ extern "C" uint32_t rt3_scene_cornell(uint32_t grid, rt3_gface* faces, float* ve
 }
 
 // Tests only: what rt3_set_spheres decides before it builds anything (rt3_sphere_plan.hpp, unchanged) — no device, no context.
+// The environment map's lookup law (rt3.h) on the host: the device's env_lookup operation for operation — IEEE f32, each rounded on its
+// own (this file is compiled with -ffp-contract=off), no fused multiply-add.
+namespace {
+inline void env_axis(float c, float m, uint32_t n, uint32_t& i0, uint32_t& i1, float& w) {
+    const float q = c / m;
+    const float u = q * 0.5f + 0.5f;
+    const float f = u * (float)n - 0.5f;
+    const float f0 = std::floor(f);
+    w = f - f0;
+    const int k = (int)std::fmin(std::fmax(f0, -1.0f), (float)n - 1.0f);
+    i0 = (uint32_t)(k > 0 ? k : 0);
+    i1 = (uint32_t)(k + 1 < (int)n - 1 ? k + 1 : (int)n - 1);
+}
+}  // namespace
+extern "C" int rt3_debug_environment_lookup(const float* rgba, uint32_t n, const float d[3], float out_rgb[3]) {
+    if (!rgba || !d || !out_rgb || n == 0 || n > RT3_ENV_MAX_FACE) return RT3_E_ARG;
+    const float x = d[0], y = d[1], z = d[2];
+    const float ax = std::fabs(x), ay = std::fabs(y), az = std::fabs(z);
+    uint32_t f; float m, sc, tc;
+    if (ax >= ay && ax >= az) { f = x < 0.0f ? 1u : 0u; m = ax; sc = x < 0.0f ? z : -z; tc = -y; }
+    else if (ay >= az)        { f = y < 0.0f ? 3u : 2u; m = ay; sc = x; tc = y < 0.0f ? -z : z; }
+    else                      { f = z < 0.0f ? 5u : 4u; m = az; sc = z < 0.0f ? -x : x; tc = -y; }
+    uint32_t i0, i1, j0, j1; float wx, wy;
+    env_axis(sc, m, n, i0, i1, wx);
+    env_axis(tc, m, n, j0, j1, wy);
+    const float* row0 = rgba + 4 * (((size_t)f * n + j0) * n);
+    const float* row1 = rgba + 4 * (((size_t)f * n + j1) * n);
+    for (int c = 0; c < 3; c++) {
+        const float c00 = row0[4 * (size_t)i0 + c], c10 = row0[4 * (size_t)i1 + c], c01 = row1[4 * (size_t)i0 + c], c11 = row1[4 * (size_t)i1 + c];
+        const float top = c00 + wx * (c10 - c00);
+        const float bot = c01 + wx * (c11 - c01);
+        out_rgb[c] = top + wy * (bot - top);
+    }
+    return 0;
+}
+
 extern "C" uint32_t rt3_debug_sphere_plan(const float* center_radius, uint32_t n, float centre[3], uint32_t direct[4]) {
     if (!centre || !direct || (n != 0 && !center_radius)) return 0;
     for (int k = 0; k < 4; k++) direct[k] = 0xFFFFFFFFu;

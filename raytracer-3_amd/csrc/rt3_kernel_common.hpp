@@ -68,6 +68,39 @@ __device__ __forceinline__ void sky(float dx, float dy, float dz, float& r, floa
     g = a * 1.0f + t * 0.7f;
     b = a * 1.0f + t * 1.0f;
 }
+// Environment map lookup (rt3.h): the cube-map face of the direction's major axis, then a bilinear read inside that face, clamped to
+// its edge.  Every operation is an IEEE f32 add, subtract, multiply, divide, compare or floor, rounded on its own (no fma_: tests/environment_ref.py and
+// rt3_debug_environment_lookup restate it bit for bit).  env_axis: one in-face coordinate c of major-axis length m -> the two texel indices and the weight.
+// A NaN floor becomes -1 before the conversion, so whatever the direction holds the four 16-byte loads stay inside the map.
+__device__ __forceinline__ void env_axis(float c, float m, uint32_t n, uint32_t& i0, uint32_t& i1, float& w) {
+    const float q = c / m;
+    const float u = q * 0.5f + 0.5f;
+    const float f = u * (float)n - 0.5f;
+    const float f0 = __builtin_floorf(f);
+    w = f - f0;
+    const int k = (int)__builtin_fminf(__builtin_fmaxf(f0, -1.0f), (float)n - 1.0f);
+    i0 = (uint32_t)(k > 0 ? k : 0);
+    i1 = (uint32_t)(k + 1 < (int)n - 1 ? k + 1 : (int)n - 1);
+}
+__device__ __forceinline__ void env_lookup(const float4* __restrict__ env, uint32_t n, float x, float y, float z, float& r, float& g, float& b) {
+    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y), az = __builtin_fabsf(z);
+    uint32_t f; float m, sc, tc;
+    if (ax >= ay && ax >= az) { f = x < 0.0f ? 1u : 0u; m = ax; sc = x < 0.0f ? z : -z; tc = -y; }
+    else if (ay >= az)        { f = y < 0.0f ? 3u : 2u; m = ay; sc = x; tc = y < 0.0f ? -z : z; }
+    else                      { f = z < 0.0f ? 5u : 4u; m = az; sc = z < 0.0f ? -x : x; tc = -y; }
+    uint32_t i0, i1, j0, j1; float wx, wy;
+    env_axis(sc, m, n, i0, i1, wx);
+    env_axis(tc, m, n, j0, j1, wy);
+    const float4* row0 = env + ((size_t)f * n + j0) * n;
+    const float4* row1 = env + ((size_t)f * n + j1) * n;
+    const float4 c00 = row0[i0], c10 = row0[i1], c01 = row1[i0], c11 = row1[i1];
+    const float tr = c00.x + wx * (c10.x - c00.x), br = c01.x + wx * (c11.x - c01.x);
+    const float tg = c00.y + wx * (c10.y - c00.y), bg = c01.y + wx * (c11.y - c01.y);
+    const float tb = c00.z + wx * (c10.z - c00.z), bb = c01.z + wx * (c11.z - c01.z);
+    r = tr + wy * (br - tr);
+    g = tg + wy * (bg - tg);
+    b = tb + wy * (bb - tb);
+}
 // glm::packUnorm4x8(vec4(1, b, g, r)), glm/detail/func_packing.inl:67-83
 __device__ __forceinline__ uint32_t pack_channel(float c) {
     float m = c < 0.0f ? 0.0f : c;
@@ -121,7 +154,12 @@ struct Rgb { float r, g, b; };   // one radiance record of the sample storage (t
 //   Query      item = one of the caller's rays, the nearest hit or the occlusion word stored: rt3_intersect*, rt3_occluded*, the AOV pass
 //   List       Render over a list of pixels (TraceArgs::active): the later rounds of rt3_render_path_adaptive*
 //   Rays       item = (sample, one of the caller's rays), shaded as a render's (TraceArgs::ray_keys): rt3_radiance*
-enum class Form : uint32_t { Render, RenderRef, Query, List, Rays };
+//   RenderEnv, ListEnv, RaysEnv   Render, List and Rays while an environment map is set (rt3_set_environment*): the same kernel with
+//              ONE difference, the miss of shade_lane reads the map where the twin evaluates the sky.  Their launch argument is an EnvTraceArgs (below).
+enum class Form : uint32_t { Render, RenderRef, Query, List, Rays, RenderEnv, ListEnv, RaysEnv };
+constexpr bool is_env(Form f) { return f == Form::RenderEnv || f == Form::ListEnv || f == Form::RaysEnv; }
+// The twin of an environment form, and every other form itself: what a kernel body and the refill helpers branch on.
+constexpr Form base_form(Form f) { return f == Form::RenderEnv ? Form::Render : f == Form::ListEnv ? Form::List : f == Form::RaysEnv ? Form::Rays : f; }
 // Batched ray queries (the QUERY forms of the trace kernels; rt3_intersect* / rt3_occluded*): item k of a launch is ray k
 // of the caller's rt3_ray[] (q_rays: two float4 per ray, origin, t_max | direction, pad); its result goes to q_out[k], an rt3_hit (16 bytes), or with
 // q_occluded one word.  They share the places of fields only the path kernels read (the VALU scan's face bounds, the sample storage, the render
@@ -178,6 +216,12 @@ struct TraceArgs {
     // the struct, and the list forms, which load `active` next to them, changed their scalar register allocation: DESIGN.md 5.2l.)
     union { const uint32_t* active; const uint32_t* ray_keys; };
 };
+// The launch argument of the environment forms: TraceArgs with the map behind it.  A struct of their own, so that TraceArgs — and with it the argument
+// layout and the code of every other kernel — stays what it was.  The helpers keep taking a TraceArgs&; shade_lane, the one reader,
+// gets the map back with env_of().  env: 6 faces of env_n x env_n float4 texels (+X, -X, +Y, -Y, +Z, -Z; row 0 first), 1 <= env_n <= 2048.
+struct EnvTraceArgs : TraceArgs { const float4* env; uint32_t env_n; uint32_t env_pad; };
+template <Form F> using trace_args = std::conditional_t<is_env(F), EnvTraceArgs, TraceArgs>;
+__device__ __forceinline__ const EnvTraceArgs& env_of(const TraceArgs& A) { return static_cast<const EnvTraceArgs&>(A); }   // only where A IS one: an environment form
 
 struct Path {
     float ox, oy, oz, dx, dy, dz;

@@ -38,8 +38,10 @@ static_assert(lev_lds_fixed(3, true) + lev_resident_blocks(3) * 2048u < 160u * 1
 
 // Form::Query: the batched ray queries' form (the nearest-hit key goes to query_sink instead of shading).
 // Form::Rays: rt3_radiance*'s form (the refill takes the caller's rays, rays_path, and everything behind it is the render's).
-template <bool HAS_TRI, bool HAS_SPH, Form F, uint32_t LEVELS, bool RES>
-__global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
+// Environment forms (FX): the body is the twin's (F = base_form(FX)); shade_lane alone gets FX.
+template <bool HAS_TRI, bool HAS_SPH, Form FX, uint32_t LEVELS, bool RES>
+__global__ __launch_bounds__(kTB) void k_trace_levels(const trace_args<FX> A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
+    constexpr Form F = base_form(FX);
     static_assert(F != Form::RenderRef || (HAS_TRI && !HAS_SPH), "RenderRef: face-only scenes");
     constexpr bool REF = F == Form::RenderRef, QUERY = F == Form::Query;
     static_assert(LEVELS == 3 || LEVELS == 4, "three or four levels");
@@ -312,7 +314,7 @@ __global__ __launch_bounds__(kTB) void k_trace_levels(const TraceArgs A, const u
         if constexpr (QUERY) query_sink(A, P, alive, keys[lane]);
         else {
             key_decode(keys[lane], kind, ibest, tbest);
-            shade_lane<HAS_TRI, HAS_SPH, F>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
+            shade_lane<HAS_TRI, HAS_SPH, FX>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
         }
     }
     if (lane == 0 && casts != 0) { atomicAdd(A.cast_counter, casts); atomicAdd(A.cast_counter + 1, mfmas); atomicAdd(A.cast_counter + 2, exact); atomicAdd(A.cast_counter + 3, bound_tests); }

@@ -887,10 +887,11 @@ __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__bui
 // wave time per part of a restock (RT3_PROFILE_PHASES; unused otherwise)
 struct RestockPhases { unsigned long long total = 0, raygen = 0, fetch = 0, tests = 0, shade = 0, compact = 0; };
 struct SphereMirror { const float4* sph; const float* invr; const float4* mat; const uint32_t* kind; uint32_t n_blocks; const uint4* ctr_tab; };     // LDS
-template <Form F>
+template <Form FX>
 __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, const SphereMirror& S, uint32_t lane, bool& alive, Path& P, TracedStock& Q,
                                                          uint32_t& chunk_next, uint32_t& chunk_end, bool& exhausted, unsigned long long& casts,
                                                          unsigned long long& exact, RestockPhases& ph) {
+    constexpr Form F = base_form(FX);                                          // (an environment form: its twin's restock, shade_lane alone gets FX)
     static_assert(F == Form::Render || F == Form::List, "refill_from_traced_stock: k_trace_mfma32's render forms");
     constexpr bool LIST = F == Form::List;
     const unsigned long long need = __ballot(!alive);
@@ -1009,7 +1010,7 @@ __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, con
             uint32_t kind, ibest;
             float tbest;
             key_decode(key, kind, ibest, tbest);
-            shade_lane<false, true, F, RT3_CTR_TABLE != 0>(A, T, live, kind, ibest, tbest, S.sph, S.invr, S.mat, S.kind, S.ctr_tab);
+            shade_lane<false, true, FX, RT3_CTR_TABLE != 0>(A, T, live, kind, ibest, tbest, S.sph, S.invr, S.mat, S.kind, S.ctr_tab);
             RT3_RPHASE(ph.shade)
             // the survivors move to lanes [0, n), the rest behind them: a permutation of the wave (ds_permute: every lane sends) — the identity when no
             // lane survives (a strip of sky) or all 64 do
@@ -1049,8 +1050,10 @@ __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, con
 // k_trace_mfma's load (2.0-2.2 GHz), holds 2.3-2.4 GHz here — and a kernel bound by vector-ALU issue runs at the clock.
 // Form::Query: the batched ray queries' form (refill from the caller's rays, no ray stock; the nearest-hit key goes to query_sink instead of shading).
 // Form::Rays: rt3_radiance*'s form (the caller's rays through rays_path, no ray stock and no strip lists; shading as in the render form, counter-hash table included).
-template <Form F>
-__global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u32x4* __restrict__ frags, uint32_t n_blocks) {
+// Environment forms (FX): the body is the twin's (F = base_form(FX)); shade_lane — here and in the restock — alone gets FX.
+template <Form FX>
+__global__ __launch_bounds__(kMB) void k_trace_mfma32(const trace_args<FX> A, const u32x4* __restrict__ frags, uint32_t n_blocks) {
+    constexpr Form F = base_form(FX);
     static_assert(F != Form::RenderRef, "k_trace_mfma32: sphere scenes, no RenderRef");
     constexpr bool QUERY = F == Form::Query;
     extern __shared__ u32x4 lds_dyn[];
@@ -1100,7 +1103,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
 
     for (;;) {
         if constexpr (F == Form::Query || F == Form::Rays) refill_queries<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else refill_from_traced_stock<F>(A, mirror, lane, alive, P, Q, chunk_next, chunk_end, exhausted, primary_casts, exact, ph_restock);
+        else refill_from_traced_stock<FX>(A, mirror, lane, alive, P, Q, chunk_next, chunk_end, exhausted, primary_casts, exact, ph_restock);
         RT3_SPHASE(ph_refill)
         const unsigned long long live = __ballot(alive);
         if (live == 0ull) break;
@@ -1134,7 +1137,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const TraceArgs A, const u
         if constexpr (QUERY) query_sink(A, P, alive, keys[lane]);
         else {
             key_decode(keys[lane], kind, ibest, tbest);
-            shade_lane<false, true, F, CTR>(A, P, alive, kind, ibest, tbest, s_sph, s_invr, s_mat, s_kind, ctr_tab);
+            shade_lane<false, true, FX, CTR>(A, P, alive, kind, ibest, tbest, s_sph, s_invr, s_mat, s_kind, ctr_tab);
         }
         RT3_SPHASE(ph_shade)
     }
@@ -1212,8 +1215,11 @@ constexpr uint32_t kResidentBlocks = (160u * 1024u - kTB * 8u - (kTB / 64u) * kP
 // Form::Query: the batched ray queries' form (the nearest-hit key goes to query_sink instead of shading).
 // Form::Rays: rt3_radiance*'s form (the refill takes the caller's rays, rays_path, and everything behind it is the render's).
 // Neither has a flat (GT = GS = SUP = 1) form.
-template <bool HAS_TRI, bool HAS_SPH, Form F, uint32_t GT, uint32_t GS, uint32_t SUP, bool RES>
-__global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
+// Environment forms (FX; grouped only): the body is the twin's (F = base_form(FX)); shade_lane alone gets FX.
+template <bool HAS_TRI, bool HAS_SPH, Form FX, uint32_t GT, uint32_t GS, uint32_t SUP, bool RES>
+__global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const trace_args<FX> A, const u32x4* __restrict__ tri_frags, const u32x4* __restrict__ sph_frags) {
+    constexpr Form F = base_form(FX);
+    static_assert(GT > 1 || GS > 1 || SUP > 1 || !is_env(FX), "the flat filter has no environment form");
     static_assert(F != Form::RenderRef || (HAS_TRI && !HAS_SPH), "RenderRef: face-only scenes");
     static_assert(GT > 1 || GS > 1 || SUP > 1 || (F != Form::Query && F != Form::Rays), "the flat filter has no Query or Rays form");
     constexpr bool REF = F == Form::RenderRef, QUERY = F == Form::Query;
@@ -1560,7 +1566,7 @@ __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const TraceArgs A, con
         if constexpr (QUERY) query_sink(A, P, alive, keys[lane]);
         else {
             key_decode(keys[lane], kind, ibest, tbest);
-            shade_lane<HAS_TRI, HAS_SPH, F>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
+            shade_lane<HAS_TRI, HAS_SPH, FX>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);
         }
     }
     if (lane == 0 && casts != 0) { atomicAdd(A.cast_counter, casts); atomicAdd(A.cast_counter + 1, mfmas); atomicAdd(A.cast_counter + 2, exact); atomicAdd(A.cast_counter + 3, bound_tests); }

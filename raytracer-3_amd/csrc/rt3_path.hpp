@@ -168,6 +168,8 @@ __device__ __forceinline__ void stock_pop(const TracedStock& Q, uint32_t src, bo
 // it as it is (SequentialRenderer.cpp:77,105-107); the scatter formulas then get the unit direction.
 // CTR: ctr_tab is the counter-hash table (rt3_kernel_common.hpp, kCtrDepthCap rows in LDS): the inner hash of rnd(base, ctr + k) depends on the
 // depth alone, so a lane below the cap reads its row instead of computing three hashes; at or beyond the cap it computes them as rnd() does.
+// Environment forms (is_env(F); A is then an EnvTraceArgs): a miss adds throughput x env_lookup(direction) where the twin adds throughput x sky — the one
+// difference between an environment form and its twin.
 template <bool HAS_TRI, bool HAS_SPH, Form F, bool CTR = false>
 __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& alive, uint32_t kind, uint32_t ibest, float tbest,
                                            const float4* sph, const float* sph_invr, const float4* sph_mat, const uint32_t* sph_kind,
@@ -180,7 +182,8 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
         if (kind == 0) {
             if (!(A.flags & RT3_FLAG_BLACK_BACKGROUND)) {
                 float r, g, b;
-                sky(dx, dy, dz, r, g, b);
+                if constexpr (is_env(F)) env_lookup(env_of(A).env, env_of(A).env_n, dx, dy, dz, r, g, b);
+                else sky(dx, dy, dz, r, g, b);
                 P.lr = fma_(P.tr, r, P.lr); P.lg = fma_(P.tg, g, P.lg); P.lb = fma_(P.tb, b, P.lb);
             }
             done = true;

@@ -262,8 +262,10 @@ __global__ __launch_bounds__(kBlock) void k_trace(const TraceArgs A) {
 // Scene records are wave-uniform loads through the constant address space (scalar cache); one path per lane, refill by ballot.
 // Form::Query: the batched ray queries' arbiter (rt3_intersect* / rt3_occluded* under the same switch): the running best starts at the ray's t_max.
 // Form::Rays: rt3_radiance*'s arbiter (the caller's rays, shaded as a render's: rays_path).  Every form exists.
-template <Form F>
-__global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
+// Environment forms (FX): the body is the twin's (F = base_form(FX)); shade_lane alone gets FX.
+template <Form FX>
+__global__ __launch_bounds__(kBlock) void k_trace_brute(const trace_args<FX> A) {
+    constexpr Form F = base_form(FX);
     constexpr bool REF = F == Form::RenderRef, QUERY = F == Form::Query;
     const uint32_t lane = lane_id();
     Path P;
@@ -300,7 +302,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_brute(const TraceArgs A) {
         if constexpr (QUERY) {
             if (alive) query_store(A, P.slot, kind, kind != 0u ? ibest : 0xFFFFFFFFu, kind != 0u ? tbest : __builtin_inff());
             alive = false;
-        } else shade_lane<true, true, F>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);   // kind says which arrays to read
+        } else shade_lane<true, true, FX>(A, P, alive, kind, ibest, tbest, A.sph, A.sph_invr, A.sph_mat, A.sph_kind);   // kind says which arrays to read
     }
     if (lane == 0 && casts != 0) atomicAdd(A.cast_counter, casts);
 }

@@ -259,6 +259,17 @@ void HipRenderer::regroup(bool spheres, bool mesh) {
         if (rt3_regroup(c, what) != 0) throw Fatal(rt3_last_error(c));
 }
 
+void HipRenderer::set_environment(const std::vector<float>& rgba, uint32_t n_face) {
+    if (n_face == 0 || rgba.size() != (size_t)24 * n_face * n_face) throw Fatal("set_environment: rgba must hold 6 x n_face x n_face texels of 4 floats");
+    for (rt3_ctx* c : ctx)
+        if (rt3_set_environment(c, rgba.data(), n_face) != 0) throw Fatal(rt3_last_error(c));
+}
+
+void HipRenderer::clear_environment() {
+    for (rt3_ctx* c : ctx)
+        if (rt3_clear_environment(c) != 0) throw Fatal(rt3_last_error(c));
+}
+
 void HipRenderer::update_mesh(const std::vector<float>& vertices, const std::vector<rt3_gface>& faces) {
     if (!faces.empty() && faces.size() != n_faces) throw Fatal("update_mesh: faces must hold the mesh's face count, or be empty");
     for (rt3_ctx* c : ctx)

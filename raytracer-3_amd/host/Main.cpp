@@ -7,7 +7,7 @@
 // usage error, -1 on a fatal backend error.  Fixed: `--key=value`, which the reference mis-parses (Main.cpp:110).
 // Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr, --denoise (PFM files),
 // --frames, --orbit and --slide (a sequence, denoised temporally), --adaptive and --counts (--spp as a budget), --rays and --radiance
-// (path-traced radiance along rays read from a file).
+// (path-traced radiance along rays read from a file), --env (an environment map from a PFM of six stacked cube faces).
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -48,6 +48,7 @@ struct Options {
     uint32_t adaptive_min = 0, adaptive_step = 16;                 // (min 0: not given = min(16, spp))
     std::string counts_path;                                       // --adaptive: the samples per pixel as a 1-channel PFM
     std::string rays_path, radiance_path;                          // Mode X: rt3_ray records in, their radiance out as a PFM of n x 1
+    std::string env_path;                                          // Mode X: the environment map, a colour PFM of N x 6N (the six faces stacked)
 };
 
 void print_usage(const char* exe) {
@@ -79,6 +80,8 @@ void print_usage(const char* exe) {
               << "\t   --rays\tMode X, with --radiance: a file of raw little-endian rt3_ray records (32 bytes each: origin, t_max = +inf, unit direction, pad).\n"
               << "\t   --radiance\tMode X, with --rays: write the path-traced radiance along those rays (--spp samples per ray, --depth, --seed) to this\n"
               << "\t\t\tpath as a 3-channel PFM, n wide and 1 high.\n"
+              << "\t   --env\tMode X: light the scene with a cube map where a ray leaves it: a colour PFM, N wide and 6N high, the faces +X, -X, +Y, -Y,\n"
+              << "\t\t\t+Z, -Z stacked from top to bottom, N up to 2048. The render, --radiance and --aov use it.\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -120,7 +123,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
                            key == "--slide" || key == "--adaptive" || key == "--counts" || key == "--regroup" ||
-                           key == "--rays" || key == "--radiance";
+                           key == "--rays" || key == "--radiance" || key == "--env";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -186,6 +189,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         else if (key == "--counts") opt.counts_path = value;
         else if (key == "--rays") opt.rays_path = value;
         else if (key == "--radiance") opt.radiance_path = value;
+        else if (key == "--env") opt.env_path = value;
         else if (key == "--regroup") {
             if (!parse_u32(value, "regroup", "Regroup", &opt.regroup)) return -1;
             if (opt.regroup == 0) { std::cerr << "--regroup must be at least 1." << std::endl; return -1; }
@@ -210,6 +214,10 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     }
     if (mode_r && !opt.rays_path.empty()) {
         std::cerr << "--rays and --radiance need the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
+    if (mode_r && !opt.env_path.empty()) {
+        std::cerr << "--env needs the path tracer (Mode X): pass --spp." << std::endl;
         return -1;
     }
     if (mode_r && opt.adaptive) {
@@ -251,6 +259,30 @@ int parse_cli(Options& opt, int argc, const char** argv) {
 // The spheres of the scene on the renderer (--slide moves them from frame to frame).
 std::vector<float> scene_cr;
 std::vector<rt3_material> scene_mats;
+
+// --env: a colour PFM ("PF", little-endian: a negative scale), N wide and 6N high -> the texels rt3_set_environment takes.  A PFM stores its rows
+// bottom to top; with that undone, rows [f N, (f + 1) N) from the top are face f, its row 0 first.
+std::vector<float> read_env_pfm(const std::string& path, uint32_t& n_face) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) throw Fatal("Could not open '" + path + "'");
+    std::string magic;
+    long long w = 0, h = 0;
+    double scale = 0.0;
+    in >> magic >> w >> h >> scale;
+    if (!in || in.get() == EOF) throw Fatal("'" + path + "' is not a PFM file");
+    if (magic != "PF" || !(scale < 0.0)) throw Fatal("'" + path + "' must be a little-endian colour PFM (PF, negative scale)");
+    if (w < 1 || w > (long long)RT3_ENV_MAX_FACE || h != 6 * w)
+        throw Fatal("'" + path + "' is " + std::to_string(w) + " x " + std::to_string(h) + ": an environment map is N wide and 6N high, N up to " +
+                    std::to_string(RT3_ENV_MAX_FACE));
+    std::vector<float> rgb((size_t)3 * w * h);
+    if (!in.read(reinterpret_cast<char*>(rgb.data()), (std::streamsize)(rgb.size() * sizeof(float)))) throw Fatal("'" + path + "' ends before its pixels do");
+    std::vector<float> rgba((size_t)4 * w * h, 0.0f);
+    for (long long y = 0; y < h; y++)                                // y: row from the top = texel row of the stacked faces
+        for (long long x = 0; x < w; x++)
+            for (int c = 0; c < 3; c++) rgba[4 * (size_t)(y * w + x) + c] = rgb[3 * (size_t)((h - 1 - y) * w + x) + c];
+    n_face = (uint32_t)w;
+    return rgba;
+}
 
 template <class Fn>
 void sphere_scene(HipRenderer& r, Fn generate) {
@@ -347,6 +379,11 @@ int main(int argc, const char** argv) {
         }
         const bool from_file = opt.scene.size() > 6 && opt.scene.compare(opt.scene.size() - 6, 6, ".scene") == 0;
         if (opt.scene != "builtin" && !from_file && path.spp == 0) path.spp = 16;   // the analytic scenes only exist in Mode X
+        if (!opt.env_path.empty()) {
+            uint32_t n_face = 0;
+            const std::vector<float> rgba = read_env_pfm(opt.env_path, n_face);
+            renderer.set_environment(rgba, n_face);
+        }
         const uint32_t seed0 = path.seed;
         const bool temporal = opt.frames > 1 && !opt.denoise_path.empty();
         const rt3_temporal_params tp{ { 5, 128, 4.0f, 1.0f }, 0.2f, 0.2f, 2.0f, 0.9f };       // the defaults of DESIGN.md 4.11 and 4.12

@@ -54,6 +54,10 @@ public:
     void update_mesh(const std::vector<float>& vertices_xyzw, const std::vector<rt3_gface>& faces = {});
     // the classes that have a scene get the group order of a full upload back after updates (rt3_regroup): nothing a render returns changes
     void regroup(bool spheres = true, bool mesh = true);
+    // Mode X: the cube map every ray that leaves the scene reads, on every device (rt3_set_environment): 6 faces of n_face x n_face texels,
+    // 4 floats each (r, g, b, ignored), faces +X, -X, +Y, -Y, +Z, -Z, row 0 first; it stays until it is replaced or cleared
+    void set_environment(const std::vector<float>& rgba, uint32_t n_face);
+    void clear_environment();
     rt3_stats stats() const;                                                     // of device 0's last render
     // Mode X only, full frames (row 0 on top) assembled from the device shards: the first-hit AOVs of the current options (rt3_render_aov),
     // and the linear (r, g, b, 0) frame of the last render (rt3_accum_resolve)

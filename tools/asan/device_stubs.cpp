@@ -46,6 +46,10 @@ void* rt3_device_alloc_words(rt3_ctx*, uint64_t) { return nullptr; }
 void rt3_device_free(rt3_ctx*, void*) {}
 int rt3_device_read_words(rt3_ctx*, const void*, uint64_t, uint32_t*) { return RT3_E_DEVICE; }
 int rt3_get_stats(rt3_ctx*, rt3_stats*) { return RT3_E_DEVICE; }
+int rt3_set_environment(rt3_ctx*, const float*, uint32_t) { return RT3_E_DEVICE; }      // (rt3_debug_environment_lookup is host code: csrc/rt3_host.cpp)
+int rt3_set_environment_device(rt3_ctx*, const void*, uint32_t, void*) { return RT3_E_DEVICE; }
+int rt3_clear_environment(rt3_ctx*) { return RT3_E_DEVICE; }
+uint32_t rt3_environment_size(rt3_ctx*) { return 0; }
 int rt3_debug_force_plain_mode_r(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_force_brute(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_force_flat_filter(rt3_ctx*, int) { return RT3_E_DEVICE; }

@@ -8,6 +8,8 @@ rt3_kernel_common.hpp, and renames no existing kernel).  Prints one line per ker
 does not have, and ends with the number of existing kernels that gained scratch or lost occupancy (exit code 1 if there is one).
 
     python tools/kernel_resources.py PARENT.log TREE.log > profiles/radiance_kernel_resources.log
+
+--brief leaves out the kernels whose figures did not change (the last line still counts them): the log of a change that adds forms and moves nothing.
 """
 import re
 import shutil
@@ -53,7 +55,9 @@ def table(path):
 
 
 def main():
-    a, b = table(sys.argv[1]), table(sys.argv[2])
+    brief = "--brief" in sys.argv[1:]
+    paths = [x for x in sys.argv[1:] if x != "--brief"]
+    a, b = table(paths[0]), table(paths[1])
     print("kernel | " + " | ".join(KEYS) + "     (parent -> this tree; one figure: unchanged)")
     worse = []
     for n in sorted(set(a) | set(b)):
@@ -66,7 +70,8 @@ def main():
         if n in a and (int(y[KEYS[3]]) > int(x[KEYS[3]]) or int(y[KEYS[4]]) < int(x[KEYS[4]])):
             worse.append(n)
             tag = "WORSE "
-        print("%s%s | %s" % (tag, n, " | ".join(cells)))
+        if not brief or n not in a or x != y:
+            print("%s%s | %s" % (tag, n, " | ".join(cells)))
     print("existing kernels: %d, new kernels: %d, existing kernels with a changed figure: %d, with new scratch or lower occupancy: %d"
           % (len(set(a) & set(b)), len(set(b) - set(a)), sum(1 for n in set(a) & set(b) if any(a[n].get(k) != b[n].get(k) for k in KEYS)), len(worse)))
     return 1 if worse else 0
