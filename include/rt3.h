@@ -32,8 +32,8 @@ extern "C" {
  * sizeof(rt3_stats) bytes of THIS version).  History: 1 = round 1; 2 = + mfma_instructions / exact_tests in rt3_stats, progressive
  * accumulation, rt3_gather_rows; 3 = + rt3_abi_version itself, one stream convention (below),
  * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh*, with
- * rt3_render_path_adaptive* (one new struct of its own), with rt3_regroup* and with the environment map (rt3_set_environment*): functions were
- * only added, no existing struct changed. */
+ * rt3_render_path_adaptive* (one new struct of its own), with rt3_regroup*, with the environment map (rt3_set_environment*) and with its
+ * importance sampling (RT3_FLAG_ENV_SAMPLING: one flag bit and two test-only functions): functions were only added, no existing struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
 
@@ -95,6 +95,9 @@ typedef struct rt3_material {
 /* Keep a per-pixel, per-channel sum of squared sample radiances beside the sums (variance estimates; the
  * "sample storage" half of reduce_v1.glsl's intent).  Read both back with rt3_accum_download(). */
 #define RT3_FLAG_VARIANCE          8u
+/* Importance sampling of the environment map with one shadow ray per Lambert scatter (next-event estimation): "Environment map: sampling"
+ * below.  Needs a map (rt3_set_environment*); without the flag every entry point returns what it returned before the flag existed. */
+#define RT3_FLAG_ENV_SAMPLING      16u
 
 /* Parameters of a Mode-X render.  tile_*: interleaved row-block sharding of the framebuffer
  * (design intent: BlockInfo{x,y,w,h} of raytracer_v4.glsl:70-79).  Row-block b (tile_rows rows) belongs
@@ -548,7 +551,7 @@ int rt3_denoise_temporal_motion_device(rt3_ctx* ctx, uint32_t width, uint32_t he
 typedef struct rt3_radiance_params {   /* 24 bytes */
     uint32_t max_depth;      /* ray casts per path, >= 1, as rt3_params */
     uint32_t seed;
-    uint32_t flags;          /* 0 or RT3_FLAG_BLACK_BACKGROUND; any other bit: RT3_E_ARG */
+    uint32_t flags;          /* 0, RT3_FLAG_BLACK_BACKGROUND or RT3_FLAG_ENV_SAMPLING (not both); any other bit: RT3_E_ARG */
     uint32_t sample_begin;   /* first sample index */
     uint32_t sample_count;   /* samples per ray, >= 1; sample_begin + sample_count <= 2^31 */
     float    t_min;          /* finite, >= 0 */
@@ -613,7 +616,7 @@ int rt3_radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, ui
  * Errors.  n_face == 0 clears the map (the pointer may then be NULL).  RT3_E_ARG, with the previous map left in place: a NULL ctx or array,
  * n_face > RT3_ENV_MAX_FACE, a misaligned device pointer, and — host form only, the device form does not validate texels — a texel whose r, g
  * or b is not finite (the message names the lowest such texel index).
- * Out of scope: importance sampling of the map (a small bright sun is noisy), seamless filtering across face edges, mip levels, rotation. */
+ * Out of scope: seamless filtering across face edges, mip levels, rotation.  (Importance sampling of the map: RT3_FLAG_ENV_SAMPLING, below.) */
 #define RT3_ENV_MAX_FACE 2048u
 /* Host array of 6 * n_face * n_face float4; the context copies it and owns the copy.  Synchronous. */
 int      rt3_set_environment(rt3_ctx* ctx, const float* rgba, uint32_t n_face);
@@ -626,6 +629,60 @@ uint32_t rt3_environment_size(rt3_ctx* ctx);
 /* Host only, no device and no context: the lookup law above in C, out_rgb = env(d).  RT3_E_ARG for a NULL pointer, n_face == 0 or
  * n_face > RT3_ENV_MAX_FACE.  The tests compare it and the device with tests/environment_ref.py bit for bit. */
 int      rt3_debug_environment_lookup(const float* rgba, uint32_t n_face, const float d[3], float out_rgb[3]);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Environment map: sampling  (DESIGN.md 4.20, 5.2o): RT3_FLAG_ENV_SAMPLING in rt3_params.flags / rt3_radiance_params.flags
+ * ------------------------------------------------------------------------------------------------- */
+/* Without the flag a path receives the map only where a scattered ray happens to leave the scene; a small bright region (a sun of a few texels)
+ * is then found by a vanishing share of the bounces.  With it every Lambert scatter also draws a direction from the map's own brightness and
+ * casts one shadow ray (next-event estimation).  Opt-in per call; rt3_render_path*, rt3_render_path_range* (shards included) and rt3_radiance*
+ * accept it (the defining property of rt3_radiance holds with it).
+ * The table.  Integers wherever something is added up, so it does not depend on the order it is built in.  M = min(N, 256) cells per face
+ * edge; cell c of an axis is the interval [c / M, (c + 1) / M) of the face coordinate u of the lookup law.  A texel's brightness is
+ * l = (max(r, 0) + max(g, 0)) + max(b, 0), the NaN-dropping max (a NaN counts as 0), +inf clamped to FLT_MAX.  A cell's weight is w = lmax * sa:
+ * lmax the largest l among the texels the bilinear lookup can read inside the cell — per axis the texels floor(c N / M - 0.5) to
+ * floor((c + 1) N / M - 0.5) + 1, clamped inside the face; for N <= 256 the cell's own texel and a ring of one around it — so w > 0 wherever
+ * the lookup can be positive (negative radiance is not sampled: a texel such as (-1, -1, -1) has brightness 0, and on a map with negative
+ * channels the flagged estimator differs from the plain one where only such texels are read); sa = 1 / (g * sqrtf(g)) with g = (s * s + t * t) + 1 at the cell's centre s = ((col + 0.5f) / M) * 2 - 1, t
+ * likewise from the row; every operation f32, rounded on its own.  With W the largest w of the map, q = 0 if w == 0 and otherwise
+ * max(1, (uint32_t)floorf(w / W * 16777216.0f)); cdf is the inclusive uint64 prefix sum of q in cell order (face, row, column), total its last
+ * entry.  The table (at most 6 * 256^2 * 12 bytes) is built on the device by the first call that carries the flag, queued on that call's stream
+ * inside the event chain as an update is, and kept until the map is set or cleared again; rt3_set_environment* costs what it cost.
+ * The sampling law.  At a Lambert scatter of a path with RNG base `base` at depth d let ctr = 1 + 8 (d + 1) and w_k = hash_u32(base ^
+ * hash_u32(ctr + k)), k = 3..6 (the scatter itself draws k = 0..2).  x = (uint64_t)w3 << 32 | w4, T = the high 64 bits of x * total; the cell
+ * is the first index with cdf[index] > T (a cell with q = 0 is never drawn).  a = u01(w5), b = u01(w6);
+ * s = ((col + a) / M) * 2 - 1, t = ((row + b) / M) * 2 - 1 in f32.  The direction is the lookup's face cases inverted,
+ *     +X (1, -t, -s)   -X (-1, -t, s)   +Y (s, 1, t)   -Y (s, -1, -t)   +Z (s, -t, 1)   -Z (-s, -t, -1)
+ * times 1 / sqrtf(fmaf(vz, vz, fmaf(vy, vy, vx * vx))), and its density per solid angle is
+ *     pdf = ((float)q / (float)total) * ((float)(M * M) * 0.25f) * (g * sqrtf(g)),   g = (s * s + t * t) + 1 at the sampled (s, t).
+ * The path law with the flag.  A Lambert hit that scatters (depth + 1 < max_depth) scatters exactly as without it — the continuation rays are
+ * the plain render's — and draws w by the law above.  With T' = throughput * albedo and c = n.w (n the normal turned towards the ray, the dot
+ * product as two fused multiply-adds): when total == 0 or not c > 0 nothing more happens; otherwise one shadow ray (hit point, w) is traced
+ * with the nearest-hit rule (t_min, t_max = +inf) and, if it meets nothing, L = fma(T' * (c / (3.14159274f * pdf)), env(w), L) per channel;
+ * if it meets something L is left as it is.  A later miss of that path adds nothing while its most recent scatter was a Lambert scatter (the
+ * shadow ray has accounted for the map); after a metal or glass scatter, and for a primary ray, a miss reads the map as always.  FLAT, metal,
+ * dielectric and the depth cut-off are unchanged.  Shadow rays are not a depth; they count in ray_casts and in the filter's counters.
+ * Multiple importance sampling is not done: on a smooth map the estimator can be noisier per sample than the plain one.
+ * Errors.  RT3_E_STATE: the flag with no map set.  RT3_E_ARG: together with RT3_FLAG_BLACK_BACKGROUND or RT3_FLAG_REFERENCE_PRIMARY;
+ * rt3_render_path_adaptive* with the flag (its later rounds would need a list form of the sampling kernels: none is built).
+ * rt3_render_aov*, rt3_camera_rays* and the accumulation calls accept the bit and ignore it. */
+/* A declaration that exists for the test suite alone (no render calls it).  The macro is empty.  Why it follows the declarator: the test that
+ * came with the environment map (tests/test_environment_abi.py) pins the exact set of `int|uint32_t rt3_*environment*(...);` declarations of
+ * this header by a pattern that ends in `);`, and the two functions below carry "environment" in their names; with the marker between `)` and
+ * `;` that pinned set stays what it was.  Once that test's list is extended the marker can go. */
+#define RT3_TEST_ONLY
+/* Host only, no device and no context: the table built serially and the sampling law above in C for one (base, depth).  *cell = the cell drawn,
+ * dir = the unit direction, *pdf = its density; a map whose table has total == 0 gives *cell = 0xFFFFFFFF, dir = 0 and *pdf = 0 (nothing is
+ * sampled).  RT3_E_ARG for a NULL pointer, n_face == 0 or n_face > RT3_ENV_MAX_FACE.  tests/environment_sample_ref.py restates it bit for bit.
+ * Cost, as befits a debug function: the calling thread keeps a copy of the last map and its table for the thread's life (96 n_face^2 bytes plus
+ * the table: about 400 MB at n_face = 2048) and every call compares the whole map with that copy before it reuses the table. */
+int      rt3_debug_environment_sample(const float* rgba, uint32_t n_face, uint32_t base, uint32_t depth, uint32_t* cell, float dir[3],
+                                      float* pdf) RT3_TEST_ONLY;
+/* The device's table of the map the context holds (built first if no call with the flag has built it): q_out and cdf_out take 6 M^2 entries,
+ * capacity_cells is what they can hold, *cells_per_edge = M (set whenever a map is set).  RT3_E_STATE without a map, RT3_E_ARG for a NULL
+ * pointer or a capacity below 6 M^2.  Synchronous. */
+int      rt3_debug_environment_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint64_t capacity_cells,
+                                     uint32_t* cells_per_edge) RT3_TEST_ONLY;
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side scene API  (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)

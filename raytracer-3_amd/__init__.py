@@ -49,6 +49,7 @@ HISTORY = np.dtype([("colour", "<f4", 3), ("length", "<f4"), ("moments", "<f4", 
                     ("normal", "<f4", 3), ("_pad1", "<f4")])
 OCCLUDED_INVALID = 0xFFFFFFFF      # rt3_occluded's word for an invalid ray
 FLAG_GAMMA2, FLAG_BLACK_BACKGROUND, FLAG_REFERENCE_PRIMARY, FLAG_VARIANCE = 1, 2, 4, 8
+FLAG_ENV_SAMPLING = 16             # importance sampling of the environment map, one shadow ray per Lambert scatter
 REGROUP_SPHERES, REGROUP_MESH = 1, 2      # rt3_regroup's `what`
 
 
@@ -127,7 +128,7 @@ class ADAPTIVE_PARAMS(C.Structure):
 
 
 class RADIANCE_PARAMS(C.Structure):
-    """rt3_radiance_params (24 bytes): ray casts per path, seed, flags (0 or FLAG_BLACK_BACKGROUND), the sample range and t_min."""
+    """rt3_radiance_params (24 bytes): ray casts per path, seed, flags (0, FLAG_BLACK_BACKGROUND or FLAG_ENV_SAMPLING), the sample range and t_min."""
     _fields_ = [("max_depth", C.c_uint32), ("seed", C.c_uint32), ("flags", C.c_uint32), ("sample_begin", C.c_uint32),
                 ("sample_count", C.c_uint32), ("t_min", C.c_float)]
 
@@ -160,6 +161,7 @@ EXPORTS = [
     "rt3_set_spheres_device", "rt3_set_mesh_device", "rt3_debug_sphere_plan", "rt3_debug_sphere_build",
     "rt3_radiance", "rt3_radiance_device",
     "rt3_set_environment", "rt3_set_environment_device", "rt3_clear_environment", "rt3_environment_size", "rt3_debug_environment_lookup",
+    "rt3_debug_environment_sample", "rt3_debug_environment_table",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -237,6 +239,7 @@ def lib():
         "rt3_set_environment": (i32, [vp, vp, u32]), "rt3_set_environment_device": (i32, [vp, vp, u32, vp]),
         "rt3_clear_environment": (i32, [vp]), "rt3_environment_size": (u32, [vp]),
         "rt3_debug_environment_lookup": (i32, [vp, u32, vp, vp]),
+        "rt3_debug_environment_sample": (i32, [vp, u32, u32, u32, vp, vp, vp]), "rt3_debug_environment_table": (i32, [vp, vp, vp, u64, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -273,6 +276,24 @@ def environment_lookup(cube, d):
         if fn(_p(rgba), rgba.shape[1], C.c_void_p(dirs.ctypes.data + 12 * k), C.c_void_p(out.ctypes.data + 12 * k)) != 0:
             raise Fatal("rt3_debug_environment_lookup refused its arguments (1 <= N <= 2048)")
     return out[0] if np.ndim(d) == 1 else out
+
+
+def environment_sample(cube, base, depth):
+    """rt3_debug_environment_sample, the map's sampling table and sampling law in C on the host: what a Lambert scatter of a path
+    with RNG base `base` at depth `depth` draws under FLAG_ENV_SAMPLING.  Scalars give (cell, float32 direction (3,), float32 pdf), arrays of K
+    give (uint32 (K,), (K, 3), (K,)).  A map whose table is empty (nothing to sample) gives cell 0xFFFFFFFF, direction 0 and pdf 0."""
+    rgba = _cube_rgba(cube)
+    b = np.asarray(base, np.uint32).reshape(-1)
+    d = np.broadcast_to(np.asarray(depth, np.uint32).reshape(-1), b.shape)
+    cell = np.zeros(len(b), np.uint32)
+    dirs = np.zeros((len(b), 3), np.float32)
+    pdf = np.zeros(len(b), np.float32)
+    fn = lib().rt3_debug_environment_sample
+    for k in range(len(b)):
+        if fn(_p(rgba), rgba.shape[1], int(b[k]), int(d[k]), C.c_void_p(cell.ctypes.data + 4 * k), C.c_void_p(dirs.ctypes.data + 12 * k),
+              C.c_void_p(pdf.ctypes.data + 4 * k)) != 0:
+            raise Fatal("rt3_debug_environment_sample refused its arguments (1 <= N <= 2048)")
+    return (int(cell[0]), dirs[0], pdf[0]) if np.ndim(base) == 0 else (cell, dirs, pdf)
 
 
 def cube_from_equirect(image, n):
@@ -1039,6 +1060,18 @@ class HipRenderer(Renderer):
     def environment_size(self):
         """N of the map that is set, 0 when none is (rt3_environment_size)."""
         return int(lib().rt3_environment_size(self._ctx))
+
+    def environment_table(self):
+        """The sampling table the device built for the map that is set (rt3_debug_environment_table; built now if no call with FLAG_ENV_SAMPLING
+        has built it): (q uint32 (6, M, M), cdf uint64 (6, M, M)), M = min(N, 256) cells per face edge, cdf the inclusive prefix sums of q."""
+        n = self.environment_size()
+        m = min(n, 256)
+        q = np.zeros(max(6 * m * m, 1), np.uint32)
+        cdf = np.zeros(max(6 * m * m, 1), np.uint64)
+        got = C.c_uint32(0)
+        self._check(lib().rt3_debug_environment_table(self._ctx, _p(q), _p(cdf), 6 * m * m, C.byref(got)))
+        assert got.value == m
+        return q[:6 * m * m].reshape(6, m, m), cdf[:6 * m * m].reshape(6, m, m)
 
     @staticmethod
     def environment_lookup(cube, d):

@@ -44,6 +44,7 @@
 #include "rt3.h"
 
 #include "rt3_sphere_plan.hpp"
+#include "rt3_env_sample.hpp"
 #include "rt3_kernel_common.hpp"
 #include "rt3_path.hpp"
 #include "rt3_valu_scan.hpp"
@@ -57,6 +58,7 @@
 #include "rt3_regroup.hpp"
 #include "rt3_scene_build.hpp"
 #include "rt3_primary_lists.hpp"
+#include "rt3_env_table.hpp"
 
 // ======================================================================================================
 // Host side of the device context
@@ -139,6 +141,9 @@ struct rt3_ctx {
     // environment map (rt3_set_environment*): the context's copy, 6 faces of env_n x env_n float4 texels; env_n == 0: none.  Scene
     // uploads, updates and regroups never touch it.
     DevBuf<float4> d_env; uint32_t env_n = 0;
+    // ... and its sampling table (RT3_FLAG_ENV_SAMPLING): env_m cells per face edge, the cells' quantised weights and their inclusive
+    // prefix sums.  Built by the first call that carries the flag (ensure_env_table), kept until the map is set or cleared again (env_table = false).
+    DevBuf<uint32_t> d_env_q, d_env_wmax; DevBuf<unsigned long long> d_env_cdf; DevBuf<uint8_t> d_env_temp; uint32_t env_m = 0; bool env_table = false;
 
     // work buffers
     DevBuf<Rgb> d_rad;
@@ -484,13 +489,22 @@ bool same_bytes(const void* a, const void* b, size_t n) { return std::memcmp(a, 
 int check_params(rt3_ctx* ctx, const rt3_params* p) {
     if (!p) return fail(ctx, RT3_E_ARG, "params is NULL");
     if (!(p->t_min >= 0.0f) || !(p->t_min < __builtin_inff())) return fail(ctx, RT3_E_ARG, "t_min must be finite and >= 0");
-    if (p->flags & ~(RT3_FLAG_GAMMA2 | RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_REFERENCE_PRIMARY | RT3_FLAG_VARIANCE))
+    if (p->flags & ~(RT3_FLAG_GAMMA2 | RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_REFERENCE_PRIMARY | RT3_FLAG_VARIANCE | RT3_FLAG_ENV_SAMPLING))
         return fail(ctx, RT3_E_ARG, "unknown bits in flags");
     if (p->width < 2 || p->height < 2) return fail(ctx, RT3_E_ARG, "width and height must be >= 2");
     if ((uint64_t)p->width * p->height > 0x7FFFFFFFull) return fail(ctx, RT3_E_ARG, "frame too large");
     if (p->spp < 1 || p->max_depth < 1) return fail(ctx, RT3_E_ARG, "spp and max_depth must be >= 1");
     if (p->tile_count > 1 && (p->tile_rows == 0 || p->tile_index >= p->tile_count))
         return fail(ctx, RT3_E_ARG, "bad tile_rows / tile_index / tile_count");
+    return 0;
+}
+
+// RT3_FLAG_ENV_SAMPLING in the flags of a render or of rt3_radiance* (rt3.h): the flags it excludes first, then the map it needs.
+int check_env_sampling(rt3_ctx* ctx, uint32_t flags) {
+    if (!(flags & RT3_FLAG_ENV_SAMPLING)) return 0;
+    if (flags & (RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_REFERENCE_PRIMARY))
+        return fail(ctx, RT3_E_ARG, "RT3_FLAG_ENV_SAMPLING cannot be combined with RT3_FLAG_BLACK_BACKGROUND or RT3_FLAG_REFERENCE_PRIMARY");
+    if (ctx->env_n == 0) return fail(ctx, RT3_E_STATE, "RT3_FLAG_ENV_SAMPLING needs an environment map: call rt3_set_environment first");
     return 0;
 }
 
@@ -576,6 +590,7 @@ struct TracePlan {
     bool filter_counted = false;                                    // the kernel counts the casts that take the filter (k_trace_mfma32's render form)
     uint32_t list_groups = 0;                                       // strip lists to build before the first batch (k_primary_lists): groups of 64 owned pixels, 0: none
     const float4* env = nullptr; uint32_t env_n = 0;                // environment forms: the map the launch hands over behind TraceArgs (env_n != 0)
+    const uint32_t* nee_q = nullptr; const unsigned long long* nee_cdf = nullptr; uint32_t nee_m = 0;      // sampling forms: the table behind the map (nee_m != 0)
 };
 // Strip lists (rt3_primary_lists.hpp): RT3_PRIMARY_LISTS=0 turns them off (the A/B reference: every primary ray takes the matrix filter),
 // RT3_PRIMARY_LIST_MAX=n sets the longest list a restock still traces itself.  The default is the best of a sweep on the bench frame at 1080p (short
@@ -638,6 +653,8 @@ void with_form(Form form, Fn fn) {
     case Form::RenderEnv: return fn(std::integral_constant<Form, Form::RenderEnv>{});
     case Form::ListEnv: return fn(std::integral_constant<Form, Form::ListEnv>{});
     case Form::RaysEnv: return fn(std::integral_constant<Form, Form::RaysEnv>{});
+    case Form::RenderEnvNee: return fn(std::integral_constant<Form, Form::RenderEnvNee>{});
+    case Form::RaysEnvNee: return fn(std::integral_constant<Form, Form::RaysEnvNee>{});
     }
 }
 // Fills A's filter fields and T for the form `form` (rt3_kernel_common.hpp).  ref_brute: a RenderRef with a camera only the brute-force kernel serves.
@@ -645,10 +662,14 @@ void with_form(Form form, Fn fn) {
 // shading as a render; A.q_rays is the caller's to set (its slot is the strip lists': they are off).
 // While an environment map is set a Render, List or Rays becomes its environment twin: the same family — the families without such a
 // form (VALU, K = 64, the flat filter) are never chosen, their switches are ignored as queries ignore them — and T carries the map for launch_trace.
-int plan_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, TracePlan& T) {
+// nee: the call carries RT3_FLAG_ENV_SAMPLING (a Render or a Rays with a map set and its table built: check_env_sampling, ensure_env_table): the sampling
+// twin of the environment form, the same family again; k_trace_mfma32's takes the plain refill, so no strip lists are built for it.
+int plan_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, TracePlan& T, bool nee = false) {
     const bool query = form == Form::Query, list = form == Form::List, rays = form == Form::Rays;
     const bool env = ctx->env_n != 0 && (form == Form::Render || list || rays);
+    if (nee && (!env || list || !ctx->env_table)) return fail(ctx, RT3_E_DEVICE, "internal: no sampling form for this call");
     if (env) { T.env = ctx->d_env; T.env_n = ctx->env_n; form = form == Form::Render ? Form::RenderEnv : list ? Form::ListEnv : Form::RaysEnv; }
+    if (nee) { T.nee_q = ctx->d_env_q; T.nee_cdf = ctx->d_env_cdf; T.nee_m = ctx->env_m; form = rays ? Form::RaysEnvNee : Form::RenderEnvNee; }
     const bool has_tri = ctx->n_faces > 0, has_sph = ctx->n_sph > 0;
     const bool brute = ctx->force_brute || getenv("RT3_BRUTE") || ref_brute;
     const bool use_mfma = !brute && (query || rays || env || !getenv("RT3_NO_MFMA"));
@@ -676,7 +697,7 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, TracePlan&
             const char* on = getenv("RT3_PRIMARY_LISTS"); const char* cap = getenv("RT3_PRIMARY_LIST_MAX");
             if (!rays) A.prim_masks = nullptr;                      // (the slot held the face bounds' address: none in a sphere-only scene; rays: it is q_rays' slot)
             A.prim_list_max = 0;
-            if (!list && !rays && !(on && atoi(on) == 0)) {             // (a list's groups of 64 are not consecutive pixels: no strip lists)
+            if (!list && !rays && !nee && !(on && atoi(on) == 0)) {             // (a list's groups of 64 are not consecutive pixels: no strip lists)
                 T.list_groups = (A.npix + 63u) / 64u;
                 int rc_;
                 if ((rc_ = ctx->d_prim_masks.ensure(ctx, (size_t)T.list_groups * T.mfma_blocks))) return rc_;
@@ -742,6 +763,17 @@ uint32_t trace_grid(const rt3_ctx* ctx, const TracePlan& T, uint32_t total) {
     return std::max(1u, std::min<uint32_t>((uint32_t)(ctx->num_cu * T.per_cu), want_blocks));
 }
 void launch_trace(const TracePlan& T, const TraceArgs& A, uint32_t grid, hipStream_t stream) {
+    if (T.nee_m != 0) {                                             // a sampling form: the map and its table behind the arguments
+        NeeTraceArgs E;
+        static_cast<TraceArgs&>(E) = A;
+        E.env = T.env; E.env_n = T.env_n; E.env_pad = 0u;
+        E.nee_q = T.nee_q; E.nee_cdf = (const uint64_t*)T.nee_cdf; E.nee_m = T.nee_m; E.nee_cells = 6u * T.nee_m * T.nee_m;
+        constexpr Form F = Form::RenderEnvNee;                      // (the two sampling forms share their signatures)
+        if (T.single) hipLaunchKernelGGL(reinterpret_cast<SingleKernelOf<F>>(T.single), dim3(grid), dim3(kMB), T.lds, stream, E, T.frag_a, T.mfma_blocks);
+        else if (T.tiled) hipLaunchKernelGGL(reinterpret_cast<TiledKernelOf<F>>(T.tiled), dim3(grid), dim3(kTB), T.lds, stream, E, T.frag_a, T.frag_b);
+        else hipLaunchKernelGGL(reinterpret_cast<TraceKernelOf<F>>(T.plain), dim3(grid), dim3(kBlock), T.lds, stream, E);
+        return;
+    }
     if (T.env_n != 0) {                                             // an environment form: the same launch with the map behind the arguments
         EnvTraceArgs E;
         static_cast<TraceArgs&>(E) = A;
@@ -786,6 +818,29 @@ int enter(rt3_ctx* ctx, void* stream_, hipStream_t* stream) {
 int leave(rt3_ctx* ctx, hipStream_t stream) {
     RT3_HIP(hipEventRecord(ctx->ev_acc, stream));
     ctx->ev_acc_recorded = true;
+    return 0;
+}
+
+// The sampling table of the map the context holds, built once per map by the first call that carries RT3_FLAG_ENV_SAMPLING: three launches
+// queued on that call's stream behind enter() — the cells' weights and their maximum, the quantisation, the prefix sums (integers: order-free) — and no
+// host wait: the kernels read the total from the last prefix sum.  A later call on another stream finds it behind the event chain, as it finds an update.
+int ensure_env_table(rt3_ctx* ctx, hipStream_t stream) {
+    if (ctx->env_table) return 0;
+    const uint32_t m = rt3env::cells_per_edge(ctx->env_n), cells = 6u * m * m;
+    size_t temp = 0;
+    int rc;
+    RT3_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, temp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)cells, stream));
+    if ((rc = ctx->d_env_q.ensure(ctx, cells)) || (rc = ctx->d_env_cdf.ensure(ctx, cells)) || (rc = ctx->d_env_wmax.ensure(ctx, 1)) ||
+        (rc = ctx->d_env_temp.ensure(ctx, std::max<size_t>(temp, 1))))
+        return rc;
+    const dim3 grid((cells + kBlock - 1) / kBlock), blk(kBlock);
+    RT3_HIP(hipMemsetAsync(ctx->d_env_wmax, 0, 4, stream));
+    hipLaunchKernelGGL(k_env_cell_weights, grid, blk, 0, stream, (const float4*)ctx->d_env, ctx->env_n, m, cells, ctx->d_env_q.get(), ctx->d_env_wmax.get());
+    hipLaunchKernelGGL(k_env_quantise, grid, blk, 0, stream, cells, (const uint32_t*)ctx->d_env_wmax, ctx->d_env_q.get(), ctx->d_env_cdf.get());
+    RT3_HIP(hipGetLastError());
+    RT3_HIP(hipcub::DeviceScan::InclusiveSum(ctx->d_env_temp.get(), temp, (const unsigned long long*)ctx->d_env_cdf.get(), ctx->d_env_cdf.get(), (int)cells, stream));
+    ctx->env_m = m;
+    ctx->env_table = true;
     return 0;
 }
 
@@ -1700,6 +1755,8 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     if (sample_count == 0 || (uint64_t)sample_begin + sample_count > p->spp) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
     if ((rc = check_scene(ctx))) return rc;
     const bool ref = (p->flags & RT3_FLAG_REFERENCE_PRIMARY) != 0, var = (p->flags & RT3_FLAG_VARIANCE) != 0;
+    const bool nee = (p->flags & RT3_FLAG_ENV_SAMPLING) != 0;
+    if ((rc = check_env_sampling(ctx, p->flags))) return rc;       // (before the older refusals of RT3_FLAG_REFERENCE_PRIMARY: the flag's own answer comes first)
     if (ref && ctx->n_sph != 0) return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY needs a triangle-only scene");
     if (ref && ctx->env_n != 0)
         return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY is not available while an environment map is set (its primary direction is not a unit vector)");
@@ -1741,7 +1798,8 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     A.rad = ctx->d_rad;
 
     TracePlan T;
-    if ((rc = plan_trace(ctx, A, ref ? Form::RenderRef : Form::Render, ref && !(cam_at_origin(cam) && !(p->lens_radius > 0.0f)), T))) return rc;
+    if (nee && (rc = ensure_env_table(ctx, stream))) return rc;
+    if ((rc = plan_trace(ctx, A, ref ? Form::RenderRef : Form::Render, ref && !(cam_at_origin(cam) && !(p->lens_radius > 0.0f)), T, nee))) return rc;
 
     if ((rc = begin_timed(ctx, stream))) return rc;
 #ifdef RT3_PROFILE
@@ -1808,6 +1866,7 @@ int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const r
     int rc = check_params(ctx, p);
     if (rc) return rc;
     if (p->flags & RT3_FLAG_REFERENCE_PRIMARY) return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY is not available to the adaptive render");
+    if (p->flags & RT3_FLAG_ENV_SAMPLING) return fail(ctx, RT3_E_ARG, "RT3_FLAG_ENV_SAMPLING is not available to the adaptive render (the sampling forms have no list form)");
     if (ap->min_spp < 2 || ap->min_spp > p->spp) return fail(ctx, RT3_E_ARG, "min_spp must lie in [2, spp]");
     if (ap->step_spp < 1) return fail(ctx, RT3_E_ARG, "step_spp must be >= 1");
     if (!(ap->threshold > 0.0f) || !(ap->threshold < __builtin_inff())) return fail(ctx, RT3_E_ARG, "threshold must be finite and > 0");
@@ -2491,7 +2550,10 @@ static_assert(sizeof(rt3_radiance_params) == 24, "rt3.h: rt3_radiance_params");
 static int radiance_checks(rt3_ctx* ctx, uint32_t n, const rt3_radiance_params* rp) {
     if (!rp) return fail(ctx, RT3_E_ARG, "radiance params is NULL");
     if (!(rp->t_min >= 0.0f) || !(rp->t_min < __builtin_inff())) return fail(ctx, RT3_E_ARG, "t_min must be finite and >= 0");
-    if (rp->flags & ~RT3_FLAG_BLACK_BACKGROUND) return fail(ctx, RT3_E_ARG, "rt3_radiance: flags may only hold RT3_FLAG_BLACK_BACKGROUND");
+    if (rp->flags & ~(RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_ENV_SAMPLING))
+        return fail(ctx, RT3_E_ARG, "rt3_radiance: flags may only hold RT3_FLAG_BLACK_BACKGROUND or RT3_FLAG_ENV_SAMPLING");
+    if ((rp->flags & RT3_FLAG_ENV_SAMPLING) && (rp->flags & RT3_FLAG_BLACK_BACKGROUND))
+        return fail(ctx, RT3_E_ARG, "RT3_FLAG_ENV_SAMPLING cannot be combined with RT3_FLAG_BLACK_BACKGROUND or RT3_FLAG_REFERENCE_PRIMARY");
     if (rp->max_depth < 1 || rp->sample_count < 1) return fail(ctx, RT3_E_ARG, "max_depth and sample_count must be >= 1");
     if ((uint64_t)rp->sample_begin + rp->sample_count > (1ull << 31)) return fail(ctx, RT3_E_ARG, "sample_begin + sample_count must be <= 2^31");
     if (n > (1u << 27)) return fail(ctx, RT3_E_ARG, "at most 2^27 rays per radiance call (split the batch and pass keys)");
@@ -2507,7 +2569,8 @@ static int radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys,
         return fail(ctx, RT3_E_ARG, "rays and out_rgba must be 16-byte and keys 4-byte aligned");
     if (ranges_overlap(d_out, (size_t)n * 16u, d_rays, (size_t)n * sizeof(rt3_ray)) || (d_keys && ranges_overlap(d_out, (size_t)n * 16u, d_keys, (size_t)n * 4u)))
         return fail(ctx, RT3_E_ARG, "out_rgba overlaps the rays or the keys");
-    if ((rc = check_scene(ctx))) return rc;
+    if ((rc = check_scene(ctx)) || (rc = check_env_sampling(ctx, rp->flags))) return rc;
+    const bool nee = (rp->flags & RT3_FLAG_ENV_SAMPLING) != 0;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
     ctx->rendered = false;
@@ -2521,7 +2584,8 @@ static int radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys,
     if (!fastdiv_ok(n, 0x7FFFFFFFu)) return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
     A.rad = ctx->d_rad;
     TracePlan T;
-    if ((rc = plan_trace(ctx, A, Form::Rays, false, T))) return rc;
+    if (nee && (rc = ensure_env_table(ctx, stream))) return rc;
+    if ((rc = plan_trace(ctx, A, Form::Rays, false, T, nee))) return rc;
     A.q_rays = (const float4*)d_rays; A.ray_keys = (const uint32_t*)d_keys;
     if ((rc = begin_timed(ctx, stream))) return rc;
     const uint32_t s_end = rp->sample_begin + rp->sample_count;
@@ -2578,6 +2642,7 @@ int rt3_clear_environment(rt3_ctx* ctx) {
     if (ctx->ev_acc_recorded) RT3_HIP(hipEventSynchronize(ctx->ev_acc));       // a launch still in flight may read the map
     ctx->d_env.reset();
     ctx->env_n = 0;
+    ctx->env_table = false;                                         // (the table's buffers stay for the next map)
     return 0;
 }
 uint32_t rt3_environment_size(rt3_ctx* ctx) { return ctx ? ctx->env_n : 0u; }
@@ -2588,6 +2653,7 @@ static int install_environment(rt3_ctx* ctx, const void* src, hipMemcpyKind kind
     int rc;
     if (ctx->env_n == n_face) {                                     // the same size: into the copy the context has, behind whatever still reads it
         if ((rc = enter(ctx, stream_, &stream))) return rc;
+        ctx->env_table = false;                                     // the next call with RT3_FLAG_ENV_SAMPLING builds the new map's table
         RT3_HIP(hipMemcpyAsync(ctx->d_env.get(), src, texels * sizeof(float4), kind, stream));
         return leave(ctx, stream);
     }
@@ -2598,6 +2664,7 @@ static int install_environment(rt3_ctx* ctx, const void* src, hipMemcpyKind kind
     if (ctx->env_n != 0 && ctx->ev_acc_recorded) RT3_HIP(hipEventSynchronize(ctx->ev_acc));    // the old copy is freed: nothing may still read it
     ctx->d_env = std::move(fresh);
     ctx->env_n = n_face;
+    ctx->env_table = false;
     return 0;
 }
 int rt3_set_environment_device(rt3_ctx* ctx, const void* d_rgba, uint32_t n_face, void* stream) {
@@ -2619,6 +2686,25 @@ int rt3_set_environment(rt3_ctx* ctx, const float* rgba, uint32_t n_face) {
             return fail(ctx, RT3_E_ARG, "environment texel " + std::to_string(i) + " is not finite");
     if ((rc = install_environment(ctx, rgba, hipMemcpyHostToDevice, n_face, ctx->stream))) return rc;      // (no staging buffer: a large map would stay in it)
     RT3_HIP(hipStreamSynchronize(ctx->stream));                     // the caller's array is free again
+    return 0;
+}
+
+// Tests only: the sampling table of the map the context holds, downloaded (built first if no call with RT3_FLAG_ENV_SAMPLING has built it yet).
+int rt3_debug_environment_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint64_t capacity_cells, uint32_t* m_out) {
+    if (!ctx) return RT3_E_ARG;
+    if (!q_out || !cdf_out || !m_out) return fail(ctx, RT3_E_ARG, "q_out / cdf_out / cells_per_edge is NULL");
+    if (ctx->env_n == 0) return fail(ctx, RT3_E_STATE, "no environment map: call rt3_set_environment first");
+    const uint32_t m = rt3env::cells_per_edge(ctx->env_n);
+    const size_t cells = (size_t)6 * m * m;
+    *m_out = m;
+    if (capacity_cells < cells) return fail(ctx, RT3_E_ARG, "capacity_cells is smaller than the table (6 x cells_per_edge^2 cells)");
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, nullptr, &stream)) || (rc = ensure_env_table(ctx, stream))) return rc;
+    RT3_HIP(hipMemcpyAsync(q_out, ctx->d_env_q.get(), cells * 4u, hipMemcpyDeviceToHost, stream));
+    RT3_HIP(hipMemcpyAsync(cdf_out, ctx->d_env_cdf.get(), cells * 8u, hipMemcpyDeviceToHost, stream));
+    if ((rc = leave(ctx, stream))) return rc;
+    RT3_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 

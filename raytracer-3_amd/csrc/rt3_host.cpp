@@ -6,6 +6,7 @@
 // Compiled with -ffp-contract=off: the reference's flattening is plain IEEE binary32 with libm double trig.
 #include "rt3.h"
 #include "rt3_sphere_plan.hpp"
+#include "rt3_env_sample.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -468,6 +469,41 @@ extern "C" int rt3_debug_environment_lookup(const float* rgba, uint32_t n, const
         const float bot = c01 + wx * (c11 - c01);
         out_rgb[c] = top + wy * (bot - top);
     }
+    return 0;
+}
+
+// The sampling table and the sampling law (rt3.h) on the host: the table built cell after cell — the device builds it in any order and
+// gets the same integers — then rt3env::sample, the very function shade_lane calls.  The entry point takes one (base, depth) per call and the tests make
+// thousands on one map, so the last map's table is kept, with a copy of the map that every call compares (a table is never reused for other texels).
+namespace {
+struct HostEnvTable {
+    std::vector<float> rgba; uint32_t n = 0;
+    std::vector<uint32_t> q; std::vector<uint64_t> cdf; uint64_t total = 0;
+    void build(const float* map, uint32_t n_face) {
+        const uint32_t m = rt3env::cells_per_edge(n_face), cells = 6u * m * m;
+        rgba.assign(map, map + (size_t)24 * n_face * n_face);
+        n = n_face;
+        std::vector<float> w(cells);
+        float w_max = 0.0f;
+        for (uint32_t k = 0; k < cells; k++) {
+            const uint32_t face = k / (m * m), in = k - face * (m * m), row = in / m, col = in - row * m;
+            w[k] = rt3env::cell_weight(map, n_face, m, face, row, col);
+            if (w[k] > w_max) w_max = w[k];
+        }
+        q.resize(cells); cdf.resize(cells);
+        total = 0;
+        for (uint32_t k = 0; k < cells; k++) { q[k] = rt3env::quantise(w[k], w_max); total += q[k]; cdf[k] = total; }
+    }
+};
+}  // namespace
+extern "C" int rt3_debug_environment_sample(const float* rgba, uint32_t n, uint32_t base, uint32_t depth, uint32_t* cell, float dir[3], float* pdf) {
+    if (!rgba || !cell || !dir || !pdf || n == 0 || n > RT3_ENV_MAX_FACE) return RT3_E_ARG;
+    static thread_local HostEnvTable T;
+    if (T.n != n || std::memcmp(T.rgba.data(), rgba, T.rgba.size() * sizeof(float)) != 0) T.build(rgba, n);
+    if (T.total == 0) { *cell = 0xFFFFFFFFu; dir[0] = dir[1] = dir[2] = 0.0f; *pdf = 0.0f; return 0; }
+    rt3env::Sample S;
+    rt3env::sample(T.q.data(), T.cdf.data(), rt3env::cells_per_edge(n), T.total, base, depth, S);
+    *cell = S.cell; dir[0] = S.dx; dir[1] = S.dy; dir[2] = S.dz; *pdf = S.pdf;
     return 0;
 }
 

@@ -156,10 +156,16 @@ struct Rgb { float r, g, b; };   // one radiance record of the sample storage (t
 //   Rays       item = (sample, one of the caller's rays), shaded as a render's (TraceArgs::ray_keys): rt3_radiance*
 //   RenderEnv, ListEnv, RaysEnv   Render, List and Rays while an environment map is set (rt3_set_environment*): the same kernel with
 //              ONE difference, the miss of shade_lane reads the map where the twin evaluates the sky.  Their launch argument is an EnvTraceArgs (below).
-enum class Form : uint32_t { Render, RenderRef, Query, List, Rays, RenderEnv, ListEnv, RaysEnv };
-constexpr bool is_env(Form f) { return f == Form::RenderEnv || f == Form::ListEnv || f == Form::RaysEnv; }
+//   RenderEnvNee, RaysEnvNee      RenderEnv and RaysEnv under RT3_FLAG_ENV_SAMPLING: a Lambert scatter also draws a direction from the
+//              map's sampling table and casts one shadow ray through the lane's own cast slot (shade_lane); the lane carries a NeePath, the launch
+//              argument is a NeeTraceArgs (both below).  No list form: the adaptive render refuses the flag.
+enum class Form : uint32_t { Render, RenderRef, Query, List, Rays, RenderEnv, ListEnv, RaysEnv, RenderEnvNee, RaysEnvNee };
+constexpr bool is_nee(Form f) { return f == Form::RenderEnvNee || f == Form::RaysEnvNee; }
+constexpr bool is_env(Form f) { return f == Form::RenderEnv || f == Form::ListEnv || f == Form::RaysEnv || is_nee(f); }
 // The twin of an environment form, and every other form itself: what a kernel body and the refill helpers branch on.
-constexpr Form base_form(Form f) { return f == Form::RenderEnv ? Form::Render : f == Form::ListEnv ? Form::List : f == Form::RaysEnv ? Form::Rays : f; }
+constexpr Form base_form(Form f) {
+    return f == Form::RenderEnv || f == Form::RenderEnvNee ? Form::Render : f == Form::ListEnv ? Form::List : f == Form::RaysEnv || f == Form::RaysEnvNee ? Form::Rays : f;
+}
 // Batched ray queries (the QUERY forms of the trace kernels; rt3_intersect* / rt3_occluded*): item k of a launch is ray k
 // of the caller's rt3_ray[] (q_rays: two float4 per ray, origin, t_max | direction, pad); its result goes to q_out[k], an rt3_hit (16 bytes), or with
 // q_occluded one word.  They share the places of fields only the path kernels read (the VALU scan's face bounds, the sample storage, the render
@@ -220,8 +226,13 @@ struct TraceArgs {
 // layout and the code of every other kernel — stays what it was.  The helpers keep taking a TraceArgs&; shade_lane, the one reader,
 // gets the map back with env_of().  env: 6 faces of env_n x env_n float4 texels (+X, -X, +Y, -Y, +Z, -Z; row 0 first), 1 <= env_n <= 2048.
 struct EnvTraceArgs : TraceArgs { const float4* env; uint32_t env_n; uint32_t env_pad; };
-template <Form F> using trace_args = std::conditional_t<is_env(F), EnvTraceArgs, TraceArgs>;
+// The launch argument of the sampling forms (RT3_FLAG_ENV_SAMPLING): EnvTraceArgs with the map's sampling table behind it, again a struct
+// of its own.  nee_q: the cells' quantised weights, nee_cdf: their inclusive prefix sums, both [6 nee_m nee_m] in (face, row, column) order; the
+// table's total is nee_cdf[nee_cells - 1], read from device memory (the host never waits for the build).
+struct NeeTraceArgs : EnvTraceArgs { const uint32_t* nee_q; const uint64_t* nee_cdf; uint32_t nee_m; uint32_t nee_cells; };
+template <Form F> using trace_args = std::conditional_t<is_nee(F), NeeTraceArgs, std::conditional_t<is_env(F), EnvTraceArgs, TraceArgs>>;
 __device__ __forceinline__ const EnvTraceArgs& env_of(const TraceArgs& A) { return static_cast<const EnvTraceArgs&>(A); }   // only where A IS one: an environment form
+__device__ __forceinline__ const NeeTraceArgs& nee_of(const TraceArgs& A) { return static_cast<const NeeTraceArgs&>(A); }   // only where A IS one: a sampling form
 
 struct Path {
     float ox, oy, oz, dx, dy, dz;
@@ -229,6 +240,14 @@ struct Path {
     uint32_t slot, base, depth;
     float tmax;              // QUERY forms: the ray's t_max (the path kernels never touch it)
 };
+// The lane state of the sampling forms (is_nee): a Path plus what a shadow ray in flight needs — it travels in the lane's own cast slot
+// (origin and direction of P), so the continuation's direction waits in c*, the contribution a miss of the shadow ray adds per unit of map radiance in e*.
+// nee: kNeeShadow, the cast in flight is the shadow ray; kNeeLambert, the path's most recent scatter was a Lambert scatter, whose light the shadow ray
+// accounted for (a later miss adds nothing).  The helpers keep taking a Path&; shade_lane, the one reader, gets the rest back with nee_path().
+struct NeePath : Path { float cx = 0.0f, cy = 0.0f, cz = 0.0f, er = 0.0f, eg = 0.0f, eb = 0.0f; uint32_t nee = 0u; };
+constexpr uint32_t kNeeShadow = 1u, kNeeLambert = 2u;
+template <Form F> using path_of = std::conditional_t<is_nee(F), NeePath, Path>;
+__device__ __forceinline__ NeePath& nee_path(Path& P) { return static_cast<NeePath&>(P); }                                  // only where P IS one: a sampling form
 
 // The reference's plane + three-edge test of one face (SequentialRenderer.cpp:53-98; hit_vertex, raytracer_v4.glsl:116-153), in
 // its own operation order.  n = (normal, n.p1) as k_commit_mesh stores it.

@@ -170,6 +170,11 @@ __device__ __forceinline__ void stock_pop(const TracedStock& Q, uint32_t src, bo
 // depth alone, so a lane below the cap reads its row instead of computing three hashes; at or beyond the cap it computes them as rnd() does.
 // Environment forms (is_env(F); A is then an EnvTraceArgs): a miss adds throughput x env_lookup(direction) where the twin adds throughput x sky — the one
 // difference between an environment form and its twin.
+// Sampling forms (is_nee(F), RT3_FLAG_ENV_SAMPLING; A is a NeeTraceArgs, P a NeePath): a Lambert scatter also draws a direction w from the
+// map's table (rt3env::sample, counters 3..6 of the scatter's block).  With c = n.w > 0 the shadow ray (p, w) takes the lane's next cast — the
+// continuation waits in the NeePath — and THAT cast's shade_lane is the first block below: a miss adds T' (c / (pi pdf)) env(w), a hit adds nothing, and
+// the lane goes on with the continuation.  The scatter itself draws what it always drew, so the continuation rays are the plain render's.  A miss
+// behind such a scatter adds nothing: the shadow ray has accounted for the map.
 template <bool HAS_TRI, bool HAS_SPH, Form F, bool CTR = false>
 __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& alive, uint32_t kind, uint32_t ibest, float tbest,
                                            const float4* sph, const float* sph_invr, const float4* sph_mat, const uint32_t* sph_kind,
@@ -177,10 +182,29 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
     constexpr bool REF = F == Form::RenderRef;
     const float ox = P.ox, oy = P.oy, oz = P.oz;
     float dx = P.dx, dy = P.dy, dz = P.dz;
+    if constexpr (is_nee(F)) {
+        NeePath& N = nee_path(P);
+        if (alive && (N.nee & kNeeShadow)) {                            // this cast was the shadow ray of the lane's last Lambert scatter
+            if (kind == 0) {
+                float r, g, b;
+                env_lookup(env_of(A).env, env_of(A).env_n, dx, dy, dz, r, g, b);
+                P.lr = fma_(N.er, r, P.lr); P.lg = fma_(N.eg, g, P.lg); P.lb = fma_(N.eb, b, P.lb);
+            }
+            P.dx = N.cx; P.dy = N.cy; P.dz = N.cz;                      // on with the continuation (origin, throughput and depth are already its)
+            N.nee = kNeeLambert;
+            return;
+        }
+    }
     if (alive) {
         bool done = false;
         if (kind == 0) {
-            if (!(A.flags & RT3_FLAG_BLACK_BACKGROUND)) {
+            if constexpr (is_nee(F)) {                                  // (RT3_FLAG_BLACK_BACKGROUND is refused with the flag)
+                if (!(nee_path(P).nee & kNeeLambert)) {
+                    float r, g, b;
+                    env_lookup(env_of(A).env, env_of(A).env_n, dx, dy, dz, r, g, b);
+                    P.lr = fma_(P.tr, r, P.lr); P.lg = fma_(P.tg, g, P.lg); P.lb = fma_(P.tb, b, P.lb);
+                }
+            } else if (!(A.flags & RT3_FLAG_BLACK_BACKGROUND)) {
                 float r, g, b;
                 if constexpr (is_env(F)) env_lookup(env_of(A).env, env_of(A).env_n, dx, dy, dz, r, g, b);
                 else sky(dx, dy, dz, r, g, b);
@@ -266,12 +290,33 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
                     P.ox = px; P.oy = py; P.oz = pz;
                     P.tr *= ar; P.tg *= ag; P.tb *= ab;
                     P.depth += 1;
+                    if constexpr (is_nee(F)) {
+                        NeePath& N = nee_path(P);
+                        N.nee = mk == RT3_MAT_LAMBERT ? kNeeLambert : 0u;
+                        if (mk == RT3_MAT_LAMBERT) {
+                            const NeeTraceArgs& E = nee_of(A);
+                            const uint64_t total = E.nee_cdf[E.nee_cells - 1u];
+                            if (total != 0ull) {
+                                rt3env::Sample S;
+                                rt3env::sample(E.nee_q, E.nee_cdf, E.nee_m, total, P.base, P.depth - 1u, S);
+                                const float c = dotf(nx, ny, nz, S.dx, S.dy, S.dz);
+                                if (c > 0.0f) {
+                                    const float k = c / (3.14159274f * S.pdf);
+                                    N.er = P.tr * k; N.eg = P.tg * k; N.eb = P.tb * k;
+                                    N.cx = P.dx; N.cy = P.dy; N.cz = P.dz;
+                                    P.dx = S.dx; P.dy = S.dy; P.dz = S.dz;
+                                    N.nee = kNeeLambert | kNeeShadow;
+                                }
+                            }
+                        }
+                    }
                 }
             }
         }
         if (done) {
             A.rad[P.slot] = Rgb{ P.lr, P.lg, P.lb };
             alive = false;
+            if constexpr (is_nee(F)) nee_path(P).nee = 0u;              // the lane's next path starts without a scatter behind it
         }
     }
 }

@@ -7,7 +7,8 @@
 // usage error, -1 on a fatal backend error.  Fixed: `--key=value`, which the reference mis-parses (Main.cpp:110).
 // Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr, --denoise (PFM files),
 // --frames, --orbit and --slide (a sequence, denoised temporally), --adaptive and --counts (--spp as a budget), --rays and --radiance
-// (path-traced radiance along rays read from a file), --env (an environment map from a PFM of six stacked cube faces).
+// (path-traced radiance along rays read from a file), --env (an environment map from a PFM of six stacked cube faces),
+// --env-sampling (importance sampling of that map with shadow rays).
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -49,6 +50,7 @@ struct Options {
     std::string counts_path;                                       // --adaptive: the samples per pixel as a 1-channel PFM
     std::string rays_path, radiance_path;                          // Mode X: rt3_ray records in, their radiance out as a PFM of n x 1
     std::string env_path;                                          // Mode X: the environment map, a colour PFM of N x 6N (the six faces stacked)
+    bool env_sampling = false;                                     // with --env: RT3_FLAG_ENV_SAMPLING
 };
 
 void print_usage(const char* exe) {
@@ -82,6 +84,8 @@ void print_usage(const char* exe) {
               << "\t\t\tpath as a 3-channel PFM, n wide and 1 high.\n"
               << "\t   --env\tMode X: light the scene with a cube map where a ray leaves it: a colour PFM, N wide and 6N high, the faces +X, -X, +Y, -Y,\n"
               << "\t\t\t+Z, -Z stacked from top to bottom, N up to 2048. The render, --radiance and --aov use it.\n"
+              << "\t   --env-sampling\tWith --env: every diffuse bounce also samples the map by its brightness and casts one shadow ray (a small bright\n"
+              << "\t\t\tsun converges). The render and --radiance; not with --adaptive, nor with a scene whose background is black.\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -119,6 +123,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         if (key == "--gpu-prerender") { opt.gpu_prerender = true; continue; }
         if (key == "--dump-scene") { opt.dump_scene = true; continue; }
         if (key == "--refit") { opt.refit = true; continue; }
+        if (key == "--env-sampling") { opt.env_sampling = true; continue; }
         const bool known = key == "-f" || key == "--format" || key == "-W" || key == "--width" || key == "-H" || key == "--height" ||
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
@@ -218,6 +223,14 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     }
     if (mode_r && !opt.env_path.empty()) {
         std::cerr << "--env needs the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
+    if (opt.env_sampling && opt.env_path.empty()) {
+        std::cerr << "--env-sampling needs --env." << std::endl;
+        return -1;
+    }
+    if (opt.env_sampling && opt.adaptive) {
+        std::cerr << "--env-sampling is not available with --adaptive." << std::endl;
         return -1;
     }
     if (mode_r && opt.adaptive) {
@@ -383,6 +396,7 @@ int main(int argc, const char** argv) {
             uint32_t n_face = 0;
             const std::vector<float> rgba = read_env_pfm(opt.env_path, n_face);
             renderer.set_environment(rgba, n_face);
+            if (opt.env_sampling) path.flags |= RT3_FLAG_ENV_SAMPLING;
         }
         const uint32_t seed0 = path.seed;
         const bool temporal = opt.frames > 1 && !opt.denoise_path.empty();
