@@ -32,8 +32,9 @@ extern "C" {
  * sizeof(rt3_stats) bytes of THIS version).  History: 1 = round 1; 2 = + mfma_instructions / exact_tests in rt3_stats, progressive
  * accumulation, rt3_gather_rows; 3 = + rt3_abi_version itself, one stream convention (below),
  * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh*, with
- * rt3_render_path_adaptive* (one new struct of its own), with rt3_regroup*, with the environment map (rt3_set_environment*) and with its
- * importance sampling (RT3_FLAG_ENV_SAMPLING: one flag bit and two test-only functions): functions were only added, no existing struct changed. */
+ * rt3_render_path_adaptive* (one new struct of its own), with rt3_regroup*, with the environment map (rt3_set_environment*), with its
+ * importance sampling (RT3_FLAG_ENV_SAMPLING: one flag bit and two test-only functions) and with the emitters' (RT3_FLAG_LIGHT_SAMPLING: the same again):
+ * functions were only added, no existing struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
 
@@ -98,6 +99,9 @@ typedef struct rt3_material {
 /* Importance sampling of the environment map with one shadow ray per Lambert scatter (next-event estimation): "Environment map: sampling"
  * below.  Needs a map (rt3_set_environment*); without the flag every entry point returns what it returned before the flag existed. */
 #define RT3_FLAG_ENV_SAMPLING      16u
+/* Importance sampling of the emissive primitives (RT3_MAT_FLAT) with one shadow ray per Lambert scatter: "Emitters: sampling" below.  Not together
+ * with RT3_FLAG_ENV_SAMPLING; without the flag every entry point returns what it returned before the flag existed. */
+#define RT3_FLAG_LIGHT_SAMPLING    32u
 
 /* Parameters of a Mode-X render.  tile_*: interleaved row-block sharding of the framebuffer
  * (design intent: BlockInfo{x,y,w,h} of raytracer_v4.glsl:70-79).  Row-block b (tile_rows rows) belongs
@@ -551,7 +555,7 @@ int rt3_denoise_temporal_motion_device(rt3_ctx* ctx, uint32_t width, uint32_t he
 typedef struct rt3_radiance_params {   /* 24 bytes */
     uint32_t max_depth;      /* ray casts per path, >= 1, as rt3_params */
     uint32_t seed;
-    uint32_t flags;          /* 0, RT3_FLAG_BLACK_BACKGROUND or RT3_FLAG_ENV_SAMPLING (not both); any other bit: RT3_E_ARG */
+    uint32_t flags;          /* RT3_FLAG_BLACK_BACKGROUND, RT3_FLAG_ENV_SAMPLING (not both), RT3_FLAG_LIGHT_SAMPLING (not with ENV_SAMPLING); any other bit: RT3_E_ARG */
     uint32_t sample_begin;   /* first sample index */
     uint32_t sample_count;   /* samples per ray, >= 1; sample_begin + sample_count <= 2^31 */
     float    t_min;          /* finite, >= 0 */
@@ -683,6 +687,58 @@ int      rt3_debug_environment_sample(const float* rgba, uint32_t n_face, uint32
  * pointer or a capacity below 6 M^2.  Synchronous. */
 int      rt3_debug_environment_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint64_t capacity_cells,
                                      uint32_t* cells_per_edge) RT3_TEST_ONLY;
+
+/* ---------------------------------------------------------------------------------------------------
+ * Emitters: sampling  (DESIGN.md 4.21, 5.2p): RT3_FLAG_LIGHT_SAMPLING in rt3_params.flags / rt3_radiance_params.flags
+ * ------------------------------------------------------------------------------------------------- */
+/* A RT3_MAT_FLAT primitive emits: a hit adds throughput * rgb and ends the path.  Without the flag a path receives that light only where a scattered
+ * ray happens to run into the emitter; a small lamp is then found by a vanishing share of the bounces.  With it every Lambert scatter also draws a
+ * point on one emitter and casts one shadow ray towards it (next-event estimation).  Opt-in per call; rt3_render_path*, rt3_render_path_range*
+ * (shards included) and rt3_radiance* accept it, with or without RT3_FLAG_BLACK_BACKGROUND, with or without a map (the defining property of
+ * rt3_radiance holds with it).
+ * The table.  One entry per primitive in the caller's order, faces first and then spheres: entry i < n_faces is face i, otherwise sphere
+ * i - n_faces (the order of rt3_hit.index).  Integers wherever something is added up.  Brightness l = (max(r, 0) + max(g, 0)) + max(b, 0) of the
+ * material's rgb, the NaN-dropping max, +inf clamped to FLT_MAX; l = 0 for any kind but RT3_MAT_FLAT.  Area of a face: e1 = p2 - p1, e2 = p3 - p1,
+ * x = e1 x e2 with every product and difference rounded on its own, g2 = fmaf(x.z, x.z, fmaf(x.y, x.y, x.x * x.x)), a = 0.5f * sqrtf(g2); of a
+ * sphere: a = 12.566371f * (r * r).  Weight w = l * a; a NaN w, or an a that is not finite and > 0 (a degenerate face, a sphere record nothing can
+ * hit), gives w = 0; +inf is clamped to FLT_MAX.  With W the largest w, q = 0 where w == 0 and otherwise max(1, (uint32_t)floorf(w / W *
+ * 16777216.0f)); cdf is the inclusive uint64 prefix sum of q, total its last entry.  The table (12 bytes per primitive) is built on the device by
+ * the first call that carries the flag, queued on that call's stream inside the event chain, and kept until the scene changes: rt3_set_spheres*,
+ * rt3_set_mesh*, rt3_mesh_commit, rt3_update_spheres* and rt3_update_mesh* invalidate it, rt3_regroup* and the environment calls do not.
+ * The sampling law.  At a Lambert scatter of a path with RNG base `base` at depth d: ctr = 1 + 8 (d + 1), w_k = hash_u32(base ^ hash_u32(ctr + k)),
+ * k = 3..6 (the counters of RT3_FLAG_ENV_SAMPLING, which the flag excludes; the scatter keeps k = 0..2).  x = (uint64_t)w3 << 32 | w4, T = the
+ * high 64 bits of x * total; the light is the first index with cdf[index] > T.  a = u01(w5), b = u01(w6).
+ *   A face: if a + b > 1 then a = 1 - a, b = 1 - b; per component y = fmaf(b, e2, fmaf(a, e1, p1)); the light's normal is x * (1 / sqrtf(g2)).
+ *   A sphere: v = the scatter's own random unit vector of (a, b); per component y = fmaf(r, v, c); the light's normal is v.
+ * With p the hit point the continuation starts from: D = y - p, d2 = D.D (every dot product here is fmaf(z, z', fmaf(y, y', x * x'))),
+ * w = D * (1 / sqrtf(d2)), cl = |n_light . w|, c = n . w with n the surface normal turned towards the ray.  The sample is dropped — no shadow ray —
+ * when total == 0; when d2 is not finite and > 0; when not cl > 0; when not c > 0; and when the light is a sphere, p lies outside it (|p - c|^2 >
+ * r * r) and v . w >= 0: the far side, which the near side hides (from inside every point counts: FLAT emits on both sides).  Otherwise
+ * pl = (float)q / (float)total, k = ((c * cl) * a_light) / ((3.14159274f * d2) * pl), and the lane parks E = T' * k, T' = throughput * albedo,
+ * with the light's index and the continuation's direction; the shadow ray (p, w) takes the next cast with the nearest-hit rule (t_min,
+ * t_max = +inf).  If its nearest hit is that very primitive (same class and index), L = fma(E, rgb_light, L) per channel; anything else, a miss
+ * included, leaves L as it is.  The lane then goes on with the continuation.
+ * The path law with the flag.  The scatter draws what it always drew: the continuation rays are the plain render's.  A hit on a FLAT primitive whose
+ * q > 0 adds nothing while the path's most recent scatter was a Lambert scatter (the shadow ray has accounted for it; the path ends there as
+ * always); a FLAT primitive with q == 0 keeps adding, and so does every FLAT hit of a primary ray or behind a metal or glass scatter.  A miss is
+ * the plain render's (sky, black, or the map's plain lookup); the depth cut-off, metal and glass are unchanged.  Shadow rays are not a depth; they
+ * count in ray_casts and in the filter's counters.  Multiple importance sampling is not done: a large emitter close to a surface can be noisier
+ * per sample than in the plain render.
+ * Errors.  RT3_E_ARG, each with a message of its own that comes before any older refusal: together with RT3_FLAG_ENV_SAMPLING (two shadow rays per
+ * scatter: not built); together with RT3_FLAG_REFERENCE_PRIMARY; rt3_render_path_adaptive* with the flag (no list form of the sampling kernels).
+ * rt3_render_aov*, rt3_camera_rays* and the accumulation calls accept the bit and ignore it. */
+/* Host only, no device and no context; for the tests.  The table built serially from the caller's arrays (faces and vertices as rt3_set_mesh takes
+ * them, spheres as rt3_set_spheres does), then the law above for one (base, depth): *light = the entry drawn, point = y, light_normal, *area = the
+ * light's, *pl = q / total.  An empty table (total == 0) gives *light = 0xFFFFFFFF and zeros.  RT3_E_ARG for a NULL pointer with a non-zero count,
+ * a NULL result pointer, or a face index out of range.  tests/light_sample_ref.py restates it bit for bit. */
+int      rt3_debug_light_sample(const rt3_gface* faces, uint32_t n_faces, const float* vertices_xyzw, uint32_t n_vertices,
+                                const rt3_material* face_materials, const float* center_radius, const rt3_material* sphere_materials,
+                                uint32_t n_spheres, uint32_t base, uint32_t depth, uint32_t* light, float point[3], float light_normal[3],
+                                float* area, float* pl);
+/* The device's table of the scene the context holds (built first if no call with the flag has built it): q_out and cdf_out take n_faces + n_spheres
+ * entries, capacity is what they can hold, *n_entries that count.  RT3_E_STATE without a scene, RT3_E_ARG for a NULL pointer or a short capacity
+ * (*n_entries is set).  Synchronous; for the tests. */
+int      rt3_debug_light_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint64_t capacity, uint32_t* n_entries);
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side scene API  (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)

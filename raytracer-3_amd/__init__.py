@@ -50,6 +50,7 @@ HISTORY = np.dtype([("colour", "<f4", 3), ("length", "<f4"), ("moments", "<f4", 
 OCCLUDED_INVALID = 0xFFFFFFFF      # rt3_occluded's word for an invalid ray
 FLAG_GAMMA2, FLAG_BLACK_BACKGROUND, FLAG_REFERENCE_PRIMARY, FLAG_VARIANCE = 1, 2, 4, 8
 FLAG_ENV_SAMPLING = 16             # importance sampling of the environment map, one shadow ray per Lambert scatter
+FLAG_LIGHT_SAMPLING = 32           # importance sampling of the emissive primitives, one shadow ray per Lambert scatter
 REGROUP_SPHERES, REGROUP_MESH = 1, 2      # rt3_regroup's `what`
 
 
@@ -128,7 +129,7 @@ class ADAPTIVE_PARAMS(C.Structure):
 
 
 class RADIANCE_PARAMS(C.Structure):
-    """rt3_radiance_params (24 bytes): ray casts per path, seed, flags (0, FLAG_BLACK_BACKGROUND or FLAG_ENV_SAMPLING), the sample range and t_min."""
+    """rt3_radiance_params (24 bytes): ray casts per path, seed, flags (FLAG_BLACK_BACKGROUND, FLAG_ENV_SAMPLING, FLAG_LIGHT_SAMPLING), the sample range and t_min."""
     _fields_ = [("max_depth", C.c_uint32), ("seed", C.c_uint32), ("flags", C.c_uint32), ("sample_begin", C.c_uint32),
                 ("sample_count", C.c_uint32), ("t_min", C.c_float)]
 
@@ -162,6 +163,7 @@ EXPORTS = [
     "rt3_radiance", "rt3_radiance_device",
     "rt3_set_environment", "rt3_set_environment_device", "rt3_clear_environment", "rt3_environment_size", "rt3_debug_environment_lookup",
     "rt3_debug_environment_sample", "rt3_debug_environment_table",
+    "rt3_debug_light_sample", "rt3_debug_light_table",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -240,6 +242,8 @@ def lib():
         "rt3_clear_environment": (i32, [vp]), "rt3_environment_size": (u32, [vp]),
         "rt3_debug_environment_lookup": (i32, [vp, u32, vp, vp]),
         "rt3_debug_environment_sample": (i32, [vp, u32, u32, u32, vp, vp, vp]), "rt3_debug_environment_table": (i32, [vp, vp, vp, u64, vp]),
+        "rt3_debug_light_sample": (i32, [vp, u32, vp, u32, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]),
+        "rt3_debug_light_table": (i32, [vp, vp, vp, u64, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -294,6 +298,35 @@ def environment_sample(cube, base, depth):
               C.c_void_p(pdf.ctypes.data + 4 * k)) != 0:
             raise Fatal("rt3_debug_environment_sample refused its arguments (1 <= N <= 2048)")
     return (int(cell[0]), dirs[0], pdf[0]) if np.ndim(base) == 0 else (cell, dirs, pdf)
+
+
+def light_sample(faces, verts, face_materials, center_radius, sphere_materials, base, depth):
+    """rt3_debug_light_sample, the emitters' sampling table and sampling law in C on the host: what a Lambert scatter of a path with
+    RNG base `base` at depth `depth` draws under FLAG_LIGHT_SAMPLING in the scene of these faces (GFACE, verts (n, 4), one MATERIAL per face) and
+    spheres ((n, 4) centre and radius, one MATERIAL each); None or empty arrays for a class the scene lacks.  Scalars give (light, float32 point
+    (3,), float32 light normal (3,), float32 area, float32 pl), arrays of K give (uint32 (K,), (K, 3), (K, 3), (K,), (K,)).  A table that is empty
+    (no emitter) gives light 0xFFFFFFFF and zeros."""
+    f = np.ascontiguousarray(faces if faces is not None else np.zeros(0, GFACE))
+    v = np.ascontiguousarray(verts if verts is not None else np.zeros((0, 4)), np.float32).reshape(-1, 4)
+    fm = np.ascontiguousarray(face_materials if face_materials is not None else np.zeros(0, MATERIAL))
+    cr = np.ascontiguousarray(center_radius if center_radius is not None else np.zeros((0, 4)), np.float32).reshape(-1, 4)
+    sm = np.ascontiguousarray(sphere_materials if sphere_materials is not None else np.zeros(0, MATERIAL))
+    if f.dtype != GFACE or fm.dtype != MATERIAL or sm.dtype != MATERIAL or len(fm) != len(f) or len(sm) != len(cr):
+        raise Fatal("light_sample: GFACE faces with one MATERIAL each, (n, 4) spheres with one MATERIAL each")
+    b = np.asarray(base, np.uint32).reshape(-1)
+    d = np.broadcast_to(np.asarray(depth, np.uint32).reshape(-1), b.shape)
+    light = np.zeros(len(b), np.uint32)
+    point = np.zeros((len(b), 3), np.float32)
+    normal = np.zeros((len(b), 3), np.float32)
+    area = np.zeros(len(b), np.float32)
+    pl = np.zeros(len(b), np.float32)
+    fn = lib().rt3_debug_light_sample
+    for k in range(len(b)):
+        if fn(_p(f) if len(f) else None, len(f), _p(v) if len(v) else None, len(v), _p(fm) if len(f) else None, _p(cr) if len(cr) else None,
+              _p(sm) if len(cr) else None, len(cr), int(b[k]), int(d[k]), C.c_void_p(light.ctypes.data + 4 * k), C.c_void_p(point.ctypes.data + 12 * k),
+              C.c_void_p(normal.ctypes.data + 12 * k), C.c_void_p(area.ctypes.data + 4 * k), C.c_void_p(pl.ctypes.data + 4 * k)) != 0:
+            raise Fatal("rt3_debug_light_sample refused its arguments (a face index out of range?)")
+    return (int(light[0]), point[0], normal[0], area[0], pl[0]) if np.ndim(base) == 0 else (light, point, normal, area, pl)
 
 
 def cube_from_equirect(image, n):
@@ -1006,7 +1039,7 @@ class HipRenderer(Renderer):
     # -- radiance along caller-supplied rays (rt3_radiance*) -----------------------------------------
     def radiance(self, rays, keys=None, samples=1, sample_begin=0, max_depth=8, seed=1, flags=0, t_min=0.001):
         """Path-traced radiance along every ray (rt3_radiance): the mean over samples [sample_begin, sample_begin + samples) of the Mode-X
-        path that starts with the ray, keyed by keys[i] (default: the ray's index) where a render keys by the pixel index.  numpy RAY /
+        path that starts with the ray (flags: FLAG_BLACK_BACKGROUND, FLAG_ENV_SAMPLING or FLAG_LIGHT_SAMPLING, the last two not together), keyed by keys[i] (default: the ray's index) where a render keys by the pixel index.  numpy RAY /
         (N, 8) float32 (keys: (N,) uint32) -> float32 (N, 4), (r, g, b, 0), NaN rgb for an invalid ray; a contiguous (N, 8) float32 torch
         tensor on the GPU (keys: an (N,) int32 tensor on that device) -> an (N, 4) float32 tensor there, computed on
         torch.cuda.current_stream()."""
@@ -1072,6 +1105,22 @@ class HipRenderer(Renderer):
         self._check(lib().rt3_debug_environment_table(self._ctx, _p(q), _p(cdf), 6 * m * m, C.byref(got)))
         assert got.value == m
         return q[:6 * m * m].reshape(6, m, m), cdf[:6 * m * m].reshape(6, m, m)
+
+    def light_table(self):
+        """The emitters' sampling table the device built for the scene that is set (rt3_debug_light_table; built now if no call with
+        FLAG_LIGHT_SAMPLING has built it): (q uint32 (n,), cdf uint64 (n,)), one entry per primitive, faces first and then spheres in the caller's
+        order, cdf the inclusive prefix sums of q."""
+        got = C.c_uint32(0)
+        one_q, one_c = np.zeros(1, np.uint32), np.zeros(1, np.uint64)
+        rc = lib().rt3_debug_light_table(self._ctx, _p(one_q), _p(one_c), 0, C.byref(got))       # (the count: refused for its capacity, the count set)
+        if got.value == 0:
+            self._check(rc)
+        n = got.value
+        q = np.zeros(n, np.uint32)
+        cdf = np.zeros(n, np.uint64)
+        self._check(lib().rt3_debug_light_table(self._ctx, _p(q), _p(cdf), n, C.byref(got)))
+        assert got.value == n
+        return q, cdf
 
     @staticmethod
     def environment_lookup(cube, d):

@@ -45,6 +45,7 @@
 
 #include "rt3_sphere_plan.hpp"
 #include "rt3_env_sample.hpp"
+#include "rt3_light_sample.hpp"
 #include "rt3_kernel_common.hpp"
 #include "rt3_path.hpp"
 #include "rt3_valu_scan.hpp"
@@ -59,6 +60,7 @@
 #include "rt3_scene_build.hpp"
 #include "rt3_primary_lists.hpp"
 #include "rt3_env_table.hpp"
+#include "rt3_light_table.hpp"
 
 // ======================================================================================================
 // Host side of the device context
@@ -144,6 +146,11 @@ struct rt3_ctx {
     // ... and its sampling table (RT3_FLAG_ENV_SAMPLING): env_m cells per face edge, the cells' quantised weights and their inclusive
     // prefix sums.  Built by the first call that carries the flag (ensure_env_table), kept until the map is set or cleared again (env_table = false).
     DevBuf<uint32_t> d_env_q, d_env_wmax; DevBuf<unsigned long long> d_env_cdf; DevBuf<uint8_t> d_env_temp; uint32_t env_m = 0; bool env_table = false;
+    // the emitters' sampling table (RT3_FLAG_LIGHT_SAMPLING): one entry per primitive, faces first and then spheres in the caller's order,
+    // the entries' quantised weights and their inclusive prefix sums.  Built by the first call that carries the flag (ensure_light_table), kept until the
+    // scene changes: every upload, commit and update sets light_table = false; regroups and the environment calls do not.  d_env_wmax and d_env_temp
+    // (the largest weight, the scan's scratch) are shared with the map's table: both builds are queued behind the event chain.
+    DevBuf<uint32_t> d_light_q; DevBuf<unsigned long long> d_light_cdf; bool light_table = false;
 
     // work buffers
     DevBuf<Rgb> d_rad;
@@ -489,7 +496,7 @@ bool same_bytes(const void* a, const void* b, size_t n) { return std::memcmp(a, 
 int check_params(rt3_ctx* ctx, const rt3_params* p) {
     if (!p) return fail(ctx, RT3_E_ARG, "params is NULL");
     if (!(p->t_min >= 0.0f) || !(p->t_min < __builtin_inff())) return fail(ctx, RT3_E_ARG, "t_min must be finite and >= 0");
-    if (p->flags & ~(RT3_FLAG_GAMMA2 | RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_REFERENCE_PRIMARY | RT3_FLAG_VARIANCE | RT3_FLAG_ENV_SAMPLING))
+    if (p->flags & ~(RT3_FLAG_GAMMA2 | RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_REFERENCE_PRIMARY | RT3_FLAG_VARIANCE | RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING))
         return fail(ctx, RT3_E_ARG, "unknown bits in flags");
     if (p->width < 2 || p->height < 2) return fail(ctx, RT3_E_ARG, "width and height must be >= 2");
     if ((uint64_t)p->width * p->height > 0x7FFFFFFFull) return fail(ctx, RT3_E_ARG, "frame too large");
@@ -505,6 +512,15 @@ int check_env_sampling(rt3_ctx* ctx, uint32_t flags) {
     if (flags & (RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_REFERENCE_PRIMARY))
         return fail(ctx, RT3_E_ARG, "RT3_FLAG_ENV_SAMPLING cannot be combined with RT3_FLAG_BLACK_BACKGROUND or RT3_FLAG_REFERENCE_PRIMARY");
     if (ctx->env_n == 0) return fail(ctx, RT3_E_STATE, "RT3_FLAG_ENV_SAMPLING needs an environment map: call rt3_set_environment first");
+    return 0;
+}
+
+// RT3_FLAG_LIGHT_SAMPLING in the flags of a render or of rt3_radiance* (rt3.h): the flags it excludes, each with an answer of its own.
+int check_light_sampling(rt3_ctx* ctx, uint32_t flags) {
+    if (!(flags & RT3_FLAG_LIGHT_SAMPLING)) return 0;
+    if (flags & RT3_FLAG_ENV_SAMPLING)
+        return fail(ctx, RT3_E_ARG, "RT3_FLAG_LIGHT_SAMPLING cannot be combined with RT3_FLAG_ENV_SAMPLING (one shadow ray per scatter)");
+    if (flags & RT3_FLAG_REFERENCE_PRIMARY) return fail(ctx, RT3_E_ARG, "RT3_FLAG_LIGHT_SAMPLING cannot be combined with RT3_FLAG_REFERENCE_PRIMARY");
     return 0;
 }
 
@@ -591,6 +607,7 @@ struct TracePlan {
     uint32_t list_groups = 0;                                       // strip lists to build before the first batch (k_primary_lists): groups of 64 owned pixels, 0: none
     const float4* env = nullptr; uint32_t env_n = 0;                // environment forms: the map the launch hands over behind TraceArgs (env_n != 0)
     const uint32_t* nee_q = nullptr; const unsigned long long* nee_cdf = nullptr; uint32_t nee_m = 0;      // sampling forms: the table behind the map (nee_m != 0)
+    const uint32_t* lt_q = nullptr; const unsigned long long* lt_cdf = nullptr; const float4* lt_sph_cr = nullptr; uint32_t lt_n = 0;   // light sampling forms: the emitters' table (lt_n != 0)
 };
 // Strip lists (rt3_primary_lists.hpp): RT3_PRIMARY_LISTS=0 turns them off (the A/B reference: every primary ray takes the matrix filter),
 // RT3_PRIMARY_LIST_MAX=n sets the longest list a restock still traces itself.  The default is the best of a sweep on the bench frame at 1080p (short
@@ -642,19 +659,31 @@ TraceKernelOf<F> valu_kernel(bool sph_lds, bool has_tri, bool has_sph) {
     });
 }
 // fn(std::integral_constant<Form, form>): the run-time form as a compile-time one.
+// RT3_FORM_MASK (bit f: Form f): the forms whose trace kernels this compilation instantiates — all of them in every build of the library.
+// tools/cvt_isa_check.py alone sets it: it reads the listing of every kernel, and compiles the device code as several listings in parallel, each with
+// some of the forms (a kernel's code does not depend on which other kernels are compiled beside it).
+#ifndef RT3_FORM_MASK
+#define RT3_FORM_MASK 0xFFFFFFFFu
+#endif
+template <Form F, class Fn>
+void form_case(Fn& fn) {
+    if constexpr (((RT3_FORM_MASK >> (uint32_t)F) & 1u) != 0u) fn(std::integral_constant<Form, F>{});
+}
 template <class Fn>
 void with_form(Form form, Fn fn) {
     switch (form) {
-    case Form::Render: return fn(std::integral_constant<Form, Form::Render>{});
-    case Form::RenderRef: return fn(std::integral_constant<Form, Form::RenderRef>{});
-    case Form::Query: return fn(std::integral_constant<Form, Form::Query>{});
-    case Form::List: return fn(std::integral_constant<Form, Form::List>{});
-    case Form::Rays: return fn(std::integral_constant<Form, Form::Rays>{});
-    case Form::RenderEnv: return fn(std::integral_constant<Form, Form::RenderEnv>{});
-    case Form::ListEnv: return fn(std::integral_constant<Form, Form::ListEnv>{});
-    case Form::RaysEnv: return fn(std::integral_constant<Form, Form::RaysEnv>{});
-    case Form::RenderEnvNee: return fn(std::integral_constant<Form, Form::RenderEnvNee>{});
-    case Form::RaysEnvNee: return fn(std::integral_constant<Form, Form::RaysEnvNee>{});
+    case Form::Render: return form_case<Form::Render>(fn);
+    case Form::RenderRef: return form_case<Form::RenderRef>(fn);
+    case Form::Query: return form_case<Form::Query>(fn);
+    case Form::List: return form_case<Form::List>(fn);
+    case Form::Rays: return form_case<Form::Rays>(fn);
+    case Form::RenderEnv: return form_case<Form::RenderEnv>(fn);
+    case Form::ListEnv: return form_case<Form::ListEnv>(fn);
+    case Form::RaysEnv: return form_case<Form::RaysEnv>(fn);
+    case Form::RenderEnvNee: return form_case<Form::RenderEnvNee>(fn);
+    case Form::RaysEnvNee: return form_case<Form::RaysEnvNee>(fn);
+    case Form::RenderLight: return form_case<Form::RenderLight>(fn);
+    case Form::RaysLight: return form_case<Form::RaysLight>(fn);
     }
 }
 // Fills A's filter fields and T for the form `form` (rt3_kernel_common.hpp).  ref_brute: a RenderRef with a camera only the brute-force kernel serves.
@@ -664,11 +693,19 @@ void with_form(Form form, Fn fn) {
 // form (VALU, K = 64, the flat filter) are never chosen, their switches are ignored as queries ignore them — and T carries the map for launch_trace.
 // nee: the call carries RT3_FLAG_ENV_SAMPLING (a Render or a Rays with a map set and its table built: check_env_sampling, ensure_env_table): the sampling
 // twin of the environment form, the same family again; k_trace_mfma32's takes the plain refill, so no strip lists are built for it.
-int plan_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, TracePlan& T, bool nee = false) {
+// light: the call carries RT3_FLAG_LIGHT_SAMPLING (a Render or a Rays with the emitters' table built: check_light_sampling, ensure_light_table): the light
+// sampling form, which is an environment form whether a map is set or not (env_n == 0: none) and so takes the families an environment form takes.
+int plan_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, TracePlan& T, bool nee = false, bool light = false) {
     const bool query = form == Form::Query, list = form == Form::List, rays = form == Form::Rays;
-    const bool env = ctx->env_n != 0 && (form == Form::Render || list || rays);
-    if (nee && (!env || list || !ctx->env_table)) return fail(ctx, RT3_E_DEVICE, "internal: no sampling form for this call");
-    if (env) { T.env = ctx->d_env; T.env_n = ctx->env_n; form = form == Form::Render ? Form::RenderEnv : list ? Form::ListEnv : Form::RaysEnv; }
+    const bool map = ctx->env_n != 0 && (form == Form::Render || list || rays);
+    const bool env = map || light;
+    if (nee && (!map || list || !ctx->env_table || light)) return fail(ctx, RT3_E_DEVICE, "internal: no sampling form for this call");
+    if (light && (!(form == Form::Render || rays) || !ctx->light_table)) return fail(ctx, RT3_E_DEVICE, "internal: no light sampling form for this call");
+    if (map) { T.env = ctx->d_env; T.env_n = ctx->env_n; form = form == Form::Render ? Form::RenderEnv : list ? Form::ListEnv : Form::RaysEnv; }
+    if (light) {
+        T.lt_q = ctx->d_light_q; T.lt_cdf = ctx->d_light_cdf; T.lt_sph_cr = ctx->d_sph_cr; T.lt_n = ctx->n_faces + ctx->n_sph;
+        form = rays ? Form::RaysLight : Form::RenderLight;
+    }
     if (nee) { T.nee_q = ctx->d_env_q; T.nee_cdf = ctx->d_env_cdf; T.nee_m = ctx->env_m; form = rays ? Form::RaysEnvNee : Form::RenderEnvNee; }
     const bool has_tri = ctx->n_faces > 0, has_sph = ctx->n_sph > 0;
     const bool brute = ctx->force_brute || getenv("RT3_BRUTE") || ref_brute;
@@ -697,7 +734,7 @@ int plan_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, TracePlan&
             const char* on = getenv("RT3_PRIMARY_LISTS"); const char* cap = getenv("RT3_PRIMARY_LIST_MAX");
             if (!rays) A.prim_masks = nullptr;                      // (the slot held the face bounds' address: none in a sphere-only scene; rays: it is q_rays' slot)
             A.prim_list_max = 0;
-            if (!list && !rays && !nee && !(on && atoi(on) == 0)) {             // (a list's groups of 64 are not consecutive pixels: no strip lists)
+            if (!list && !rays && !nee && !light && !(on && atoi(on) == 0)) {             // (a list's groups of 64 are not consecutive pixels: no strip lists)
                 T.list_groups = (A.npix + 63u) / 64u;
                 int rc_;
                 if ((rc_ = ctx->d_prim_masks.ensure(ctx, (size_t)T.list_groups * T.mfma_blocks))) return rc_;
@@ -763,6 +800,17 @@ uint32_t trace_grid(const rt3_ctx* ctx, const TracePlan& T, uint32_t total) {
     return std::max(1u, std::min<uint32_t>((uint32_t)(ctx->num_cu * T.per_cu), want_blocks));
 }
 void launch_trace(const TracePlan& T, const TraceArgs& A, uint32_t grid, hipStream_t stream) {
+    if (T.lt_n != 0) {                                              // a light sampling form: the map (or none) and the emitters' table behind the arguments
+        LightTraceArgs E;
+        static_cast<TraceArgs&>(E) = A;
+        E.env = T.env; E.env_n = T.env_n; E.env_pad = 0u;
+        E.lt_q = T.lt_q; E.lt_cdf = (const uint64_t*)T.lt_cdf; E.lt_sph_cr = T.lt_sph_cr; E.lt_n = T.lt_n; E.lt_pad = 0u;
+        constexpr Form F = Form::RenderLight;                       // (the two light sampling forms share their signatures)
+        if (T.single) hipLaunchKernelGGL(reinterpret_cast<SingleKernelOf<F>>(T.single), dim3(grid), dim3(kMB), T.lds, stream, E, T.frag_a, T.mfma_blocks);
+        else if (T.tiled) hipLaunchKernelGGL(reinterpret_cast<TiledKernelOf<F>>(T.tiled), dim3(grid), dim3(kTB), T.lds, stream, E, T.frag_a, T.frag_b);
+        else hipLaunchKernelGGL(reinterpret_cast<TraceKernelOf<F>>(T.plain), dim3(grid), dim3(kBlock), T.lds, stream, E);
+        return;
+    }
     if (T.nee_m != 0) {                                             // a sampling form: the map and its table behind the arguments
         NeeTraceArgs E;
         static_cast<TraceArgs&>(E) = A;
@@ -841,6 +889,29 @@ int ensure_env_table(rt3_ctx* ctx, hipStream_t stream) {
     RT3_HIP(hipcub::DeviceScan::InclusiveSum(ctx->d_env_temp.get(), temp, (const unsigned long long*)ctx->d_env_cdf.get(), ctx->d_env_cdf.get(), (int)cells, stream));
     ctx->env_m = m;
     ctx->env_table = true;
+    return 0;
+}
+
+// The emitters' sampling table of the scene the context holds, built once per scene by the first call that carries RT3_FLAG_LIGHT_SAMPLING:
+// the same three launches as ensure_env_table, over one entry per primitive, queued on that call's stream behind enter(), and no host wait.
+int ensure_light_table(rt3_ctx* ctx, hipStream_t stream) {
+    if (ctx->light_table) return 0;
+    const uint32_t n = ctx->n_faces + ctx->n_sph;                   // (check_scene: >= 1, and far below 2^31)
+    size_t temp = 0;
+    int rc;
+    RT3_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, temp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n, stream));
+    if ((rc = ctx->d_light_q.ensure(ctx, n)) || (rc = ctx->d_light_cdf.ensure(ctx, n)) || (rc = ctx->d_env_wmax.ensure(ctx, 1)) ||
+        (rc = ctx->d_env_temp.ensure(ctx, std::max<size_t>(temp, 1))))
+        return rc;
+    const dim3 grid((n + kBlock - 1) / kBlock), blk(kBlock);
+    RT3_HIP(hipMemsetAsync(ctx->d_env_wmax, 0, 4, stream));
+    hipLaunchKernelGGL(k_light_weights, grid, blk, 0, stream, (const float4*)ctx->d_tri, (const float4*)ctx->d_tri_mat, (const uint32_t*)ctx->d_tri_kind, ctx->n_faces,
+                       (const float4*)ctx->d_sph_cr, (const float4*)ctx->d_sph_mat, (const uint32_t*)ctx->d_sph_kind, ctx->n_sph, ctx->d_light_q.get(),
+                       ctx->d_env_wmax.get());
+    hipLaunchKernelGGL(k_light_quantise, grid, blk, 0, stream, n, (const uint32_t*)ctx->d_env_wmax, ctx->d_light_q.get(), ctx->d_light_cdf.get());
+    RT3_HIP(hipGetLastError());
+    RT3_HIP(hipcub::DeviceScan::InclusiveSum(ctx->d_env_temp.get(), temp, (const unsigned long long*)ctx->d_light_cdf.get(), ctx->d_light_cdf.get(), (int)n, stream));
+    ctx->light_table = true;
     return 0;
 }
 
@@ -985,6 +1056,7 @@ int rt3_mesh_commit(rt3_ctx* ctx, const rt3_material* face_materials) {
     const uint32_t n = (uint32_t)ctx->d_gfaces.size(), n_pad = (n + 3u) / 4u * 4u, n_verts = (uint32_t)ctx->d_verts.size();
     ctx->n_faces = 0;
     ctx->mesh_in_sync = false;
+    ctx->light_table = false;                                       // the scene changes: the next call with RT3_FLAG_LIGHT_SAMPLING builds the emitters' table again
     ctx->update_error_pending = false;
     ctx->tri = FilterRows();
     for (DevBuf<float4>* b : { &ctx->d_tri, &ctx->d_tri_mat, &ctx->d_tri_bound, &ctx->d_tri_rec }) b->reset();
@@ -1090,6 +1162,7 @@ int rt3_set_spheres(rt3_ctx* ctx, const float* center_radius, const rt3_material
         kind[i] = materials[i].kind;
     }
     ctx->n_sph = 0;                                                 // (no spheres until everything below has been issued)
+    ctx->light_table = false;
     int rc;
     sphere_filter_centre(center_radius, n, ctx->sph_centre);
     ctx->n_direct = sphere_direct_list(center_radius, n, ctx->sph_centre, ctx->direct);
@@ -1129,6 +1202,7 @@ int rt3_update_spheres_device(rt3_ctx* ctx, const void* d_center_radius, uint32_
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
     ctx->n_sph = 0;                                                 // (no spheres until everything below has been issued)
+    ctx->light_table = false;
     hipLaunchKernelGGL(k_refit_spheres, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)d_center_radius, n,
                        (const uint32_t*)ctx->d_sph_slot, ctx->sph_centre[0], ctx->sph_centre[1], ctx->sph_centre[2], ctx->d_sph.get(),
                        ctx->d_sph_cr.get(), ctx->d_sph_invr.get(), (u32x4*)ctx->d_sph_frag.get(), (u32x4*)ctx->d_sph_frag32.get(), ctx->sph.grp.get());
@@ -1186,6 +1260,7 @@ static int update_mesh_issue(rt3_ctx* ctx, const void* d_faces, const void* d_ve
     const uint32_t n = ctx->n_faces;
     ctx->n_faces = 0;                                               // (no mesh until everything below has been issued)
     ctx->mesh_in_sync = false;
+    ctx->light_table = false;
     if (clear_error || !ctx->update_error_pending) RT3_HIP(hipMemsetAsync(ctx->d_error, 0, 4, stream));
     RT3_HIP(hipMemcpyAsync(ctx->d_verts, d_verts, ctx->d_verts.size() * sizeof(float4), hipMemcpyDeviceToDevice, stream));
     if (d_faces) RT3_HIP(hipMemcpyAsync(ctx->d_gfaces, d_faces, (size_t)n * sizeof(rt3_gface), hipMemcpyDeviceToDevice, stream));
@@ -1432,7 +1507,7 @@ static int build_scratch(rt3_ctx* ctx, uint32_t n, bool sort_scratch, size_t* te
     return 0;
 }
 static void clear_spheres(rt3_ctx* ctx) {                           // what rt3_set_spheres(n = 0) leaves
-    ctx->n_sph = 0; ctx->n_direct = 0; ctx->sph_left_out = false;
+    ctx->n_sph = 0; ctx->n_direct = 0; ctx->sph_left_out = false; ctx->light_table = false;
     for (int a = 0; a < 3; a++) ctx->sph_centre[a] = 0.0f;
     ctx->sph = FilterRows();
     for (DevBuf<float4>* b : { &ctx->d_sph, &ctx->d_sph_mat, &ctx->d_sph_cr }) b->reset();
@@ -1488,6 +1563,7 @@ int rt3_set_spheres_device(rt3_ctx* ctx, const void* d_center_radius, const void
     if (h[kSbBadKind]) return fail(ctx, RT3_E_ARG, "unknown material kind");
     // ---- phase 2
     ctx->n_sph = 0;                                                 // (no spheres until everything below has been issued)
+    ctx->light_table = false;
     std::memcpy(ctx->sph_centre, h + kSbCentre, sizeof ctx->sph_centre);
     ctx->n_direct = std::min(h[kSbCand], 4u);
     for (uint32_t k = 0; k < ctx->n_direct; k++) ctx->direct[k] = 0xFFFFFFFFu - h[kSbBest + 2 * k];     // (the key's low word)
@@ -1529,7 +1605,7 @@ int rt3_set_spheres_device(rt3_ctx* ctx, const void* d_center_radius, const void
 }
 
 static void clear_mesh(rt3_ctx* ctx) {                              // what rt3_mesh_commit drops before it builds
-    ctx->n_faces = 0; ctx->mesh_in_sync = false; ctx->update_error_pending = false; ctx->tri_bounded = 0;
+    ctx->n_faces = 0; ctx->mesh_in_sync = false; ctx->update_error_pending = false; ctx->tri_bounded = 0; ctx->light_table = false;
     ctx->tri = FilterRows();
     for (DevBuf<float4>* b : { &ctx->d_tri, &ctx->d_tri_mat, &ctx->d_tri_bound, &ctx->d_tri_rec }) b->reset();
     ctx->d_tri_kind.reset(); ctx->d_tri_frag.reset(); ctx->d_tri_frag_r.reset(); ctx->d_face_mats_in.reset();
@@ -1752,10 +1828,11 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     if (!cam || !d_out) return fail(ctx, RT3_E_ARG, "cam / d_out_pixels is NULL");
     int rc = check_params(ctx, p);
     if (rc) return rc;
+    if ((rc = check_light_sampling(ctx, p->flags))) return rc;     // (the flag's own answers come before every older refusal)
     if (sample_count == 0 || (uint64_t)sample_begin + sample_count > p->spp) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
     if ((rc = check_scene(ctx))) return rc;
     const bool ref = (p->flags & RT3_FLAG_REFERENCE_PRIMARY) != 0, var = (p->flags & RT3_FLAG_VARIANCE) != 0;
-    const bool nee = (p->flags & RT3_FLAG_ENV_SAMPLING) != 0;
+    const bool nee = (p->flags & RT3_FLAG_ENV_SAMPLING) != 0, light = (p->flags & RT3_FLAG_LIGHT_SAMPLING) != 0;
     if ((rc = check_env_sampling(ctx, p->flags))) return rc;       // (before the older refusals of RT3_FLAG_REFERENCE_PRIMARY: the flag's own answer comes first)
     if (ref && ctx->n_sph != 0) return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY needs a triangle-only scene");
     if (ref && ctx->env_n != 0)
@@ -1799,7 +1876,8 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
 
     TracePlan T;
     if (nee && (rc = ensure_env_table(ctx, stream))) return rc;
-    if ((rc = plan_trace(ctx, A, ref ? Form::RenderRef : Form::Render, ref && !(cam_at_origin(cam) && !(p->lens_radius > 0.0f)), T, nee))) return rc;
+    if (light && (rc = ensure_light_table(ctx, stream))) return rc;
+    if ((rc = plan_trace(ctx, A, ref ? Form::RenderRef : Form::Render, ref && !(cam_at_origin(cam) && !(p->lens_radius > 0.0f)), T, nee, light))) return rc;
 
     if ((rc = begin_timed(ctx, stream))) return rc;
 #ifdef RT3_PROFILE
@@ -1865,6 +1943,8 @@ int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const r
     if (!cam || !ap || !d_out) return fail(ctx, RT3_E_ARG, "cam / adaptive params / d_out_pixels is NULL");
     int rc = check_params(ctx, p);
     if (rc) return rc;
+    if (p->flags & RT3_FLAG_LIGHT_SAMPLING)
+        return fail(ctx, RT3_E_ARG, "RT3_FLAG_LIGHT_SAMPLING is not available to the adaptive render (the light sampling forms have no list form)");
     if (p->flags & RT3_FLAG_REFERENCE_PRIMARY) return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY is not available to the adaptive render");
     if (p->flags & RT3_FLAG_ENV_SAMPLING) return fail(ctx, RT3_E_ARG, "RT3_FLAG_ENV_SAMPLING is not available to the adaptive render (the sampling forms have no list form)");
     if (ap->min_spp < 2 || ap->min_spp > p->spp) return fail(ctx, RT3_E_ARG, "min_spp must lie in [2, spp]");
@@ -2550,8 +2630,10 @@ static_assert(sizeof(rt3_radiance_params) == 24, "rt3.h: rt3_radiance_params");
 static int radiance_checks(rt3_ctx* ctx, uint32_t n, const rt3_radiance_params* rp) {
     if (!rp) return fail(ctx, RT3_E_ARG, "radiance params is NULL");
     if (!(rp->t_min >= 0.0f) || !(rp->t_min < __builtin_inff())) return fail(ctx, RT3_E_ARG, "t_min must be finite and >= 0");
-    if (rp->flags & ~(RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_ENV_SAMPLING))
-        return fail(ctx, RT3_E_ARG, "rt3_radiance: flags may only hold RT3_FLAG_BLACK_BACKGROUND or RT3_FLAG_ENV_SAMPLING");
+    int rc_light = check_light_sampling(ctx, rp->flags);           // (the flag's own answers come before every older refusal)
+    if (rc_light) return rc_light;
+    if (rp->flags & ~(RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING))
+        return fail(ctx, RT3_E_ARG, "rt3_radiance: flags may only hold RT3_FLAG_BLACK_BACKGROUND, RT3_FLAG_ENV_SAMPLING or RT3_FLAG_LIGHT_SAMPLING");
     if ((rp->flags & RT3_FLAG_ENV_SAMPLING) && (rp->flags & RT3_FLAG_BLACK_BACKGROUND))
         return fail(ctx, RT3_E_ARG, "RT3_FLAG_ENV_SAMPLING cannot be combined with RT3_FLAG_BLACK_BACKGROUND or RT3_FLAG_REFERENCE_PRIMARY");
     if (rp->max_depth < 1 || rp->sample_count < 1) return fail(ctx, RT3_E_ARG, "max_depth and sample_count must be >= 1");
@@ -2570,7 +2652,7 @@ static int radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys,
     if (ranges_overlap(d_out, (size_t)n * 16u, d_rays, (size_t)n * sizeof(rt3_ray)) || (d_keys && ranges_overlap(d_out, (size_t)n * 16u, d_keys, (size_t)n * 4u)))
         return fail(ctx, RT3_E_ARG, "out_rgba overlaps the rays or the keys");
     if ((rc = check_scene(ctx)) || (rc = check_env_sampling(ctx, rp->flags))) return rc;
-    const bool nee = (rp->flags & RT3_FLAG_ENV_SAMPLING) != 0;
+    const bool nee = (rp->flags & RT3_FLAG_ENV_SAMPLING) != 0, light = (rp->flags & RT3_FLAG_LIGHT_SAMPLING) != 0;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
     ctx->rendered = false;
@@ -2585,7 +2667,8 @@ static int radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys,
     A.rad = ctx->d_rad;
     TracePlan T;
     if (nee && (rc = ensure_env_table(ctx, stream))) return rc;
-    if ((rc = plan_trace(ctx, A, Form::Rays, false, T, nee))) return rc;
+    if (light && (rc = ensure_light_table(ctx, stream))) return rc;
+    if ((rc = plan_trace(ctx, A, Form::Rays, false, T, nee, light))) return rc;
     A.q_rays = (const float4*)d_rays; A.ray_keys = (const uint32_t*)d_keys;
     if ((rc = begin_timed(ctx, stream))) return rc;
     const uint32_t s_end = rp->sample_begin + rp->sample_count;
@@ -2703,6 +2786,24 @@ int rt3_debug_environment_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out
     if ((rc = enter(ctx, nullptr, &stream)) || (rc = ensure_env_table(ctx, stream))) return rc;
     RT3_HIP(hipMemcpyAsync(q_out, ctx->d_env_q.get(), cells * 4u, hipMemcpyDeviceToHost, stream));
     RT3_HIP(hipMemcpyAsync(cdf_out, ctx->d_env_cdf.get(), cells * 8u, hipMemcpyDeviceToHost, stream));
+    if ((rc = leave(ctx, stream))) return rc;
+    RT3_HIP(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// Tests only: the emitters' sampling table of the scene the context holds, downloaded (built first if no call with RT3_FLAG_LIGHT_SAMPLING has built it yet).
+int rt3_debug_light_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint64_t capacity, uint32_t* n_entries) {
+    if (!ctx) return RT3_E_ARG;
+    if (!q_out || !cdf_out || !n_entries) return fail(ctx, RT3_E_ARG, "q_out / cdf_out / n_entries is NULL");
+    int rc;
+    if ((rc = check_scene(ctx))) return rc;
+    const size_t n = (size_t)ctx->n_faces + ctx->n_sph;
+    *n_entries = (uint32_t)n;
+    if (capacity < n) return fail(ctx, RT3_E_ARG, "capacity is smaller than the table (one entry per face and per sphere)");
+    hipStream_t stream;
+    if ((rc = enter(ctx, nullptr, &stream)) || (rc = ensure_light_table(ctx, stream))) return rc;
+    RT3_HIP(hipMemcpyAsync(q_out, ctx->d_light_q.get(), n * 4u, hipMemcpyDeviceToHost, stream));
+    RT3_HIP(hipMemcpyAsync(cdf_out, ctx->d_light_cdf.get(), n * 8u, hipMemcpyDeviceToHost, stream));
     if ((rc = leave(ctx, stream))) return rc;
     RT3_HIP(hipStreamSynchronize(stream));
     return 0;

@@ -7,6 +7,7 @@
 #include "rt3.h"
 #include "rt3_sphere_plan.hpp"
 #include "rt3_env_sample.hpp"
+#include "rt3_light_sample.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -504,6 +505,71 @@ extern "C" int rt3_debug_environment_sample(const float* rgba, uint32_t n, uint3
     rt3env::Sample S;
     rt3env::sample(T.q.data(), T.cdf.data(), rt3env::cells_per_edge(n), T.total, base, depth, S);
     *cell = S.cell; dir[0] = S.dx; dir[1] = S.dy; dir[2] = S.dz; *pdf = S.pdf;
+    return 0;
+}
+
+// The emitters' sampling table and sampling law (rt3.h "Emitters: sampling") on the host: the table built entry after entry — the device
+// builds it in any order and gets the same integers — then rt3light::pick and the point functions, the very ones shade_lane calls.  One (base, depth)
+// per call and thousands of calls per scene in the tests, so the last scene's table is kept with a copy of the arrays that every call compares.
+namespace {
+struct HostLightTable {
+    std::vector<uint8_t> key;                                       // the caller's arrays, byte for byte
+    std::vector<rt3light::Face> face; std::vector<float> cr;
+    std::vector<uint32_t> q; std::vector<uint64_t> cdf; uint64_t total = 0;
+    bool valid = false;
+    static void append(std::vector<uint8_t>& k, const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; k.insert(k.end(), b, b + n); }
+    static std::vector<uint8_t> key_of(const rt3_gface* faces, uint32_t nf, const float* verts, uint32_t nv, const rt3_material* fm, const float* sph,
+                                       const rt3_material* sm, uint32_t ns) {
+        std::vector<uint8_t> k;
+        append(k, &nf, 4); append(k, &nv, 4); append(k, &ns, 4);
+        if (nf) { append(k, faces, (size_t)nf * sizeof(rt3_gface)); append(k, fm, (size_t)nf * sizeof(rt3_material)); }
+        if (nv) append(k, verts, (size_t)nv * 16u);
+        if (ns) { append(k, sph, (size_t)ns * 16u); append(k, sm, (size_t)ns * sizeof(rt3_material)); }
+        return k;
+    }
+    void build(const rt3_gface* faces, uint32_t nf, const float* verts, const rt3_material* fm, const float* sph, const rt3_material* sm, uint32_t ns) {
+        const uint32_t n = nf + ns;
+        face.resize(nf); cr.assign(sph, sph + (size_t)4 * ns);
+        std::vector<float> w(n);
+        float w_max = 0.0f;
+        for (uint32_t i = 0; i < nf; i++) {
+            rt3light::face_of(verts + 4 * (size_t)faces[i].v1, verts + 4 * (size_t)faces[i].v2, verts + 4 * (size_t)faces[i].v3, face[i]);
+            w[i] = rt3light::weight(rt3light::brightness(fm[i].kind, fm[i].rgb[0], fm[i].rgb[1], fm[i].rgb[2]), rt3light::face_area(face[i]));
+        }
+        for (uint32_t i = 0; i < ns; i++)
+            w[nf + i] = rt3light::weight(rt3light::brightness(sm[i].kind, sm[i].rgb[0], sm[i].rgb[1], sm[i].rgb[2]), rt3light::sphere_area(sph[4 * (size_t)i + 3]));
+        for (uint32_t k = 0; k < n; k++) if (w[k] > w_max) w_max = w[k];
+        q.resize(n); cdf.resize(n);
+        total = 0;
+        for (uint32_t k = 0; k < n; k++) { q[k] = rt3light::quantise(w[k], w_max); total += q[k]; cdf[k] = total; }
+        valid = true;
+    }
+};
+}  // namespace
+extern "C" int rt3_debug_light_sample(const rt3_gface* faces, uint32_t n_faces, const float* vertices, uint32_t n_vertices, const rt3_material* face_materials,
+                                      const float* center_radius, const rt3_material* sphere_materials, uint32_t n_spheres, uint32_t base, uint32_t depth,
+                                      uint32_t* light, float point[3], float light_normal[3], float* area, float* pl) {
+    if (!light || !point || !light_normal || !area || !pl) return RT3_E_ARG;
+    if ((n_faces && (!faces || !face_materials)) || (n_vertices && !vertices) || (n_spheres && (!center_radius || !sphere_materials))) return RT3_E_ARG;
+    if ((uint64_t)n_faces + n_spheres > 0x7FFFFFFFull) return RT3_E_ARG;
+    for (uint32_t i = 0; i < n_faces; i++)
+        if (faces[i].v1 >= n_vertices || faces[i].v2 >= n_vertices || faces[i].v3 >= n_vertices) return RT3_E_ARG;
+    static thread_local HostLightTable T;
+    std::vector<uint8_t> key = HostLightTable::key_of(faces, n_faces, vertices, n_vertices, face_materials, center_radius, sphere_materials, n_spheres);
+    if (!T.valid || T.key != key) {
+        T.build(faces, n_faces, vertices, face_materials, center_radius, sphere_materials, n_spheres);
+        T.key = std::move(key);
+    }
+    *light = rt3light::kNoLight; *area = 0.0f; *pl = 0.0f;
+    for (int a = 0; a < 3; a++) point[a] = light_normal[a] = 0.0f;
+    if (T.total == 0) return 0;
+    float ua, ub;
+    const uint32_t li = rt3light::pick(T.cdf.data(), n_faces + n_spheres, T.total, base, depth, ua, ub);
+    rt3light::Point Y;
+    if (li < n_faces) rt3light::point_on_face(T.face[li], ua, ub, Y);
+    else { const float* s = T.cr.data() + 4 * (size_t)(li - n_faces); rt3light::point_on_sphere(s[0], s[1], s[2], s[3], ua, ub, Y); }
+    *light = li; point[0] = Y.x; point[1] = Y.y; point[2] = Y.z; light_normal[0] = Y.nx; light_normal[1] = Y.ny; light_normal[2] = Y.nz;
+    *area = Y.area; *pl = (float)T.q[li] / (float)T.total;
     return 0;
 }
 

@@ -159,12 +159,19 @@ struct Rgb { float r, g, b; };   // one radiance record of the sample storage (t
 //   RenderEnvNee, RaysEnvNee      RenderEnv and RaysEnv under RT3_FLAG_ENV_SAMPLING: a Lambert scatter also draws a direction from the
 //              map's sampling table and casts one shadow ray through the lane's own cast slot (shade_lane); the lane carries a NeePath, the launch
 //              argument is a NeeTraceArgs (both below).  No list form: the adaptive render refuses the flag.
-enum class Form : uint32_t { Render, RenderRef, Query, List, Rays, RenderEnv, ListEnv, RaysEnv, RenderEnvNee, RaysEnvNee };
+//   RenderLight, RaysLight        Render and Rays under RT3_FLAG_LIGHT_SAMPLING: a Lambert scatter also draws a point on an emissive
+//              primitive from the emitters' sampling table and casts one shadow ray towards it through the lane's own cast slot; the lane carries a
+//              LightPath, the launch argument is a LightTraceArgs (both below).  With or without a map: env_n == 0 there means none, and the miss then
+//              evaluates the sky — a branch at run time, not two more forms.  No list form: the adaptive render refuses the flag.
+enum class Form : uint32_t { Render, RenderRef, Query, List, Rays, RenderEnv, ListEnv, RaysEnv, RenderEnvNee, RaysEnvNee, RenderLight, RaysLight };
 constexpr bool is_nee(Form f) { return f == Form::RenderEnvNee || f == Form::RaysEnvNee; }
-constexpr bool is_env(Form f) { return f == Form::RenderEnv || f == Form::ListEnv || f == Form::RaysEnv || is_nee(f); }
+constexpr bool is_light(Form f) { return f == Form::RenderLight || f == Form::RaysLight; }
+constexpr bool has_shadow(Form f) { return is_nee(f) || is_light(f); }                 // a lane's cast may be a shadow ray: no stock entry can hold one
+constexpr bool is_env(Form f) { return f == Form::RenderEnv || f == Form::ListEnv || f == Form::RaysEnv || is_nee(f) || is_light(f); }
 // The twin of an environment form, and every other form itself: what a kernel body and the refill helpers branch on.
 constexpr Form base_form(Form f) {
-    return f == Form::RenderEnv || f == Form::RenderEnvNee ? Form::Render : f == Form::ListEnv ? Form::List : f == Form::RaysEnv || f == Form::RaysEnvNee ? Form::Rays : f;
+    return f == Form::RenderEnv || f == Form::RenderEnvNee || f == Form::RenderLight ? Form::Render : f == Form::ListEnv ? Form::List
+         : f == Form::RaysEnv || f == Form::RaysEnvNee || f == Form::RaysLight ? Form::Rays : f;
 }
 // Batched ray queries (the QUERY forms of the trace kernels; rt3_intersect* / rt3_occluded*): item k of a launch is ray k
 // of the caller's rt3_ray[] (q_rays: two float4 per ray, origin, t_max | direction, pad); its result goes to q_out[k], an rt3_hit (16 bytes), or with
@@ -230,9 +237,16 @@ struct EnvTraceArgs : TraceArgs { const float4* env; uint32_t env_n; uint32_t en
 // of its own.  nee_q: the cells' quantised weights, nee_cdf: their inclusive prefix sums, both [6 nee_m nee_m] in (face, row, column) order; the
 // table's total is nee_cdf[nee_cells - 1], read from device memory (the host never waits for the build).
 struct NeeTraceArgs : EnvTraceArgs { const uint32_t* nee_q; const uint64_t* nee_cdf; uint32_t nee_m; uint32_t nee_cells; };
-template <Form F> using trace_args = std::conditional_t<is_nee(F), NeeTraceArgs, std::conditional_t<is_env(F), EnvTraceArgs, TraceArgs>>;
+// The launch argument of the light sampling forms (RT3_FLAG_LIGHT_SAMPLING): EnvTraceArgs (env_n == 0: no map is set) with the emitters'
+// sampling table behind it, a struct of its own once more.  lt_q: the entries' quantised weights, lt_cdf: their inclusive prefix sums, both [lt_n], faces
+// first and then spheres in the caller's order (lt_n = n_tri + n_sph); the total is lt_cdf[lt_n - 1], read from device memory.  lt_sph_cr: the spheres'
+// (C, r) as the caller gave them — the law samples with r, the trace kernels keep r^2 and 1 / r.
+struct LightTraceArgs : EnvTraceArgs { const uint32_t* lt_q; const uint64_t* lt_cdf; const float4* lt_sph_cr; uint32_t lt_n; uint32_t lt_pad; };
+template <Form F> using trace_args = std::conditional_t<is_light(F), LightTraceArgs,
+                                     std::conditional_t<is_nee(F), NeeTraceArgs, std::conditional_t<is_env(F), EnvTraceArgs, TraceArgs>>>;
 __device__ __forceinline__ const EnvTraceArgs& env_of(const TraceArgs& A) { return static_cast<const EnvTraceArgs&>(A); }   // only where A IS one: an environment form
 __device__ __forceinline__ const NeeTraceArgs& nee_of(const TraceArgs& A) { return static_cast<const NeeTraceArgs&>(A); }   // only where A IS one: a sampling form
+__device__ __forceinline__ const LightTraceArgs& light_of(const TraceArgs& A) { return static_cast<const LightTraceArgs&>(A); }   // only where A IS one: a light sampling form
 
 struct Path {
     float ox, oy, oz, dx, dy, dz;
@@ -246,8 +260,12 @@ struct Path {
 // accounted for (a later miss adds nothing).  The helpers keep taking a Path&; shade_lane, the one reader, gets the rest back with nee_path().
 struct NeePath : Path { float cx = 0.0f, cy = 0.0f, cz = 0.0f, er = 0.0f, eg = 0.0f, eb = 0.0f; uint32_t nee = 0u; };
 constexpr uint32_t kNeeShadow = 1u, kNeeLambert = 2u;
-template <Form F> using path_of = std::conditional_t<is_nee(F), NeePath, Path>;
+// The lane state of the light sampling forms (is_light): a NeePath — e* is then the contribution per unit of the light's radiance — plus
+// the table entry of the light the shadow ray in flight was aimed at: the ray adds only where its nearest hit IS that primitive.
+struct LightPath : NeePath { uint32_t light = 0u; };
+template <Form F> using path_of = std::conditional_t<is_light(F), LightPath, std::conditional_t<is_nee(F), NeePath, Path>>;
 __device__ __forceinline__ NeePath& nee_path(Path& P) { return static_cast<NeePath&>(P); }                                  // only where P IS one: a sampling form
+__device__ __forceinline__ LightPath& light_path(Path& P) { return static_cast<LightPath&>(P); }                            // only where P IS one: a light sampling form
 
 // The reference's plane + three-edge test of one face (SequentialRenderer.cpp:53-98; hit_vertex, raytracer_v4.glsl:116-153), in
 // its own operation order.  n = (normal, n.p1) as k_commit_mesh stores it.

@@ -1051,7 +1051,7 @@ __device__ __forceinline__ void refill_from_traced_stock(const TraceArgs& A, con
 // Form::Query: the batched ray queries' form (refill from the caller's rays, no ray stock; the nearest-hit key goes to query_sink instead of shading).
 // Form::Rays: rt3_radiance*'s form (the caller's rays through rays_path, no ray stock and no strip lists; shading as in the render form, counter-hash table included).
 // Environment forms (FX): the body is the twin's (F = base_form(FX)); shade_lane — here and in the restock — alone gets FX.
-// Sampling forms (is_nee(FX)): the render form takes the plain refill — no traced stock, no strip lists (the host builds none).
+// Sampling forms (has_shadow(FX): is_nee, DESIGN.md 5.2o, and is_light, 5.2p): the render form takes the plain refill — no traced stock, no strip lists (the host builds none).
 template <Form FX>
 __global__ __launch_bounds__(kMB) void k_trace_mfma32(const trace_args<FX> A, const u32x4* __restrict__ frags, uint32_t n_blocks) {
     constexpr Form F = base_form(FX);
@@ -1082,7 +1082,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const trace_args<FX> A, co
     }
     __syncthreads();                                                            // the only barrier
 
-    path_of<FX> P;                                                               // (a NeePath in the sampling forms, a Path in every other)
+    path_of<FX> P;                                                               // (a NeePath or a LightPath in the sampling forms, a Path in every other)
     P.ox = P.oy = P.oz = 0.0f; P.dx = P.dy = 0.0f; P.dz = 1.0f;
     P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0; P.tmax = __builtin_inff();
     bool alive = false;
@@ -1104,7 +1104,7 @@ __global__ __launch_bounds__(kMB) void k_trace_mfma32(const trace_args<FX> A, co
 
     for (;;) {
         if constexpr (F == Form::Query || F == Form::Rays) refill_queries<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);
-        else if constexpr (is_nee(FX)) refill_lanes<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);     // the plain refill: a stock entry cannot hold a shadow ray
+        else if constexpr (has_shadow(FX)) refill_lanes<F>(A, lane, alive, P, chunk_next, chunk_end, exhausted);     // the plain refill: a stock entry cannot hold a shadow ray
         else refill_from_traced_stock<FX>(A, mirror, lane, alive, P, Q, chunk_next, chunk_end, exhausted, primary_casts, exact, ph_restock);
         RT3_SPHASE(ph_refill)
         const unsigned long long live = __ballot(alive);
@@ -1246,7 +1246,7 @@ __global__ __launch_bounds__(kTB) void k_trace_mfma_tiled(const trace_args<FX> A
         __syncthreads();                                                        // the only barrier
     }
 
-    path_of<FX> P;                                                               // (a NeePath in the sampling forms, a Path in every other)
+    path_of<FX> P;                                                               // (a NeePath or a LightPath in the sampling forms, a Path in every other)
     P.ox = P.oy = P.oz = 0.0f; P.dx = P.dy = 0.0f; P.dz = 1.0f;
     P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0; P.tmax = __builtin_inff();
     bool alive = false;

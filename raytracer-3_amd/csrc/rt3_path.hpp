@@ -195,10 +195,31 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
             return;
         }
     }
+    if constexpr (is_light(F)) {
+        LightPath& N = light_path(P);
+        if (alive && (N.nee & kNeeShadow)) {                            // this cast was the shadow ray of the lane's last Lambert scatter
+            const bool face_hit = HAS_TRI && (!HAS_SPH || kind == 1);
+            const uint32_t entry = face_hit ? ibest : A.n_tri + ibest;  // the table's order: faces first, then spheres, each by rt3_hit.index
+            if (kind != 0 && entry == N.light) {                        // the nearest hit IS the chosen light: nothing hides it
+                const float4 m = face_hit ? A.tri_mat[ibest] : sph_mat[ibest];
+                P.lr = fma_(N.er, m.x, P.lr); P.lg = fma_(N.eg, m.y, P.lg); P.lb = fma_(N.eb, m.z, P.lb);
+            }
+            P.dx = N.cx; P.dy = N.cy; P.dz = N.cz;                      // on with the continuation (origin, throughput and depth are already its)
+            N.nee = kNeeLambert;
+            return;
+        }
+    }
     if (alive) {
         bool done = false;
         if (kind == 0) {
-            if constexpr (is_nee(F)) {                                  // (RT3_FLAG_BLACK_BACKGROUND is refused with the flag)
+            if constexpr (is_light(F)) {                                // the plain render's miss: black, the map's plain lookup, or the sky
+                if (!(A.flags & RT3_FLAG_BLACK_BACKGROUND)) {
+                    float r, g, b;
+                    if (env_of(A).env_n != 0u) env_lookup(env_of(A).env, env_of(A).env_n, dx, dy, dz, r, g, b);
+                    else sky(dx, dy, dz, r, g, b);
+                    P.lr = fma_(P.tr, r, P.lr); P.lg = fma_(P.tg, g, P.lg); P.lb = fma_(P.tb, b, P.lb);
+                }
+            } else if constexpr (is_nee(F)) {                                 // (RT3_FLAG_BLACK_BACKGROUND is refused with the flag)
                 if (!(nee_path(P).nee & kNeeLambert)) {
                     float r, g, b;
                     env_lookup(env_of(A).env, env_of(A).env_n, dx, dy, dz, r, g, b);
@@ -227,7 +248,12 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
                 nx = (px - s.x) * invr; ny = (py - s.y) * invr; nz = (pz - s.z) * invr;
             }
             if (mk == RT3_MAT_FLAT) {
-                P.lr = fma_(P.tr, m.x, P.lr); P.lg = fma_(P.tg, m.y, P.lg); P.lb = fma_(P.tb, m.z, P.lb);
+                bool adds = true;
+                if constexpr (is_light(F)) {                            // behind a Lambert scatter the shadow ray has accounted for every light of the table
+                    if (light_path(P).nee & kNeeLambert)
+                        adds = light_of(A).lt_q[HAS_TRI && (!HAS_SPH || kind == 1) ? ibest : A.n_tri + ibest] == 0u;
+                }
+                if (adds) { P.lr = fma_(P.tr, m.x, P.lr); P.lg = fma_(P.tg, m.y, P.lg); P.lb = fma_(P.tb, m.z, P.lb); }
                 done = true;
             } else if (P.depth + 1 == A.max_depth) {
                 done = true;
@@ -290,6 +316,39 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
                     P.ox = px; P.oy = py; P.oz = pz;
                     P.tr *= ar; P.tg *= ag; P.tb *= ab;
                     P.depth += 1;
+                    if constexpr (is_light(F)) {
+                        LightPath& N = light_path(P);
+                        N.nee = mk == RT3_MAT_LAMBERT ? kNeeLambert : 0u;
+                        if (mk == RT3_MAT_LAMBERT) {
+                            const LightTraceArgs& E = light_of(A);
+                            const uint64_t total = E.lt_cdf[E.lt_n - 1u];
+                            if (total != 0ull) {
+                                float ua, ub;
+                                const uint32_t li = rt3light::pick(E.lt_cdf, E.lt_n, total, P.base, P.depth - 1u, ua, ub);
+                                const bool is_sph = !HAS_TRI || (HAS_SPH && li >= A.n_tri);
+                                rt3light::Point Y;
+                                float4 cr = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                                if (is_sph) {
+                                    cr = E.lt_sph_cr[li - A.n_tri];
+                                    rt3light::point_on_sphere(cr.x, cr.y, cr.z, cr.w, ua, ub, Y);
+                                } else {
+                                    const float4 a = A.tri[(size_t)li * 4 + 1], b = A.tri[(size_t)li * 4 + 2], c = A.tri[(size_t)li * 4 + 3];
+                                    const float p1[3] = { a.x, a.y, a.z }, p2[3] = { b.x, b.y, b.z }, p3[3] = { c.x, c.y, c.z };
+                                    rt3light::Face f;
+                                    rt3light::face_of(p1, p2, p3, f);
+                                    rt3light::point_on_face(f, ua, ub, Y);
+                                }
+                                float wx, wy, wz, k;
+                                if (rt3light::connect(Y, is_sph, cr.x, cr.y, cr.z, cr.w, px, py, pz, nx, ny, nz, E.lt_q[li], total, wx, wy, wz, k)) {
+                                    N.er = P.tr * k; N.eg = P.tg * k; N.eb = P.tb * k;
+                                    N.cx = P.dx; N.cy = P.dy; N.cz = P.dz;
+                                    P.dx = wx; P.dy = wy; P.dz = wz;
+                                    N.light = li;
+                                    N.nee = kNeeLambert | kNeeShadow;
+                                }
+                            }
+                        }
+                    }
                     if constexpr (is_nee(F)) {
                         NeePath& N = nee_path(P);
                         N.nee = mk == RT3_MAT_LAMBERT ? kNeeLambert : 0u;
@@ -316,7 +375,7 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
         if (done) {
             A.rad[P.slot] = Rgb{ P.lr, P.lg, P.lb };
             alive = false;
-            if constexpr (is_nee(F)) nee_path(P).nee = 0u;              // the lane's next path starts without a scatter behind it
+            if constexpr (has_shadow(F)) nee_path(P).nee = 0u;              // the lane's next path starts without a scatter behind it
         }
     }
 }

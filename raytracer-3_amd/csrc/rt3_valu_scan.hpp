@@ -268,7 +268,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_brute(const trace_args<FX> A) 
     constexpr Form F = base_form(FX);
     constexpr bool REF = F == Form::RenderRef, QUERY = F == Form::Query;
     const uint32_t lane = lane_id();
-    path_of<FX> P;                                                               // (a NeePath in the sampling forms, a Path in every other)
+    path_of<FX> P;                                                               // (a NeePath or a LightPath in the sampling forms, a Path in every other)
     P.ox = P.oy = P.oz = 0.0f; P.dx = P.dy = 0.0f; P.dz = 1.0f;
     P.tr = P.tg = P.tb = 0.0f; P.lr = P.lg = P.lb = 0.0f; P.slot = 0; P.base = 0; P.depth = 0; P.tmax = __builtin_inff();
     bool alive = false;

@@ -448,7 +448,7 @@ std::vector<float> HipRenderer::motion(Camera& camera, const std::vector<float>&
 std::vector<float> HipRenderer::radiance(const std::vector<rt3_ray>& rays, const std::vector<uint32_t>& keys, uint32_t sample_begin) const {
     if (path.spp == 0) throw Fatal("radiance along rays needs the path tracer (Mode X)");
     if (!keys.empty() && keys.size() != rays.size()) throw Fatal("radiance: keys and rays differ in length");
-    const rt3_radiance_params rp = { path.max_depth, path.seed, path.flags & (RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_ENV_SAMPLING), sample_begin, path.spp, path.t_min };
+    const rt3_radiance_params rp = { path.max_depth, path.seed, path.flags & (RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING), sample_begin, path.spp, path.t_min };
     std::vector<float> out(4 * rays.size());
     if (rt3_radiance(ctx[0], rays.data(), keys.empty() ? nullptr : keys.data(), (uint32_t)rays.size(), &rp, out.data()) != 0)
         throw Fatal(rt3_last_error(ctx[0]));

@@ -8,7 +8,7 @@
 // Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr, --denoise (PFM files),
 // --frames, --orbit and --slide (a sequence, denoised temporally), --adaptive and --counts (--spp as a budget), --rays and --radiance
 // (path-traced radiance along rays read from a file), --env (an environment map from a PFM of six stacked cube faces),
-// --env-sampling (importance sampling of that map with shadow rays).
+// --env-sampling (importance sampling of that map with shadow rays), --light-sampling (the same for the emissive primitives).
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -51,6 +51,7 @@ struct Options {
     std::string rays_path, radiance_path;                          // Mode X: rt3_ray records in, their radiance out as a PFM of n x 1
     std::string env_path;                                          // Mode X: the environment map, a colour PFM of N x 6N (the six faces stacked)
     bool env_sampling = false;                                     // with --env: RT3_FLAG_ENV_SAMPLING
+    bool light_sampling = false;                                   // Mode X: RT3_FLAG_LIGHT_SAMPLING
 };
 
 void print_usage(const char* exe) {
@@ -86,6 +87,8 @@ void print_usage(const char* exe) {
               << "\t\t\t+Z, -Z stacked from top to bottom, N up to 2048. The render, --radiance and --aov use it.\n"
               << "\t   --env-sampling\tWith --env: every diffuse bounce also samples the map by its brightness and casts one shadow ray (a small bright\n"
               << "\t\t\tsun converges). The render and --radiance; not with --adaptive, nor with a scene whose background is black.\n"
+              << "\t   --light-sampling\tMode X: every diffuse bounce also samples the emissive primitives by brightness times area and casts one shadow\n"
+              << "\t\t\tray (a small lamp converges). The render and --radiance; not with --adaptive, nor with --env-sampling.\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -124,6 +127,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         if (key == "--dump-scene") { opt.dump_scene = true; continue; }
         if (key == "--refit") { opt.refit = true; continue; }
         if (key == "--env-sampling") { opt.env_sampling = true; continue; }
+        if (key == "--light-sampling") { opt.light_sampling = true; continue; }
         const bool known = key == "-f" || key == "--format" || key == "-W" || key == "--width" || key == "-H" || key == "--height" ||
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
@@ -231,6 +235,18 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     }
     if (opt.env_sampling && opt.adaptive) {
         std::cerr << "--env-sampling is not available with --adaptive." << std::endl;
+        return -1;
+    }
+    if (mode_r && opt.light_sampling) {
+        std::cerr << "--light-sampling needs the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
+    if (opt.light_sampling && opt.env_sampling) {
+        std::cerr << "--light-sampling is not available with --env-sampling." << std::endl;
+        return -1;
+    }
+    if (opt.light_sampling && opt.adaptive) {
+        std::cerr << "--light-sampling is not available with --adaptive." << std::endl;
         return -1;
     }
     if (mode_r && opt.adaptive) {
@@ -398,6 +414,7 @@ int main(int argc, const char** argv) {
             renderer.set_environment(rgba, n_face);
             if (opt.env_sampling) path.flags |= RT3_FLAG_ENV_SAMPLING;
         }
+        if (opt.light_sampling) path.flags |= RT3_FLAG_LIGHT_SAMPLING;
         const uint32_t seed0 = path.seed;
         const bool temporal = opt.frames > 1 && !opt.denoise_path.empty();
         const rt3_temporal_params tp{ { 5, 128, 4.0f, 1.0f }, 0.2f, 0.2f, 2.0f, 0.9f };       // the defaults of DESIGN.md 4.11 and 4.12

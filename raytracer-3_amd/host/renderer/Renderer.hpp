@@ -28,7 +28,7 @@ struct History {
 
 // Mode-X knobs the reference API has no place for (spp / depth / seed ...); spp == 0 means Mode R.
 struct PathOptions {
-    uint32_t spp = 0, max_depth = 50, seed = 1, flags = 0;          // flags: RT3_FLAG_* of rt3.h; RT3_FLAG_ENV_SAMPLING needs set_environment() first
+    uint32_t spp = 0, max_depth = 50, seed = 1, flags = 0;          // flags: RT3_FLAG_* of rt3.h; RT3_FLAG_ENV_SAMPLING needs set_environment() first, RT3_FLAG_LIGHT_SAMPLING excludes it
     float lens_radius = 0.0f, t_min = 0.001f;
     uint32_t tile_rows = 8;
 };
@@ -74,7 +74,7 @@ public:
     // frame's spheres (4 floats each) and merged vertices (xyzw), an empty vector for a class that did not move
     std::vector<float> motion(Camera& camera, const std::vector<float>& prev_center_radius, const std::vector<float>& prev_vertices_xyzw) const;
     // Mode X only: path-traced radiance along the caller's rays on device 0 (rt3_radiance), (r, g, b, 0) per ray: path.spp samples from sample_begin
-    // on, path.max_depth, path.seed, path.t_min and the BLACK_BACKGROUND and ENV_SAMPLING bits of path.flags; keys: empty (a ray's index is its key) or one per ray
+    // on, path.max_depth, path.seed, path.t_min and the BLACK_BACKGROUND, ENV_SAMPLING and LIGHT_SAMPLING bits of path.flags; keys: empty (a ray's index is its key) or one per ray
     std::vector<float> radiance(const std::vector<rt3_ray>& rays, const std::vector<uint32_t>& keys = {}, uint32_t sample_begin = 0) const;
     size_t faces() const { return n_faces; }
     size_t spheres() const { return n_spheres; }

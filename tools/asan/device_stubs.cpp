@@ -51,6 +51,7 @@ int rt3_set_environment_device(rt3_ctx*, const void*, uint32_t, void*) { return 
 int rt3_clear_environment(rt3_ctx*) { return RT3_E_DEVICE; }
 uint32_t rt3_environment_size(rt3_ctx*) { return 0; }
 int rt3_debug_environment_table(rt3_ctx*, uint32_t*, uint64_t*, uint64_t, uint32_t*) { return RT3_E_DEVICE; }     // (rt3_debug_environment_sample is host code too)
+int rt3_debug_light_table(rt3_ctx*, uint32_t*, uint64_t*, uint64_t, uint32_t*) { return RT3_E_DEVICE; }                 // (rt3_debug_light_sample is host code too)
 int rt3_debug_force_plain_mode_r(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_force_brute(rt3_ctx*, int) { return RT3_E_DEVICE; }
 int rt3_debug_force_flat_filter(rt3_ctx*, int) { return RT3_E_DEVICE; }

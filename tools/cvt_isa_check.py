@@ -8,7 +8,8 @@ apart.  This script makes that a BUILD-TIME property:
 
     python tools/cvt_isa_check.py [listing.s]        exit 1 if any v_cvt_pk_bf16_f32 of the listing has a reader of its destination register
                                                      in the next issue slot; without an argument it compiles the product sources itself
-                                                     (hipcc -S, device only) — tests/test_cvt_isa.py runs it that way in the CPU suite
+                                                     (hipcc -S, device only; four listings in parallel, FORM_PARTS below) —
+                                                     tests/test_cvt_isa.py runs it that way in the CPU suite
     python tools/cvt_isa_check.py --table a.s b.s    per kernel: distance (wait states) from every conversion to its first reader, and back to the
                                                      last MFMA that READ the destination register as an A/B operand (the write-after-read window)
 """
@@ -89,12 +90,28 @@ def analyse(body):
     return rows
 
 
+# The trace kernels are instantiated per Form (rt3_kernel_common.hpp): RT3_FORM_MASK (rt3_device.hip) compiles some of the forms only.  One listing of
+# everything takes ten minutes on one core; with four or more cores the forms are compiled as four listings in parallel (a kernel's code does not depend
+# on which kernels are compiled beside it; the kernels that have no form are in every listing and counted once).
+FORM_PARTS = [0x007, 0x038, 0x3C0, 0xC00]                            # Render RenderRef Query | List Rays RenderEnv | ListEnv RaysEnv RenderEnvNee RaysEnvNee | RenderLight RaysLight
+N_FORMS = 12
+
+
 def compile_product():
-    out = os.path.join(tempfile.mkdtemp(prefix="rt3_isa_"), "rt3_device.s")
     src = os.path.join(ROOT, "raytracer-3_amd", "csrc", "rt3_device.hip")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I", os.path.join(ROOT, "include"),
-                           "-S", "--cuda-device-only", "-o", out, src], stderr=subprocess.DEVNULL)
-    return out
+    common = open(os.path.join(ROOT, "raytracer-3_amd", "csrc", "rt3_kernel_common.hpp")).read()
+    forms = re.search(r"enum class Form : uint32_t \{([^}]*)\}", common).group(1).split(",")
+    if len(forms) != N_FORMS:
+        raise SystemExit("cvt_isa_check.py: rt3_kernel_common.hpp has %d forms, FORM_PARTS covers %d" % (len(forms), N_FORMS))
+    assert sum(FORM_PARTS) == (1 << N_FORMS) - 1 and all(a & b == 0 for i, a in enumerate(FORM_PARTS) for b in FORM_PARTS[i + 1:])
+    masks = FORM_PARTS if (os.cpu_count() or 1) >= 4 else [(1 << N_FORMS) - 1]
+    tmp = tempfile.mkdtemp(prefix="rt3_isa_")
+    outs = [os.path.join(tmp, "rt3_device_%03x.s" % m) for m in masks]
+    procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I", os.path.join(ROOT, "include"),
+                               "-DRT3_FORM_MASK=0x%xu" % m, "-S", "--cuda-device-only", "-o", out, src], stderr=subprocess.DEVNULL) for m, out in zip(masks, outs)]
+    if any([p.wait() != 0 for p in procs]):
+        raise SystemExit("cvt_isa_check.py: hipcc failed")
+    return outs
 
 
 def main():
@@ -111,10 +128,14 @@ def main():
                 print("  %-70s conversions %3d | wait states to first reader (8 = 8+): %s | back to last MFMA reading the register as A/B: %s"
                       % (name[:70], len(rows), dict(sorted(fwd.items(), key=str)), dict(back)))
         return 0
-    path = args[0] if args else compile_product()
+    paths = [args[0]] if args else compile_product()
+    path = ", ".join(paths)
+    every = {}
+    for one in paths:
+        every.update(kernels(one))                                    # (a kernel that is in several listings is the same code in each)
     bad = 0
     total = 0
-    for name, body in sorted(kernels(path).items()):
+    for name, body in sorted(every.items()):
         for fwd, _back, nxt in analyse(body):
             total += 1
             if fwd == 0:
