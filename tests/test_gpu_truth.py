@@ -3,7 +3,9 @@
 Every other GPU test compares the kernels with the CPU oracle or with each other, all written by the same hand from the same formulas; these
 compare them with the geometry itself: (a) rt3_intersect / rt3_occluded with a brute-force float64 nearest hit, (b) rt3_camera_rays with the
 float64 camera ray and the documented key layout, (c) rt3_render_aov with the float64 hit and normal, (d) the Lambert scatter with the
-cosine law, (e) the metal scatter with the mirror law, (f) the dielectric with Snell and Schlick.  Tolerances are the derived float32 error
+cosine law, (e) the metal scatter with the mirror law, (f) the dielectric with Snell and Schlick, (g) the path loop over many bounces with
+the closed form of an integrating sphere (also through rt3_radiance and RT3_FLAG_LIGHT_SAMPLING), (h) metal fuzz with its absorption law,
+(i) a glass sphere with its enumerated path tree, (j) the sky and the RGBA8 pack.  Tolerances are the derived float32 error
 bounds of truth_ref.py or statistical; rays the bounds cannot decide are left out and counted.  The same checks run against the oracle,
 without a GPU, in tests/test_truth_ref.py, which also shows that each helper used here rejects the fault it guards against."""
 import numpy as np
@@ -157,3 +159,148 @@ def test_dielectric_obeys_snell_and_schlick(rt3, renderer, back):
     fig = K.check_glass(px, ex, need_tir=back)
     print("kernel glass,", "back" if back else "front", fig)
     assert fig["counted"] > 500
+
+
+# ------------------------------------------------------------------------------------------------ (g) the integrating sphere
+def first_hits_meet_the_wall(rt3, renderer, c, pp, spp, step=256):
+    """rt3_intersect over rt3_camera_rays, every sample of every pixel: the wall and nothing else."""
+    for s in range(0, spp, step):
+        first = renderer.intersect(renderer.camera_rays(c, pp, s, min(step, spp - s)), 0.001)
+        if not K.all_meet_the_wall(first["kind"], first["index"]):
+            return False
+    return True
+
+
+@pytest.mark.parametrize("case", range(len(K.INTEGRATING)), ids=K.INTEGRATING_IDS)
+def test_multi_bounce_transport_in_the_integrating_sphere(rt3, renderer, case):
+    """Mean, every pixel and ray_casts per sample of a depth-D render against the closed form (truth_ref.integrating_sphere), 6 sigma with
+    the exact sigma.  Figures: DESIGN.md 5.2k."""
+    r, R, a, E, D = K.INTEGRATING[case]
+    sc = K.integrating_scene(r, R, a, E)
+    cam, p = K.integrating_camera(r, R, D)
+    c, pp = cam.struct(rt3.rt3_camera), params(rt3, p)
+    upload(rt3, renderer, sc)
+    assert first_hits_meet_the_wall(rt3, renderer, c, pp, p.spp)
+    renderer.render_path(c, pp)
+    casts = renderer.stats().ray_casts
+    mean = renderer.accum_resolve(pp)
+    assert np.array_equal(mean[..., 0], mean[..., 1]) and np.array_equal(mean[..., 0], mean[..., 2])
+    fig = K.check_integrating(T.integrating_sphere(r, R, a, E, D), mean[..., 0], p.spp, casts / (p.width * p.height * p.spp), D)
+    print("kernel integrating sphere", K.INTEGRATING_IDS[case], fig)
+
+
+def test_radiance_in_the_integrating_sphere(rt3, renderer):
+    """rt3_radiance along 2^14 rays that start in the gap and meet the wall, 64 samples each, depth 8: the same mean, the same bound."""
+    r, R, a, E, D = K.INTEGRATING[2]
+    upload(rt3, renderer, K.integrating_scene(r, R, a, E))
+    o, d = K.integrating_rays(r, R, 1 << 14)
+    rays = np.zeros(len(o), rt3.RAY)
+    rays["origin"], rays["direction"], rays["t_max"] = o, d, np.inf
+    first = renderer.intersect(rays, 0.001)
+    assert K.all_meet_the_wall(first["kind"], first["index"])
+    rad = renderer.radiance(rays, samples=64, max_depth=D, seed=13, flags=rt3.FLAG_BLACK_BACKGROUND, t_min=0.001)
+    assert np.array_equal(rad[:, 0], rad[:, 1]) and np.array_equal(rad[:, 0], rad[:, 2])
+    fig = K.check_integrating(T.integrating_sphere(r, R, a, E, D), rad[:, 0], 64, each=False)
+    print("kernel rt3_radiance in the integrating sphere", fig)
+
+
+@pytest.mark.parametrize("depth", [2, 12])
+def test_light_sampling_in_the_integrating_sphere(rt3, renderer, depth):
+    """RT3_FLAG_LIGHT_SAMPLING, which the oracle does not implement, against the same closed form: a shadow ray at every wall hit gives a
+    sample within [0, light_sample_range], so its sigma is at most half that range (the furnace test's derivation); 6 half-ranges /
+    sqrt(samples).  The measured z in units of the exact plain sigma is printed beside it."""
+    r, R, a, E, _ = K.INTEGRATING[4]
+    w, h, spp = 64, 48, 1024
+    upload(rt3, renderer, K.integrating_scene(r, R, a, E))
+    cam, p = K.integrating_camera(r, R, depth, size=(w, h, spp), seed=9, flags=K.FLAG_BLACK | rt3.FLAG_LIGHT_SAMPLING)
+    c, pp = cam.struct(rt3.rt3_camera), params(rt3, p)
+    assert first_hits_meet_the_wall(rt3, renderer, c, pp, spp)
+    renderer.render_path(c, pp)
+    mean = renderer.accum_resolve(pp)[..., 0].astype(np.float64).mean()
+    law = T.integrating_sphere(r, R, a, E, depth)
+    fig = K.check_range_mean(mean, law["mean"], 0.0, K.light_sample_range(r, R, a, E, depth), w * h * spp)
+    print("kernel light sampling in the integrating sphere, depth", depth, fig, "z in plain sigmas %.2f" % (
+        (mean - law["mean"]) / (law["sigma"] / np.sqrt(w * h * spp))))
+
+
+def test_light_sampling_leaves_the_pixels_on_the_emitter(rt3, renderer):
+    """The camera turned to the emitter: a pixel whose every primary ray meets it shows E exactly, flag or not."""
+    r, R, a, E, D = K.INTEGRATING[4]
+    upload(rt3, renderer, K.integrating_scene(r, R, a, E))
+    cam, p = K.integrating_camera(r, R, D, size=(64, 48, 16), flags=K.FLAG_BLACK | rt3.FLAG_LIGHT_SAMPLING, inward=True)
+    c, pp = cam.struct(rt3.rt3_camera), params(rt3, p)
+    first = renderer.intersect(renderer.camera_rays(c, pp), 0.001)
+    on = ((first["kind"] == rt3.HIT_SPHERE) & (first["index"] == K.EMITTER)).reshape(p.spp, -1).all(axis=0)
+    assert on.sum() > 500 and (~on).sum() > 500
+    renderer.render_path(c, pp)
+    mean = renderer.accum_resolve(pp).reshape(-1, 4)
+    assert (mean[on, :3] == np.float32(E)).all() and (mean[~on, :3] != np.float32(E)).any()
+
+
+# ------------------------------------------------------------------------------------------------ (h) metal fuzz
+_fuzz_cos = {}
+
+
+def fuzz_cosines(rt3, ground):
+    """The float64 cosines of incidence of every sample, once per ground: they do not depend on f."""
+    if ground not in _fuzz_cos:
+        cam, p = K.fuzz_camera(ground)
+        o, d, _ = K.expected_camera_rays(cam, p)
+        _fuzz_cos[ground] = K.fuzz_cosines(K.fuzz_scene(ground, 1.0, *source(rt3)), o, d, p.spp)
+    return _fuzz_cos[ground]
+
+
+@pytest.mark.parametrize("f", K.FUZZ["fs"])
+@pytest.mark.parametrize("ground", ["triangles", "sphere"])
+def test_metal_fuzz_obeys_the_absorption_law(rt3, renderer, ground, f):
+    sc = K.fuzz_scene(ground, f, *source(rt3))
+    cam, p = K.fuzz_camera(ground)
+    c, pp = cam.struct(rt3.rt3_camera), params(rt3, p)
+    upload(rt3, renderer, sc)
+    renderer.render_path(c, pp)
+    mean = renderer.accum_resolve(pp)
+    assert (mean[..., 3] == 0).all()
+    fig = K.check_fuzz(mean[..., :3].reshape(-1, 3), fuzz_cosines(rt3, ground), f)
+    print("kernel fuzz", ground, f, fig)
+    assert fig["statistical"] > 100 and (f == 1.0 or fig["exact"] > 100)
+
+
+# ------------------------------------------------------------------------------------------------ (i) a glass sphere
+def test_glass_sphere_follows_the_path_tree(rt3, renderer):
+    """The reference's own share of skipped pixels: 34 of 2304 (1.5 %)."""
+    sc, cam, p = K.glass_sphere_scene()
+    c, pp = cam.struct(rt3.rt3_camera), params(rt3, p)
+    upload(rt3, renderer, sc)
+    rays = renderer.camera_rays(c, pp)
+    K.check_camera_rays(cam, p, rays["origin"], rays["direction"], K.expected_camera_rays(cam, p))
+    tree = K.glass_tree(sc, p, rays["origin"], rays["direction"])      # behind the rays the kernel really traced
+    fig = K.check_glass_tree(renderer.render_path(c, pp), tree)
+    print("kernel glass sphere", fig)
+    assert fig["through_glass"] >= 500 and fig["reflected"] >= 20 and fig["counted"] >= 100
+
+
+# ------------------------------------------------------------------------------------------------ (j) sky and pack
+def test_sky(rt3, renderer):
+    sc, cam, p = K.sky_scene()
+    c, pp = cam.struct(rt3.rt3_camera), params(rt3, p)
+    upload(rt3, renderer, sc)
+    renderer.render_path(c, pp)
+    assert renderer.stats().ray_casts == p.width * p.height
+    fig = K.check_sky(renderer.accum_resolve(pp)[..., :3], cam, p)
+    print("kernel sky", fig)
+    assert fig["t_range"][0] < 0.4 and fig["t_range"][1] > 0.8       # below and above the horizon
+
+
+@pytest.mark.parametrize("gamma2", [False, True], ids=["linear", "gamma2"])
+def test_pack(rt3, renderer, gamma2):
+    sc, cam, p = K.pack_scene(gamma2)
+    rgb, amb, hit = K.pack_expectation(sc, cam, p)
+    assert not amb.any()
+    c, pp = cam.struct(rt3.rt3_camera), params(rt3, p)
+    upload(rt3, renderer, sc)
+    px = renderer.render_path(c, pp)
+    linear = renderer.accum_resolve(pp)                                # of the same call
+    assert np.array_equal(linear[..., :3].reshape(-1, 3), rgb), "the linear frame is the material's colour, bit for bit"
+    fig = K.check_pack(px, linear[..., :3], gamma2)
+    print("kernel pack", "gamma2" if gamma2 else "linear", fig)
+    assert fig["ties"] == 0 and fig["bytes_seen"] == 256 and fig["clamped"] > 20 and fig["zeros"] > 1000

@@ -4,7 +4,8 @@
 answer set built from the reference's own output, so the suite is known to notice that fault.  3. The CPU oracle against truth: the checks
 of tests/test_gpu_truth.py with oracle_nearest / oracle_render_path in the kernels' place (the kernels equal the oracle bit for bit, so what
 holds here is what they can pass).  The oracle exports neither camera rays nor AOVs; (b) and (c) have their self-checks here and their
-comparison on the GPU.
+comparison on the GPU.  4.-6. The same three steps for the closed forms and enumerable laws behind multi-bounce transport (the integrating
+sphere), metal fuzz, a glass sphere's path tree, the sky and the RGBA8 pack.
 
 Figures of this file's run (rays or pixels compared / skipped as ambiguous / largest error over bound or |z|): see DESIGN.md 5.2k."""
 import json
@@ -173,10 +174,10 @@ def mixed64(oracle):
     return dict(sc=sc, o=o, d=d, cls=cls, t_min=t_min, ref=ref, kind=kind, index=index, t=t)
 
 
-def render(oracle, sc, cam, p, want_sum=False):
+def render(oracle, sc, cam, p, want_sum=False, threads=8):
     mat = lambda m: None if m is None else np.ascontiguousarray(m).view(oracle.MATERIAL)      # noqa: E731
     return oracle.render_path(cam.struct(oracle.Camera), oracle.make_params(**p.kwargs()), spheres=sc["spheres"], smats=mat(sc["smats"]),
-                              faces=sc["faces"], verts=sc["verts"], fmats=mat(sc["fmats"]), want_sum=want_sum)
+                              faces=sc["faces"], verts=sc["verts"], fmats=mat(sc["fmats"]), want_sum=want_sum, threads=threads)
 
 
 # ====================================================================================================================== 2. mutants
@@ -335,3 +336,201 @@ def test_oracle_snell_and_schlick(oracle, back):
     if not back:
         R = ex["R"][ex["specular"] & ~ex["skip"]]
         assert R.min() > 0.04 and R.max() < 0.5 and fig["total_reflection"] == 0
+
+
+# ====================================================================================================================== 4. closed forms: known answers
+def test_integrating_sphere_known_answers():
+    law = T.integrating_sphere(1.0, 2.0, 0.8, 3.0, 2)
+    assert law["F"] == 0.25 and abs(law["mean"] - 0.8 * 0.25 * 3.0) < 1e-15 and law["casts"] == 2.0          # D = 2: one bounce, a F E
+    assert abs(law["second"] - (0.8 * 3.0) ** 2 * 0.25) < 1e-15
+    law = T.integrating_sphere(1.0, 2.0, 0.8, 3.0, 3)
+    assert abs(law["mean"] - 3.0 * 0.25 * (0.8 + 0.64 * 0.75)) < 1e-15 and law["casts"] == 2.75
+    assert T.integrating_sphere(1.0, 2.0, 0.8, 3.0, 1)["mean"] == 0.0                                          # D = 1: the wall, and nothing else
+    # D -> infinity: the geometric series a F E / (1 - a (1 - F)), and 1 + 1 / F casts
+    law = T.integrating_sphere(1.0, 2.0, 0.8, 3.0, 400)
+    assert abs(law["mean"] - 0.8 * 0.25 * 3.0 / (1.0 - 0.8 * 0.75)) < 1e-12 and abs(law["casts"] - 5.0) < 1e-12
+
+
+def test_fuzz_absorption_known_answers_and_by_sampling():
+    assert T.fuzz_absorption(0.0, 1.0) == 0.5 and T.fuzz_absorption(1.0, 1.0) == 0.0 and T.fuzz_absorption(0.25, 0.5) == 0.25
+    assert T.fuzz_absorption(0.6, 0.5) == 0.0
+    rng = np.random.default_rng(2)                                     # the construction itself, in float64: r + f u against n
+    u = K.unit(rng, 400000)
+    for cos, f in ((0.3, 1.0), (0.1, 0.2), (0.45, 0.5)):
+        r = np.array([np.sqrt(1.0 - cos * cos), cos, 0.0])
+        share = (((r[None] + f * u) @ np.array([0.0, 1.0, 0.0])) <= 0).mean()
+        p = T.fuzz_absorption(cos, f)
+        assert abs(share - p) < 6.0 * np.sqrt(p * (1 - p) / len(u))
+
+
+def test_sky_and_pack_known_answers():
+    assert np.allclose(T.sky([[0.0, 1.0, 0.0], [0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 3.0, 0.0]]),
+                       [[0.5, 0.7, 1.0], [1.0, 1.0, 1.0], [0.75, 0.85, 1.0], [0.5, 0.7, 1.0]], atol=1e-15)
+    w, b, tie = T.pack([[1.0, 0.5, 0.0], [2.0, 0.25, 0.001], [0.5, 0.5 / 255.0, 1.4999 / 255.0]], False)
+    assert [hex(int(x)) for x in w] == ["0xff8000ff", "0xff4000ff", "0x800101ff"]      # 127.5 rounds away from zero, as roundf does
+    assert tie.tolist() == [[False, True, False], [False, False, False], [True, True, False]]
+    w, b, tie = T.pack([[0.25, 4.0, 1.0 / 255.0 ** 2]], True)
+    assert b.tolist() == [[128, 255, 1]] and tie[0, 0] and not tie[0, 1]
+
+
+# ====================================================================================================================== 5. mutants of the new helpers
+def test_mutant_integrating_sphere_off_by_one_and_linear_form_factor_are_rejected():
+    w, h, spp = K.INTEGRATING_SIZE
+    for r, R, a, E, D in K.INTEGRATING:
+        law = T.integrating_sphere(r, R, a, E, D)
+        K.check_integrating(law, np.full(w * h, law["mean"]), spp, law["casts"], D)                    # the law's own noise-free frame passes
+        one_more = T.integrating_sphere(r, R, a, E, D + 1)                                              # D terms for D - 1
+        if D <= 8:                                                      # the extra term a^D (1 - F)^(D - 1) F E: 17 sigma of the frame mean at D = 8,
+            with pytest.raises(AssertionError, match="sigma"):         # 0.3 at R = 4, D = 12, 1e-5 at D = 30: the shallow cases guard the cut-off
+                K.check_integrating(law, np.full(w * h, one_more["mean"]), spp)
+        if D <= 12:                                                     # one more cast with probability (1 - F)^(D - 1): 0.49 at R = 4, D = 12
+            with pytest.raises(AssertionError, match="casts"):
+                K.check_integrating(law, np.full(w * h, law["mean"]), spp, one_more["casts"], D)
+        linear = T.integrating_sphere(np.sqrt(r * R), R, a, E, D)                                       # F = r / R
+        assert linear["F"] == pytest.approx(r / R)
+        with pytest.raises(AssertionError, match="sigma"):
+            K.check_integrating(law, np.full(w * h, linear["mean"]), spp)
+
+
+@pytest.fixture(scope="module")
+def fuzz_cos(oracle):
+    """Scene-independent of f: the cosines of incidence of every sample of the fuzz frame, per ground."""
+    cam, p = K.fuzz_camera()
+    o, d, _ = K.expected_camera_rays(cam, p)
+    tri = K.fuzz_scene("triangles", 1.0, make_triangle(oracle), oracle.merge)
+    return {"triangles": K.fuzz_cosines(tri, o, d, p.spp), "sphere": K.fuzz_cosines(K.fuzz_scene("sphere", 1.0), o, d, p.spp)}
+
+
+@pytest.mark.parametrize("f", K.FUZZ["fs"])
+def test_mutant_fuzz_in_the_ball_and_unscaled_fuzz_are_rejected(fuzz_cos, f):
+    cos = fuzz_cos["triangles"]
+    full = np.array(K.FUZZ["rgb"]) * K.FUZZ["c"]
+    frame = lambda law: full[None] * (1.0 - law(cos, f).mean(axis=0))[:, None]      # noqa: E731
+    fig = K.check_fuzz(frame(T.fuzz_absorption), cos, f)
+    assert fig["statistical"] > 100 and (f == 1.0 or fig["exact"] > 100)
+    assert cos.max() > 0.97 and cos.min() < 0.17
+    with pytest.raises(AssertionError, match="sigma"):
+        K.check_fuzz(frame(K.absorption_in_the_ball), cos, f)
+    if f != 1.0:
+        with pytest.raises(AssertionError):
+            K.check_fuzz(frame(K.absorption_unscaled), cos, f)
+    with pytest.raises(AssertionError):
+        K.check_fuzz(frame(T.fuzz_absorption)[:, ::-1], cos, f)        # the attenuation's channels swapped
+
+
+@pytest.fixture(scope="module")
+def glass_sphere():
+    """The glass-sphere scene with the float32 primary rays of DESIGN.md 4.1 (themselves within (b)'s bounds of camera_ray) and their tree."""
+    sc, cam, p = K.glass_sphere_scene()
+    o, d = K.pinhole_rays_f32(cam, p)
+    K.check_camera_rays(cam, p, o, d, K.expected_camera_rays(cam, p))
+    return sc, cam, p, o, d, K.glass_tree(sc, p, o, d)
+
+
+def test_mutant_glass_sphere_with_ri_kept_or_the_normal_unflipped_is_rejected(glass_sphere):
+    sc, cam, p, o, d, tree = glass_sphere
+    rng = np.random.default_rng(4)
+    fig = K.check_glass_tree(K.sample_glass_tree(tree, rng), tree)
+    assert fig["through_glass"] >= 500 and fig["reflected"] >= 20
+    for m in ("ri_kept", "normal_unflipped"):
+        with pytest.raises(AssertionError):
+            K.check_glass_tree(K.sample_glass_tree(K.glass_tree(sc, p, o, d, mutate=m), rng), tree)
+
+
+def test_mutant_sky_of_y_is_rejected():
+    sc, cam, p = K.sky_scene()
+    xx, yy = K.pixel_grid(p)
+    _, d, _ = T.camera_ray(cam, p, xx, yy)
+    fig = K.check_sky(T.sky(d), cam, p)
+    assert fig["t_range"][0] < 0.4 and fig["t_range"][1] > 0.8       # below and above the horizon
+    with pytest.raises(AssertionError, match="bound"):
+        K.check_sky(K.sky_of_y(d), cam, p)
+
+
+@pytest.mark.parametrize("gamma2", [False, True], ids=["linear", "gamma2"])
+def test_mutant_pack_truncated_reversed_or_gamma_after_the_bytes_is_rejected(gamma2):
+    sc, cam, p = K.pack_scene(gamma2)
+    rgb, amb, hit = K.pack_expectation(sc, cam, p)
+    words, b, tie = T.pack(rgb, gamma2)
+    fig = K.check_pack(words, rgb, gamma2)
+    assert fig["ties"] == 0 and fig["bytes_seen"] == 256 and fig["clamped"] > 20 and fig["zeros"] > 1000
+
+    def truncated(x, g):
+        x = np.asarray(x, np.float32).astype(np.float64)
+        t = np.floor(255.0 * np.clip(np.sqrt(x) if g else x, 0.0, 1.0)).astype(np.uint32)
+        return (t[:, 0] << 24) | (t[:, 1] << 16) | (t[:, 2] << 8) | np.uint32(0xFF)
+
+    def bytes_then_gamma(x, g):
+        lin = T.pack(x, False)[1]
+        t = np.floor(255.0 * np.sqrt(lin / 255.0) + 0.5).astype(np.uint32)
+        return (t[:, 0] << 24) | (t[:, 1] << 16) | (t[:, 2] << 8) | np.uint32(0xFF)
+
+    with pytest.raises(AssertionError, match="another byte"):
+        K.check_pack(truncated(rgb, gamma2), rgb, gamma2)
+    with pytest.raises(AssertionError):
+        K.check_pack((b[:, 2] << 24) | (b[:, 1] << 16) | (b[:, 0] << 8) | np.uint32(0xFF), rgb, gamma2)      # a, b, g, r for r, g, b, a
+    with pytest.raises(AssertionError):
+        K.check_pack(np.uint32(0xFF000000) | (b[:, 2] << 16) | (b[:, 1] << 8) | b[:, 0], rgb, gamma2)         # the word's bytes reversed
+    if gamma2:
+        with pytest.raises(AssertionError, match="another byte"):
+            K.check_pack(bytes_then_gamma(rgb, gamma2), rgb, gamma2)
+
+
+# ====================================================================================================================== 6. the oracle against the closed forms
+THREADS = 16
+
+
+@pytest.mark.parametrize("case", range(len(K.INTEGRATING)), ids=K.INTEGRATING_IDS)
+def test_oracle_integrating_sphere(oracle, case):
+    r, R, a, E, D = K.INTEGRATING[case]
+    sc = K.integrating_scene(r, R, a, E)
+    cam, p = K.integrating_camera(r, R, D)
+    o, d, _ = K.expected_camera_rays(cam, p)
+    first = T.nearest_hit(o, d, p.t_min, np.inf, sc["spheres"], chunk=1 << 16)
+    assert K.all_meet_the_wall(first["kind"], first["index"]) and not first["ambiguous"].any()
+    _, total, casts = render(oracle, sc, cam, p, want_sum=True, threads=THREADS)
+    assert np.array_equal(total[..., 0], total[..., 1]) and np.array_equal(total[..., 0], total[..., 2])
+    n = p.width * p.height * p.spp
+    fig = K.check_integrating(T.integrating_sphere(r, R, a, E, D), total[..., 0].astype(np.float64) / p.spp, p.spp, casts / n, D)
+    print("oracle integrating sphere", K.INTEGRATING_IDS[case], fig)
+
+
+@pytest.mark.parametrize("f", K.FUZZ["fs"])
+@pytest.mark.parametrize("ground", ["triangles", "sphere"])
+def test_oracle_metal_fuzz_obeys_the_absorption_law(oracle, fuzz_cos, ground, f):
+    sc = K.fuzz_scene(ground, f, make_triangle(oracle), oracle.merge)
+    cam, p = K.fuzz_camera(ground)
+    _, total, _ = render(oracle, sc, cam, p, want_sum=True, threads=THREADS)
+    fig = K.check_fuzz(total.reshape(-1, 3).astype(np.float64) / p.spp, fuzz_cos[ground], f)
+    print("oracle fuzz", ground, f, fig)
+    assert fig["statistical"] > 100 and (f == 1.0 or fig["exact"] > 100)
+
+
+def test_oracle_glass_sphere_follows_the_path_tree(oracle, glass_sphere):
+    """The reference's own share of skipped pixels: 34 of 2304 (1.5 %)."""
+    sc, cam, p, o, d, tree = glass_sphere
+    px, _ = render(oracle, sc, cam, p)
+    fig = K.check_glass_tree(px, tree)
+    print("oracle glass sphere", fig)
+    assert fig["through_glass"] >= 500 and fig["reflected"] >= 20 and fig["counted"] >= 100
+
+
+def test_oracle_sky(oracle):
+    sc, cam, p = K.sky_scene()
+    px, total, casts = render(oracle, sc, cam, p, want_sum=True)
+    assert casts == p.width * p.height
+    fig = K.check_sky(total, cam, p)
+    print("oracle sky", fig)
+    assert fig["t_range"][0] < 0.4 and fig["t_range"][1] > 0.8       # below and above the horizon
+
+
+@pytest.mark.parametrize("gamma2", [False, True], ids=["linear", "gamma2"])
+def test_oracle_pack(oracle, gamma2):
+    sc, cam, p = K.pack_scene(gamma2)
+    rgb, amb, hit = K.pack_expectation(sc, cam, p)
+    assert not amb.any()
+    px, total, _ = render(oracle, sc, cam, p, want_sum=True)
+    assert np.array_equal(total.reshape(-1, 3), rgb), "the linear frame is the material's colour, bit for bit"
+    fig = K.check_pack(px, total, gamma2)
+    print("oracle pack", "gamma2" if gamma2 else "linear", fig)
+    assert fig["ties"] == 0 and fig["bytes_seen"] == 256 and fig["clamped"] > 20 and fig["zeros"] > 1000

@@ -506,3 +506,454 @@ def specular_frame(sc, cam, p, mutate=None):
         tir[glass] = total
         specular |= glass
     return dict(allowed=allowed, skip=skip, R=R, tir=tir, specular=specular, primary=h0, secondary=debug)
+
+
+def pixel_grid(p):
+    xx, yy = np.meshgrid(np.arange(p.width), T.owned_rows(p))
+    return xx.reshape(-1), yy.reshape(-1)
+
+
+# ====================================================================================================================== (g) the integrating sphere
+# (r, R, albedo, E, max_depth): the first geometry at four depths, a second one at depth 12
+INTEGRATING = [(1.0, 2.0, 0.8, 3.0, 2), (1.0, 2.0, 0.8, 3.0, 3), (1.0, 2.0, 0.8, 3.0, 8), (1.0, 2.0, 0.8, 3.0, 30), (1.0, 4.0, 0.6, 5.0, 12)]
+INTEGRATING_IDS = ["R2_D2", "R2_D3", "R2_D8", "R2_D30", "R4_D12"]
+INTEGRATING_SIZE = (48, 32, 256)
+EMITTER, WALL, SHELL = 0, 1, 2
+
+
+def integrating_scene(r, R, albedo, E):
+    """A FLAT sphere (r, radiance E) at the centre of a Lambert sphere (R, albedo a), and a second Lambert sphere of the same albedo
+    2^-10 R outside it.  The outer shell is for float32, not for the law: a scattered ray that leaves the wall at a grazing angle meets the
+    wall again at a t of the order of t_min and can lose that root to rounding (tests/test_gpu_env_sampling.py counts 3 such rays in
+    10 000); without the shell it would escape into the black background, with it it scatters on from a point 2^-10 R further out, where
+    F differs by 0.2 %.  At R = 2 the shell changed no bit of the oracle's frame; it stays so that the law holds for the next scene too."""
+    sph = np.array([[0.0, 0.0, 0.0, r], [0.0, 0.0, 0.0, R], [0.0, 0.0, 0.0, R * (1.0 + 2.0 ** -10)]], np.float32)
+    sm = np.concatenate([material(MAT_FLAT, (E, E, E)), material(MAT_LAMBERT, (albedo,) * 3), material(MAT_LAMBERT, (albedo,) * 3)])
+    return dict(spheres=sph, smats=sm, faces=None, verts=None, fmats=None)
+
+
+def integrating_camera(r, R, max_depth, size=INTEGRATING_SIZE, seed=7, flags=FLAG_BLACK, inward=False):
+    """Between the emitter and the wall, looking outward (every sample meets the wall first); inward: at the emitter, for the pixels on it."""
+    w, h, spp = size
+    eye = np.array([0.3, 0.2, 0.5])
+    eye = eye / np.linalg.norm(eye) * 0.5 * (r + R)
+    return (look_at(w, h, eye, (0.0, 0.0, 0.0) if inward else 2.0 * eye, 40.0),
+            Params(w, h, spp=spp, max_depth=max_depth, seed=seed, flags=flags))
+
+
+def all_meet_the_wall(kind, index):
+    return bool(((np.asarray(kind) == T.SPHERE) & (np.asarray(index) == WALL)).all())
+
+
+def check_integrating(law, mean, n_pixel, casts_per_sample=None, max_depth=None, each=True, sigmas=6.0):
+    """Values (linear means over n_pixel samples each, any shape) against integrating_sphere's law: the mean of all within 6 sigma /
+    sqrt(all samples), each (a frame's pixels) within 6 sigma / sqrt(n_pixel); casts per sample within 6 ((D - 1) / 2) / sqrt(all samples)
+    of the closed form — a path casts between 1 and D rays, and half that range bounds the standard deviation of any variable."""
+    mean = np.asarray(mean, np.float64).reshape(-1)
+    n = mean.size * n_pixel
+    z = (mean.mean() - law["mean"]) / (law["sigma"] / np.sqrt(n))
+    worst = float((np.abs(mean - law["mean"]) / (law["sigma"] / np.sqrt(n_pixel))).max())
+    fig = dict(samples=int(n), mean=float(mean.mean()), expected=float(law["mean"]), z=float(z), worst_pixel=worst)
+    assert abs(z) <= sigmas, "the mean %.6f is %.1f sigma from %.6f" % (mean.mean(), z, law["mean"])
+    assert not each or worst <= sigmas, "a pixel is %.1f sigma from the closed form" % worst
+    if casts_per_sample is not None:
+        bound = sigmas * 0.5 * (max_depth - 1.0) / np.sqrt(n)
+        fig.update(casts=float(casts_per_sample), casts_expected=law["casts"])
+        assert abs(casts_per_sample - law["casts"]) <= bound, "%.5f casts per sample where %.5f +- %.5f are expected" % (
+            casts_per_sample, law["casts"], bound)
+    return fig
+
+
+def integrating_rays(r, R, n, seed=21):
+    """n rays that start between the emitter and the wall and move away from the centre (o.d >= 0.1 |o|): none can meet the emitter."""
+    rng = np.random.default_rng(seed)
+    radial = unit(rng, n)
+    o = radial * rng.uniform(r + 0.1 * (R - r), R - 0.1 * (R - r), (n, 1))
+    d = radial + 0.9 * unit(rng, n)
+    return o.astype(np.float32), _f32_unit(d)
+
+
+def light_sample_range(r, R, albedo, E, max_depth):
+    """The largest value of a sample with a shadow ray to the emitter at every wall hit: sum over the wall hits j = 1 .. D - 1 of a^j E k,
+    k = c c_l A / (pi d^2 p_l) with both cosines at most 1, A = 4 pi r^2, p_l = 1 (one light) and d >= R - r: k <= 4 r^2 / (R - r)^2."""
+    j = np.arange(1, max_depth, dtype=np.float64)
+    return E * 4.0 * r * r / (R - r) ** 2 * (albedo ** j).sum()
+
+
+def check_range_mean(mean, expected, low, high, n, sigmas=6.0):
+    """The mean of n independent samples that lie in [low, high] against its expectation: a variable confined to an interval has a
+    standard deviation of at most half the interval's length."""
+    bound = sigmas * 0.5 * (high - low) / np.sqrt(n)
+    z = (mean - expected) / (0.5 * (high - low) / np.sqrt(n))
+    assert abs(mean - expected) <= bound, "the mean %.6f is off %.6f by more than %.6f" % (mean, expected, bound)
+    return dict(mean=float(mean), expected=float(expected), bound=float(bound), z_of_half_ranges=float(z))
+
+
+# ====================================================================================================================== (h) metal fuzz
+# rgb and c have few mantissa bits: the sum of 1024 equal samples is then exact in float32 (k rgb c needs 7 + 10 bits), and a pixel without
+# absorption equals rgb c; with arbitrary values the running sum alone would round up to spp / 2 times
+FUZZ = dict(rgb=(0.8125, 0.5625, 0.3125), c=2.5, size=(48, 32, 1024), fs=(1.0, 0.5, 0.2))
+
+
+def fuzz_scene(ground, f, make_triangle=None, merge=None):
+    """A METAL ground (two triangles in y = 0 whose stored normal points down, away from the camera; or a sphere of r = 1000 below y = 0)
+    inside one FLAT sphere of radiance c and radius 60: every scattered ray that is not absorbed meets the emitter."""
+    c = FUZZ["c"]
+    metal = material(MAT_METAL, FUZZ["rgb"], f)
+    if ground == "sphere":
+        sph = np.array([[0.0, 0.0, 0.0, 60.0], [0.0, -1000.0, 0.0, 1000.0]], np.float32)
+        return dict(spheres=sph, smats=np.concatenate([material(MAT_FLAT, (c, c, c)), metal]), faces=None, verts=None, fmats=None)
+    q = [(-60.0, 0.0, -60.0), (60.0, 0.0, -60.0), (60.0, 0.0, 60.0), (-60.0, 0.0, 60.0)]
+    faces, verts = merge([make_triangle(q[0], q[2], q[1]), make_triangle(q[0], q[3], q[2])])
+    assert (faces["normal"][:, 1] < 0).all(), "the stored normals must point away from the camera"
+    return dict(spheres=np.array([[0.0, 0.0, 0.0, 60.0]], np.float32), smats=material(MAT_FLAT, (c, c, c)), faces=faces, verts=verts,
+                fmats=np.repeat(metal, 2))
+
+
+def fuzz_camera(ground="triangles"):
+    """One above the ground, looking along it: the cosine of incidence falls from 0.98 to 0.16 down the frame.
+
+    t_min is 0.001 over the triangles and 0.5 over the sphere.  No surface of this scene is nearer than 1 to a ray's start (the camera's
+    height; the emitter is 53 from the part of the ground in view), so any t_min below 1 leaves the truth as it is.  In float32 a ray that
+    leaves the r = 1000 sphere meets it again at t = |dc| / (2 r cos), cos the cosine it leaves at and dc the error of c = |oc|^2 - r^2,
+    up to 13.5u r^2 = 0.8 (5u (|oc|^2 + r^2) of its roundings, error_bound_disc, and 2 r times the hit point's sqrt(3) u r): 4e-4 / cos.
+    With t_min = 0.001 that swallows the rays that leave within some degrees of the surface: measured on the oracle, 3.2 % of a pixel at
+    f = 0.2 and the whole frame 13 sigma low at f = 1.  That is the reference's t_min at the radius of its own ground sphere, not a fault
+    of the scatter law, which this scene is about; at 0.5 the frame is 0.7 sigma off."""
+    w, h, spp = FUZZ["size"]
+    return (Cam((0.0, 1.0, 0.0), (2.0, 0.0, 0.0), (0.0, 0.0, -6.0), (-1.0, 0.0, -0.2)),
+            Params(w, h, spp=spp, max_depth=2, seed=3, flags=FLAG_BLACK, t_min=0.5 if ground == "sphere" else 0.001))
+
+
+def fuzz_cosines(sc, origins, directions, spp):
+    """The cosine of incidence of every sample's primary ray on the ground, (spp, pixels); asserts that every ray meets the ground."""
+    rec = T.nearest_hit(origins, directions, 0.001, np.inf, sc["spheres"], sc["faces"], sc["verts"], chunk=1 << 16)
+    ground = (rec["kind"] == T.FACE) if sc["faces"] is not None else ((rec["kind"] == T.SPHERE) & (rec["index"] == 1))
+    assert ground.all(), "a primary ray misses the ground"
+    return (-(rec["normal"] * np.asarray(directions, np.float64)).sum(axis=1)).reshape(spp, -1)
+
+
+def check_fuzz(mean, cos, f, absorption=T.fuzz_absorption, sigmas=6.0):
+    """The linear frame (pixels, 3) against rgb c (1 - mean P(absorbed)) per pixel: within 6 sigma, sigma^2 = (rgb c)^2 q (1 - q) / spp with
+    q the pixel's mean survival (the variance of a mean of Bernoulli draws of differing q_i is at most that); a pixel no sample of which
+    can be absorbed equals rgb c to 4u relative.  exact counts the pixels whose every sample has cos > f (1 + 1e-4)."""
+    mean = np.asarray(mean, np.float64).reshape(-1, 3)
+    spp = cos.shape[0]
+    q = 1.0 - absorption(cos, f).mean(axis=0)
+    full = np.array(FUZZ["rgb"], np.float64) * FUZZ["c"]
+    exact = (cos > f * (1.0 + 1e-4)).all(axis=0)
+    sure = q == 1.0
+    assert (sure | ~exact).all()
+    stat = ~sure
+    fig = dict(statistical=int(stat.sum()), exact=int(exact.sum()), max_z=0.0, frame_z=0.0)
+    if sure.any():
+        rel = np.abs(mean[sure] / full[None] - 1.0).max()
+        assert rel <= 4.0 * T.U, "a pixel without absorption is %.3g off rgb c" % rel
+    if stat.any():
+        sigma = np.sqrt(q[stat] * (1.0 - q[stat]) / spp)
+        z = (mean[stat] / full[None] - q[stat][:, None]) / sigma[:, None]
+        fig["max_z"] = float(np.abs(z).max())
+        fig["frame_z"] = float((mean[stat, 0] / full[0] - q[stat]).sum() / np.sqrt((sigma ** 2).sum()))
+        assert fig["max_z"] <= sigmas, "a pixel is %.1f sigma from the absorption law" % fig["max_z"]
+    return fig
+
+
+def absorption_in_the_ball(cos, f):
+    """Mutant: u uniform IN the unit ball; its component along n has the density 3 (1 - s^2) / 4, so P = 1/2 - 3x/4 + x^3/4, x = cos / f."""
+    x = np.minimum(np.asarray(cos, np.float64) / f, 1.0)
+    return 0.5 - 0.75 * x + 0.25 * x ** 3
+
+
+def absorption_unscaled(cos, f):
+    """Mutant: the fuzz vector not scaled by f."""
+    return T.fuzz_absorption(cos, 1.0)
+
+
+# ====================================================================================================================== (i) a glass sphere
+GLASS_SPHERE_DEPTH = 6
+GLASS_MIN_WEIGHT = 1e-3
+
+
+def glass_sphere_scene():
+    """mirror_scene's sphere and shell with the sphere DIELECTRIC (ior 1.5), 1 spp, max_depth 6.  A unit sphere is a strong lens: an error
+    of a ray's direction moves its next hit on the sphere, the normal there turns with it, and a reflection doubles that, so a
+    direction's bound grows about sixfold per interface (interface_gains).  With ior 1.5 the leaf 'enter, reflect, reflect, leave' weighs
+    (1 - R)^2 R^2 >= 0.96^2 0.04^2 = 1.5e-3 in every pixel through the glass, above the 1e-3 from which a leaf counts, and meets its
+    target after four interfaces.  So the tree starts from the primary rays the source itself traced (float32, promoted exactly; the
+    primary ray has its own check, (b)) and not from a direction known to error_bound_dir only; the camera stands 1.8 from the centre
+    (|oc| enters a sphere's error_bound_t, and it is the lever arm of the first hit); and t_min is 0.1: a ray that starts on the glass has
+    a root at 0 that is uncertain by its origin's error (0.001 after four interfaces, times 1 + tan of the incidence in the bound), while
+    the chords through the sphere are longer than 1.49 and the targets more than 2 away."""
+    sc, _, _ = mirror_scene()
+    sc["smats"] = sc["smats"].copy()
+    sc["smats"]["kind"][0], sc["smats"]["param"][0] = MAT_DIELECTRIC, 1.5
+    cam = look_at(48, 48, (1.0, 0.6, 1.37), (0.0, 0.0, 0.0), 70.0)
+    return sc, cam, Params(48, 48, max_depth=GLASS_SPHERE_DEPTH, seed=6, flags=FLAG_BLACK, t_min=0.1)
+
+
+def pinhole_rays_f32(cam, p):
+    """The float32 primary rays of a spp-1 pinhole frame as DESIGN.md 4.1 forms them, every operation rounded to float32: u = x / (W - 1),
+    v = (H - 1 - y) / (H - 1), dir = ((llc + u hor) + v ver) - org, d = dir * (1 / sqrt((x x + y y) + z z)).  For a source that does not
+    export its rays; held against camera_ray by check_camera_rays where it is used."""
+    f = np.float32
+    xx, yy = pixel_grid(p)
+    u = (xx.astype(f) / (f(p.width) - f(1.0)))[:, None]
+    v = ((p.height - 1 - yy).astype(f) / (f(p.height) - f(1.0)))[:, None]
+    org, hor, ver, llc = (np.array(getattr(cam, name), f)[None] for name in ("origin", "horizontal", "vertical", "lower_left_corner"))
+    d = ((llc + u * hor) + v * ver) - org
+    inv = f(1.0) / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    d = d * inv[:, None]
+    assert d.dtype == f
+    return np.broadcast_to(org, d.shape).copy(), d
+
+
+def sphere_interface(o, d, c, r, inside, ri):
+    """A ray's meeting with a sphere it is known to meet, in float64: the point (the far root from inside, the near one from outside),
+    and the reflected and the refracted unit direction there (the refracted one NaN beyond the critical angle)."""
+    oc = c - o
+    a, h = (d * d).sum(axis=1), (oc * d).sum(axis=1)
+    s = np.sqrt(np.maximum(h * h - a * ((oc * oc).sum(axis=1) - r * r), 0.0))
+    t = np.where(inside, h + s, h - s) / a
+    P = o + t[:, None] * d
+    n = (P - c) / r[:, None] * np.where(inside, -1.0, 1.0)[:, None]
+    du = d / np.sqrt(a)[:, None]
+    return P, T.reflect(du, n), T.refract(du, n, ri)[0]
+
+
+def interface_gains(o, d, c, r, inside, ri, step=2.0 ** -20):
+    """How far the hit point and the two outgoing directions of sphere_interface move per unit of a small displacement of the ray's origin
+    (across the ray: along it nothing moves) and per radian of its direction: central differences of the float64 interface along two
+    axes across the ray, combined as a root of the sum of squares, which is at least the gain along any axis between them.  A ray
+    uncertain by (origin_err, dir_err) leaves the interface uncertain by gain_o origin_err + gain_d dir_err, to first order: the point's
+    displacement along the ray and across it, the normal's turn with the point and the direction's own error are one linear map, and
+    adding their separate bounds (as the single bounce of specular_frame may) would triple the growth per interface."""
+    du = d / np.linalg.norm(d, axis=1, keepdims=True)
+    e1 = np.cross(du, np.where((np.abs(du[:, :1]) < 0.6), [[1.0, 0.0, 0.0]], [[0.0, 1.0, 0.0]]))
+    e1 /= np.linalg.norm(e1, axis=1, keepdims=True)
+    e2 = np.cross(du, e1)
+    sq = {name: 0.0 for name in ("point_o", "point_d", "reflect_o", "reflect_d", "refract_o", "refract_d")}
+    for e in (e1, e2):
+        for what, plus, minus in (("o", sphere_interface(o + step * e, du, c, r, inside, ri), sphere_interface(o - step * e, du, c, r, inside, ri)),
+                                  ("d", sphere_interface(o, du + step * e, c, r, inside, ri), sphere_interface(o, du - step * e, c, r, inside, ri))):
+            for name, x, y in zip(("point_", "reflect_", "refract_"), plus, minus):
+                sq[name + what] = sq[name + what] + (((x - y) / (2.0 * step)) ** 2).sum(axis=1)
+    return {name: np.sqrt(v) for name, v in sq.items()}
+
+
+def glass_tree(sc, p, origins, directions, mutate=None):
+    """The float64 path tree behind every primary ray (origins, directions: one per pixel, float32 promoted exactly) of a spp-1 frame of
+    FLAT targets around DIELECTRIC spheres.  At an interface a path goes on
+    reflected with weight R (Schlick) or refracted with 1 - R (reflected only beyond the critical angle), ri = 1 / ior where the ray meets
+    the outward normal from outside and ior from inside, where the normal is turned to face it.  A branch ends on a target (its colour), in
+    the background or at the depth cut-off (black).  A leaf's slot is its string of decisions (0 reflected, 1 refracted), padded with
+    zeros to max_depth - 1 bits: leaves are prefix-free, so slots are unique.  Per slot and pixel: colour, weight (0: no such leaf),
+    ambiguous (any hit along the branch, with the errors of origin and direction carried from interface to interface by interface_gains
+    plus each interface's own float32 bounds; or an interface within its error of the critical angle), reflected (the branch contains a
+    reflection).
+    mutate: 'ri_kept' (ri = 1 / ior on the way out too), 'normal_unflipped' (the outward normal inside as well)."""
+    o, d = np.asarray(origins, np.float64), np.asarray(directions, np.float64)
+    n = len(o)
+    bits = p.max_depth - 1
+    L = 1 << bits
+    out = dict(colour=np.full((L, n), BLACK, np.uint32), weight=np.zeros((L, n)), ambiguous=np.zeros((L, n), bool),
+               reflected=np.zeros((L, n), bool), glass=np.zeros(n, bool))
+    sph = np.asarray(sc["spheres"], np.float64)
+    kinds, params_, codes = sc["smats"]["kind"], sc["smats"]["param"].astype(np.float64), sc["sphere_codes"]
+    a = dict(pix=np.arange(n), code=np.zeros(n, np.int64), nb=np.zeros(n, np.int64), o=o, d=d, eo=np.zeros(n), ed=np.zeros(n), w=np.ones(n),
+             amb=np.zeros(n, bool), refl=np.zeros(n, bool))
+    for k in range(p.max_depth):
+        if not len(a["pix"]):
+            break
+        h = T.nearest_hit(a["o"], a["d"], p.t_min, np.inf, sc["spheres"], origin_err=a["eo"], dir_err=a["ed"])
+        amb = a["amb"] | h["ambiguous"]
+        si = np.where(h["kind"] == T.SPHERE, h["index"], 0).astype(np.int64)
+        issph = h["kind"] == T.SPHERE
+        glass = issph & (kinds[si] == MAT_DIELECTRIC)
+        if k == 0:
+            out["glass"][a["pix"]] = glass
+        last = k + 1 == p.max_depth
+        leaf = ~glass | last
+        slot = a["code"][leaf] << (bits - a["nb"][leaf])
+        px = a["pix"][leaf]
+        out["colour"][slot, px] = np.where(issph & (kinds[si] == MAT_FLAT), codes[si], BLACK)[leaf]
+        out["weight"][slot, px] = a["w"][leaf]
+        out["ambiguous"][slot, px] = amb[leaf]
+        out["reflected"][slot, px] = a["refl"][leaf]
+        g = glass & (not last)
+        if not g.any():
+            break
+        oo, dd, t, eo, ed = a["o"][g], a["d"][g], h["t"][g], a["eo"][g], a["ed"][g]
+        c, r, ior = sph[si[g], :3], sph[si[g], 3], params_[si[g]]
+        P = oo + t[:, None] * dd
+        nout = (P - c) / r[:, None]
+        front = (dd * nout).sum(axis=1) < 0
+        nrm = nout if mutate == "normal_unflipped" else h["normal"][g]
+        ri = 1.0 / ior if mutate == "ri_kept" else np.where(front, 1.0 / ior, ior)
+        du = dd / np.linalg.norm(dd, axis=1, keepdims=True)
+        cos_in = -(du * nrm).sum(axis=1)
+        sin_in = np.sqrt(np.maximum(1.0 - cos_in ** 2, 0.0))
+        fd, total = T.refract(du, nrm, ri)
+        total = total | np.isnan(fd).any(axis=1)
+        R = np.where(total, 1.0, np.clip(T.schlick(cos_in, ri), 0.0, 1.0))
+        cos_out = np.sqrt(np.maximum(1.0 - (ri * sin_in) ** 2, 1e-24))
+        # what this interface adds by its own float32 arithmetic: the hit's error_bound_t without a ray uncertainty, the normal's bound with it
+        oc = c - oo
+        oc2, a2 = (oc * oc).sum(axis=1), (dd * dd).sum(axis=1)
+        disc = (oc * dd).sum(axis=1) ** 2 - a2 * (oc2 - r * r)
+        t_own = T.error_bound_t_sphere(np.sqrt(oc2), oc2 + r * r, np.sqrt(np.maximum(disc, 0.0)), t, np.abs(oc2 - r * r), np.maximum(np.abs(a2 - 1.0), 8.0 * T.U))
+        M = np.maximum(np.abs(oo).max(axis=1), np.abs(c).max(axis=1) + r)
+        n_own = T.error_bound_normal_sphere(t_own, M, r)
+        # what it does to the uncertainty the ray arrives with: the gains of the float64 interface itself
+        G = interface_gains(oo, dd, c, r, ~front, np.where(front, 1.0 / ior, ior))
+        p_err = G["point_o"] * eo + G["point_d"] * ed + t_own + T.SQRT3 * T.U * M
+        n_err = n_own + (G["point_o"] * eo + G["point_d"] * ed) / r
+        r_err = G["reflect_o"] * eo + G["reflect_d"] * ed + T.reflect_error(0.0, n_own)
+        f_err = G["refract_o"] * eo + G["refract_d"] * ed + T.refract_error(0.0, n_own, ri, np.abs(cos_in), cos_out)
+        amb_g = amb[g] | (np.abs(ri * sin_in - 1.0) < 64.0 * T.U + 2.0 * ri * (ed + n_err))
+        keep = ~total
+        child = lambda sel, bit, direction, err, w, refl: dict(                      # noqa: E731
+            pix=a["pix"][g][sel], code=(a["code"][g][sel] << 1) | bit, nb=a["nb"][g][sel] + 1, o=P[sel], d=direction[sel], eo=p_err[sel], ed=err[sel],
+            w=w[sel], amb=amb_g[sel], refl=refl[sel])
+        every = np.ones(len(t), bool)
+        kids = [child(every, 0, T.reflect(du, nrm), r_err, a["w"][g] * R, every),
+                child(keep, 1, fd, np.where(np.isfinite(f_err), f_err, 1.0), a["w"][g] * (1.0 - R), a["refl"][g])]
+        a = {key: np.concatenate([kid[key] for kid in kids]) for key in kids[0]}
+        alive = a["w"] > 0.0
+        a = {key: v[alive] for key, v in a.items()}
+    return out
+
+
+def sample_glass_tree(tree, rng):
+    """A frame that follows a tree faithfully: per pixel one leaf, drawn by weight."""
+    cdf = np.cumsum(tree["weight"], axis=0)
+    pick = (rng.random(cdf.shape[1])[None] * cdf[-1][None] >= cdf).sum(axis=0)
+    return tree["colour"][np.minimum(pick, len(cdf) - 1), np.arange(cdf.shape[1])]
+
+
+def check_glass_tree(pixels, tree, cap=SPECULAR_CAP):
+    """(a) every pixel shows the colour of one of its leaves; a pixel is skipped when a leaf of weight > 1e-3 is ambiguous.  (b) the number
+    of pixels that show their all-refract leaf (enter, leave: slot 11 0..0) within 6 sigma of the sum of that leaf's weights, over the
+    pixels where no other leaf has its colour.  (c) counts: through the glass, showing a leaf with a reflection in it (no leaf without one
+    has that colour)."""
+    pixels = np.asarray(pixels, np.uint32).reshape(-1)
+    w, col = tree["weight"], tree["colour"]
+    L = len(w)
+    present = w > 0.0
+    skip = (tree["ambiguous"] & (w > GLASS_MIN_WEIGHT)).any(axis=0)
+    heaviest = np.argmax(w, axis=0)
+    allowed = np.where(present, col, col[heaviest, np.arange(w.shape[1])][None])
+    check_frame(pixels, allowed, skip, cap)
+    glass = tree["glass"] & ~skip
+    rr = (L >> 1) | (L >> 2)                                              # refracted twice, then a leaf
+    others = present.copy()
+    others[rr] = False
+    unique = present[rr] & ~((col == col[rr][None]) & others).any(axis=0)
+    counted = glass & unique
+    shown = int((pixels[counted] == col[rr][counted]).sum())
+    z = check_count(shown, w[rr][counted])
+    match = present & (col == pixels[None])
+    reflected = glass & (match & tree["reflected"]).any(axis=0) & ~(match & ~tree["reflected"]).any(axis=0)
+    return dict(compared=int((~skip).sum()), skipped=int(skip.sum()), through_glass=int(glass.sum()), counted=int(counted.sum()),
+                all_refract=shown, expected=float(w[rr][counted].sum()), z=z, reflected=int(reflected.sum()))
+
+
+# ====================================================================================================================== (j) sky and pack
+SKY_SIZE = (64, 36)
+
+
+def sky_scene():
+    """One sphere behind the camera: every primary ray escapes."""
+    sc = dict(spheres=np.array([[0.0, 0.0, 50.0, 1.0]], np.float32), smats=material(MAT_FLAT, (1.0, 1.0, 1.0)), faces=None, verts=None, fmats=None)
+    w, h = SKY_SIZE
+    return sc, look_at(w, h, (0.5, 1.0, 2.0), (0.2, 1.4, -1.0), 70.0), Params(w, h)
+
+
+def check_sky(linear, cam, p, law=T.sky):
+    """The linear frame (pixels, 3) against the float64 sky of the float64 primary ray, within error_bound_sky of the primary direction's bound."""
+    xx, yy = pixel_grid(p)
+    _, d, ln = T.camera_ray(cam, p, xx, yy)
+    bound = T.error_bound_sky(T.error_bound_dir(cam, p.width, p.height, ln))
+    ratio = np.abs(np.asarray(linear, np.float64).reshape(-1, 3) - law(d)) / bound[:, None]
+    assert ratio.max() <= 1.0, "a sky channel is %.2f of its bound off" % ratio.max()
+    return dict(compared=int(ratio.size), max_ratio=float(ratio.max()), t_range=(float(0.5 * (d[:, 1].min() + 1)), float(0.5 * (d[:, 1].max() + 1))))
+
+
+def sky_of_y(d):
+    """Mutant: t = y."""
+    t = np.asarray(d, np.float64)[..., 1]
+    return (1.0 - t)[..., None] * np.ones(3) + t[..., None] * np.array([0.5, 0.7, 1.0])
+
+
+PACK_GRID = (20, 15, 3)                                                # 300 blocks of 3 x 3 pixels
+PACK_CAP = 0.01
+
+
+def pack_values():
+    """900 channel values, three per sphere: for every byte b a value that packs to it without gamma ((b + e) / 255) and one that does
+    with gamma 2 (((b + e) / 255)^2), |e| <= 0.4; exact zeros; values above 1 (just above, and far); the rest uniform in [0, 1.2].  A
+    value is redrawn until 255 x and 255 sqrt(x) are both 0.02 from a half-integer, so the reference leaves no channel out; shuffled, so
+    the three channels of a sphere are unrelated numbers."""
+    rng = np.random.default_rng(17)
+    gx, gy, _ = PACK_GRID
+
+    def clear(x):
+        x = float(np.float32(x))
+        return all(abs(v - np.floor(v) - 0.5) > 0.02 for v in (255.0 * x, 255.0 * np.sqrt(x)))
+
+    def draw(make):
+        while True:
+            x = make()
+            if clear(x):
+                return x
+
+    vals = [draw(lambda: max((b + rng.uniform(-0.4, 0.4)) / 255.0, 1e-4)) for b in range(256)]
+    vals += [draw(lambda: max((b + rng.uniform(-0.4, 0.4)) / 255.0, 1e-3) ** 2) for b in range(256)]
+    vals += [0.0] * 12 + [1.0, 1.0 + 2.0 ** -23, 1.001, 1.5, 2.0, 7.25, 100.0, 255.0, 1000.0]
+    vals += [draw(lambda: rng.uniform(0.0, 1.2)) for _ in range(3 * gx * gy - len(vals))]
+    vals = np.array(vals, np.float32)
+    while True:
+        rgb = rng.permutation(vals).reshape(-1, 3)
+        if ((rgb[:, 0] != rgb[:, 1]) & (rgb[:, 1] != rgb[:, 2]) & (rgb[:, 0] != rgb[:, 2])).all():
+            return rgb
+
+
+def pack_scene(gamma2):
+    """A grid of FLAT spheres on the image plane, one per 3 x 3 pixel block, radius 1.2 pixels, centred on the block's middle pixel."""
+    gx, gy, b = PACK_GRID
+    w, h = gx * b, gy * b
+    cam = Cam((0.0, 0.0, 0.0), (float(w - 1), 0.0, 0.0), (0.0, float(h - 1), 0.0), (-0.5 * (w - 1), -0.5 * (h - 1), -64.0))      # one unit per pixel
+    rgb = pack_values()
+    ix, iy = np.meshgrid(np.arange(gx), np.arange(gy))
+    cx = -0.5 * (w - 1) + b * ix.reshape(-1) + 1.0
+    cy = -0.5 * (h - 1) + (h - 1.0 - (b * iy.reshape(-1) + 1.0))
+    sph = np.stack([cx, cy, np.full(len(cx), -64.0), np.full(len(cx), 1.2)], axis=1).astype(np.float32)
+    sm = np.concatenate([material(MAT_FLAT, c) for c in rgb])
+    return (dict(spheres=sph, smats=sm, faces=None, verts=None, fmats=None), cam,
+            Params(w, h, flags=FLAG_BLACK | (1 if gamma2 else 0)))
+
+
+def pack_expectation(sc, cam, p):
+    """Per pixel the float32 linear colour the float64 nearest hit asks for (black where the ray escapes), and the pixels it cannot decide."""
+    xx, yy = pixel_grid(p)
+    o, d, ln = T.camera_ray(cam, p, xx, yy)
+    rec = T.nearest_hit(o, d, p.t_min, np.inf, sc["spheres"], dir_err=T.error_bound_dir(cam, p.width, p.height, ln))
+    hit = rec["kind"] == T.SPHERE
+    rgb = np.where(hit[:, None], sc["smats"]["rgb"][np.where(hit, rec["index"], 0)], np.float32(0.0)).astype(np.float32)
+    assert len(np.unique(rec["index"][hit])) == len(sc["spheres"]), "a sphere of the grid is not seen"
+    return rgb, rec["ambiguous"], hit
+
+
+def check_pack(pixels, linear, gamma2, pack=T.pack, cap=PACK_CAP):
+    """Packed pixels against T.pack of the same source's float32 linear frame, channel by channel; the channels within the tie margin are
+    left out and counted.  Returns the figures and the set of bytes seen."""
+    pixels = np.asarray(pixels, np.uint32).reshape(-1)
+    linear = np.asarray(linear, np.float32).reshape(-1, 3)
+    _, want, tie = pack(linear, gamma2)
+    assert tie.mean() <= cap, "%d of %d channels at a tie" % (int(tie.sum()), tie.size)
+    got = np.stack([(pixels >> 24) & 0xFF, (pixels >> 16) & 0xFF, (pixels >> 8) & 0xFF], axis=1)
+    assert ((pixels & 0xFF) == 0xFF).all(), "the low byte is 0xFF"
+    bad = ~tie & (got != want)
+    assert not bad.any(), "%d channels pack to another byte, first %s" % (int(bad.sum()), [
+        (float(linear[i, c]), int(got[i, c]), int(want[i, c])) for i, c in zip(*np.nonzero(bad))][:3])
+    return dict(compared=int((~tie).sum()), ties=int(tie.sum()), bytes_seen=len(np.unique(want[~tie])), clamped=int((linear > 1.0).sum()),
+                zeros=int((linear == 0.0).sum()))

@@ -454,3 +454,62 @@ def refract_error(dir_err, normal_err, ri, cos_in, cos_out):
     (cos, the tangential part times ri, sqrt|1 - |tang|^2|, two fmas, normalise) rounds about 12 times on values of at most 1; the
     square root amplifies the error of |tang|^2 (4u) by 1 / (2 cos(out)^2) in angle: 12u + 4u / cos(out)^2."""
     return ri * cos_in / cos_out * (dir_err + normal_err) + normal_err + 12.0 * U + 4.0 * U / (cos_out * cos_out)
+
+
+# ====================================================================================================================== closed forms
+def integrating_sphere(r, R, albedo, E, max_depth):
+    """A FLAT sphere of radius r and radiance E at the centre of a Lambert sphere of radius R and albedo a, seen from between the two by a
+    ray that meets the wall first.  At every wall point the emitter fills the same cosine-weighted share of the hemisphere, F = (r / R)^2
+    (form_factor_sphere with D = R and theta = 0), and everything else of it is wall.  A path therefore meets the emitter after j wall
+    hits with probability (1 - F)^(j - 1) F and then returns a^j E; max_depth = D casts at most D rays, so j runs from 1 to D - 1 (the
+    first cast meets the wall, the j-th scattered ray is cast j + 1) and a path still on the wall after D casts returns 0.  Ray j + 1 is
+    cast iff the first j - 1 scattered rays met the wall.  Exact, so the standard deviation of a sample is exact too."""
+    F = (float(r) / float(R)) ** 2
+    j = np.arange(1, int(max_depth), dtype=np.float64)
+    alive = (1.0 - F) ** (j - 1.0)
+    mean = E * F * (albedo ** j * alive).sum()
+    second = E * E * F * (albedo ** (2.0 * j) * alive).sum()
+    return dict(F=F, mean=mean, second=second, sigma=float(np.sqrt(second - mean * mean)), casts=1.0 + alive.sum())
+
+
+def fuzz_absorption(cos, f):
+    """Metal with fuzz f: the scattered direction is r + f u, r the unit mirror direction (r.n = cos, the cosine of incidence) and u
+    uniform on the unit sphere; the sample is absorbed iff (r + f u).n <= 0, i.e. u.n <= -cos / f.  u.n is uniform on [-1, 1]
+    (Archimedes: the area of a sphere between two parallel planes depends on their distance only), so P = max(0, (1 - cos / f) / 2)."""
+    return np.maximum(0.0, 0.5 * (1.0 - np.asarray(cos, np.float64) / f))
+
+
+def sky(d):
+    """The two-colour sky along unit directions d: (1 - t) (1, 1, 1) + t (0.5, 0.7, 1.0), t = (d_y + 1) / 2."""
+    d = np.asarray(d, np.float64)
+    t = 0.5 * (d[..., 1] / np.linalg.norm(d, axis=-1) + 1.0)
+    return (1.0 - t)[..., None] * np.ones(3) + t[..., None] * np.array([0.5, 0.7, 1.0])
+
+
+def error_bound_sky(dir_err):
+    """|channel32 - channel64| of the sky along a float32 primary direction that is dir_err (an angle, error_bound_dir: the normalisation
+    is counted there) off the float64 one.
+
+    * d_y moves by at most dir_err.  The sky normalises once more, y / sqrt(d.d): the dot product rounds 5 times on values of at most 1
+      (2.5u on the length), the square root and the quotient once each: 4.5u on a value of at most 1.
+    * t = (y + 1) / 2, rounded once: dt <= (dir_err + 4.5u) / 2 + u.
+    * a channel 1 - t (1 - c), c >= 0.5, evaluated as (1 - t) + t c: it moves by (1 - c) dt <= dt / 2; 1 - t, the product t c and the sum
+      round once each on values of at most 1 (3u); the float32 constant 0.7 is within 0.7u of 0.7 (u more, generously).
+
+    bound = dir_err / 4 + 1.625u + 4u <= dir_err / 4 + 6u
+    """
+    return 0.25 * np.asarray(dir_err, np.float64) + 6.0 * U
+
+
+def pack(rgb, gamma2):
+    """RGBA8 of linear float32 colours (n, 3), promoted exactly: byte = round(255 clip(g(x), 0, 1)), g the square root (gamma 2) or the
+    identity; r << 24 | g << 16 | b << 8 | 0xFF.  Returns (words, bytes (n, 3), tie): tie marks the channels whose 255 g(x) lies within
+    255 * 4u * max(1, g(x)) of a half-integer — the float32 evaluation rounds g(x) and the product by 255 once each (2u relative) and is
+    given twice that."""
+    x = np.asarray(rgb, np.float32).astype(np.float64).reshape(-1, 3)
+    g = np.sqrt(np.maximum(x, 0.0)) if gamma2 else x
+    v = 255.0 * np.clip(g, 0.0, 1.0)
+    b = np.floor(v + 0.5).astype(np.uint32)
+    raw = 255.0 * g
+    tie = (np.abs(raw - np.floor(raw) - 0.5) <= 255.0 * 4.0 * U * np.maximum(1.0, g)) & (raw > 0.0) & (raw < 255.5)
+    return (b[:, 0] << 24) | (b[:, 1] << 16) | (b[:, 2] << 8) | np.uint32(0xFF), b, tie
