@@ -33,8 +33,8 @@ extern "C" {
  * accumulation, rt3_gather_rows; 3 = + rt3_abi_version itself, one stream convention (below),
  * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh*, with
  * rt3_render_path_adaptive* (one new struct of its own), with rt3_regroup*, with the environment map (rt3_set_environment*), with its
- * importance sampling (RT3_FLAG_ENV_SAMPLING: one flag bit and two test-only functions) and with the emitters' (RT3_FLAG_LIGHT_SAMPLING: the same again):
- * functions were only added, no existing struct changed. */
+ * importance sampling (RT3_FLAG_ENV_SAMPLING: one flag bit and two test-only functions), with the emitters' (RT3_FLAG_LIGHT_SAMPLING: the same again)
+ * and with the display transform (rt3_display*: one new struct of its own): functions were only added, no existing struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
 
@@ -739,6 +739,64 @@ int      rt3_debug_light_sample(const rt3_gface* faces, uint32_t n_faces, const 
  * entries, capacity is what they can hold, *n_entries that count.  RT3_E_STATE without a scene, RT3_E_ARG for a NULL pointer or a short capacity
  * (*n_entries is set).  Synchronous; for the tests. */
 int      rt3_debug_light_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint64_t capacity, uint32_t* n_entries);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Display transform  (DESIGN.md 4.22, 5.2q): a linear float frame -> RGBA8 words: exposure, a tone curve, a transfer function
+ * ------------------------------------------------------------------------------------------------- */
+#define RT3_DISPLAY_CLAMP          0u   /* curve: none; values above 1 clip */
+#define RT3_DISPLAY_REINHARD       1u   /* curve: extended Reinhard on the luminance, `white` is mapped to 1 */
+#define RT3_DISPLAY_FILMIC         2u   /* curve: the rational filmic fit (2.51, 0.03, 2.43, 0.59, 0.14) per channel */
+#define RT3_DISPLAY_LINEAR         0u   /* transfer: none: the pack of a render without RT3_FLAG_GAMMA2 */
+#define RT3_DISPLAY_GAMMA2         1u   /* transfer: a square root: the pack of a render with RT3_FLAG_GAMMA2 */
+#define RT3_DISPLAY_SRGB           2u   /* transfer: the sRGB encoding, from a table of 4096 bytes */
+#define RT3_DISPLAY_AUTO_EXPOSURE  1u   /* flags: the gain follows the frame's trimmed log-average luminance */
+typedef struct rt3_display_params {      /* 32 bytes */
+    uint32_t curve;                      /* RT3_DISPLAY_CLAMP 0 | RT3_DISPLAY_REINHARD 1 | RT3_DISPLAY_FILMIC 2 */
+    uint32_t transfer;                   /* RT3_DISPLAY_LINEAR 0 | RT3_DISPLAY_GAMMA2 1 | RT3_DISPLAY_SRGB 2 */
+    uint32_t flags;                      /* RT3_DISPLAY_AUTO_EXPOSURE 1; any other bit: RT3_E_ARG */
+    uint32_t trim_low;                   /* auto: share of the counted pixels dropped from the dark end, in 1/1024; default 102 */
+    uint32_t trim_high;                  /* ... from the bright end; trim_low + trim_high <= 1023; default 51 */
+    float    exposure;                   /* linear gain, finite and > 0; default 1 */
+    float    key;                        /* auto: the value the trimmed log-average luminance is mapped to; finite and > 0; default 0.18 */
+    float    white;                      /* REINHARD: luminance mapped to 1; finite and >= 2^-10, or +inf (plain Reinhard); default 4 */
+} rt3_display_params;
+/* width x height pixels of (r, g, b, ignored) floats, as rt3_accum_resolve / rt3_denoise write them, to one word per pixel in the layout of
+ * rt3_render_path's frame, 0xFF | B << 8 | G << 16 | R << 24.  Geometry does not matter: a whole frame and a shard's compact rows are both accepted.
+ * trim_*, key and white are checked even where they are not used.  No transcendental function and no floating-point sum over pixels: every statistic
+ * is an integer, every per-pixel step is + - * /, sqrtf, fmaf, a comparison or a table lookup, each an IEEE f32 operation rounded on its own.
+ * The gain.  Without RT3_DISPLAY_AUTO_EXPOSURE, gain = exposure.  With it, per pixel y_c = c > 0 ? fminf(c, FLT_MAX) : 0 (NaN and negatives become 0),
+ * Y = fmaf(0.0722f, y_b, fmaf(0.7152f, y_g, 0.2126f * y_r)), k = (int32_t)(bits(Y) >> 19) - 1776.  k < 0 (Y < 2^-16): the pixel is dark; it is counted
+ * in `dark` and not in the histogram.  Otherwise hist[min(k, 511)] += 1: 512 bins, 16 per octave, 2^-16 up to 2^16; +inf lands in bin 511.  With
+ * n = sum(hist): lo = (n * trim_low) >> 10 and hi = (n * trim_high) >> 10 in uint64; the ranks [lo, n - hi) are kept, ranks assigned in bin order:
+ * kept_k = max(0, min(end_k, n - hi) - max(begin_k, lo)).  m = n - lo - hi, S = sum(kept_k * k), P = (S << 19) / m as a uint64 floor division,
+ * Lavg = float_from_bits((111u << 23) + (uint32_t)P + (1u << 18)) — the bin centre; the float's bit pattern serves as its piecewise-linear log2 —
+ * and gain = exposure * (key / Lavg).  n == 0 gives gain = exposure.
+ * Per pixel and channel.  x = g > 0 ? fminf(g, 65504.0f) : 0 with g = gain * c (NaN, negatives and 0 * inf become 0).  The curve: CLAMP y = x;
+ * REINHARD Yx = fmaf(0.0722f, x_b, fmaf(0.7152f, x_g, 0.2126f * x_r)), s = (1.0f + Yx / (white * white)) / (1.0f + Yx), y = x * s; FILMIC
+ * y = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f), nothing fused.  z = fminf(y, 1.0f).  The transfer: LINEAR byte = pack(z), the
+ * channel pack of rt3_render_path (round(z * 255), half away from zero); GAMMA2 byte = pack(sqrtf(z)); SRGB byte = table[(uint32_t)roundf(z * 4095.0f)],
+ * table[i] = the number of k in 1 .. 255 with (k - 0.5) / 255 at or below the sRGB encoding of i / 4095 (4096 bytes; monotone, every code, steps of 1).
+ * Anchor.  CLAMP, exposure 1, no flag: applied to rt3_accum_resolve's frame it returns, word for word, what rt3_render_path returned for that render —
+ * LINEAR for a render without RT3_FLAG_GAMMA2, GAMMA2 for one with it.
+ * No scene is needed.  The call never touches the accumulation of a progressive render and leaves rt3_get_stats as it was.  Streams as for queries;
+ * the host form is synchronous; the device form never waits for the device, with the flag neither: the gain stays in device memory between the
+ * kernels.  The device form allocates only on a context's first call with the flag (516 words of state).  RT3_E_ARG for a NULL pointer, width or
+ * height 0, width x height > 2^26, a parameter outside the ranges above (unknown curve, transfer or flag bits included), a device input that is not
+ * 16-byte aligned or a device output that is not 4-byte aligned, or an output that overlaps the input; a refused call writes nothing.  Out of scope:
+ * one exposure shared by the shards of a multi-device frame (gather first, or pass the gain as `exposure`), eye adaptation, local operators, dither. */
+int      rt3_display(rt3_ctx* ctx, uint32_t width, uint32_t height, const float* rgba, const rt3_display_params* p, uint32_t* out_pixels);
+int      rt3_display_device(rt3_ctx* ctx, uint32_t width, uint32_t height, const void* d_rgba, const rt3_display_params* p, void* d_out_pixels,
+                            void* stream);
+/* Tests only: the histogram, the dark count and the gain of the context's last call with RT3_DISPLAY_AUTO_EXPOSURE (any of them may be NULL).
+ * RT3_E_STATE if there was none.  Synchronous. */
+int      rt3_debug_display_state(rt3_ctx* ctx, uint32_t hist[512], uint32_t* dark, float* gain);
+/* Host only, no device and no context; for the tests: the law above in C.  *bin = 0 .. 511, 0xFFFFFFFF for a dark pixel; the gain of a histogram
+ * under p's exposure, key and trims (flags are not looked at); one pixel's word for a given gain; the table.  RT3_E_ARG for a NULL pointer or
+ * parameters rt3_display would refuse.  tests/display_ref.py restates them bit for bit. */
+int      rt3_debug_display_bin(const float rgb[3], uint32_t* bin);
+int      rt3_debug_display_gain(const uint32_t hist[512], const rt3_display_params* p, float* gain);
+int      rt3_debug_display_pixel(const float rgb[3], float gain, const rt3_display_params* p, uint32_t* word);
+int      rt3_debug_display_srgb_table(uint8_t out[4096]);
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side scene API  (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)

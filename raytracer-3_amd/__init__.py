@@ -52,6 +52,13 @@ FLAG_GAMMA2, FLAG_BLACK_BACKGROUND, FLAG_REFERENCE_PRIMARY, FLAG_VARIANCE = 1, 2
 FLAG_ENV_SAMPLING = 16             # importance sampling of the environment map, one shadow ray per Lambert scatter
 FLAG_LIGHT_SAMPLING = 32           # importance sampling of the emissive primitives, one shadow ray per Lambert scatter
 REGROUP_SPHERES, REGROUP_MESH = 1, 2      # rt3_regroup's `what`
+# the display transform (rt3_display): curve, transfer, flags of rt3_display_params
+DISPLAY_CLAMP, DISPLAY_REINHARD, DISPLAY_FILMIC = 0, 1, 2
+DISPLAY_LINEAR, DISPLAY_GAMMA2, DISPLAY_SRGB = 0, 1, 2
+DISPLAY_AUTO_EXPOSURE = 1
+DISPLAY_DARK = 0xFFFFFFFF          # rt3_debug_display_bin's word for a pixel below 2^-16
+_DISPLAY_CURVES = {"clamp": DISPLAY_CLAMP, "reinhard": DISPLAY_REINHARD, "filmic": DISPLAY_FILMIC}
+_DISPLAY_TRANSFERS = {"linear": DISPLAY_LINEAR, "gamma2": DISPLAY_GAMMA2, "srgb": DISPLAY_SRGB}
 
 
 class rt3_camera(C.Structure):
@@ -134,6 +141,21 @@ class RADIANCE_PARAMS(C.Structure):
                 ("sample_count", C.c_uint32), ("t_min", C.c_float)]
 
 
+class DISPLAY_PARAMS(C.Structure):
+    """rt3_display_params (32 bytes): curve, transfer, flags, the auto-exposure's trims in 1/1024, exposure, key, white."""
+    _fields_ = [("curve", C.c_uint32), ("transfer", C.c_uint32), ("flags", C.c_uint32), ("trim_low", C.c_uint32), ("trim_high", C.c_uint32),
+                ("exposure", C.c_float), ("key", C.c_float), ("white", C.c_float)]
+
+
+def display_params(curve="filmic", transfer="srgb", exposure=1.0, auto=False, key=0.18, white=4.0, trim_low=102, trim_high=51):
+    """DISPLAY_PARAMS from names ("clamp" | "reinhard" | "filmic", "linear" | "gamma2" | "srgb") or the DISPLAY_* constants."""
+    c = _DISPLAY_CURVES.get(curve, curve) if isinstance(curve, str) else curve
+    t = _DISPLAY_TRANSFERS.get(transfer, transfer) if isinstance(transfer, str) else transfer
+    if isinstance(c, str) or isinstance(t, str):
+        raise Fatal("display: curve is clamp | reinhard | filmic, transfer is linear | gamma2 | srgb")
+    return DISPLAY_PARAMS(int(c), int(t), DISPLAY_AUTO_EXPOSURE if auto else 0, int(trim_low), int(trim_high), float(exposure), float(key), float(white))
+
+
 class Fatal(RuntimeError):
     """Mirror of CppDebugger::Fatal: every backend error is fatal (Main.cpp:305-308)."""
 
@@ -164,6 +186,8 @@ EXPORTS = [
     "rt3_set_environment", "rt3_set_environment_device", "rt3_clear_environment", "rt3_environment_size", "rt3_debug_environment_lookup",
     "rt3_debug_environment_sample", "rt3_debug_environment_table",
     "rt3_debug_light_sample", "rt3_debug_light_table",
+    "rt3_display", "rt3_display_device", "rt3_debug_display_state", "rt3_debug_display_bin", "rt3_debug_display_gain", "rt3_debug_display_pixel",
+    "rt3_debug_display_srgb_table",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -244,6 +268,10 @@ def lib():
         "rt3_debug_environment_sample": (i32, [vp, u32, u32, u32, vp, vp, vp]), "rt3_debug_environment_table": (i32, [vp, vp, vp, u64, vp]),
         "rt3_debug_light_sample": (i32, [vp, u32, vp, u32, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]),
         "rt3_debug_light_table": (i32, [vp, vp, vp, u64, vp]),
+        "rt3_display": (i32, [vp, u32, u32, vp, vp, vp]), "rt3_display_device": (i32, [vp, u32, u32, vp, vp, vp, vp]),
+        "rt3_debug_display_state": (i32, [vp, vp, vp, vp]), "rt3_debug_display_bin": (i32, [vp, vp]),
+        "rt3_debug_display_gain": (i32, [vp, vp, vp]), "rt3_debug_display_pixel": (i32, [vp, f32, vp, vp]),
+        "rt3_debug_display_srgb_table": (i32, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -327,6 +355,51 @@ def light_sample(faces, verts, face_materials, center_radius, sphere_materials, 
               C.c_void_p(normal.ctypes.data + 12 * k), C.c_void_p(area.ctypes.data + 4 * k), C.c_void_p(pl.ctypes.data + 4 * k)) != 0:
             raise Fatal("rt3_debug_light_sample refused its arguments (a face index out of range?)")
     return (int(light[0]), point[0], normal[0], area[0], pl[0]) if np.ndim(base) == 0 else (light, point, normal, area, pl)
+
+
+def display_bin(rgb):
+    """rt3_debug_display_bin, the auto-exposure's histogram bin in C on the host: (3,) -> int, (K, 3) -> uint32 (K,); 0 .. 511, or
+    DISPLAY_DARK for a pixel whose luminance is below 2^-16."""
+    c = np.ascontiguousarray(np.asarray(rgb, np.float32).reshape(-1, 3))
+    out = np.zeros(len(c), np.uint32)
+    fn = lib().rt3_debug_display_bin
+    for k in range(len(c)):
+        if fn(C.c_void_p(c.ctypes.data + 12 * k), C.c_void_p(out.ctypes.data + 4 * k)) != 0:
+            raise Fatal("rt3_debug_display_bin refused its arguments")
+    return int(out[0]) if np.ndim(rgb) == 1 else out
+
+
+def display_gain(hist, exposure=1.0, key=0.18, trim_low=102, trim_high=51):
+    """rt3_debug_display_gain, the auto-exposure's gain of a histogram of 512 uint32 bins in C on the host -> float32."""
+    h = np.ascontiguousarray(hist, np.uint32)
+    if h.shape != (512,):
+        raise Fatal("display_gain: the histogram has 512 bins")
+    p = display_params(exposure=exposure, key=key, trim_low=trim_low, trim_high=trim_high)
+    g = C.c_float(0.0)
+    if lib().rt3_debug_display_gain(_p(h), C.byref(p), C.byref(g)) != 0:
+        raise Fatal("rt3_debug_display_gain refused its arguments (exposure and key finite and > 0, trim_low + trim_high <= 1023)")
+    return np.float32(g.value)
+
+
+def display_pixel(rgb, gain, curve="filmic", transfer="srgb", white=4.0):
+    """rt3_debug_display_pixel, one pixel through the gain, the curve and the transfer in C on the host: (3,) -> int, (K, 3) ->
+    uint32 (K,) words 0xFF | B << 8 | G << 16 | R << 24."""
+    c = np.ascontiguousarray(np.asarray(rgb, np.float32).reshape(-1, 3))
+    out = np.zeros(len(c), np.uint32)
+    p = display_params(curve, transfer, white=white)
+    fn = lib().rt3_debug_display_pixel
+    for k in range(len(c)):
+        if fn(C.c_void_p(c.ctypes.data + 12 * k), C.c_float(gain), C.byref(p), C.c_void_p(out.ctypes.data + 4 * k)) != 0:
+            raise Fatal("rt3_debug_display_pixel refused its arguments (white >= 2^-10)")
+    return int(out[0]) if np.ndim(rgb) == 1 else out
+
+
+def display_srgb_table():
+    """rt3_debug_display_srgb_table: the 4096 bytes the sRGB transfer looks up, uint8 (4096,)."""
+    out = np.zeros(4096, np.uint8)
+    if lib().rt3_debug_display_srgb_table(_p(out)) != 0:
+        raise Fatal("rt3_debug_display_srgb_table failed")
+    return out
 
 
 def cube_from_equirect(image, n):
@@ -1193,6 +1266,46 @@ class HipRenderer(Renderer):
         out = np.zeros((h, w, 4), np.float32)
         self._check(lib().rt3_denoise(self._ctx, w, h, _p(c), _p(a), C.byref(p), _p(out)))
         return out
+
+    # -- the display transform ---------------------------------------------------------------------------
+    def display(self, colour, curve="filmic", transfer="srgb", exposure=1.0, auto=False, key=0.18, white=4.0, trim_low=102, trim_high=51):
+        """A linear float frame to RGBA8 words (rt3_display): exposure — given, or with auto=True times key over the frame's trimmed log-average
+        luminance —, the tone curve ("clamp" | "reinhard" | "filmic") and the transfer function ("linear" | "gamma2" | "srgb").  numpy: float32
+        (H, W, 4) as accum_resolve or denoise return it -> uint32 (H, W), 0xFF | B << 8 | G << 16 | R << 24 as render_path packs.  torch: a contiguous
+        (H, W, 4) float32 tensor on the GPU -> a new (H, W) uint32 tensor (int32 bit patterns where torch has no uint32), computed on torch.cuda.current_stream() with no
+        host wait.  display(accum_resolve(p), "clamp", "linear" | "gamma2") is render_path's frame."""
+        p = display_params(curve, transfer, exposure, auto, key, white, trim_low, trim_high)
+        if type(colour).__module__.startswith("torch"):
+            import torch
+            if (not colour.is_cuda or colour.dtype != torch.float32 or colour.dim() != 3 or colour.shape[2] != 4
+                    or not colour.is_contiguous()):
+                raise Fatal("device colour must be a contiguous (H, W, 4) float32 tensor on the GPU")
+            h, w = colour.shape[:2]
+            out = torch.empty((h, w), dtype=getattr(torch, "uint32", torch.int32), device=colour.device)
+            stream = torch.cuda.current_stream(colour.device).cuda_stream
+            self._check(lib().rt3_display_device(self._ctx, w, h, C.c_void_p(colour.data_ptr()), C.byref(p), C.c_void_p(out.data_ptr()),
+                                                 C.c_void_p(stream)))
+            return out
+        c = np.ascontiguousarray(colour, np.float32)
+        if c.ndim != 3 or c.shape[2] != 4:
+            raise Fatal("display: colour must be float32 (H, W, 4)")
+        h, w = c.shape[:2]
+        out = np.zeros((h, w), np.uint32)
+        self._check(lib().rt3_display(self._ctx, w, h, _p(c), C.byref(p), _p(out)))
+        return out
+
+    def display_device(self, width, height, d_rgba_ptr, display_params_c, d_out_ptr, stream_ptr=None):
+        """Asynchronous display transform between device buffers (rt3_display_device): width * height float4 in, as many 4-byte words out."""
+        self._check(lib().rt3_display_device(self._ctx, width, height, C.c_void_p(d_rgba_ptr), C.byref(display_params_c), C.c_void_p(d_out_ptr),
+                                             C.c_void_p(stream_ptr or 0)))
+
+    def display_state(self):
+        """What the last display call with auto-exposure left on the device (rt3_debug_display_state; synchronous): (hist uint32 (512,), dark, gain
+        float32)."""
+        hist = np.zeros(512, np.uint32)
+        dark, gain = C.c_uint32(0), C.c_float(0.0)
+        self._check(lib().rt3_debug_display_state(self._ctx, _p(hist), C.byref(dark), C.byref(gain)))
+        return hist, int(dark.value), np.float32(gain.value)
 
     def denoise_temporal(self, colour, aov, camera_c, prev=None, iterations=5, normal_power=128, sigma_luminance=4.0, sigma_depth=1.0,
                          alpha=0.2, moments_alpha=0.2, depth_tolerance=2.0, normal_tolerance=0.9, motion=None):

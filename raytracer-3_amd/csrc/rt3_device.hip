@@ -17,6 +17,7 @@
 //                           ordered compaction of the pixels that stay active, the resolves by a pixel's own count
 //   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve (in place for 4.18)
 //   rt3_denoise.hpp         the launchers of the AOV-guided a-trous denoiser, its temporal form and the motion plane (kernels: rt3_denoise.hip)
+//   rt3_display.hpp         the launcher of the display transform (kernels: rt3_display.hip; the law: rt3_display_law.hpp)
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
 //   rt3_regroup.hpp         the group order of the multi-level filter again on the device (rt3_regroup*): the median split as stable sorts,
 //                           in LDS for parts of up to 4096 primitives
@@ -55,6 +56,8 @@
 #include "rt3_adaptive.hpp"
 #include "rt3_aov.hpp"
 #include "rt3_denoise.hpp"
+#include "rt3_display_law.hpp"
+#include "rt3_display.hpp"
 #include "rt3_scene_kernels.hpp"
 #include "rt3_regroup.hpp"
 #include "rt3_scene_build.hpp"
@@ -160,6 +163,9 @@ struct rt3_ctx {
     DevBuf<uint4> d_ahits;                                          // and the per-pixel running sums (three planes; not d_accum, which belongs to
     DevBuf<float4> d_aacc;                                          // the progressive render)
     DevBuf<float4> d_dn;                                            // denoiser scratch (rt3_denoise*): two (I, v) planes, the guide plane, the depth slopes
+    // the display transform's auto-exposure (rt3_display*): hist[512], dark, n and the gain's bits, allocated by the first call with the flag and
+    // zeroed at the start of each such call; display_auto: there has been one (rt3_debug_display_state)
+    DevBuf<uint32_t> d_display; bool display_auto = false;
     // The host forms' inputs and results on the device, each carved out at float4 offsets.  Shared by all of them: each one ends in
     // hipStreamSynchronize(ctx->stream), and no device form touches it.
     DevBuf<float4> stage;
@@ -2806,6 +2812,68 @@ int rt3_debug_light_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint
     RT3_HIP(hipMemcpyAsync(cdf_out, ctx->d_light_cdf.get(), n * 8u, hipMemcpyDeviceToHost, stream));
     if ((rc = leave(ctx, stream))) return rc;
     RT3_HIP(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// ---- The display transform
+static int display_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* rgba, const rt3_display_params* p, const void* out) {
+    if (!p) return fail(ctx, RT3_E_ARG, "p is NULL");
+    if (!rgba || !out) return fail(ctx, RT3_E_ARG, "rgba / out_pixels is NULL");
+    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must have 1 .. 2^26 pixels");
+    if (const char* why = rt3disp::refusal(*p)) return fail(ctx, RT3_E_ARG, why);
+    const size_t npix = (size_t)w * h;
+    if (ranges_overlap(out, npix * sizeof(uint32_t), rgba, npix * sizeof(float4))) return fail(ctx, RT3_E_ARG, "out_pixels overlaps rgba");
+    return 0;
+}
+
+// Without the flag one launch, k_display_map with the uniform gain; with it the state zeroed on the stream, k_display_histogram, k_display_gain and
+// k_display_map reading the gain where k_display_gain left it.  Nothing here waits for the device, and nothing is timed: rt3_get_stats stays as it was.
+int rt3_display_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_rgba, const rt3_display_params* p, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = display_checks(ctx, w, h, d_rgba, p, d_out);
+    if (rc) return rc;
+    if ((uintptr_t)d_rgba % 16u != 0 || (uintptr_t)d_out % 4u != 0) return fail(ctx, RT3_E_ARG, "d_rgba must be 16-byte and d_out_pixels 4-byte aligned");
+    const bool auto_exposure = (p->flags & RT3_DISPLAY_AUTO_EXPOSURE) != 0;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    if (auto_exposure && (rc = ctx->d_display.ensure(ctx, rt3disp::kStateWords))) return rc;      // (the state is the context's: the first such call allocates it)
+    const DisplayLaunch L{ w * h, p->curve, p->transfer, auto_exposure, p->trim_low, p->trim_high, p->exposure, p->key, p->white, d_rgba, d_out,
+                           auto_exposure ? ctx->d_display.get() : nullptr };
+    RT3_HIP(display_launch(L, stream));
+    if (auto_exposure) ctx->display_auto = true;
+    return leave(ctx, stream);
+}
+
+// The host form: the frame and the words on the device in ctx->stage (one float4 per pixel, then one per four words).
+int rt3_display(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* rgba, const rt3_display_params* p, uint32_t* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = display_checks(ctx, w, h, rgba, p, out);
+    if (rc) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)w * h;
+    if ((rc = ctx->stage.ensure(ctx, npix + (npix + 3) / 4))) return rc;
+    float4* const dc = ctx->stage;
+    uint32_t* const dout = (uint32_t*)(dc + npix);
+    RT3_HIP(hipMemcpyAsync(dc, rgba, npix * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = rt3_display_device(ctx, w, h, dc, p, dout, ctx->stream))) return rc;
+    RT3_HIP(hipMemcpyAsync(out, dout, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int rt3_debug_display_state(rt3_ctx* ctx, uint32_t hist[512], uint32_t* dark, float* gain) {
+    if (!ctx) return RT3_E_ARG;
+    if (!ctx->display_auto) return fail(ctx, RT3_E_STATE, "no call with RT3_DISPLAY_AUTO_EXPOSURE on this context");
+    uint32_t state[rt3disp::kStateWords];
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, nullptr, &stream))) return rc;            // behind the call that wrote the state, whatever stream it ran on
+    RT3_HIP(hipMemcpyAsync(state, ctx->d_display.get(), sizeof state, hipMemcpyDeviceToHost, stream));
+    if ((rc = leave(ctx, stream))) return rc;
+    RT3_HIP(hipStreamSynchronize(stream));
+    if (hist) std::memcpy(hist, state, rt3disp::kBins * sizeof(uint32_t));
+    if (dark) *dark = state[rt3disp::kBins];
+    if (gain) *gain = rt3disp::float_of(state[rt3disp::kBins + 2]);
     return 0;
 }
 

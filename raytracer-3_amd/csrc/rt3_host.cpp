@@ -8,6 +8,7 @@
 #include "rt3_sphere_plan.hpp"
 #include "rt3_env_sample.hpp"
 #include "rt3_light_sample.hpp"
+#include "rt3_display_law.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -570,6 +571,29 @@ extern "C" int rt3_debug_light_sample(const rt3_gface* faces, uint32_t n_faces, 
     else { const float* s = T.cr.data() + 4 * (size_t)(li - n_faces); rt3light::point_on_sphere(s[0], s[1], s[2], s[3], ua, ub, Y); }
     *light = li; point[0] = Y.x; point[1] = Y.y; point[2] = Y.z; light_normal[0] = Y.nx; light_normal[1] = Y.ny; light_normal[2] = Y.nz;
     *area = Y.area; *pl = (float)T.q[li] / (float)T.total;
+    return 0;
+}
+
+// The display transform's law (rt3.h "Display transform") on the host: the functions of rt3_display_law.hpp the kernels call, one pixel or
+// one histogram per call.  A refused call writes nothing.
+extern "C" int rt3_debug_display_bin(const float rgb[3], uint32_t* bin) {
+    if (!rgb || !bin) return RT3_E_ARG;
+    *bin = rt3disp::bin(rgb[0], rgb[1], rgb[2]);
+    return 0;
+}
+extern "C" int rt3_debug_display_gain(const uint32_t hist[512], const rt3_display_params* p, float* gain) {
+    if (!hist || !p || !gain || rt3disp::refusal(*p)) return RT3_E_ARG;
+    *gain = rt3disp::gain_of(hist, p->trim_low, p->trim_high, p->exposure, p->key);
+    return 0;
+}
+extern "C" int rt3_debug_display_pixel(const float rgb[3], float gain, const rt3_display_params* p, uint32_t* word) {
+    if (!rgb || !p || !word || rt3disp::refusal(*p)) return RT3_E_ARG;
+    *word = rt3disp::pixel(rgb[0], rgb[1], rgb[2], gain, p->curve, p->transfer, p->white, rt3disp::kSrgbTable);
+    return 0;
+}
+extern "C" int rt3_debug_display_srgb_table(uint8_t out[4096]) {
+    if (!out) return RT3_E_ARG;
+    std::memcpy(out, rt3disp::kSrgbTable, sizeof rt3disp::kSrgbTable);
     return 0;
 }
 

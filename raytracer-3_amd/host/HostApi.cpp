@@ -433,6 +433,11 @@ std::vector<float> HipRenderer::denoise_temporal(Camera& camera, const rt3_tempo
     return out;
 }
 
+void HipRenderer::display(Camera& camera, const std::vector<float>& rgba, const rt3_display_params& params) const {
+    if (rgba.size() != 4 * (size_t)camera.w() * camera.h()) throw Fatal("display: the frame's size differs from the camera's");
+    if (rt3_display(ctx[0], camera.w(), camera.h(), rgba.data(), &params, camera.get_frame().d()) != 0) throw Fatal(rt3_last_error(ctx[0]));
+}
+
 std::vector<float> HipRenderer::motion(Camera& camera, const std::vector<float>& prev_center_radius,
                                        const std::vector<float>& prev_vertices_xyzw) const {
     const std::vector<rt3_aov> guides = aov(camera);

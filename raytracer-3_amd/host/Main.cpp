@@ -8,7 +8,8 @@
 // Added (defaults reproduce the reference render): --scene, --spp, --depth, --seed, --gpus; Mode X only: --aov, --hdr, --denoise (PFM files),
 // --frames, --orbit and --slide (a sequence, denoised temporally), --adaptive and --counts (--spp as a budget), --rays and --radiance
 // (path-traced radiance along rays read from a file), --env (an environment map from a PFM of six stacked cube faces),
-// --env-sampling (importance sampling of that map with shadow rays), --light-sampling (the same for the emissive primitives).
+// --env-sampling (importance sampling of that map with shadow rays), --light-sampling (the same for the emissive primitives),
+// --display (the image written is the linear frame through exposure, a tone curve and a transfer function).
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -52,6 +53,8 @@ struct Options {
     std::string env_path;                                          // Mode X: the environment map, a colour PFM of N x 6N (the six faces stacked)
     bool env_sampling = false;                                     // with --env: RT3_FLAG_ENV_SAMPLING
     bool light_sampling = false;                                   // Mode X: RT3_FLAG_LIGHT_SAMPLING
+    bool display = false;                                          // Mode X: the image written is rt3_display of the linear (or the denoised) frame
+    rt3_display_params display_params{ RT3_DISPLAY_FILMIC, RT3_DISPLAY_SRGB, 0u, 102u, 51u, 1.0f, 0.18f, 4.0f };      // the defaults of DESIGN.md 4.22
 };
 
 void print_usage(const char* exe) {
@@ -89,6 +92,9 @@ void print_usage(const char* exe) {
               << "\t\t\tsun converges). The render and --radiance; not with --adaptive, nor with a scene whose background is black.\n"
               << "\t   --light-sampling\tMode X: every diffuse bounce also samples the emissive primitives by brightness times area and casts one shadow\n"
               << "\t\t\tray (a small lamp converges). The render and --radiance; not with --adaptive, nor with --env-sampling.\n"
+              << "\t   --display\tMode X: CURVE[,TRANSFER[,EXPOSURE]]: the image written is the linear frame (with a single-frame --denoise, the\n"
+              << "\t\t\tdenoised one) through a display transform: CURVE clamp | reinhard | filmic, TRANSFER linear | gamma2 | srgb (default: srgb),\n"
+              << "\t\t\tEXPOSURE a positive gain, or auto: from the frame's trimmed log-average luminance (default: 1).\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -132,7 +138,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
                            key == "--slide" || key == "--adaptive" || key == "--counts" || key == "--regroup" ||
-                           key == "--rays" || key == "--radiance" || key == "--env";
+                           key == "--rays" || key == "--radiance" || key == "--env" || key == "--display";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -199,6 +205,32 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         else if (key == "--rays") opt.rays_path = value;
         else if (key == "--radiance") opt.radiance_path = value;
         else if (key == "--env") opt.env_path = value;
+        else if (key == "--display") {                               // CURVE[,TRANSFER[,EXPOSURE]]
+            const size_t c1 = value.find(','), c2 = c1 == std::string::npos ? c1 : value.find(',', c1 + 1);
+            const std::string curve = value.substr(0, c1);
+            const std::string transfer = c1 == std::string::npos ? "srgb" : value.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+            const std::string exposure = c2 == std::string::npos ? "1" : value.substr(c2 + 1);
+            rt3_display_params& dp = opt.display_params;
+            if (curve == "clamp") dp.curve = RT3_DISPLAY_CLAMP;
+            else if (curve == "reinhard") dp.curve = RT3_DISPLAY_REINHARD;
+            else if (curve == "filmic") dp.curve = RT3_DISPLAY_FILMIC;
+            else { std::cerr << "Unknown display curve '" << curve << "'" << std::endl; return -1; }
+            if (transfer == "linear") dp.transfer = RT3_DISPLAY_LINEAR;
+            else if (transfer == "gamma2") dp.transfer = RT3_DISPLAY_GAMMA2;
+            else if (transfer == "srgb") dp.transfer = RT3_DISPLAY_SRGB;
+            else { std::cerr << "Unknown display transfer '" << transfer << "'" << std::endl; return -1; }
+            if (exposure == "auto") { dp.flags = RT3_DISPLAY_AUTO_EXPOSURE; dp.exposure = 1.0f; }
+            else {
+                char* end = nullptr;
+                const double e = std::strtod(exposure.c_str(), &end);
+                if (end == exposure.c_str() || *end != '\0' || !std::isfinite(e) || !((float)e > 0.0f) || !std::isfinite((float)e)) {
+                    std::cerr << "Invalid display exposure '" << exposure << "'" << std::endl;
+                    return -1;
+                }
+                dp.flags = 0u; dp.exposure = (float)e;
+            }
+            opt.display = true;
+        }
         else if (key == "--regroup") {
             if (!parse_u32(value, "regroup", "Regroup", &opt.regroup)) return -1;
             if (opt.regroup == 0) { std::cerr << "--regroup must be at least 1." << std::endl; return -1; }
@@ -247,6 +279,10 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     }
     if (opt.light_sampling && opt.adaptive) {
         std::cerr << "--light-sampling is not available with --adaptive." << std::endl;
+        return -1;
+    }
+    if (mode_r && opt.display) {
+        std::cerr << "--display needs the path tracer (Mode X): pass --spp." << std::endl;
         return -1;
     }
     if (mode_r && opt.adaptive) {
@@ -456,6 +492,12 @@ int main(int argc, const char** argv) {
         const rt3_stats st = renderer.stats();
         std::cerr << "rendered " << opt.width << "x" << opt.height << (path.spp ? " x " + std::to_string(path.spp) + " spp" : " (mode R)")
                   << " in " << st.total_ms << " ms on device 0: " << st.ray_casts << " rays, " << st.prim_tests << " ray-primitive tests\n";
+        const rt3_denoise_params dp{ 5, 128, 4.0f, 1.0f };                         // the defaults of DESIGN.md 4.11
+        std::vector<float> denoised;                                 // --display with a single-frame --denoise: the frame both outputs come from
+        if (opt.display) {                                           // the image becomes the display transform of the linear frame
+            if (!opt.denoise_path.empty() && !temporal) denoised = renderer.denoise(cam, dp);
+            renderer.display(cam, denoised.empty() ? renderer.hdr() : denoised, opt.display_params);
+        }
         if (opt.png) cam.get_frame().to_png(opt.output_path);
         else cam.get_frame().to_ppm(opt.output_path);
         const uint32_t w = cam.w(), h = cam.h();
@@ -483,8 +525,7 @@ int main(int argc, const char** argv) {
             }
         }
         if (!opt.denoise_path.empty() && !temporal) {
-            const rt3_denoise_params dp{ 5, 128, 4.0f, 1.0f };                     // the defaults of DESIGN.md 4.11
-            const std::vector<float> out = renderer.denoise(cam, dp);
+            const std::vector<float> out = denoised.empty() ? renderer.denoise(cam, dp) : denoised;
             if (rt3_frame_to_pfm(out.data(), w, h, 3, 4, opt.denoise_path.c_str()) != 0) throw Fatal("Could not write '" + opt.denoise_path + "'");
         }
         if (!opt.rays_path.empty()) {                                // last: it replaces the render's stats, and touches nothing the outputs above read

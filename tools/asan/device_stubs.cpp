@@ -90,6 +90,9 @@ int rt3_denoise_temporal_motion(rt3_ctx*, uint32_t, uint32_t, const rt3_camera*,
                                 const float*, const rt3_temporal_params*, float*, rt3_history*) { return RT3_E_DEVICE; }
 int rt3_denoise_temporal_motion_device(rt3_ctx*, uint32_t, uint32_t, const rt3_camera*, const void*, const void*, const rt3_camera*, const void*,
                                        const void*, const rt3_temporal_params*, void*, void*, void*) { return RT3_E_DEVICE; }
+int rt3_display(rt3_ctx*, uint32_t, uint32_t, const float*, const rt3_display_params*, uint32_t*) { return RT3_E_DEVICE; }     // (rt3_debug_display_bin / _gain / _pixel / _srgb_table are host code)
+int rt3_display_device(rt3_ctx*, uint32_t, uint32_t, const void*, const rt3_display_params*, void*, void*) { return RT3_E_DEVICE; }
+int rt3_debug_display_state(rt3_ctx*, uint32_t*, uint32_t*, float*) { return RT3_E_DEVICE; }
 // (rt3_rows_owned / rt3_row_of_local are pure host arithmetic that happens to live in rt3_device.hip)
 uint32_t rt3_rows_owned(const rt3_params* p) {
     uint32_t n = 0;
