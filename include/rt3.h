@@ -34,7 +34,8 @@ extern "C" {
  * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh*, with
  * rt3_render_path_adaptive* (one new struct of its own), with rt3_regroup*, with the environment map (rt3_set_environment*), with its
  * importance sampling (RT3_FLAG_ENV_SAMPLING: one flag bit and two test-only functions), with the emitters' (RT3_FLAG_LIGHT_SAMPLING: the same again)
- * and with the display transform (rt3_display*: one new struct of its own): functions were only added, no existing struct changed. */
+ * with the display transform (rt3_display*: one new struct of its own) and with the lens models (rt3_lens_rays*, rt3_render_lens*,
+ * rt3_render_lens_aov*: one new struct of its own): functions were only added, no existing struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
 
@@ -587,6 +588,82 @@ int rt3_radiance(rt3_ctx* ctx, const rt3_ray* rays, const uint32_t* keys, uint32
 /* Device arrays (n rt3_ray and, or NULL, n uint32 in; n float4 out), asynchronous on `stream` (NULL = the context's own stream). */
 int rt3_radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, uint32_t n, const rt3_radiance_params* p, void* d_out_rgba,
                         void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Lens models  (DESIGN.md 4.23, 5.2r): equirectangular, fisheye, orthographic and cube frames, generated and rendered on the device
+ * ------------------------------------------------------------------------------------------------- */
+#define RT3_LENS_EQUIRECT 1u   /* the whole sphere; column W/2 looks along `forward`, row 0 is `up` */
+#define RT3_LENS_FISHEYE  2u   /* equidistant: angle from `forward` proportional to the distance from the image centre */
+#define RT3_LENS_ORTHO    3u   /* parallel rays along `forward` from a window of 2 half_extent[0] x 2 half_extent[1] */
+#define RT3_LENS_CUBE     4u   /* W = N, H = 6 N: the six faces of rt3_set_environment's layout, stacked +X -X +Y -Y +Z -Z */
+typedef struct rt3_lens {      /* 80 bytes */
+    uint32_t model;
+    float    half_fov_turns;   /* FISHEYE: half the field of view across the shorter image side, in turns (degrees / 720); in (0, 0.5] */
+    float    half_extent[2];   /* ORTHO: finite, > 0 */
+    float    origin[3];  float _pad0;
+    float    right[3];   float _pad1;   /* an orthonormal, right-handed frame: right x up = -forward ... */
+    float    up[3];      float _pad2;
+    float    forward[3]; float _pad3;   /* ... the local axes are (X, Y, Z) = (right, up, -forward) */
+} rt3_lens;
+/* Fields of other models are ignored.  A lens is refused (RT3_E_ARG) for: an unknown model; a non-finite origin or axis; an axis whose d.d, taken
+ * as the fused chain of the ray validity rule (fma(dz, dz, fma(dy, dy, dx * dx))), is further than 2^-20 from 1; two axes whose dot product (the same
+ * chain) exceeds 2^-20 in magnitude; half_fov_turns outside (0, 0.5] for FISHEYE; a half_extent that is not finite and > 0 for ORTHO;
+ * height != 6 * width for CUBE.
+ * The ray law.  Every operation is an IEEE f32 operation rounded on its own, nothing fused except inside sincos2pi (the (cos, sin)(2 pi u) of the
+ * path law's scatter).  For frame pixel (x, y), row 0 on top, and sample s of params->spp, with W = width, H = height:
+ *     base = hash2(y * W + x, hash2(s, seed));  (jx, jy) = exactly the jitter of rt3_render_path's ray cast 0: counters 1 and 2 of base, the same
+ *     strata (spp a perfect square > 1), none at spp == 1;
+ *     px = ((float)x + 0.5f) + jx;  py = ((float)y + 0.5f) - jy;  a = px / (float)W;  b = py / (float)H.
+ * The local direction l:
+ *     EQUIRECT  (ct, st) = sincos2pi(b * 0.5f);  (cp, sp) = sincos2pi(a);  l = (-sp * st, ct, -cp * st)
+ *     FISHEYE   m = 0.5f * (float)min(W, H);  nx = (px - 0.5f * (float)W) / m;  ny = (0.5f * (float)H - py) / m;  r = sqrtf(nx * nx + ny * ny);
+ *               tau = fminf(r * half_fov_turns, 0.5f);  (c, sn) = sincos2pi(tau);  k = r > 0 ? sn / r : 0;  l = (nx * k, ny * k, c).
+ *               Pixels outside the image circle continue the mapping up to the pole behind the lens: no ray is invalid.
+ *     ORTHO     nx = a * 2.0f - 1.0f;  ny = 1.0f - b * 2.0f;  e1 = nx * half_extent[0];  e2 = ny * half_extent[1];
+ *               the origin per component is (origin_c + e1 * right_c) + e2 * up_c;  l = (0, 0, 1)
+ *     CUBE      N = W;  f = y / N;  j = y - f * N;  sc = a * 2.0f - 1.0f;  tc = ((((float)j + 0.5f) - jy) / (float)N) * 2.0f - 1.0f;
+ *               (vx, vy, vz) = the row of face f in the table of "Environment map: sampling" below (+X (1, -t, -s) ...) with s = sc, t = tc;
+ *               l = (vx, vy, -vz): under the identity frame (right +X, up +Y, forward -Z) texel (f, j, i)'s ray is the direction the lookup law
+ *               maps back to that texel, so the frame, reshaped to (6, N, N, 4), is a map of the scene's surroundings.
+ * World direction per component: w_c = (l.x * right_c + l.y * up_c) + l.z * forward_c; then d = w * (1.0f / sqrtf(w.x * w.x + w.y * w.y + w.z * w.z)).
+ * The record is (origin, +inf | d, 0).  Every generated ray passes the validity rule of queries and radiance.
+ * rt3_lens_rays*: the twin of rt3_camera_rays*: for samples [sample_begin, sample_begin + sample_count) of params->spp, record
+ * (s - sample_begin) * npix + pix over the owned pixels (compact tile rows).  No scene needed; max_depth, t_min, lens_radius and flags are checked as
+ * rt3_params always is and otherwise not used.  Owned pixels x samples <= 2^31 - 2^16.  Unlike the camera's frames a lens frame may be one pixel wide
+ * or high (width, height >= 1: a cube of N = 1).
+ * rt3_render_lens*: linear float4 per owned pixel.  Defining property: the value of owned pixel pix (frame pixel index q = y * W + x) is
+ * (S.r / n, S.g / n, S.b / n, 0), n = (float)sample_count, S the f32 sum from +0, in sample order, over s in [sample_begin, sample_begin +
+ * sample_count), of what rt3_radiance returns for record (s, pix) of rt3_lens_rays under keys = q, seed / max_depth / t_min from params,
+ * sample_begin = s, sample_count = 1 and the bits RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING of params->flags.  Every
+ * rule of those flags carries over (the map, the sampling tables, their mutual refusals).  RT3_FLAG_GAMMA2 is accepted and ignored: the output is
+ * linear, rt3_display* packs it.  RT3_FLAG_REFERENCE_PRIMARY, RT3_FLAG_VARIANCE, a lens_radius that is not 0 and unknown bits are refused
+ * (RT3_E_ARG).  Owned pixels <= 2^27.  RT3_E_STATE without a scene.  Tiles as in rt3_params: a shard writes its compact rows, which equal the same
+ * rows of the whole frame bit for bit.
+ * rt3_render_lens_aov*: the twin of rt3_render_aov*: the lens rays of all spp samples, each traced with rt3_intersect's rule (t_min from params,
+ * t_max = +inf), reduced per pixel exactly as rt3_aov describes; the miss albedo is the sky's or the map's as there.  max_depth is not used;
+ * RT3_FLAG_REFERENCE_PRIMARY and a lens_radius that is not 0 are refused.
+ * Context.  As rt3_radiance*: the accumulation of a progressive or adaptive render is never touched; streams and the event chain work as for
+ * queries; rt3_get_stats afterwards reports samples = owned pixels x sample_count (x spp for the AOVs) with casts, launches, times and filter counters
+ * summed — a render traces every sample with a launch of its own (the Rays form maps an item to ray item % npix, and here each sample has its own
+ * rays); scratch belongs to the context (32 B per ray of a batch, plus 4 B per pixel of keys for a shard); batches are sized by
+ * rt3_set_sample_storage_cap at 44 B per (pixel, sample) and the result does not depend on them; the device forms never wait for the device.  Device
+ * pointers are 16-byte aligned.
+ * Out of scope: thin-lens depth of field for these models, the temporal denoiser and the motion plane (their reprojection is pinhole), the adaptive
+ * render. */
+/* Host: origin = from and the frame that looks from `from` towards `at` with `vup` up (forward = unit(at - from), right = unit(forward x vup),
+ * up = right x forward); sets model, leaves half_fov_turns and half_extent, zeroes the pads. */
+void rt3_lens_look_at(rt3_lens* lens, uint32_t model, const float from[3], const float at[3], const float vup[3]);
+int  rt3_lens_rays(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* params, uint32_t sample_begin, uint32_t sample_count, rt3_ray* out_rays);
+int  rt3_lens_rays_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* params, uint32_t sample_begin, uint32_t sample_count,
+                          void* d_out_rays, void* stream);
+int  rt3_render_lens(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* params, uint32_t sample_begin, uint32_t sample_count, float* out_rgba);
+int  rt3_render_lens_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* params, uint32_t sample_begin, uint32_t sample_count,
+                            void* d_out_rgba, void* stream);
+int  rt3_render_lens_aov(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* params, rt3_aov* out_aov);
+int  rt3_render_lens_aov_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* params, void* d_out_aov, void* stream);
+/* Host only, no device and no context: the law above in C for one (pixel, sample) of the whole frame.  RT3_E_ARG for a NULL pointer, a lens the
+ * entry points refuse, width or height 0, spp 0, x >= width, y >= height or s >= spp.  tests/lens_ref.py restates it bit for bit. */
+int  rt3_debug_lens_ray(const rt3_lens* lens, const rt3_params* params, uint32_t x, uint32_t y, uint32_t s, rt3_ray* out);
 
 /* ---------------------------------------------------------------------------------------------------
  * Environment map  (DESIGN.md 4.19, 5.2n): a cube map answers every Mode-X ray that leaves the scene

@@ -57,6 +57,14 @@ DISPLAY_CLAMP, DISPLAY_REINHARD, DISPLAY_FILMIC = 0, 1, 2
 DISPLAY_LINEAR, DISPLAY_GAMMA2, DISPLAY_SRGB = 0, 1, 2
 DISPLAY_AUTO_EXPOSURE = 1
 DISPLAY_DARK = 0xFFFFFFFF          # rt3_debug_display_bin's word for a pixel below 2^-16
+LENS_EQUIRECT = 1
+LENS_FISHEYE = 2
+LENS_ORTHO = 3
+LENS_CUBE = 4
+_LENS_MODELS = {"equirect": LENS_EQUIRECT, "fisheye": LENS_FISHEYE, "ortho": LENS_ORTHO, "cube": LENS_CUBE}
+# rt3_lens: 80 bytes
+LENS = np.dtype([("model", "<u4"), ("half_fov_turns", "<f4"), ("half_extent", "<f4", 2), ("origin", "<f4", 3), ("_pad0", "<f4"),
+                 ("right", "<f4", 3), ("_pad1", "<f4"), ("up", "<f4", 3), ("_pad2", "<f4"), ("forward", "<f4", 3), ("_pad3", "<f4")])
 _DISPLAY_CURVES = {"clamp": DISPLAY_CLAMP, "reinhard": DISPLAY_REINHARD, "filmic": DISPLAY_FILMIC}
 _DISPLAY_TRANSFERS = {"linear": DISPLAY_LINEAR, "gamma2": DISPLAY_GAMMA2, "srgb": DISPLAY_SRGB}
 
@@ -156,6 +164,37 @@ def display_params(curve="filmic", transfer="srgb", exposure=1.0, auto=False, ke
     return DISPLAY_PARAMS(int(c), int(t), DISPLAY_AUTO_EXPOSURE if auto else 0, int(trim_low), int(trim_high), float(exposure), float(key), float(white))
 
 
+class rt3_lens(C.Structure):
+    """rt3_lens (80 bytes): the model, the fisheye's half field of view in turns, the orthographic window's half extents, the origin and the
+    orthonormal frame (right, up, forward), right x up = -forward."""
+    _fields_ = [("model", C.c_uint32), ("half_fov_turns", C.c_float), ("half_extent", C.c_float * 2),
+                ("origin", C.c_float * 3), ("_pad0", C.c_float), ("right", C.c_float * 3), ("_pad1", C.c_float),
+                ("up", C.c_float * 3), ("_pad2", C.c_float), ("forward", C.c_float * 3), ("_pad3", C.c_float)]
+
+
+def make_lens(model, origin, at, vup=(0.0, 1.0, 0.0), fov_deg=180.0, extent=(1.0, 1.0)):
+    """An rt3_lens at `origin` that looks towards `at` with `vup` up (rt3_lens_look_at).  model: LENS_* or "equirect" | "fisheye" | "ortho" | "cube";
+    fov_deg: the fisheye's whole field of view across the shorter image side; extent: the orthographic window's (width, height)."""
+    m = _LENS_MODELS.get(model, model) if isinstance(model, str) else model
+    if isinstance(m, str):
+        raise Fatal("lens: model is equirect | fisheye | ortho | cube")
+    lens = rt3_lens()
+    o, a, u = _f3(origin), _f3(at), _f3(vup)
+    lib().rt3_lens_look_at(C.byref(lens), int(m), o, a, u)
+    lens.half_fov_turns = np.float32(fov_deg) / np.float32(720.0)
+    lens.half_extent[0] = np.float32(extent[0]) * np.float32(0.5)
+    lens.half_extent[1] = np.float32(extent[1]) * np.float32(0.5)
+    return lens
+
+
+def lens_ray(lens, params, x, y, s):
+    """The lens law on the host (rt3_debug_lens_ray; no device): sample s of frame pixel (x, y) as one RAY record."""
+    out = np.zeros(1, RAY)
+    if lib().rt3_debug_lens_ray(C.byref(lens), C.byref(params), int(x), int(y), int(s), _p(out)) != 0:
+        raise Fatal("rt3_debug_lens_ray: a lens the entry points refuse, or a pixel / sample outside the frame")
+    return out[0]
+
+
 class Fatal(RuntimeError):
     """Mirror of CppDebugger::Fatal: every backend error is fatal (Main.cpp:305-308)."""
 
@@ -188,6 +227,8 @@ EXPORTS = [
     "rt3_debug_light_sample", "rt3_debug_light_table",
     "rt3_display", "rt3_display_device", "rt3_debug_display_state", "rt3_debug_display_bin", "rt3_debug_display_gain", "rt3_debug_display_pixel",
     "rt3_debug_display_srgb_table",
+    "rt3_lens_look_at", "rt3_lens_rays", "rt3_lens_rays_device", "rt3_render_lens", "rt3_render_lens_device", "rt3_render_lens_aov",
+    "rt3_render_lens_aov_device", "rt3_debug_lens_ray",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -272,6 +313,11 @@ def lib():
         "rt3_debug_display_state": (i32, [vp, vp, vp, vp]), "rt3_debug_display_bin": (i32, [vp, vp]),
         "rt3_debug_display_gain": (i32, [vp, vp, vp]), "rt3_debug_display_pixel": (i32, [vp, f32, vp, vp]),
         "rt3_debug_display_srgb_table": (i32, [vp]),
+        "rt3_lens_look_at": (None, [vp, u32, vp, vp, vp]),
+        "rt3_lens_rays": (i32, [vp, vp, vp, u32, u32, vp]), "rt3_lens_rays_device": (i32, [vp, vp, vp, u32, u32, vp, vp]),
+        "rt3_render_lens": (i32, [vp, vp, vp, u32, u32, vp]), "rt3_render_lens_device": (i32, [vp, vp, vp, u32, u32, vp, vp]),
+        "rt3_render_lens_aov": (i32, [vp, vp, vp, vp]), "rt3_render_lens_aov_device": (i32, [vp, vp, vp, vp, vp]),
+        "rt3_debug_lens_ray": (i32, [vp, vp, u32, u32, u32, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -1142,6 +1188,68 @@ class HipRenderer(Renderer):
         """Asynchronous rt3_radiance_device: n rt3_ray at d_rays_ptr, n uint32 keys at d_keys_ptr (or None), n float4 out at d_out_ptr."""
         self._check(lib().rt3_radiance_device(self._ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_keys_ptr or 0), n, C.byref(radiance_params),
                                               C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
+
+    # -- lens models (rt3_lens_rays*, rt3_render_lens*, rt3_render_lens_aov*; DESIGN.md 4.23) ------------------------------------------
+    @staticmethod
+    def _lens_range(params, sample_begin, sample_count):
+        return int(sample_begin), int(params.spp - sample_begin if sample_count is None else sample_count)
+
+    def lens_rays(self, lens, params, sample_begin=0, sample_count=None, device=None):
+        """The lens's rays for samples [begin, begin + count) (default: all spp), sample-major as camera_rays returns the camera's: a RAY array,
+        or with device (a torch device, or True for the current one) a (n, 8) float32 tensor there, queued on torch.cuda.current_stream()."""
+        sb, sc = self._lens_range(params, sample_begin, sample_count)
+        n = lib().rt3_rows_owned(C.byref(params)) * params.width * max(sc, 0)
+        if device is not None and device is not False:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device()) if device is True else torch.device(device)
+            out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            self.lens_rays_device(lens, params, sb, sc, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return out
+        out = np.zeros(n, RAY)
+        self._check(lib().rt3_lens_rays(self._ctx, C.byref(lens), C.byref(params), sb, sc, _p(out)))
+        return out
+
+    def lens_rays_device(self, lens, params, sample_begin, sample_count, d_out_ptr, stream_ptr=None):
+        self._check(lib().rt3_lens_rays_device(self._ctx, C.byref(lens), C.byref(params), sample_begin, sample_count, C.c_void_p(d_out_ptr),
+                                               C.c_void_p(stream_ptr or 0)))
+
+    def render_lens(self, lens, params, sample_begin=0, sample_count=None, device=None):
+        """The lens frame, linear (rt3_render_lens): the mean radiance over samples [begin, begin + count) (default: all spp) of every owned pixel,
+        float32 (rows_owned, width, 4), (r, g, b, 0) — a numpy array, or with device (a torch device, or True for the current one) a tensor there,
+        queued on torch.cuda.current_stream().  A cube lens's frame, reshaped to (6, N, N, 4), is what set_environment takes."""
+        sb, sc = self._lens_range(params, sample_begin, sample_count)
+        rows = lib().rt3_rows_owned(C.byref(params))
+        if device is not None and device is not False:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device()) if device is True else torch.device(device)
+            out = torch.empty((rows, params.width, 4), dtype=torch.float32, device=dev)
+            self.render_lens_device(lens, params, sb, sc, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return out
+        out = np.zeros((rows, params.width, 4), np.float32)
+        self._check(lib().rt3_render_lens(self._ctx, C.byref(lens), C.byref(params), sb, sc, _p(out)))
+        return out
+
+    def render_lens_device(self, lens, params, sample_begin, sample_count, d_out_ptr, stream_ptr=None):
+        """Asynchronous rt3_render_lens_device into a device buffer of rows_owned * width float4."""
+        self._check(lib().rt3_render_lens_device(self._ctx, C.byref(lens), C.byref(params), sample_begin, sample_count, C.c_void_p(d_out_ptr),
+                                                 C.c_void_p(stream_ptr or 0)))
+
+    def render_lens_aov(self, lens, params, device=None):
+        """First-hit AOVs of the lens frame (rt3_render_lens_aov): an AOV array of shape (rows_owned, width), or with device a (rows_owned, width,
+        12) float32 tensor of the 48-byte records there, queued on torch.cuda.current_stream() — what denoise() takes beside render_lens()."""
+        rows = lib().rt3_rows_owned(C.byref(params))
+        if device is not None and device is not False:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device()) if device is True else torch.device(device)
+            out = torch.empty((rows, params.width, 12), dtype=torch.float32, device=dev)
+            self.render_lens_aov_device(lens, params, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return out
+        out = np.zeros((rows, params.width), AOV)
+        self._check(lib().rt3_render_lens_aov(self._ctx, C.byref(lens), C.byref(params), _p(out)))
+        return out
+
+    def render_lens_aov_device(self, lens, params, d_out_ptr, stream_ptr=None):
+        self._check(lib().rt3_render_lens_aov_device(self._ctx, C.byref(lens), C.byref(params), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
 
     # -- the environment map (rt3_set_environment*; DESIGN.md 4.19) -----------------------------------------------------
     def set_environment(self, cube):

@@ -36,6 +36,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <set>
 #include <string>
@@ -47,6 +48,7 @@
 #include "rt3_sphere_plan.hpp"
 #include "rt3_env_sample.hpp"
 #include "rt3_light_sample.hpp"
+#include "rt3_lens_law.hpp"
 #include "rt3_kernel_common.hpp"
 #include "rt3_path.hpp"
 #include "rt3_valu_scan.hpp"
@@ -55,6 +57,7 @@
 #include "rt3_reduce.hpp"
 #include "rt3_adaptive.hpp"
 #include "rt3_aov.hpp"
+#include "rt3_lens.hpp"
 #include "rt3_denoise.hpp"
 #include "rt3_display_law.hpp"
 #include "rt3_display.hpp"
@@ -162,6 +165,7 @@ struct rt3_ctx {
     DevBuf<float4> d_arays;                                         // first-hit AOVs (rt3_render_aov*): one batch's camera rays and their hits,
     DevBuf<uint4> d_ahits;                                          // and the per-pixel running sums (three planes; not d_accum, which belongs to
     DevBuf<float4> d_aacc;                                          // the progressive render)
+    DevBuf<uint32_t> d_lens_keys;                                   // a shard's frame pixel indices (rt3_render_lens*: the keys of its rays)
     DevBuf<float4> d_dn;                                            // denoiser scratch (rt3_denoise*): two (I, v) planes, the guide plane, the depth slopes
     // the display transform's auto-exposure (rt3_display*): hist[512], dark, n and the gain's bits, allocated by the first call with the flag and
     // zeroed at the start of each such call; display_auto: there has been one (rt3_debug_display_state)
@@ -2277,17 +2281,15 @@ int rt3_camera_rays(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, ui
     return 0;
 }
 
-// Per sample batch: k_camera_rays -> the query form of the scene's trace kernel on that buffer -> k_aov_accumulate; then one k_aov_resolve.
-// The batches share one ev_begin / ev_end and one counter reset, as the render's batch loop does.
-int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, void* d_out, void* stream_) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = aov_common_checks(ctx, cam, p, d_out, "d_out_aov");
-    if (rc) return rc;
-    if ((rc = check_scene(ctx))) return rc;
-    hipStream_t stream;
-    if ((rc = enter(ctx, stream_, &stream))) return rc;
+// Per sample batch: the batch's rays (make_rays(s0, ns): k_camera_rays, or k_lens_rays for a lens frame) into d_arays -> the query form of the scene's
+// trace kernel on that buffer -> k_aov_accumulate; then one k_aov_resolve.  The batches share one ev_begin / ev_end and one counter reset, as the
+// render's batch loop does.  A: what k_aov_accumulate reads — the scene's records and the flags.  The caller has checked its arguments and the scene
+// and is behind enter().
+static int aov_pass(rt3_ctx* ctx, const rt3_params* p, const TraceArgs& A, void* d_out, hipStream_t stream,
+                    const std::function<int(uint32_t, uint32_t)>& make_rays) {
     const uint32_t npix = rt3_rows_owned(p) * p->width;
     ctx->rendered = false;
+    int rc;
     if (npix == 0) return (rc = begin_timed(ctx, stream)) ? rc : end_timed(ctx, stream, 0, nullptr);
     // batch size: 48 B per (pixel, sample) — the ray (32) and its hit (16) — under the sample storage cap
     const uint64_t per_spp = (uint64_t)npix * (sizeof(rt3_ray) + sizeof(rt3_hit));
@@ -2297,8 +2299,6 @@ int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
     if ((rc = ctx->d_arays.ensure(ctx, (size_t)npix * batch * 2u)) || (rc = ctx->d_ahits.ensure(ctx, (size_t)npix * batch)) ||
         (rc = ctx->d_aacc.ensure(ctx, (size_t)npix * 3u)))
         return rc;
-    TraceArgs A;                                                    // camera rays and the accumulation
-    if ((rc = path_args(ctx, cam, p, npix, A))) return rc;
     TraceArgs Q = scene_args(ctx);                                  // the query launches, as query_device sets them up
     Q.t_min = p->t_min;
     Q.q_rays = ctx->d_arays; Q.q_out = ctx->d_ahits; Q.q_occluded = 0u;
@@ -2306,10 +2306,8 @@ int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
     if ((rc = plan_trace(ctx, Q, Form::Query, false, T)) || (rc = begin_timed(ctx, stream))) return rc;
     for (uint32_t s0 = 0; s0 < p->spp; s0 += batch) {
         const uint32_t ns = std::min(batch, p->spp - s0);
-        A.s0 = s0;
-        A.total = Q.total = npix * ns;
-        hipLaunchKernelGGL(k_camera_rays, dim3((A.total + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, ctx->d_arays);
-        RT3_HIP(hipGetLastError());
+        Q.total = npix * ns;
+        if ((rc = make_rays(s0, ns))) return rc;
         if ((rc = issue_trace(ctx, Q, T, Q.total, stream))) return rc;
         hipLaunchKernelGGL(k_aov_accumulate, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, (const float4*)ctx->d_arays,
                            (const uint4*)ctx->d_ahits, ctx->d_aacc, npix, ns, s0 == 0 ? 1 : 0, (const float4*)ctx->d_env, ctx->env_n);
@@ -2318,6 +2316,26 @@ int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
     hipLaunchKernelGGL(k_aov_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_aacc, npix, p->spp, (float4*)d_out);
     RT3_HIP(hipGetLastError());
     return end_timed(ctx, stream, (uint64_t)npix * p->spp, &T);
+}
+
+int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = aov_common_checks(ctx, cam, p, d_out, "d_out_aov");
+    if (rc) return rc;
+    if ((rc = check_scene(ctx))) return rc;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    const uint32_t npix = rt3_rows_owned(p) * p->width;
+    ctx->rendered = false;
+    TraceArgs A = scene_args(ctx);                                  // camera rays and the accumulation (a shard that owns no pixel launches neither)
+    if (npix != 0 && (rc = path_args(ctx, cam, p, npix, A))) return rc;
+    return aov_pass(ctx, p, A, d_out, stream, [&](uint32_t s0, uint32_t ns) {
+        A.s0 = s0;
+        A.total = npix * ns;
+        hipLaunchKernelGGL(k_camera_rays, dim3((A.total + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, ctx->d_arays.get());
+        RT3_HIP(hipGetLastError());
+        return 0;
+    });
 }
 
 int rt3_render_aov(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, rt3_aov* out) {
@@ -2715,6 +2733,194 @@ int rt3_radiance(rt3_ctx* ctx, const rt3_ray* rays, const uint32_t* keys, uint32
 }
 int rt3_radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, uint32_t n, const rt3_radiance_params* p, void* d_out_rgba, void* stream) {
     return radiance_device(ctx, d_rays, d_keys, n, p, d_out_rgba, stream);
+}
+
+// ---- Lens models: k_lens_rays writes a batch's rays (and a shard's keys) into the context's scratch; a render then runs
+// radiance_device's loop with ONE trace launch per sample — the Rays form maps item j to ray j % npix, and here every sample has rays of its own, so a
+// launch covers one sample's slice of the rays and of the sample storage (s0 = s, total = npix) — and the AOV pass runs rt3_render_aov_device's loop.
+static_assert(sizeof(rt3_lens) == 80, "rt3.h: rt3_lens");
+// rt3_params' own rules (check_params) with one difference: a lens frame may be one pixel wide or high (a cube of N = 1); then the lens.
+static int lens_checks(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, const void* d_out, const char* what, bool device) {
+    if (!lens || !d_out) return fail(ctx, RT3_E_ARG, std::string("lens / ") + what + " is NULL");
+    if (!p) return fail(ctx, RT3_E_ARG, "params is NULL");
+    if (!(p->t_min >= 0.0f) || !(p->t_min < __builtin_inff())) return fail(ctx, RT3_E_ARG, "t_min must be finite and >= 0");
+    if (p->flags & ~(RT3_FLAG_GAMMA2 | RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_REFERENCE_PRIMARY | RT3_FLAG_VARIANCE | RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING))
+        return fail(ctx, RT3_E_ARG, "unknown bits in flags");
+    if (p->width < 1 || p->height < 1) return fail(ctx, RT3_E_ARG, "width and height must be >= 1");
+    if ((uint64_t)p->width * p->height > 0x7FFFFFFFull) return fail(ctx, RT3_E_ARG, "frame too large");
+    if (p->spp < 1 || p->max_depth < 1) return fail(ctx, RT3_E_ARG, "spp and max_depth must be >= 1");
+    if (p->tile_count > 1 && (p->tile_rows == 0 || p->tile_index >= p->tile_count))
+        return fail(ctx, RT3_E_ARG, "bad tile_rows / tile_index / tile_count");
+    if (const char* why = rt3lens::refusal(lens, p->width, p->height)) return fail(ctx, RT3_E_ARG, why);
+    if (device && (uintptr_t)d_out % 16u != 0) return fail(ctx, RT3_E_ARG, std::string(what) + " must be 16-byte aligned");
+    return 0;
+}
+// The rays of samples [s0, s0 + ns) of the npix owned pixels -> d_rays (2 * npix * ns float4) and, non-null, the pixels' keys -> d_keys (npix words).
+static int launch_lens_rays(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, uint32_t npix, uint32_t s0, uint32_t ns, float4* d_rays,
+                            uint32_t* d_keys, hipStream_t stream) {
+    LensArgs A;
+    A.lens = *lens;
+    A.frame = rt3lens::Frame{ p->width, p->height, p->spp, p->seed, rt3lens::edge_of(p->spp) };
+    A.tile_rows = p->tile_rows; A.tile_index = p->tile_index; A.tile_count = p->tile_count;
+    A.npix = npix; A.s0 = s0; A.total = npix * ns;
+    const dim3 grid((A.total + kBlock - 1) / kBlock), block(kBlock);
+    switch (lens->model) {
+    case RT3_LENS_EQUIRECT: hipLaunchKernelGGL(k_lens_rays<RT3_LENS_EQUIRECT>, grid, block, 0, stream, A, d_rays, d_keys); break;
+    case RT3_LENS_FISHEYE:  hipLaunchKernelGGL(k_lens_rays<RT3_LENS_FISHEYE>, grid, block, 0, stream, A, d_rays, d_keys); break;
+    case RT3_LENS_ORTHO:    hipLaunchKernelGGL(k_lens_rays<RT3_LENS_ORTHO>, grid, block, 0, stream, A, d_rays, d_keys); break;
+    default:                hipLaunchKernelGGL(k_lens_rays<RT3_LENS_CUBE>, grid, block, 0, stream, A, d_rays, d_keys); break;
+    }
+    RT3_HIP(hipGetLastError());
+    return 0;
+}
+static bool lens_sample_range_ok(const rt3_params* p, uint32_t sample_begin, uint32_t sample_count) {
+    return sample_count != 0 && (uint64_t)sample_begin + sample_count <= p->spp;
+}
+
+int rt3_lens_rays_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, uint32_t sample_begin, uint32_t sample_count, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = lens_checks(ctx, lens, p, d_out, "rays", true);
+    if (rc) return rc;
+    if (!lens_sample_range_ok(p, sample_begin, sample_count)) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
+    const uint32_t npix = rt3_rows_owned(p) * p->width;
+    if ((uint64_t)npix * sample_count > 0x7FFF0000ull) return fail(ctx, RT3_E_ARG, "too many rays for one call (owned pixels x samples > 2^31 - 2^16)");
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    if (npix != 0 && (rc = launch_lens_rays(ctx, lens, p, npix, sample_begin, sample_count, (float4*)d_out, nullptr, stream))) return rc;
+    return leave(ctx, stream);
+}
+
+int rt3_lens_rays(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, uint32_t sample_begin, uint32_t sample_count, rt3_ray* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = lens_checks(ctx, lens, p, out, "out_rays", false);
+    if (rc) return rc;
+    if (!lens_sample_range_ok(p, sample_begin, sample_count)) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
+    const uint64_t n = (uint64_t)rt3_rows_owned(p) * p->width * sample_count;
+    if (n > 0x7FFF0000ull) return fail(ctx, RT3_E_ARG, "too many rays for one call (owned pixels x samples > 2^31 - 2^16)");
+    RT3_HIP(hipSetDevice(ctx->device));
+    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(2 * n, 1)))) return rc;
+    if ((rc = rt3_lens_rays_device(ctx, lens, p, sample_begin, sample_count, ctx->stage, ctx->stream))) return rc;
+    if (n) RT3_HIP(hipMemcpyAsync(out, ctx->stage, n * sizeof(rt3_ray), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+static int render_lens_checks(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, uint32_t sample_begin, uint32_t sample_count, const void* out,
+                              const char* what, bool device) {
+    int rc = lens_checks(ctx, lens, p, out, what, device);
+    if (rc) return rc;
+    if ((rc = check_light_sampling(ctx, p->flags))) return rc;      // (the flag's own answers come before every older refusal)
+    if (p->flags & (RT3_FLAG_REFERENCE_PRIMARY | RT3_FLAG_VARIANCE))
+        return fail(ctx, RT3_E_ARG, "rt3_render_lens: RT3_FLAG_REFERENCE_PRIMARY and RT3_FLAG_VARIANCE do not apply to a lens frame");
+    if ((p->flags & RT3_FLAG_ENV_SAMPLING) && (p->flags & RT3_FLAG_BLACK_BACKGROUND))
+        return fail(ctx, RT3_E_ARG, "RT3_FLAG_ENV_SAMPLING cannot be combined with RT3_FLAG_BLACK_BACKGROUND or RT3_FLAG_REFERENCE_PRIMARY");
+    if (!(p->lens_radius == 0.0f)) return fail(ctx, RT3_E_ARG, "rt3_render_lens: lens_radius must be 0 (no depth of field for the lens models)");
+    if (!lens_sample_range_ok(p, sample_begin, sample_count)) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
+    if ((uint64_t)rt3_rows_owned(p) * p->width > (1ull << 27)) return fail(ctx, RT3_E_ARG, "at most 2^27 owned pixels per lens render (shard the frame)");
+    return 0;
+}
+
+int rt3_render_lens_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, uint32_t sample_begin, uint32_t sample_count, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = render_lens_checks(ctx, lens, p, sample_begin, sample_count, d_out, "d_out_rgba", true);
+    if (rc) return rc;
+    if ((rc = check_scene(ctx)) || (rc = check_env_sampling(ctx, p->flags))) return rc;
+    const uint32_t flags = p->flags & (RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING);
+    const bool nee = (flags & RT3_FLAG_ENV_SAMPLING) != 0, light = (flags & RT3_FLAG_LIGHT_SAMPLING) != 0;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    const uint32_t npix = rt3_rows_owned(p) * p->width;
+    ctx->rendered = false;
+    if (npix == 0) return (rc = begin_timed(ctx, stream)) ? rc : end_timed(ctx, stream, 0, nullptr);
+    // batch size: 44 B per (pixel, sample) — the ray (32) and its radiance record (12) — under the sample storage cap
+    const uint64_t per_spp = (uint64_t)npix * (sizeof(rt3_ray) + sizeof(Rgb));
+    uint32_t batch = (uint32_t)std::min<uint64_t>(sample_count, std::max<uint64_t>(1, ctx->rad_cap_bytes / per_spp));
+    batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / npix);          // (npix <= 2^27: at least 15)
+    const bool shard = p->tile_count > 1;                           // a whole frame's ray index is its frame pixel index: no keys
+    if ((rc = ctx->d_arays.ensure(ctx, (size_t)npix * batch * 2u)) || (rc = ctx->d_rad.ensure(ctx, (size_t)npix * batch)) ||
+        (shard && (rc = ctx->d_lens_keys.ensure(ctx, npix))))
+        return rc;
+    uint32_t* const d_keys = shard ? ctx->d_lens_keys.get() : nullptr;
+    TraceArgs A = scene_args(ctx);
+    A.max_depth = p->max_depth; A.seed = p->seed; A.flags = flags; A.t_min = p->t_min;
+    A.npix = npix; A.div_npix = make_fastdiv(npix);
+    if (!fastdiv_ok(npix, 0x7FFFFFFFu)) return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
+    TracePlan T;
+    if (nee && (rc = ensure_env_table(ctx, stream))) return rc;
+    if (light && (rc = ensure_light_table(ctx, stream))) return rc;
+    if ((rc = plan_trace(ctx, A, Form::Rays, false, T, nee, light))) return rc;
+    A.ray_keys = d_keys;
+    A.total = npix;                                                 // one launch per sample: its slice of the rays and of the storage
+    if ((rc = begin_timed(ctx, stream))) return rc;
+    const uint32_t s_end = sample_begin + sample_count;
+    const dim3 ag((npix + kBlock - 1) / kBlock), ab(kBlock);
+    for (uint32_t s0 = sample_begin; s0 < s_end; s0 += batch) {
+        const uint32_t ns = std::min(batch, s_end - s0);
+        if ((rc = launch_lens_rays(ctx, lens, p, npix, s0, ns, ctx->d_arays, d_keys, stream))) return rc;
+        for (uint32_t i = 0; i < ns; i++) {
+            A.s0 = s0 + i;
+            A.q_rays = ctx->d_arays.get() + (size_t)i * npix * 2u;
+            A.rad = ctx->d_rad.get() + (size_t)i * npix;
+            if ((rc = issue_trace(ctx, A, T, npix, stream))) return rc;
+        }
+        hipLaunchKernelGGL(k_accumulate<false>, ag, ab, 0, stream, ctx->d_rad, (float4*)d_out, (float4*)nullptr, npix, ns, s0 == sample_begin ? 1 : 0);
+        RT3_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_resolve_float_inplace, ag, ab, 0, stream, (float4*)d_out, npix, sample_count);
+    RT3_HIP(hipGetLastError());
+    return end_timed(ctx, stream, (uint64_t)npix * sample_count, &T);
+}
+
+int rt3_render_lens(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, uint32_t sample_begin, uint32_t sample_count, float* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = render_lens_checks(ctx, lens, p, sample_begin, sample_count, out, "out_rgba", false);
+    if (rc) return rc;
+    if ((rc = check_scene(ctx))) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
+    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(npix, 1)))) return rc;
+    if ((rc = rt3_render_lens_device(ctx, lens, p, sample_begin, sample_count, ctx->stage, ctx->stream))) return rc;
+    if (npix) RT3_HIP(hipMemcpyAsync(out, ctx->stage, npix * 16u, hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+static int lens_aov_checks(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, const void* out, const char* what, bool device) {
+    int rc = lens_checks(ctx, lens, p, out, what, device);
+    if (rc) return rc;
+    if (p->flags & RT3_FLAG_REFERENCE_PRIMARY) return fail(ctx, RT3_E_ARG, "rt3_render_lens_aov: RT3_FLAG_REFERENCE_PRIMARY does not apply to a lens frame");
+    if (!(p->lens_radius == 0.0f)) return fail(ctx, RT3_E_ARG, "rt3_render_lens_aov: lens_radius must be 0 (no depth of field for the lens models)");
+    return 0;
+}
+
+// rt3_render_aov_device's pass with k_lens_rays in k_camera_rays' place.
+int rt3_render_lens_aov_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = lens_aov_checks(ctx, lens, p, d_out, "d_out_aov", true);
+    if (rc) return rc;
+    if ((rc = check_scene(ctx))) return rc;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    const uint32_t npix = rt3_rows_owned(p) * p->width;
+    TraceArgs A = scene_args(ctx);                                  // the accumulation: the scene's records and the flags
+    A.flags = p->flags;
+    return aov_pass(ctx, p, A, d_out, stream, [&](uint32_t s0, uint32_t ns) {
+        return launch_lens_rays(ctx, lens, p, npix, s0, ns, ctx->d_arays, nullptr, stream);
+    });
+}
+
+int rt3_render_lens_aov(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, rt3_aov* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = lens_aov_checks(ctx, lens, p, out, "out_aov", false);
+    if (rc) return rc;
+    if ((rc = check_scene(ctx))) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
+    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(3 * npix, 1)))) return rc;
+    if ((rc = rt3_render_lens_aov_device(ctx, lens, p, ctx->stage, ctx->stream))) return rc;
+    if (npix) RT3_HIP(hipMemcpyAsync(out, ctx->stage, npix * sizeof(rt3_aov), hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 // ---- Environment map: the context's own copy of a cube map, read by the miss of the environment forms (5.2n) and by k_aov_accumulate.

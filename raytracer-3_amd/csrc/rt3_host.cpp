@@ -9,6 +9,7 @@
 #include "rt3_env_sample.hpp"
 #include "rt3_light_sample.hpp"
 #include "rt3_display_law.hpp"
+#include "rt3_lens_law.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -602,4 +603,31 @@ extern "C" uint32_t rt3_debug_sphere_plan(const float* center_radius, uint32_t n
     for (int k = 0; k < 4; k++) direct[k] = 0xFFFFFFFFu;
     sphere_filter_centre(center_radius, n, centre);
     return sphere_direct_list(center_radius, n, centre, direct);
+}
+
+// The lens models' law (rt3.h "Lens models") on the host: the statement of rt3_lens_law.hpp k_lens_rays evaluates, one ray per call,
+// and the frame a lens looks through.  A refused call writes nothing.
+extern "C" int rt3_debug_lens_ray(const rt3_lens* lens, const rt3_params* p, uint32_t x, uint32_t y, uint32_t s, rt3_ray* out) {
+    if (!lens || !p || !out || p->width == 0 || p->height == 0 || p->spp == 0 || x >= p->width || y >= p->height || s >= p->spp) return RT3_E_ARG;
+    if (rt3lens::refusal(lens, p->width, p->height)) return RT3_E_ARG;
+    const rt3lens::Frame f{ p->width, p->height, p->spp, p->seed, rt3lens::edge_of(p->spp) };
+    rt3lens::ray_of(*lens, f, x, y, s, out->origin, out->direction);
+    out->t_max = __builtin_inff();
+    out->_pad = 0u;
+    return 0;
+}
+// Worked out in double and rounded once per component: each axis is then a unit vector to a few 2^-25, far inside the 2^-20 the entry points ask for.
+extern "C" void rt3_lens_look_at(rt3_lens* lens, uint32_t model, const float from[3], const float at[3], const float vup[3]) {
+    if (!lens || !from || !at || !vup) return;
+    double f[3], r[3], u[3];
+    for (int c = 0; c < 3; c++) f[c] = (double)at[c] - (double)from[c];
+    const double lf = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+    for (int c = 0; c < 3; c++) f[c] /= lf;
+    r[0] = f[1] * vup[2] - f[2] * vup[1]; r[1] = f[2] * vup[0] - f[0] * vup[2]; r[2] = f[0] * vup[1] - f[1] * vup[0];
+    const double lr = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    for (int c = 0; c < 3; c++) r[c] /= lr;
+    u[0] = r[1] * f[2] - r[2] * f[1]; u[1] = r[2] * f[0] - r[0] * f[2]; u[2] = r[0] * f[1] - r[1] * f[0];
+    lens->model = model;
+    for (int c = 0; c < 3; c++) { lens->origin[c] = from[c]; lens->right[c] = (float)r[c]; lens->up[c] = (float)u[c]; lens->forward[c] = (float)f[c]; }
+    lens->_pad0 = lens->_pad1 = lens->_pad2 = lens->_pad3 = 0.0f;
 }

@@ -460,6 +460,34 @@ std::vector<float> HipRenderer::radiance(const std::vector<rt3_ray>& rays, const
     return out;
 }
 
+static rt3_params lens_params(const PathOptions& path, uint32_t width, uint32_t height) {
+    return rt3_params{ width, height, path.spp, path.max_depth, path.seed, path.flags & ~(uint32_t)RT3_FLAG_VARIANCE, 0.0f, path.t_min, path.tile_rows, 0, 1 };
+}
+
+std::vector<float> HipRenderer::render_lens(const rt3_lens& lens, uint32_t width, uint32_t height) const {
+    if (path.spp == 0) throw Fatal("a lens frame needs the path tracer (Mode X)");
+    const rt3_params p = lens_params(path, width, height);
+    std::vector<float> out(4 * (size_t)width * height);
+    if (rt3_render_lens(ctx[0], &lens, &p, 0, p.spp, out.data()) != 0) throw Fatal(rt3_last_error(ctx[0]));
+    return out;
+}
+
+std::vector<rt3_aov> HipRenderer::lens_aov(const rt3_lens& lens, uint32_t width, uint32_t height) const {
+    if (path.spp == 0) throw Fatal("a lens frame's AOVs need the path tracer (Mode X)");
+    const rt3_params p = lens_params(path, width, height);
+    std::vector<rt3_aov> out((size_t)width * height);
+    if (rt3_render_lens_aov(ctx[0], &lens, &p, out.data()) != 0) throw Fatal(rt3_last_error(ctx[0]));
+    return out;
+}
+
+std::vector<float> HipRenderer::denoise(uint32_t width, uint32_t height, const std::vector<float>& colour, const std::vector<rt3_aov>& guides,
+                                        const rt3_denoise_params& params) const {
+    if (colour.size() != 4 * (size_t)width * height || guides.size() != (size_t)width * height) throw Fatal("denoise: the frames' sizes differ from width x height");
+    std::vector<float> out(colour.size());
+    if (rt3_denoise(ctx[0], width, height, colour.data(), guides.data(), &params, out.data()) != 0) throw Fatal(rt3_last_error(ctx[0]));
+    return out;
+}
+
 rt3_stats HipRenderer::stats() const {
     rt3_stats s;
     if (rt3_get_stats(ctx[0], &s) != 0) throw Fatal(rt3_last_error(ctx[0]));

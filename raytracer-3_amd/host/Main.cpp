@@ -9,7 +9,8 @@
 // --frames, --orbit and --slide (a sequence, denoised temporally), --adaptive and --counts (--spp as a budget), --rays and --radiance
 // (path-traced radiance along rays read from a file), --env (an environment map from a PFM of six stacked cube faces),
 // --env-sampling (importance sampling of that map with shadow rays), --light-sampling (the same for the emissive primitives),
-// --display (the image written is the linear frame through exposure, a tone curve and a transfer function).
+// --display (the image written is the linear frame through exposure, a tone curve and a transfer function), --lens, --lens-fov and
+// --lens-extent (the frame of another lens model at the scene's camera position: equirectangular, fisheye, orthographic, cube).
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -54,6 +55,10 @@ struct Options {
     bool env_sampling = false;                                     // with --env: RT3_FLAG_ENV_SAMPLING
     bool light_sampling = false;                                   // Mode X: RT3_FLAG_LIGHT_SAMPLING
     bool display = false;                                          // Mode X: the image written is rt3_display of the linear (or the denoised) frame
+    uint32_t lens = 0;                                             // Mode X: RT3_LENS_* of the frame to render instead of the camera's (0: none)
+    float lens_fov = 180.0f;                                       // fisheye: the whole field of view across the shorter image side, in degrees
+    float lens_extent[2] = { 2.0f, 2.0f };                         // ortho: the window's width and height
+    bool have_lens_fov = false, have_lens_extent = false;
     rt3_display_params display_params{ RT3_DISPLAY_FILMIC, RT3_DISPLAY_SRGB, 0u, 102u, 51u, 1.0f, 0.18f, 4.0f };      // the defaults of DESIGN.md 4.22
 };
 
@@ -95,6 +100,11 @@ void print_usage(const char* exe) {
               << "\t   --display\tMode X: CURVE[,TRANSFER[,EXPOSURE]]: the image written is the linear frame (with a single-frame --denoise, the\n"
               << "\t\t\tdenoised one) through a display transform: CURVE clamp | reinhard | filmic, TRANSFER linear | gamma2 | srgb (default: srgb),\n"
               << "\t\t\tEXPOSURE a positive gain, or auto: from the frame's trimmed log-average luminance (default: 1).\n"
+              << "\t   --lens\tMode X: equirect | fisheye | ortho | cube: render the frame of that lens model (rt3_render_lens) at the scene's camera\n"
+              << "\t\t\tposition, looking where the camera looks, instead of the camera's; cube needs -H equal to 6 times -W (the layout --env reads).\n"
+              << "\t\t\t--hdr, --aov, --denoise and --display act on the lens frame. Not with --adaptive, --frames or --gpus above 1.\n"
+              << "\t   --lens-fov\tWith --lens fisheye: the field of view across the shorter image side, in degrees, above 0 up to 360 (default: 180).\n"
+              << "\t   --lens-extent\tWith --lens ortho: W,H: the width and height of the window the parallel rays start from (default: 2,2).\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
 }
 
@@ -138,7 +148,8 @@ int parse_cli(Options& opt, int argc, const char** argv) {
                            key == "--scene" || key == "--spp" || key == "--depth" || key == "--seed" || key == "--gpus" ||
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
                            key == "--slide" || key == "--adaptive" || key == "--counts" || key == "--regroup" ||
-                           key == "--rays" || key == "--radiance" || key == "--env" || key == "--display";
+                           key == "--rays" || key == "--radiance" || key == "--env" || key == "--display" || key == "--lens" || key == "--lens-fov" ||
+                           key == "--lens-extent";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -231,6 +242,32 @@ int parse_cli(Options& opt, int argc, const char** argv) {
             }
             opt.display = true;
         }
+        else if (key == "--lens") {
+            if (value == "equirect") opt.lens = RT3_LENS_EQUIRECT;
+            else if (value == "fisheye") opt.lens = RT3_LENS_FISHEYE;
+            else if (value == "ortho") opt.lens = RT3_LENS_ORTHO;
+            else if (value == "cube") opt.lens = RT3_LENS_CUBE;
+            else { std::cerr << "Unknown lens '" << value << "'" << std::endl; return -1; }
+        }
+        else if (key == "--lens-fov") {                              // degrees in (0, 360]
+            char* end = nullptr;
+            const double deg = std::strtod(value.c_str(), &end);
+            if (end == value.c_str() || *end != '\0' || !(deg > 0.0) || !(deg <= 360.0)) { std::cerr << "Invalid lens-fov '" << value << "'" << std::endl; return -1; }
+            opt.lens_fov = (float)deg; opt.have_lens_fov = true;
+        }
+        else if (key == "--lens-extent") {                           // W,H: two finite numbers above 0
+            const char* at = value.c_str();
+            bool ok = true;
+            for (int c = 0; c < 2 && ok; c++) {
+                char* end = nullptr;
+                const double v = std::strtod(at, &end);
+                ok = end != at && std::isfinite(v) && (float)v > 0.0f && std::isfinite((float)v) && *end == (c < 1 ? ',' : '\0');
+                opt.lens_extent[c] = (float)v;
+                at = end + 1;
+            }
+            if (!ok) { std::cerr << "Invalid lens-extent '" << value << "'" << std::endl; return -1; }
+            opt.have_lens_extent = true;
+        }
         else if (key == "--regroup") {
             if (!parse_u32(value, "regroup", "Regroup", &opt.regroup)) return -1;
             if (opt.regroup == 0) { std::cerr << "--regroup must be at least 1." << std::endl; return -1; }
@@ -294,6 +331,21 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         return -1;
     }
     if (opt.frames == 0) { std::cerr << "--frames must be at least 1." << std::endl; return -1; }
+    if ((opt.have_lens_fov || opt.have_lens_extent) && opt.lens == 0) {
+        std::cerr << "--lens-fov and --lens-extent need --lens." << std::endl;
+        return -1;
+    }
+    if (opt.lens != 0) {
+        if (opt.spp == 0) { std::cerr << "--lens needs the path tracer (Mode X): pass --spp." << std::endl; return -1; }
+        if (opt.adaptive) { std::cerr << "--lens is not available with --adaptive." << std::endl; return -1; }
+        if (opt.frames > 1) { std::cerr << "--lens renders one frame: it is not available with --frames." << std::endl; return -1; }
+        if (opt.gpus > 1) { std::cerr << "--lens renders on one device: it is not available with --gpus above 1." << std::endl; return -1; }
+        if (!opt.rays_path.empty()) { std::cerr << "--lens is not available with --rays and --radiance." << std::endl; return -1; }
+        if (opt.lens == RT3_LENS_CUBE && (uint64_t)opt.height != 6ull * opt.width) {
+            std::cerr << "--lens cube needs a frame of six stacked faces: -H must be 6 times -W." << std::endl;
+            return -1;
+        }
+    }
     if (mode_r && opt.frames > 1) {
         std::cerr << "--frames needs the path tracer (Mode X): pass --spp." << std::endl;
         return -1;
@@ -451,6 +503,44 @@ int main(int argc, const char** argv) {
             if (opt.env_sampling) path.flags |= RT3_FLAG_ENV_SAMPLING;
         }
         if (opt.light_sampling) path.flags |= RT3_FLAG_LIGHT_SAMPLING;
+        if (opt.lens != 0) {                                         // the frame of another lens model, at the camera's place
+            const uint32_t w = opt.width, h = opt.height;
+            const float origin[3] = { 0.0f, 0.0f, 0.0f }, ahead[3] = { 0.0f, 0.0f, -1.0f }, up[3] = { 0.0f, 1.0f, 0.0f };       // the reference camera
+            rt3_lens lens{};
+            if (la.on) rt3_lens_look_at(&lens, opt.lens, &la.from.x, &la.at.x, &la.vup.x);
+            else rt3_lens_look_at(&lens, opt.lens, origin, ahead, up);
+            lens.half_fov_turns = opt.lens_fov / 720.0f;
+            lens.half_extent[0] = 0.5f * opt.lens_extent[0]; lens.half_extent[1] = 0.5f * opt.lens_extent[1];
+            if (la.on) cam.look_at(w, h, la.from, la.at, la.vup, la.vfov, la.focus);      // (the camera only lends its frame buffer to the image)
+            path.lens_radius = 0.0f;
+            renderer.configure(path);
+            const std::vector<float> linear = renderer.render_lens(lens, w, h);
+            const rt3_stats st = renderer.stats();
+            std::cerr << "rendered a lens frame of " << w << "x" << h << " x " << path.spp << " spp in " << st.total_ms << " ms on device 0: " << st.ray_casts
+                      << " rays, " << st.launches << " launches\n";
+            const bool need_aov = !opt.aov_prefix.empty() || !opt.denoise_path.empty();
+            const std::vector<rt3_aov> aov = need_aov ? renderer.lens_aov(lens, w, h) : std::vector<rt3_aov>();
+            const rt3_denoise_params dp{ 5, 128, 4.0f, 1.0f };                       // the defaults of DESIGN.md 4.11
+            const std::vector<float> denoised = opt.denoise_path.empty() ? std::vector<float>() : renderer.denoise(w, h, linear, aov, dp);
+            // the image: --display's transform, or the one that reproduces the ordinary Mode-X pack (no curve, the scene's gamma)
+            const rt3_display_params pack{ RT3_DISPLAY_CLAMP, (path.flags & RT3_FLAG_GAMMA2) ? RT3_DISPLAY_GAMMA2 : RT3_DISPLAY_LINEAR, 0u, 102u, 51u, 1.0f, 0.18f, 4.0f };
+            renderer.display(cam, opt.display && !denoised.empty() ? denoised : linear, opt.display ? opt.display_params : pack);
+            if (opt.png) cam.get_frame().to_png(opt.output_path);
+            else cam.get_frame().to_ppm(opt.output_path);
+            if (!opt.hdr_path.empty() && rt3_frame_to_pfm(linear.data(), w, h, 3, 4, opt.hdr_path.c_str()) != 0) throw Fatal("Could not write '" + opt.hdr_path + "'");
+            if (!opt.aov_prefix.empty()) {
+                const float* base = reinterpret_cast<const float*>(aov.data());
+                const struct { const char* name; size_t offset; uint32_t channels; } planes[] = { { ".albedo.pfm", 0, 3 }, { ".normal.pfm", 4, 3 }, { ".depth.pfm", 7, 1 } };
+                for (const auto& pl : planes) {
+                    const std::string out = opt.aov_prefix + pl.name;
+                    if (rt3_frame_to_pfm(base + pl.offset, w, h, pl.channels, sizeof(rt3_aov) / sizeof(float), out.c_str()) != 0)
+                        throw Fatal("Could not write '" + out + "'");
+                }
+            }
+            if (!denoised.empty() && rt3_frame_to_pfm(denoised.data(), w, h, 3, 4, opt.denoise_path.c_str()) != 0)
+                throw Fatal("Could not write '" + opt.denoise_path + "'");
+            return 0;
+        }
         const uint32_t seed0 = path.seed;
         const bool temporal = opt.frames > 1 && !opt.denoise_path.empty();
         const rt3_temporal_params tp{ { 5, 128, 4.0f, 1.0f }, 0.2f, 0.2f, 2.0f, 0.9f };       // the defaults of DESIGN.md 4.11 and 4.12

@@ -79,6 +79,14 @@ public:
     // Mode X only: path-traced radiance along the caller's rays on device 0 (rt3_radiance), (r, g, b, 0) per ray: path.spp samples from sample_begin
     // on, path.max_depth, path.seed, path.t_min and the BLACK_BACKGROUND, ENV_SAMPLING and LIGHT_SAMPLING bits of path.flags; keys: empty (a ray's index is its key) or one per ray
     std::vector<float> radiance(const std::vector<rt3_ray>& rays, const std::vector<uint32_t>& keys = {}, uint32_t sample_begin = 0) const;
+    // Mode X only: a whole lens frame of width x height on device 0 (rt3_render_lens), linear (r, g, b, 0) per pixel: path.spp samples,
+    // path.max_depth, path.seed, path.t_min and the BLACK_BACKGROUND, ENV_SAMPLING and LIGHT_SAMPLING bits of path.flags; and its first-hit AOVs
+    // (rt3_render_lens_aov).  A cube lens's frame (width N, height 6 N) is the array set_environment takes.
+    std::vector<float> render_lens(const rt3_lens& lens, uint32_t width, uint32_t height) const;
+    std::vector<rt3_aov> lens_aov(const rt3_lens& lens, uint32_t width, uint32_t height) const;
+    // rt3_denoise on device 0 for frames the caller holds (a lens frame and its AOVs)
+    std::vector<float> denoise(uint32_t width, uint32_t height, const std::vector<float>& colour, const std::vector<rt3_aov>& guides,
+                               const rt3_denoise_params& params) const;
     size_t faces() const { return n_faces; }
     size_t spheres() const { return n_spheres; }
 

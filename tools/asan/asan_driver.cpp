@@ -219,6 +219,39 @@ void sphere_plans() {
     CHECK(nd <= 4 && centre[0] == 1.0f && centre[1] == 2.0f && centre[2] == 3.0f);
 }
 
+// rt3_debug_lens_ray / rt3_lens_look_at (csrc/rt3_lens_law.hpp): every model over a small frame into exact buffers — stratified, unstratified and
+// unjittered — unit directions, and the lenses the entry points refuse
+void lens_law() {
+    const float from[3] = { 0.3f, 1.1f, 2.0f }, at[3] = { -0.2f, 0.4f, -1.0f }, vup[3] = { 0.1f, 1.0f, 0.05f };
+    for (uint32_t model = RT3_LENS_EQUIRECT; model <= RT3_LENS_CUBE; model++) {
+        Exact<rt3_lens> lens(1);
+        std::memset(lens.p, 0, sizeof(rt3_lens));
+        rt3_lens_look_at(lens.p, model, from, at, vup);
+        lens.p->half_fov_turns = 0.5f;
+        lens.p->half_extent[0] = 2.0f; lens.p->half_extent[1] = 1.5f;
+        for (uint32_t spp : { 1u, 3u, 4u }) {
+            Exact<rt3_params> P(1);
+            *P.p = rt3_params{ 5u, model == RT3_LENS_CUBE ? 30u : 7u, spp, 1u, 9u, 0u, 0.0f, 0.001f, 8u, 0u, 1u };
+            Exact<rt3_ray> out(1);
+            for (uint32_t s = 0; s < spp; s++)
+                for (uint32_t y = 0; y < P.p->height; y++)
+                    for (uint32_t x = 0; x < P.p->width; x++) {
+                        CHECK(rt3_debug_lens_ray(lens.p, P.p, x, y, s, out.p) == 0);
+                        const float* d = out.p->direction;
+                        CHECK(std::fabs((double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2] - 1.0) <= 0x1p-20 && std::isinf(out.p->t_max));
+                    }
+            CHECK(rt3_debug_lens_ray(lens.p, P.p, P.p->width, 0, 0, out.p) == RT3_E_ARG && rt3_debug_lens_ray(lens.p, P.p, 0, 0, spp, out.p) == RT3_E_ARG);
+            lens.p->up[0] += 0.5f;
+            CHECK(rt3_debug_lens_ray(lens.p, P.p, 0, 0, 0, out.p) == RT3_E_ARG);
+            lens.p->up[0] -= 0.5f;
+        }
+    }
+    rt3_params P = { 4, 4, 1, 1, 1, 0, 0.0f, 0.001f, 8, 0, 1 };
+    rt3_ray out;
+    rt3_lens bad{};
+    CHECK(rt3_debug_lens_ray(&bad, &P, 0, 0, 0, &out) == RT3_E_ARG && rt3_debug_lens_ray(nullptr, &P, 0, 0, 0, &out) == RT3_E_ARG);
+}
+
 void oracle_loops() {
     // Mode R: a tessellated sphere + a triangle, every row (the caller of the reference loop chooses the rows)
     const float center[3] = { -0.5f, 0.0f, -4.0f }, blue[3] = { 0, 0, 1 }, red[3] = { 1, 0, 0 };
@@ -279,6 +312,7 @@ int main(int argc, const char** argv) {
         cameras_and_frames();
         scenes();
         sphere_plans();
+        lens_law();
         oracle_loops();
         std::printf("rt3_asan selftest: %s (%d failed checks)\n", failures ? "FAILED" : "ok", failures);
         return failures ? 1 : 0;

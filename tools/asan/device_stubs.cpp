@@ -72,6 +72,12 @@ int rt3_intersect_device(rt3_ctx*, const void*, uint32_t, float, void*, void*) {
 int rt3_occluded_device(rt3_ctx*, const void*, uint32_t, float, void*, void*) { return RT3_E_DEVICE; }
 int rt3_radiance(rt3_ctx*, const rt3_ray*, const uint32_t*, uint32_t, const rt3_radiance_params*, float*) { return RT3_E_DEVICE; }
 int rt3_radiance_device(rt3_ctx*, const void*, const void*, uint32_t, const rt3_radiance_params*, void*, void*) { return RT3_E_DEVICE; }
+int rt3_lens_rays(rt3_ctx*, const rt3_lens*, const rt3_params*, uint32_t, uint32_t, rt3_ray*) { return RT3_E_DEVICE; }     // (rt3_debug_lens_ray / rt3_lens_look_at are host code)
+int rt3_lens_rays_device(rt3_ctx*, const rt3_lens*, const rt3_params*, uint32_t, uint32_t, void*, void*) { return RT3_E_DEVICE; }
+int rt3_render_lens(rt3_ctx*, const rt3_lens*, const rt3_params*, uint32_t, uint32_t, float*) { return RT3_E_DEVICE; }
+int rt3_render_lens_device(rt3_ctx*, const rt3_lens*, const rt3_params*, uint32_t, uint32_t, void*, void*) { return RT3_E_DEVICE; }
+int rt3_render_lens_aov(rt3_ctx*, const rt3_lens*, const rt3_params*, rt3_aov*) { return RT3_E_DEVICE; }
+int rt3_render_lens_aov_device(rt3_ctx*, const rt3_lens*, const rt3_params*, void*, void*) { return RT3_E_DEVICE; }
 int rt3_camera_rays(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t, uint32_t, rt3_ray*) { return RT3_E_DEVICE; }
 int rt3_camera_rays_device(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t, uint32_t, void*, void*) { return RT3_E_DEVICE; }
 int rt3_render_aov(rt3_ctx*, const rt3_camera*, const rt3_params*, rt3_aov*) { return RT3_E_DEVICE; }
