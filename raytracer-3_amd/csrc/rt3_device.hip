@@ -170,7 +170,7 @@ struct rt3_ctx {
     // the display transform's auto-exposure (rt3_display*): hist[512], dark, n and the gain's bits, allocated by the first call with the flag and
     // zeroed at the start of each such call; display_auto: there has been one (rt3_debug_display_state)
     DevBuf<uint32_t> d_display; bool display_auto = false;
-    // The host forms' inputs and results on the device, each carved out at float4 offsets.  Shared by all of them: each one ends in
+    // The host forms' inputs and results on the device, each carved out at a float4 offset by staged().  Shared by all of them: each one ends in
     // hipStreamSynchronize(ctx->stream), and no device form touches it.
     DevBuf<float4> stage;
     DevBuf<uint32_t> d_work;                                        // [0] work counter
@@ -503,12 +503,12 @@ int blocks_per_cu(rt3_ctx* ctx, const void* kernel, int block, size_t lds, int* 
 
 bool same_bytes(const void* a, const void* b, size_t n) { return std::memcmp(a, b, n) == 0; }
 
-int check_params(rt3_ctx* ctx, const rt3_params* p) {
+int check_params(rt3_ctx* ctx, const rt3_params* p, uint32_t min_edge = 2) {
     if (!p) return fail(ctx, RT3_E_ARG, "params is NULL");
     if (!(p->t_min >= 0.0f) || !(p->t_min < __builtin_inff())) return fail(ctx, RT3_E_ARG, "t_min must be finite and >= 0");
     if (p->flags & ~(RT3_FLAG_GAMMA2 | RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_REFERENCE_PRIMARY | RT3_FLAG_VARIANCE | RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING))
         return fail(ctx, RT3_E_ARG, "unknown bits in flags");
-    if (p->width < 2 || p->height < 2) return fail(ctx, RT3_E_ARG, "width and height must be >= 2");
+    if (p->width < min_edge || p->height < min_edge) return fail(ctx, RT3_E_ARG, "width and height must be >= " + std::to_string(min_edge));
     if ((uint64_t)p->width * p->height > 0x7FFFFFFFull) return fail(ctx, RT3_E_ARG, "frame too large");
     if (p->spp < 1 || p->max_depth < 1) return fail(ctx, RT3_E_ARG, "spp and max_depth must be >= 1");
     if (p->tile_count > 1 && (p->tile_rows == 0 || p->tile_index >= p->tile_count))
@@ -809,42 +809,33 @@ uint32_t trace_grid(const rt3_ctx* ctx, const TracePlan& T, uint32_t total) {
     const uint32_t want_blocks = (total + kWorkChunk * waves_per_block - 1) / (kWorkChunk * waves_per_block);
     return std::max(1u, std::min<uint32_t>((uint32_t)(ctx->num_cu * T.per_cu), want_blocks));
 }
+// The launch of T's kernel — single, tiled or plain — with the argument struct E of the forms that share F's signatures.
+template <Form F, class Args>
+void launch_as(const TracePlan& T, const Args& E, uint32_t grid, hipStream_t stream) {
+    static_assert(std::is_same<Args, trace_args<F>>::value, "the argument struct of the form the kernel pointer is cast back to");
+    if (T.single) hipLaunchKernelGGL(reinterpret_cast<SingleKernelOf<F>>(T.single), dim3(grid), dim3(kMB), T.lds, stream, E, T.frag_a, T.mfma_blocks);
+    else if (T.tiled) hipLaunchKernelGGL(reinterpret_cast<TiledKernelOf<F>>(T.tiled), dim3(grid), dim3(kTB), T.lds, stream, E, T.frag_a, T.frag_b);
+    else hipLaunchKernelGGL(reinterpret_cast<TraceKernelOf<F>>(T.plain), dim3(grid), dim3(kBlock), T.lds, stream, E);
+}
 void launch_trace(const TracePlan& T, const TraceArgs& A, uint32_t grid, hipStream_t stream) {
+    const auto with_map = [&](EnvTraceArgs& E) { static_cast<TraceArgs&>(E) = A; E.env = T.env; E.env_n = T.env_n; E.env_pad = 0u; };
     if (T.lt_n != 0) {                                              // a light sampling form: the map (or none) and the emitters' table behind the arguments
         LightTraceArgs E;
-        static_cast<TraceArgs&>(E) = A;
-        E.env = T.env; E.env_n = T.env_n; E.env_pad = 0u;
+        with_map(E);
         E.lt_q = T.lt_q; E.lt_cdf = (const uint64_t*)T.lt_cdf; E.lt_sph_cr = T.lt_sph_cr; E.lt_n = T.lt_n; E.lt_pad = 0u;
-        constexpr Form F = Form::RenderLight;                       // (the two light sampling forms share their signatures)
-        if (T.single) hipLaunchKernelGGL(reinterpret_cast<SingleKernelOf<F>>(T.single), dim3(grid), dim3(kMB), T.lds, stream, E, T.frag_a, T.mfma_blocks);
-        else if (T.tiled) hipLaunchKernelGGL(reinterpret_cast<TiledKernelOf<F>>(T.tiled), dim3(grid), dim3(kTB), T.lds, stream, E, T.frag_a, T.frag_b);
-        else hipLaunchKernelGGL(reinterpret_cast<TraceKernelOf<F>>(T.plain), dim3(grid), dim3(kBlock), T.lds, stream, E);
-        return;
-    }
-    if (T.nee_m != 0) {                                             // a sampling form: the map and its table behind the arguments
+        launch_as<Form::RenderLight>(T, E, grid, stream);           // (the two light sampling forms share their signatures)
+    } else if (T.nee_m != 0) {                                      // a sampling form: the map and its table behind the arguments
         NeeTraceArgs E;
-        static_cast<TraceArgs&>(E) = A;
-        E.env = T.env; E.env_n = T.env_n; E.env_pad = 0u;
+        with_map(E);
         E.nee_q = T.nee_q; E.nee_cdf = (const uint64_t*)T.nee_cdf; E.nee_m = T.nee_m; E.nee_cells = 6u * T.nee_m * T.nee_m;
-        constexpr Form F = Form::RenderEnvNee;                      // (the two sampling forms share their signatures)
-        if (T.single) hipLaunchKernelGGL(reinterpret_cast<SingleKernelOf<F>>(T.single), dim3(grid), dim3(kMB), T.lds, stream, E, T.frag_a, T.mfma_blocks);
-        else if (T.tiled) hipLaunchKernelGGL(reinterpret_cast<TiledKernelOf<F>>(T.tiled), dim3(grid), dim3(kTB), T.lds, stream, E, T.frag_a, T.frag_b);
-        else hipLaunchKernelGGL(reinterpret_cast<TraceKernelOf<F>>(T.plain), dim3(grid), dim3(kBlock), T.lds, stream, E);
-        return;
-    }
-    if (T.env_n != 0) {                                             // an environment form: the same launch with the map behind the arguments
+        launch_as<Form::RenderEnvNee>(T, E, grid, stream);          // (the two sampling forms share their signatures)
+    } else if (T.env_n != 0) {                                      // an environment form: the same launch with the map behind the arguments
         EnvTraceArgs E;
-        static_cast<TraceArgs&>(E) = A;
-        E.env = T.env; E.env_n = T.env_n; E.env_pad = 0u;
-        constexpr Form F = Form::RenderEnv;                         // (the three environment forms share their signatures)
-        if (T.single) hipLaunchKernelGGL(reinterpret_cast<SingleKernelOf<F>>(T.single), dim3(grid), dim3(kMB), T.lds, stream, E, T.frag_a, T.mfma_blocks);
-        else if (T.tiled) hipLaunchKernelGGL(reinterpret_cast<TiledKernelOf<F>>(T.tiled), dim3(grid), dim3(kTB), T.lds, stream, E, T.frag_a, T.frag_b);
-        else hipLaunchKernelGGL(reinterpret_cast<TraceKernelOf<F>>(T.plain), dim3(grid), dim3(kBlock), T.lds, stream, E);
-        return;
+        with_map(E);
+        launch_as<Form::RenderEnv>(T, E, grid, stream);             // (the three environment forms share their signatures)
+    } else {
+        launch_as<Form::Render>(T, A, grid, stream);
     }
-    if (T.single) hipLaunchKernelGGL(T.single, dim3(grid), dim3(kMB), T.lds, stream, A, T.frag_a, T.mfma_blocks);
-    else if (T.tiled) hipLaunchKernelGGL(T.tiled, dim3(grid), dim3(kTB), T.lds, stream, A, T.frag_a, T.frag_b);
-    else hipLaunchKernelGGL(T.plain, dim3(grid), dim3(kBlock), T.lds, stream, A);
 }
 
 // One timed trace launch of a call: the kernel of T over the n work items A describes (a batch of samples; DESIGN.md 4.9: the rays A.q_rays points to).
@@ -879,50 +870,89 @@ int leave(rt3_ctx* ctx, hipStream_t stream) {
     return 0;
 }
 
-// The sampling table of the map the context holds, built once per map by the first call that carries RT3_FLAG_ENV_SAMPLING: three launches
-// queued on that call's stream behind enter() — the cells' weights and their maximum, the quantisation, the prefix sums (integers: order-free) — and no
-// host wait: the kernels read the total from the last prefix sum.  A later call on another stream finds it behind the event chain, as it finds an update.
-int ensure_env_table(rt3_ctx* ctx, hipStream_t stream) {
-    if (ctx->env_table) return 0;
-    const uint32_t m = rt3env::cells_per_edge(ctx->env_n), cells = 6u * m * m;
-    size_t temp = 0;
+// The round trip of a host form — the variant of an entry point that takes host pointers — through ctx->stage.  A StageSeg is one input or one result,
+// its host pointer and its bytes: a NULL pointer is an absent optional segment, an empty one (a shard that owns no pixel) is never copied.  staged() sizes
+// the buffer ONCE for all of them (DevBuf::ensure frees what it replaces: no segment can be added behind the first copy), queues the inputs' copies on
+// ctx->stream, calls device_form(d) — d[i]: segment i's 16-byte-aligned address, NULL for an absent one — then queues the results' copies and waits.
+struct StageSeg { const void* src; void* dst; size_t bytes; bool present; };
+StageSeg stage_in(const void* host, size_t bytes) { return { host, nullptr, bytes, host != nullptr }; }
+StageSeg stage_out(void* host, size_t bytes) { return { nullptr, host, bytes, host != nullptr }; }
+template <size_t N, class DeviceForm>
+int staged(rt3_ctx* ctx, const StageSeg (&seg)[N], DeviceForm device_form) {
+    RT3_HIP(hipSetDevice(ctx->device));
+    size_t first[N], quads = 0;
+    for (size_t i = 0; i < N; i++) { first[i] = quads; if (seg[i].present) quads += std::max<size_t>((seg[i].bytes + 15) / 16, 1); }
     int rc;
-    RT3_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, temp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)cells, stream));
-    if ((rc = ctx->d_env_q.ensure(ctx, cells)) || (rc = ctx->d_env_cdf.ensure(ctx, cells)) || (rc = ctx->d_env_wmax.ensure(ctx, 1)) ||
-        (rc = ctx->d_env_temp.ensure(ctx, std::max<size_t>(temp, 1))))
-        return rc;
-    const dim3 grid((cells + kBlock - 1) / kBlock), blk(kBlock);
-    RT3_HIP(hipMemsetAsync(ctx->d_env_wmax, 0, 4, stream));
-    hipLaunchKernelGGL(k_env_cell_weights, grid, blk, 0, stream, (const float4*)ctx->d_env, ctx->env_n, m, cells, ctx->d_env_q.get(), ctx->d_env_wmax.get());
-    hipLaunchKernelGGL(k_env_quantise, grid, blk, 0, stream, cells, (const uint32_t*)ctx->d_env_wmax, ctx->d_env_q.get(), ctx->d_env_cdf.get());
-    RT3_HIP(hipGetLastError());
-    RT3_HIP(hipcub::DeviceScan::InclusiveSum(ctx->d_env_temp.get(), temp, (const unsigned long long*)ctx->d_env_cdf.get(), ctx->d_env_cdf.get(), (int)cells, stream));
-    ctx->env_m = m;
-    ctx->env_table = true;
+    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(quads, 1)))) return rc;
+    void* d[N];
+    for (size_t i = 0; i < N; i++) {
+        d[i] = seg[i].present ? ctx->stage.get() + first[i] : nullptr;
+        if (seg[i].src && seg[i].bytes) RT3_HIP(hipMemcpyAsync(d[i], seg[i].src, seg[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if ((rc = device_form(d))) return rc;
+    for (size_t i = 0; i < N; i++)
+        if (seg[i].dst && seg[i].bytes) RT3_HIP(hipMemcpyAsync(seg[i].dst, d[i], seg[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RT3_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
-
-// The emitters' sampling table of the scene the context holds, built once per scene by the first call that carries RT3_FLAG_LIGHT_SAMPLING:
-// the same three launches as ensure_env_table, over one entry per primitive, queued on that call's stream behind enter(), and no host wait.
-int ensure_light_table(rt3_ctx* ctx, hipStream_t stream) {
-    if (ctx->light_table) return 0;
-    const uint32_t n = ctx->n_faces + ctx->n_sph;                   // (check_scene: >= 1, and far below 2^31)
+// Samples per batch: as many of `count` as the sample storage cap holds at `bytes` per item and sample, and as keep the item index of a batch over
+// n items below 2^31 - 2^16.  0: not even one sample fits the index.
+uint32_t sample_batch(const rt3_ctx* ctx, uint32_t count, uint32_t n, size_t bytes) {
+    const uint64_t batch = std::min<uint64_t>(count, std::max<uint64_t>(1, ctx->rad_cap_bytes / ((uint64_t)n * bytes)));
+    return (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / n);
+}
+// The accumulation is valid again: what a later rt3_render_path_range must match to continue it, and what rt3_accum_* read.
+void commit_accumulation(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t done, uint32_t npix, bool adaptive) {
+    ctx->acc_valid = true; ctx->acc_adaptive = adaptive; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = done; ctx->acc_npix = npix;
+}
+// One sampling table of n entries: three launches queued on the calling entry point's stream behind enter() — the two of launches(grid, block): the
+// entries' weights into q and their maximum into d_env_wmax, then q and cdf quantised from both; and the prefix sums of cdf in place (integers: order-free) —
+// with no host wait: the kernels read the total from the last prefix sum.  d_env_wmax and d_env_temp (the scan's scratch) are shared by both tables: the
+// builds are queued behind the event chain, where a later call on another stream finds the table as it finds an update.
+template <class Launches>
+int build_sampling_table(rt3_ctx* ctx, uint32_t n, DevBuf<uint32_t>& q, DevBuf<unsigned long long>& cdf, hipStream_t stream, Launches launches) {
     size_t temp = 0;
     int rc;
     RT3_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, temp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n, stream));
-    if ((rc = ctx->d_light_q.ensure(ctx, n)) || (rc = ctx->d_light_cdf.ensure(ctx, n)) || (rc = ctx->d_env_wmax.ensure(ctx, 1)) ||
-        (rc = ctx->d_env_temp.ensure(ctx, std::max<size_t>(temp, 1))))
+    if ((rc = q.ensure(ctx, n)) || (rc = cdf.ensure(ctx, n)) || (rc = ctx->d_env_wmax.ensure(ctx, 1)) || (rc = ctx->d_env_temp.ensure(ctx, std::max<size_t>(temp, 1))))
         return rc;
-    const dim3 grid((n + kBlock - 1) / kBlock), blk(kBlock);
     RT3_HIP(hipMemsetAsync(ctx->d_env_wmax, 0, 4, stream));
-    hipLaunchKernelGGL(k_light_weights, grid, blk, 0, stream, (const float4*)ctx->d_tri, (const float4*)ctx->d_tri_mat, (const uint32_t*)ctx->d_tri_kind, ctx->n_faces,
-                       (const float4*)ctx->d_sph_cr, (const float4*)ctx->d_sph_mat, (const uint32_t*)ctx->d_sph_kind, ctx->n_sph, ctx->d_light_q.get(),
-                       ctx->d_env_wmax.get());
-    hipLaunchKernelGGL(k_light_quantise, grid, blk, 0, stream, n, (const uint32_t*)ctx->d_env_wmax, ctx->d_light_q.get(), ctx->d_light_cdf.get());
+    launches(dim3((n + kBlock - 1) / kBlock), dim3(kBlock));
     RT3_HIP(hipGetLastError());
-    RT3_HIP(hipcub::DeviceScan::InclusiveSum(ctx->d_env_temp.get(), temp, (const unsigned long long*)ctx->d_light_cdf.get(), ctx->d_light_cdf.get(), (int)n, stream));
-    ctx->light_table = true;
+    RT3_HIP(hipcub::DeviceScan::InclusiveSum(ctx->d_env_temp.get(), temp, (const unsigned long long*)cdf.get(), cdf.get(), (int)n, stream));
     return 0;
+}
+// The sampling table of the map the context holds, built once per map by the first call that carries RT3_FLAG_ENV_SAMPLING.
+int ensure_env_table(rt3_ctx* ctx, hipStream_t stream) {
+    if (ctx->env_table) return 0;
+    const uint32_t m = rt3env::cells_per_edge(ctx->env_n), cells = 6u * m * m;
+    const int rc = build_sampling_table(ctx, cells, ctx->d_env_q, ctx->d_env_cdf, stream, [&](dim3 grid, dim3 blk) {
+        hipLaunchKernelGGL(k_env_cell_weights, grid, blk, 0, stream, (const float4*)ctx->d_env, ctx->env_n, m, cells, ctx->d_env_q.get(), ctx->d_env_wmax.get());
+        hipLaunchKernelGGL(k_env_quantise, grid, blk, 0, stream, cells, (const uint32_t*)ctx->d_env_wmax, ctx->d_env_q.get(), ctx->d_env_cdf.get());
+    });
+    if (!rc) { ctx->env_m = m; ctx->env_table = true; }
+    return rc;
+}
+// The emitters' table of the scene the context holds, one entry per primitive, built by the first call with RT3_FLAG_LIGHT_SAMPLING.
+int ensure_light_table(rt3_ctx* ctx, hipStream_t stream) {
+    if (ctx->light_table) return 0;
+    const uint32_t n = ctx->n_faces + ctx->n_sph;                   // (check_scene: >= 1, and far below 2^31)
+    const int rc = build_sampling_table(ctx, n, ctx->d_light_q, ctx->d_light_cdf, stream, [&](dim3 grid, dim3 blk) {
+        hipLaunchKernelGGL(k_light_weights, grid, blk, 0, stream, (const float4*)ctx->d_tri, (const float4*)ctx->d_tri_mat, (const uint32_t*)ctx->d_tri_kind, ctx->n_faces,
+                           (const float4*)ctx->d_sph_cr, (const float4*)ctx->d_sph_mat, (const uint32_t*)ctx->d_sph_kind, ctx->n_sph, ctx->d_light_q.get(),
+                           ctx->d_env_wmax.get());
+        hipLaunchKernelGGL(k_light_quantise, grid, blk, 0, stream, n, (const uint32_t*)ctx->d_env_wmax, ctx->d_light_q.get(), ctx->d_light_cdf.get());
+    });
+    if (!rc) ctx->light_table = true;
+    return rc;
+}
+// plan_trace for a call whose flags may carry RT3_FLAG_ENV_SAMPLING or RT3_FLAG_LIGHT_SAMPLING: the tables those flags need first, queued on `stream`.
+int plan_sampled_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, uint32_t flags, hipStream_t stream, TracePlan& T) {
+    const bool nee = (flags & RT3_FLAG_ENV_SAMPLING) != 0, light = (flags & RT3_FLAG_LIGHT_SAMPLING) != 0;
+    int rc;
+    if (nee && (rc = ensure_env_table(ctx, stream))) return rc;
+    if (light && (rc = ensure_light_table(ctx, stream))) return rc;
+    return plan_trace(ctx, A, form, ref_brute, T, nee, light);
 }
 
 // The calls rt3_get_stats reports on (Mode-X renders, queries, AOVs) issue their launches between these two; each clears ctx->rendered before
@@ -1228,12 +1258,8 @@ int rt3_update_spheres(rt3_ctx* ctx, const float* center_radius, uint32_t n) {
     if (rc) return rc;
     for (uint32_t i = 0; i < n; i++)                                // rt3_set_spheres' check; the scene is untouched
         if (!(center_radius[4 * (size_t)i + 3] > 0.0f)) return fail(ctx, RT3_E_ARG, "sphere " + std::to_string(i) + " has a non-positive radius");
-    RT3_HIP(hipSetDevice(ctx->device));
-    if ((rc = ctx->stage.ensure(ctx, n))) return rc;
-    RT3_HIP(hipMemcpyAsync(ctx->stage, center_radius, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = rt3_update_spheres_device(ctx, ctx->stage.get(), n, ctx->stream))) return rc;
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_in(center_radius, (size_t)n * sizeof(float4)) },
+                  [&](void* const* d) { return rt3_update_spheres_device(ctx, d[0], n, ctx->stream); });
 }
 
 // The launches of a mesh update, after the new vertices (and faces) have been queued into d_verts / d_gfaces on `stream`.
@@ -1262,8 +1288,8 @@ static int update_mesh_checks(rt3_ctx* ctx, const void* vertices, uint32_t n_ver
     if (n_vertices != ctx->d_verts.size()) return fail(ctx, RT3_E_ARG, "n_vertices must equal the vertex count of the merged entity buffers");
     return 0;
 }
-// clear_error: the host form reads the error word itself; the device form leaves it to the next rt3_synchronize.
-static int update_mesh_issue(rt3_ctx* ctx, const void* d_faces, const void* d_verts, void* stream_, bool clear_error) {
+// host_err: the host form reads the error word itself, behind the update; the device form (NULL) leaves it to the next rt3_synchronize.
+static int update_mesh_issue(rt3_ctx* ctx, const void* d_faces, const void* d_verts, void* stream_, uint32_t* host_err) {
     hipStream_t stream;
     int rc;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
@@ -1271,7 +1297,7 @@ static int update_mesh_issue(rt3_ctx* ctx, const void* d_faces, const void* d_ve
     ctx->n_faces = 0;                                               // (no mesh until everything below has been issued)
     ctx->mesh_in_sync = false;
     ctx->light_table = false;
-    if (clear_error || !ctx->update_error_pending) RT3_HIP(hipMemsetAsync(ctx->d_error, 0, 4, stream));
+    if (host_err || !ctx->update_error_pending) RT3_HIP(hipMemsetAsync(ctx->d_error, 0, 4, stream));
     RT3_HIP(hipMemcpyAsync(ctx->d_verts, d_verts, ctx->d_verts.size() * sizeof(float4), hipMemcpyDeviceToDevice, stream));
     if (d_faces) RT3_HIP(hipMemcpyAsync(ctx->d_gfaces, d_faces, (size_t)n * sizeof(rt3_gface), hipMemcpyDeviceToDevice, stream));
     ctx->n_faces = n;                                               // (refit_mesh reads the count; taken back below if it fails)
@@ -1279,6 +1305,7 @@ static int update_mesh_issue(rt3_ctx* ctx, const void* d_faces, const void* d_ve
     if (!rc) rc = leave(ctx, stream);
     if (rc) { ctx->n_faces = 0; return rc; }
     ctx->mesh_in_sync = true;
+    if (host_err) RT3_HIP(hipMemcpyAsync(host_err, ctx->d_error, 4, hipMemcpyDeviceToHost, stream));
     return 0;
 }
 
@@ -1287,7 +1314,7 @@ int rt3_update_mesh_device(rt3_ctx* ctx, const void* d_faces, const void* d_vert
     int rc = update_mesh_checks(ctx, d_vertices, n_vertices);
     if (rc) return rc;
     if (((uintptr_t)d_faces | (uintptr_t)d_vertices) % 16u != 0) return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
-    if ((rc = update_mesh_issue(ctx, d_faces, d_vertices, stream_, false))) return rc;
+    if ((rc = update_mesh_issue(ctx, d_faces, d_vertices, stream_, nullptr))) return rc;
     if (d_faces) ctx->update_error_pending = true;
     return 0;
 }
@@ -1296,17 +1323,10 @@ int rt3_update_mesh(rt3_ctx* ctx, const rt3_gface* faces, const float* vertices,
     if (!ctx) return RT3_E_ARG;
     int rc = update_mesh_checks(ctx, vertices, n_vertices);
     if (rc) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
-    const size_t nf = faces ? ctx->n_faces : 0;
-    if ((rc = ctx->stage.ensure(ctx, (size_t)n_vertices + 3 * nf))) return rc;
-    float4* const dv = ctx->stage;
-    float4* const df = dv + n_vertices;
-    RT3_HIP(hipMemcpyAsync(dv, vertices, (size_t)n_vertices * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    if (faces) RT3_HIP(hipMemcpyAsync(df, faces, nf * sizeof(rt3_gface), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = update_mesh_issue(ctx, faces ? df : nullptr, dv, ctx->stream, true))) return rc;
     uint32_t err = 0;
-    RT3_HIP(hipMemcpyAsync(&err, ctx->d_error, 4, hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    rc = staged(ctx, { stage_in(vertices, (size_t)n_vertices * sizeof(float4)), stage_in(faces, (size_t)ctx->n_faces * sizeof(rt3_gface)) },
+                [&](void* const* d) { return update_mesh_issue(ctx, d[1], d[0], ctx->stream, &err); });
+    if (rc) return rc;
     ctx->update_error_pending = false;
     if (err) {                                                      // as after rt3_set_mesh with such a face: no mesh
         ctx->n_faces = 0; ctx->mesh_in_sync = false;
@@ -1775,14 +1795,13 @@ int rt3_render_device(rt3_ctx* ctx, const rt3_camera* cam, uint32_t width, uint3
     if (!ctx) return RT3_E_ARG;
     if (!cam || !d_out) return fail(ctx, RT3_E_ARG, "cam / d_out_pixels is NULL");
     if (width < 2 || height < 2 || (uint64_t)width * height > 0x7FFFFFFFull) return fail(ctx, RT3_E_ARG, "bad frame size");
-    RT3_HIP(hipSetDevice(ctx->device));
-    const hipStream_t stream = stream_of(ctx, stream_);            // (Mode R's buffers are the caller's; the scene's are not: an update may be in flight)
-    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(stream, ctx->ev_acc, 0));
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;            // (Mode R's buffers are the caller's; the scene's are not: an update may be in flight)
     ctx->rendered = false;                                          // stats are valid again once every launch below has been issued
     ctx->ev_used = 0;
     hipEvent_t a, b;
-    int rc = take_event_pair(ctx, &a, &b);
-    if (rc) return rc;
+    if ((rc = take_event_pair(ctx, &a, &b))) return rc;
     const uint32_t npix = width * height;
     // k_mode_r_mfma / k_mode_r_fast need n.o == 0 exactly (camera at the origin, as Camera::update always builds it) and finite rays;
     // any other camera takes the plain brute-force kernel, which reproduces the reference for every input.
@@ -1821,14 +1840,26 @@ int rt3_render(rt3_ctx* ctx, const rt3_camera* cam, uint32_t width, uint32_t hei
     if (!ctx) return RT3_E_ARG;
     if (!out_pixels) return fail(ctx, RT3_E_ARG, "out_pixels is NULL");
     if (width < 2 || height < 2 || (uint64_t)width * height > 0x7FFFFFFFull) return fail(ctx, RT3_E_ARG, "bad frame size");
-    RT3_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)width * height;
-    int rc = ctx->stage.ensure(ctx, (npix + 3) / 4);
-    if (rc) return rc;
-    uint32_t* const d_out = (uint32_t*)ctx->stage.get();
-    if ((rc = rt3_render_device(ctx, cam, width, height, d_out, ctx->stream))) return rc;
-    RT3_HIP(hipMemcpyAsync(out_pixels, d_out, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
+    return staged(ctx, { stage_out(out_pixels, (size_t)width * height * 4) },
+                  [&](void* const* d) { return rt3_render_device(ctx, cam, width, height, d[0], ctx->stream); });
+}
+
+// Samples [s_begin, s_begin + s_count) of B's n_items items (every owned pixel, or the list `active`: DESIGN.md 4.15), at most `per` per batch: the trace, then the sums.
+static int trace_and_sum(rt3_ctx* ctx, const TracePlan& P, TraceArgs& B, uint32_t n_items, const uint32_t* active, bool var, uint32_t s_begin,
+                         uint32_t s_count, uint32_t per, hipStream_t stream) {
+    const dim3 ag((n_items + kBlock - 1) / kBlock), ab(kBlock);
+    for (uint32_t s0 = s_begin; s0 < s_begin + s_count; s0 += per) {
+        const uint32_t ns = std::min(per, s_begin + s_count - s0);
+        B.s0 = s0;
+        B.total = n_items * ns;
+        const int rc = issue_trace(ctx, B, P, B.total, stream);
+        if (rc) return rc;
+        if (active) hipLaunchKernelGGL(k_accumulate_list<true>, ag, ab, 0, stream, ctx->d_rad, active, n_items, ctx->d_accum, ctx->d_accum_sq,
+                                       ctx->d_counts, ns, s0 + ns);
+        else if (var) hipLaunchKernelGGL(k_accumulate<true>, ag, ab, 0, stream, ctx->d_rad, ctx->d_accum, ctx->d_accum_sq, n_items, ns, s0 == 0 ? 1 : 0);
+        else hipLaunchKernelGGL(k_accumulate<false>, ag, ab, 0, stream, ctx->d_rad, ctx->d_accum, (float4*)nullptr, n_items, ns, s0 == 0 ? 1 : 0);
+        RT3_HIP(hipGetLastError());
+    }
     return 0;
 }
 
@@ -1842,7 +1873,6 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     if (sample_count == 0 || (uint64_t)sample_begin + sample_count > p->spp) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
     if ((rc = check_scene(ctx))) return rc;
     const bool ref = (p->flags & RT3_FLAG_REFERENCE_PRIMARY) != 0, var = (p->flags & RT3_FLAG_VARIANCE) != 0;
-    const bool nee = (p->flags & RT3_FLAG_ENV_SAMPLING) != 0, light = (p->flags & RT3_FLAG_LIGHT_SAMPLING) != 0;
     if ((rc = check_env_sampling(ctx, p->flags))) return rc;       // (before the older refusals of RT3_FLAG_REFERENCE_PRIMARY: the flag's own answer comes first)
     if (ref && ctx->n_sph != 0) return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY needs a triangle-only scene");
     if (ref && ctx->env_n != 0)
@@ -1850,8 +1880,7 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
 
-    const uint32_t rows = rt3_rows_owned(p);
-    const uint32_t npix = rows * p->width;
+    const uint32_t npix = rt3_rows_owned(p) * p->width;
     if (sample_begin != 0) {                                        // a continuation: of this very accumulation?
         if (ctx->acc_valid && ctx->acc_adaptive)
             return fail(ctx, RT3_E_STATE, "the accumulation held by this context is an adaptive one: it cannot be continued (start with sample_begin = 0)");
@@ -1865,14 +1894,10 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     ctx->acc_adaptive = false;
     if (npix == 0) {
         if ((rc = begin_timed(ctx, stream)) || (rc = end_timed(ctx, stream, 0, nullptr))) return rc;
-        ctx->acc_valid = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = sample_begin + sample_count; ctx->acc_npix = 0;
+        commit_accumulation(ctx, cam, p, sample_begin + sample_count, 0, false);
         return 0;
     }
-
-    // batch size: per-sample storage of 12 B per (pixel, sample), capped
-    uint64_t per_spp = (uint64_t)npix * sizeof(Rgb);
-    uint32_t batch = (uint32_t)std::min<uint64_t>(sample_count, std::max<uint64_t>(1, ctx->rad_cap_bytes / per_spp));
-    batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / npix);
+    const uint32_t batch = sample_batch(ctx, sample_count, npix, sizeof(Rgb));      // 12 B per (pixel, sample)
     if (batch == 0) return fail(ctx, RT3_E_ARG, "frame too large for one sample batch");
     if ((rc = ctx->d_rad.ensure(ctx, (size_t)npix * batch))) return rc;
     if (sample_begin == 0) {
@@ -1883,12 +1908,9 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     TraceArgs A;
     if ((rc = path_args(ctx, cam, p, npix, A))) return rc;
     A.rad = ctx->d_rad;
-
     TracePlan T;
-    if (nee && (rc = ensure_env_table(ctx, stream))) return rc;
-    if (light && (rc = ensure_light_table(ctx, stream))) return rc;
-    if ((rc = plan_trace(ctx, A, ref ? Form::RenderRef : Form::Render, ref && !(cam_at_origin(cam) && !(p->lens_radius > 0.0f)), T, nee, light))) return rc;
-
+    if ((rc = plan_sampled_trace(ctx, A, ref ? Form::RenderRef : Form::Render, ref && !(cam_at_origin(cam) && !(p->lens_radius > 0.0f)), p->flags, stream, T)))
+        return rc;
     if ((rc = begin_timed(ctx, stream))) return rc;
 #ifdef RT3_PROFILE
     RT3_HIP(hipMemsetAsync(ctx->d_casts + 6, 0xFF, 8, stream));
@@ -1898,21 +1920,12 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
         launch_primary_lists(ctx, A, T.list_groups, T.mfma_blocks, stream);
         RT3_HIP(hipGetLastError());
     }
-    for (uint32_t s0 = sample_begin; s0 < sample_begin + sample_count; s0 += batch) {
-        const uint32_t ns = std::min(batch, sample_begin + sample_count - s0);
-        A.s0 = s0;
-        A.total = npix * ns;
-        if ((rc = issue_trace(ctx, A, T, A.total, stream))) return rc;
-        const dim3 ag((npix + kBlock - 1) / kBlock), ab(kBlock);
-        if (var) hipLaunchKernelGGL(k_accumulate<true>, ag, ab, 0, stream, ctx->d_rad, ctx->d_accum, ctx->d_accum_sq, npix, ns, s0 == 0 ? 1 : 0);
-        else hipLaunchKernelGGL(k_accumulate<false>, ag, ab, 0, stream, ctx->d_rad, ctx->d_accum, (float4*)nullptr, npix, ns, s0 == 0 ? 1 : 0);
-        RT3_HIP(hipGetLastError());
-    }
+    if ((rc = trace_and_sum(ctx, T, A, npix, nullptr, var, sample_begin, sample_count, batch, stream))) return rc;
     hipLaunchKernelGGL(k_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
                        ctx->d_accum, npix, sample_begin + sample_count, p->flags, (uint32_t*)d_out);
     RT3_HIP(hipGetLastError());
     if ((rc = end_timed(ctx, stream, (uint64_t)npix * sample_count, &T))) return rc;
-    ctx->acc_valid = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = sample_begin + sample_count; ctx->acc_npix = npix;
+    commit_accumulation(ctx, cam, p, sample_begin + sample_count, npix, false);
     return 0;
 }
 
@@ -1927,14 +1940,8 @@ int rt3_render_path_range(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
     if (!out_pixels) return fail(ctx, RT3_E_ARG, "out_pixels is NULL");
     int rc = check_params(ctx, p);
     if (rc) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
-    if ((rc = ctx->stage.ensure(ctx, (std::max<size_t>(npix, 1) + 3) / 4))) return rc;
-    uint32_t* const d_out = (uint32_t*)ctx->stage.get();
-    if ((rc = rt3_render_path_range_device(ctx, cam, p, sample_begin, sample_count, d_out, ctx->stream))) return rc;
-    if (npix) RT3_HIP(hipMemcpyAsync(out_pixels, d_out, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_out(out_pixels, (size_t)rt3_rows_owned(p) * p->width * 4) },
+                  [&](void* const* d) { return rt3_render_path_range_device(ctx, cam, p, sample_begin, sample_count, d[0], ctx->stream); });
 }
 
 int rt3_render_path(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, uint32_t* out_pixels) {
@@ -1974,16 +1981,13 @@ int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const r
     ctx->acc_adaptive = false;
     if (npix == 0) {
         if ((rc = begin_timed(ctx, stream)) || (rc = end_timed(ctx, stream, 0, nullptr))) return rc;
-        ctx->acc_valid = true; ctx->acc_adaptive = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = p->spp; ctx->acc_npix = 0;
+        commit_accumulation(ctx, cam, p, p->spp, 0, true);
         return 0;
     }
 
     // sample storage: sized once, for the dense round or the longest later round over every pixel; a list round takes as many samples per batch
     // as fit in it (n_active in the place of npix)
-    const uint64_t per_spp = (uint64_t)npix * sizeof(Rgb);
-    const uint32_t longest = std::max(ap->min_spp, std::min(ap->step_spp, p->spp));
-    uint32_t batch = (uint32_t)std::min<uint64_t>(longest, std::max<uint64_t>(1, ctx->rad_cap_bytes / per_spp));
-    batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / npix);
+    const uint32_t batch = sample_batch(ctx, std::max(ap->min_spp, std::min(ap->step_spp, p->spp)), npix, sizeof(Rgb));
     if (batch == 0) return fail(ctx, RT3_E_ARG, "frame too large for one sample batch");
     const size_t rad_items = (size_t)npix * batch;
     const uint32_t n_blocks = (npix + kBlock - 1) / kBlock;
@@ -2007,24 +2011,7 @@ int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const r
         launch_primary_lists(ctx, A, T.list_groups, T.mfma_blocks, stream);
         RT3_HIP(hipGetLastError());
     }
-    // one round: samples [s_begin, s_begin + s_count) of the n_items pixels the arguments B address, in batches of at most rad_items records
-    auto render_round = [&](const TracePlan& P, TraceArgs& B, uint32_t n_items, const uint32_t* active, uint32_t s_begin, uint32_t s_count) -> int {
-        const uint32_t per = (uint32_t)std::min<uint64_t>(s_count, std::min<uint64_t>(rad_items / n_items, 0x7FFF0000ull / n_items));
-        for (uint32_t s0 = s_begin; s0 < s_begin + s_count; s0 += per) {
-            const uint32_t ns = std::min(per, s_begin + s_count - s0);
-            B.s0 = s0;
-            B.total = n_items * ns;
-            int rc_;
-            if ((rc_ = issue_trace(ctx, B, P, B.total, stream))) return rc_;
-            const dim3 ag((n_items + kBlock - 1) / kBlock), ab(kBlock);
-            if (active) hipLaunchKernelGGL(k_accumulate_list<true>, ag, ab, 0, stream, ctx->d_rad, active, n_items, ctx->d_accum, ctx->d_accum_sq,
-                                           ctx->d_counts, ns, s0 + ns);
-            else hipLaunchKernelGGL(k_accumulate<true>, ag, ab, 0, stream, ctx->d_rad, ctx->d_accum, ctx->d_accum_sq, npix, ns, s0 == 0 ? 1 : 0);
-            RT3_HIP(hipGetLastError());
-        }
-        return 0;
-    };
-    if ((rc = render_round(T, A, npix, nullptr, 0, ap->min_spp))) return rc;
+    if ((rc = trace_and_sum(ctx, T, A, npix, nullptr, true, 0, ap->min_spp, batch, stream))) return rc;
     hipLaunchKernelGGL(k_fill_words, dim3(n_blocks), dim3(kBlock), 0, stream, ctx->d_counts, npix, ap->min_spp);
     RT3_HIP(hipGetLastError());
 
@@ -2050,7 +2037,8 @@ int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const r
         B.div_npix = make_fastdiv(n_active);
         if (!fastdiv_ok(n_active, 0x7FFFFFFFu)) return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
         const uint32_t ns = std::min(ap->step_spp, p->spp - done);
-        if ((rc = render_round(TL, B, n_active, ctx->d_active[cur], done, ns))) return rc;
+        const uint32_t per = (uint32_t)std::min<uint64_t>(rad_items / n_active, 0x7FFF0000ull / n_active);      // the list's samples per batch of the storage
+        if ((rc = trace_and_sum(ctx, TL, B, n_active, ctx->d_active[cur], true, done, ns, per, stream))) return rc;
         samples += (uint64_t)n_active * ns;
         done += ns;
         cur ^= 1u;
@@ -2060,7 +2048,7 @@ int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const r
     RT3_HIP(hipGetLastError());
     if (d_out_counts) RT3_HIP(hipMemcpyAsync(d_out_counts, ctx->d_counts, (size_t)npix * 4, hipMemcpyDeviceToDevice, stream));
     if ((rc = end_timed(ctx, stream, samples, &T))) return rc;
-    ctx->acc_valid = true; ctx->acc_adaptive = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = p->spp; ctx->acc_npix = npix;
+    commit_accumulation(ctx, cam, p, p->spp, npix, true);
     return 0;
 }
 
@@ -2070,17 +2058,9 @@ int rt3_render_path_adaptive(rt3_ctx* ctx, const rt3_camera* cam, const rt3_para
     if (!out_pixels) return fail(ctx, RT3_E_ARG, "out_pixels is NULL");
     int rc = check_params(ctx, p);
     if (rc) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
-    const size_t quads = (std::max<size_t>(npix, 1) + 3) / 4;        // pixels, then counts, each at a float4 offset of the staging buffer
-    if ((rc = ctx->stage.ensure(ctx, 2 * quads))) return rc;
-    uint32_t* const d_out = (uint32_t*)ctx->stage.get();
-    uint32_t* const d_counts = (uint32_t*)(ctx->stage.get() + quads);
-    if ((rc = rt3_render_path_adaptive_device(ctx, cam, p, ap, d_out, out_counts ? d_counts : nullptr, ctx->stream))) return rc;
-    if (npix) RT3_HIP(hipMemcpyAsync(out_pixels, d_out, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (npix && out_counts) RT3_HIP(hipMemcpyAsync(out_counts, d_counts, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    const size_t bytes = (size_t)rt3_rows_owned(p) * p->width * 4;
+    return staged(ctx, { stage_out(out_pixels, bytes), stage_out(out_counts, bytes) },
+                  [&](void* const* d) { return rt3_render_path_adaptive_device(ctx, cam, p, ap, d[0], d[1], ctx->stream); });      // (no counts asked for: a NULL d_out_counts)
 }
 
 // Checkpoint of the accumulation: what rt3_render_path_range keeps between calls, 4 floats per owned pixel.
@@ -2121,7 +2101,7 @@ int rt3_accum_upload(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, c
             RT3_HIP(hipMemcpy(ctx->d_accum_sq, sum_sq, (size_t)npix * sizeof(float4), hipMemcpyHostToDevice));
         }
     }
-    ctx->acc_valid = true; ctx->acc_params = *p; ctx->acc_cam = *cam; ctx->acc_done = samples_done; ctx->acc_npix = npix;
+    commit_accumulation(ctx, cam, p, samples_done, npix, false);
     return 0;
 }
 
@@ -2213,15 +2193,8 @@ static int query_host(rt3_ctx* ctx, const rt3_ray* rays, uint32_t n, float t_min
     if (!rays || !out) return fail(ctx, RT3_E_ARG, "rays / results array is NULL");
     int rc = check_scene(ctx);
     if (rc) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
-    if ((rc = ctx->stage.ensure(ctx, (size_t)n * 3u))) return rc;
-    float4* const d_rays = ctx->stage.get();                        // two float4 per ray, then one per result
-    float4* const d_out = d_rays + (size_t)n * 2u;
-    RT3_HIP(hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(rt3_ray), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = query_device(ctx, d_rays, n, t_min, d_out, ctx->stream, occluded))) return rc;
-    RT3_HIP(hipMemcpyAsync(out, d_out, (size_t)n * (occluded ? 4u : sizeof(rt3_hit)), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_in(rays, (size_t)n * sizeof(rt3_ray)), stage_out(out, (size_t)n * (occluded ? 4u : sizeof(rt3_hit))) },
+                  [&](void* const* d) { return query_device(ctx, d[0], n, t_min, d[1], ctx->stream, occluded); });
 }
 static_assert(sizeof(rt3_ray) == 32 && sizeof(rt3_hit) == 16, "rt3.h: query wire structs");
 
@@ -2273,12 +2246,8 @@ int rt3_camera_rays(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, ui
     if (sample_count == 0 || (uint64_t)sample_begin + sample_count > p->spp) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
     const uint64_t n = (uint64_t)rt3_rows_owned(p) * p->width * sample_count;
     if (n > 0x7FFF0000ull) return fail(ctx, RT3_E_ARG, "too many rays for one call (owned pixels x samples > 2^31 - 2^16)");
-    RT3_HIP(hipSetDevice(ctx->device));
-    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(2 * n, 1)))) return rc;
-    if ((rc = rt3_camera_rays_device(ctx, cam, p, sample_begin, sample_count, ctx->stage, ctx->stream))) return rc;
-    if (n) RT3_HIP(hipMemcpyAsync(out, ctx->stage, n * sizeof(rt3_ray), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_out(out, n * sizeof(rt3_ray)) },
+                  [&](void* const* d) { return rt3_camera_rays_device(ctx, cam, p, sample_begin, sample_count, d[0], ctx->stream); });
 }
 
 // Per sample batch: the batch's rays (make_rays(s0, ns): k_camera_rays, or k_lens_rays for a lens frame) into d_arays -> the query form of the scene's
@@ -2291,10 +2260,7 @@ static int aov_pass(rt3_ctx* ctx, const rt3_params* p, const TraceArgs& A, void*
     ctx->rendered = false;
     int rc;
     if (npix == 0) return (rc = begin_timed(ctx, stream)) ? rc : end_timed(ctx, stream, 0, nullptr);
-    // batch size: 48 B per (pixel, sample) — the ray (32) and its hit (16) — under the sample storage cap
-    const uint64_t per_spp = (uint64_t)npix * (sizeof(rt3_ray) + sizeof(rt3_hit));
-    uint32_t batch = (uint32_t)std::min<uint64_t>(p->spp, std::max<uint64_t>(1, ctx->rad_cap_bytes / per_spp));
-    batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / npix);
+    const uint32_t batch = sample_batch(ctx, p->spp, npix, sizeof(rt3_ray) + sizeof(rt3_hit));      // 48 B per (pixel, sample): the ray and its hit
     if (batch == 0) return fail(ctx, RT3_E_ARG, "frame too large for one sample batch");
     if ((rc = ctx->d_arays.ensure(ctx, (size_t)npix * batch * 2u)) || (rc = ctx->d_ahits.ensure(ctx, (size_t)npix * batch)) ||
         (rc = ctx->d_aacc.ensure(ctx, (size_t)npix * 3u)))
@@ -2316,6 +2282,49 @@ static int aov_pass(rt3_ctx* ctx, const rt3_params* p, const TraceArgs& A, void*
     hipLaunchKernelGGL(k_aov_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_aacc, npix, p->spp, (float4*)d_out);
     RT3_HIP(hipGetLastError());
     return end_timed(ctx, stream, (uint64_t)npix * p->spp, &T);
+}
+
+// The Rays form over n rays: samples [rp.sample_begin, rp.sample_begin + rp.sample_count) in batches under the sample storage cap;
+// per batch the trace, then k_accumulate<false> into d_out in sample order (d_accum and the acc_* state are never touched), and the division in place.
+// d_rays: the caller's rays, one launch per batch over the items (sample in batch, ray).  Without them every sample has rays of its own: make_rays(s0, ns)
+// writes a batch's into d_arays and, the Rays form mapping item j to ray j % n, each sample is a launch over its slice of the rays and of the storage.
+// d_keys: the rays' keys or nullptr.  Called behind the arguments' checks and enter().
+static int radiance_pass(rt3_ctx* ctx, uint32_t n, const rt3_radiance_params& rp, void* d_out, const uint32_t* d_keys, const float4* d_rays,
+                         hipStream_t stream, const std::function<int(uint32_t, uint32_t)>& make_rays) {
+    const bool per_sample = d_rays == nullptr;
+    ctx->rendered = false;
+    int rc;
+    if (n == 0) return (rc = begin_timed(ctx, stream)) ? rc : end_timed(ctx, stream, 0, nullptr);
+    // 12 B per (ray, sample) of radiance and, for rays made here, the ray's 32 (n <= 2^27: at least 15 samples fit the item index)
+    const uint32_t batch = sample_batch(ctx, rp.sample_count, n, sizeof(Rgb) + (per_sample ? sizeof(rt3_ray) : 0));
+    if ((rc = ctx->d_rad.ensure(ctx, (size_t)n * batch)) || (per_sample && (rc = ctx->d_arays.ensure(ctx, (size_t)n * batch * 2u)))) return rc;
+    TraceArgs A = scene_args(ctx);
+    A.max_depth = rp.max_depth; A.seed = rp.seed; A.flags = rp.flags; A.t_min = rp.t_min;
+    A.npix = n; A.div_npix = make_fastdiv(n);
+    if (!fastdiv_ok(n, 0x7FFFFFFFu)) return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
+    TracePlan T;
+    if ((rc = plan_sampled_trace(ctx, A, Form::Rays, false, rp.flags, stream, T))) return rc;
+    A.ray_keys = d_keys;
+    if ((rc = begin_timed(ctx, stream))) return rc;
+    const uint32_t s_end = rp.sample_begin + rp.sample_count;
+    const dim3 ag((n + kBlock - 1) / kBlock), ab(kBlock);
+    for (uint32_t s0 = rp.sample_begin; s0 < s_end; s0 += batch) {
+        const uint32_t ns = std::min(batch, s_end - s0);
+        if (per_sample && (rc = make_rays(s0, ns))) return rc;
+        const uint32_t launches = per_sample ? ns : 1u, each = ns / launches;      // samples per launch
+        for (uint32_t i = 0; i < launches; i++) {
+            A.s0 = s0 + i * each;
+            A.total = n * each;
+            A.q_rays = per_sample ? ctx->d_arays.get() + (size_t)i * n * 2u : d_rays;
+            A.rad = ctx->d_rad.get() + (size_t)i * n * each;
+            if ((rc = issue_trace(ctx, A, T, A.total, stream))) return rc;
+        }
+        hipLaunchKernelGGL(k_accumulate<false>, ag, ab, 0, stream, ctx->d_rad, (float4*)d_out, (float4*)nullptr, n, ns, s0 == rp.sample_begin ? 1 : 0);
+        RT3_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_resolve_float_inplace, ag, ab, 0, stream, (float4*)d_out, n, rp.sample_count);
+    RT3_HIP(hipGetLastError());
+    return end_timed(ctx, stream, (uint64_t)n * rp.sample_count, &T);
 }
 
 int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, void* d_out, void* stream_) {
@@ -2343,13 +2352,8 @@ int rt3_render_aov(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, rt3
     if (!out) return fail(ctx, RT3_E_ARG, "out_aov is NULL");
     int rc = check_params(ctx, p);
     if (rc) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
-    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(3 * npix, 1)))) return rc;
-    if ((rc = rt3_render_aov_device(ctx, cam, p, ctx->stage, ctx->stream))) return rc;
-    if (npix) RT3_HIP(hipMemcpyAsync(out, ctx->stage, npix * sizeof(rt3_aov), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_out(out, (size_t)rt3_rows_owned(p) * p->width * sizeof(rt3_aov)) },
+                  [&](void* const* d) { return rt3_render_aov_device(ctx, cam, p, d[0], ctx->stream); });
 }
 
 int rt3_accum_resolve_device(rt3_ctx* ctx, void* d_out, void* stream_) {
@@ -2374,14 +2378,8 @@ int rt3_accum_resolve(rt3_ctx* ctx, float* rgba) {
     if (!ctx) return RT3_E_ARG;
     if (!rgba) return fail(ctx, RT3_E_ARG, "rgba is NULL");
     if (!ctx->acc_valid) return fail(ctx, RT3_E_STATE, "no accumulation on this context");
-    RT3_HIP(hipSetDevice(ctx->device));
-    const size_t npix = ctx->acc_npix;
-    int rc;
-    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(npix, 1)))) return rc;
-    if ((rc = rt3_accum_resolve_device(ctx, ctx->stage, ctx->stream))) return rc;
-    if (npix) RT3_HIP(hipMemcpyAsync(rgba, ctx->stage, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_out(rgba, (size_t)ctx->acc_npix * sizeof(float4)) },
+                  [&](void* const* d) { return rt3_accum_resolve_device(ctx, d[0], ctx->stream); });
 }
 static_assert(sizeof(rt3_aov) == 48, "rt3.h: rt3_aov");
 
@@ -2424,18 +2422,9 @@ int rt3_denoise(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* colour, const
     if (!ctx) return RT3_E_ARG;
     int rc = denoise_checks(ctx, w, h, colour, aov, p, out);
     if (rc) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)w * h;
-    if ((rc = ctx->stage.ensure(ctx, 5 * npix))) return rc;
-    float4* const dc = ctx->stage;
-    float4* const da = dc + npix;
-    float4* const dout = da + 3 * npix;
-    RT3_HIP(hipMemcpyAsync(dc, colour, npix * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    RT3_HIP(hipMemcpyAsync(da, aov, npix * sizeof(rt3_aov), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = rt3_denoise_device(ctx, w, h, dc, da, p, dout, ctx->stream))) return rc;
-    RT3_HIP(hipMemcpyAsync(out, dout, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_in(colour, npix * sizeof(float4)), stage_in(aov, npix * sizeof(rt3_aov)), stage_out(out, npix * sizeof(float4)) },
+                  [&](void* const* d) { return rt3_denoise_device(ctx, w, h, d[0], d[1], p, d[2], ctx->stream); });
 }
 static_assert(sizeof(rt3_denoise_params) == 16, "rt3.h: rt3_denoise_params");
 
@@ -2540,33 +2529,17 @@ int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_
     return rt3_denoise_temporal_motion_device(ctx, w, h, cam, d_colour, d_aov, prev_cam, d_prev_history, nullptr, p, d_out, d_out_history, stream_);
 }
 
-// The host form: colour, AOVs, both histories, the result and the motion plane on the device in ctx->stage (12 float4 per pixel).
 int rt3_denoise_temporal_motion(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
                                 const rt3_camera* prev_cam, const rt3_history* prev_history, const float* motion,
                                 const rt3_temporal_params* p, float* out, rt3_history* out_history) {
     if (!ctx) return RT3_E_ARG;
     int rc = temporal_checks(ctx, w, h, cam, colour, aov, prev_cam, prev_history, motion, p, out, out_history);
     if (rc) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)w * h;
-    if ((rc = ctx->stage.ensure(ctx, (motion ? 12 : 11) * npix))) return rc;
-    float4* const dc = ctx->stage;
-    float4* const da = dc + npix;
-    float4* const dprev = da + 3 * npix;
-    float4* const dhist = dprev + 3 * npix;
-    float4* const dout = dhist + 3 * npix;
-    float4* const dmot = dout + npix;
-    if (motion) RT3_HIP(hipMemcpyAsync(dmot, motion, npix * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    RT3_HIP(hipMemcpyAsync(dc, colour, npix * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    RT3_HIP(hipMemcpyAsync(da, aov, npix * sizeof(rt3_aov), hipMemcpyHostToDevice, ctx->stream));
-    if (prev_history) RT3_HIP(hipMemcpyAsync(dprev, prev_history, npix * sizeof(rt3_history), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = rt3_denoise_temporal_motion_device(ctx, w, h, cam, dc, da, prev_cam, prev_history ? dprev : nullptr, motion ? dmot : nullptr, p, dout,
-                                                 dhist, ctx->stream)))
-        return rc;
-    RT3_HIP(hipMemcpyAsync(out, dout, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipMemcpyAsync(out_history, dhist, npix * sizeof(rt3_history), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_in(colour, npix * sizeof(float4)), stage_in(aov, npix * sizeof(rt3_aov)),
+                         stage_in(prev_history, npix * sizeof(rt3_history)), stage_in(motion, npix * sizeof(float4)),
+                         stage_out(out, npix * sizeof(float4)), stage_out(out_history, npix * sizeof(rt3_history)) },
+                  [&](void* const* d) { return rt3_denoise_temporal_motion_device(ctx, w, h, cam, d[0], d[1], prev_cam, d[2], d[3], p, d[4], d[5], ctx->stream); });
 }
 
 int rt3_denoise_temporal(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
@@ -2624,32 +2597,19 @@ int rt3_motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* ca
     return leave(ctx, stream);
 }
 
-// The host form: the AOVs, the plane and the previous arrays on the device in ctx->stage (4 float4 per pixel, one per sphere and vertex).
 int rt3_motion(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_aov* aov, const float* prev_sph, uint32_t n_prev_sph,
                const float* prev_verts, uint32_t n_prev_verts, float* out) {
     if (!ctx) return RT3_E_ARG;
     int rc = motion_checks(ctx, w, h, cam, aov, prev_sph, n_prev_sph, prev_verts, n_prev_verts, out);
     if (rc) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)w * h;
-    if ((rc = ctx->stage.ensure(ctx, 4 * npix + n_prev_sph + n_prev_verts))) return rc;
-    float4* const da = ctx->stage;
-    float4* const dout = da + 3 * npix;
-    float4* const dsph = dout + npix;
-    float4* const dverts = dsph + n_prev_sph;
-    RT3_HIP(hipMemcpyAsync(da, aov, npix * sizeof(rt3_aov), hipMemcpyHostToDevice, ctx->stream));
-    if (prev_sph) RT3_HIP(hipMemcpyAsync(dsph, prev_sph, (size_t)n_prev_sph * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    if (prev_verts) RT3_HIP(hipMemcpyAsync(dverts, prev_verts, (size_t)n_prev_verts * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = rt3_motion_device(ctx, w, h, cam, da, prev_sph ? dsph : nullptr, n_prev_sph, prev_verts ? dverts : nullptr, n_prev_verts, dout, ctx->stream)))
-        return rc;
-    RT3_HIP(hipMemcpyAsync(out, dout, npix * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_in(aov, npix * sizeof(rt3_aov)), stage_in(prev_sph, (size_t)n_prev_sph * sizeof(float4)),
+                     stage_in(prev_verts, (size_t)n_prev_verts * sizeof(float4)), stage_out(out, npix * sizeof(float4)) },
+                  [&](void* const* d) { return rt3_motion_device(ctx, w, h, cam, d[0], d[1], n_prev_sph, d[2], n_prev_verts, d[3], ctx->stream); });
 }
 
 // ---- Radiance along caller-supplied rays: the rays form of the kernel a query would take on the scene, over the items
-// (sample in batch, ray); the batch loop is rt3_render_path_range_device's with the caller's output as the sum buffer — d_accum and the acc_* state of a
-// progressive or adaptive render are never touched — then the division in place.
+// (sample in batch, ray), through radiance_pass with the caller's rays and the caller's output as the sum buffer.
 static_assert(sizeof(rt3_radiance_params) == 24, "rt3.h: rt3_radiance_params");
 static int radiance_checks(rt3_ctx* ctx, uint32_t n, const rt3_radiance_params* rp) {
     if (!rp) return fail(ctx, RT3_E_ARG, "radiance params is NULL");
@@ -2665,7 +2625,7 @@ static int radiance_checks(rt3_ctx* ctx, uint32_t n, const rt3_radiance_params* 
     if (n > (1u << 27)) return fail(ctx, RT3_E_ARG, "at most 2^27 rays per radiance call (split the batch and pass keys)");
     return 0;
 }
-static int radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, uint32_t n, const rt3_radiance_params* rp, void* d_out, void* stream_) {
+int rt3_radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, uint32_t n, const rt3_radiance_params* rp, void* d_out, void* stream_) {
     if (!ctx) return RT3_E_ARG;
     int rc = radiance_checks(ctx, n, rp);
     if (rc) return rc;
@@ -2676,81 +2636,29 @@ static int radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys,
     if (ranges_overlap(d_out, (size_t)n * 16u, d_rays, (size_t)n * sizeof(rt3_ray)) || (d_keys && ranges_overlap(d_out, (size_t)n * 16u, d_keys, (size_t)n * 4u)))
         return fail(ctx, RT3_E_ARG, "out_rgba overlaps the rays or the keys");
     if ((rc = check_scene(ctx)) || (rc = check_env_sampling(ctx, rp->flags))) return rc;
-    const bool nee = (rp->flags & RT3_FLAG_ENV_SAMPLING) != 0, light = (rp->flags & RT3_FLAG_LIGHT_SAMPLING) != 0;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
-    ctx->rendered = false;
-    // batch size: per-sample storage of 12 B per (ray, sample), capped (n <= 2^27: at least 15 samples fit the item index)
-    uint32_t batch = (uint32_t)std::min<uint64_t>(rp->sample_count, std::max<uint64_t>(1, ctx->rad_cap_bytes / ((uint64_t)n * sizeof(Rgb))));
-    batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / n);
-    if ((rc = ctx->d_rad.ensure(ctx, (size_t)n * batch))) return rc;
-    TraceArgs A = scene_args(ctx);
-    A.max_depth = rp->max_depth; A.seed = rp->seed; A.flags = rp->flags; A.t_min = rp->t_min;
-    A.npix = n; A.div_npix = make_fastdiv(n);
-    if (!fastdiv_ok(n, 0x7FFFFFFFu)) return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
-    A.rad = ctx->d_rad;
-    TracePlan T;
-    if (nee && (rc = ensure_env_table(ctx, stream))) return rc;
-    if (light && (rc = ensure_light_table(ctx, stream))) return rc;
-    if ((rc = plan_trace(ctx, A, Form::Rays, false, T, nee, light))) return rc;
-    A.q_rays = (const float4*)d_rays; A.ray_keys = (const uint32_t*)d_keys;
-    if ((rc = begin_timed(ctx, stream))) return rc;
-    const uint32_t s_end = rp->sample_begin + rp->sample_count;
-    const dim3 ag((n + kBlock - 1) / kBlock), ab(kBlock);
-    for (uint32_t s0 = rp->sample_begin; s0 < s_end; s0 += batch) {
-        const uint32_t ns = std::min(batch, s_end - s0);
-        A.s0 = s0;
-        A.total = n * ns;
-        if ((rc = issue_trace(ctx, A, T, A.total, stream))) return rc;
-        hipLaunchKernelGGL(k_accumulate<false>, ag, ab, 0, stream, ctx->d_rad, (float4*)d_out, (float4*)nullptr, n, ns, s0 == rp->sample_begin ? 1 : 0);
-        RT3_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_resolve_float_inplace, ag, ab, 0, stream, (float4*)d_out, n, rp->sample_count);
-    RT3_HIP(hipGetLastError());
-    return end_timed(ctx, stream, (uint64_t)n * rp->sample_count, &T);
+    return radiance_pass(ctx, n, *rp, d_out, (const uint32_t*)d_keys, (const float4*)d_rays, stream, nullptr);
 }
-static int radiance_host(rt3_ctx* ctx, const rt3_ray* rays, const uint32_t* keys, uint32_t n, const rt3_radiance_params* rp, float* out) {
+int rt3_radiance(rt3_ctx* ctx, const rt3_ray* rays, const uint32_t* keys, uint32_t n, const rt3_radiance_params* rp, float* out) {
     if (!ctx) return RT3_E_ARG;
     int rc = radiance_checks(ctx, n, rp);
     if (rc) return rc;
     if (n == 0) return 0;
     if (!rays || !out) return fail(ctx, RT3_E_ARG, "rays / out_rgba array is NULL");
     if ((rc = check_scene(ctx))) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
-    if ((rc = ctx->stage.ensure(ctx, (size_t)n * 3u + ((size_t)n + 3u) / 4u))) return rc;
-    float4* const d_rays = ctx->stage.get();                        // two float4 per ray, one per result, then the keys
-    float4* const d_out = d_rays + (size_t)n * 2u;
-    uint32_t* const d_keys = keys ? (uint32_t*)(d_out + n) : nullptr;
-    RT3_HIP(hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(rt3_ray), hipMemcpyHostToDevice, ctx->stream));
-    if (keys) RT3_HIP(hipMemcpyAsync(d_keys, keys, (size_t)n * 4u, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = radiance_device(ctx, d_rays, d_keys, n, rp, d_out, ctx->stream))) return rc;
-    RT3_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 16u, hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-int rt3_radiance(rt3_ctx* ctx, const rt3_ray* rays, const uint32_t* keys, uint32_t n, const rt3_radiance_params* p, float* out_rgba) {
-    return radiance_host(ctx, rays, keys, n, p, out_rgba);
-}
-int rt3_radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, uint32_t n, const rt3_radiance_params* p, void* d_out_rgba, void* stream) {
-    return radiance_device(ctx, d_rays, d_keys, n, p, d_out_rgba, stream);
+    return staged(ctx, { stage_in(rays, (size_t)n * sizeof(rt3_ray)), stage_in(keys, (size_t)n * 4u), stage_out(out, (size_t)n * 16u) },
+                  [&](void* const* d) { return rt3_radiance_device(ctx, d[0], d[1], n, rp, d[2], ctx->stream); });
 }
 
-// ---- Lens models: k_lens_rays writes a batch's rays (and a shard's keys) into the context's scratch; a render then runs
-// radiance_device's loop with ONE trace launch per sample — the Rays form maps item j to ray j % npix, and here every sample has rays of its own, so a
-// launch covers one sample's slice of the rays and of the sample storage (s0 = s, total = npix) — and the AOV pass runs rt3_render_aov_device's loop.
+// ---- Lens models: k_lens_rays writes a batch's rays (and a shard's keys) into the context's scratch; a render is
+// radiance_pass with k_lens_rays as its ray generator (one trace launch per sample), and the AOVs are aov_pass with k_lens_rays in k_camera_rays' place.
 static_assert(sizeof(rt3_lens) == 80, "rt3.h: rt3_lens");
-// rt3_params' own rules (check_params) with one difference: a lens frame may be one pixel wide or high (a cube of N = 1); then the lens.
+// rt3_params' own rules (check_params) for a frame that may be one pixel wide or high (a cube of N = 1), then the lens.
 static int lens_checks(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, const void* d_out, const char* what, bool device) {
     if (!lens || !d_out) return fail(ctx, RT3_E_ARG, std::string("lens / ") + what + " is NULL");
-    if (!p) return fail(ctx, RT3_E_ARG, "params is NULL");
-    if (!(p->t_min >= 0.0f) || !(p->t_min < __builtin_inff())) return fail(ctx, RT3_E_ARG, "t_min must be finite and >= 0");
-    if (p->flags & ~(RT3_FLAG_GAMMA2 | RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_REFERENCE_PRIMARY | RT3_FLAG_VARIANCE | RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING))
-        return fail(ctx, RT3_E_ARG, "unknown bits in flags");
-    if (p->width < 1 || p->height < 1) return fail(ctx, RT3_E_ARG, "width and height must be >= 1");
-    if ((uint64_t)p->width * p->height > 0x7FFFFFFFull) return fail(ctx, RT3_E_ARG, "frame too large");
-    if (p->spp < 1 || p->max_depth < 1) return fail(ctx, RT3_E_ARG, "spp and max_depth must be >= 1");
-    if (p->tile_count > 1 && (p->tile_rows == 0 || p->tile_index >= p->tile_count))
-        return fail(ctx, RT3_E_ARG, "bad tile_rows / tile_index / tile_count");
+    const int rc = check_params(ctx, p, 1);
+    if (rc) return rc;
     if (const char* why = rt3lens::refusal(lens, p->width, p->height)) return fail(ctx, RT3_E_ARG, why);
     if (device && (uintptr_t)d_out % 16u != 0) return fail(ctx, RT3_E_ARG, std::string(what) + " must be 16-byte aligned");
     return 0;
@@ -2797,12 +2705,8 @@ int rt3_lens_rays(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, uint3
     if (!lens_sample_range_ok(p, sample_begin, sample_count)) return fail(ctx, RT3_E_ARG, "sample range outside [0, spp)");
     const uint64_t n = (uint64_t)rt3_rows_owned(p) * p->width * sample_count;
     if (n > 0x7FFF0000ull) return fail(ctx, RT3_E_ARG, "too many rays for one call (owned pixels x samples > 2^31 - 2^16)");
-    RT3_HIP(hipSetDevice(ctx->device));
-    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(2 * n, 1)))) return rc;
-    if ((rc = rt3_lens_rays_device(ctx, lens, p, sample_begin, sample_count, ctx->stage, ctx->stream))) return rc;
-    if (n) RT3_HIP(hipMemcpyAsync(out, ctx->stage, n * sizeof(rt3_ray), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_out(out, n * sizeof(rt3_ray)) },
+                  [&](void* const* d) { return rt3_lens_rays_device(ctx, lens, p, sample_begin, sample_count, d[0], ctx->stream); });
 }
 
 static int render_lens_checks(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, uint32_t sample_begin, uint32_t sample_count, const void* out,
@@ -2825,50 +2729,17 @@ int rt3_render_lens_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params*
     int rc = render_lens_checks(ctx, lens, p, sample_begin, sample_count, d_out, "d_out_rgba", true);
     if (rc) return rc;
     if ((rc = check_scene(ctx)) || (rc = check_env_sampling(ctx, p->flags))) return rc;
-    const uint32_t flags = p->flags & (RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING);
-    const bool nee = (flags & RT3_FLAG_ENV_SAMPLING) != 0, light = (flags & RT3_FLAG_LIGHT_SAMPLING) != 0;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
     const uint32_t npix = rt3_rows_owned(p) * p->width;
-    ctx->rendered = false;
-    if (npix == 0) return (rc = begin_timed(ctx, stream)) ? rc : end_timed(ctx, stream, 0, nullptr);
-    // batch size: 44 B per (pixel, sample) — the ray (32) and its radiance record (12) — under the sample storage cap
-    const uint64_t per_spp = (uint64_t)npix * (sizeof(rt3_ray) + sizeof(Rgb));
-    uint32_t batch = (uint32_t)std::min<uint64_t>(sample_count, std::max<uint64_t>(1, ctx->rad_cap_bytes / per_spp));
-    batch = (uint32_t)std::min<uint64_t>(batch, 0x7FFF0000ull / npix);          // (npix <= 2^27: at least 15)
     const bool shard = p->tile_count > 1;                           // a whole frame's ray index is its frame pixel index: no keys
-    if ((rc = ctx->d_arays.ensure(ctx, (size_t)npix * batch * 2u)) || (rc = ctx->d_rad.ensure(ctx, (size_t)npix * batch)) ||
-        (shard && (rc = ctx->d_lens_keys.ensure(ctx, npix))))
-        return rc;
+    if (shard && npix && (rc = ctx->d_lens_keys.ensure(ctx, npix))) return rc;
     uint32_t* const d_keys = shard ? ctx->d_lens_keys.get() : nullptr;
-    TraceArgs A = scene_args(ctx);
-    A.max_depth = p->max_depth; A.seed = p->seed; A.flags = flags; A.t_min = p->t_min;
-    A.npix = npix; A.div_npix = make_fastdiv(npix);
-    if (!fastdiv_ok(npix, 0x7FFFFFFFu)) return fail(ctx, RT3_E_DEVICE, "internal: magic-number division self-check failed");
-    TracePlan T;
-    if (nee && (rc = ensure_env_table(ctx, stream))) return rc;
-    if (light && (rc = ensure_light_table(ctx, stream))) return rc;
-    if ((rc = plan_trace(ctx, A, Form::Rays, false, T, nee, light))) return rc;
-    A.ray_keys = d_keys;
-    A.total = npix;                                                 // one launch per sample: its slice of the rays and of the storage
-    if ((rc = begin_timed(ctx, stream))) return rc;
-    const uint32_t s_end = sample_begin + sample_count;
-    const dim3 ag((npix + kBlock - 1) / kBlock), ab(kBlock);
-    for (uint32_t s0 = sample_begin; s0 < s_end; s0 += batch) {
-        const uint32_t ns = std::min(batch, s_end - s0);
-        if ((rc = launch_lens_rays(ctx, lens, p, npix, s0, ns, ctx->d_arays, d_keys, stream))) return rc;
-        for (uint32_t i = 0; i < ns; i++) {
-            A.s0 = s0 + i;
-            A.q_rays = ctx->d_arays.get() + (size_t)i * npix * 2u;
-            A.rad = ctx->d_rad.get() + (size_t)i * npix;
-            if ((rc = issue_trace(ctx, A, T, npix, stream))) return rc;
-        }
-        hipLaunchKernelGGL(k_accumulate<false>, ag, ab, 0, stream, ctx->d_rad, (float4*)d_out, (float4*)nullptr, npix, ns, s0 == sample_begin ? 1 : 0);
-        RT3_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_resolve_float_inplace, ag, ab, 0, stream, (float4*)d_out, npix, sample_count);
-    RT3_HIP(hipGetLastError());
-    return end_timed(ctx, stream, (uint64_t)npix * sample_count, &T);
+    const rt3_radiance_params rp{ p->max_depth, p->seed, p->flags & (RT3_FLAG_BLACK_BACKGROUND | RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING),
+                                  sample_begin, sample_count, p->t_min };
+    return radiance_pass(ctx, npix, rp, d_out, d_keys, nullptr, stream, [&](uint32_t s0, uint32_t ns) {
+        return launch_lens_rays(ctx, lens, p, npix, s0, ns, ctx->d_arays, d_keys, stream);
+    });
 }
 
 int rt3_render_lens(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, uint32_t sample_begin, uint32_t sample_count, float* out) {
@@ -2876,13 +2747,8 @@ int rt3_render_lens(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, uin
     int rc = render_lens_checks(ctx, lens, p, sample_begin, sample_count, out, "out_rgba", false);
     if (rc) return rc;
     if ((rc = check_scene(ctx))) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
-    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(npix, 1)))) return rc;
-    if ((rc = rt3_render_lens_device(ctx, lens, p, sample_begin, sample_count, ctx->stage, ctx->stream))) return rc;
-    if (npix) RT3_HIP(hipMemcpyAsync(out, ctx->stage, npix * 16u, hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_out(out, (size_t)rt3_rows_owned(p) * p->width * 16u) },
+                  [&](void* const* d) { return rt3_render_lens_device(ctx, lens, p, sample_begin, sample_count, d[0], ctx->stream); });
 }
 
 static int lens_aov_checks(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, const void* out, const char* what, bool device) {
@@ -2893,7 +2759,7 @@ static int lens_aov_checks(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params*
     return 0;
 }
 
-// rt3_render_aov_device's pass with k_lens_rays in k_camera_rays' place.
+// aov_pass with k_lens_rays in k_camera_rays' place.
 int rt3_render_lens_aov_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, void* d_out, void* stream_) {
     if (!ctx) return RT3_E_ARG;
     int rc = lens_aov_checks(ctx, lens, p, d_out, "d_out_aov", true);
@@ -2914,13 +2780,8 @@ int rt3_render_lens_aov(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p,
     int rc = lens_aov_checks(ctx, lens, p, out, "out_aov", false);
     if (rc) return rc;
     if ((rc = check_scene(ctx))) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
-    const size_t npix = (size_t)rt3_rows_owned(p) * p->width;
-    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(3 * npix, 1)))) return rc;
-    if ((rc = rt3_render_lens_aov_device(ctx, lens, p, ctx->stage, ctx->stream))) return rc;
-    if (npix) RT3_HIP(hipMemcpyAsync(out, ctx->stage, npix * sizeof(rt3_aov), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_out(out, (size_t)rt3_rows_owned(p) * p->width * sizeof(rt3_aov)) },
+                  [&](void* const* d) { return rt3_render_lens_aov_device(ctx, lens, p, d[0], ctx->stream); });
 }
 
 // ---- Environment map: the context's own copy of a cube map, read by the miss of the environment forms (5.2n) and by k_aov_accumulate.
@@ -2984,7 +2845,18 @@ int rt3_set_environment(rt3_ctx* ctx, const float* rgba, uint32_t n_face) {
     return 0;
 }
 
-// Tests only: the sampling table of the map the context holds, downloaded (built first if no call with RT3_FLAG_ENV_SAMPLING has built it yet).
+// Tests only: a sampling table of n entries downloaded, built first (ensure) if no call that carries its flag has built it yet.
+static int download_table(rt3_ctx* ctx, int (*ensure)(rt3_ctx*, hipStream_t), const DevBuf<uint32_t>& q, const DevBuf<unsigned long long>& cdf, size_t n,
+                          uint32_t* q_out, uint64_t* cdf_out) {
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, nullptr, &stream)) || (rc = ensure(ctx, stream))) return rc;
+    RT3_HIP(hipMemcpyAsync(q_out, q.get(), n * 4u, hipMemcpyDeviceToHost, stream));
+    RT3_HIP(hipMemcpyAsync(cdf_out, cdf.get(), n * 8u, hipMemcpyDeviceToHost, stream));
+    if ((rc = leave(ctx, stream))) return rc;
+    RT3_HIP(hipStreamSynchronize(stream));
+    return 0;
+}
 int rt3_debug_environment_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint64_t capacity_cells, uint32_t* m_out) {
     if (!ctx) return RT3_E_ARG;
     if (!q_out || !cdf_out || !m_out) return fail(ctx, RT3_E_ARG, "q_out / cdf_out / cells_per_edge is NULL");
@@ -2993,17 +2865,8 @@ int rt3_debug_environment_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out
     const size_t cells = (size_t)6 * m * m;
     *m_out = m;
     if (capacity_cells < cells) return fail(ctx, RT3_E_ARG, "capacity_cells is smaller than the table (6 x cells_per_edge^2 cells)");
-    hipStream_t stream;
-    int rc;
-    if ((rc = enter(ctx, nullptr, &stream)) || (rc = ensure_env_table(ctx, stream))) return rc;
-    RT3_HIP(hipMemcpyAsync(q_out, ctx->d_env_q.get(), cells * 4u, hipMemcpyDeviceToHost, stream));
-    RT3_HIP(hipMemcpyAsync(cdf_out, ctx->d_env_cdf.get(), cells * 8u, hipMemcpyDeviceToHost, stream));
-    if ((rc = leave(ctx, stream))) return rc;
-    RT3_HIP(hipStreamSynchronize(stream));
-    return 0;
+    return download_table(ctx, ensure_env_table, ctx->d_env_q, ctx->d_env_cdf, cells, q_out, cdf_out);
 }
-
-// Tests only: the emitters' sampling table of the scene the context holds, downloaded (built first if no call with RT3_FLAG_LIGHT_SAMPLING has built it yet).
 int rt3_debug_light_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint64_t capacity, uint32_t* n_entries) {
     if (!ctx) return RT3_E_ARG;
     if (!q_out || !cdf_out || !n_entries) return fail(ctx, RT3_E_ARG, "q_out / cdf_out / n_entries is NULL");
@@ -3012,13 +2875,7 @@ int rt3_debug_light_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint
     const size_t n = (size_t)ctx->n_faces + ctx->n_sph;
     *n_entries = (uint32_t)n;
     if (capacity < n) return fail(ctx, RT3_E_ARG, "capacity is smaller than the table (one entry per face and per sphere)");
-    hipStream_t stream;
-    if ((rc = enter(ctx, nullptr, &stream)) || (rc = ensure_light_table(ctx, stream))) return rc;
-    RT3_HIP(hipMemcpyAsync(q_out, ctx->d_light_q.get(), n * 4u, hipMemcpyDeviceToHost, stream));
-    RT3_HIP(hipMemcpyAsync(cdf_out, ctx->d_light_cdf.get(), n * 8u, hipMemcpyDeviceToHost, stream));
-    if ((rc = leave(ctx, stream))) return rc;
-    RT3_HIP(hipStreamSynchronize(stream));
-    return 0;
+    return download_table(ctx, ensure_light_table, ctx->d_light_q, ctx->d_light_cdf, n, q_out, cdf_out);
 }
 
 // ---- The display transform
@@ -3050,21 +2907,13 @@ int rt3_display_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_rgba,
     return leave(ctx, stream);
 }
 
-// The host form: the frame and the words on the device in ctx->stage (one float4 per pixel, then one per four words).
 int rt3_display(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* rgba, const rt3_display_params* p, uint32_t* out) {
     if (!ctx) return RT3_E_ARG;
     int rc = display_checks(ctx, w, h, rgba, p, out);
     if (rc) return rc;
-    RT3_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)w * h;
-    if ((rc = ctx->stage.ensure(ctx, npix + (npix + 3) / 4))) return rc;
-    float4* const dc = ctx->stage;
-    uint32_t* const dout = (uint32_t*)(dc + npix);
-    RT3_HIP(hipMemcpyAsync(dc, rgba, npix * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = rt3_display_device(ctx, w, h, dc, p, dout, ctx->stream))) return rc;
-    RT3_HIP(hipMemcpyAsync(out, dout, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return staged(ctx, { stage_in(rgba, npix * sizeof(float4)), stage_out(out, npix * sizeof(uint32_t)) },
+                  [&](void* const* d) { return rt3_display_device(ctx, w, h, d[0], p, d[1], ctx->stream); });
 }
 
 int rt3_debug_display_state(rt3_ctx* ctx, uint32_t hist[512], uint32_t* dark, float* gain) {

@@ -261,3 +261,24 @@ def test_a_threshold_nothing_reaches_keeps_every_pixel_to_the_budget(rt3, render
     assert full.mean() > 0.5 and np.array_equal(pixels[full], want[full])
     assert renderer.stats().samples == int(counts.sum(dtype=np.uint64))
 
+
+# ------------------------------------------------------------------------------------------------ host form = device form, optional inputs present and absent
+def test_adaptive_render_with_and_without_counts(rt3, renderer):
+    from test_gpu_host_forms import H, W, host, mixed_scene, vp
+    import torch
+    _, _, _, cam, p = mixed_scene(rt3, renderer)
+    p.spp = 6
+    L, ctx = rt3.lib(), renderer._ctx
+    ap = rt3.ADAPTIVE_PARAMS(2, 1, 1e-6, 0.0)
+    for with_counts in (False, True):
+        out, counts = np.zeros((H, W), np.uint32), np.full((H, W), 0xA5A5A5A5, np.uint32)
+        assert L.rt3_render_path_adaptive(ctx, C.byref(cam.c), C.byref(p), C.byref(ap), out.ctypes.data_as(vp),
+                                          counts.ctypes.data_as(vp) if with_counts else None) == 0
+        d_out = torch.zeros(H * W, dtype=torch.int32, device="cuda")
+        d_counts = torch.full((H * W,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+        renderer.render_adaptive_device(cam.c, p, d_out, d_counts if with_counts else None, threshold=1e-6, min_spp=2, step_spp=1, dark=0.0)
+        assert host(d_out) == out.tobytes()
+        if with_counts:
+            assert host(d_counts) == counts.tobytes() and counts.min() >= 2 and counts.max() <= 6
+        else:
+            assert (counts == 0xA5A5A5A5).all() and (d_counts.cpu().numpy() == 0x5A5A5A5A).all()

@@ -487,3 +487,38 @@ def test_cli_writes_a_pfm_per_frame_of_a_slide_sequence(tmp_path):
     subprocess.run(args[:11] + args[13:], cwd=str(still), check=True, capture_output=True, timeout=300)
     assert (still / "P.0.pfm").read_bytes() == (tmp_path / "P.0.pfm").read_bytes()          # frame 0 is the unmoved scene
     assert (still / "P.2.pfm").read_bytes() != (tmp_path / "P.2.pfm").read_bytes()
+
+
+# ------------------------------------------------------------------------------------------------ host form = device form, optional inputs present and absent
+def test_motion_with_each_previous_array_present_and_absent(rt3, renderer):
+    from test_gpu_host_forms import F, H, W, dev, host, mixed_scene, records
+    cr, faces, verts, cam, p = mixed_scene(rt3, renderer)
+    aov = renderer.render_aov(cam.c, p)
+    prev_cr, prev_v = cr.copy(), verts.copy()
+    prev_cr[:, :3] += F(0.05)
+    prev_v[:, :3] -= F(0.03)
+    for ps, pv in ((None, None), (prev_cr, None), (None, prev_v), (prev_cr, prev_v)):
+        plane = renderer.motion(aov, cam.c, prev_center_radius=ps, prev_vertices=pv)
+        t = renderer.motion(records(aov, H, W), cam.c, prev_center_radius=None if ps is None else dev(ps),
+                            prev_vertices=None if pv is None else dev(pv))
+        assert host(t) == plane.tobytes(), (ps is not None, pv is not None)
+
+
+def test_temporal_denoise_with_motion_and_history_present_and_absent(rt3, renderer):
+    from test_gpu_host_forms import F, H, W, host, mixed_scene, records
+    cr, _, _, cam, p = mixed_scene(rt3, renderer)
+    colour, aov = synthetic(rt3, H, W, 3)
+    plane = np.zeros((H, W, 4), F)
+    plane[1:3, 2:6] = (0.2, -0.1, 0.05, 1.0)
+    _, h0 = renderer.denoise_temporal(colour, aov, cam.c, None, iterations=2)
+    _, t0 = renderer.denoise_temporal(records(colour, H, W), records(aov, H, W), cam.c, None, iterations=2)
+    assert host(t0[0]) == h0[0].tobytes()
+    outs = []
+    for prev, tprev in ((None, None), (h0, t0)):
+        for mo in (None, plane):
+            out, hist = renderer.denoise_temporal(colour, aov, cam.c, prev, iterations=2, motion=mo)
+            t_out, t_hist = renderer.denoise_temporal(records(colour, H, W), records(aov, H, W), cam.c, tprev, iterations=2,
+                                                      motion=None if mo is None else records(mo, H, W))
+            assert host(t_out) == out.tobytes() and host(t_hist[0]) == hist[0].tobytes(), (prev is not None, mo is not None)
+            outs.append(out.tobytes() + hist[0].tobytes())
+    assert outs[0] == outs[1]                                           # without a previous frame the plane is checked and not read

@@ -425,3 +425,17 @@ def test_cli_radiance_equals_the_python_call(rt3, renderer, tmp_path):
     rc, out, err = run("-f", "ppm", "-W", "32", "-H", "18", "--scene", "three", "--spp", "4", "--rays", str(tmp_path / "none.bin"),
                        "--radiance", str(tmp_path / "rad2.pfm"), str(tmp_path / "three.ppm"))
     assert rc == -1 and "Could not open" in err
+
+
+# ------------------------------------------------------------------------------------------------ host form = device form, optional inputs present and absent
+def test_radiance_on_five_rays_with_and_without_keys(rt3, renderer):
+    from test_gpu_host_forms import DEPTH, SEED, SPP, dev, host, mixed_scene
+    import torch
+    _, _, _, cam, p = mixed_scene(rt3, renderer)
+    rays = renderer.camera_rays(cam.c, p, 0, 1)[9:14]                  # 5 rays: 20 bytes of keys, no whole number of 16-byte units (the staged segments stay aligned)
+    keys = np.array([40, 3, 77, 12, 5], np.uint32)
+    t_rays = dev(rays).reshape(5, 8)
+    for k in (None, keys):
+        out = renderer.radiance(rays, keys=k, samples=SPP, max_depth=DEPTH, seed=SEED)
+        t = renderer.radiance(t_rays, keys=None if k is None else torch.from_numpy(k.view(np.int32)).cuda(), samples=SPP, max_depth=DEPTH, seed=SEED)
+        assert host(t) == out.tobytes(), k is not None

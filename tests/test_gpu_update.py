@@ -419,3 +419,22 @@ def test_a_range_render_across_an_update_behaves_as_across_a_full_upload(rt3, re
         rc1 = L.rt3_render_path_range(r._ctx, C.byref(cam.c), C.byref(p), 2, 2, ptr(out))
         results.append((rc0, rc1, out.tobytes()))
     assert results[0] == results[1] and results[0][0] == 0
+
+
+# ------------------------------------------------------------------------------------------------ host form = device form, optional inputs present and absent
+def test_update_mesh_with_and_without_faces(rt3, renderer):
+    from test_gpu_host_forms import F, dev, mixed_scene
+    _, faces, verts, cam, p = mixed_scene(rt3, renderer)
+    v2 = verts.copy()
+    v2[:, :3] += F(0.07)
+    f2 = faces[::-1].copy()                                            # the two faces' records swapped: other indices, normals and colours
+    for f in (None, f2):
+        mixed_scene(rt3, renderer)
+        renderer.update_mesh(v2, faces=f)
+        want = [a.tobytes() for a in renderer.mesh_download()] + [renderer.render_aov(cam.c, p).tobytes(), renderer.render_path(cam.c, p).tobytes()]
+        mixed_scene(rt3, renderer)
+        renderer.update_mesh(dev(v2), faces=None if f is None else dev(f))
+        renderer.synchronize()
+        got = [a.tobytes() for a in renderer.mesh_download()] + [renderer.render_aov(cam.c, p).tobytes(), renderer.render_path(cam.c, p).tobytes()]
+        assert got == want, f is not None
+    mixed_scene(rt3, renderer)                                         # (a host-form scene again: regroup() and friends leave torch's stream)
