@@ -34,8 +34,9 @@ extern "C" {
  * filter_tests / bound_tests in rt3_stats (80 bytes).  Still 3 with rt3_update_spheres* / rt3_update_mesh*, with
  * rt3_render_path_adaptive* (one new struct of its own), with rt3_regroup*, with the environment map (rt3_set_environment*), with its
  * importance sampling (RT3_FLAG_ENV_SAMPLING: one flag bit and two test-only functions), with the emitters' (RT3_FLAG_LIGHT_SAMPLING: the same again)
- * with the display transform (rt3_display*: one new struct of its own) and with the lens models (rt3_lens_rays*, rt3_render_lens*,
- * rt3_render_lens_aov*: one new struct of its own): functions were only added, no existing struct changed. */
+ * with the display transform (rt3_display*: one new struct of its own), with the lens models (rt3_lens_rays*, rt3_render_lens*,
+ * rt3_render_lens_aov*: one new struct of its own) and with lens sequences (rt3_denoise_temporal_optic*, rt3_motion_optic*): functions were only
+ * added, no existing struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
 
@@ -648,8 +649,8 @@ typedef struct rt3_lens {      /* 80 bytes */
  * rays); scratch belongs to the context (32 B per ray of a batch, plus 4 B per pixel of keys for a shard); batches are sized by
  * rt3_set_sample_storage_cap at 44 B per (pixel, sample) and the result does not depend on them; the device forms never wait for the device.  Device
  * pointers are 16-byte aligned.
- * Out of scope: thin-lens depth of field for these models, the temporal denoiser and the motion plane (their reprojection is pinhole), the adaptive
- * render. */
+ * Out of scope: thin-lens depth of field for these models and the adaptive render.  (The temporal denoiser and the motion plane of a lens frame:
+ * "Lens sequences", below.) */
 /* Host: origin = from and the frame that looks from `from` towards `at` with `vup` up (forward = unit(at - from), right = unit(forward x vup),
  * up = right x forward); sets model, leaves half_fov_turns and half_extent, zeroes the pads. */
 void rt3_lens_look_at(rt3_lens* lens, uint32_t model, const float from[3], const float at[3], const float vup[3]);
@@ -664,6 +665,60 @@ int  rt3_render_lens_aov_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_pa
 /* Host only, no device and no context: the law above in C for one (pixel, sample) of the whole frame.  RT3_E_ARG for a NULL pointer, a lens the
  * entry points refuse, width or height 0, spp 0, x >= width, y >= height or s >= spp.  tests/lens_ref.py restates it bit for bit. */
 int  rt3_debug_lens_ray(const rt3_lens* lens, const rt3_params* params, uint32_t x, uint32_t y, uint32_t s, rt3_ray* out);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Lens sequences  (DESIGN.md 4.24, 5.2s): the temporal denoiser and the motion plane for frames rendered through a lens
+ * ------------------------------------------------------------------------------------------------- */
+/* rt3_denoise_temporal_optic* is rt3_denoise_temporal_motion* and rt3_motion_optic* is rt3_motion* with a lens where those take a camera: the frame is
+ * the whole W x H frame of rt3_render_lens* / rt3_render_lens_aov* for `lens`, prev_lens the lens of the previous frame (NULL with prev_history for the
+ * first frame).  Everything that does not involve the view is unchanged: the records, the parameters, the consistency tests, the blend, the variance,
+ * the passes, the history, the streams, the scratch, the errors.  What changes (every operation an IEEE f32 one rounded on its own, nothing fused;
+ * dot(a, b) = (ax bx + ay by) + az bz):
+ * The centre ray of pixel (x, y) is the lens law's ray for spp == 1 (no jitter: px = x + 0.5, py = y + 0.5): origin o_p (per pixel for ORTHO) and unit
+ * direction d.  The shown point of a hit is P = o_p + z d per component, z the AOV depth.
+ * turns(c, s), the angle of (c, s) in turns, in [0, 1):
+ *     ac = |c|, as = |s|, hi = max(ac, as), lo = min(ac, as);  NaN unless ac and as are finite and hi > 0;
+ *     t = lo / hi;  z = t * t;  p = a16;  for k in (a14, a12, a10, a8, a6, a4, a2): p = p * z, p = p + k;  p = p * z;  p = p + 1.0f;
+ *     u = (t * p) * 0.159154937f;  if (as > ac) u = 0.25f - u;  if (c < 0) u = 0.5f - u;  if (s < 0) u = 1.0f - u;  if (u >= 1.0f) u = 0.0f
+ *     a2 ... a16 = -0.3333314528, 0.1999355085, -0.1420889944, 0.1065626393, -0.0752896400, 0.0429096138, -0.0161657367, 0.0028662257
+ *     (Abramowitz & Stegun 4.4.49); within 2^-23 turns of atan2.
+ * The previous position.  r = P - o' for a hit ((P + m) - o' for a moved pixel), r = d for a miss, o' the previous lens's origin; an ORTHO miss is not
+ * projected (x' = x, y' = y).  lx = dot(r, right'), ly = dot(r, up'), lz = dot(r, forward');  the depth the history's is compared with is
+ * zhat = sqrtf(dot(r, r)), for ORTHO lz.  Then the frame position (px, py) and x' = px - 0.5f, y' = py - 0.5f:
+ *     EQUIRECT  hxz = sqrtf(lx * lx + lz * lz);  a = turns(-lz, -lx);  b = 2.0f * turns(ly, hxz);  px = a * W;  py = b * H
+ *     FISHEYE   hxy = sqrtf(lx * lx + ly * ly);  tau = turns(lz, hxy);  rr = tau / half_fov_turns';  if hxy > 0: nx = rr * (lx / hxy), ny = rr * (ly / hxy);
+ *               else if tau == 0: nx = ny = 0;  else no history (the pole behind the lens);
+ *               m = 0.5f * (float)min(W, H);  px = nx * m + 0.5f * W;  py = 0.5f * H - ny * m
+ *     ORTHO     nx = lx / half_extent'[0];  ny = ly / half_extent'[1];  px = ((nx + 1.0f) * 0.5f) * W;  py = ((1.0f - ny) * 0.5f) * H
+ *     CUBE      v = (lx, ly, -lz);  (f, m, sc, tc) by the face cases of the environment lookup law;  N = W;
+ *               px = ((sc / m) * 0.5f + 0.5f) * N;  py = (float)(f * N) + ((tc / m) * 0.5f + 0.5f) * N
+ * A NaN x' or y' (r = 0) is no history.  The bilinear taps are the camera's with two changes: EQUIRECT wraps columns (-1 -> W - 1, W -> 0); CUBE skips a
+ * tap outside rows [f N, (f + 1) N) (no filtering across faces, as in the environment map).
+ * Shortcut: when prev_lens equals lens bit for bit in model, origin, the three axes and the model's own parameter (half_fov_turns for FISHEYE,
+ * half_extent for ORTHO; pads and other models' fields are ignored), a pixel that has not moved takes x' = x, y' = y.  A moved pixel is always projected.
+ * Errors: those of rt3_denoise_temporal_motion* and rt3_motion*, with "a camera they refuse" replaced by "a lens the lens entry points refuse for this
+ * W x H" (CUBE needs H = 6 W); prev_lens must have the model of lens.  W, H >= 2.  No scene is needed for the denoiser; rt3_motion_optic reads the
+ * scene on the context as rt3_motion does.
+ * Out of scope: the spatial passes cross the face edges of a stacked cube frame and do not wrap an equirectangular frame's columns (rt3_denoise's
+ * behaviour on those frames); sharded lens frames. */
+int   rt3_denoise_temporal_optic(rt3_ctx* ctx, uint32_t width, uint32_t height, const rt3_lens* lens, const float* colour_rgba, const rt3_aov* aov,
+                                 const rt3_lens* prev_lens, const rt3_history* prev_history, const float* motion,
+                                 const rt3_temporal_params* p, float* out_rgba, rt3_history* out_history);
+int   rt3_denoise_temporal_optic_device(rt3_ctx* ctx, uint32_t width, uint32_t height, const rt3_lens* lens, const void* d_colour_rgba,
+                                        const void* d_aov, const rt3_lens* prev_lens, const void* d_prev_history, const void* d_motion,
+                                        const rt3_temporal_params* p, void* d_out_rgba, void* d_out_history, void* stream);
+int   rt3_motion_optic(rt3_ctx* ctx, uint32_t width, uint32_t height, const rt3_lens* lens, const rt3_aov* aov,
+                       const float* prev_center_radius, uint32_t n_prev_spheres,
+                       const float* prev_vertices_xyzw, uint32_t n_prev_vertices, float* out_motion);
+int   rt3_motion_optic_device(rt3_ctx* ctx, uint32_t width, uint32_t height, const rt3_lens* lens, const void* d_aov,
+                              const void* d_prev_center_radius, uint32_t n_prev_spheres,
+                              const void* d_prev_vertices_xyzw, uint32_t n_prev_vertices, void* d_out_motion, void* stream);
+/* Host only, no device and no context: turns, and the previous position of r in prev_lens's W x H frame: out_xy_depth = (x', y', zhat), *face the
+ * cube face (0 otherwise), *valid = 0 for no history.  An ORTHO miss (is_hit == 0) is not projected: (NaN, NaN, zhat), *valid = 1.  RT3_E_ARG for a
+ * NULL pointer, width or height below 2, or a lens the entry points refuse.  tests/optic_ref.py restates both bit for bit. */
+float rt3_debug_turns(float c, float s);
+int   rt3_debug_optic_pixel(const rt3_lens* prev_lens, uint32_t width, uint32_t height, const float r[3], uint32_t is_hit,
+                            float out_xy_depth[3], uint32_t* face, uint32_t* valid);
 
 /* ---------------------------------------------------------------------------------------------------
  * Environment map  (DESIGN.md 4.19, 5.2n): a cube map answers every Mode-X ray that leaves the scene

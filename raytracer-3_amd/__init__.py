@@ -195,6 +195,24 @@ def lens_ray(lens, params, x, y, s):
     return out[0]
 
 
+def turns(c, s):
+    """The angle of the vector (c, s) in turns, in [0, 1), as the inverse lens law computes it (rt3_debug_turns; no device): float32, NaN for
+    (0, 0) and for non-finite input."""
+    return np.float32(lib().rt3_debug_turns(float(np.float32(c)), float(np.float32(s))))
+
+
+def lens_pixel(prev_lens, width, height, r, is_hit=True):
+    """The inverse lens law on the host (rt3_debug_optic_pixel; no device): where r — a point relative to prev_lens's origin, or for a miss a
+    direction — lies in prev_lens's width x height frame -> (x', y', zhat float32, face, valid).  valid False: no history.  An orthographic miss is
+    not projected: x' and y' are NaN and valid is True."""
+    out = np.zeros(3, np.float32)
+    v = np.ascontiguousarray(r, np.float32).reshape(3)
+    face, valid = C.c_uint32(0), C.c_uint32(0)
+    if lib().rt3_debug_optic_pixel(C.byref(prev_lens), int(width), int(height), _p(v), 1 if is_hit else 0, _p(out), C.byref(face), C.byref(valid)) != 0:
+        raise Fatal("rt3_debug_optic_pixel: a lens the entry points refuse for this frame, or a frame below 2 x 2")
+    return out[0], out[1], out[2], int(face.value), bool(valid.value)
+
+
 class Fatal(RuntimeError):
     """Mirror of CppDebugger::Fatal: every backend error is fatal (Main.cpp:305-308)."""
 
@@ -229,6 +247,8 @@ EXPORTS = [
     "rt3_debug_display_srgb_table",
     "rt3_lens_look_at", "rt3_lens_rays", "rt3_lens_rays_device", "rt3_render_lens", "rt3_render_lens_device", "rt3_render_lens_aov",
     "rt3_render_lens_aov_device", "rt3_debug_lens_ray",
+    "rt3_denoise_temporal_optic", "rt3_denoise_temporal_optic_device", "rt3_motion_optic", "rt3_motion_optic_device", "rt3_debug_turns",
+    "rt3_debug_optic_pixel",
 ]
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
@@ -318,6 +338,11 @@ def lib():
         "rt3_render_lens": (i32, [vp, vp, vp, u32, u32, vp]), "rt3_render_lens_device": (i32, [vp, vp, vp, u32, u32, vp, vp]),
         "rt3_render_lens_aov": (i32, [vp, vp, vp, vp]), "rt3_render_lens_aov_device": (i32, [vp, vp, vp, vp, vp]),
         "rt3_debug_lens_ray": (i32, [vp, vp, u32, u32, u32, vp]),
+        "rt3_denoise_temporal_optic": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rt3_denoise_temporal_optic_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rt3_motion_optic": (i32, [vp, u32, u32, vp, vp, vp, u32, vp, u32, vp]),
+        "rt3_motion_optic_device": (i32, [vp, u32, u32, vp, vp, vp, u32, vp, u32, vp, vp]),
+        "rt3_debug_turns": (f32, [f32, f32]), "rt3_debug_optic_pixel": (i32, [vp, u32, u32, vp, u32, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -1425,7 +1450,21 @@ class HipRenderer(Renderer):
         torch.cuda.current_stream()."""
         p = TEMPORAL_PARAMS(DENOISE_PARAMS(iterations, normal_power, sigma_luminance, sigma_depth), alpha, moments_alpha, depth_tolerance,
                             normal_tolerance)
-        cam = rt3_camera.from_buffer_copy(bytes(camera_c))
+        return self._denoise_temporal(colour, aov, rt3_camera.from_buffer_copy(bytes(camera_c)), prev, motion, p,
+                                      lib().rt3_denoise_temporal_motion, lib().rt3_denoise_temporal_motion_device)
+
+    def denoise_temporal_lens(self, colour, aov, lens, prev=None, motion=None, iterations=5, normal_power=128, sigma_luminance=4.0,
+                              sigma_depth=1.0, alpha=0.2, moments_alpha=0.2, depth_tolerance=2.0, normal_tolerance=0.9):
+        """denoise_temporal for a frame rendered through a lens (rt3_denoise_temporal_optic) -> (out, (history, lens)): colour
+        and aov the whole frame of render_lens / render_lens_aov for `lens`, prev None or what the previous call returned second, motion None
+        or the plane motion_lens() returned for this frame.  numpy or torch as denoise_temporal; torch runs on torch.cuda.current_stream()."""
+        p = TEMPORAL_PARAMS(DENOISE_PARAMS(iterations, normal_power, sigma_luminance, sigma_depth), alpha, moments_alpha, depth_tolerance,
+                            normal_tolerance)
+        return self._denoise_temporal(colour, aov, rt3_lens.from_buffer_copy(bytes(lens)), prev, motion, p,
+                                      lib().rt3_denoise_temporal_optic, lib().rt3_denoise_temporal_optic_device)
+
+    def _denoise_temporal(self, colour, aov, cam, prev, motion, p, host_fn, device_fn):
+        """Both temporal calls: cam is a copy of the frame's view (an rt3_camera or an rt3_lens), host_fn / device_fn the entry points for it."""
         prev_rec, prev_cam = prev if prev is not None else (None, None)
         pc = C.byref(prev_cam) if prev_cam is not None else None
         if type(colour).__module__.startswith("torch"):
@@ -1446,7 +1485,7 @@ class HipRenderer(Renderer):
             out = torch.empty_like(colour)
             hist = torch.empty((h, w, 12), dtype=torch.float32, device=colour.device)
             stream = torch.cuda.current_stream(colour.device).cuda_stream
-            self._check(lib().rt3_denoise_temporal_motion_device(
+            self._check(device_fn(
                 self._ctx, w, h, C.byref(cam), C.c_void_p(colour.data_ptr()), C.c_void_p(aov.data_ptr()), pc,
                 C.c_void_p(prev_rec.data_ptr()) if prev_rec is not None else None,
                 C.c_void_p(motion.data_ptr()) if motion is not None else None, C.byref(p), C.c_void_p(out.data_ptr()),
@@ -1469,8 +1508,7 @@ class HipRenderer(Renderer):
                 raise Fatal("denoise_temporal: motion must be float32 (H, W, 4)")
         out = np.zeros((h, w, 4), np.float32)
         hist = np.zeros((h, w), HISTORY)
-        self._check(lib().rt3_denoise_temporal_motion(self._ctx, w, h, C.byref(cam), _p(c), _p(a), pc, _p(pr), _p(mo), C.byref(p), _p(out),
-                                                      _p(hist)))
+        self._check(host_fn(self._ctx, w, h, C.byref(cam), _p(c), _p(a), pc, _p(pr), _p(mo), C.byref(p), _p(out), _p(hist)))
         return out, (hist, cam)
 
     def motion(self, aov, camera_c, prev_center_radius=None, prev_vertices=None):
@@ -1479,7 +1517,17 @@ class HipRenderer(Renderer):
         ((n_vertices, 4), the merged vertices as mesh_download returns them) are the previous frame's, None for a class that did not move.
         numpy: aov an (H, W) AOV array.  torch: a contiguous tensor of (H, W) 48-byte records and contiguous float32 GPU tensors for the
         previous arrays -> a new tensor, computed on torch.cuda.current_stream()."""
-        cam = rt3_camera.from_buffer_copy(bytes(camera_c))
+        return self._motion(aov, rt3_camera.from_buffer_copy(bytes(camera_c)), prev_center_radius, prev_vertices, lib().rt3_motion,
+                            lib().rt3_motion_device)
+
+    def motion_lens(self, aov, lens, prev_center_radius=None, prev_vertices=None):
+        """motion for a frame rendered through a lens (rt3_motion_optic): aov the AOVs of render_lens_aov for `lens`; the
+        shown point lies on the lens's centre ray.  numpy or torch as motion."""
+        return self._motion(aov, rt3_lens.from_buffer_copy(bytes(lens)), prev_center_radius, prev_vertices, lib().rt3_motion_optic,
+                            lib().rt3_motion_optic_device)
+
+    def _motion(self, aov, cam, prev_center_radius, prev_vertices, host_fn, device_fn):
+        """Both motion calls: cam is a copy of the frame's view (an rt3_camera or an rt3_lens), host_fn / device_fn the entry points for it."""
         if type(aov).__module__.startswith("torch"):
             import torch
             if not aov.is_cuda or aov.dim() < 2 or aov.numel() * aov.element_size() != aov.shape[0] * aov.shape[1] * 48 or not aov.is_contiguous():
@@ -1496,8 +1544,7 @@ class HipRenderer(Renderer):
                 ptrs += [C.c_void_p(t.data_ptr()), t.shape[0]]
             out = torch.empty((h, w, 4), dtype=torch.float32, device=aov.device)
             stream = torch.cuda.current_stream(aov.device).cuda_stream
-            self._check(lib().rt3_motion_device(self._ctx, w, h, C.byref(cam), C.c_void_p(aov.data_ptr()), *ptrs, C.c_void_p(out.data_ptr()),
-                                                C.c_void_p(stream)))
+            self._check(device_fn(self._ctx, w, h, C.byref(cam), C.c_void_p(aov.data_ptr()), *ptrs, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
             return out
         a = np.ascontiguousarray(aov)
         if a.dtype != AOV or a.ndim != 2:
@@ -1506,8 +1553,7 @@ class HipRenderer(Renderer):
         ps = None if prev_center_radius is None else np.ascontiguousarray(prev_center_radius, np.float32).reshape(-1, 4)
         pv = None if prev_vertices is None else np.ascontiguousarray(prev_vertices, np.float32).reshape(-1, 4)
         out = np.zeros((h, w, 4), np.float32)
-        self._check(lib().rt3_motion(self._ctx, w, h, C.byref(cam), _p(a), _p(ps), 0 if ps is None else len(ps), _p(pv),
-                                     0 if pv is None else len(pv), _p(out)))
+        self._check(host_fn(self._ctx, w, h, C.byref(cam), _p(a), _p(ps), 0 if ps is None else len(ps), _p(pv), 0 if pv is None else len(pv), _p(out)))
         return out
 
     def set_sample_storage_cap(self, nbytes):

@@ -4,11 +4,15 @@
 // of DESIGN.md 4.11 with no contraction (the library builds with -ffp-contract=off), so tests/denoise_ref.py restates it in numpy.
 // A translation unit of its own (gfx950 only): the kernels share nothing with the render path, and compiled apart they add about 2 s to the
 // build instead of about 14 s inside rt3_device.hip.  rt3_device.hip checks the arguments, owns the scratch and calls denoise_launch().
+// k_temporal_reproject and k_motion take the view as a template parameter: the pinhole camera, or a lens model whose law is rt3_lens_law.hpp's
+// (DESIGN.md 4.24, 5.2s).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "rt3_denoise.hpp"
+#include "rt3_lens_law.hpp"
 
 namespace {
 
@@ -215,14 +219,30 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_denoise_atrous(const Deno
     }
 }
 
-// What k_temporal_reproject reads besides DenoiseArgs: this frame's camera, the previous camera's constants, the parameters.
-struct TemporalArgs {
+// The view a frame was rendered through, a compile-time choice of k_temporal_reproject and k_motion: the pinhole camera, or one of the lens
+// models (RT3_LENS_*).  The model is the same for every pixel of a launch, so it is a template parameter, not a per-lane switch.
+constexpr uint32_t kViewCamera = 0;
+
+// The camera's part of k_temporal_reproject's arguments: this frame's camera and the previous camera's constants.
+struct CameraReproject {
     float ox, oy, oz, hx, hy, hz, vx, vy, vz, lx, ly, lz;      // this frame's camera
     float pox, poy, poz, plx, ply, plz;                        // o' and L = llc' - o'
     float nx, ny, nz, aux, auy, auz, avx, avy, avz, ln;        // n = h x v, a_u, a_v, L . n
+};
+// The camera's part of k_motion's arguments: this frame's camera.
+struct CameraRays { float ox, oy, oz, hx, hy, hz, vx, vy, vz, lx, ly, lz; };
+// A lens frame's part of either: this frame's lens, the previous one (k_motion does not read it), the frame, and whether the two
+// lenses are equal in every bit the inverse law reads.
+struct LensArgs { rt3_lens lens, prev; uint32_t width, height, same; };
+
+// What k_temporal_reproject reads besides DenoiseArgs: the view, then the parameters.
+template <class View>
+struct TemporalArgs {
+    View view;
     uint32_t has_prev, same_cam;
     float alpha, moments_alpha, depth_tolerance, normal_tolerance;
 };
+template <uint32_t VIEW> using TemporalArgsOf = TemporalArgs<std::conditional_t<VIEW == kViewCamera, CameraReproject, LensArgs>>;
 
 __device__ __forceinline__ float dn_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
@@ -230,9 +250,10 @@ __device__ __forceinline__ float dn_dot(float ax, float ay, float az, float bx, 
 // blended I, the guide and gz planes as k_denoise_prepare writes them, and the history record of the pixel with (I, length) in its first
 // float4 (pass 0 replaces I), (M1, M2, depth, 0) and (normal, 0).  MOTION: a pixel that hit and whose motion record
 // (m, moved) has moved != 0 adds m to its world point and is projected even under a byte-equal camera; every other pixel takes the
-// operations of the MOTION = false kernel.
-template <bool MOTION>
-__global__ __launch_bounds__(kDnTile * kDnTile) void k_temporal_reproject(const DenoiseArgs D, const TemporalArgs T,
+// operations of the MOTION = false kernel.  VIEW: kViewCamera, or the lens model of both lenses: steps 2 and 3 are then the
+// lens's centre ray and rt3lens::project, and step 4 wraps an equirectangular frame's columns and keeps a cube frame's taps on the face.
+template <uint32_t VIEW, bool MOTION>
+__global__ __launch_bounds__(kDnTile * kDnTile) void k_temporal_reproject(const DenoiseArgs D, const TemporalArgsOf<VIEW> T,
                                                                          const float4* __restrict__ colour, const float4* __restrict__ aov,
                                                                          const float4* __restrict__ prev, float4* __restrict__ il,
                                                                          float4* __restrict__ guide, float* __restrict__ gz,
@@ -260,40 +281,75 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_temporal_reproject(const 
 
     float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, s1 = 0.0f, s2 = 0.0f, nmin = __builtin_inff();
     if (T.has_prev) {
-        // 2: the world point of the pixel-centre ray, relative to the previous origin (the sky: the direction)
-        const float u = (float)x / ((float)W - 1.0f), v = (float)(H - 1 - y) / ((float)H - 1.0f);
-        const float dx = ((T.lx + u * T.hx) + v * T.vx) - T.ox;
-        const float dy = ((T.ly + u * T.hy) + v * T.vy) - T.oy;
-        const float dz = ((T.lz + u * T.hz) + v * T.vz) - T.oz;
-        const float inv = 1.0f / __builtin_sqrtf(dn_dot(dx, dy, dz, dx, dy, dz));
-        const float ux = dx * inv, uy = dy * inv, uz = dz * inv;
         const bool hit = !__builtin_isinf(n.w);
-        float rx = hit ? (T.ox + n.w * ux) - T.pox : ux;
-        float ry = hit ? (T.oy + n.w * uy) - T.poy : uy;
-        float rz = hit ? (T.oz + n.w * uz) - T.poz : uz;
-        bool moved = false;
-        if (MOTION && hit) {
-            const float4 m = motion[p];
-            moved = m.w != 0.0f;
-            if (moved) {
-                rx = ((T.ox + n.w * ux) + m.x) - T.pox;
-                ry = ((T.oy + n.w * uy) + m.y) - T.poy;
-                rz = ((T.oz + n.w * uz) + m.z) - T.poz;
-            }
-        }
-        // 3: project into the previous camera (skipped for a byte-equal camera: every pixel that has not moved maps to itself)
-        float xp = (float)x, yp = (float)y;
+        float rx, ry, rz, xp, yp;
         bool ok = true;
-        if (!T.same_cam || moved) {
-            const float sc = T.ln / dn_dot(rx, ry, rz, T.nx, T.ny, T.nz);
-            ok = __builtin_isfinite(sc) && sc > 0.0f;
-            const float px = sc * rx - T.plx, py = sc * ry - T.ply, pz = sc * rz - T.plz;
-            xp = dn_dot(px, py, pz, T.aux, T.auy, T.auz) * ((float)W - 1.0f);
-            yp = ((float)H - 1.0f) - dn_dot(px, py, pz, T.avx, T.avy, T.avz) * ((float)H - 1.0f);
+        uint32_t face = 0;                                          // RT3_LENS_CUBE: the face the taps stay on
+        if constexpr (VIEW == kViewCamera) {
+            const CameraReproject& V = T.view;
+            // 2: the world point of the pixel-centre ray, relative to the previous origin (the sky: the direction)
+            const float u = (float)x / ((float)W - 1.0f), v = (float)(H - 1 - y) / ((float)H - 1.0f);
+            const float dx = ((V.lx + u * V.hx) + v * V.vx) - V.ox;
+            const float dy = ((V.ly + u * V.hy) + v * V.vy) - V.oy;
+            const float dz = ((V.lz + u * V.hz) + v * V.vz) - V.oz;
+            const float inv = 1.0f / __builtin_sqrtf(dn_dot(dx, dy, dz, dx, dy, dz));
+            const float ux = dx * inv, uy = dy * inv, uz = dz * inv;
+            rx = hit ? (V.ox + n.w * ux) - V.pox : ux;
+            ry = hit ? (V.oy + n.w * uy) - V.poy : uy;
+            rz = hit ? (V.oz + n.w * uz) - V.poz : uz;
+            bool moved = false;
+            if (MOTION && hit) {
+                const float4 m = motion[p];
+                moved = m.w != 0.0f;
+                if (moved) {
+                    rx = ((V.ox + n.w * ux) + m.x) - V.pox;
+                    ry = ((V.oy + n.w * uy) + m.y) - V.poy;
+                    rz = ((V.oz + n.w * uz) + m.z) - V.poz;
+                }
+            }
+            // 3: project into the previous camera (skipped for a byte-equal camera: every pixel that has not moved maps to itself)
+            xp = (float)x; yp = (float)y;
+            if (!T.same_cam || moved) {
+                const float sc = V.ln / dn_dot(rx, ry, rz, V.nx, V.ny, V.nz);
+                ok = __builtin_isfinite(sc) && sc > 0.0f;
+                const float px = sc * rx - V.plx, py = sc * ry - V.ply, pz = sc * rz - V.plz;
+                xp = dn_dot(px, py, pz, V.aux, V.auy, V.auz) * ((float)W - 1.0f);
+                yp = ((float)H - 1.0f) - dn_dot(px, py, pz, V.avx, V.avy, V.avz) * ((float)H - 1.0f);
+            }
+        } else {
+            const LensArgs& V = T.view;
+            // 2 (4.24): the shown point on the lens's centre ray (spp 1: no jitter), relative to the previous origin (a miss: the direction)
+            const rt3lens::Frame F{ V.width, V.height, 1u, 0u, 0u };
+            float o[3], d[3];
+            rt3lens::ray<VIEW>(V.lens, F, (uint32_t)x, (uint32_t)y, 0u, o, d);
+            rx = hit ? (o[0] + n.w * d[0]) - V.prev.origin[0] : d[0];
+            ry = hit ? (o[1] + n.w * d[1]) - V.prev.origin[1] : d[1];
+            rz = hit ? (o[2] + n.w * d[2]) - V.prev.origin[2] : d[2];
+            bool moved = false;
+            if (MOTION && hit) {
+                const float4 m = motion[p];
+                moved = m.w != 0.0f;
+                if (moved) {
+                    rx = ((o[0] + n.w * d[0]) + m.x) - V.prev.origin[0];
+                    ry = ((o[1] + n.w * d[1]) + m.y) - V.prev.origin[1];
+                    rz = ((o[2] + n.w * d[2]) + m.z) - V.prev.origin[2];
+                }
+            }
+            // 3 (4.24): the inverse law of the previous lens (skipped for an equal lens and a pixel that has not moved, and for an orthographic
+            // miss, whose direction says nothing about where it was)
+            xp = (float)x; yp = (float)y;
+            if (VIEW == RT3_LENS_CUBE) face = (uint32_t)y / V.width;
+            if ((!V.same || moved) && !(VIEW == RT3_LENS_ORTHO && !hit)) {
+                const float r[3] = { rx, ry, rz };
+                float zunused;
+                ok = rt3lens::project<VIEW>(V.prev, V.width, V.height, r, xp, yp, zunused, face);
+            }
         }
         // 4: the bilinear taps that lie in the frame and are consistent (no tap can when x' or y' is outside (-1, W) x (-1, H), or NaN)
         if (ok && xp > -1.0f && xp < (float)W && yp > -1.0f && yp < (float)H) {
-            const float zhat = __builtin_sqrtf(dn_dot(rx, ry, rz, rx, ry, rz));
+            float zhat;
+            if constexpr (VIEW == RT3_LENS_ORTHO) zhat = dn_dot(rx, ry, rz, T.view.prev.forward[0], T.view.prev.forward[1], T.view.prev.forward[2]);
+            else zhat = __builtin_sqrtf(dn_dot(rx, ry, rz, rx, ry, rz));
             const float bound = T.depth_tolerance * (g + 1e-3f * zhat);
             const float x0 = __builtin_floorf(xp), y0 = __builtin_floorf(yp);
             const float fx = xp - x0, fy = yp - y0;
@@ -301,7 +357,10 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_temporal_reproject(const 
             const float wt[4] = { (1.0f - fx) * (1.0f - fy), fx * (1.0f - fy), (1.0f - fx) * fy, fx * fy };
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const int qx = ix + (k & 1), qy = iy + (k >> 1);
+                int qx = ix + (k & 1);
+                const int qy = iy + (k >> 1);
+                if (VIEW == RT3_LENS_EQUIRECT) qx = qx < 0 ? qx + W : qx >= W ? qx - W : qx;           // the columns wrap: -1 -> W - 1, W -> 0
+                if (VIEW == RT3_LENS_CUBE && (qy < (int)(face * (uint32_t)W) || qy >= (int)((face + 1u) * (uint32_t)W))) continue;   // no tap across faces
                 if (wt[k] == 0.0f || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
                 const size_t q = 3 * (size_t)(qy * W + qx);
                 const float4 hm = prev[q + 1], hn = prev[q + 2];
@@ -345,10 +404,12 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_temporal_reproject(const 
 
 // What k_motion reads: this frame's camera, the context's current primitives in the caller's order and the caller's
 // previous ones (nullptr: that class did not move).
+template <class View>
 struct MotionArgs {
     uint32_t width, height, tiles_x;
     uint32_t n_sph, n_faces, n_verts;
-    float ox, oy, oz, hx, hy, hz, vx, vy, vz, lx, ly, lz;      // this frame's camera
+    using view_type = View;
+    View view;                                                 // this frame's camera, or its lens
     const float4* __restrict__ aov;                            // rt3_aov records (3 float4 each)
     const float4* __restrict__ sph;                            // (C, r) as rt3_set_spheres took them
     const float* __restrict__ sph_invr;                        // 1 / r
@@ -360,7 +421,10 @@ struct MotionArgs {
 
 // per pixel the world-space displacement from the point it shows to where that surface point was in the previous frame,
 // (mx, my, mz, 1), or (0, 0, 0, 0) where nothing moved or nothing is known.  Every gather index is checked against its buffer first.
-__global__ __launch_bounds__(kDnTile * kDnTile) void k_motion(const MotionArgs M, float4* __restrict__ out) {
+// VIEW: kViewCamera, or the lens model: step 2's point then lies on the lens's centre ray.
+template <uint32_t VIEW> using MotionArgsOf = MotionArgs<std::conditional_t<VIEW == kViewCamera, CameraRays, LensArgs>>;
+template <uint32_t VIEW>
+__global__ __launch_bounds__(kDnTile * kDnTile) void k_motion(const MotionArgsOf<VIEW> M, float4* __restrict__ out) {
     const uint32_t ty = blockIdx.x / M.tiles_x, tx = blockIdx.x - ty * M.tiles_x;
     const int x = (int)(tx * kDnTile + threadIdx.x), y = (int)(ty * kDnTile + threadIdx.y);
     const int W = (int)M.width, H = (int)M.height;
@@ -374,12 +438,21 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_motion(const MotionArgs M
     const bool face = kind == 1u && M.prev_verts && index < M.n_faces;          // RT3_HIT_FACE
     if (!__builtin_isinf(z) && (sphere || face)) {
         // 2: the shown point on the pixel-centre ray (4.12 step 2)
-        const float u = (float)x / ((float)W - 1.0f), v = (float)(H - 1 - y) / ((float)H - 1.0f);
-        const float dx = ((M.lx + u * M.hx) + v * M.vx) - M.ox;
-        const float dy = ((M.ly + u * M.hy) + v * M.vy) - M.oy;
-        const float dz = ((M.lz + u * M.hz) + v * M.vz) - M.oz;
-        const float inv = 1.0f / __builtin_sqrtf(dn_dot(dx, dy, dz, dx, dy, dz));
-        const float px = M.ox + z * (dx * inv), py = M.oy + z * (dy * inv), pz = M.oz + z * (dz * inv);
+        float px, py, pz;
+        if constexpr (VIEW == kViewCamera) {
+            const CameraRays& V = M.view;
+            const float u = (float)x / ((float)W - 1.0f), v = (float)(H - 1 - y) / ((float)H - 1.0f);
+            const float dx = ((V.lx + u * V.hx) + v * V.vx) - V.ox;
+            const float dy = ((V.ly + u * V.hy) + v * V.vy) - V.oy;
+            const float dz = ((V.lz + u * V.hz) + v * V.vz) - V.oz;
+            const float inv = 1.0f / __builtin_sqrtf(dn_dot(dx, dy, dz, dx, dy, dz));
+            px = V.ox + z * (dx * inv); py = V.oy + z * (dy * inv); pz = V.oz + z * (dz * inv);
+        } else {
+            const rt3lens::Frame F{ M.view.width, M.view.height, 1u, 0u, 0u };
+            float o[3], d[3];
+            rt3lens::ray<VIEW>(M.view.lens, F, (uint32_t)x, (uint32_t)y, 0u, o, d);
+            px = o[0] + z * d[0]; py = o[1] + z * d[1]; pz = o[2] + z * d[2];
+        }
         if (sphere) {
             // 3: translation and uniform scaling about the centre
             const float4 c = M.sph[index], q = M.prev_sph[index];
@@ -457,6 +530,24 @@ hipError_t denoise_launch(const DenoiseLaunch& L, hipStream_t stream) {
     return hipSuccess;
 }
 
+// The launch argument of the lens forms: both lenses by value, the frame, and whether the inverse law may take the shortcut.
+static LensArgs lens_args(const rt3_lens* lens, const rt3_lens* prev, uint32_t w, uint32_t h) {
+    LensArgs A;
+    A.lens = *lens; A.prev = *prev;
+    A.width = w; A.height = h;
+    A.same = rt3lens::same_optic(*lens, *prev) ? 1u : 0u;
+    return A;
+}
+
+template <uint32_t VIEW>
+static void launch_reproject(dim3 grid, dim3 block, hipStream_t stream, const DenoiseArgs& D, const TemporalArgsOf<VIEW>& A, const DenoiseLaunch& L,
+                             const TemporalLaunch& T, float4* pa, float4* guide, float* gz) {
+    if (T.motion) hipLaunchKernelGGL((k_temporal_reproject<VIEW, true>), grid, block, 0, stream, D, A, (const float4*)L.colour, (const float4*)L.aov,
+                                     (const float4*)T.prev_history, pa, guide, gz, (float4*)T.out_history, (const float4*)T.motion);
+    else hipLaunchKernelGGL((k_temporal_reproject<VIEW, false>), grid, block, 0, stream, D, A, (const float4*)L.colour, (const float4*)L.aov,
+                            (const float4*)T.prev_history, pa, guide, gz, (float4*)T.out_history, nullptr);
+}
+
 hipError_t temporal_launch(const TemporalLaunch& T, hipStream_t stream) {
     const DenoiseLaunch& L = T.base;
     const uint32_t w = L.width, h = L.height;
@@ -472,26 +563,37 @@ hipError_t temporal_launch(const TemporalLaunch& T, hipStream_t stream) {
     while ((1u << D.squarings) < L.normal_power) D.squarings++;
     D.sigma_l = L.sigma_l; D.sigma_z = L.sigma_z;
     D.guide = guide; D.gz = gz;
-    TemporalArgs A;
-    A.ox = T.cam[0]; A.oy = T.cam[1]; A.oz = T.cam[2];
-    A.hx = T.cam[3]; A.hy = T.cam[4]; A.hz = T.cam[5];
-    A.vx = T.cam[6]; A.vy = T.cam[7]; A.vz = T.cam[8];
-    A.lx = T.cam[9]; A.ly = T.cam[10]; A.lz = T.cam[11];
-    A.pox = T.prev_o[0]; A.poy = T.prev_o[1]; A.poz = T.prev_o[2];
-    A.plx = T.prev_l[0]; A.ply = T.prev_l[1]; A.plz = T.prev_l[2];
-    A.nx = T.prev_n[0]; A.ny = T.prev_n[1]; A.nz = T.prev_n[2];
-    A.aux = T.a_u[0]; A.auy = T.a_u[1]; A.auz = T.a_u[2];
-    A.avx = T.a_v[0]; A.avy = T.a_v[1]; A.avz = T.a_v[2];
-    A.ln = T.ln;
-    A.has_prev = T.has_prev; A.same_cam = T.same_cam;
-    A.alpha = T.alpha; A.moments_alpha = T.moments_alpha; A.depth_tolerance = T.depth_tolerance; A.normal_tolerance = T.normal_tolerance;
     const dim3 grid(D.tiles_x * ((h + kDnTile - 1) / kDnTile)), block(kDnTile, kDnTile);
     const float4* aov = (const float4*)L.aov;
     float4* const hist = (float4*)T.out_history;
-    if (T.motion) hipLaunchKernelGGL(k_temporal_reproject<true>, grid, block, 0, stream, D, A, (const float4*)L.colour, aov,
-                                     (const float4*)T.prev_history, pa, guide, gz, hist, (const float4*)T.motion);
-    else hipLaunchKernelGGL(k_temporal_reproject<false>, grid, block, 0, stream, D, A, (const float4*)L.colour, aov,
-                            (const float4*)T.prev_history, pa, guide, gz, hist, nullptr);
+    if (T.lens) {
+        TemporalArgs<LensArgs> A;
+        A.view = lens_args(T.lens, T.has_prev ? T.prev_lens : T.lens, w, h);
+        A.has_prev = T.has_prev; A.same_cam = A.view.same;
+        A.alpha = T.alpha; A.moments_alpha = T.moments_alpha; A.depth_tolerance = T.depth_tolerance; A.normal_tolerance = T.normal_tolerance;
+        switch (T.lens->model) {
+        case RT3_LENS_EQUIRECT: launch_reproject<RT3_LENS_EQUIRECT>(grid, block, stream, D, A, L, T, pa, guide, gz); break;
+        case RT3_LENS_FISHEYE:  launch_reproject<RT3_LENS_FISHEYE>(grid, block, stream, D, A, L, T, pa, guide, gz); break;
+        case RT3_LENS_ORTHO:    launch_reproject<RT3_LENS_ORTHO>(grid, block, stream, D, A, L, T, pa, guide, gz); break;
+        default:                launch_reproject<RT3_LENS_CUBE>(grid, block, stream, D, A, L, T, pa, guide, gz); break;
+        }
+    } else {
+        TemporalArgs<CameraReproject> A;
+        CameraReproject& V = A.view;
+        V.ox = T.cam[0]; V.oy = T.cam[1]; V.oz = T.cam[2];
+        V.hx = T.cam[3]; V.hy = T.cam[4]; V.hz = T.cam[5];
+        V.vx = T.cam[6]; V.vy = T.cam[7]; V.vz = T.cam[8];
+        V.lx = T.cam[9]; V.ly = T.cam[10]; V.lz = T.cam[11];
+        V.pox = T.prev_o[0]; V.poy = T.prev_o[1]; V.poz = T.prev_o[2];
+        V.plx = T.prev_l[0]; V.ply = T.prev_l[1]; V.plz = T.prev_l[2];
+        V.nx = T.prev_n[0]; V.ny = T.prev_n[1]; V.nz = T.prev_n[2];
+        V.aux = T.a_u[0]; V.auy = T.a_u[1]; V.auz = T.a_u[2];
+        V.avx = T.a_v[0]; V.avy = T.a_v[1]; V.avz = T.a_v[2];
+        V.ln = T.ln;
+        A.has_prev = T.has_prev; A.same_cam = T.same_cam;
+        A.alpha = T.alpha; A.moments_alpha = T.moments_alpha; A.depth_tolerance = T.depth_tolerance; A.normal_tolerance = T.normal_tolerance;
+        launch_reproject<kViewCamera>(grid, block, stream, D, A, L, T, pa, guide, gz);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_denoise_moments<true>, grid, block, 0, stream, D, (const float4*)pa, pb, (const float4*)hist);
@@ -510,19 +612,36 @@ hipError_t temporal_launch(const TemporalLaunch& T, hipStream_t stream) {
     return hipSuccess;
 }
 
-hipError_t motion_launch(const MotionLaunch& L, hipStream_t stream) {
-    MotionArgs M;
+template <uint32_t VIEW>
+static void launch_motion(const MotionLaunch& L, const typename MotionArgsOf<VIEW>::view_type& view, hipStream_t stream) {
+    MotionArgsOf<VIEW> M;
     M.width = L.width; M.height = L.height;
     M.tiles_x = (L.width + kDnTile - 1) / kDnTile;
     M.n_sph = L.n_sph; M.n_faces = L.n_faces; M.n_verts = L.n_verts;
-    M.ox = L.cam[0]; M.oy = L.cam[1]; M.oz = L.cam[2];
-    M.hx = L.cam[3]; M.hy = L.cam[4]; M.hz = L.cam[5];
-    M.vx = L.cam[6]; M.vy = L.cam[7]; M.vz = L.cam[8];
-    M.lx = L.cam[9]; M.ly = L.cam[10]; M.lz = L.cam[11];
+    M.view = view;
     M.aov = (const float4*)L.aov;
     M.sph = (const float4*)L.sph; M.sph_invr = L.sph_invr; M.prev_sph = (const float4*)L.prev_sph;
     M.gfaces = (const uint4*)L.gfaces; M.verts = (const float4*)L.verts; M.prev_verts = (const float4*)L.prev_verts;
     const dim3 grid(M.tiles_x * ((L.height + kDnTile - 1) / kDnTile)), block(kDnTile, kDnTile);
-    hipLaunchKernelGGL(k_motion, grid, block, 0, stream, M, (float4*)L.out);
+    hipLaunchKernelGGL(k_motion<VIEW>, grid, block, 0, stream, M, (float4*)L.out);
+}
+
+hipError_t motion_launch(const MotionLaunch& L, hipStream_t stream) {
+    if (L.lens) {
+        const LensArgs V = lens_args(L.lens, L.lens, L.width, L.height);
+        switch (L.lens->model) {
+        case RT3_LENS_EQUIRECT: launch_motion<RT3_LENS_EQUIRECT>(L, V, stream); break;
+        case RT3_LENS_FISHEYE:  launch_motion<RT3_LENS_FISHEYE>(L, V, stream); break;
+        case RT3_LENS_ORTHO:    launch_motion<RT3_LENS_ORTHO>(L, V, stream); break;
+        default:                launch_motion<RT3_LENS_CUBE>(L, V, stream); break;
+        }
+    } else {
+        CameraRays V;
+        V.ox = L.cam[0]; V.oy = L.cam[1]; V.oz = L.cam[2];
+        V.hx = L.cam[3]; V.hy = L.cam[4]; V.hz = L.cam[5];
+        V.vx = L.cam[6]; V.vy = L.cam[7]; V.vz = L.cam[8];
+        V.lx = L.cam[9]; V.ly = L.cam[10]; V.lz = L.cam[11];
+        launch_motion<kViewCamera>(L, V, stream);
+    }
     return hipGetLastError();
 }

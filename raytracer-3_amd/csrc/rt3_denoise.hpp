@@ -1,5 +1,6 @@
 // rt3_denoise.hpp — what rt3_device.hip needs of the denoiser (rt3_denoise.hip): its launchers.
 #pragma once
+#include "rt3.h"
 
 // One rt3_denoise_device call once its arguments have been checked: k_denoise_prepare, k_denoise_moments and `iterations` a-trous passes on
 // `stream`.  scratch: 3 * width * height float4 plus width * height floats (the two (I, v) planes, the guide plane, the depth slopes).
@@ -27,6 +28,8 @@ struct TemporalLaunch {
     const void* prev_history;               // width * height rt3_history (3 float4 each), or nullptr without has_prev
     void* out_history;                      // width * height rt3_history
     const void* motion;                     // width * height float4 (m, moved) as motion_launch writes them, or nullptr
+    const rt3_lens* lens;                   // nullptr: the camera above.  Else a lens frame: this frame's lens and, with has_prev,
+    const rt3_lens* prev_lens;              // the previous one, of the same model; the camera fields above are not read
 };
 hipError_t temporal_launch(const TemporalLaunch& L, hipStream_t stream);
 
@@ -36,6 +39,7 @@ hipError_t temporal_launch(const TemporalLaunch& L, hipStream_t stream);
 struct MotionLaunch {
     uint32_t width, height;
     float cam[12];                          // this frame's rt3_camera
+    const rt3_lens* lens;                   // nullptr: the camera.  Else this frame's lens, and cam is not read
     const void* aov;                        // width * height rt3_aov
     const void* sph;                        // n_sph float4 (C, r): the records rt3_set_spheres took
     const float* sph_invr;                  // n_sph reciprocal radii

@@ -2455,12 +2455,13 @@ static bool camera_ok(const rt3_camera* c) {
     return dot3h(l, n) != 0.0f;
 }
 
-static int temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* colour, const void* aov,
-                           const rt3_camera* prev_cam, const void* prev_history, const void* motion, const rt3_temporal_params* p,
-                           const void* out, const void* out_history) {
-    if (!p || !cam) return fail(ctx, RT3_E_ARG, "p / cam is NULL");
+// What every form checks.  view / prev_view: the cameras, or the lenses (what = "cam" / "lens"); views_ok refuses them (0: fine).
+static int temporal_checks_of(rt3_ctx* ctx, uint32_t w, uint32_t h, const char* what, const void* view, const void* colour, const void* aov,
+                              const void* prev_view, const void* prev_history, const void* motion, const rt3_temporal_params* p,
+                              const void* out, const void* out_history, const std::function<int()>& views_ok) {
+    if (!p || !view) return fail(ctx, RT3_E_ARG, std::string("p / ") + what + " is NULL");
     if (!colour || !aov || !out || !out_history) return fail(ctx, RT3_E_ARG, "colour / aov / out / out_history is NULL");
-    if (!prev_cam != !prev_history) return fail(ctx, RT3_E_ARG, "prev_cam and prev_history must both be NULL or both be non-NULL");
+    if (!prev_view != !prev_history) return fail(ctx, RT3_E_ARG, std::string("prev_") + what + " and prev_history must both be NULL or both be non-NULL");
     if (w < 2 || h < 2 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must be at least 2 x 2 and have at most 2^26 pixels");
     int rc = denoise_checks(ctx, w, h, colour, aov, &p->spatial, out);
     if (rc) return rc;
@@ -2468,8 +2469,7 @@ static int temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camer
         return fail(ctx, RT3_E_ARG, "alpha and moments_alpha must be in (0, 1]");
     if (!std::isfinite(p->depth_tolerance) || !(p->depth_tolerance > 0.0f)) return fail(ctx, RT3_E_ARG, "depth_tolerance must be finite and > 0");
     if (!(p->normal_tolerance >= -1.0f && p->normal_tolerance <= 1.0f)) return fail(ctx, RT3_E_ARG, "normal_tolerance must be in [-1, 1]");
-    if (!camera_ok(cam) || (prev_cam && !camera_ok(prev_cam)))
-        return fail(ctx, RT3_E_ARG, "a camera has a non-finite field, horizontal x vertical = 0, or an image plane through its origin");
+    if ((rc = views_ok())) return rc;
     const size_t npix = (size_t)w * h, nf = npix * sizeof(float4), nh = npix * sizeof(rt3_history);
     const struct { const void* ptr; size_t n; } in[4] = { { colour, nf }, { aov, npix * sizeof(rt3_aov) }, { prev_history, nh }, { motion, nf } };
     for (const auto& i : in)
@@ -2477,6 +2477,16 @@ static int temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camer
             return fail(ctx, RT3_E_ARG, "an output overlaps an input");
     if (ranges_overlap(out, nf, out_history, nh)) return fail(ctx, RT3_E_ARG, "out_rgba and out_history overlap");
     return 0;
+}
+
+static int temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* colour, const void* aov,
+                           const rt3_camera* prev_cam, const void* prev_history, const void* motion, const rt3_temporal_params* p,
+                           const void* out, const void* out_history) {
+    return temporal_checks_of(ctx, w, h, "cam", cam, colour, aov, prev_cam, prev_history, motion, p, out, out_history, [&]() {
+        if (!camera_ok(cam) || (prev_cam && !camera_ok(prev_cam)))
+            return fail(ctx, RT3_E_ARG, "a camera has a non-finite field, horizontal x vertical = 0, or an image plane through its origin");
+        return 0;
+    });
 }
 
 // k_temporal_reproject -> k_denoise_moments<true> -> the passes (pass 0 also writes the history colour); the same scratch as rt3_denoise.
@@ -2552,12 +2562,15 @@ static_assert(sizeof(rt3_temporal_params) == 32, "rt3.h: rt3_temporal_params");
 
 // ---- The motion plane
 // What both forms check: the frame, the camera, and the previous arrays against the scene on the context.
-static int motion_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* aov, const void* prev_sph, uint32_t n_prev_sph,
-                         const void* prev_verts, uint32_t n_prev_verts, const void* out) {
-    if (!cam || !aov || !out) return fail(ctx, RT3_E_ARG, "cam / aov / out_motion is NULL");
+// cam or lens: the frame's view, exactly one of them.
+static int motion_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_lens* lens, const void* aov, const void* prev_sph,
+                         uint32_t n_prev_sph, const void* prev_verts, uint32_t n_prev_verts, const void* out) {
+    if ((!cam && !lens) || !aov || !out) return fail(ctx, RT3_E_ARG, "cam / lens / aov / out_motion is NULL");
     if (w < 2 || h < 2 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must be at least 2 x 2 and have at most 2^26 pixels");
-    if (!camera_ok(cam))
+    if (cam && !camera_ok(cam))
         return fail(ctx, RT3_E_ARG, "the camera has a non-finite field, horizontal x vertical = 0, or an image plane through its origin");
+    if (lens)
+        if (const char* why = rt3lens::refusal(lens, w, h)) return fail(ctx, RT3_E_ARG, why);
     if ((!prev_sph && n_prev_sph) || (!prev_verts && n_prev_verts)) return fail(ctx, RT3_E_ARG, "a NULL previous array must have a count of 0");
     if (prev_sph && ctx->n_sph == 0) return fail(ctx, RT3_E_STATE, "previous spheres were given, but the context has no spheres");
     if (prev_verts && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "previous vertices were given, but the context has no committed mesh");
@@ -2573,16 +2586,17 @@ static int motion_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera*
     return 0;
 }
 
-int rt3_motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_aov, const void* d_prev_sph, uint32_t n_prev_sph,
-                      const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = motion_checks(ctx, w, h, cam, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out);
+// The device form for either view (cam or lens, exactly one).
+static int motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_lens* lens, const void* d_aov, const void* d_prev_sph,
+                         uint32_t n_prev_sph, const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
+    int rc = motion_checks(ctx, w, h, cam, lens, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out);
     if (rc) return rc;
     if (((uintptr_t)d_aov | (uintptr_t)d_prev_sph | (uintptr_t)d_prev_verts | (uintptr_t)d_out) % 16u != 0)
         return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
     MotionLaunch L{};
     L.width = w; L.height = h;
-    std::memcpy(L.cam, cam, sizeof(rt3_camera));
+    if (cam) std::memcpy(L.cam, cam, sizeof(rt3_camera));
+    L.lens = lens;
     L.aov = d_aov;
     // a class without a previous array is never gathered: its buffers and counts stay out of the launch
     if (d_prev_sph) { L.sph = ctx->d_sph_cr; L.sph_invr = ctx->d_sph_invr; L.prev_sph = d_prev_sph; L.n_sph = ctx->n_sph; }
@@ -2597,15 +2611,94 @@ int rt3_motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* ca
     return leave(ctx, stream);
 }
 
+int rt3_motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_aov, const void* d_prev_sph, uint32_t n_prev_sph,
+                      const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    return motion_device(ctx, w, h, cam, nullptr, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out, stream_);
+}
+
 int rt3_motion(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_aov* aov, const float* prev_sph, uint32_t n_prev_sph,
                const float* prev_verts, uint32_t n_prev_verts, float* out) {
     if (!ctx) return RT3_E_ARG;
-    int rc = motion_checks(ctx, w, h, cam, aov, prev_sph, n_prev_sph, prev_verts, n_prev_verts, out);
+    int rc = motion_checks(ctx, w, h, cam, nullptr, aov, prev_sph, n_prev_sph, prev_verts, n_prev_verts, out);
     if (rc) return rc;
     const size_t npix = (size_t)w * h;
     return staged(ctx, { stage_in(aov, npix * sizeof(rt3_aov)), stage_in(prev_sph, (size_t)n_prev_sph * sizeof(float4)),
                      stage_in(prev_verts, (size_t)n_prev_verts * sizeof(float4)), stage_out(out, npix * sizeof(float4)) },
                   [&](void* const* d) { return rt3_motion_device(ctx, w, h, cam, d[0], d[1], n_prev_sph, d[2], n_prev_verts, d[3], ctx->stream); });
+}
+
+// ---- Lens sequences: the two calls above for a frame rendered through a lens.  The lens forms of k_temporal_reproject and
+// k_motion take the lenses by value; nothing is worked out here but the checks.
+static int optic_temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const void* colour, const void* aov,
+                                 const rt3_lens* prev_lens, const void* prev_history, const void* motion, const rt3_temporal_params* p,
+                                 const void* out, const void* out_history) {
+    return temporal_checks_of(ctx, w, h, "lens", lens, colour, aov, prev_lens, prev_history, motion, p, out, out_history, [&]() {
+        if (const char* why = rt3lens::refusal(lens, w, h)) return fail(ctx, RT3_E_ARG, why);
+        if (prev_lens) {
+            if (const char* why = rt3lens::refusal(prev_lens, w, h)) return fail(ctx, RT3_E_ARG, std::string("prev_") + why);
+            if (prev_lens->model != lens->model) return fail(ctx, RT3_E_ARG, "prev_lens must have the model of lens");
+        }
+        return 0;
+    });
+}
+
+int rt3_denoise_temporal_optic_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const void* d_colour, const void* d_aov,
+                                      const rt3_lens* prev_lens, const void* d_prev_history, const void* d_motion,
+                                      const rt3_temporal_params* p, void* d_out, void* d_out_history, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = optic_temporal_checks(ctx, w, h, lens, d_colour, d_aov, prev_lens, d_prev_history, d_motion, p, d_out, d_out_history);
+    if (rc) return rc;
+    if (((uintptr_t)d_colour | (uintptr_t)d_aov | (uintptr_t)d_prev_history | (uintptr_t)d_motion | (uintptr_t)d_out | (uintptr_t)d_out_history) % 16u != 0)
+        return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
+    const size_t npix = (size_t)w * h;
+    TemporalLaunch T{};
+    T.base = DenoiseLaunch{ w, h, p->spatial.iterations, p->spatial.normal_power, p->spatial.sigma_luminance, p->spatial.sigma_depth,
+                            d_colour, d_aov, d_out, nullptr };
+    T.lens = lens;
+    T.prev_lens = prev_lens;
+    T.has_prev = prev_lens ? 1u : 0u;
+    T.alpha = p->alpha; T.moments_alpha = p->moments_alpha; T.depth_tolerance = p->depth_tolerance; T.normal_tolerance = p->normal_tolerance;
+    T.prev_history = d_prev_history;
+    T.out_history = d_out_history;
+    T.motion = prev_lens ? d_motion : nullptr;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream)) || (rc = ctx->d_dn.ensure(ctx, 3 * npix + (npix + 3) / 4))) return rc;     // the scratch is the context's
+    T.base.scratch = ctx->d_dn;
+    RT3_HIP(temporal_launch(T, stream));
+    return leave(ctx, stream);
+}
+
+int rt3_denoise_temporal_optic(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const float* colour, const rt3_aov* aov,
+                               const rt3_lens* prev_lens, const rt3_history* prev_history, const float* motion,
+                               const rt3_temporal_params* p, float* out, rt3_history* out_history) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = optic_temporal_checks(ctx, w, h, lens, colour, aov, prev_lens, prev_history, motion, p, out, out_history);
+    if (rc) return rc;
+    const size_t npix = (size_t)w * h;
+    return staged(ctx, { stage_in(colour, npix * sizeof(float4)), stage_in(aov, npix * sizeof(rt3_aov)),
+                         stage_in(prev_history, npix * sizeof(rt3_history)), stage_in(motion, npix * sizeof(float4)),
+                         stage_out(out, npix * sizeof(float4)), stage_out(out_history, npix * sizeof(rt3_history)) },
+                  [&](void* const* d) { return rt3_denoise_temporal_optic_device(ctx, w, h, lens, d[0], d[1], prev_lens, d[2], d[3], p, d[4], d[5], ctx->stream); });
+}
+
+int rt3_motion_optic_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const void* d_aov, const void* d_prev_sph, uint32_t n_prev_sph,
+                            const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    if (!lens) return fail(ctx, RT3_E_ARG, "lens / aov / out_motion is NULL");
+    return motion_device(ctx, w, h, nullptr, lens, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out, stream_);
+}
+
+int rt3_motion_optic(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const rt3_aov* aov, const float* prev_sph, uint32_t n_prev_sph,
+                     const float* prev_verts, uint32_t n_prev_verts, float* out) {
+    if (!ctx) return RT3_E_ARG;
+    if (!lens) return fail(ctx, RT3_E_ARG, "lens / aov / out_motion is NULL");
+    int rc = motion_checks(ctx, w, h, nullptr, lens, aov, prev_sph, n_prev_sph, prev_verts, n_prev_verts, out);
+    if (rc) return rc;
+    const size_t npix = (size_t)w * h;
+    return staged(ctx, { stage_in(aov, npix * sizeof(rt3_aov)), stage_in(prev_sph, (size_t)n_prev_sph * sizeof(float4)),
+                     stage_in(prev_verts, (size_t)n_prev_verts * sizeof(float4)), stage_out(out, npix * sizeof(float4)) },
+                  [&](void* const* d) { return rt3_motion_optic_device(ctx, w, h, lens, d[0], d[1], n_prev_sph, d[2], n_prev_verts, d[3], ctx->stream); });
 }
 
 // ---- Radiance along caller-supplied rays: the rays form of the kernel a query would take on the scene, over the items

@@ -616,6 +616,27 @@ extern "C" int rt3_debug_lens_ray(const rt3_lens* lens, const rt3_params* p, uin
     out->_pad = 0u;
     return 0;
 }
+// The inverse law (rt3.h "Lens sequences") on the host: the statements of rt3_lens_law.hpp k_temporal_reproject evaluates.
+extern "C" float rt3_debug_turns(float c, float s) { return rt3lens::turns(c, s); }
+extern "C" int rt3_debug_optic_pixel(const rt3_lens* prev_lens, uint32_t width, uint32_t height, const float r[3], uint32_t is_hit,
+                                     float out_xy_depth[3], uint32_t* face, uint32_t* valid) {
+    if (!prev_lens || !r || !out_xy_depth || !face || !valid || width < 2 || height < 2) return RT3_E_ARG;
+    if (rt3lens::refusal(prev_lens, width, height)) return RT3_E_ARG;
+    float xp = __builtin_nanf(""), yp = __builtin_nanf(""), zhat = 0.0f;      // (the pole behind a fisheye leaves x', y' as they are)
+    uint32_t f = 0;
+    const bool ok = rt3lens::project_of(*prev_lens, width, height, r, xp, yp, zhat, f);
+    if (prev_lens->model == RT3_LENS_ORTHO && !is_hit) {            // not projected: the pixel keeps its own position
+        out_xy_depth[0] = out_xy_depth[1] = __builtin_nanf("");
+        out_xy_depth[2] = zhat;
+        *face = 0;
+        *valid = 1;
+        return 0;
+    }
+    out_xy_depth[0] = xp; out_xy_depth[1] = yp; out_xy_depth[2] = zhat;
+    *face = f;
+    *valid = ok ? 1u : 0u;
+    return 0;
+}
 // Worked out in double and rounded once per component: each axis is then a unit vector to a few 2^-25, far inside the 2^-20 the entry points ask for.
 extern "C" void rt3_lens_look_at(rt3_lens* lens, uint32_t model, const float from[3], const float at[3], const float vup[3]) {
     if (!lens || !from || !at || !vup) return;

@@ -1,6 +1,8 @@
-// rt3_lens_law.hpp — the lens models' ray law (rt3.h "Lens models"), one statement for the device and the host.
-// Included by rt3_device.hip (k_lens_rays and the drivers' checks, rt3_lens.hpp) and by rt3_host.cpp (rt3_debug_lens_ray, rt3_lens_look_at: the serial
-// restatement the tests compare with tests/lens_ref.py).  Every float operation is an IEEE f32 operation rounded on its own (every file is compiled with
+// rt3_lens_law.hpp — the lens models' ray law (rt3.h "Lens models") and its inverse (rt3.h "Lens sequences"), one
+// statement for the device and the host.
+// Included by rt3_device.hip (k_lens_rays and the drivers' checks, rt3_lens.hpp), by rt3_denoise.hip (the lens forms of k_temporal_reproject and
+// k_motion) and by rt3_host.cpp (rt3_debug_lens_ray, rt3_lens_look_at, rt3_debug_turns, rt3_debug_optic_pixel: the serial restatement the tests
+// compare with tests/lens_ref.py and tests/optic_ref.py).  Every float operation is an IEEE f32 operation rounded on its own (every file is compiled with
 // -ffp-contract=off); the fused multiply-adds of sincos2pi and of the validity rule's d.d are written out.  The hash, u01 and sincos2pi restate
 // rt3_kernel_common.hpp's, which exist for the device only.
 #pragma once
@@ -151,6 +153,98 @@ inline void ray_of(const rt3_lens& L, const Frame& F, uint32_t x, uint32_t y, ui
     case RT3_LENS_FISHEYE:  ray<RT3_LENS_FISHEYE>(L, F, x, y, s, o, d); break;
     case RT3_LENS_ORTHO:    ray<RT3_LENS_ORTHO>(L, F, x, y, s, o, d); break;
     default:                ray<RT3_LENS_CUBE>(L, F, x, y, s, o, d); break;
+    }
+}
+
+// ---- The inverse law (rt3.h "Lens sequences"): from a world point back to a frame position.
+
+// The angle of the vector (c, s) in turns, in [0, 1): plain f32 * + - / and comparisons (no fma), an odd degree-17 polynomial of atan on [0, 1]
+// (Abramowitz & Stegun 4.4.49) and three reflections.  NaN for (0, 0) and for a component that is not finite.  Within 2^-23 turns of atan2.
+RT3_HD float turns(float c, float s) {
+    const float ac = __builtin_fabsf(c), as = __builtin_fabsf(s);
+    const float hi = ac > as ? ac : as, lo = ac > as ? as : ac;
+    if (!finite(ac) || !finite(as) || !(hi > 0.0f)) return __builtin_nanf("");
+    const float t = lo / hi;
+    const float z = t * t;
+    float p = 0.0028662257f;
+    p = p * z; p = p + -0.0161657367f;
+    p = p * z; p = p + 0.0429096138f;
+    p = p * z; p = p + -0.0752896400f;
+    p = p * z; p = p + 0.1065626393f;
+    p = p * z; p = p + -0.1420889944f;
+    p = p * z; p = p + 0.1999355085f;
+    p = p * z; p = p + -0.3333314528f;
+    p = p * z; p = p + 1.0f;
+    float u = (t * p) * 0.159154937f;
+    if (as > ac) u = 0.25f - u;
+    if (c < 0.0f) u = 0.5f - u;
+    if (s < 0.0f) u = 1.0f - u;
+    if (u >= 1.0f) u = 0.0f;
+    return u;
+}
+
+// Bit equality of the fields the inverse law reads: the model, the origin, the three axes and the model's own parameter.
+inline bool same_optic(const rt3_lens& a, const rt3_lens& b) {
+    if (a.model != b.model) return false;
+    bool same = __builtin_memcmp(a.origin, b.origin, 12) == 0 && __builtin_memcmp(a.right, b.right, 12) == 0 &&
+                __builtin_memcmp(a.up, b.up, 12) == 0 && __builtin_memcmp(a.forward, b.forward, 12) == 0;
+    if (a.model == RT3_LENS_FISHEYE) same = same && __builtin_memcmp(&a.half_fov_turns, &b.half_fov_turns, 4) == 0;
+    if (a.model == RT3_LENS_ORTHO) same = same && __builtin_memcmp(a.half_extent, b.half_extent, 8) == 0;
+    return same;
+}
+
+// r (the point relative to the lens's origin; for a miss of a central model the direction) -> the frame position (x', y') in the pixel-index
+// coordinates of the taps (pixel centres at integers), the depth zhat the history's is compared with, and for CUBE the face the taps stay on.
+// false: no history (the pole behind a fisheye, r = 0).  L is the PREVIOUS lens, W x H its frame.  An ORTHO miss is not projected: the caller
+// keeps x' = x, y' = y.
+template <uint32_t MODEL>
+RT3_HD bool project(const rt3_lens& L, uint32_t width, uint32_t height, const float r[3], float& xp, float& yp, float& zhat, uint32_t& face) {
+    const float W = (float)width, H = (float)height;
+    const float lx = dot3(r[0], r[1], r[2], L.right[0], L.right[1], L.right[2]);
+    const float ly = dot3(r[0], r[1], r[2], L.up[0], L.up[1], L.up[2]);
+    const float lz = dot3(r[0], r[1], r[2], L.forward[0], L.forward[1], L.forward[2]);
+    zhat = MODEL == RT3_LENS_ORTHO ? lz : __builtin_sqrtf(dot3(r[0], r[1], r[2], r[0], r[1], r[2]));
+    face = 0;
+    float px, py;
+    if (MODEL == RT3_LENS_EQUIRECT) {
+        const float hxz = __builtin_sqrtf(lx * lx + lz * lz);
+        const float a = turns(-lz, -lx);
+        const float b = 2.0f * turns(ly, hxz);
+        px = a * W; py = b * H;
+    } else if (MODEL == RT3_LENS_FISHEYE) {
+        const float hxy = __builtin_sqrtf(lx * lx + ly * ly);
+        const float tau = turns(lz, hxy);
+        const float rr = tau / L.half_fov_turns;
+        float nx, ny;
+        if (hxy > 0.0f) { nx = rr * (lx / hxy); ny = rr * (ly / hxy); }
+        else if (tau == 0.0f) { nx = 0.0f; ny = 0.0f; }
+        else return false;
+        const float m = 0.5f * (float)(width < height ? width : height);
+        px = nx * m + 0.5f * W; py = 0.5f * H - ny * m;
+    } else if (MODEL == RT3_LENS_ORTHO) {
+        const float nx = lx / L.half_extent[0];
+        const float ny = ly / L.half_extent[1];
+        px = ((nx + 1.0f) * 0.5f) * W; py = ((1.0f - ny) * 0.5f) * H;
+    } else {                                                        // RT3_LENS_CUBE: the lookup law's face cases (rt3.h "Environment map")
+        const float vx = lx, vy = ly, vz = -lz;
+        const float ax = __builtin_fabsf(vx), ay = __builtin_fabsf(vy), az = __builtin_fabsf(vz);
+        float m, sc, tc;
+        if (ax >= ay && ax >= az) { face = vx < 0.0f ? 1u : 0u; m = ax; sc = vx < 0.0f ? vz : -vz; tc = -vy; }
+        else if (ay >= az)        { face = vy < 0.0f ? 3u : 2u; m = ay; sc = vx; tc = vy < 0.0f ? -vz : vz; }
+        else                      { face = vz < 0.0f ? 5u : 4u; m = az; sc = vz < 0.0f ? -vx : vx; tc = -vy; }
+        px = ((sc / m) * 0.5f + 0.5f) * W; py = (float)(face * width) + ((tc / m) * 0.5f + 0.5f) * W;
+    }
+    xp = px - 0.5f; yp = py - 0.5f;
+    return xp == xp && yp == yp;
+}
+
+// The same with the model taken from the lens (the host's form).
+inline bool project_of(const rt3_lens& L, uint32_t width, uint32_t height, const float r[3], float& xp, float& yp, float& zhat, uint32_t& face) {
+    switch (L.model) {
+    case RT3_LENS_EQUIRECT: return project<RT3_LENS_EQUIRECT>(L, width, height, r, xp, yp, zhat, face);
+    case RT3_LENS_FISHEYE:  return project<RT3_LENS_FISHEYE>(L, width, height, r, xp, yp, zhat, face);
+    case RT3_LENS_ORTHO:    return project<RT3_LENS_ORTHO>(L, width, height, r, xp, yp, zhat, face);
+    default:                return project<RT3_LENS_CUBE>(L, width, height, r, xp, yp, zhat, face);
     }
 }
 

@@ -488,6 +488,36 @@ std::vector<float> HipRenderer::denoise(uint32_t width, uint32_t height, const s
     return out;
 }
 
+std::vector<float> HipRenderer::denoise_temporal_lens(const rt3_lens& lens, uint32_t width, uint32_t height, const std::vector<float>& colour,
+                                                      const std::vector<rt3_aov>& guides, const rt3_temporal_params& params, LensHistory& history,
+                                                      const std::vector<float>& motion) const {
+    const size_t npix = (size_t)width * height;
+    if (colour.size() != 4 * npix || guides.size() != npix) throw Fatal("denoise_temporal_lens: the frames' sizes differ from width x height");
+    const bool have = !history.records.empty();
+    if (have && history.records.size() != npix) throw Fatal("denoise_temporal_lens: the history's frame size differs from width x height");
+    if (!motion.empty() && motion.size() != 4 * npix) throw Fatal("denoise_temporal_lens: the motion plane's frame size differs from width x height");
+    std::vector<float> out(colour.size());
+    std::vector<rt3_history> next(npix);
+    if (rt3_denoise_temporal_optic(ctx[0], width, height, &lens, colour.data(), guides.data(), have ? &history.lens : nullptr,
+                                   have ? history.records.data() : nullptr, motion.empty() ? nullptr : motion.data(), &params, out.data(),
+                                   next.data()) != 0)
+        throw Fatal(rt3_last_error(ctx[0]));
+    history.records.swap(next);
+    history.lens = lens;
+    return out;
+}
+
+std::vector<float> HipRenderer::motion_lens(const rt3_lens& lens, uint32_t width, uint32_t height, const std::vector<rt3_aov>& guides,
+                                            const std::vector<float>& prev_center_radius, const std::vector<float>& prev_vertices_xyzw) const {
+    if (guides.size() != (size_t)width * height) throw Fatal("motion_lens: the AOVs' size differs from width x height");
+    std::vector<float> out(4 * guides.size());
+    if (rt3_motion_optic(ctx[0], width, height, &lens, guides.data(), prev_center_radius.empty() ? nullptr : prev_center_radius.data(),
+                         (uint32_t)(prev_center_radius.size() / 4), prev_vertices_xyzw.empty() ? nullptr : prev_vertices_xyzw.data(),
+                         (uint32_t)(prev_vertices_xyzw.size() / 4), out.data()) != 0)
+        throw Fatal(rt3_last_error(ctx[0]));
+    return out;
+}
+
 rt3_stats HipRenderer::stats() const {
     rt3_stats s;
     if (rt3_get_stats(ctx[0], &s) != 0) throw Fatal(rt3_last_error(ctx[0]));

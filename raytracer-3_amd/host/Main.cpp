@@ -10,7 +10,8 @@
 // (path-traced radiance along rays read from a file), --env (an environment map from a PFM of six stacked cube faces),
 // --env-sampling (importance sampling of that map with shadow rays), --light-sampling (the same for the emissive primitives),
 // --display (the image written is the linear frame through exposure, a tone curve and a transfer function), --lens, --lens-fov and
-// --lens-extent (the frame of another lens model at the scene's camera position: equirectangular, fisheye, orthographic, cube).
+// --lens-extent (the frame of another lens model at the scene's camera position: equirectangular, fisheye, orthographic, cube),
+// --lens-frames (a sequence of such frames, denoised temporally through the lens).
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -59,6 +60,8 @@ struct Options {
     float lens_fov = 180.0f;                                       // fisheye: the whole field of view across the shorter image side, in degrees
     float lens_extent[2] = { 2.0f, 2.0f };                         // ortho: the window's width and height
     bool have_lens_fov = false, have_lens_extent = false;
+    uint32_t lens_frames = 1;                                      // --lens: frames of a sequence of lens frames (frame k renders with seed + k)
+    bool have_lens_frames = false;
     rt3_display_params display_params{ RT3_DISPLAY_FILMIC, RT3_DISPLAY_SRGB, 0u, 102u, 51u, 1.0f, 0.18f, 4.0f };      // the defaults of DESIGN.md 4.22
 };
 
@@ -102,7 +105,10 @@ void print_usage(const char* exe) {
               << "\t\t\tEXPOSURE a positive gain, or auto: from the frame's trimmed log-average luminance (default: 1).\n"
               << "\t   --lens\tMode X: equirect | fisheye | ortho | cube: render the frame of that lens model (rt3_render_lens) at the scene's camera\n"
               << "\t\t\tposition, looking where the camera looks, instead of the camera's; cube needs -H equal to 6 times -W (the layout --env reads).\n"
-              << "\t\t\t--hdr, --aov, --denoise and --display act on the lens frame. Not with --adaptive, --frames or --gpus above 1.\n"
+              << "\t\t\t--hdr, --aov, --denoise and --display act on the lens frame. Not with --adaptive, --frames (a sequence: --lens-frames) or --gpus above 1.\n"
+              << "\t   --lens-frames\tWith --lens: render a sequence of N lens frames, frame k with seed + k; --orbit turns the lens's origin as it turns the\n"
+              << "\t\t\tcamera's look-from point, --slide and --refit move the spheres, and --denoise PREFIX writes PREFIX.<k>.pfm for every frame,\n"
+              << "\t\t\tdenoised temporally through the lens (rt3_denoise_temporal_optic). The image written is the last frame.\n"
               << "\t   --lens-fov\tWith --lens fisheye: the field of view across the shorter image side, in degrees, above 0 up to 360 (default: 180).\n"
               << "\t   --lens-extent\tWith --lens ortho: W,H: the width and height of the window the parallel rays start from (default: 2,2).\n"
               << "\n\t-h,--help\tShows this help menu, then exits.\n\n";
@@ -149,7 +155,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
                            key == "--slide" || key == "--adaptive" || key == "--counts" || key == "--regroup" ||
                            key == "--rays" || key == "--radiance" || key == "--env" || key == "--display" || key == "--lens" || key == "--lens-fov" ||
-                           key == "--lens-extent";
+                           key == "--lens-extent" || key == "--lens-frames";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -249,6 +255,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
             else if (value == "cube") opt.lens = RT3_LENS_CUBE;
             else { std::cerr << "Unknown lens '" << value << "'" << std::endl; return -1; }
         }
+        else if (key == "--lens-frames") { if (!parse_u32(value, "lens-frames", "Lens-frames", &opt.lens_frames)) return -1; opt.have_lens_frames = true; }
         else if (key == "--lens-fov") {                              // degrees in (0, 360]
             char* end = nullptr;
             const double deg = std::strtod(value.c_str(), &end);
@@ -335,6 +342,8 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         std::cerr << "--lens-fov and --lens-extent need --lens." << std::endl;
         return -1;
     }
+    if (opt.have_lens_frames && opt.lens == 0) { std::cerr << "--lens-frames needs --lens: a camera sequence is --frames." << std::endl; return -1; }
+    if (opt.have_lens_frames && opt.lens_frames == 0) { std::cerr << "--lens-frames must be at least 1." << std::endl; return -1; }
     if (opt.lens != 0) {
         if (opt.spp == 0) { std::cerr << "--lens needs the path tracer (Mode X): pass --spp." << std::endl; return -1; }
         if (opt.adaptive) { std::cerr << "--lens is not available with --adaptive." << std::endl; return -1; }
@@ -358,7 +367,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         std::cerr << "--slide needs a sphere scene (--scene three, weekend or stress100k)." << std::endl;
         return -1;
     }
-    if (opt.have_slide && opt.frames < 2) {
+    if (opt.have_slide && opt.frames < 2 && opt.lens_frames < 2) {
         std::cerr << "--slide needs a sequence: pass --frames N with N of at least 2." << std::endl;
         return -1;
     }
@@ -503,25 +512,62 @@ int main(int argc, const char** argv) {
             if (opt.env_sampling) path.flags |= RT3_FLAG_ENV_SAMPLING;
         }
         if (opt.light_sampling) path.flags |= RT3_FLAG_LIGHT_SAMPLING;
-        if (opt.lens != 0) {                                         // the frame of another lens model, at the camera's place (DESIGN.md 4.23)
+        const uint32_t seed0 = path.seed;
+        const rt3_temporal_params tp{ { 5, 128, 4.0f, 1.0f }, 0.2f, 0.2f, 2.0f, 0.9f };       // the defaults of DESIGN.md 4.11 and 4.12
+        std::vector<float> shown_cr = scene_cr, prev_cr;             // --slide: the spheres of this frame and of the one before
+        // --slide, frame k > 0: every sphere of odd index translated by k * slide, uploaded or (--refit) updated in place
+        const auto slide_spheres = [&](uint32_t k) {
+            prev_cr = shown_cr;
+            for (size_t i = 1; i < scene_mats.size(); i += 2)
+                for (int c = 0; c < 3; c++) shown_cr[4 * i + c] = scene_cr[4 * i + c] + (float)k * opt.slide[c];
+            if (opt.refit) {
+                renderer.update_spheres(shown_cr);
+                if (opt.regroup != 0 && k % opt.regroup == 0) renderer.regroup(true, false);
+            }
+            else renderer.set_spheres(shown_cr, scene_mats);
+        };
+        // --orbit, frame k: the look-from point turned by k * orbit about the vertical axis through the look-at point
+        const auto orbit_from = [&](uint32_t k) {
+            if (k == 0) return la.from;
+            const double a = (double)k * (double)opt.orbit * 3.14159265358979323846 / 180.0, c = std::cos(a), sn = std::sin(a);
+            const double dx = (double)la.from.x - la.at.x, dz = (double)la.from.z - la.at.z;
+            return glm::vec3(la.at.x + (c * dx + sn * dz), (double)la.from.y, la.at.z + (c * dz - sn * dx));
+        };
+        if (opt.lens != 0) {                                         // the frame of another lens model, at the camera's place (DESIGN.md 4.23, 4.24)
             const uint32_t w = opt.width, h = opt.height;
             const float origin[3] = { 0.0f, 0.0f, 0.0f }, ahead[3] = { 0.0f, 0.0f, -1.0f }, up[3] = { 0.0f, 1.0f, 0.0f };       // the reference camera
             rt3_lens lens{};
-            if (la.on) rt3_lens_look_at(&lens, opt.lens, &la.from.x, &la.at.x, &la.vup.x);
-            else rt3_lens_look_at(&lens, opt.lens, origin, ahead, up);
-            lens.half_fov_turns = opt.lens_fov / 720.0f;
-            lens.half_extent[0] = 0.5f * opt.lens_extent[0]; lens.half_extent[1] = 0.5f * opt.lens_extent[1];
             if (la.on) cam.look_at(w, h, la.from, la.at, la.vup, la.vfov, la.focus);      // (the camera only lends its frame buffer to the image)
             path.lens_radius = 0.0f;
-            renderer.configure(path);
-            const std::vector<float> linear = renderer.render_lens(lens, w, h);
-            const rt3_stats st = renderer.stats();
+            const bool temporal = opt.lens_frames > 1 && !opt.denoise_path.empty();
+            LensHistory history;
+            std::vector<float> linear;
+            rt3_stats st{};                                          // the last frame's render (the AOV pass of a temporal frame replaces the context's)
+            for (uint32_t k = 0; k < opt.lens_frames; k++) {         // (--lens-frames: frame k with seed + k, the lens's origin on --orbit's circle)
+                if (opt.have_slide && k > 0) slide_spheres(k);
+                if (la.on) { const glm::vec3 from = orbit_from(k); rt3_lens_look_at(&lens, opt.lens, &from.x, &la.at.x, &la.vup.x); }
+                else rt3_lens_look_at(&lens, opt.lens, origin, ahead, up);
+                lens.half_fov_turns = opt.lens_fov / 720.0f;
+                lens.half_extent[0] = 0.5f * opt.lens_extent[0]; lens.half_extent[1] = 0.5f * opt.lens_extent[1];
+                path.seed = seed0 + k;
+                renderer.configure(path);
+                linear = renderer.render_lens(lens, w, h);
+                st = renderer.stats();
+                if (temporal) {
+                    const std::vector<rt3_aov> guides = renderer.lens_aov(lens, w, h);
+                    std::vector<float> motion;
+                    if (opt.have_slide && k > 0) motion = renderer.motion_lens(lens, w, h, guides, prev_cr, {});
+                    const std::vector<float> out = renderer.denoise_temporal_lens(lens, w, h, linear, guides, tp, history, motion);
+                    const std::string name = opt.denoise_path + "." + std::to_string(k) + ".pfm";
+                    if (rt3_frame_to_pfm(out.data(), w, h, 3, 4, name.c_str()) != 0) throw Fatal("Could not write '" + name + "'");
+                }
+            }
             std::cerr << "rendered a lens frame of " << w << "x" << h << " x " << path.spp << " spp in " << st.total_ms << " ms on device 0: " << st.ray_casts
                       << " rays, " << st.launches << " launches\n";
-            const bool need_aov = !opt.aov_prefix.empty() || !opt.denoise_path.empty();
+            const bool need_aov = !opt.aov_prefix.empty() || (!opt.denoise_path.empty() && !temporal);
             const std::vector<rt3_aov> aov = need_aov ? renderer.lens_aov(lens, w, h) : std::vector<rt3_aov>();
             const rt3_denoise_params dp{ 5, 128, 4.0f, 1.0f };                       // the defaults of DESIGN.md 4.11
-            const std::vector<float> denoised = opt.denoise_path.empty() ? std::vector<float>() : renderer.denoise(w, h, linear, aov, dp);
+            const std::vector<float> denoised = opt.denoise_path.empty() || temporal ? std::vector<float>() : renderer.denoise(w, h, linear, aov, dp);
             // the image: --display's transform, or the one that reproduces the ordinary Mode-X pack (no curve, the scene's gamma)
             const rt3_display_params pack{ RT3_DISPLAY_CLAMP, (path.flags & RT3_FLAG_GAMMA2) ? RT3_DISPLAY_GAMMA2 : RT3_DISPLAY_LINEAR, 0u, 102u, 51u, 1.0f, 0.18f, 4.0f };
             renderer.display(cam, opt.display && !denoised.empty() ? denoised : linear, opt.display ? opt.display_params : pack);
@@ -541,29 +587,12 @@ int main(int argc, const char** argv) {
                 throw Fatal("Could not write '" + opt.denoise_path + "'");
             return 0;
         }
-        const uint32_t seed0 = path.seed;
         const bool temporal = opt.frames > 1 && !opt.denoise_path.empty();
-        const rt3_temporal_params tp{ { 5, 128, 4.0f, 1.0f }, 0.2f, 0.2f, 2.0f, 0.9f };       // the defaults of DESIGN.md 4.11 and 4.12
         History history;
-        std::vector<float> shown_cr = scene_cr, prev_cr;             // --slide: the spheres of this frame and of the one before
         std::vector<uint32_t> counts;                                // --adaptive: the samples every pixel of the last frame received
         for (uint32_t k = 0; k < opt.frames; k++) {
-            if (opt.have_slide && k > 0) {                           // frame k: every sphere of odd index translated by k * slide
-                prev_cr = shown_cr;
-                for (size_t i = 1; i < scene_mats.size(); i += 2)
-                    for (int c = 0; c < 3; c++) shown_cr[4 * i + c] = scene_cr[4 * i + c] + (float)k * opt.slide[c];
-                if (opt.refit) {
-                    renderer.update_spheres(shown_cr);
-                    if (opt.regroup != 0 && k % opt.regroup == 0) renderer.regroup(true, false);
-                }
-                else renderer.set_spheres(shown_cr, scene_mats);
-            }
-            if (la.on) {                                             // frame k: the look-from point turned by k * orbit about the vertical axis
-                const double a = (double)k * (double)opt.orbit * 3.14159265358979323846 / 180.0, c = std::cos(a), sn = std::sin(a);
-                const double dx = (double)la.from.x - la.at.x, dz = (double)la.from.z - la.at.z;
-                const glm::vec3 from(la.at.x + (c * dx + sn * dz), (double)la.from.y, la.at.z + (c * dz - sn * dx));
-                cam.look_at(opt.width, opt.height, k == 0 ? la.from : from, la.at, la.vup, la.vfov, la.focus);
-            }
+            if (opt.have_slide && k > 0) slide_spheres(k);
+            if (la.on) cam.look_at(opt.width, opt.height, orbit_from(k), la.at, la.vup, la.vfov, la.focus);
             path.seed = seed0 + k;
             renderer.configure(path);
             if (opt.adaptive) {

@@ -25,6 +25,11 @@ struct History {
     std::vector<rt3_history> records;
     rt3_camera camera{};
 };
+// The same for a sequence of lens frames (rt3_denoise_temporal_optic): the last frame's history records and lens.
+struct LensHistory {
+    std::vector<rt3_history> records;
+    rt3_lens lens{};
+};
 
 // Mode-X knobs the reference API has no place for (spp / depth / seed ...); spp == 0 means Mode R.
 struct PathOptions {
@@ -84,6 +89,14 @@ public:
     // (rt3_render_lens_aov).  A cube lens's frame (width N, height 6 N) is the array set_environment takes.
     std::vector<float> render_lens(const rt3_lens& lens, uint32_t width, uint32_t height) const;
     std::vector<rt3_aov> lens_aov(const rt3_lens& lens, uint32_t width, uint32_t height) const;
+    // One frame of a sequence of lens frames through the temporal denoiser on device 0 (rt3_denoise_temporal_optic): colour and guides
+    // are render_lens's and lens_aov's for `lens`; `history` is the previous frame's and is replaced by this frame's; motion: empty, or motion_lens's plane
+    std::vector<float> denoise_temporal_lens(const rt3_lens& lens, uint32_t width, uint32_t height, const std::vector<float>& colour,
+                                             const std::vector<rt3_aov>& guides, const rt3_temporal_params& params, LensHistory& history,
+                                             const std::vector<float>& motion = {}) const;
+    // The motion plane of the current scene on device 0 for a lens frame (rt3_motion_optic): guides are lens_aov's for `lens`; the previous arrays as motion()
+    std::vector<float> motion_lens(const rt3_lens& lens, uint32_t width, uint32_t height, const std::vector<rt3_aov>& guides,
+                                   const std::vector<float>& prev_center_radius, const std::vector<float>& prev_vertices_xyzw) const;
     // rt3_denoise on device 0 for frames the caller holds (a lens frame and its AOVs)
     std::vector<float> denoise(uint32_t width, uint32_t height, const std::vector<float>& colour, const std::vector<rt3_aov>& guides,
                                const rt3_denoise_params& params) const;

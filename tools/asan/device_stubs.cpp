@@ -96,6 +96,12 @@ int rt3_denoise_temporal_motion(rt3_ctx*, uint32_t, uint32_t, const rt3_camera*,
                                 const float*, const rt3_temporal_params*, float*, rt3_history*) { return RT3_E_DEVICE; }
 int rt3_denoise_temporal_motion_device(rt3_ctx*, uint32_t, uint32_t, const rt3_camera*, const void*, const void*, const rt3_camera*, const void*,
                                        const void*, const rt3_temporal_params*, void*, void*, void*) { return RT3_E_DEVICE; }
+int rt3_denoise_temporal_optic(rt3_ctx*, uint32_t, uint32_t, const rt3_lens*, const float*, const rt3_aov*, const rt3_lens*, const rt3_history*,
+                               const float*, const rt3_temporal_params*, float*, rt3_history*) { return RT3_E_DEVICE; }     // (rt3_debug_turns / rt3_debug_optic_pixel are host code)
+int rt3_denoise_temporal_optic_device(rt3_ctx*, uint32_t, uint32_t, const rt3_lens*, const void*, const void*, const rt3_lens*, const void*,
+                                      const void*, const rt3_temporal_params*, void*, void*, void*) { return RT3_E_DEVICE; }
+int rt3_motion_optic(rt3_ctx*, uint32_t, uint32_t, const rt3_lens*, const rt3_aov*, const float*, uint32_t, const float*, uint32_t, float*) { return RT3_E_DEVICE; }
+int rt3_motion_optic_device(rt3_ctx*, uint32_t, uint32_t, const rt3_lens*, const void*, const void*, uint32_t, const void*, uint32_t, void*, void*) { return RT3_E_DEVICE; }
 int rt3_display(rt3_ctx*, uint32_t, uint32_t, const float*, const rt3_display_params*, uint32_t*) { return RT3_E_DEVICE; }     // (rt3_debug_display_bin / _gain / _pixel / _srgb_table are host code)
 int rt3_display_device(rt3_ctx*, uint32_t, uint32_t, const void*, const rt3_display_params*, void*, void*) { return RT3_E_DEVICE; }
 int rt3_debug_display_state(rt3_ctx*, uint32_t*, uint32_t*, float*) { return RT3_E_DEVICE; }
