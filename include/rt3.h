@@ -35,8 +35,8 @@ extern "C" {
  * rt3_render_path_adaptive* (one new struct of its own), with rt3_regroup*, with the environment map (rt3_set_environment*), with its
  * importance sampling (RT3_FLAG_ENV_SAMPLING: one flag bit and two test-only functions), with the emitters' (RT3_FLAG_LIGHT_SAMPLING: the same again)
  * with the display transform (rt3_display*: one new struct of its own), with the lens models (rt3_lens_rays*, rt3_render_lens*,
- * rt3_render_lens_aov*: one new struct of its own) and with lens sequences (rt3_denoise_temporal_optic*, rt3_motion_optic*): functions were only
- * added, no existing struct changed. */
+ * rt3_render_lens_aov*: one new struct of its own), with lens sequences (rt3_denoise_temporal_optic*, rt3_motion_optic*) and with display
+ * sequences (rt3_display_sequence*: two new structs of their own): functions were only added, no existing struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
 
@@ -915,7 +915,8 @@ typedef struct rt3_display_params {      /* 32 bytes */
  * kernels.  The device form allocates only on a context's first call with the flag (516 words of state).  RT3_E_ARG for a NULL pointer, width or
  * height 0, width x height > 2^26, a parameter outside the ranges above (unknown curve, transfer or flag bits included), a device input that is not
  * 16-byte aligned or a device output that is not 4-byte aligned, or an output that overlaps the input; a refused call writes nothing.  Out of scope:
- * one exposure shared by the shards of a multi-device frame (gather first, or pass the gain as `exposure`), eye adaptation, local operators, dither. */
+ * one exposure shared by the shards of a multi-device frame (gather first, or pass the gain as `exposure`), local operators other than the bloom of
+ * rt3_display_sequence (below, with eye adaptation over a sequence), dither. */
 int      rt3_display(rt3_ctx* ctx, uint32_t width, uint32_t height, const float* rgba, const rt3_display_params* p, uint32_t* out_pixels);
 int      rt3_display_device(rt3_ctx* ctx, uint32_t width, uint32_t height, const void* d_rgba, const rt3_display_params* p, void* d_out_pixels,
                             void* stream);
@@ -929,6 +930,72 @@ int      rt3_debug_display_bin(const float rgb[3], uint32_t* bin);
 int      rt3_debug_display_gain(const uint32_t hist[512], const rt3_display_params* p, float* gain);
 int      rt3_debug_display_pixel(const float rgb[3], float gain, const rt3_display_params* p, uint32_t* word);
 int      rt3_debug_display_srgb_table(uint8_t out[4096]);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Display sequences  (DESIGN.md 4.25, 5.2t): rt3_display with an exposure that follows a sequence of frames and a bloom pyramid
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rt3_exposure {            /* 16 bytes; one per sequence, owned by the caller, host or device */
+    uint32_t level;                      /* P: the adapted log-luminance, in 2^-19 of a histogram bin; 0 .. 511 << 19 */
+    uint32_t frames;                     /* frames that have set it; 0 = no level yet */
+    float    gain;                       /* the gain the call applied */
+    uint32_t _pad;                       /* 0 */
+} rt3_exposure;
+typedef struct rt3_display_sequence_params {   /* 64 bytes */
+    rt3_display_params display;          /* as for rt3_display; its refusals unchanged */
+    uint32_t adapt_brighter;             /* share of the way to a BRIGHTER target per frame, in 1/1024; 1 .. 1024; default 256 */
+    uint32_t adapt_darker;               /* ... to a darker target; 1 .. 1024; default 64 */
+    uint32_t bloom_levels;               /* L: 0 = no bloom, else 1 .. 8 */
+    float    bloom_threshold;            /* T: finite, >= 0; default 1 */
+    float    bloom_intensity;            /* finite, >= 0; default 0.25 */
+    uint32_t _pad[3];                    /* 0, else RT3_E_ARG */
+} rt3_display_sequence_params;
+/* rt3_display (above: the frame, the words, the histogram, the curve and the transfer are its) with two additions: the gain follows the sequence
+ * through a state the caller keeps between the frames, and a bloom pyramid is added to the frame before the tone curve.  The frame is a real
+ * width x height image (a shard's compact rows are not: gather first).
+ * The exposure.  hist, n, the trim, m and S as for rt3_display; the frame's target is P_t = (S << 19) / m (uint64 floor division).
+ *   Without RT3_DISPLAY_AUTO_EXPOSURE: gain = display.exposure; prev_exposure must be NULL; out_exposure, if given, gets {0, 0, gain, 0}.
+ *   With it and no usable history (prev_exposure NULL, or prev.frames == 0): n > 0 gives level = P_t, frames = 1; n == 0 gives
+ *   {0, 0, display.exposure, 0} (an all-dark first frame sets nothing).
+ *   With it and prev.frames > 0: n == 0 gives level = prev.level (a black frame does not move the eye).  Otherwise d = P_t - prev.level,
+ *   rate = d > 0 ? adapt_brighter : adapt_darker, d == 0 gives level = prev.level, else step = max(1, (|d| * rate) >> 10) in uint64 and
+ *   level = prev.level + step for d > 0, prev.level - step for d < 0: step <= |d|, so the level moves monotonically and lands on P_t exactly.
+ *   frames = min(prev.frames + 1, 0xFFFFFFFF).
+ *   The gain, wherever a level was set: gain = exposure * (key / float_from_bits((111u << 23) + level + (1u << 18))), rt3_display's expression:
+ *   rates of 1024 (and a first frame) reproduce rt3_display.  prev.gain and prev._pad are not read.
+ *   A prev.level above 511 << 19: the host form refuses it (RT3_E_ARG); the device form, which cannot look without waiting, reads it as 511 << 19.
+ * The bloom (bloom_levels = L >= 1; every operation an IEEE f32 operation rounded on its own, nothing fused but the luminance's two fmaf).
+ *   With x_c = g > 0 ? fminf(g, 65504.0f) : 0, g = gain * c, as rt3_display forms it, on planes of (r, g, b):
+ *   Bright pass: Y = fmaf(0.0722f, x_b, fmaf(0.7152f, x_g, 0.2126f * x_r)), k = Y > T ? (Y - T) / Y : 0, b0_c = x_c * k.
+ *   Down, l = 1 .. L: W_l = (W_{l-1} + 1) >> 1, H_l likewise (W_0 x H_0 is the frame); D_l(i, j) = ((s(2i, 2j) + s(2i+1, 2j)) + (s(2i, 2j+1) +
+ *   s(2i+1, 2j+1))) * 0.25f with s = D_{l-1}, D_0 = b0, source indices clamped to the last column and row.
+ *   Up: up(U)(i, j) onto a w x h plane from a Wc x Hc plane: ia = i >> 1, ib = i odd ? min(ia + 1, Wc - 1) : max(ia - 1, 0), ja and jb likewise
+ *   from j and Hc; r(jr) = 0.75f * U(ia, jr) + 0.25f * U(ib, jr); the value is 0.75f * r(ja) + 0.25f * r(jb).  U_L = D_L; for l = L-1 .. 1
+ *   U_l = D_l + up(U_{l+1}); B = up(U_1) * (1.0f / (float)L) at the frame's size.
+ *   Composite: x'_c = fminf(x_c + bloom_intensity * B_c, 65504.0f); the curve and the transfer run on x' as rt3_display runs them on x.  The
+ *   histogram reads the input frame, never the bloom.  A frame with no pixel above T, and an intensity of 0, give the words without bloom.
+ * Streams and the event chain as for rt3_display; the host form is synchronous, the device form never waits for the device.  The pyramid
+ * (width x height / 3 texels of 16 bytes, a little more for odd sizes) is the context's, grows on demand and is kept after the call.  The call
+ * never touches the accumulation and leaves rt3_get_stats as it was.  d_prev_exposure == d_out_exposure is allowed (one 16-byte record serves a
+ * sequence; prev_exposure == out_exposure likewise).  RT3_E_ARG, nothing written: a NULL ctx, p, input or output pixels; whatever rt3_display
+ * refuses in p->display; a rate outside 1 .. 1024; bloom_levels > 8; a threshold or an intensity that is not finite and >= 0 (checked with
+ * bloom_levels == 0 too); a non-zero pad; prev_exposure without the flag; a host prev.level above 511 << 19; width or height 0 or
+ * width x height > 2^26; a device input that is not 16-byte aligned, device words or exposure records that are not 4-byte aligned; any overlap
+ * among the four buffers other than prev == out.  Out of scope: bloom and one exposure across the shards of a multi-device frame. */
+int      rt3_display_sequence(rt3_ctx* ctx, uint32_t width, uint32_t height, const float* rgba, const rt3_display_sequence_params* p,
+                              const rt3_exposure* prev_exposure, rt3_exposure* out_exposure, uint32_t* out_pixels);
+int      rt3_display_sequence_device(rt3_ctx* ctx, uint32_t width, uint32_t height, const void* d_rgba, const rt3_display_sequence_params* p,
+                                     const void* d_prev_exposure, void* d_out_exposure, void* d_out_pixels, void* stream);
+/* Tests only: U_1 (W_1 x H_1 float4, the fourth float 0) of the context's last call with bloom_levels >= 1, and B (width x height float4), formed
+ * from U_1 by the device function the composite uses.  Either output may be NULL; capacity_pixels is what out_bloom can hold (out_u1 needs no more);
+ * *w and *h are set to that call's frame size whenever the context has one.  RT3_E_STATE if there was no such call, RT3_E_ARG for NULL w / h or a
+ * short capacity.  Synchronous. */
+int      rt3_debug_display_bloom(rt3_ctx* ctx, float* out_u1, float* out_bloom, uint64_t capacity_pixels, uint32_t* w, uint32_t* h);
+/* Host only, no device and no context; for the tests: the laws above in C, serially.  rt3_debug_exposure_step: the state after a frame with this
+ * histogram (prev may be NULL).  rt3_debug_bloom: U_1 (W_1 x H_1 float4) and B (w x h float4) of a w x h float4 frame under a given gain; either
+ * output may be NULL; levels 1 .. 8.  RT3_E_ARG for what the entry points refuse; a refused call writes nothing.
+ * tests/display_sequence_ref.py restates them bit for bit. */
+int      rt3_debug_exposure_step(const rt3_exposure* prev, const uint32_t hist[512], const rt3_display_sequence_params* p, rt3_exposure* out);
+int      rt3_debug_bloom(uint32_t w, uint32_t h, const float* rgba, float gain, float threshold, uint32_t levels, float* out_u1, float* out_bloom);
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side scene API  (the step before the path: entities -> GFace[]/vec4[]; plain CPU code)

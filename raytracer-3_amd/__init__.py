@@ -164,6 +164,26 @@ def display_params(curve="filmic", transfer="srgb", exposure=1.0, auto=False, ke
     return DISPLAY_PARAMS(int(c), int(t), DISPLAY_AUTO_EXPOSURE if auto else 0, int(trim_low), int(trim_high), float(exposure), float(key), float(white))
 
 
+# rt3_exposure (16 bytes): the state of a sequence's eye adaptation — level, frames, the gain applied, a pad
+EXPOSURE = np.dtype([("level", np.uint32), ("frames", np.uint32), ("gain", np.float32), ("_pad", np.uint32)])
+EXPOSURE_MAX_LEVEL = 511 << 19
+
+
+class DISPLAY_SEQUENCE_PARAMS(C.Structure):
+    """rt3_display_sequence_params (64 bytes): rt3_display's parameters, the adaptation's two rates in 1/1024, the bloom's levels, threshold and
+    intensity, three pad words."""
+    _fields_ = [("display", DISPLAY_PARAMS), ("adapt_brighter", C.c_uint32), ("adapt_darker", C.c_uint32), ("bloom_levels", C.c_uint32),
+                ("bloom_threshold", C.c_float), ("bloom_intensity", C.c_float), ("_pad", C.c_uint32 * 3)]
+
+
+def display_sequence_params(curve="filmic", transfer="srgb", exposure=1.0, auto=False, key=0.18, white=4.0, trim_low=102, trim_high=51,
+                            adapt=(256, 64), bloom=None):
+    """DISPLAY_SEQUENCE_PARAMS: display_params' arguments, adapt = (brighter, darker) in 1/1024, bloom = None or (levels, threshold, intensity)."""
+    levels, threshold, intensity = bloom if bloom is not None else (0, 1.0, 0.25)
+    return DISPLAY_SEQUENCE_PARAMS(display_params(curve, transfer, exposure, auto, key, white, trim_low, trim_high), int(adapt[0]), int(adapt[1]),
+                                   int(levels), float(threshold), float(intensity))
+
+
 class rt3_lens(C.Structure):
     """rt3_lens (80 bytes): the model, the fisheye's half field of view in turns, the orthographic window's half extents, the origin and the
     orthonormal frame (right, up, forward), right x up = -forward."""
@@ -245,6 +265,7 @@ EXPORTS = [
     "rt3_debug_light_sample", "rt3_debug_light_table",
     "rt3_display", "rt3_display_device", "rt3_debug_display_state", "rt3_debug_display_bin", "rt3_debug_display_gain", "rt3_debug_display_pixel",
     "rt3_debug_display_srgb_table",
+    "rt3_display_sequence", "rt3_display_sequence_device", "rt3_debug_display_bloom", "rt3_debug_exposure_step", "rt3_debug_bloom",
     "rt3_lens_look_at", "rt3_lens_rays", "rt3_lens_rays_device", "rt3_render_lens", "rt3_render_lens_device", "rt3_render_lens_aov",
     "rt3_render_lens_aov_device", "rt3_debug_lens_ray",
     "rt3_denoise_temporal_optic", "rt3_denoise_temporal_optic_device", "rt3_motion_optic", "rt3_motion_optic_device", "rt3_debug_turns",
@@ -333,6 +354,10 @@ def lib():
         "rt3_debug_display_state": (i32, [vp, vp, vp, vp]), "rt3_debug_display_bin": (i32, [vp, vp]),
         "rt3_debug_display_gain": (i32, [vp, vp, vp]), "rt3_debug_display_pixel": (i32, [vp, f32, vp, vp]),
         "rt3_debug_display_srgb_table": (i32, [vp]),
+        "rt3_display_sequence": (i32, [vp, u32, u32, vp, vp, vp, vp, vp]),
+        "rt3_display_sequence_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "rt3_debug_display_bloom": (i32, [vp, vp, vp, u64, vp, vp]), "rt3_debug_exposure_step": (i32, [vp, vp, vp, vp]),
+        "rt3_debug_bloom": (i32, [u32, u32, vp, f32, f32, u32, vp, vp]),
         "rt3_lens_look_at": (None, [vp, u32, vp, vp, vp]),
         "rt3_lens_rays": (i32, [vp, vp, vp, u32, u32, vp]), "rt3_lens_rays_device": (i32, [vp, vp, vp, u32, u32, vp, vp]),
         "rt3_render_lens": (i32, [vp, vp, vp, u32, u32, vp]), "rt3_render_lens_device": (i32, [vp, vp, vp, u32, u32, vp, vp]),
@@ -471,6 +496,33 @@ def display_srgb_table():
     if lib().rt3_debug_display_srgb_table(_p(out)) != 0:
         raise Fatal("rt3_debug_display_srgb_table failed")
     return out
+
+
+def exposure_step(prev, hist, params):
+    """rt3_debug_exposure_step, the adaptation law in C on the host: the EXPOSURE record after a frame with this histogram of 512
+    uint32 bins under params (a DISPLAY_SEQUENCE_PARAMS); prev: None or the EXPOSURE record before."""
+    h = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+    if h.size != 512:
+        raise Fatal("exposure_step: the histogram has 512 bins")
+    before = np.array(prev, EXPOSURE).reshape(1) if prev is not None else None
+    out = np.zeros(1, EXPOSURE)
+    if lib().rt3_debug_exposure_step(_p(before), _p(h), C.byref(params), _p(out)) != 0:
+        raise Fatal("rt3_debug_exposure_step refused its arguments (rates 1 .. 1024, prev only with auto-exposure, prev.level <= 511 << 19)")
+    return out[0]
+
+
+def bloom_plane(colour, gain, threshold, levels):
+    """rt3_debug_bloom, the bloom law in C on the host, serially: float32 (H, W, 4) -> (U_1 float32 (H_1, W_1, 4), B float32
+    (H, W, 4)) under the given gain, threshold and number of levels (1 .. 8)."""
+    c = np.ascontiguousarray(colour, np.float32)
+    if c.ndim != 3 or c.shape[2] != 4:
+        raise Fatal("bloom_plane: colour must be float32 (H, W, 4)")
+    h, w = c.shape[:2]
+    u1 = np.zeros(((h + 1) // 2, (w + 1) // 2, 4), np.float32)
+    b = np.zeros((h, w, 4), np.float32)
+    if lib().rt3_debug_bloom(w, h, _p(c), float(np.float32(gain)), float(np.float32(threshold)), int(levels), _p(u1), _p(b)) != 0:
+        raise Fatal("rt3_debug_bloom refused its arguments (levels 1 .. 8, a finite threshold >= 0, 1 .. 2^26 pixels)")
+    return u1, b
 
 
 def cube_from_equirect(image, n):
@@ -1439,6 +1491,59 @@ class HipRenderer(Renderer):
         dark, gain = C.c_uint32(0), C.c_float(0.0)
         self._check(lib().rt3_debug_display_state(self._ctx, _p(hist), C.byref(dark), C.byref(gain)))
         return hist, int(dark.value), np.float32(gain.value)
+
+    # -- display sequences -------------------------------------------------------------------------------
+    def display_sequence(self, colour, prev=None, *, curve="filmic", transfer="srgb", exposure=1.0, auto=False, key=0.18, white=4.0, trim_low=102,
+                         trim_high=51, adapt=(256, 64), bloom=None):
+        """One frame of a sequence through the display transform (rt3_display_sequence) -> (words, exposure).  As display(), with two additions: with
+        auto=True the gain follows the sequence — prev is None for the first frame, else the exposure the previous call returned, and the level
+        moves adapt = (brighter, darker) / 1024 of the way to this frame's target —, and bloom = (levels, threshold, intensity) adds a bloom pyramid
+        before the tone curve (None: no bloom).  numpy: float32 (H, W, 4) -> (uint32 (H, W), an EXPOSURE record); prev an EXPOSURE record.  torch: a
+        contiguous (H, W, 4) float32 tensor on the GPU -> (an (H, W) uint32 tensor, a 16-byte int32 (4,) tensor holding the rt3_exposure record), both
+        on the GPU, computed on torch.cuda.current_stream() with no host wait; prev such a 16-byte tensor, kept on the device."""
+        p = display_sequence_params(curve, transfer, exposure, auto, key, white, trim_low, trim_high, adapt, bloom)
+        if type(colour).__module__.startswith("torch"):
+            import torch
+            if (not colour.is_cuda or colour.dtype != torch.float32 or colour.dim() != 3 or colour.shape[2] != 4
+                    or not colour.is_contiguous()):
+                raise Fatal("device colour must be a contiguous (H, W, 4) float32 tensor on the GPU")
+            if prev is not None and (not type(prev).__module__.startswith("torch") or not prev.is_cuda or not prev.is_contiguous()
+                                     or prev.numel() * prev.element_size() != 16):
+                raise Fatal("display_sequence: with a device frame prev must be a contiguous 16-byte tensor on the GPU")
+            h, w = colour.shape[:2]
+            out = torch.empty((h, w), dtype=getattr(torch, "uint32", torch.int32), device=colour.device)
+            state = torch.empty(4, dtype=torch.int32, device=colour.device)
+            stream = torch.cuda.current_stream(colour.device).cuda_stream
+            self._check(lib().rt3_display_sequence_device(self._ctx, w, h, C.c_void_p(colour.data_ptr()), C.byref(p),
+                                                          C.c_void_p(prev.data_ptr()) if prev is not None else None, C.c_void_p(state.data_ptr()),
+                                                          C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+            return out, state
+        c = np.ascontiguousarray(colour, np.float32)
+        if c.ndim != 3 or c.shape[2] != 4:
+            raise Fatal("display_sequence: colour must be float32 (H, W, 4)")
+        h, w = c.shape[:2]
+        before = np.array(prev, EXPOSURE).reshape(1) if prev is not None else None
+        out, state = np.zeros((h, w), np.uint32), np.zeros(1, EXPOSURE)
+        self._check(lib().rt3_display_sequence(self._ctx, w, h, _p(c), C.byref(p), _p(before), _p(state), _p(out)))
+        return out, state[0]
+
+    def display_sequence_device(self, width, height, d_rgba_ptr, params_c, d_prev_ptr, d_out_exposure_ptr, d_out_ptr, stream_ptr=None):
+        """Asynchronous rt3_display_sequence_device between device buffers: width * height float4 in, as many 4-byte words out, the 16-byte
+        rt3_exposure records before (0: none) and after (0: not wanted); the two may be the same buffer.  params_c: a DISPLAY_SEQUENCE_PARAMS."""
+        self._check(lib().rt3_display_sequence_device(self._ctx, width, height, C.c_void_p(d_rgba_ptr), C.byref(params_c), C.c_void_p(d_prev_ptr or 0),
+                                                      C.c_void_p(d_out_exposure_ptr or 0), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def display_bloom_state(self):
+        """What the last display_sequence call with bloom left on the device (rt3_debug_display_bloom; synchronous): (U_1 float32 (H_1, W_1, 4), B
+        float32 (H, W, 4)) — the pyramid's finest plane after the up-sampling sums, and the bloom the composite added, at the frame's size."""
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        rc = lib().rt3_debug_display_bloom(self._ctx, None, None, 0, C.byref(w), C.byref(h))
+        if w.value == 0:
+            self._check(rc)
+        u1 = np.zeros(((h.value + 1) // 2, (w.value + 1) // 2, 4), np.float32)
+        b = np.zeros((h.value, w.value, 4), np.float32)
+        self._check(lib().rt3_debug_display_bloom(self._ctx, _p(u1), _p(b), w.value * h.value, C.byref(w), C.byref(h)))
+        return u1, b
 
     def denoise_temporal(self, colour, aov, camera_c, prev=None, iterations=5, normal_power=128, sigma_luminance=4.0, sigma_depth=1.0,
                          alpha=0.2, moments_alpha=0.2, depth_tolerance=2.0, normal_tolerance=0.9, motion=None):

@@ -18,6 +18,7 @@
 //   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve (in place for 4.18)
 //   rt3_denoise.hpp         the launchers of the AOV-guided a-trous denoiser, its temporal form and the motion plane (kernels: rt3_denoise.hip)
 //   rt3_display.hpp         the launcher of the display transform (kernels: rt3_display.hip; the law: rt3_display_law.hpp)
+//   rt3_display_sequence.hpp  the launcher of display sequences (kernels: rt3_display_sequence.hip; the law: rt3_display_sequence_law.hpp)
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
 //   rt3_regroup.hpp         the group order of the multi-level filter again on the device (rt3_regroup*): the median split as stable sorts,
 //                           in LDS for parts of up to 4096 primitives
@@ -61,6 +62,8 @@
 #include "rt3_denoise.hpp"
 #include "rt3_display_law.hpp"
 #include "rt3_display.hpp"
+#include "rt3_display_sequence_law.hpp"
+#include "rt3_display_sequence.hpp"
 #include "rt3_scene_kernels.hpp"
 #include "rt3_regroup.hpp"
 #include "rt3_scene_build.hpp"
@@ -170,6 +173,9 @@ struct rt3_ctx {
     // the display transform's auto-exposure (rt3_display*): hist[512], dark, n and the gain's bits, allocated by the first call with the flag and
     // zeroed at the start of each such call; display_auto: there has been one (rt3_debug_display_state)
     DevBuf<uint32_t> d_display; bool display_auto = false;
+    // the bloom pyramid of rt3_display_sequence* (DESIGN.md 4.25): D_1 .. D_L one behind the other, grown on demand and kept after the call —
+    // plane 1 then holds U_1 of the bloom_w x bloom_h frame (bloom_levels != 0: there has been such a call); d_bloom_plane: rt3_debug_display_bloom's B
+    DevBuf<float4> d_bloom, d_bloom_plane; uint32_t bloom_w = 0, bloom_h = 0, bloom_levels = 0;
     // The host forms' inputs and results on the device, each carved out at a float4 offset by staged().  Shared by all of them: each one ends in
     // hipStreamSynchronize(ctx->stream), and no device form touches it.
     DevBuf<float4> stage;
@@ -3022,6 +3028,84 @@ int rt3_debug_display_state(rt3_ctx* ctx, uint32_t hist[512], uint32_t* dark, fl
     if (hist) std::memcpy(hist, state, rt3disp::kBins * sizeof(uint32_t));
     if (dark) *dark = state[rt3disp::kBins];
     if (gain) *gain = rt3disp::float_of(state[rt3disp::kBins + 2]);
+    return 0;
+}
+
+// ---- Display sequences
+static int display_sequence_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* rgba, const rt3_display_sequence_params* p, const void* prev,
+                                   const void* out_exposure, const void* out) {
+    if (!p) return fail(ctx, RT3_E_ARG, "p is NULL");
+    if (!rgba || !out) return fail(ctx, RT3_E_ARG, "rgba / out_pixels is NULL");
+    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must have 1 .. 2^26 pixels");
+    if (const char* why = rt3dseq::refusal(*p)) return fail(ctx, RT3_E_ARG, why);
+    if (prev && !(p->display.flags & RT3_DISPLAY_AUTO_EXPOSURE)) return fail(ctx, RT3_E_ARG, "prev_exposure needs RT3_DISPLAY_AUTO_EXPOSURE");
+    const size_t npix = (size_t)w * h;
+    const struct { const void* at; size_t bytes; } buf[4] = { { rgba, npix * sizeof(float4) }, { out, npix * sizeof(uint32_t) },
+                                                              { prev, sizeof(rt3_exposure) }, { out_exposure, sizeof(rt3_exposure) } };
+    for (int a = 0; a < 4; a++)
+        for (int b = a + 1; b < 4; b++) {
+            if (!buf[a].at || !buf[b].at || (a == 2 && buf[a].at == buf[b].at)) continue;      // prev == out_exposure: one record serves a sequence
+            if (ranges_overlap(buf[a].at, buf[a].bytes, buf[b].at, buf[b].bytes)) return fail(ctx, RT3_E_ARG, "rgba, out_pixels and the exposure records must not overlap (prev_exposure == out_exposure apart)");
+        }
+    return 0;
+}
+
+// rt3_display_device's launches with k_display_gain_step in k_display_gain's place, and with bloom the pyramid's 2 L - 1 launches in front of a map that
+// composites.  Nothing here waits for the device, and nothing is timed: rt3_get_stats stays as it was.
+int rt3_display_sequence_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_rgba, const rt3_display_sequence_params* p, const void* d_prev,
+                                void* d_out_exposure, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = display_sequence_checks(ctx, w, h, d_rgba, p, d_prev, d_out_exposure, d_out);
+    if (rc) return rc;
+    if ((uintptr_t)d_rgba % 16u != 0 || (uintptr_t)d_out % 4u != 0 || (uintptr_t)d_prev % 4u != 0 || (uintptr_t)d_out_exposure % 4u != 0)
+        return fail(ctx, RT3_E_ARG, "d_rgba must be 16-byte, d_out_pixels and the exposure records 4-byte aligned");
+    const rt3_display_params& d = p->display;
+    const bool auto_exposure = (d.flags & RT3_DISPLAY_AUTO_EXPOSURE) != 0;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    if (auto_exposure && (rc = ctx->d_display.ensure(ctx, rt3disp::kStateWords))) return rc;
+    if (p->bloom_levels && (rc = ctx->d_bloom.ensure(ctx, rt3dseq::pyramid_texels(w, h, p->bloom_levels)))) return rc;
+    const DisplaySequenceLaunch S{ { w * h, d.curve, d.transfer, auto_exposure, d.trim_low, d.trim_high, d.exposure, d.key, d.white, d_rgba, d_out,
+                                     auto_exposure ? ctx->d_display.get() : nullptr },
+                                   w, h, p->adapt_brighter, p->adapt_darker, p->bloom_levels, p->bloom_threshold, p->bloom_intensity,
+                                   (const rt3_exposure*)d_prev, (rt3_exposure*)d_out_exposure, p->bloom_levels ? ctx->d_bloom.get() : nullptr };
+    RT3_HIP(display_sequence_launch(S, stream));
+    if (auto_exposure) ctx->display_auto = true;
+    if (p->bloom_levels) { ctx->bloom_w = w; ctx->bloom_h = h; ctx->bloom_levels = p->bloom_levels; }
+    return leave(ctx, stream);
+}
+
+int rt3_display_sequence(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* rgba, const rt3_display_sequence_params* p, const rt3_exposure* prev,
+                         rt3_exposure* out_exposure, uint32_t* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = display_sequence_checks(ctx, w, h, rgba, p, prev, out_exposure, out);
+    if (rc) return rc;
+    if (prev && prev->level > rt3dseq::kMaxLevel) return fail(ctx, RT3_E_ARG, "prev_exposure->level is above 511 << 19");
+    const size_t npix = (size_t)w * h;
+    return staged(ctx, { stage_in(rgba, npix * sizeof(float4)), stage_in(prev, sizeof(rt3_exposure)), stage_out(out_exposure, sizeof(rt3_exposure)),
+                         stage_out(out, npix * sizeof(uint32_t)) },
+                  [&](void* const* d) { return rt3_display_sequence_device(ctx, w, h, d[0], p, d[1], d[2], d[3], ctx->stream); });
+}
+
+int rt3_debug_display_bloom(rt3_ctx* ctx, float* out_u1, float* out_bloom, uint64_t capacity_pixels, uint32_t* w_out, uint32_t* h_out) {
+    if (!ctx) return RT3_E_ARG;
+    if (!w_out || !h_out) return fail(ctx, RT3_E_ARG, "w / h is NULL");
+    if (ctx->bloom_levels == 0) return fail(ctx, RT3_E_STATE, "no rt3_display_sequence call with bloom_levels >= 1 on this context");
+    const uint32_t w = ctx->bloom_w, h = ctx->bloom_h, w1 = rt3dseq::half_of(w), h1 = rt3dseq::half_of(h);
+    const size_t npix = (size_t)w * h;
+    *w_out = w; *h_out = h;
+    if (capacity_pixels < npix) return fail(ctx, RT3_E_ARG, "capacity_pixels is smaller than the frame of the last bloom call");
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, nullptr, &stream))) return rc;            // behind the call that wrote the pyramid, whatever stream it ran on
+    if (out_u1) RT3_HIP(hipMemcpyAsync(out_u1, ctx->d_bloom.get(), (size_t)w1 * h1 * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    if (out_bloom) {
+        if ((rc = ctx->d_bloom_plane.ensure(ctx, npix))) return rc;
+        RT3_HIP(bloom_plane_launch(ctx->d_bloom.get(), w1, h1, ctx->d_bloom_plane.get(), w, h, ctx->bloom_levels, stream));
+        RT3_HIP(hipMemcpyAsync(out_bloom, ctx->d_bloom_plane.get(), npix * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    }
+    if ((rc = leave(ctx, stream))) return rc;
+    RT3_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 

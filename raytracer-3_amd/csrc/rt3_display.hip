@@ -116,20 +116,29 @@ MapKernel map_of(uint32_t curve, uint32_t transfer) {
 
 }  // namespace
 
+hipError_t display_histogram_launch(const DisplayLaunch& L, hipStream_t stream) {
+    // zeroed at the start of the call, not at its end: rt3_debug_display_state reads what the call left
+    const hipError_t e = hipMemsetAsync(L.state, 0, kStateWords * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    const uint32_t per_block = kHistBlock * kHistLoads, want = (L.npix + per_block - 1) / per_block;
+    hipLaunchKernelGGL(k_display_histogram, dim3(want < kHistMaxGrid ? want : kHistMaxGrid), dim3(kHistBlock), 0, stream, (const float4*)L.rgba, L.npix,
+                       L.state);
+    return hipGetLastError();
+}
+
+hipError_t display_map_launch(const DisplayLaunch& L, hipStream_t stream) {
+    const MapKernel map = L.auto_exposure ? map_of<true>(L.curve, L.transfer) : map_of<false>(L.curve, L.transfer);
+    hipLaunchKernelGGL(map, dim3(display_grid(L.npix)), dim3(kDispBlock), 0, stream, (const float4*)L.rgba, (uint32_t*)L.out, L.npix, L.exposure,
+                       (const uint32_t*)L.state, L.white);
+    return hipGetLastError();
+}
+
 hipError_t display_launch(const DisplayLaunch& L, hipStream_t stream) {
-    const dim3 grid(display_grid(L.npix)), block(kDispBlock);
-    const float4* in = (const float4*)L.rgba;
     hipError_t e;
     if (L.auto_exposure) {
-        // zeroed at the start of the call, not at its end: rt3_debug_display_state reads what the call left
-        if ((e = hipMemsetAsync(L.state, 0, kStateWords * sizeof(uint32_t), stream)) != hipSuccess) return e;
-        const uint32_t per_block = kHistBlock * kHistLoads, want = (L.npix + per_block - 1) / per_block;
-        hipLaunchKernelGGL(k_display_histogram, dim3(want < kHistMaxGrid ? want : kHistMaxGrid), dim3(kHistBlock), 0, stream, in, L.npix, L.state);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = display_histogram_launch(L, stream)) != hipSuccess) return e;
         hipLaunchKernelGGL(k_display_gain, dim3(1), dim3(kBins), 0, stream, L.state, L.trim_low, L.trim_high, L.exposure, L.key);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    const MapKernel map = L.auto_exposure ? map_of<true>(L.curve, L.transfer) : map_of<false>(L.curve, L.transfer);
-    hipLaunchKernelGGL(map, grid, block, 0, stream, in, (uint32_t*)L.out, L.npix, L.exposure, (const uint32_t*)L.state, L.white);
-    return hipGetLastError();
+    return display_map_launch(L, stream);
 }

@@ -15,3 +15,7 @@ struct DisplayLaunch {
     uint32_t* state;
 };
 hipError_t display_launch(const DisplayLaunch& L, hipStream_t stream);
+// Its first and last steps on their own, for rt3_display_sequence.hip, which puts a gain kernel of its own between them: the state zeroed and
+// k_display_histogram (auto_exposure only); k_display_map, which with auto_exposure reads the gain from word kBins + 2 of the state.
+hipError_t display_histogram_launch(const DisplayLaunch& L, hipStream_t stream);
+hipError_t display_map_launch(const DisplayLaunch& L, hipStream_t stream);

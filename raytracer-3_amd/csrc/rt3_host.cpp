@@ -9,6 +9,7 @@
 #include "rt3_env_sample.hpp"
 #include "rt3_light_sample.hpp"
 #include "rt3_display_law.hpp"
+#include "rt3_display_sequence_law.hpp"
 #include "rt3_lens_law.hpp"
 
 #include <cmath>
@@ -595,6 +596,58 @@ extern "C" int rt3_debug_display_pixel(const float rgb[3], float gain, const rt3
 extern "C" int rt3_debug_display_srgb_table(uint8_t out[4096]) {
     if (!out) return RT3_E_ARG;
     std::memcpy(out, rt3disp::kSrgbTable, sizeof rt3disp::kSrgbTable);
+    return 0;
+}
+
+// The law of display sequences (rt3.h "Display sequences") on the host: the functions of rt3_display_sequence_law.hpp the kernels call,
+// one histogram or one frame per call, serially.  A refused call writes nothing.
+extern "C" int rt3_debug_exposure_step(const rt3_exposure* prev, const uint32_t hist[512], const rt3_display_sequence_params* p, rt3_exposure* out) {
+    if (!hist || !p || !out || rt3dseq::refusal(*p)) return RT3_E_ARG;
+    const rt3_display_params& d = p->display;
+    if (!(d.flags & RT3_DISPLAY_AUTO_EXPOSURE)) {
+        if (prev) return RT3_E_ARG;
+        *out = rt3_exposure{ 0u, 0u, d.exposure, 0u };
+        return 0;
+    }
+    if (prev && prev->level > rt3dseq::kMaxLevel) return RT3_E_ARG;
+    uint64_t n = 0;
+    const uint32_t target = rt3dseq::target_of(hist, d.trim_low, d.trim_high, &n);
+    *out = rt3dseq::exposure_next(prev ? prev->level : 0u, prev ? prev->frames : 0u, n, target, p->adapt_brighter, p->adapt_darker, d.exposure, d.key);
+    return 0;
+}
+extern "C" int rt3_debug_bloom(uint32_t w, uint32_t h, const float* rgba, float gain, float threshold, uint32_t levels, float* out_u1, float* out_bloom) {
+    using namespace rt3dseq;
+    if (!rgba || w == 0 || h == 0 || (uint64_t)w * h > (1ull << 26) || levels < 1 || levels > kMaxBloomLevels) return RT3_E_ARG;
+    if (!(threshold >= 0.0f) || !(threshold <= kFltMax)) return RT3_E_ARG;
+    const auto store = [](std::vector<float>& plane, size_t t, const Rgb& c) { plane[4 * t] = c.r; plane[4 * t + 1] = c.g; plane[4 * t + 2] = c.b; plane[4 * t + 3] = 0.0f; };
+    std::vector<std::vector<float>> d(levels + 1);                  // d[l]: D_l, then U_l; d[0]: b0
+    std::vector<uint32_t> pw(levels + 1), ph(levels + 1);
+    pw[0] = w; ph[0] = h;
+    d[0].resize(4 * (size_t)w * h);
+    for (size_t t = 0; t < (size_t)w * h; t++) store(d[0], t, bright(exposed(rgba[4 * t], rgba[4 * t + 1], rgba[4 * t + 2], gain), threshold));
+    for (uint32_t l = 1; l <= levels; l++) {
+        pw[l] = half_of(pw[l - 1]); ph[l] = half_of(ph[l - 1]);
+        d[l].resize(4 * (size_t)pw[l] * ph[l]);
+        const Plane s{ d[l - 1].data(), pw[l - 1], ph[l - 1] };
+        for (uint32_t j = 0; j < ph[l]; j++)
+            for (uint32_t i = 0; i < pw[l]; i++) store(d[l], (size_t)j * pw[l] + i, down_texel(s, i, j));
+    }
+    for (uint32_t l = levels - 1; l >= 1; l--) {
+        const Plane u{ d[l + 1].data(), pw[l + 1], ph[l + 1] }, own{ d[l].data(), pw[l], ph[l] };
+        for (uint32_t j = 0; j < ph[l]; j++)
+            for (uint32_t i = 0; i < pw[l]; i++) store(d[l], (size_t)j * pw[l] + i, sum(texel(own, i, j), up_texel(u, i, j)));
+    }
+    if (out_u1) std::memcpy(out_u1, d[1].data(), d[1].size() * sizeof(float));
+    if (out_bloom) {
+        const Plane u1{ d[1].data(), pw[1], ph[1] };
+        const float weight = level_weight(levels);
+        for (uint32_t j = 0; j < h; j++)
+            for (uint32_t i = 0; i < w; i++) {
+                const Rgb b = bloom_texel(u1, i, j, weight);
+                float* o = out_bloom + 4 * ((size_t)j * w + i);
+                o[0] = b.r; o[1] = b.g; o[2] = b.b; o[3] = 0.0f;
+            }
+    }
     return 0;
 }
 

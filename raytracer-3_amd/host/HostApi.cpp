@@ -438,6 +438,13 @@ void HipRenderer::display(Camera& camera, const std::vector<float>& rgba, const 
     if (rt3_display(ctx[0], camera.w(), camera.h(), rgba.data(), &params, camera.get_frame().d()) != 0) throw Fatal(rt3_last_error(ctx[0]));
 }
 
+void HipRenderer::display_sequence(Camera& camera, const std::vector<float>& rgba, const rt3_display_sequence_params& params, rt3_exposure& state) const {
+    if (rgba.size() != 4 * (size_t)camera.w() * camera.h()) throw Fatal("display_sequence: the frame's size differs from the camera's");
+    const bool follows = (params.display.flags & RT3_DISPLAY_AUTO_EXPOSURE) != 0;     // (without the flag there is no state to pass in)
+    if (rt3_display_sequence(ctx[0], camera.w(), camera.h(), rgba.data(), &params, follows ? &state : nullptr, &state, camera.get_frame().d()) != 0)
+        throw Fatal(rt3_last_error(ctx[0]));
+}
+
 std::vector<float> HipRenderer::motion(Camera& camera, const std::vector<float>& prev_center_radius,
                                        const std::vector<float>& prev_vertices_xyzw) const {
     const std::vector<rt3_aov> guides = aov(camera);

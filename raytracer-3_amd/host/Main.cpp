@@ -11,7 +11,8 @@
 // --env-sampling (importance sampling of that map with shadow rays), --light-sampling (the same for the emissive primitives),
 // --display (the image written is the linear frame through exposure, a tone curve and a transfer function), --lens, --lens-fov and
 // --lens-extent (the frame of another lens model at the scene's camera position: equirectangular, fisheye, orthographic, cube),
-// --lens-frames (a sequence of such frames, denoised temporally through the lens).
+// --lens-frames (a sequence of such frames, denoised temporally through the lens), --display-frames, --adapt and --bloom (an image
+// per frame of a sequence through the display transform, an exposure that follows the sequence, a bloom pyramid).
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -63,6 +64,14 @@ struct Options {
     uint32_t lens_frames = 1;                                      // --lens: frames of a sequence of lens frames (frame k renders with seed + k)
     bool have_lens_frames = false;
     rt3_display_params display_params{ RT3_DISPLAY_FILMIC, RT3_DISPLAY_SRGB, 0u, 102u, 51u, 1.0f, 0.18f, 4.0f };      // the defaults of DESIGN.md 4.22
+    std::string display_frames;                                    // with --display and a sequence: PREFIX of one image per frame (rt3_display_sequence)
+    bool have_adapt = false, have_bloom = false;
+    uint32_t adapt[2] = { 256u, 64u };                             // --adapt: the share of the way to a brighter / darker target per frame, in 1/1024
+    uint32_t bloom_levels = 0;                                     // --bloom: the pyramid's levels, the threshold, the intensity
+    float bloom_threshold = 1.0f, bloom_intensity = 0.25f;
+    rt3_display_sequence_params sequence_params() const {
+        return rt3_display_sequence_params{ display_params, adapt[0], adapt[1], bloom_levels, bloom_threshold, bloom_intensity, { 0u, 0u, 0u } };
+    }
 };
 
 void print_usage(const char* exe) {
@@ -103,6 +112,13 @@ void print_usage(const char* exe) {
               << "\t   --display\tMode X: CURVE[,TRANSFER[,EXPOSURE]]: the image written is the linear frame (with a single-frame --denoise, the\n"
               << "\t\t\tdenoised one) through a display transform: CURVE clamp | reinhard | filmic, TRANSFER linear | gamma2 | srgb (default: srgb),\n"
               << "\t\t\tEXPOSURE a positive gain, or auto: from the frame's trimmed log-average luminance (default: 1).\n"
+              << "\t   --display-frames\tWith --display and a sequence (--frames or --lens-frames): also write PREFIX.<k>.ppm (.png under -f png) for every\n"
+              << "\t\t\tframe k: the display transform of that frame (with --denoise PREFIX, of its temporally denoised frame); an auto exposure\n"
+              << "\t\t\tfollows the sequence instead of jumping from frame to frame (rt3_display_sequence).\n"
+              << "\t   --adapt\tWith --display ...,auto: BRIGHTER,DARKER: the share of the way the exposure moves per frame towards a brighter and\n"
+              << "\t\t\ta darker target, in 1/1024, each 1 .. 1024 (default: 256,64).\n"
+              << "\t   --bloom\tWith --display: LEVELS[,THRESHOLD[,INTENSITY]]: add INTENSITY times a bloom pyramid of LEVELS levels (1 .. 8) of what\n"
+              << "\t\t\texceeds THRESHOLD after the exposure, before the tone curve (default: threshold 1, intensity 0.25).\n"
               << "\t   --lens\tMode X: equirect | fisheye | ortho | cube: render the frame of that lens model (rt3_render_lens) at the scene's camera\n"
               << "\t\t\tposition, looking where the camera looks, instead of the camera's; cube needs -H equal to 6 times -W (the layout --env reads).\n"
               << "\t\t\t--hdr, --aov, --denoise and --display act on the lens frame. Not with --adaptive, --frames (a sequence: --lens-frames) or --gpus above 1.\n"
@@ -130,6 +146,22 @@ bool parse_u32(const std::string& text, const char* what_lower, const char* what
     return false;
 }
 
+// "a,b,c" -> the numbers, at most cap of them: how many there are, -1 if a field is not a finite number or there are more than cap.
+int parse_numbers(const std::string& text, double* out, int cap) {
+    int n = 0;
+    size_t at = 0;
+    for (;;) {
+        const size_t comma = text.find(',', at);
+        const std::string field = text.substr(at, comma == std::string::npos ? comma : comma - at);
+        char* end = nullptr;
+        const double v = std::strtod(field.c_str(), &end);
+        if (n == cap || field.empty() || end == field.c_str() || *end != '\0' || !std::isfinite(v)) return -1;
+        out[n++] = v;
+        if (comma == std::string::npos) return n;
+        at = comma + 1;
+    }
+}
+
 // 1 = go on, 0 = help was shown, -1 = usage error (the three return values of the reference's parse_cli)
 int parse_cli(Options& opt, int argc, const char** argv) {
     bool have_path = false;
@@ -155,7 +187,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
                            key == "--slide" || key == "--adaptive" || key == "--counts" || key == "--regroup" ||
                            key == "--rays" || key == "--radiance" || key == "--env" || key == "--display" || key == "--lens" || key == "--lens-fov" ||
-                           key == "--lens-extent" || key == "--lens-frames";
+                           key == "--lens-extent" || key == "--lens-frames" || key == "--display-frames" || key == "--adapt" || key == "--bloom";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -248,6 +280,26 @@ int parse_cli(Options& opt, int argc, const char** argv) {
             }
             opt.display = true;
         }
+        else if (key == "--display-frames") opt.display_frames = value;
+        else if (key == "--adapt") {                                 // BRIGHTER,DARKER in 1/1024
+            double v[3];
+            if (parse_numbers(value, v, 3) != 2 || !(v[0] >= 1.0 && v[0] <= 1024.0 && v[1] >= 1.0 && v[1] <= 1024.0) || v[0] != std::floor(v[0]) ||
+                v[1] != std::floor(v[1])) {
+                std::cerr << "Invalid adapt '" << value << "' (BRIGHTER,DARKER: two whole numbers 1 .. 1024)" << std::endl;
+                return -1;
+            }
+            opt.adapt[0] = (uint32_t)v[0]; opt.adapt[1] = (uint32_t)v[1]; opt.have_adapt = true;
+        }
+        else if (key == "--bloom") {                                 // LEVELS[,THRESHOLD[,INTENSITY]]
+            double v[4] = { 0.0, 1.0, 0.25, 0.0 };
+            const int n = parse_numbers(value, v, 4);
+            if (n < 1 || n > 3 || !(v[0] >= 1.0 && v[0] <= 8.0) || v[0] != std::floor(v[0]) || !(v[1] >= 0.0) || !std::isfinite((float)v[1]) ||
+                !(v[2] >= 0.0) || !std::isfinite((float)v[2])) {
+                std::cerr << "Invalid bloom '" << value << "' (LEVELS[,THRESHOLD[,INTENSITY]]: 1 .. 8 levels, a threshold and an intensity of at least 0)" << std::endl;
+                return -1;
+            }
+            opt.bloom_levels = (uint32_t)v[0]; opt.bloom_threshold = (float)v[1]; opt.bloom_intensity = (float)v[2]; opt.have_bloom = true;
+        }
         else if (key == "--lens") {
             if (value == "equirect") opt.lens = RT3_LENS_EQUIRECT;
             else if (value == "fisheye") opt.lens = RT3_LENS_FISHEYE;
@@ -327,6 +379,22 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     }
     if (mode_r && opt.display) {
         std::cerr << "--display needs the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
+    if (!opt.display_frames.empty() && !opt.display) {
+        std::cerr << "--display-frames needs --display: it is the transform every frame goes through." << std::endl;
+        return -1;
+    }
+    if (!opt.display_frames.empty() && opt.frames < 2 && opt.lens_frames < 2) {
+        std::cerr << "--display-frames needs a sequence: pass --frames N (with --lens: --lens-frames N) with N of at least 2." << std::endl;
+        return -1;
+    }
+    if (opt.have_adapt && !(opt.display && (opt.display_params.flags & RT3_DISPLAY_AUTO_EXPOSURE))) {
+        std::cerr << "--adapt needs --display with the auto exposure: a given exposure does not move." << std::endl;
+        return -1;
+    }
+    if (opt.have_bloom && !opt.display) {
+        std::cerr << "--bloom needs --display: it is added before the tone curve." << std::endl;
         return -1;
     }
     if (mode_r && opt.adaptive) {
@@ -533,6 +601,20 @@ int main(int argc, const char** argv) {
             const double dx = (double)la.from.x - la.at.x, dz = (double)la.from.z - la.at.z;
             return glm::vec3(la.at.x + (c * dx + sn * dz), (double)la.from.y, la.at.z + (c * dz - sn * dx));
         };
+        // --display-frames, frame k: the display transform of `frame` as one frame of the sequence (the exposure's state is carried from frame to
+        // frame), written as PREFIX.k.ppm | .png.  --bloom alone: the final image goes through the same call with a state of its own.
+        rt3_exposure exposure_state{};
+        const auto write_display_frame = [&](uint32_t k, const std::vector<float>& frame) {
+            renderer.display_sequence(cam, frame, opt.sequence_params(), exposure_state);
+            const std::string name = opt.display_frames + "." + std::to_string(k) + (opt.png ? ".png" : ".ppm");
+            if (opt.png) cam.get_frame().to_png(name);
+            else cam.get_frame().to_ppm(name);
+        };
+        const auto display_image = [&](const std::vector<float>& frame) {
+            rt3_exposure alone{};
+            if (opt.have_bloom) renderer.display_sequence(cam, frame, opt.sequence_params(), alone);
+            else renderer.display(cam, frame, opt.display_params);
+        };
         if (opt.lens != 0) {                                         // the frame of another lens model, at the camera's place
             const uint32_t w = opt.width, h = opt.height;
             const float origin[3] = { 0.0f, 0.0f, 0.0f }, ahead[3] = { 0.0f, 0.0f, -1.0f }, up[3] = { 0.0f, 1.0f, 0.0f };       // the reference camera
@@ -560,7 +642,8 @@ int main(int argc, const char** argv) {
                     const std::vector<float> out = renderer.denoise_temporal_lens(lens, w, h, linear, guides, tp, history, motion);
                     const std::string name = opt.denoise_path + "." + std::to_string(k) + ".pfm";
                     if (rt3_frame_to_pfm(out.data(), w, h, 3, 4, name.c_str()) != 0) throw Fatal("Could not write '" + name + "'");
-                }
+                    if (!opt.display_frames.empty()) write_display_frame(k, out);
+                } else if (!opt.display_frames.empty()) write_display_frame(k, linear);
             }
             std::cerr << "rendered a lens frame of " << w << "x" << h << " x " << path.spp << " spp in " << st.total_ms << " ms on device 0: " << st.ray_casts
                       << " rays, " << st.launches << " launches\n";
@@ -570,7 +653,8 @@ int main(int argc, const char** argv) {
             const std::vector<float> denoised = opt.denoise_path.empty() || temporal ? std::vector<float>() : renderer.denoise(w, h, linear, aov, dp);
             // the image: --display's transform, or the one that reproduces the ordinary Mode-X pack (no curve, the scene's gamma)
             const rt3_display_params pack{ RT3_DISPLAY_CLAMP, (path.flags & RT3_FLAG_GAMMA2) ? RT3_DISPLAY_GAMMA2 : RT3_DISPLAY_LINEAR, 0u, 102u, 51u, 1.0f, 0.18f, 4.0f };
-            renderer.display(cam, opt.display && !denoised.empty() ? denoised : linear, opt.display ? opt.display_params : pack);
+            if (opt.display) display_image(denoised.empty() ? linear : denoised);
+            else renderer.display(cam, linear, pack);
             if (opt.png) cam.get_frame().to_png(opt.output_path);
             else cam.get_frame().to_ppm(opt.output_path);
             if (!opt.hdr_path.empty() && rt3_frame_to_pfm(linear.data(), w, h, 3, 4, opt.hdr_path.c_str()) != 0) throw Fatal("Could not write '" + opt.hdr_path + "'");
@@ -605,7 +689,8 @@ int main(int argc, const char** argv) {
                 const std::vector<float> out = renderer.denoise_temporal(cam, tp, history, motion);
                 const std::string name = opt.denoise_path + "." + std::to_string(k) + ".pfm";
                 if (rt3_frame_to_pfm(out.data(), cam.w(), cam.h(), 3, 4, name.c_str()) != 0) throw Fatal("Could not write '" + name + "'");
-            }
+                if (!opt.display_frames.empty()) write_display_frame(k, out);
+            } else if (!opt.display_frames.empty()) write_display_frame(k, renderer.hdr());
         }
 
         const rt3_stats st = renderer.stats();
@@ -615,7 +700,7 @@ int main(int argc, const char** argv) {
         std::vector<float> denoised;                                 // --display with a single-frame --denoise: the frame both outputs come from
         if (opt.display) {                                           // the image becomes the display transform of the linear frame
             if (!opt.denoise_path.empty() && !temporal) denoised = renderer.denoise(cam, dp);
-            renderer.display(cam, denoised.empty() ? renderer.hdr() : denoised, opt.display_params);
+            display_image(denoised.empty() ? renderer.hdr() : denoised);
         }
         if (opt.png) cam.get_frame().to_png(opt.output_path);
         else cam.get_frame().to_ppm(opt.output_path);

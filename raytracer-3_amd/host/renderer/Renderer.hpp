@@ -81,6 +81,9 @@ public:
     // A linear (r, g, b, .) frame of the camera's size — hdr()'s, a denoiser's — through the display transform on device 0 (rt3_display): exposure,
     // tone curve, transfer function; fills camera.get_frame().d() with the words render() would pack
     void display(Camera& camera, const std::vector<float>& rgba, const rt3_display_params& params) const;
+    // The same for one frame of a sequence (rt3_display_sequence): with auto-exposure the gain follows the sequence through `state` —
+    // zeroed before the first frame, replaced by every call —, and params.bloom_levels adds a bloom pyramid before the tone curve
+    void display_sequence(Camera& camera, const std::vector<float>& rgba, const rt3_display_sequence_params& params, rt3_exposure& state) const;
     // Mode X only: path-traced radiance along the caller's rays on device 0 (rt3_radiance), (r, g, b, 0) per ray: path.spp samples from sample_begin
     // on, path.max_depth, path.seed, path.t_min and the BLACK_BACKGROUND, ENV_SAMPLING and LIGHT_SAMPLING bits of path.flags; keys: empty (a ray's index is its key) or one per ray
     std::vector<float> radiance(const std::vector<rt3_ray>& rays, const std::vector<uint32_t>& keys = {}, uint32_t sample_begin = 0) const;

@@ -296,6 +296,29 @@ void oracle_loops() {
     CHECK(std::memcmp(x.p, img.p, x.bytes()) == 0);
 }
 
+// Display sequences on the host (rt3_debug_exposure_step, rt3_debug_bloom): every level of the pyramid at sizes that reach 1 x 1 before the last one.
+void display_sequences() {
+    const uint32_t sizes[3][2] = { { 1, 1 }, { 3, 2 }, { 67, 3 } };
+    for (const auto& s : sizes) {
+        const uint32_t w = s[0], h = s[1], w1 = (w + 1) / 2, h1 = (h + 1) / 2;
+        Exact<float> frame(4 * (size_t)w * h), u1(4 * (size_t)w1 * h1), bloom(4 * (size_t)w * h);
+        for (size_t i = 0; i < frame.n; i++) frame.p[i] = (float)((i * 7) % 13) * 0.5f;
+        CHECK(rt3_debug_bloom(w, h, frame.p, 1.0f, 0.0f, 8, u1.p, bloom.p) == 0);
+        CHECK(rt3_debug_bloom(w, h, frame.p, 1.0f, 0.0f, 8, nullptr, bloom.p) == 0 && rt3_debug_bloom(w, h, frame.p, 1.0f, 0.0f, 8, u1.p, nullptr) == 0);
+        for (size_t i = 0; i < bloom.n; i++) CHECK(bloom.p[i] >= 0.0f && bloom.p[i] <= 8.0f);
+        CHECK(rt3_debug_bloom(w, h, frame.p, 1.0f, 0.0f, 9, u1.p, bloom.p) == RT3_E_ARG);
+    }
+    Exact<uint32_t> hist(512);
+    for (size_t k = 0; k < hist.n; k++) hist.p[k] = (uint32_t)(k % 5);
+    rt3_display_sequence_params p = { { RT3_DISPLAY_FILMIC, RT3_DISPLAY_SRGB, RT3_DISPLAY_AUTO_EXPOSURE, 102, 51, 1.0f, 0.18f, 4.0f }, 256, 64, 0, 1.0f, 0.25f, { 0, 0, 0 } };
+    rt3_exposure a, b;
+    CHECK(rt3_debug_exposure_step(nullptr, hist.p, &p, &a) == 0 && a.frames == 1 && a.level <= (511u << 19));
+    const rt3_exposure dark = { 0, 5, 1.0f, 0 };
+    CHECK(rt3_debug_exposure_step(&dark, hist.p, &p, &b) == 0 && b.frames == 6 && b.level > 0 && b.level < a.level);
+    p._pad[2] = 1;
+    CHECK(rt3_debug_exposure_step(&dark, hist.p, &p, &b) == RT3_E_ARG);
+}
+
 }  // namespace
 
 int main(int argc, const char** argv) {
@@ -313,6 +336,7 @@ int main(int argc, const char** argv) {
         scenes();
         sphere_plans();
         lens_law();
+        display_sequences();
         oracle_loops();
         std::printf("rt3_asan selftest: %s (%d failed checks)\n", failures ? "FAILED" : "ok", failures);
         return failures ? 1 : 0;

@@ -105,6 +105,9 @@ int rt3_motion_optic_device(rt3_ctx*, uint32_t, uint32_t, const rt3_lens*, const
 int rt3_display(rt3_ctx*, uint32_t, uint32_t, const float*, const rt3_display_params*, uint32_t*) { return RT3_E_DEVICE; }     // (rt3_debug_display_bin / _gain / _pixel / _srgb_table are host code)
 int rt3_display_device(rt3_ctx*, uint32_t, uint32_t, const void*, const rt3_display_params*, void*, void*) { return RT3_E_DEVICE; }
 int rt3_debug_display_state(rt3_ctx*, uint32_t*, uint32_t*, float*) { return RT3_E_DEVICE; }
+int rt3_display_sequence(rt3_ctx*, uint32_t, uint32_t, const float*, const rt3_display_sequence_params*, const rt3_exposure*, rt3_exposure*, uint32_t*) { return RT3_E_DEVICE; }     // (rt3_debug_exposure_step / rt3_debug_bloom are host code)
+int rt3_display_sequence_device(rt3_ctx*, uint32_t, uint32_t, const void*, const rt3_display_sequence_params*, const void*, void*, void*, void*) { return RT3_E_DEVICE; }
+int rt3_debug_display_bloom(rt3_ctx*, float*, float*, uint64_t, uint32_t*, uint32_t*) { return RT3_E_DEVICE; }
 // (rt3_rows_owned / rt3_row_of_local are pure host arithmetic that happens to live in rt3_device.hip)
 uint32_t rt3_rows_owned(const rt3_params* p) {
     uint32_t n = 0;
