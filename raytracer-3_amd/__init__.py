@@ -270,7 +270,15 @@ EXPORTS = [
     "rt3_render_lens_aov_device", "rt3_debug_lens_ray",
     "rt3_denoise_temporal_optic", "rt3_denoise_temporal_optic_device", "rt3_motion_optic", "rt3_motion_optic_device", "rt3_debug_turns",
     "rt3_debug_optic_pixel",
+    "rt3_set_texture", "rt3_set_texture_device", "rt3_clear_textures", "rt3_texture_size", "rt3_bind_sphere_textures",
+    "rt3_bind_sphere_textures_device", "rt3_bind_mesh_textures", "rt3_bind_mesh_textures_device", "rt3_debug_texture_lookup",
+    "rt3_debug_texture_sphere_uv", "rt3_debug_texture_face_uv",
 ]
+TEX_MAX_TEXTURES = 256   # RT3_TEX_MAX_TEXTURES: texture slots per context
+TEX_MAX_SIDE = 8192      # RT3_TEX_MAX_SIDE
+TEX_NONE = 0xFFFFFFFF    # RT3_TEX_NONE: a primitive without a texture
+TEX_REPEAT, TEX_CLAMP = 0, 1
+_TEX_WRAPS = {"repeat": TEX_REPEAT, "clamp": TEX_CLAMP, TEX_REPEAT: TEX_REPEAT, TEX_CLAMP: TEX_CLAMP}
 ABI_VERSION = 3          # RT3_ABI_VERSION of include/rt3.h these bindings (the STATS / PARAMS struct layouts below) were written against
 
 _lib = None
@@ -368,6 +376,12 @@ def lib():
         "rt3_motion_optic": (i32, [vp, u32, u32, vp, vp, vp, u32, vp, u32, vp]),
         "rt3_motion_optic_device": (i32, [vp, u32, u32, vp, vp, vp, u32, vp, u32, vp, vp]),
         "rt3_debug_turns": (f32, [f32, f32]), "rt3_debug_optic_pixel": (i32, [vp, u32, u32, vp, u32, vp, vp, vp]),
+        "rt3_set_texture": (i32, [vp, u32, vp, u32, u32, u32]), "rt3_set_texture_device": (i32, [vp, u32, vp, u32, u32, u32, vp]),
+        "rt3_clear_textures": (i32, [vp]), "rt3_texture_size": (i32, [vp, u32, vp, vp, vp]),
+        "rt3_bind_sphere_textures": (i32, [vp, vp, u32]), "rt3_bind_sphere_textures_device": (i32, [vp, vp, u32, vp]),
+        "rt3_bind_mesh_textures": (i32, [vp, vp, vp, u32]), "rt3_bind_mesh_textures_device": (i32, [vp, vp, vp, u32, vp]),
+        "rt3_debug_texture_lookup": (i32, [vp, u32, u32, u32, vp, vp]), "rt3_debug_texture_sphere_uv": (i32, [vp, vp]),
+        "rt3_debug_texture_face_uv": (i32, [vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -404,6 +418,61 @@ def environment_lookup(cube, d):
         if fn(_p(rgba), rgba.shape[1], C.c_void_p(dirs.ctypes.data + 12 * k), C.c_void_p(out.ctypes.data + 12 * k)) != 0:
             raise Fatal("rt3_debug_environment_lookup refused its arguments (1 <= N <= 2048)")
     return out[0] if np.ndim(d) == 1 else out
+
+
+def _image_rgba(image):
+    """(H, W, 3 | 4) -> contiguous float32 (H, W, 4), the layout rt3_set_texture takes (row 0 on top; the fourth channel is ignored: 0 when absent)."""
+    a = np.asarray(image, np.float32)
+    if a.ndim != 3 or a.shape[2] not in (3, 4) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise Fatal("a texture is an array of shape (H, W, 3) or (H, W, 4)")
+    if a.shape[2] == 3:
+        a = np.concatenate([a, np.zeros(a.shape[:2] + (1,), np.float32)], axis=2)
+    return np.ascontiguousarray(a)
+
+
+def _torch_word_dtypes():
+    import torch
+    return tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+
+
+def _tex_wrap(wrap):
+    if wrap not in _TEX_WRAPS:
+        raise Fatal("wrap is 'repeat' or 'clamp'")
+    return _TEX_WRAPS[wrap]
+
+
+def texture_lookup(image, uv, wrap="repeat"):
+    """rt3_debug_texture_lookup, the texture lookup law in C on the host: image (H, W, 3 | 4), uv (2,) or (K, 2) -> float32 (3,) or (K, 3)."""
+    rgba = _image_rgba(image)
+    q = np.ascontiguousarray(np.asarray(uv, np.float32).reshape(-1, 2))
+    out = np.zeros((len(q), 3), np.float32)
+    fn = lib().rt3_debug_texture_lookup
+    for k in range(len(q)):
+        if fn(_p(rgba), rgba.shape[1], rgba.shape[0], _tex_wrap(wrap), C.c_void_p(q.ctypes.data + 8 * k), C.c_void_p(out.ctypes.data + 12 * k)) != 0:
+            raise Fatal("rt3_debug_texture_lookup refused its arguments (1 <= W, H <= 8192, W * H <= 2^26)")
+    return out[0] if np.ndim(uv) == 1 else out
+
+
+def texture_sphere_uv(n):
+    """rt3_debug_texture_sphere_uv, a sphere's (u, v) from its unit outward normal in C on the host: n (3,) or (K, 3) -> float32 (2,) or (K, 2)."""
+    q = np.ascontiguousarray(np.asarray(n, np.float32).reshape(-1, 3))
+    out = np.zeros((len(q), 2), np.float32)
+    fn = lib().rt3_debug_texture_sphere_uv
+    for k in range(len(q)):
+        fn(C.c_void_p(q.ctypes.data + 12 * k), C.c_void_p(out.ctypes.data + 8 * k))
+    return out[0] if np.ndim(n) == 1 else out
+
+
+def texture_face_uv(p1, p2, p3, uv6, p):
+    """rt3_debug_texture_face_uv, a face's (u, v) at the point p in C on the host: vertices (3,), uv6 (6,), p (3,) or (K, 3) -> float32 (2,) or (K, 2)."""
+    a, b, c = (np.ascontiguousarray(np.asarray(x, np.float32).reshape(3)) for x in (p1, p2, p3))
+    t = np.ascontiguousarray(np.asarray(uv6, np.float32).reshape(6))
+    q = np.ascontiguousarray(np.asarray(p, np.float32).reshape(-1, 3))
+    out = np.zeros((len(q), 2), np.float32)
+    fn = lib().rt3_debug_texture_face_uv
+    for k in range(len(q)):
+        fn(_p(a), _p(b), _p(c), _p(t), C.c_void_p(q.ctypes.data + 12 * k), C.c_void_p(out.ctypes.data + 8 * k))
+    return out[0] if np.ndim(p) == 1 else out
 
 
 def environment_sample(cube, base, depth):
@@ -1327,6 +1396,76 @@ class HipRenderer(Renderer):
 
     def render_lens_aov_device(self, lens, params, d_out_ptr, stream_ptr=None):
         self._check(lib().rt3_render_lens_aov_device(self._ctx, C.byref(lens), C.byref(params), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
+
+    # -- image textures (rt3_set_texture*, rt3_bind_*_textures*) ---------------------------------------
+    def set_texture(self, slot, image, wrap="repeat"):
+        """Fills texture slot `slot` (< TEX_MAX_TEXTURES) with a copy of `image`: a numpy array (H, W, 3 | 4), row 0 on top, or a contiguous
+        (H, W, 4) float32 torch tensor on the GPU, copied on torch.cuda.current_stream() (rt3_set_texture_device; its texels are not validated).
+        wrap: "repeat" or "clamp", for both axes.  None frees the slot."""
+        if image is None:
+            self._check(lib().rt3_set_texture(self._ctx, int(slot), None, 0, 0, 0))
+            return
+        if type(image).__module__.startswith("torch"):
+            import torch
+            if not image.is_cuda or image.dtype != torch.float32 or image.dim() != 3 or image.shape[2] != 4 or not image.is_contiguous():
+                raise Fatal("a device texture must be a contiguous (H, W, 4) float32 tensor on the GPU")
+            stream = torch.cuda.current_stream(image.device).cuda_stream
+            self._check(lib().rt3_set_texture_device(self._ctx, int(slot), C.c_void_p(image.data_ptr()), int(image.shape[1]), int(image.shape[0]),
+                                                     _tex_wrap(wrap), C.c_void_p(stream or 0)))
+            return
+        rgba = _image_rgba(image)
+        self._check(lib().rt3_set_texture(self._ctx, int(slot), _p(rgba), rgba.shape[1], rgba.shape[0], _tex_wrap(wrap)))
+
+    def clear_textures(self):
+        """Empties every slot and drops both bindings (rt3_clear_textures)."""
+        self._check(lib().rt3_clear_textures(self._ctx))
+
+    def texture_size(self, slot):
+        """(W, H, wrap) of the texture in `slot`, wrap as "repeat" or "clamp"; (0, 0, "repeat") for an empty slot (rt3_texture_size)."""
+        w, h, wrap = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(lib().rt3_texture_size(self._ctx, int(slot), C.byref(w), C.byref(h), C.byref(wrap)))
+        return int(w.value), int(h.value), "clamp" if wrap.value == TEX_CLAMP else "repeat"
+
+    def bind_sphere_textures(self, slots):
+        """One texture slot per sphere, in the order of set_spheres (TEX_NONE: untextured); None unbinds the spheres.  numpy / a sequence, or a
+        contiguous int32 / uint32 torch tensor on the GPU, read on torch.cuda.current_stream() (rt3_bind_sphere_textures_device).  The binding
+        survives update_spheres() and regroup(); set_spheres() drops it."""
+        if slots is None:
+            self._check(lib().rt3_bind_sphere_textures(self._ctx, None, 0))
+            return
+        if type(slots).__module__.startswith("torch"):
+            import torch
+            if not slots.is_cuda or slots.dtype not in _torch_word_dtypes() or slots.dim() != 1 or not slots.is_contiguous():
+                raise Fatal("device texture slots must be a contiguous 1-D int32 / uint32 tensor on the GPU")
+            stream = torch.cuda.current_stream(slots.device).cuda_stream
+            self._check(lib().rt3_bind_sphere_textures_device(self._ctx, C.c_void_p(slots.data_ptr()), int(slots.shape[0]), C.c_void_p(stream or 0)))
+            return
+        s = np.ascontiguousarray(np.asarray(slots, np.int64).astype(np.uint32).reshape(-1))
+        self._check(lib().rt3_bind_sphere_textures(self._ctx, _p(s), len(s)))
+
+    def bind_mesh_textures(self, slots, uv):
+        """One texture slot per committed face (TEX_NONE: untextured) and the faces' texture coordinates, uv (n_faces, 3, 2) or (n_faces, 6):
+        (u, v) of the face's first, second and third vertex; slots None unbinds the mesh.  numpy, or contiguous torch tensors on the GPU (slots
+        int32 / uint32, uv float32), read on torch.cuda.current_stream() (rt3_bind_mesh_textures_device; uv is not validated).  The binding survives
+        update_mesh() and regroup(); a new mesh drops it."""
+        if slots is None:
+            self._check(lib().rt3_bind_mesh_textures(self._ctx, None, None, 0))
+            return
+        if type(slots).__module__.startswith("torch"):
+            import torch
+            if (not slots.is_cuda or slots.dtype not in _torch_word_dtypes() or slots.dim() != 1 or not slots.is_contiguous() or
+                    not type(uv).__module__.startswith("torch") or not uv.is_cuda or uv.dtype != torch.float32 or not uv.is_contiguous() or
+                    uv.numel() != 6 * slots.shape[0]):
+                raise Fatal("device texture slots must be a contiguous 1-D int32 / uint32 tensor and uv a contiguous float32 tensor of 6 floats per face, both on the GPU")
+            stream = torch.cuda.current_stream(slots.device).cuda_stream
+            self._check(lib().rt3_bind_mesh_textures_device(self._ctx, C.c_void_p(slots.data_ptr()), C.c_void_p(uv.data_ptr()), int(slots.shape[0]),
+                                                            C.c_void_p(stream or 0)))
+            return
+        s = np.ascontiguousarray(np.asarray(slots, np.int64).astype(np.uint32).reshape(-1))
+        t = np.ascontiguousarray(np.asarray(uv, np.float32).reshape(-1))
+        if len(t) != 6 * len(s):
+            raise Fatal("uv holds 6 floats per face: (u, v) of each of its three vertices")
+        self._check(lib().rt3_bind_mesh_textures(self._ctx, _p(s), _p(t), len(s)))
 
     # -- the environment map (rt3_set_environment*; DESIGN.md 4.19) -----------------------------------------------------
     def set_environment(self, cube):

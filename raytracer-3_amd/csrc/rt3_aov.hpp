@@ -26,10 +26,11 @@ __global__ __launch_bounds__(kBlock) void k_camera_rays(const TraceArgs A, float
 // starts at sample 0 (the sums start from zero and sample 0's hit is recorded).  Material and sphere records are read in the caller's primitive
 // order — the order of a hit's index — through the fields scene_args() fills in; hit point and normal are computed as shade_lane() does.
 // env_n != 0: an environment map is set and a miss's albedo is its lookup, where it is the sky otherwise — a run-time test, this is no
-// trace kernel.
-__global__ __launch_bounds__(kBlock) void k_aov_accumulate(const TraceArgs A, const float4* __restrict__ rays, const uint4* __restrict__ hits,
+// trace kernel.  X.slots != null: the context is textured and a hit's albedo is rgb x the bound texel (tex_modulate), again at run time.
+// The lookup's registers would take the kernel from 8 waves per SIMD to 6 (78 VGPRs); bounded to 7 it keeps 72 and no scratch, bounded to 8 it spills.
+__global__ __launch_bounds__(kBlock, 7) void k_aov_accumulate(const TraceArgs A, const float4* __restrict__ rays, const uint4* __restrict__ hits,
                                                           float4* __restrict__ acc, uint32_t npix, uint32_t ns, int first,
-                                                          const float4* __restrict__ env, uint32_t env_n) {
+                                                          const float4* __restrict__ env, uint32_t env_n, const TexTable X) {
     const uint32_t pix = blockIdx.x * kBlock + threadIdx.x;
     if (pix >= npix) return;
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -51,17 +52,20 @@ __global__ __launch_bounds__(kBlock) void k_aov_accumulate(const TraceArgs A, co
             }
         } else if (kind == RT3_HIT_FACE || kind == RT3_HIT_SPHERE) {
             float4 m; uint32_t mk;
+            float px, py, pz;
             if (kind == RT3_HIT_FACE) {
                 m = A.tri_mat[idx]; mk = A.tri_kind[idx];
                 const float4 fn = A.tri[(size_t)idx * 4];
+                px = ro.x + t * rd.x; py = ro.y + t * rd.y; pz = ro.z + t * rd.z;
                 nx = fn.x; ny = fn.y; nz = fn.z;
             } else {
                 m = A.sph_mat[idx]; mk = A.sph_kind[idx];
                 const float4 c = A.sph[idx];
                 const float invr = A.sph_invr[idx];
-                const float px = fma_(t, rd.x, ro.x), py = fma_(t, rd.y, ro.y), pz = fma_(t, rd.z, ro.z);
+                px = fma_(t, rd.x, ro.x); py = fma_(t, rd.y, ro.y); pz = fma_(t, rd.z, ro.z);
                 nx = (px - c.x) * invr; ny = (py - c.y) * invr; nz = (pz - c.z) * invr;
             }
+            if (X.slots != nullptr) tex_modulate(X, kind == RT3_HIT_FACE, idx, A.tri, px, py, pz, nx, ny, nz, mk, m);     // textured: the modulated albedo
             if (!(dotf(rd.x, rd.y, rd.z, nx, ny, nz) < 0.0f)) { nx = -nx; ny = -ny; nz = -nz; }
             // a dielectric's device record holds (1/ior, r0, r0', ior), not a colour: its albedo is its attenuation, 1
             if (mk == RT3_MAT_DIELECTRIC) { ar = ag = ab = 1.0f; }

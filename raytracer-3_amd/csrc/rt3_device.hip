@@ -15,6 +15,7 @@
 //                           (the reduce pass reduce_v1.glsl never got) — the image is bitwise independent of scheduling and GPU count
 //   rt3_adaptive.hpp        adaptive sampling (rt3_render_path_adaptive*): the reduce pass over an active list, the convergence rule, the
 //                           ordered compaction of the pixels that stay active, the resolves by a pixel's own count
+//   rt3_texture_law.hpp     image textures: the lookup and the (u, v) of a sphere and of a face, host and device (the texture forms: 5.2u)
 //   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve (in place for 4.18)
 //   rt3_denoise.hpp         the launchers of the AOV-guided a-trous denoiser, its temporal form and the motion plane (kernels: rt3_denoise.hip)
 //   rt3_display.hpp         the launcher of the display transform (kernels: rt3_display.hip; the law: rt3_display_law.hpp)
@@ -50,6 +51,7 @@
 #include "rt3_env_sample.hpp"
 #include "rt3_light_sample.hpp"
 #include "rt3_lens_law.hpp"
+#include "rt3_texture_law.hpp"
 #include "rt3_kernel_common.hpp"
 #include "rt3_path.hpp"
 #include "rt3_valu_scan.hpp"
@@ -160,6 +162,14 @@ struct rt3_ctx {
     // scene changes: every upload, commit and update sets light_table = false; regroups and the environment calls do not.  d_env_wmax and d_env_temp
     // (the largest weight, the scan's scratch) are shared with the map's table: both builds are queued behind the event chain.
     DevBuf<uint32_t> d_light_q; DevBuf<unsigned long long> d_light_cdf; bool light_table = false;
+    // image textures (rt3_set_texture*, rt3_bind_*_textures*): the slots' own copies (w == 0: empty) and their descriptors on the device
+    // (d_tex_slots, RT3_TEX_MAX_TEXTURES of them, written behind the event chain); per class the binding in the caller's order and, on the host, the set
+    // of slots it names (one bit per slot) — all zero: the class has no binding, whatever d_*_tex still holds.  Uploads of a class clear its set
+    // (drop_*_binding); updates and regroups never touch any of this.
+    struct TexSlot { DevBuf<float4> texels; uint32_t w = 0, h = 0, wrap = 0; };
+    TexSlot tex[RT3_TEX_MAX_TEXTURES];
+    DevBuf<uint4> d_tex_slots; DevBuf<uint32_t> d_sph_tex, d_tri_tex, d_tex_check; DevBuf<float2> d_tri_uv;
+    uint32_t sph_tex_used[RT3_TEX_MAX_TEXTURES / 32] = {}, tri_tex_used[RT3_TEX_MAX_TEXTURES / 32] = {};
 
     // work buffers
     DevBuf<Rgb> d_rad;
@@ -547,6 +557,36 @@ int check_scene(rt3_ctx* ctx) {
     return 0;
 }
 
+// Image textures.  A class is bound while its binding names a slot; the context is textured while a class with primitives is bound.
+bool any_slot(const uint32_t (&used)[RT3_TEX_MAX_TEXTURES / 32]) { uint32_t a = 0; for (uint32_t w : used) a |= w; return a != 0; }
+bool textured(const rt3_ctx* ctx) { return (ctx->n_sph != 0 && any_slot(ctx->sph_tex_used)) || (ctx->n_faces != 0 && any_slot(ctx->tri_tex_used)); }
+void drop_sphere_binding(rt3_ctx* ctx) { std::memset(ctx->sph_tex_used, 0, sizeof ctx->sph_tex_used); }
+void drop_mesh_binding(rt3_ctx* ctx) { std::memset(ctx->tri_tex_used, 0, sizeof ctx->tri_tex_used); }
+// What a launch of a textured context hands over; all null otherwise.
+TexTable tex_table(const rt3_ctx* ctx) {
+    TexTable X{ nullptr, nullptr, nullptr, nullptr };
+    if (!textured(ctx)) return X;
+    X.slots = ctx->d_tex_slots;
+    if (ctx->n_sph != 0 && any_slot(ctx->sph_tex_used)) X.sph_tex = ctx->d_sph_tex;
+    if (ctx->n_faces != 0 && any_slot(ctx->tri_tex_used)) { X.tri_tex = ctx->d_tri_tex; X.tri_uv = ctx->d_tri_uv; }
+    return X;
+}
+// An entry point that reads the textures (rt3.h), called with its flags: nothing while the context is not textured; the flags refused while it is, then
+// every slot a binding names must hold a texture.
+int check_textures(rt3_ctx* ctx, uint32_t flags) {
+    if (!textured(ctx)) return 0;
+    if (flags & RT3_FLAG_REFERENCE_PRIMARY)
+        return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY is not available while textures are bound (its primary direction is not a unit vector)");
+    if (flags & (RT3_FLAG_ENV_SAMPLING | RT3_FLAG_LIGHT_SAMPLING))
+        return fail(ctx, RT3_E_ARG, "RT3_FLAG_ENV_SAMPLING and RT3_FLAG_LIGHT_SAMPLING are not available while textures are bound "
+                                    "(the sampling tables' weights do not see the texels)");
+    for (uint32_t s = 0; s < RT3_TEX_MAX_TEXTURES; s++) {
+        const bool named = (ctx->n_sph != 0 && ((ctx->sph_tex_used[s / 32] >> (s % 32)) & 1u)) || (ctx->n_faces != 0 && ((ctx->tri_tex_used[s / 32] >> (s % 32)) & 1u));
+        if (named && ctx->tex[s].w == 0) return fail(ctx, RT3_E_STATE, "a binding names texture slot " + std::to_string(s) + ", which is empty: call rt3_set_texture first");
+    }
+    return 0;
+}
+
 // The scene half of TraceArgs (what renders and queries share): records, filter centres, direct spheres, counters.
 TraceArgs scene_args(const rt3_ctx* ctx) {
     TraceArgs A;
@@ -624,6 +664,7 @@ struct TracePlan {
     const float4* env = nullptr; uint32_t env_n = 0;                // environment forms: the map the launch hands over behind TraceArgs (env_n != 0)
     const uint32_t* nee_q = nullptr; const unsigned long long* nee_cdf = nullptr; uint32_t nee_m = 0;      // sampling forms: the table behind the map (nee_m != 0)
     const uint32_t* lt_q = nullptr; const unsigned long long* lt_cdf = nullptr; const float4* lt_sph_cr = nullptr; uint32_t lt_n = 0;   // light sampling forms: the emitters' table (lt_n != 0)
+    TexTable tex{ nullptr, nullptr, nullptr, nullptr };             // texture forms: the slot table and the bindings behind the map (tex.slots != null)
 };
 // Strip lists (rt3_primary_lists.hpp): RT3_PRIMARY_LISTS=0 turns them off (the A/B reference: every primary ray takes the matrix filter),
 // RT3_PRIMARY_LIST_MAX=n sets the longest list a restock still traces itself.  The default is the best of a sweep on the bench frame at 1080p (short
@@ -700,6 +741,9 @@ void with_form(Form form, Fn fn) {
     case Form::RaysEnvNee: return form_case<Form::RaysEnvNee>(fn);
     case Form::RenderLight: return form_case<Form::RenderLight>(fn);
     case Form::RaysLight: return form_case<Form::RaysLight>(fn);
+    case Form::RenderTex: return form_case<Form::RenderTex>(fn);
+    case Form::ListTex: return form_case<Form::ListTex>(fn);
+    case Form::RaysTex: return form_case<Form::RaysTex>(fn);
     }
 }
 // Fills A's filter fields and T for the form `form` (rt3_kernel_common.hpp).  ref_brute: a RenderRef with a camera only the brute-force kernel serves.
@@ -714,10 +758,13 @@ void with_form(Form form, Fn fn) {
 int plan_trace(rt3_ctx* ctx, TraceArgs& A, Form form, bool ref_brute, TracePlan& T, bool nee = false, bool light = false) {
     const bool query = form == Form::Query, list = form == Form::List, rays = form == Form::Rays;
     const bool map = ctx->env_n != 0 && (form == Form::Render || list || rays);
-    const bool env = map || light;
+    const bool tex = textured(ctx) && (form == Form::Render || list || rays);
+    const bool env = map || light || tex;
     if (nee && (!map || list || !ctx->env_table || light)) return fail(ctx, RT3_E_DEVICE, "internal: no sampling form for this call");
     if (light && (!(form == Form::Render || rays) || !ctx->light_table)) return fail(ctx, RT3_E_DEVICE, "internal: no light sampling form for this call");
+    if (tex && (nee || light)) return fail(ctx, RT3_E_DEVICE, "internal: no texture form under a sampling flag");     // (check_textures refuses the flags)
     if (map) { T.env = ctx->d_env; T.env_n = ctx->env_n; form = form == Form::Render ? Form::RenderEnv : list ? Form::ListEnv : Form::RaysEnv; }
+    if (tex) { T.tex = tex_table(ctx); form = rays ? Form::RaysTex : list ? Form::ListTex : Form::RenderTex; }         // (with the map, if one is set)
     if (light) {
         T.lt_q = ctx->d_light_q; T.lt_cdf = ctx->d_light_cdf; T.lt_sph_cr = ctx->d_sph_cr; T.lt_n = ctx->n_faces + ctx->n_sph;
         form = rays ? Form::RaysLight : Form::RenderLight;
@@ -825,7 +872,12 @@ void launch_as(const TracePlan& T, const Args& E, uint32_t grid, hipStream_t str
 }
 void launch_trace(const TracePlan& T, const TraceArgs& A, uint32_t grid, hipStream_t stream) {
     const auto with_map = [&](EnvTraceArgs& E) { static_cast<TraceArgs&>(E) = A; E.env = T.env; E.env_n = T.env_n; E.env_pad = 0u; };
-    if (T.lt_n != 0) {                                              // a light sampling form: the map (or none) and the emitters' table behind the arguments
+    if (T.tex.slots != nullptr) {                                   // a texture form: the map (or none), then the slot table and the bindings
+        TexTraceArgs E;
+        with_map(E);
+        E.tex = T.tex;
+        launch_as<Form::RenderTex>(T, E, grid, stream);             // (the three texture forms share their signatures)
+    } else if (T.lt_n != 0) {                                       // a light sampling form: the map (or none) and the emitters' table behind the arguments
         LightTraceArgs E;
         with_map(E);
         E.lt_q = T.lt_q; E.lt_cdf = (const uint64_t*)T.lt_cdf; E.lt_sph_cr = T.lt_sph_cr; E.lt_n = T.lt_n; E.lt_pad = 0u;
@@ -1103,6 +1155,7 @@ int rt3_mesh_commit(rt3_ctx* ctx, const rt3_material* face_materials) {
     ctx->n_faces = 0;
     ctx->mesh_in_sync = false;
     ctx->light_table = false;                                       // the scene changes: the next call with RT3_FLAG_LIGHT_SAMPLING builds the emitters' table again
+    drop_mesh_binding(ctx);                                         // a full upload: the faces' texture binding goes with the old mesh
     ctx->update_error_pending = false;
     ctx->tri = FilterRows();
     for (DevBuf<float4>* b : { &ctx->d_tri, &ctx->d_tri_mat, &ctx->d_tri_bound, &ctx->d_tri_rec }) b->reset();
@@ -1209,6 +1262,7 @@ int rt3_set_spheres(rt3_ctx* ctx, const float* center_radius, const rt3_material
     }
     ctx->n_sph = 0;                                                 // (no spheres until everything below has been issued)
     ctx->light_table = false;
+    drop_sphere_binding(ctx);                                       // a full upload: the spheres' texture binding goes with the old spheres
     int rc;
     sphere_filter_centre(center_radius, n, ctx->sph_centre);
     ctx->n_direct = sphere_direct_list(center_radius, n, ctx->sph_centre, ctx->direct);
@@ -1544,6 +1598,7 @@ static int build_scratch(rt3_ctx* ctx, uint32_t n, bool sort_scratch, size_t* te
 }
 static void clear_spheres(rt3_ctx* ctx) {                           // what rt3_set_spheres(n = 0) leaves
     ctx->n_sph = 0; ctx->n_direct = 0; ctx->sph_left_out = false; ctx->light_table = false;
+    drop_sphere_binding(ctx);
     for (int a = 0; a < 3; a++) ctx->sph_centre[a] = 0.0f;
     ctx->sph = FilterRows();
     for (DevBuf<float4>* b : { &ctx->d_sph, &ctx->d_sph_mat, &ctx->d_sph_cr }) b->reset();
@@ -1600,6 +1655,7 @@ int rt3_set_spheres_device(rt3_ctx* ctx, const void* d_center_radius, const void
     // ---- phase 2
     ctx->n_sph = 0;                                                 // (no spheres until everything below has been issued)
     ctx->light_table = false;
+    drop_sphere_binding(ctx);
     std::memcpy(ctx->sph_centre, h + kSbCentre, sizeof ctx->sph_centre);
     ctx->n_direct = std::min(h[kSbCand], 4u);
     for (uint32_t k = 0; k < ctx->n_direct; k++) ctx->direct[k] = 0xFFFFFFFFu - h[kSbBest + 2 * k];     // (the key's low word)
@@ -1642,6 +1698,7 @@ int rt3_set_spheres_device(rt3_ctx* ctx, const void* d_center_radius, const void
 
 static void clear_mesh(rt3_ctx* ctx) {                              // what rt3_mesh_commit drops before it builds
     ctx->n_faces = 0; ctx->mesh_in_sync = false; ctx->update_error_pending = false; ctx->tri_bounded = 0; ctx->light_table = false;
+    drop_mesh_binding(ctx);
     ctx->tri = FilterRows();
     for (DevBuf<float4>* b : { &ctx->d_tri, &ctx->d_tri_mat, &ctx->d_tri_bound, &ctx->d_tri_rec }) b->reset();
     ctx->d_tri_kind.reset(); ctx->d_tri_frag.reset(); ctx->d_tri_frag_r.reset(); ctx->d_face_mats_in.reset();
@@ -1883,6 +1940,7 @@ int rt3_render_path_range_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_
     if (ref && ctx->n_sph != 0) return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY needs a triangle-only scene");
     if (ref && ctx->env_n != 0)
         return fail(ctx, RT3_E_ARG, "RT3_FLAG_REFERENCE_PRIMARY is not available while an environment map is set (its primary direction is not a unit vector)");
+    if ((rc = check_textures(ctx, p->flags))) return rc;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
 
@@ -1976,7 +2034,7 @@ int rt3_render_path_adaptive_device(rt3_ctx* ctx, const rt3_camera* cam, const r
     if (!(ap->dark >= 0.0f) || !(ap->dark < __builtin_inff())) return fail(ctx, RT3_E_ARG, "dark must be finite and >= 0");
     if ((uintptr_t)d_out % 16u != 0) return fail(ctx, RT3_E_ARG, "d_out_pixels must be 16-byte aligned");
     if ((uintptr_t)d_out_counts % 4u != 0) return fail(ctx, RT3_E_ARG, "d_out_counts must be 4-byte aligned");
-    if ((rc = check_scene(ctx))) return rc;
+    if ((rc = check_scene(ctx)) || (rc = check_textures(ctx, p->flags))) return rc;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
 
@@ -2282,7 +2340,7 @@ static int aov_pass(rt3_ctx* ctx, const rt3_params* p, const TraceArgs& A, void*
         if ((rc = make_rays(s0, ns))) return rc;
         if ((rc = issue_trace(ctx, Q, T, Q.total, stream))) return rc;
         hipLaunchKernelGGL(k_aov_accumulate, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, (const float4*)ctx->d_arays,
-                           (const uint4*)ctx->d_ahits, ctx->d_aacc, npix, ns, s0 == 0 ? 1 : 0, (const float4*)ctx->d_env, ctx->env_n);
+                           (const uint4*)ctx->d_ahits, ctx->d_aacc, npix, ns, s0 == 0 ? 1 : 0, (const float4*)ctx->d_env, ctx->env_n, tex_table(ctx));
         RT3_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_aov_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const float4*)ctx->d_aacc, npix, p->spp, (float4*)d_out);
@@ -2337,7 +2395,7 @@ int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
     if (!ctx) return RT3_E_ARG;
     int rc = aov_common_checks(ctx, cam, p, d_out, "d_out_aov");
     if (rc) return rc;
-    if ((rc = check_scene(ctx))) return rc;
+    if ((rc = check_scene(ctx)) || (rc = check_textures(ctx, 0u))) return rc;       // (the AOVs draw no shadow rays: the sampling flags change nothing here)
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
     const uint32_t npix = rt3_rows_owned(p) * p->width;
@@ -2734,7 +2792,7 @@ int rt3_radiance_device(rt3_ctx* ctx, const void* d_rays, const void* d_keys, ui
         return fail(ctx, RT3_E_ARG, "rays and out_rgba must be 16-byte and keys 4-byte aligned");
     if (ranges_overlap(d_out, (size_t)n * 16u, d_rays, (size_t)n * sizeof(rt3_ray)) || (d_keys && ranges_overlap(d_out, (size_t)n * 16u, d_keys, (size_t)n * 4u)))
         return fail(ctx, RT3_E_ARG, "out_rgba overlaps the rays or the keys");
-    if ((rc = check_scene(ctx)) || (rc = check_env_sampling(ctx, rp->flags))) return rc;
+    if ((rc = check_scene(ctx)) || (rc = check_env_sampling(ctx, rp->flags)) || (rc = check_textures(ctx, rp->flags))) return rc;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
     return radiance_pass(ctx, n, *rp, d_out, (const uint32_t*)d_keys, (const float4*)d_rays, stream, nullptr);
@@ -2827,7 +2885,7 @@ int rt3_render_lens_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params*
     if (!ctx) return RT3_E_ARG;
     int rc = render_lens_checks(ctx, lens, p, sample_begin, sample_count, d_out, "d_out_rgba", true);
     if (rc) return rc;
-    if ((rc = check_scene(ctx)) || (rc = check_env_sampling(ctx, p->flags))) return rc;
+    if ((rc = check_scene(ctx)) || (rc = check_env_sampling(ctx, p->flags)) || (rc = check_textures(ctx, p->flags))) return rc;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
     const uint32_t npix = rt3_rows_owned(p) * p->width;
@@ -2863,7 +2921,7 @@ int rt3_render_lens_aov_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_par
     if (!ctx) return RT3_E_ARG;
     int rc = lens_aov_checks(ctx, lens, p, d_out, "d_out_aov", true);
     if (rc) return rc;
-    if ((rc = check_scene(ctx))) return rc;
+    if ((rc = check_scene(ctx)) || (rc = check_textures(ctx, 0u))) return rc;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
     const uint32_t npix = rt3_rows_owned(p) * p->width;
@@ -2942,6 +3000,209 @@ int rt3_set_environment(rt3_ctx* ctx, const float* rgba, uint32_t n_face) {
     if ((rc = install_environment(ctx, rgba, hipMemcpyHostToDevice, n_face, ctx->stream))) return rc;      // (no staging buffer: a large map would stay in it)
     RT3_HIP(hipStreamSynchronize(ctx->stream));                     // the caller's array is free again
     return 0;
+}
+
+// ---- Image textures: the slots' copies, their descriptors on the device, the two bindings.  Read by shade_lane of the texture forms
+// (5.2u) and by k_aov_accumulate, both through tex_modulate.
+namespace {
+// One slot's descriptor, written on the stream (the value travels in the launch: no host memory has to outlive the call).
+__global__ void k_tex_set_slot(uint4* __restrict__ slots, uint32_t slot, uint4 d) {
+    if (threadIdx.x == 0 && blockIdx.x == 0 && slot < RT3_TEX_MAX_TEXTURES) slots[slot] = d;
+}
+// A binding's check: out[0] = the lowest index whose entry is neither RT3_TEX_NONE nor a slot (0xFFFFFFFF: none), out[1 + s / 32] bit s % 32: slot s is named.
+__global__ __launch_bounds__(kBlock) void k_tex_check_binding(const uint32_t* __restrict__ slots, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t s = slots[i];
+    if (s == RT3_TEX_NONE) return;
+    if (s >= RT3_TEX_MAX_TEXTURES) atomicMin(out, i);
+    else atomicOr(out + 1u + s / 32u, 1u << (s % 32u));
+}
+uint4 tex_descriptor(const float4* texels, uint32_t w, uint32_t h, uint32_t wrap) {
+    const uint64_t a = (uint64_t)(uintptr_t)texels;
+    return make_uint4((uint32_t)a, (uint32_t)(a >> 32), w | (h << 16), wrap);
+}
+// The descriptor table, allocated (all slots empty) by the first call that needs it.
+int ensure_tex_slots(rt3_ctx* ctx) {
+    if (ctx->d_tex_slots.size() != 0) return 0;
+    const int rc = ctx->d_tex_slots.alloc(ctx, RT3_TEX_MAX_TEXTURES);
+    if (rc) return rc;
+    RT3_HIP(hipMemset(ctx->d_tex_slots.get(), 0, RT3_TEX_MAX_TEXTURES * sizeof(uint4)));
+    return 0;
+}
+int texture_checks(rt3_ctx* ctx, uint32_t slot, const void* rgba, uint32_t w, uint32_t h, uint32_t wrap) {
+    if (slot >= RT3_TEX_MAX_TEXTURES) return fail(ctx, RT3_E_ARG, "slot must be < " + std::to_string(RT3_TEX_MAX_TEXTURES));
+    if (w == 0 || h == 0) return 0;                                 // frees the slot: nothing else is read
+    if (w > RT3_TEX_MAX_SIDE || h > RT3_TEX_MAX_SIDE) return fail(ctx, RT3_E_ARG, "texture sides must be <= " + std::to_string(RT3_TEX_MAX_SIDE));
+    if ((uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "a texture holds at most 2^26 texels");
+    if (wrap != RT3_TEX_REPEAT && wrap != RT3_TEX_CLAMP) return fail(ctx, RT3_E_ARG, "wrap must be RT3_TEX_REPEAT or RT3_TEX_CLAMP");
+    if (!rgba) return fail(ctx, RT3_E_ARG, "texture array is NULL");
+    return 0;
+}
+// Empties the slot: the descriptor first, behind the event chain; then, once nothing in flight can read it, the copy.
+int free_texture(rt3_ctx* ctx, uint32_t slot, void* stream_) {
+    rt3_ctx::TexSlot& S = ctx->tex[slot];
+    if (S.w == 0) return 0;
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    hipLaunchKernelGGL(k_tex_set_slot, dim3(1), dim3(1), 0, stream, ctx->d_tex_slots.get(), slot, make_uint4(0u, 0u, 0u, 0u));
+    RT3_HIP(hipGetLastError());
+    if ((rc = leave(ctx, stream))) return rc;
+    RT3_HIP(hipEventSynchronize(ctx->ev_acc));
+    S.texels.reset();
+    S.w = S.h = S.wrap = 0;
+    return 0;
+}
+// The copy of both forms (install_environment's pattern): into the copy the slot has when the size is the same, else into a fresh one — allocated first,
+// so that a failure leaves the slot as it was — and the old copy is freed once nothing can still read it.
+int install_texture(rt3_ctx* ctx, uint32_t slot, const void* src, hipMemcpyKind kind, uint32_t w, uint32_t h, uint32_t wrap, void* stream_) {
+    rt3_ctx::TexSlot& S = ctx->tex[slot];
+    const size_t texels = (size_t)w * h;
+    hipStream_t stream;
+    int rc;
+    if ((rc = ensure_tex_slots(ctx))) return rc;
+    const bool same = S.w != 0 && (size_t)S.w * S.h == texels;
+    DevBuf<float4> fresh;
+    if (!same && (rc = fresh.alloc(ctx, texels))) return rc;
+    float4* const dst = same ? S.texels.get() : fresh.get();
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    RT3_HIP(hipMemcpyAsync(dst, src, texels * sizeof(float4), kind, stream));
+    hipLaunchKernelGGL(k_tex_set_slot, dim3(1), dim3(1), 0, stream, ctx->d_tex_slots.get(), slot, tex_descriptor(dst, w, h, wrap));
+    RT3_HIP(hipGetLastError());
+    if ((rc = leave(ctx, stream))) return rc;
+    if (!same) {
+        if (S.w != 0) RT3_HIP(hipEventSynchronize(ctx->ev_acc));    // the old copy is freed: nothing may still read it (the new descriptor is behind the event)
+        S.texels = std::move(fresh);
+    }
+    S.w = w; S.h = h; S.wrap = wrap;
+    return 0;
+}
+// A binding of n entries from device arrays (the host forms stage theirs): the check of the caller's slots with the call's one wait, then — nothing of
+// the context has been touched so far — the copies into the context's own arrays behind the event chain.
+int install_binding(rt3_ctx* ctx, bool mesh, const void* d_slots, const void* d_uv6, uint32_t n, void* stream_) {
+    hipStream_t stream;
+    int rc;
+    if ((rc = ensure_tex_slots(ctx)) || (rc = ctx->d_tex_check.ensure(ctx, 1u + RT3_TEX_MAX_TEXTURES / 32u))) return rc;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    uint32_t h[1u + RT3_TEX_MAX_TEXTURES / 32u];
+    RT3_HIP(hipMemsetAsync(ctx->d_tex_check.get(), 0xFF, 4, stream));
+    RT3_HIP(hipMemsetAsync(ctx->d_tex_check.get() + 1, 0, sizeof h - 4, stream));
+    hipLaunchKernelGGL(k_tex_check_binding, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const uint32_t*)d_slots, n, ctx->d_tex_check.get());
+    RT3_HIP(hipGetLastError());
+    RT3_HIP(hipMemcpyAsync(h, ctx->d_tex_check.get(), sizeof h, hipMemcpyDeviceToHost, stream));
+    RT3_HIP(hipStreamSynchronize(stream));
+    if (h[0] != 0xFFFFFFFFu)
+        return fail(ctx, RT3_E_ARG, std::string(mesh ? "face " : "sphere ") + std::to_string(h[0]) + ": its texture slot is neither RT3_TEX_NONE nor < " +
+                                    std::to_string(RT3_TEX_MAX_TEXTURES));
+    DevBuf<uint32_t>& bind = mesh ? ctx->d_tri_tex : ctx->d_sph_tex;
+    if ((rc = bind.ensure(ctx, n)) || (mesh && (rc = ctx->d_tri_uv.ensure(ctx, (size_t)n * 3u)))) return rc;      // (grows behind hipFree's own wait)
+    RT3_HIP(hipMemcpyAsync(bind.get(), d_slots, (size_t)n * 4u, hipMemcpyDeviceToDevice, stream));
+    if (mesh) RT3_HIP(hipMemcpyAsync(ctx->d_tri_uv.get(), d_uv6, (size_t)n * 6u * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    if ((rc = leave(ctx, stream))) return rc;
+    std::memcpy(mesh ? ctx->tri_tex_used : ctx->sph_tex_used, h + 1, sizeof ctx->sph_tex_used);
+    return 0;
+}
+// What both forms of a binding check first.  unbind: the call is the class's unbinding (NULL slots or a count of 0).
+int binding_checks(rt3_ctx* ctx, bool mesh, const void* slots, const void* uv6, uint32_t n, bool* unbind) {
+    *unbind = slots == nullptr || n == 0;
+    if (*unbind) return 0;
+    const uint32_t have = mesh ? ctx->n_faces : ctx->n_sph;
+    if (have == 0) return fail(ctx, RT3_E_STATE, mesh ? "no committed mesh to bind textures to: call rt3_set_mesh / rt3_mesh_commit first"
+                                                      : "no spheres to bind textures to: call rt3_set_spheres first");
+    if (n != have) return fail(ctx, RT3_E_ARG, mesh ? "n_faces must equal the context's face count" : "n must equal the context's sphere count");
+    if (mesh && !uv6) return fail(ctx, RT3_E_ARG, "uv6 is NULL");
+    return 0;
+}
+}  // namespace
+
+int rt3_set_texture_device(rt3_ctx* ctx, uint32_t slot, const void* d_rgba, uint32_t w, uint32_t h, uint32_t wrap, void* stream) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = texture_checks(ctx, slot, d_rgba, w, h, wrap);
+    if (rc) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    if (w == 0 || h == 0) return free_texture(ctx, slot, stream);
+    if ((uintptr_t)d_rgba % 16u != 0) return fail(ctx, RT3_E_ARG, "d_rgba must be 16-byte aligned");
+    return install_texture(ctx, slot, d_rgba, hipMemcpyDeviceToDevice, w, h, wrap, stream);
+}
+int rt3_set_texture(rt3_ctx* ctx, uint32_t slot, const float* rgba, uint32_t w, uint32_t h, uint32_t wrap) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = texture_checks(ctx, slot, rgba, w, h, wrap);
+    if (rc) return rc;
+    RT3_HIP(hipSetDevice(ctx->device));
+    if (w == 0 || h == 0) return free_texture(ctx, slot, ctx->stream);
+    if ((uintptr_t)rgba % 4u != 0) return fail(ctx, RT3_E_ARG, "rgba must be 4-byte aligned");
+    const size_t texels = (size_t)w * h;
+    for (size_t i = 0; i < texels; i++)
+        if (!std::isfinite(rgba[4 * i]) || !std::isfinite(rgba[4 * i + 1]) || !std::isfinite(rgba[4 * i + 2]))
+            return fail(ctx, RT3_E_ARG, "texel " + std::to_string(i) + " is not finite");
+    if ((rc = install_texture(ctx, slot, rgba, hipMemcpyHostToDevice, w, h, wrap, ctx->stream))) return rc;        // (no staging buffer: a large image would stay in it)
+    RT3_HIP(hipStreamSynchronize(ctx->stream));                     // the caller's array is free again
+    return 0;
+}
+int rt3_clear_textures(rt3_ctx* ctx) {
+    if (!ctx) return RT3_E_ARG;
+    RT3_HIP(hipSetDevice(ctx->device));
+    drop_sphere_binding(ctx);
+    drop_mesh_binding(ctx);
+    for (uint32_t s = 0; s < RT3_TEX_MAX_TEXTURES; s++) {
+        const int rc = free_texture(ctx, s, ctx->stream);
+        if (rc) return rc;
+    }
+    return 0;
+}
+int rt3_texture_size(rt3_ctx* ctx, uint32_t slot, uint32_t* w, uint32_t* h, uint32_t* wrap) {
+    if (!ctx) return RT3_E_ARG;
+    if (slot >= RT3_TEX_MAX_TEXTURES) return fail(ctx, RT3_E_ARG, "slot must be < " + std::to_string(RT3_TEX_MAX_TEXTURES));
+    if (w) *w = ctx->tex[slot].w;
+    if (h) *h = ctx->tex[slot].h;
+    if (wrap) *wrap = ctx->tex[slot].wrap;
+    return 0;
+}
+int rt3_bind_sphere_textures_device(rt3_ctx* ctx, const void* d_slots, uint32_t n, void* stream) {
+    if (!ctx) return RT3_E_ARG;
+    bool unbind;
+    int rc = binding_checks(ctx, false, d_slots, nullptr, n, &unbind);
+    if (rc) return rc;
+    if (unbind) { drop_sphere_binding(ctx); return 0; }
+    if ((uintptr_t)d_slots % 4u != 0) return fail(ctx, RT3_E_ARG, "d_slots must be 4-byte aligned");
+    return install_binding(ctx, false, d_slots, nullptr, n, stream);
+}
+int rt3_bind_sphere_textures(rt3_ctx* ctx, const uint32_t* slots, uint32_t n) {
+    if (!ctx) return RT3_E_ARG;
+    bool unbind;
+    int rc = binding_checks(ctx, false, slots, nullptr, n, &unbind);
+    if (rc) return rc;
+    if (unbind) { drop_sphere_binding(ctx); return 0; }
+    if ((uintptr_t)slots % 4u != 0) return fail(ctx, RT3_E_ARG, "slots must be 4-byte aligned");
+    for (uint32_t i = 0; i < n; i++)
+        if (slots[i] != RT3_TEX_NONE && slots[i] >= RT3_TEX_MAX_TEXTURES)
+            return fail(ctx, RT3_E_ARG, "sphere " + std::to_string(i) + ": its texture slot is neither RT3_TEX_NONE nor < " + std::to_string(RT3_TEX_MAX_TEXTURES));
+    return staged(ctx, { stage_in(slots, (size_t)n * 4u) }, [&](void* const* d) { return install_binding(ctx, false, d[0], nullptr, n, ctx->stream); });
+}
+int rt3_bind_mesh_textures_device(rt3_ctx* ctx, const void* d_slots, const void* d_uv6, uint32_t n_faces, void* stream) {
+    if (!ctx) return RT3_E_ARG;
+    bool unbind;
+    int rc = binding_checks(ctx, true, d_slots, d_uv6, n_faces, &unbind);
+    if (rc) return rc;
+    if (unbind) { drop_mesh_binding(ctx); return 0; }
+    if (((uintptr_t)d_slots | (uintptr_t)d_uv6) % 4u != 0) return fail(ctx, RT3_E_ARG, "d_slots and d_uv6 must be 4-byte aligned");
+    return install_binding(ctx, true, d_slots, d_uv6, n_faces, stream);
+}
+int rt3_bind_mesh_textures(rt3_ctx* ctx, const uint32_t* slots, const float* uv6, uint32_t n_faces) {
+    if (!ctx) return RT3_E_ARG;
+    bool unbind;
+    int rc = binding_checks(ctx, true, slots, uv6, n_faces, &unbind);
+    if (rc) return rc;
+    if (unbind) { drop_mesh_binding(ctx); return 0; }
+    if (((uintptr_t)slots | (uintptr_t)uv6) % 4u != 0) return fail(ctx, RT3_E_ARG, "slots and uv6 must be 4-byte aligned");
+    for (uint32_t i = 0; i < n_faces; i++)
+        if (slots[i] != RT3_TEX_NONE && slots[i] >= RT3_TEX_MAX_TEXTURES)
+            return fail(ctx, RT3_E_ARG, "face " + std::to_string(i) + ": its texture slot is neither RT3_TEX_NONE nor < " + std::to_string(RT3_TEX_MAX_TEXTURES));
+    for (size_t i = 0; i < (size_t)n_faces * 6u; i++)
+        if (!std::isfinite(uv6[i])) return fail(ctx, RT3_E_ARG, "face " + std::to_string(i / 6u) + ": a uv coordinate is not finite");
+    return staged(ctx, { stage_in(slots, (size_t)n_faces * 4u), stage_in(uv6, (size_t)n_faces * 6u * sizeof(float)) },
+                  [&](void* const* d) { return install_binding(ctx, true, d[0], d[1], n_faces, ctx->stream); });
 }
 
 // Tests only: a sampling table of n entries downloaded, built first (ensure) if no call that carries its flag has built it yet.

@@ -11,6 +11,7 @@
 #include "rt3_display_law.hpp"
 #include "rt3_display_sequence_law.hpp"
 #include "rt3_lens_law.hpp"
+#include "rt3_texture_law.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -671,6 +672,25 @@ extern "C" int rt3_debug_lens_ray(const rt3_lens* lens, const rt3_params* p, uin
 }
 // The inverse law (rt3.h "Lens sequences") on the host: the statements of rt3_lens_law.hpp k_temporal_reproject evaluates.
 extern "C" float rt3_debug_turns(float c, float s) { return rt3lens::turns(c, s); }
+
+// The image texture law in C (rt3.h "Image textures"; rt3_texture_law.hpp is the one statement, the device's too).
+extern "C" int rt3_debug_texture_lookup(const float* rgba, uint32_t w, uint32_t h, uint32_t wrap, const float uv[2], float out_rgb[3]) {
+    if (!rgba || !uv || !out_rgb || w == 0 || h == 0 || w > RT3_TEX_MAX_SIDE || h > RT3_TEX_MAX_SIDE || (uint64_t)w * h > (1ull << 26)) return RT3_E_ARG;
+    if (wrap != RT3_TEX_REPEAT && wrap != RT3_TEX_CLAMP) return RT3_E_ARG;
+    struct Texel { float x, y, z, w; };
+    rt3tex::lookup(reinterpret_cast<const Texel*>(rgba), w, h, wrap, uv[0], uv[1], out_rgb[0], out_rgb[1], out_rgb[2]);
+    return 0;
+}
+extern "C" int rt3_debug_texture_sphere_uv(const float n[3], float uv[2]) {
+    if (!n || !uv) return RT3_E_ARG;
+    rt3tex::sphere_uv(n[0], n[1], n[2], uv[0], uv[1]);
+    return 0;
+}
+extern "C" int rt3_debug_texture_face_uv(const float p1[3], const float p2[3], const float p3[3], const float uv6[6], const float p[3], float uv[2]) {
+    if (!p1 || !p2 || !p3 || !uv6 || !p || !uv) return RT3_E_ARG;
+    rt3tex::face_uv(p1, p2, p3, uv6, p, uv[0], uv[1]);
+    return 0;
+}
 extern "C" int rt3_debug_optic_pixel(const rt3_lens* prev_lens, uint32_t width, uint32_t height, const float r[3], uint32_t is_hit,
                                      float out_xy_depth[3], uint32_t* face, uint32_t* valid) {
     if (!prev_lens || !r || !out_xy_depth || !face || !valid || width < 2 || height < 2) return RT3_E_ARG;

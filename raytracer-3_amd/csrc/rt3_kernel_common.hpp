@@ -163,15 +163,22 @@ struct Rgb { float r, g, b; };   // one radiance record of the sample storage (t
 //              primitive from the emitters' sampling table and casts one shadow ray towards it through the lane's own cast slot; the lane carries a
 //              LightPath, the launch argument is a LightTraceArgs (both below).  With or without a map: env_n == 0 there means none, and the miss then
 //              evaluates the sky — a branch at run time, not two more forms.  No list form: the adaptive render refuses the flag.
-enum class Form : uint32_t { Render, RenderRef, Query, List, Rays, RenderEnv, ListEnv, RaysEnv, RenderEnvNee, RaysEnvNee, RenderLight, RaysLight };
+//   RenderTex, ListTex, RaysTex   Render, List and Rays while the context is textured (rt3_bind_*_textures*): the same kernel with ONE
+//              difference, shade_lane multiplies the material's rgb by the bound texture's texel where it has just fetched the material (tex_modulate,
+//              below).  The launch argument is a TexTraceArgs (below).  With or without a map: env_n == 0 there means none, and the miss then evaluates
+//              the sky — a branch at run time, as in the light forms.  (New forms go to the END of the enum: a kernel's name carries its form's number.)
+enum class Form : uint32_t { Render, RenderRef, Query, List, Rays, RenderEnv, ListEnv, RaysEnv, RenderEnvNee, RaysEnvNee, RenderLight, RaysLight,
+                             RenderTex, ListTex, RaysTex };
 constexpr bool is_nee(Form f) { return f == Form::RenderEnvNee || f == Form::RaysEnvNee; }
 constexpr bool is_light(Form f) { return f == Form::RenderLight || f == Form::RaysLight; }
+constexpr bool is_tex(Form f) { return f == Form::RenderTex || f == Form::ListTex || f == Form::RaysTex; }
 constexpr bool has_shadow(Form f) { return is_nee(f) || is_light(f); }                 // a lane's cast may be a shadow ray: no stock entry can hold one
-constexpr bool is_env(Form f) { return f == Form::RenderEnv || f == Form::ListEnv || f == Form::RaysEnv || is_nee(f) || is_light(f); }
+constexpr bool is_env(Form f) { return f == Form::RenderEnv || f == Form::ListEnv || f == Form::RaysEnv || is_nee(f) || is_light(f) || is_tex(f); }
 // The twin of an environment form, and every other form itself: what a kernel body and the refill helpers branch on.
 constexpr Form base_form(Form f) {
-    return f == Form::RenderEnv || f == Form::RenderEnvNee || f == Form::RenderLight ? Form::Render : f == Form::ListEnv ? Form::List
-         : f == Form::RaysEnv || f == Form::RaysEnvNee || f == Form::RaysLight ? Form::Rays : f;
+    return f == Form::RenderEnv || f == Form::RenderEnvNee || f == Form::RenderLight || f == Form::RenderTex ? Form::Render
+         : f == Form::ListEnv || f == Form::ListTex ? Form::List
+         : f == Form::RaysEnv || f == Form::RaysEnvNee || f == Form::RaysLight || f == Form::RaysTex ? Form::Rays : f;
 }
 // Batched ray queries (the QUERY forms of the trace kernels; rt3_intersect* / rt3_occluded*): item k of a launch is ray k
 // of the caller's rt3_ray[] (q_rays: two float4 per ray, origin, t_max | direction, pad); its result goes to q_out[k], an rt3_hit (16 bytes), or with
@@ -242,11 +249,45 @@ struct NeeTraceArgs : EnvTraceArgs { const uint32_t* nee_q; const uint64_t* nee_
 // first and then spheres in the caller's order (lt_n = n_tri + n_sph); the total is lt_cdf[lt_n - 1], read from device memory.  lt_sph_cr: the spheres'
 // (C, r) as the caller gave them — the law samples with r, the trace kernels keep r^2 and 1 / r.
 struct LightTraceArgs : EnvTraceArgs { const uint32_t* lt_q; const uint64_t* lt_cdf; const float4* lt_sph_cr; uint32_t lt_n; uint32_t lt_pad; };
-template <Form F> using trace_args = std::conditional_t<is_light(F), LightTraceArgs,
-                                     std::conditional_t<is_nee(F), NeeTraceArgs, std::conditional_t<is_env(F), EnvTraceArgs, TraceArgs>>>;
+// Image textures (rt3.h "Image textures").  TexTable: what a lookup at a hit needs — the slot table (one 16-byte descriptor per slot:
+// the texel pointer, W | H << 16, the wrap mode; a null pointer: an empty slot), the two binding arrays in the caller's primitive order (RT3_TEX_NONE:
+// untextured; null: the class has no binding) and the faces' six uv floats.  The launch argument of the texture forms: EnvTraceArgs (env_n == 0: no map
+// is set) with the table behind it, a struct of its own once more; k_aov_accumulate takes the table as an argument of its own.
+struct TexTable { const uint4* slots; const uint32_t* sph_tex; const uint32_t* tri_tex; const float2* tri_uv; };
+struct TexTraceArgs : EnvTraceArgs { TexTable tex; };
+template <Form F> using trace_args = std::conditional_t<is_tex(F), TexTraceArgs, std::conditional_t<is_light(F), LightTraceArgs,
+                                     std::conditional_t<is_nee(F), NeeTraceArgs, std::conditional_t<is_env(F), EnvTraceArgs, TraceArgs>>>>;
 __device__ __forceinline__ const EnvTraceArgs& env_of(const TraceArgs& A) { return static_cast<const EnvTraceArgs&>(A); }   // only where A IS one: an environment form
 __device__ __forceinline__ const NeeTraceArgs& nee_of(const TraceArgs& A) { return static_cast<const NeeTraceArgs&>(A); }   // only where A IS one: a sampling form
 __device__ __forceinline__ const LightTraceArgs& light_of(const TraceArgs& A) { return static_cast<const LightTraceArgs&>(A); }   // only where A IS one: a light sampling form
+__device__ __forceinline__ const TexTraceArgs& tex_of(const TraceArgs& A) { return static_cast<const TexTraceArgs&>(A); }         // only where A IS one: a texture form
+// The shading rule of a textured hit (rt3.h): m.xyz *= texel for a flat, Lambert or metal primitive that is bound to a slot.  face: the hit is face idx
+// (tri: the faces' records, four float4 each) at the point p = o + t d, else sphere idx with the unit outward normal n, before the flip.  The slot differs
+// from lane to lane: its descriptor comes with one 16-byte vector load, then the four taps as four independent 16-byte loads behind one wait.  A slot the
+// host would have refused (out of range, empty) leaves m alone: no address is formed from it.
+__device__ __forceinline__ void tex_modulate(const TexTable& X, bool face, uint32_t idx, const float4* __restrict__ tri, float px, float py, float pz,
+                                             float nx, float ny, float nz, uint32_t mk, float4& m) {
+    const uint32_t* bind = face ? X.tri_tex : X.sph_tex;
+    if (mk == RT3_MAT_DIELECTRIC || bind == nullptr) return;
+    const uint32_t slot = bind[idx];
+    if (slot >= RT3_TEX_MAX_TEXTURES) return;                       // (RT3_TEX_NONE among them)
+    const uint4 d = X.slots[slot];
+    const float4* texels = reinterpret_cast<const float4*>(((uint64_t)d.y << 32) | d.x);
+    if (texels == nullptr) return;
+    float u, v;
+    if (face) {
+        const float4 a = tri[(size_t)idx * 4 + 1], b = tri[(size_t)idx * 4 + 2], c = tri[(size_t)idx * 4 + 3];
+        const float2 t1 = X.tri_uv[(size_t)idx * 3], t2 = X.tri_uv[(size_t)idx * 3 + 1], t3 = X.tri_uv[(size_t)idx * 3 + 2];
+        const float p1[3] = { a.x, a.y, a.z }, p2[3] = { b.x, b.y, b.z }, p3[3] = { c.x, c.y, c.z }, p[3] = { px, py, pz };
+        const float uv6[6] = { t1.x, t1.y, t2.x, t2.y, t3.x, t3.y };
+        rt3tex::face_uv(p1, p2, p3, uv6, p, u, v);
+    } else {
+        rt3tex::sphere_uv(nx, ny, nz, u, v);
+    }
+    float r, g, b;
+    rt3tex::lookup(texels, d.z & 0xFFFFu, d.z >> 16, d.w, u, v, r, g, b);
+    m.x = m.x * r; m.y = m.y * g; m.z = m.z * b;
+}
 
 struct Path {
     float ox, oy, oz, dx, dy, dz;

@@ -170,6 +170,8 @@ __device__ __forceinline__ void stock_pop(const TracedStock& Q, uint32_t src, bo
 // depth alone, so a lane below the cap reads its row instead of computing three hashes; at or beyond the cap it computes them as rnd() does.
 // Environment forms (is_env(F); A is then an EnvTraceArgs): a miss adds throughput x env_lookup(direction) where the twin adds throughput x sky — the one
 // difference between an environment form and its twin.
+// Texture forms (is_tex(F); A is then a TexTraceArgs): where the material has just been fetched, its rgb is multiplied by the texel of the
+// texture the hit primitive is bound to (tex_modulate) — the one difference between a texture form and its twin; a miss reads the map if one is set.
 // Sampling forms (is_nee(F), RT3_FLAG_ENV_SAMPLING; A is a NeeTraceArgs, P a NeePath): a Lambert scatter also draws a direction w from the
 // map's table (rt3env::sample, counters 3..6 of the scatter's block).  With c = n.w > 0 the shadow ray (p, w) takes the lane's next cast — the
 // continuation waits in the NeePath — and THAT cast's shade_lane is the first block below: a miss adds T' (c / (pi pdf)) env(w), a hit adds nothing, and
@@ -227,7 +229,11 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
                 }
             } else if (!(A.flags & RT3_FLAG_BLACK_BACKGROUND)) {
                 float r, g, b;
-                if constexpr (is_env(F)) env_lookup(env_of(A).env, env_of(A).env_n, dx, dy, dz, r, g, b);
+                if constexpr (is_tex(F)) {                          // with or without a map, as the light forms
+                    if (env_of(A).env_n != 0u) env_lookup(env_of(A).env, env_of(A).env_n, dx, dy, dz, r, g, b);
+                    else sky(dx, dy, dz, r, g, b);
+                }
+                else if constexpr (is_env(F)) env_lookup(env_of(A).env, env_of(A).env_n, dx, dy, dz, r, g, b);
                 else sky(dx, dy, dz, r, g, b);
                 P.lr = fma_(P.tr, r, P.lr); P.lg = fma_(P.tg, g, P.lg); P.lb = fma_(P.tb, b, P.lb);
             }
@@ -247,6 +253,8 @@ __device__ __forceinline__ void shade_lane(const TraceArgs& A, Path& P, bool& al
                 px = fma_(tbest, dx, ox); py = fma_(tbest, dy, oy); pz = fma_(tbest, dz, oz);
                 nx = (px - s.x) * invr; ny = (py - s.y) * invr; nz = (pz - s.z) * invr;
             }
+            if constexpr (is_tex(F))                                // the one difference from the twin: rgb x the bound texture's texel
+                tex_modulate(tex_of(A).tex, HAS_TRI && (!HAS_SPH || kind == 1), ibest, A.tri, px, py, pz, nx, ny, nz, mk, m);
             if (mk == RT3_MAT_FLAT) {
                 bool adds = true;
                 if constexpr (is_light(F)) {                            // behind a Lambert scatter the shadow ray has accounted for every light of the table

@@ -270,6 +270,23 @@ void HipRenderer::clear_environment() {
         if (rt3_clear_environment(c) != 0) throw Fatal(rt3_last_error(c));
 }
 
+void HipRenderer::set_texture(uint32_t slot, const std::vector<float>& rgba, uint32_t w, uint32_t h, uint32_t wrap) {
+    if (rgba.size() != (size_t)4 * w * h) throw Fatal("set_texture: rgba must hold w x h texels of 4 floats");
+    for (rt3_ctx* c : ctx)
+        if (rt3_set_texture(c, slot, rgba.data(), w, h, wrap) != 0) throw Fatal(rt3_last_error(c));
+}
+
+void HipRenderer::bind_sphere_textures(const std::vector<uint32_t>& slots) {
+    for (rt3_ctx* c : ctx)
+        if (rt3_bind_sphere_textures(c, slots.empty() ? nullptr : slots.data(), (uint32_t)slots.size()) != 0) throw Fatal(rt3_last_error(c));
+}
+
+void HipRenderer::bind_mesh_textures(const std::vector<uint32_t>& slots, const std::vector<float>& uv6) {
+    if (uv6.size() != slots.size() * 6) throw Fatal("bind_mesh_textures: uv6 must hold 6 floats per face");
+    for (rt3_ctx* c : ctx)
+        if (rt3_bind_mesh_textures(c, slots.empty() ? nullptr : slots.data(), uv6.data(), (uint32_t)slots.size()) != 0) throw Fatal(rt3_last_error(c));
+}
+
 void HipRenderer::update_mesh(const std::vector<float>& vertices, const std::vector<rt3_gface>& faces) {
     if (!faces.empty() && faces.size() != n_faces) throw Fatal("update_mesh: faces must hold the mesh's face count, or be empty");
     for (rt3_ctx* c : ctx)

@@ -13,6 +13,7 @@
 // --lens-extent (the frame of another lens model at the scene's camera position: equirectangular, fisheye, orthographic, cube),
 // --lens-frames (a sequence of such frames, denoised temporally through the lens), --display-frames, --adapt and --bloom (an image
 // per frame of a sequence through the display transform, an exposure that follows the sequence, a bloom pyramid).
+#include <algorithm>
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -56,7 +57,11 @@ struct Options {
     std::string env_path;                                          // Mode X: the environment map, a colour PFM of N x 6N (the six faces stacked)
     bool env_sampling = false;                                     // with --env: RT3_FLAG_ENV_SAMPLING
     bool light_sampling = false;                                   // Mode X: RT3_FLAG_LIGHT_SAMPLING
-    bool display = false;                                          // Mode X: the image written is rt3_display of the linear (or the denoised) frame
+    struct Texture { std::string path; uint32_t wrap; };           // Mode X, sphere scenes: --texture FILE.pfm[,repeat|clamp], use k fills slot k
+    std::vector<Texture> textures;
+    struct SphereBind { bool all; uint32_t index, slot; };         // --bind-sphere INDEX=SLOT | all=SLOT, applied in the order given
+    std::vector<SphereBind> sphere_binds;
+    bool display = false;                                         // Mode X: the image written is rt3_display of the linear (or the denoised) frame
     uint32_t lens = 0;                                             // Mode X: RT3_LENS_* of the frame to render instead of the camera's (0: none)
     float lens_fov = 180.0f;                                       // fisheye: the whole field of view across the shorter image side, in degrees
     float lens_extent[2] = { 2.0f, 2.0f };                         // ortho: the window's width and height
@@ -109,6 +114,10 @@ void print_usage(const char* exe) {
               << "\t\t\tsun converges). The render and --radiance; not with --adaptive, nor with a scene whose background is black.\n"
               << "\t   --light-sampling\tMode X: every diffuse bounce also samples the emissive primitives by brightness times area and casts one shadow\n"
               << "\t\t\tray (a small lamp converges). The render and --radiance; not with --adaptive, nor with --env-sampling.\n"
+              << "\t   --texture\tMode X, the sphere scenes (three, weekend, stress100k): FILE.pfm[,repeat|clamp]: an image texture from a colour PFM, up to\n"
+              << "\t\t\t8192 on a side (default: repeat). Each use takes the next slot, from 0. Not with --env-sampling or --light-sampling.\n"
+              << "\t   --bind-sphere\tWith --texture: INDEX=SLOT or all=SLOT: the sphere of that index (or every sphere) takes the texture of that slot as\n"
+              << "\t\t\tits albedo map (glass ignores it). May be given several times; later uses override earlier ones.\n"
               << "\t   --display\tMode X: CURVE[,TRANSFER[,EXPOSURE]]: the image written is the linear frame (with a single-frame --denoise, the\n"
               << "\t\t\tdenoised one) through a display transform: CURVE clamp | reinhard | filmic, TRANSFER linear | gamma2 | srgb (default: srgb),\n"
               << "\t\t\tEXPOSURE a positive gain, or auto: from the frame's trimmed log-average luminance (default: 1).\n"
@@ -187,7 +196,8 @@ int parse_cli(Options& opt, int argc, const char** argv) {
                            key == "--aov" || key == "--hdr" || key == "--denoise" || key == "--frames" || key == "--orbit" ||
                            key == "--slide" || key == "--adaptive" || key == "--counts" || key == "--regroup" ||
                            key == "--rays" || key == "--radiance" || key == "--env" || key == "--display" || key == "--lens" || key == "--lens-fov" ||
-                           key == "--lens-extent" || key == "--lens-frames" || key == "--display-frames" || key == "--adapt" || key == "--bloom";
+                           key == "--lens-extent" || key == "--lens-frames" || key == "--display-frames" || key == "--adapt" || key == "--bloom" ||
+                           key == "--texture" || key == "--bind-sphere";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -254,6 +264,35 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         else if (key == "--rays") opt.rays_path = value;
         else if (key == "--radiance") opt.radiance_path = value;
         else if (key == "--env") opt.env_path = value;
+        else if (key == "--texture") {                               // FILE.pfm[,repeat|clamp]
+            Options::Texture t{ value, RT3_TEX_REPEAT };
+            const size_t comma = value.rfind(',');
+            if (comma != std::string::npos) {
+                const std::string mode = value.substr(comma + 1);
+                if (mode == "repeat" || mode == "clamp") { t.path = value.substr(0, comma); t.wrap = mode == "clamp" ? RT3_TEX_CLAMP : RT3_TEX_REPEAT; }
+                else { std::cerr << "Invalid texture wrap '" << mode << "'" << std::endl; return -1; }
+            }
+            if (t.path.empty() || opt.textures.size() == RT3_TEX_MAX_TEXTURES) { std::cerr << "Invalid texture '" << value << "'" << std::endl; return -1; }
+            opt.textures.push_back(t);
+        }
+        else if (key == "--bind-sphere") {                           // INDEX=SLOT | all=SLOT
+            const size_t eq = value.find('=');
+            const std::string who = value.substr(0, eq), slot = eq == std::string::npos ? "" : value.substr(eq + 1);
+            Options::SphereBind b{ who == "all", 0u, 0u };
+            char* end = nullptr;
+            bool ok = !slot.empty() && std::isdigit((unsigned char)slot[0]);
+            const unsigned long long s = ok ? std::strtoull(slot.c_str(), &end, 10) : 0ull;
+            ok = ok && *end == '\0' && s < RT3_TEX_MAX_TEXTURES;
+            if (ok && !b.all) {
+                ok = !who.empty() && std::isdigit((unsigned char)who[0]);
+                const unsigned long long i = ok ? std::strtoull(who.c_str(), &end, 10) : 0ull;
+                ok = ok && *end == '\0' && i <= std::numeric_limits<uint32_t>::max();
+                b.index = (uint32_t)i;
+            }
+            if (!ok) { std::cerr << "Invalid bind-sphere '" << value << "'" << std::endl; return -1; }
+            b.slot = (uint32_t)s;
+            opt.sphere_binds.push_back(b);
+        }
         else if (key == "--display") {                               // CURVE[,TRANSFER[,EXPOSURE]]
             const size_t c1 = value.find(','), c2 = c1 == std::string::npos ? c1 : value.find(',', c1 + 1);
             const std::string curve = value.substr(0, c1);
@@ -364,6 +403,15 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     if (opt.env_sampling && opt.adaptive) {
         std::cerr << "--env-sampling is not available with --adaptive." << std::endl;
         return -1;
+    }
+    if (!opt.textures.empty() || !opt.sphere_binds.empty()) {
+        const char* why = mode_r ? "--texture and --bind-sphere need the path tracer (Mode X): pass --spp."
+                        : !(opt.scene == "three" || opt.scene == "weekend" || opt.scene == "stress100k") ? "--texture and --bind-sphere need a sphere scene (three, weekend, stress100k)."
+                        : opt.env_sampling || opt.light_sampling ? "--texture is not available with --env-sampling or --light-sampling."
+                        : nullptr;
+        for (const Options::SphereBind& b : opt.sphere_binds)
+            if (!why && b.slot >= opt.textures.size()) why = "--bind-sphere names a slot that no --texture fills.";
+        if (why) { std::cerr << why << std::endl; return -1; }
     }
     if (mode_r && opt.light_sampling) {
         std::cerr << "--light-sampling needs the path tracer (Mode X): pass --spp." << std::endl;
@@ -478,6 +526,29 @@ std::vector<float> read_env_pfm(const std::string& path, uint32_t& n_face) {
     return rgba;
 }
 
+// --texture: a colour PFM, W wide and H high -> the texels rt3_set_texture takes, row 0 on top (a PFM stores its rows bottom to top).
+std::vector<float> read_texture_pfm(const std::string& path, uint32_t& w_out, uint32_t& h_out) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) throw Fatal("Could not open '" + path + "'");
+    std::string magic;
+    long long w = 0, h = 0;
+    double scale = 0.0;
+    in >> magic >> w >> h >> scale;
+    if (!in || in.get() == EOF) throw Fatal("'" + path + "' is not a PFM file");
+    if (magic != "PF" || !(scale < 0.0)) throw Fatal("'" + path + "' must be a little-endian colour PFM (PF, negative scale)");
+    if (w < 1 || h < 1 || w > (long long)RT3_TEX_MAX_SIDE || h > (long long)RT3_TEX_MAX_SIDE || w * h > (1ll << 26))
+        throw Fatal("'" + path + "' is " + std::to_string(w) + " x " + std::to_string(h) + ": a texture is up to " + std::to_string(RT3_TEX_MAX_SIDE) +
+                    " on a side and holds up to 2^26 texels");
+    std::vector<float> rgb((size_t)3 * w * h);
+    if (!in.read(reinterpret_cast<char*>(rgb.data()), (std::streamsize)(rgb.size() * sizeof(float)))) throw Fatal("'" + path + "' ends before its pixels do");
+    std::vector<float> rgba((size_t)4 * w * h, 0.0f);
+    for (long long y = 0; y < h; y++)                                // y: row from the top
+        for (long long x = 0; x < w; x++)
+            for (int c = 0; c < 3; c++) rgba[4 * (size_t)(y * w + x) + c] = rgb[3 * (size_t)((h - 1 - y) * w + x) + c];
+    w_out = (uint32_t)w; h_out = (uint32_t)h;
+    return rgba;
+}
+
 template <class Fn>
 void sphere_scene(HipRenderer& r, Fn generate) {
     const uint32_t n = generate(nullptr, nullptr, 0);
@@ -580,6 +651,22 @@ int main(int argc, const char** argv) {
             if (opt.env_sampling) path.flags |= RT3_FLAG_ENV_SAMPLING;
         }
         if (opt.light_sampling) path.flags |= RT3_FLAG_LIGHT_SAMPLING;
+        // --texture / --bind-sphere: the slots once, the spheres' binding now and again after every full upload of the spheres (it goes with them)
+        std::vector<uint32_t> sphere_slots;
+        for (size_t k = 0; k < opt.textures.size(); k++) {
+            uint32_t tw = 0, th = 0;
+            const std::vector<float> rgba = read_texture_pfm(opt.textures[k].path, tw, th);
+            renderer.set_texture((uint32_t)k, rgba, tw, th, opt.textures[k].wrap);
+        }
+        if (!opt.sphere_binds.empty()) {
+            sphere_slots.assign(scene_mats.size(), RT3_TEX_NONE);
+            for (const Options::SphereBind& b : opt.sphere_binds) {
+                if (b.all) std::fill(sphere_slots.begin(), sphere_slots.end(), b.slot);
+                else if (b.index < sphere_slots.size()) sphere_slots[b.index] = b.slot;
+                else throw Fatal("--bind-sphere: the scene has no sphere " + std::to_string(b.index));
+            }
+            renderer.bind_sphere_textures(sphere_slots);
+        }
         const uint32_t seed0 = path.seed;
         const rt3_temporal_params tp{ { 5, 128, 4.0f, 1.0f }, 0.2f, 0.2f, 2.0f, 0.9f };       // the defaults of DESIGN.md 4.11 and 4.12
         std::vector<float> shown_cr = scene_cr, prev_cr;             // --slide: the spheres of this frame and of the one before
@@ -592,7 +679,10 @@ int main(int argc, const char** argv) {
                 renderer.update_spheres(shown_cr);
                 if (opt.regroup != 0 && k % opt.regroup == 0) renderer.regroup(true, false);
             }
-            else renderer.set_spheres(shown_cr, scene_mats);
+            else {
+                renderer.set_spheres(shown_cr, scene_mats);
+                if (!sphere_slots.empty()) renderer.bind_sphere_textures(sphere_slots);
+            }
         };
         // --orbit, frame k: the look-from point turned by k * orbit about the vertical axis through the look-at point
         const auto orbit_from = [&](uint32_t k) {

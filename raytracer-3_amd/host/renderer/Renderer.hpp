@@ -63,6 +63,12 @@ public:
     // 4 floats each (r, g, b, ignored), faces +X, -X, +Y, -Y, +Z, -Z, row 0 first; it stays until it is replaced or cleared
     void set_environment(const std::vector<float>& rgba, uint32_t n_face);
     void clear_environment();
+    // Mode X: image textures on every device (rt3_set_texture, rt3_bind_*_textures).  A slot holds w x h texels of 4 floats (r, g, b,
+    // ignored), row 0 on top, wrap RT3_TEX_REPEAT or RT3_TEX_CLAMP; a binding names one slot per primitive in the upload's order (RT3_TEX_NONE: none),
+    // for faces with 6 uv floats each.  Slots stay until they are replaced; a binding goes with the next full upload of its class.  Empty slots: unbinds.
+    void set_texture(uint32_t slot, const std::vector<float>& rgba, uint32_t w, uint32_t h, uint32_t wrap = RT3_TEX_REPEAT);
+    void bind_sphere_textures(const std::vector<uint32_t>& slots);
+    void bind_mesh_textures(const std::vector<uint32_t>& slots, const std::vector<float>& uv6);
     rt3_stats stats() const;                                                     // of device 0's last render
     // Mode X only, full frames (row 0 on top) assembled from the device shards: the first-hit AOVs of the current options (rt3_render_aov),
     // and the linear (r, g, b, 0) frame of the last render (rt3_accum_resolve)

@@ -108,6 +108,14 @@ int rt3_debug_display_state(rt3_ctx*, uint32_t*, uint32_t*, float*) { return RT3
 int rt3_display_sequence(rt3_ctx*, uint32_t, uint32_t, const float*, const rt3_display_sequence_params*, const rt3_exposure*, rt3_exposure*, uint32_t*) { return RT3_E_DEVICE; }     // (rt3_debug_exposure_step / rt3_debug_bloom are host code)
 int rt3_display_sequence_device(rt3_ctx*, uint32_t, uint32_t, const void*, const rt3_display_sequence_params*, const void*, void*, void*, void*) { return RT3_E_DEVICE; }
 int rt3_debug_display_bloom(rt3_ctx*, float*, float*, uint64_t, uint32_t*, uint32_t*) { return RT3_E_DEVICE; }
+int rt3_set_texture(rt3_ctx*, uint32_t, const float*, uint32_t, uint32_t, uint32_t) { return RT3_E_DEVICE; }     // (rt3_debug_texture_lookup / _sphere_uv / _face_uv are host code)
+int rt3_set_texture_device(rt3_ctx*, uint32_t, const void*, uint32_t, uint32_t, uint32_t, void*) { return RT3_E_DEVICE; }
+int rt3_clear_textures(rt3_ctx*) { return RT3_E_DEVICE; }
+int rt3_texture_size(rt3_ctx*, uint32_t, uint32_t*, uint32_t*, uint32_t*) { return RT3_E_DEVICE; }
+int rt3_bind_sphere_textures(rt3_ctx*, const uint32_t*, uint32_t) { return RT3_E_DEVICE; }
+int rt3_bind_sphere_textures_device(rt3_ctx*, const void*, uint32_t, void*) { return RT3_E_DEVICE; }
+int rt3_bind_mesh_textures(rt3_ctx*, const uint32_t*, const float*, uint32_t) { return RT3_E_DEVICE; }
+int rt3_bind_mesh_textures_device(rt3_ctx*, const void*, const void*, uint32_t, void*) { return RT3_E_DEVICE; }
 // (rt3_rows_owned / rt3_row_of_local are pure host arithmetic that happens to live in rt3_device.hip)
 uint32_t rt3_rows_owned(const rt3_params* p) {
     uint32_t n = 0;

@@ -8,7 +8,7 @@ apart.  This script makes that a BUILD-TIME property:
 
     python tools/cvt_isa_check.py [listing.s]        exit 1 if any v_cvt_pk_bf16_f32 of the listing has a reader of its destination register
                                                      in the next issue slot; without an argument it compiles the product sources itself
-                                                     (hipcc -S, device only; four listings in parallel, FORM_PARTS below) —
+                                                     (hipcc -S, device only; five listings in parallel, FORM_PARTS below) —
                                                      tests/test_cvt_isa.py runs it that way in the CPU suite
     python tools/cvt_isa_check.py --table a.s b.s    per kernel: distance (wait states) from every conversion to its first reader, and back to the
                                                      last MFMA that READ the destination register as an A/B operand (the write-after-read window)
@@ -91,10 +91,10 @@ def analyse(body):
 
 
 # The trace kernels are instantiated per Form (rt3_kernel_common.hpp): RT3_FORM_MASK (rt3_device.hip) compiles some of the forms only.  One listing of
-# everything takes ten minutes on one core; with four or more cores the forms are compiled as four listings in parallel (a kernel's code does not depend
+# everything takes ten minutes on one core; with four or more cores the forms are compiled as five listings in parallel (a kernel's code does not depend
 # on which kernels are compiled beside it; the kernels that have no form are in every listing and counted once).
-FORM_PARTS = [0x007, 0x038, 0x3C0, 0xC00]                            # Render RenderRef Query | List Rays RenderEnv | ListEnv RaysEnv RenderEnvNee RaysEnvNee | RenderLight RaysLight
-N_FORMS = 12
+FORM_PARTS = [0x007, 0x038, 0x3C0, 0xC00, 0x7000]                    # Render RenderRef Query | List Rays RenderEnv | ListEnv RaysEnv RenderEnvNee RaysEnvNee | RenderLight RaysLight | RenderTex ListTex RaysTex
+N_FORMS = 15
 
 
 def compile_product():
