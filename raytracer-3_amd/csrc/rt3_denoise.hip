@@ -3,15 +3,19 @@
 // k_denoise_moments, then k_denoise_atrous once per pass; the last pass remodulates into the caller's frame.  Every sum runs in the tap order
 // of DESIGN.md 4.11 with no contraction (the library builds with -ffp-contract=off), so tests/denoise_ref.py restates it in numpy.
 // A translation unit of its own (gfx950 only): the kernels share nothing with the render path, and compiled apart they add about 2 s to the
-// build instead of about 14 s inside rt3_device.hip.  rt3_device.hip checks the arguments, owns the scratch and calls denoise_launch().
+// build instead of about 14 s inside rt3_device.hip.  The entry points are below the kernels: they check the arguments, take the scratch from the
+// context (rt3_ctx.hpp) and launch.
 // k_temporal_reproject and k_motion take the view as a template parameter: the pinhole camera, or a lens model whose law is rt3_lens_law.hpp's
 // (DESIGN.md 4.24, 5.2s).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <string>
 #include <type_traits>
 
-#include "rt3_denoise.hpp"
+#include "rt3_ctx.hpp"
 #include "rt3_lens_law.hpp"
 
 namespace {
@@ -498,36 +502,128 @@ __global__ __launch_bounds__(kDnTile * kDnTile) void k_motion(const MotionArgsOf
 
 }  // namespace
 
-hipError_t denoise_launch(const DenoiseLaunch& L, hipStream_t stream) {
-    const uint32_t w = L.width, h = L.height;
-    const size_t npix = (size_t)w * h;
-    float4* const pa = L.scratch;
-    float4* const pb = pa + npix;
-    float4* const guide = pb + npix;
-    float* const gz = reinterpret_cast<float*>(guide + npix);
+// ======================================================================================================
+// The entry points (rt3.h): the checks, the context's scratch, the launches
+// ======================================================================================================
+static_assert(sizeof(rt3_denoise_params) == 16, "rt3.h: rt3_denoise_params");
+static_assert(sizeof(rt3_history) == 48, "rt3.h: rt3_history");
+static_assert(sizeof(rt3_temporal_params) == 32, "rt3.h: rt3_temporal_params");
+
+// ---- The denoiser
+static int denoise_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* colour, const void* aov, const rt3_denoise_params* p,
+                          const void* out) {
+    if (!p) return fail(ctx, RT3_E_ARG, "p is NULL");
+    if (!colour || !aov || !out) return fail(ctx, RT3_E_ARG, "colour / aov / out is NULL");
+    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must have 1 .. 2^26 pixels");
+    if (p->iterations < 1 || p->iterations > 8) return fail(ctx, RT3_E_ARG, "iterations must be 1 .. 8");
+    if (p->normal_power < 1 || p->normal_power > 1024 || (p->normal_power & (p->normal_power - 1)))
+        return fail(ctx, RT3_E_ARG, "normal_power must be a power of two in 1 .. 1024");
+    if (!std::isfinite(p->sigma_luminance) || !(p->sigma_luminance > 0.0f) || !std::isfinite(p->sigma_depth) || !(p->sigma_depth > 0.0f))
+        return fail(ctx, RT3_E_ARG, "sigma_luminance and sigma_depth must be finite and > 0");
+    return 0;
+}
+
+// The scratch of a call over n = w * h pixels (ctx->d_dn, the context's): scratch_quads(n) float4 entries, [0, n) and [n, 2n) the two (I, v)
+// planes the passes ping-pong, [2n, 3n) the guide, then n floats of depth slope.  With it what every kernel of the call reads and the launch
+// geometry: one thread per pixel, 16 x 16 tiles.
+static size_t scratch_quads(size_t npix) { return 3 * npix + (npix + 3) / 4; }
+struct DenoisePlan {
     DenoiseArgs D;
-    D.width = w; D.height = h;
-    D.tiles_x = (w + kDnTile - 1) / kDnTile;
-    D.squarings = 0;
-    while ((1u << D.squarings) < L.normal_power) D.squarings++;
-    D.sigma_l = L.sigma_l; D.sigma_z = L.sigma_z;
-    D.guide = guide; D.gz = gz;
-    const dim3 grid(D.tiles_x * ((h + kDnTile - 1) / kDnTile)), block(kDnTile, kDnTile);
-    const float4* aov = (const float4*)L.aov;
-    hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, stream, D, (const float4*)L.colour, aov, pa, guide, gz);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_denoise_moments<false>, grid, block, 0, stream, D, (const float4*)pa, pb, nullptr);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    float4* src = pb;
-    float4* dst = pa;
-    for (uint32_t i = 0; i < L.iterations; i++) {
-        if (i + 1 == L.iterations) hipLaunchKernelGGL((k_denoise_atrous<true, false>), grid, block, 0, stream, D, (const float4*)src, (float4*)L.out, 1 << i, aov, nullptr);
-        else hipLaunchKernelGGL((k_denoise_atrous<false, false>), grid, block, 0, stream, D, (const float4*)src, dst, 1 << i, aov, nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+    float4 *pa, *pb, *guide;
+    float* gz;
+    dim3 grid, block;
+    DenoisePlan(uint32_t w, uint32_t h, const rt3_denoise_params& p, float4* scratch) : block(kDnTile, kDnTile) {
+        const size_t npix = (size_t)w * h;
+        pa = scratch; pb = pa + npix; guide = pb + npix;
+        gz = reinterpret_cast<float*>(guide + npix);
+        D.width = w; D.height = h;
+        D.tiles_x = (w + kDnTile - 1) / kDnTile;
+        D.squarings = 0;
+        while ((1u << D.squarings) < p.normal_power) D.squarings++;
+        D.sigma_l = p.sigma_luminance; D.sigma_z = p.sigma_depth;
+        D.guide = guide; D.gz = gz;
+        grid = dim3(D.tiles_x * ((h + kDnTile - 1) / kDnTile));
+    }
+};
+
+// k_denoise_atrous once per pass from plane pb, ping-ponging the two (I, v) planes; the last pass remodulates into `out`.  hist (the temporal
+// call): pass 0 also writes the history colour.
+static int atrous_passes(rt3_ctx* ctx, const DenoisePlan& P, uint32_t iterations, const float4* aov, float4* out, float4* hist, hipStream_t stream) {
+    float4* src = P.pb;
+    float4* dst = P.pa;
+    for (uint32_t i = 0; i < iterations; i++) {
+        const bool last = i + 1 == iterations, history = hist && i == 0;
+        const auto pass = last ? (history ? k_denoise_atrous<true, true> : k_denoise_atrous<true, false>)
+                               : (history ? k_denoise_atrous<false, true> : k_denoise_atrous<false, false>);
+        hipLaunchKernelGGL(pass, P.grid, P.block, 0, stream, P.D, (const float4*)src, last ? out : dst, 1 << i, aov, history ? hist : (float4*)nullptr);
+        RT3_HIP(hipGetLastError());
         float4* t = src; src = dst; dst = t;
     }
-    return hipSuccess;
+    return 0;
+}
+
+extern "C" int rt3_denoise_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_colour, const void* d_aov, const rt3_denoise_params* p, void* d_out,
+                                  void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = denoise_checks(ctx, w, h, d_colour, d_aov, p, d_out);
+    if (rc) return rc;
+    if (((uintptr_t)d_colour | (uintptr_t)d_aov | (uintptr_t)d_out) % 16u != 0)
+        return fail(ctx, RT3_E_ARG, "d_colour_rgba, d_aov and d_out_rgba must be 16-byte aligned");
+    const size_t npix = (size_t)w * h;
+    const uintptr_t o = (uintptr_t)d_out, oe = o + npix * sizeof(float4);
+    const uintptr_t c = (uintptr_t)d_colour, a = (uintptr_t)d_aov;
+    if ((o < c + npix * sizeof(float4) && c < oe) || (o < a + npix * sizeof(rt3_aov) && a < oe))
+        return fail(ctx, RT3_E_ARG, "d_out_rgba overlaps an input");
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream)) || (rc = ctx->d_dn.ensure(ctx, scratch_quads(npix)))) return rc;
+    const DenoisePlan P(w, h, *p, ctx->d_dn);
+    const float4* const aov = (const float4*)d_aov;
+    hipLaunchKernelGGL(k_denoise_prepare, P.grid, P.block, 0, stream, P.D, (const float4*)d_colour, aov, P.pa, P.guide, P.gz);
+    RT3_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_denoise_moments<false>, P.grid, P.block, 0, stream, P.D, (const float4*)P.pa, P.pb, (const float4*)nullptr);
+    RT3_HIP(hipGetLastError());
+    if ((rc = atrous_passes(ctx, P, p->iterations, aov, (float4*)d_out, nullptr, stream))) return rc;
+    return leave(ctx, stream);
+}
+
+extern "C" int rt3_denoise(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* colour, const rt3_aov* aov, const rt3_denoise_params* p, float* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = denoise_checks(ctx, w, h, colour, aov, p, out);
+    if (rc) return rc;
+    const size_t npix = (size_t)w * h;
+    return staged(ctx, { stage_in(colour, npix * sizeof(float4)), stage_in(aov, npix * sizeof(rt3_aov)), stage_out(out, npix * sizeof(float4)) },
+                  [&](void* const* d) { return rt3_denoise_device(ctx, w, h, d[0], d[1], p, d[2], ctx->stream); });
+}
+
+// ---- The views of the temporal denoiser and of the motion plane: the pinhole camera, or a lens
+// h x v, written out: (hy vz - hz vy, hz vx - hx vz, hx vy - hy vx)
+static void cross3(const float* h, const float* v, float* out) {
+    out[0] = h[1] * v[2] - h[2] * v[1];
+    out[1] = h[2] * v[0] - h[0] * v[2];
+    out[2] = h[0] * v[1] - h[1] * v[0];
+}
+
+static float dot3h(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// A camera the reprojection can use: finite fields, horizontal x vertical != 0, and an image plane that misses the origin.
+static bool camera_ok(const rt3_camera* c) {
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(c->origin[i]) || !std::isfinite(c->horizontal[i]) || !std::isfinite(c->vertical[i]) || !std::isfinite(c->lower_left_corner[i]))
+            return false;
+    float n[3], l[3];
+    cross3(c->horizontal, c->vertical, n);
+    if (n[0] == 0.0f && n[1] == 0.0f && n[2] == 0.0f) return false;
+    for (int i = 0; i < 3; i++) l[i] = c->lower_left_corner[i] - c->origin[i];
+    return dot3h(l, n) != 0.0f;
+}
+
+// This frame's camera, the first twelve floats of CameraReproject and of CameraRays.
+template <class V>
+static void set_camera(V& v, const rt3_camera* c) {
+    v.ox = c->origin[0]; v.oy = c->origin[1]; v.oz = c->origin[2];
+    v.hx = c->horizontal[0]; v.hy = c->horizontal[1]; v.hz = c->horizontal[2];
+    v.vx = c->vertical[0]; v.vy = c->vertical[1]; v.vz = c->vertical[2];
+    v.lx = c->lower_left_corner[0]; v.ly = c->lower_left_corner[1]; v.lz = c->lower_left_corner[2];
 }
 
 // The launch argument of the lens forms: both lenses by value, the frame, and whether the inverse law may take the shortcut.
@@ -539,109 +635,286 @@ static LensArgs lens_args(const rt3_lens* lens, const rt3_lens* prev, uint32_t w
     return A;
 }
 
-template <uint32_t VIEW>
-static void launch_reproject(dim3 grid, dim3 block, hipStream_t stream, const DenoiseArgs& D, const TemporalArgsOf<VIEW>& A, const DenoiseLaunch& L,
-                             const TemporalLaunch& T, float4* pa, float4* guide, float* gz) {
-    if (T.motion) hipLaunchKernelGGL((k_temporal_reproject<VIEW, true>), grid, block, 0, stream, D, A, (const float4*)L.colour, (const float4*)L.aov,
-                                     (const float4*)T.prev_history, pa, guide, gz, (float4*)T.out_history, (const float4*)T.motion);
-    else hipLaunchKernelGGL((k_temporal_reproject<VIEW, false>), grid, block, 0, stream, D, A, (const float4*)L.colour, (const float4*)L.aov,
-                            (const float4*)T.prev_history, pa, guide, gz, (float4*)T.out_history, nullptr);
+// fn(the view as a compile-time constant): kViewCamera, or the lens's model.
+template <uint32_t VIEW> using ViewConstant = std::integral_constant<uint32_t, VIEW>;
+template <class Fn>
+static void with_view(const rt3_camera*, Fn fn) { fn(ViewConstant<kViewCamera>{}); }
+template <class Fn>
+static void with_view(const rt3_lens* lens, Fn fn) {
+    switch (lens->model) {
+    case RT3_LENS_EQUIRECT: fn(ViewConstant<RT3_LENS_EQUIRECT>{}); break;
+    case RT3_LENS_FISHEYE:  fn(ViewConstant<RT3_LENS_FISHEYE>{}); break;
+    case RT3_LENS_ORTHO:    fn(ViewConstant<RT3_LENS_ORTHO>{}); break;
+    default:                fn(ViewConstant<RT3_LENS_CUBE>{}); break;
+    }
 }
 
-hipError_t temporal_launch(const TemporalLaunch& T, hipStream_t stream) {
-    const DenoiseLaunch& L = T.base;
-    const uint32_t w = L.width, h = L.height;
+// ---- The temporal denoiser, for a frame rendered through a camera or through a lens: View is rt3_camera or rt3_lens,
+// view / prev_view this frame's and the previous frame's.  What follows is overloaded on it: its name in the refusals, what refuses a pair of
+// views, and the view's part of k_temporal_reproject's arguments.
+static const char* view_name(const rt3_camera*) { return "cam"; }
+static const char* view_name(const rt3_lens*) { return "lens"; }
+
+static int views_ok(rt3_ctx* ctx, uint32_t, uint32_t, const rt3_camera* cam, const rt3_camera* prev_cam) {
+    if (!camera_ok(cam) || (prev_cam && !camera_ok(prev_cam)))
+        return fail(ctx, RT3_E_ARG, "a camera has a non-finite field, horizontal x vertical = 0, or an image plane through its origin");
+    return 0;
+}
+static int views_ok(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const rt3_lens* prev_lens) {
+    if (const char* why = rt3lens::refusal(lens, w, h)) return fail(ctx, RT3_E_ARG, why);
+    if (prev_lens) {
+        if (const char* why = rt3lens::refusal(prev_lens, w, h)) return fail(ctx, RT3_E_ARG, std::string("prev_") + why);
+        if (prev_lens->model != lens->model) return fail(ctx, RT3_E_ARG, "prev_lens must have the model of lens");
+    }
+    return 0;
+}
+
+// The projection constants of DESIGN.md 4.12 step 3, in f32 in this order: L = llc' - o', n = h x v, a_u = (v x n) / (h . (v x n)),
+// a_v = (n x h) / (v . (n x h)) component by component, then L . n.  Without a previous camera they stay zero and are not read.
+static TemporalArgs<CameraReproject> reproject_args(const rt3_camera* cam, const rt3_camera* prev_cam, uint32_t, uint32_t) {
+    TemporalArgs<CameraReproject> A{};
+    CameraReproject& V = A.view;
+    set_camera(V, cam);
+    if (prev_cam) {
+        const float* hh = prev_cam->horizontal;
+        const float* vv = prev_cam->vertical;
+        float l[3], n[3], vn[3], nh[3];
+        for (int i = 0; i < 3; i++) l[i] = prev_cam->lower_left_corner[i] - prev_cam->origin[i];
+        cross3(hh, vv, n);
+        cross3(vv, n, vn);
+        const float du = dot3h(hh, vn);
+        cross3(n, hh, nh);
+        const float dv = dot3h(vv, nh);
+        V.pox = prev_cam->origin[0]; V.poy = prev_cam->origin[1]; V.poz = prev_cam->origin[2];
+        V.plx = l[0]; V.ply = l[1]; V.plz = l[2];
+        V.nx = n[0]; V.ny = n[1]; V.nz = n[2];
+        V.aux = vn[0] / du; V.auy = vn[1] / du; V.auz = vn[2] / du;
+        V.avx = nh[0] / dv; V.avy = nh[1] / dv; V.avz = nh[2] / dv;
+        V.ln = dot3h(l, n);
+        A.has_prev = 1;
+        A.same_cam = std::memcmp(prev_cam, cam, sizeof(rt3_camera)) == 0;
+    }
+    return A;
+}
+// The lens forms of k_temporal_reproject take the lenses by value; nothing is worked out here.
+static TemporalArgs<LensArgs> reproject_args(const rt3_lens* lens, const rt3_lens* prev_lens, uint32_t w, uint32_t h) {
+    TemporalArgs<LensArgs> A{};
+    A.view = lens_args(lens, prev_lens ? prev_lens : lens, w, h);
+    A.has_prev = prev_lens ? 1u : 0u;
+    A.same_cam = A.view.same;
+    return A;
+}
+
+// What every form checks.
+template <class View>
+static int temporal_checks_of(rt3_ctx* ctx, uint32_t w, uint32_t h, const View* view, const void* colour, const void* aov, const View* prev_view,
+                              const void* prev_history, const void* motion, const rt3_temporal_params* p, const void* out, const void* out_history) {
+    const char* const what = view_name(view);
+    if (!p || !view) return fail(ctx, RT3_E_ARG, std::string("p / ") + what + " is NULL");
+    if (!colour || !aov || !out || !out_history) return fail(ctx, RT3_E_ARG, "colour / aov / out / out_history is NULL");
+    if (!prev_view != !prev_history) return fail(ctx, RT3_E_ARG, std::string("prev_") + what + " and prev_history must both be NULL or both be non-NULL");
+    if (w < 2 || h < 2 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must be at least 2 x 2 and have at most 2^26 pixels");
+    int rc = denoise_checks(ctx, w, h, colour, aov, &p->spatial, out);
+    if (rc) return rc;
+    if (!(p->alpha > 0.0f && p->alpha <= 1.0f) || !(p->moments_alpha > 0.0f && p->moments_alpha <= 1.0f))
+        return fail(ctx, RT3_E_ARG, "alpha and moments_alpha must be in (0, 1]");
+    if (!std::isfinite(p->depth_tolerance) || !(p->depth_tolerance > 0.0f)) return fail(ctx, RT3_E_ARG, "depth_tolerance must be finite and > 0");
+    if (!(p->normal_tolerance >= -1.0f && p->normal_tolerance <= 1.0f)) return fail(ctx, RT3_E_ARG, "normal_tolerance must be in [-1, 1]");
+    if ((rc = views_ok(ctx, w, h, view, prev_view))) return rc;
+    const size_t npix = (size_t)w * h, nf = npix * sizeof(float4), nh = npix * sizeof(rt3_history);
+    const struct { const void* ptr; size_t n; } in[4] = { { colour, nf }, { aov, npix * sizeof(rt3_aov) }, { prev_history, nh }, { motion, nf } };
+    for (const auto& i : in)
+        if (i.ptr && (ranges_overlap(out, nf, i.ptr, i.n) || ranges_overlap(out_history, nh, i.ptr, i.n)))
+            return fail(ctx, RT3_E_ARG, "an output overlaps an input");
+    if (ranges_overlap(out, nf, out_history, nh)) return fail(ctx, RT3_E_ARG, "out_rgba and out_history overlap");
+    return 0;
+}
+
+// The device form for either view: k_temporal_reproject -> k_denoise_moments<true> -> the passes (pass 0 also writes the history colour); the
+// same scratch as rt3_denoise.  d_motion: the plane rt3_motion wrote, or NULL; without a previous frame it is checked and not read.
+template <class View>
+static int temporal_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const View* view, const void* d_colour, const void* d_aov, const View* prev_view,
+                           const void* d_prev_history, const void* d_motion, const rt3_temporal_params* p, void* d_out, void* d_out_history,
+                           void* stream_) {
+    int rc = temporal_checks_of(ctx, w, h, view, d_colour, d_aov, prev_view, d_prev_history, d_motion, p, d_out, d_out_history);
+    if (rc) return rc;
+    if (((uintptr_t)d_colour | (uintptr_t)d_aov | (uintptr_t)d_prev_history | (uintptr_t)d_motion | (uintptr_t)d_out | (uintptr_t)d_out_history) % 16u != 0)
+        return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
+    auto A = reproject_args(view, prev_view, w, h);
+    A.alpha = p->alpha; A.moments_alpha = p->moments_alpha; A.depth_tolerance = p->depth_tolerance; A.normal_tolerance = p->normal_tolerance;
+    const float4* const colour = (const float4*)d_colour;
+    const float4* const aov = (const float4*)d_aov;
+    const float4* const prev = (const float4*)d_prev_history;
+    const float4* const motion = prev_view ? (const float4*)d_motion : nullptr;
+    float4* const hist = (float4*)d_out_history;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream)) || (rc = ctx->d_dn.ensure(ctx, scratch_quads((size_t)w * h)))) return rc;
+    const DenoisePlan P(w, h, p->spatial, ctx->d_dn);
+    with_view(view, [&](auto model) {
+        constexpr uint32_t VIEW = decltype(model)::value;
+        if (motion) hipLaunchKernelGGL((k_temporal_reproject<VIEW, true>), P.grid, P.block, 0, stream, P.D, A, colour, aov, prev, P.pa, P.guide, P.gz, hist, motion);
+        else hipLaunchKernelGGL((k_temporal_reproject<VIEW, false>), P.grid, P.block, 0, stream, P.D, A, colour, aov, prev, P.pa, P.guide, P.gz, hist, motion);
+    });
+    RT3_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_denoise_moments<true>, P.grid, P.block, 0, stream, P.D, (const float4*)P.pa, P.pb, (const float4*)hist);
+    RT3_HIP(hipGetLastError());
+    if ((rc = atrous_passes(ctx, P, p->spatial.iterations, aov, (float4*)d_out, hist, stream))) return rc;
+    return leave(ctx, stream);
+}
+
+// The host form for either view.
+template <class View>
+static int temporal_host(rt3_ctx* ctx, uint32_t w, uint32_t h, const View* view, const float* colour, const rt3_aov* aov, const View* prev_view,
+                         const rt3_history* prev_history, const float* motion, const rt3_temporal_params* p, float* out, rt3_history* out_history) {
+    int rc = temporal_checks_of(ctx, w, h, view, colour, aov, prev_view, prev_history, motion, p, out, out_history);
+    if (rc) return rc;
     const size_t npix = (size_t)w * h;
-    float4* const pa = L.scratch;
-    float4* const pb = pa + npix;
-    float4* const guide = pb + npix;
-    float* const gz = reinterpret_cast<float*>(guide + npix);
-    DenoiseArgs D;
-    D.width = w; D.height = h;
-    D.tiles_x = (w + kDnTile - 1) / kDnTile;
-    D.squarings = 0;
-    while ((1u << D.squarings) < L.normal_power) D.squarings++;
-    D.sigma_l = L.sigma_l; D.sigma_z = L.sigma_z;
-    D.guide = guide; D.gz = gz;
-    const dim3 grid(D.tiles_x * ((h + kDnTile - 1) / kDnTile)), block(kDnTile, kDnTile);
-    const float4* aov = (const float4*)L.aov;
-    float4* const hist = (float4*)T.out_history;
-    if (T.lens) {
-        TemporalArgs<LensArgs> A;
-        A.view = lens_args(T.lens, T.has_prev ? T.prev_lens : T.lens, w, h);
-        A.has_prev = T.has_prev; A.same_cam = A.view.same;
-        A.alpha = T.alpha; A.moments_alpha = T.moments_alpha; A.depth_tolerance = T.depth_tolerance; A.normal_tolerance = T.normal_tolerance;
-        switch (T.lens->model) {
-        case RT3_LENS_EQUIRECT: launch_reproject<RT3_LENS_EQUIRECT>(grid, block, stream, D, A, L, T, pa, guide, gz); break;
-        case RT3_LENS_FISHEYE:  launch_reproject<RT3_LENS_FISHEYE>(grid, block, stream, D, A, L, T, pa, guide, gz); break;
-        case RT3_LENS_ORTHO:    launch_reproject<RT3_LENS_ORTHO>(grid, block, stream, D, A, L, T, pa, guide, gz); break;
-        default:                launch_reproject<RT3_LENS_CUBE>(grid, block, stream, D, A, L, T, pa, guide, gz); break;
-        }
-    } else {
-        TemporalArgs<CameraReproject> A;
-        CameraReproject& V = A.view;
-        V.ox = T.cam[0]; V.oy = T.cam[1]; V.oz = T.cam[2];
-        V.hx = T.cam[3]; V.hy = T.cam[4]; V.hz = T.cam[5];
-        V.vx = T.cam[6]; V.vy = T.cam[7]; V.vz = T.cam[8];
-        V.lx = T.cam[9]; V.ly = T.cam[10]; V.lz = T.cam[11];
-        V.pox = T.prev_o[0]; V.poy = T.prev_o[1]; V.poz = T.prev_o[2];
-        V.plx = T.prev_l[0]; V.ply = T.prev_l[1]; V.plz = T.prev_l[2];
-        V.nx = T.prev_n[0]; V.ny = T.prev_n[1]; V.nz = T.prev_n[2];
-        V.aux = T.a_u[0]; V.auy = T.a_u[1]; V.auz = T.a_u[2];
-        V.avx = T.a_v[0]; V.avy = T.a_v[1]; V.avz = T.a_v[2];
-        V.ln = T.ln;
-        A.has_prev = T.has_prev; A.same_cam = T.same_cam;
-        A.alpha = T.alpha; A.moments_alpha = T.moments_alpha; A.depth_tolerance = T.depth_tolerance; A.normal_tolerance = T.normal_tolerance;
-        launch_reproject<kViewCamera>(grid, block, stream, D, A, L, T, pa, guide, gz);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_denoise_moments<true>, grid, block, 0, stream, D, (const float4*)pa, pb, (const float4*)hist);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    float4* src = pb;
-    float4* dst = pa;
-    for (uint32_t i = 0; i < L.iterations; i++) {
-        const bool last = i + 1 == L.iterations;
-        if (i == 0 && last) hipLaunchKernelGGL((k_denoise_atrous<true, true>), grid, block, 0, stream, D, (const float4*)src, (float4*)L.out, 1, aov, hist);
-        else if (i == 0) hipLaunchKernelGGL((k_denoise_atrous<false, true>), grid, block, 0, stream, D, (const float4*)src, dst, 1, aov, hist);
-        else if (last) hipLaunchKernelGGL((k_denoise_atrous<true, false>), grid, block, 0, stream, D, (const float4*)src, (float4*)L.out, 1 << i, aov, nullptr);
-        else hipLaunchKernelGGL((k_denoise_atrous<false, false>), grid, block, 0, stream, D, (const float4*)src, dst, 1 << i, aov, nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        float4* t = src; src = dst; dst = t;
-    }
-    return hipSuccess;
+    return staged(ctx, { stage_in(colour, npix * sizeof(float4)), stage_in(aov, npix * sizeof(rt3_aov)),
+                         stage_in(prev_history, npix * sizeof(rt3_history)), stage_in(motion, npix * sizeof(float4)),
+                         stage_out(out, npix * sizeof(float4)), stage_out(out_history, npix * sizeof(rt3_history)) },
+                  [&](void* const* d) { return temporal_device(ctx, w, h, view, d[0], d[1], prev_view, d[2], d[3], p, d[4], d[5], ctx->stream); });
 }
 
-template <uint32_t VIEW>
-static void launch_motion(const MotionLaunch& L, const typename MotionArgsOf<VIEW>::view_type& view, hipStream_t stream) {
-    MotionArgsOf<VIEW> M;
-    M.width = L.width; M.height = L.height;
-    M.tiles_x = (L.width + kDnTile - 1) / kDnTile;
-    M.n_sph = L.n_sph; M.n_faces = L.n_faces; M.n_verts = L.n_verts;
-    M.view = view;
-    M.aov = (const float4*)L.aov;
-    M.sph = (const float4*)L.sph; M.sph_invr = L.sph_invr; M.prev_sph = (const float4*)L.prev_sph;
-    M.gfaces = (const uint4*)L.gfaces; M.verts = (const float4*)L.verts; M.prev_verts = (const float4*)L.prev_verts;
-    const dim3 grid(M.tiles_x * ((L.height + kDnTile - 1) / kDnTile)), block(kDnTile, kDnTile);
-    hipLaunchKernelGGL(k_motion<VIEW>, grid, block, 0, stream, M, (float4*)L.out);
+extern "C" {
+
+int rt3_denoise_temporal_motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_colour, const void* d_aov,
+                                       const rt3_camera* prev_cam, const void* d_prev_history, const void* d_motion,
+                                       const rt3_temporal_params* p, void* d_out, void* d_out_history, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    return temporal_device(ctx, w, h, cam, d_colour, d_aov, prev_cam, d_prev_history, d_motion, p, d_out, d_out_history, stream_);
 }
 
-hipError_t motion_launch(const MotionLaunch& L, hipStream_t stream) {
-    if (L.lens) {
-        const LensArgs V = lens_args(L.lens, L.lens, L.width, L.height);
-        switch (L.lens->model) {
-        case RT3_LENS_EQUIRECT: launch_motion<RT3_LENS_EQUIRECT>(L, V, stream); break;
-        case RT3_LENS_FISHEYE:  launch_motion<RT3_LENS_FISHEYE>(L, V, stream); break;
-        case RT3_LENS_ORTHO:    launch_motion<RT3_LENS_ORTHO>(L, V, stream); break;
-        default:                launch_motion<RT3_LENS_CUBE>(L, V, stream); break;
-        }
-    } else {
-        CameraRays V;
-        V.ox = L.cam[0]; V.oy = L.cam[1]; V.oz = L.cam[2];
-        V.hx = L.cam[3]; V.hy = L.cam[4]; V.hz = L.cam[5];
-        V.vx = L.cam[6]; V.vy = L.cam[7]; V.vz = L.cam[8];
-        V.lx = L.cam[9]; V.ly = L.cam[10]; V.lz = L.cam[11];
-        launch_motion<kViewCamera>(L, V, stream);
-    }
-    return hipGetLastError();
+int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_colour, const void* d_aov,
+                                const rt3_camera* prev_cam, const void* d_prev_history, const rt3_temporal_params* p, void* d_out,
+                                void* d_out_history, void* stream_) {
+    return rt3_denoise_temporal_motion_device(ctx, w, h, cam, d_colour, d_aov, prev_cam, d_prev_history, nullptr, p, d_out, d_out_history, stream_);
 }
+
+int rt3_denoise_temporal_motion(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
+                                const rt3_camera* prev_cam, const rt3_history* prev_history, const float* motion,
+                                const rt3_temporal_params* p, float* out, rt3_history* out_history) {
+    if (!ctx) return RT3_E_ARG;
+    return temporal_host(ctx, w, h, cam, colour, aov, prev_cam, prev_history, motion, p, out, out_history);
+}
+
+int rt3_denoise_temporal(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
+                         const rt3_camera* prev_cam, const rt3_history* prev_history, const rt3_temporal_params* p, float* out,
+                         rt3_history* out_history) {
+    return rt3_denoise_temporal_motion(ctx, w, h, cam, colour, aov, prev_cam, prev_history, nullptr, p, out, out_history);
+}
+
+// Lens sequences: the same for a frame rendered through a lens.
+int rt3_denoise_temporal_optic_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const void* d_colour, const void* d_aov,
+                                      const rt3_lens* prev_lens, const void* d_prev_history, const void* d_motion,
+                                      const rt3_temporal_params* p, void* d_out, void* d_out_history, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    return temporal_device(ctx, w, h, lens, d_colour, d_aov, prev_lens, d_prev_history, d_motion, p, d_out, d_out_history, stream_);
+}
+
+int rt3_denoise_temporal_optic(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const float* colour, const rt3_aov* aov,
+                               const rt3_lens* prev_lens, const rt3_history* prev_history, const float* motion,
+                               const rt3_temporal_params* p, float* out, rt3_history* out_history) {
+    if (!ctx) return RT3_E_ARG;
+    return temporal_host(ctx, w, h, lens, colour, aov, prev_lens, prev_history, motion, p, out, out_history);
+}
+
+}  // extern "C"
+
+// ---- The motion plane
+// What both forms check: the frame, the view, and the previous arrays against the scene on the context.
+// cam or lens: the frame's view, exactly one of them.
+static int motion_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_lens* lens, const void* aov, const void* prev_sph,
+                         uint32_t n_prev_sph, const void* prev_verts, uint32_t n_prev_verts, const void* out) {
+    if ((!cam && !lens) || !aov || !out) return fail(ctx, RT3_E_ARG, "cam / lens / aov / out_motion is NULL");
+    if (w < 2 || h < 2 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must be at least 2 x 2 and have at most 2^26 pixels");
+    if (cam && !camera_ok(cam))
+        return fail(ctx, RT3_E_ARG, "the camera has a non-finite field, horizontal x vertical = 0, or an image plane through its origin");
+    if (lens)
+        if (const char* why = rt3lens::refusal(lens, w, h)) return fail(ctx, RT3_E_ARG, why);
+    if ((!prev_sph && n_prev_sph) || (!prev_verts && n_prev_verts)) return fail(ctx, RT3_E_ARG, "a NULL previous array must have a count of 0");
+    if (prev_sph && ctx->n_sph == 0) return fail(ctx, RT3_E_STATE, "previous spheres were given, but the context has no spheres");
+    if (prev_verts && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "previous vertices were given, but the context has no committed mesh");
+    if (prev_verts && !ctx->mesh_in_sync)
+        return fail(ctx, RT3_E_STATE, "the merged entity buffers were changed after the last rt3_mesh_commit (rt3_mesh_begin / rt3_mesh_put without a commit)");
+    if (prev_sph && n_prev_sph != ctx->n_sph) return fail(ctx, RT3_E_ARG, "n_prev_spheres must equal the context's sphere count");
+    if (prev_verts && n_prev_verts != ctx->d_verts.size()) return fail(ctx, RT3_E_ARG, "n_prev_vertices must equal the vertex count of the merged entity buffers");
+    const size_t npix = (size_t)w * h, no = npix * sizeof(float4);
+    const struct { const void* ptr; size_t n; } in[3] = { { aov, npix * sizeof(rt3_aov) }, { prev_sph, (size_t)n_prev_sph * sizeof(float4) },
+                                                          { prev_verts, (size_t)n_prev_verts * sizeof(float4) } };
+    for (const auto& i : in)
+        if (i.ptr && ranges_overlap(out, no, i.ptr, i.n)) return fail(ctx, RT3_E_ARG, "out_motion overlaps an input");
+    return 0;
+}
+
+// The device form for either view (cam or lens, exactly one): k_motion, one launch.  A class whose previous array is NULL did not move and is
+// never gathered: its buffers and counts stay out of the launch; the counts bound every gather of the other.
+static int motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_lens* lens, const void* d_aov, const void* d_prev_sph,
+                         uint32_t n_prev_sph, const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
+    int rc = motion_checks(ctx, w, h, cam, lens, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out);
+    if (rc) return rc;
+    if (((uintptr_t)d_aov | (uintptr_t)d_prev_sph | (uintptr_t)d_prev_verts | (uintptr_t)d_out) % 16u != 0)
+        return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    const auto launch = [&](auto model) {
+        constexpr uint32_t VIEW = decltype(model)::value;
+        MotionArgsOf<VIEW> M{};
+        M.width = w; M.height = h;
+        M.tiles_x = (w + kDnTile - 1) / kDnTile;
+        if constexpr (VIEW == kViewCamera) set_camera(M.view, cam);
+        else M.view = lens_args(lens, lens, w, h);
+        M.aov = (const float4*)d_aov;
+        if (d_prev_sph) { M.sph = ctx->d_sph_cr; M.sph_invr = ctx->d_sph_invr; M.prev_sph = (const float4*)d_prev_sph; M.n_sph = ctx->n_sph; }
+        if (d_prev_verts) {
+            M.gfaces = (const uint4*)ctx->d_gfaces.get(); M.verts = ctx->d_verts; M.prev_verts = (const float4*)d_prev_verts;
+            M.n_faces = ctx->n_faces; M.n_verts = (uint32_t)ctx->d_verts.size();
+        }
+        const dim3 grid(M.tiles_x * ((h + kDnTile - 1) / kDnTile)), block(kDnTile, kDnTile);
+        hipLaunchKernelGGL(k_motion<VIEW>, grid, block, 0, stream, M, (float4*)d_out);
+    };
+    if (lens) with_view(lens, launch);
+    else with_view(cam, launch);
+    RT3_HIP(hipGetLastError());
+    return leave(ctx, stream);
+}
+
+// The host form for either view.
+static int motion_host(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_lens* lens, const rt3_aov* aov, const float* prev_sph,
+                       uint32_t n_prev_sph, const float* prev_verts, uint32_t n_prev_verts, float* out) {
+    int rc = motion_checks(ctx, w, h, cam, lens, aov, prev_sph, n_prev_sph, prev_verts, n_prev_verts, out);
+    if (rc) return rc;
+    const size_t npix = (size_t)w * h;
+    return staged(ctx, { stage_in(aov, npix * sizeof(rt3_aov)), stage_in(prev_sph, (size_t)n_prev_sph * sizeof(float4)),
+                         stage_in(prev_verts, (size_t)n_prev_verts * sizeof(float4)), stage_out(out, npix * sizeof(float4)) },
+                  [&](void* const* d) { return motion_device(ctx, w, h, cam, lens, d[0], d[1], n_prev_sph, d[2], n_prev_verts, d[3], ctx->stream); });
+}
+
+extern "C" {
+
+int rt3_motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_aov, const void* d_prev_sph, uint32_t n_prev_sph,
+                      const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    return motion_device(ctx, w, h, cam, nullptr, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out, stream_);
+}
+
+int rt3_motion(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_aov* aov, const float* prev_sph, uint32_t n_prev_sph,
+               const float* prev_verts, uint32_t n_prev_verts, float* out) {
+    if (!ctx) return RT3_E_ARG;
+    return motion_host(ctx, w, h, cam, nullptr, aov, prev_sph, n_prev_sph, prev_verts, n_prev_verts, out);
+}
+
+int rt3_motion_optic_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const void* d_aov, const void* d_prev_sph, uint32_t n_prev_sph,
+                            const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    if (!lens) return fail(ctx, RT3_E_ARG, "lens / aov / out_motion is NULL");
+    return motion_device(ctx, w, h, nullptr, lens, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out, stream_);
+}
+
+int rt3_motion_optic(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const rt3_aov* aov, const float* prev_sph, uint32_t n_prev_sph,
+                     const float* prev_verts, uint32_t n_prev_verts, float* out) {
+    if (!ctx) return RT3_E_ARG;
+    if (!lens) return fail(ctx, RT3_E_ARG, "lens / aov / out_motion is NULL");
+    return motion_host(ctx, w, h, nullptr, lens, aov, prev_sph, n_prev_sph, prev_verts, n_prev_verts, out);
+}
+
+}  // extern "C"

@@ -17,16 +17,19 @@
 //                           ordered compaction of the pixels that stay active, the resolves by a pixel's own count
 //   rt3_texture_law.hpp     image textures: the lookup and the (u, v) of a sphere and of a face, host and device (the texture forms: 5.2u)
 //   rt3_aov.hpp             camera rays as records, first-hit AOVs over the query engine, the linear float resolve (in place for 4.18)
-//   rt3_denoise.hpp         the launchers of the AOV-guided a-trous denoiser, its temporal form and the motion plane (kernels: rt3_denoise.hip)
-//   rt3_display.hpp         the launcher of the display transform (kernels: rt3_display.hip; the law: rt3_display_law.hpp)
-//   rt3_display_sequence.hpp  the launcher of display sequences (kernels: rt3_display_sequence.hip; the law: rt3_display_sequence_law.hpp)
 //   rt3_scene_kernels.hpp   HIP equivalents of the pre-render shaders and of the merge
 //   rt3_regroup.hpp         the group order of the multi-level filter again on the device (rt3_regroup*): the median split as stable sorts,
 //                           in LDS for parts of up to 4096 primitives
 //   rt3_scene_build.hpp     a full upload from device arrays (rt3_set_spheres_device / rt3_set_mesh_device): validation, the medians, the direct
 //                           list and the ordered compaction into the initial group order
 //   rt3_sphere_plan.hpp     host: the filter centre and the direct list of a sphere upload (shared with rt3_host.cpp)
-//   below                   the device context and the extern "C" entry points
+//   rt3_ctx.hpp             the device context (struct rt3_ctx, DevBuf) and what every entry point shares: RT3_HIP, fail, enter / leave, staged
+//   below                   the host side of the render path and its extern "C" entry points: the scene, the renders, queries, AOVs, lenses,
+//                           radiance, the environment map and textures
+// The post-process entry points live with their kernels, in units of their own that include rt3_ctx.hpp as this one does:
+//   rt3_denoise.hip           rt3_denoise*, rt3_denoise_temporal*, rt3_motion* 
+//   rt3_display.hip           rt3_display*, rt3_debug_display_state
+//   rt3_display_sequence.hip  rt3_display_sequence*, rt3_debug_display_bloom
 //
 // Compiled with -ffp-contract=off: a*b+c is two roundings unless written __builtin_fmaf.  Division and sqrt are
 // the correctly rounded forms (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt), f32 denormals are kept.
@@ -47,6 +50,7 @@
 
 #include "rt3.h"
 
+#include "rt3_ctx.hpp"
 #include "rt3_sphere_plan.hpp"
 #include "rt3_env_sample.hpp"
 #include "rt3_light_sample.hpp"
@@ -61,11 +65,6 @@
 #include "rt3_adaptive.hpp"
 #include "rt3_aov.hpp"
 #include "rt3_lens.hpp"
-#include "rt3_denoise.hpp"
-#include "rt3_display_law.hpp"
-#include "rt3_display.hpp"
-#include "rt3_display_sequence_law.hpp"
-#include "rt3_display_sequence.hpp"
 #include "rt3_scene_kernels.hpp"
 #include "rt3_regroup.hpp"
 #include "rt3_scene_build.hpp"
@@ -76,179 +75,9 @@
 // ======================================================================================================
 // Host side of the device context
 // ======================================================================================================
-// A device buffer of n elements of T that the context owns: freed when it is replaced and when the context is deleted.  A failed allocation
-// leaves it null with capacity 0 and reports through ctx->err (alloc / upload below).
-template <typename T>
-class DevBuf {
-public:
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept { swap(o); }
-    DevBuf& operator=(DevBuf&& o) noexcept { swap(o); return *this; }      // (what this held leaves with o)
-    ~DevBuf() { reset(); }
-    T* get() const { return p_; }
-    operator T*() const { return p_; }
-    size_t size() const { return n_; }
-    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }
-    int alloc(rt3_ctx* ctx, size_t n);                              // exactly n elements (n = 0: none)
-    int ensure(rt3_ctx* ctx, size_t n) { return n_ >= n && p_ ? 0 : alloc(ctx, n); }     // grows only
-    int upload(rt3_ctx* ctx, const std::vector<T>& v);              // exactly v (empty: none)
-private:
-    void swap(DevBuf& o) { std::swap(p_, o.p_); std::swap(n_, o.n_); }
-    T* p_ = nullptr;
-    size_t n_ = 0;
-};
-
-// The rows of the multi-level filter of one primitive class, built by build_rows: the members' (cx, cy, cz, r^2) records in
-// group order and the primitive index of each, the leaf groups' bounds, the rows' bounds in f32 (rows behind a ray are dropped before their
-// leaves are tested) and as fragments, and the super-rows of kSuper rows (four levels) as f32 records and as fragments.
-struct FilterRows {
-    DevBuf<float4> grp; DevBuf<uint32_t> perm; DevBuf<float4> leaf; DevBuf<float4> rowb; DevBuf<u32x4> gfrag; DevBuf<float4> srowb; DevBuf<u32x4> sfrag;
-    uint32_t n_groups = 0, n_leaves = 0, n_super = 0;              // rows the matrix filter scans, leaf groups, super-rows
-};
-
-// What rt3_regroup* keeps per primitive class: the parts of every level above the LDS limit and of the level k_split_lds
-// starts from, as begins[0 .. n_parts] one after the other — they depend on the count alone — built with the first regroup of a scene size.
-struct RegroupPlan {
-    struct Level { uint32_t offset, n_parts; };
-    bool ready = false;
-    uint32_t n_reg = 0, n_region = 0, max_parts = 0;                // primitives in the split region, its positions (pads included), parts of the widest global level
-    size_t temp_bytes = 0;                                          // the radix sorts' temporary storage
-    std::vector<Level> levels;
-    DevBuf<uint32_t> table;
-};
-
-struct rt3_ctx {
-    int device = 0;
-    int num_cu = 0;
-    hipStream_t stream = nullptr;                                   // used by the synchronous entry points
-    std::string err;
-
-    // mesh
-    uint32_t n_faces = 0;
-    DevBuf<float4> d_tri, d_tri_mat, d_tri_bound; DevBuf<uint32_t> d_tri_kind; DevBuf<u32x4> d_tri_frag;
-    // merged entity buffers on the device (GFace[] / vec4[] as the reference keeps them), filled by rt3_mesh_*; their sizes bound rt3_mesh_put
-    DevBuf<rt3_gface> d_gfaces; DevBuf<float4> d_verts;
-    bool mesh_in_sync = false;                                      // d_gfaces / d_verts are what the committed faces were built from (rt3_motion reads them)
-    DevBuf<rt3_material> d_face_mats_in; DevBuf<uint32_t> d_error;
-    // spheres
-    uint32_t n_sph = 0;
-    DevBuf<float4> d_sph; DevBuf<uint32_t> d_sph_frag, d_sph_frag32; float sph_centre[3] = { 0.0f, 0.0f, 0.0f }; uint32_t n_direct = 0; uint32_t direct[4] = { 0, 0, 0, 0 }; float tri_centre[3] = { 0.0f, 0.0f, 0.0f }; DevBuf<uint32_t> d_box; DevBuf<u32x4> d_tri_frag_r; DevBuf<float> d_sph_invr; DevBuf<float4> d_sph_mat; DevBuf<uint32_t> d_sph_kind;
-
-    DevBuf<float4> d_sph_cr;                                        // (C, r) as the caller gave them, in the caller's order (rt3_motion compares and scales by them)
-    // what rt3_update_spheres* needs from the last rt3_set_spheres: every sphere's position in sph.grp (0xFFFFFFFF: a direct sphere), and whether
-    // a sphere was left out of the group order for a non-finite record (an update could make it finite again, and it has no slot)
-    DevBuf<uint32_t> d_sph_slot; bool sph_left_out = false;
-    // rt3_regroup*: the faces face_group_order put in the bounded part at commit; the plans; scratch (centres, ping-pong ids and keys, the
-    // parts' boxes, sort temporaries), grown by the first regroup of a scene size and kept
-    uint32_t tri_bounded = 0;
-    RegroupPlan rg_sph, rg_tri;
-    DevBuf<float4> d_rg_cen; DevBuf<uint32_t> d_rg_ids[2], d_rg_box; DevBuf<uint64_t> d_rg_keys[2]; DevBuf<uint8_t> d_rg_temp;
-    DevBuf<uint32_t> d_sb;                                          // rt3_set_*_device: the build's header and the compaction's block counts (rt3_scene_build.hpp)
-    bool update_error_pending = false;                              // a device-form rt3_update_mesh_device with faces: d_error is read by the next rt3_synchronize
-
-    // rows of the multi-level filter: faces and spheres, each in the order of a spatial median split
-    FilterRows tri, sph;
-    DevBuf<float4> d_tri_rec;                                       // the faces' records in group order (the exact test of the multi-level filter reads these)
-    DevBuf<uint32_t> d_strips;                                      // deferred member tests: kStripPairs pairs per wave of the grid
-    DevBuf<uint32_t> d_prim_masks;                                  // strip lists of the last k_trace_mfma32 render: [group of 64 owned pixels][row block]
-    // environment map (rt3_set_environment*): the context's copy, 6 faces of env_n x env_n float4 texels; env_n == 0: none.  Scene
-    // uploads, updates and regroups never touch it.
-    DevBuf<float4> d_env; uint32_t env_n = 0;
-    // ... and its sampling table (RT3_FLAG_ENV_SAMPLING): env_m cells per face edge, the cells' quantised weights and their inclusive
-    // prefix sums.  Built by the first call that carries the flag (ensure_env_table), kept until the map is set or cleared again (env_table = false).
-    DevBuf<uint32_t> d_env_q, d_env_wmax; DevBuf<unsigned long long> d_env_cdf; DevBuf<uint8_t> d_env_temp; uint32_t env_m = 0; bool env_table = false;
-    // the emitters' sampling table (RT3_FLAG_LIGHT_SAMPLING): one entry per primitive, faces first and then spheres in the caller's order,
-    // the entries' quantised weights and their inclusive prefix sums.  Built by the first call that carries the flag (ensure_light_table), kept until the
-    // scene changes: every upload, commit and update sets light_table = false; regroups and the environment calls do not.  d_env_wmax and d_env_temp
-    // (the largest weight, the scan's scratch) are shared with the map's table: both builds are queued behind the event chain.
-    DevBuf<uint32_t> d_light_q; DevBuf<unsigned long long> d_light_cdf; bool light_table = false;
-    // image textures (rt3_set_texture*, rt3_bind_*_textures*): the slots' own copies (w == 0: empty) and their descriptors on the device
-    // (d_tex_slots, RT3_TEX_MAX_TEXTURES of them, written behind the event chain); per class the binding in the caller's order and, on the host, the set
-    // of slots it names (one bit per slot) — all zero: the class has no binding, whatever d_*_tex still holds.  Uploads of a class clear its set
-    // (drop_*_binding); updates and regroups never touch any of this.
-    struct TexSlot { DevBuf<float4> texels; uint32_t w = 0, h = 0, wrap = 0; };
-    TexSlot tex[RT3_TEX_MAX_TEXTURES];
-    DevBuf<uint4> d_tex_slots; DevBuf<uint32_t> d_sph_tex, d_tri_tex, d_tex_check; DevBuf<float2> d_tri_uv;
-    uint32_t sph_tex_used[RT3_TEX_MAX_TEXTURES / 32] = {}, tri_tex_used[RT3_TEX_MAX_TEXTURES / 32] = {};
-
-    // work buffers
-    DevBuf<Rgb> d_rad;
-    DevBuf<float4> d_accum;
-    DevBuf<float4> d_accum_sq;                                      // RT3_FLAG_VARIANCE: per-pixel sums of squares
-    DevBuf<float4> d_arays;                                         // first-hit AOVs (rt3_render_aov*): one batch's camera rays and their hits,
-    DevBuf<uint4> d_ahits;                                          // and the per-pixel running sums (three planes; not d_accum, which belongs to
-    DevBuf<float4> d_aacc;                                          // the progressive render)
-    DevBuf<uint32_t> d_lens_keys;                                   // a shard's frame pixel indices (rt3_render_lens*: the keys of its rays)
-    DevBuf<float4> d_dn;                                            // denoiser scratch (rt3_denoise*): two (I, v) planes, the guide plane, the depth slopes
-    // the display transform's auto-exposure (rt3_display*): hist[512], dark, n and the gain's bits, allocated by the first call with the flag and
-    // zeroed at the start of each such call; display_auto: there has been one (rt3_debug_display_state)
-    DevBuf<uint32_t> d_display; bool display_auto = false;
-    // the bloom pyramid of rt3_display_sequence* (DESIGN.md 4.25): D_1 .. D_L one behind the other, grown on demand and kept after the call —
-    // plane 1 then holds U_1 of the bloom_w x bloom_h frame (bloom_levels != 0: there has been such a call); d_bloom_plane: rt3_debug_display_bloom's B
-    DevBuf<float4> d_bloom, d_bloom_plane; uint32_t bloom_w = 0, bloom_h = 0, bloom_levels = 0;
-    // The host forms' inputs and results on the device, each carved out at a float4 offset by staged().  Shared by all of them: each one ends in
-    // hipStreamSynchronize(ctx->stream), and no device form touches it.
-    DevBuf<float4> stage;
-    DevBuf<uint32_t> d_work;                                        // [0] work counter
-    DevBuf<unsigned long long> d_casts;
-    uint64_t rad_cap_bytes = 16ull << 30;
-    bool force_plain_mode_r = false;                                // tests: compare the two Mode-R kernels
-    bool force_brute = false;                                       // tests / fuzzers: unfiltered Mode-X kernel
-    bool force_flat = false;                                        // tests / A-B: one filter row per primitive (no groups)
-    uint64_t last_filter_rows = 0;                                  // rows the matrix filter scanned per ray cast in the last Mode-X render
-    bool last_filter_counted = false;                               // ... and the kernel counted the casts that took the filter itself (d_casts[16])
-    // the accumulation a progressive render continues (rt3_render_path_range): what it belongs to and how far it got
-    bool acc_valid = false; rt3_params acc_params{}; rt3_camera acc_cam{}; uint32_t acc_done = 0; uint32_t acc_npix = 0;
-    // adaptive sampling (rt3_render_path_adaptive*): the accumulation holds a different number of samples per pixel, d_counts[pix]; the two
-    // active lists (ping-pong), the rule's verdict per pixel, the compaction's block counts and, behind them, the length of the new list
-    bool acc_adaptive = false;
-    DevBuf<uint32_t> d_counts, d_active[2], d_block_counts; DevBuf<uint8_t> d_unconverged;
-    // launch configuration per (kernel, dynamic LDS): max dynamic LDS attribute set, workgroups per CU
-    std::map<std::pair<const void*, size_t>, int> occupancy;
-    std::set<int> peers_enabled;                                    // devices this context's device may already write to
-
-    // stats of the last render
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;              // per dominant-kernel launch
-    uint32_t ev_used = 0;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    hipEvent_t ev_acc = nullptr; bool ev_acc_recorded = false;      // end of the last Mode-X render: what the next user of d_rad / d_accum waits for
-    hipStream_t last_stream = nullptr;
-    uint64_t last_samples = 0;
-    bool last_was_path = false;
-    bool last_mfma16 = false;                                       // the last trace kernel was a tiled one (16x16x32 MFMAs)
-    bool rendered = false;
-    // what the render in flight will report once its last launch has been issued (committed only then)
-};
-
-#define RT3_HIP(call)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                               \
-            return RT3_E_DEVICE;                                                                        \
-        }                                                                                               \
-    } while (0)
-
-template <typename T>
-int DevBuf<T>::alloc(rt3_ctx* ctx, size_t n) {
-    reset();
-    if (n) RT3_HIP(hipMalloc((void**)&p_, n * sizeof(T)));
-    n_ = n;
-    return 0;
-}
-template <typename T>
-int DevBuf<T>::upload(rt3_ctx* ctx, const std::vector<T>& v) {
-    const int rc = alloc(ctx, v.size());
-    if (rc) return rc;
-    if (!v.empty()) RT3_HIP(hipMemcpy(p_, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
 namespace {
 
 thread_local std::string g_create_error;
-
-int fail(rt3_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
 
 CamDev cam_dev(const rt3_camera* c) {
     return CamDev{ c->origin[0], c->origin[1], c->origin[2], c->horizontal[0], c->horizontal[1], c->horizontal[2],
@@ -911,48 +740,6 @@ int issue_trace(rt3_ctx* ctx, const TraceArgs& A, const TracePlan& T, uint32_t n
     return 0;
 }
 
-// ---- What the entry points share.  rt3.h: a NULL stream is the context's own.
-hipStream_t stream_of(const rt3_ctx* ctx, void* stream_) { return stream_ ? (hipStream_t)stream_ : ctx->stream; }
-
-// d_rad, d_accum, the scratch and the counters belong to the context, not to a stream: whatever stream the previous call ran on, this one
-// starts behind it (a wait on the device; nothing if it is the same stream).  leave() marks where the next call starts.
-int enter(rt3_ctx* ctx, void* stream_, hipStream_t* stream) {
-    RT3_HIP(hipSetDevice(ctx->device));
-    *stream = stream_of(ctx, stream_);
-    if (ctx->ev_acc_recorded) RT3_HIP(hipStreamWaitEvent(*stream, ctx->ev_acc, 0));
-    return 0;
-}
-int leave(rt3_ctx* ctx, hipStream_t stream) {
-    RT3_HIP(hipEventRecord(ctx->ev_acc, stream));
-    ctx->ev_acc_recorded = true;
-    return 0;
-}
-
-// The round trip of a host form — the variant of an entry point that takes host pointers — through ctx->stage.  A StageSeg is one input or one result,
-// its host pointer and its bytes: a NULL pointer is an absent optional segment, an empty one (a shard that owns no pixel) is never copied.  staged() sizes
-// the buffer ONCE for all of them (DevBuf::ensure frees what it replaces: no segment can be added behind the first copy), queues the inputs' copies on
-// ctx->stream, calls device_form(d) — d[i]: segment i's 16-byte-aligned address, NULL for an absent one — then queues the results' copies and waits.
-struct StageSeg { const void* src; void* dst; size_t bytes; bool present; };
-StageSeg stage_in(const void* host, size_t bytes) { return { host, nullptr, bytes, host != nullptr }; }
-StageSeg stage_out(void* host, size_t bytes) { return { nullptr, host, bytes, host != nullptr }; }
-template <size_t N, class DeviceForm>
-int staged(rt3_ctx* ctx, const StageSeg (&seg)[N], DeviceForm device_form) {
-    RT3_HIP(hipSetDevice(ctx->device));
-    size_t first[N], quads = 0;
-    for (size_t i = 0; i < N; i++) { first[i] = quads; if (seg[i].present) quads += std::max<size_t>((seg[i].bytes + 15) / 16, 1); }
-    int rc;
-    if ((rc = ctx->stage.ensure(ctx, std::max<size_t>(quads, 1)))) return rc;
-    void* d[N];
-    for (size_t i = 0; i < N; i++) {
-        d[i] = seg[i].present ? ctx->stage.get() + first[i] : nullptr;
-        if (seg[i].src && seg[i].bytes) RT3_HIP(hipMemcpyAsync(d[i], seg[i].src, seg[i].bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if ((rc = device_form(d))) return rc;
-    for (size_t i = 0; i < N; i++)
-        if (seg[i].dst && seg[i].bytes) RT3_HIP(hipMemcpyAsync(seg[i].dst, d[i], seg[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
-    RT3_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
 // Samples per batch: as many of `count` as the sample storage cap holds at `bytes` per item and sample, and as keep the item index of a batch over
 // n items below 2^31 - 2^16.  0: not even one sample fits the index.
 uint32_t sample_batch(const rt3_ctx* ctx, uint32_t count, uint32_t n, size_t bytes) {
@@ -2447,324 +2234,6 @@ int rt3_accum_resolve(rt3_ctx* ctx, float* rgba) {
 }
 static_assert(sizeof(rt3_aov) == 48, "rt3.h: rt3_aov");
 
-// ---- The denoiser
-static int denoise_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* colour, const void* aov, const rt3_denoise_params* p,
-                          const void* out) {
-    if (!p) return fail(ctx, RT3_E_ARG, "p is NULL");
-    if (!colour || !aov || !out) return fail(ctx, RT3_E_ARG, "colour / aov / out is NULL");
-    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must have 1 .. 2^26 pixels");
-    if (p->iterations < 1 || p->iterations > 8) return fail(ctx, RT3_E_ARG, "iterations must be 1 .. 8");
-    if (p->normal_power < 1 || p->normal_power > 1024 || (p->normal_power & (p->normal_power - 1)))
-        return fail(ctx, RT3_E_ARG, "normal_power must be a power of two in 1 .. 1024");
-    if (!std::isfinite(p->sigma_luminance) || !(p->sigma_luminance > 0.0f) || !std::isfinite(p->sigma_depth) || !(p->sigma_depth > 0.0f))
-        return fail(ctx, RT3_E_ARG, "sigma_luminance and sigma_depth must be finite and > 0");
-    return 0;
-}
-
-// k_denoise_prepare -> k_denoise_moments -> k_denoise_atrous per pass, ping-ponging two (I, v) planes of the scratch; the last pass writes
-// d_out.  Scratch layout (float4 entries): [0, n) and [n, 2n) the (I, v) planes, [2n, 3n) the guide, then n floats of depth slope.
-int rt3_denoise_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_colour, const void* d_aov, const rt3_denoise_params* p, void* d_out,
-                       void* stream_) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = denoise_checks(ctx, w, h, d_colour, d_aov, p, d_out);
-    if (rc) return rc;
-    if (((uintptr_t)d_colour | (uintptr_t)d_aov | (uintptr_t)d_out) % 16u != 0)
-        return fail(ctx, RT3_E_ARG, "d_colour_rgba, d_aov and d_out_rgba must be 16-byte aligned");
-    const size_t npix = (size_t)w * h;
-    const uintptr_t o = (uintptr_t)d_out, oe = o + npix * sizeof(float4);
-    const uintptr_t c = (uintptr_t)d_colour, a = (uintptr_t)d_aov;
-    if ((o < c + npix * sizeof(float4) && c < oe) || (o < a + npix * sizeof(rt3_aov) && a < oe))
-        return fail(ctx, RT3_E_ARG, "d_out_rgba overlaps an input");
-    hipStream_t stream;
-    if ((rc = enter(ctx, stream_, &stream)) || (rc = ctx->d_dn.ensure(ctx, 3 * npix + (npix + 3) / 4))) return rc;     // the scratch is the context's
-    const DenoiseLaunch L{ w, h, p->iterations, p->normal_power, p->sigma_luminance, p->sigma_depth, d_colour, d_aov, d_out, ctx->d_dn };
-    RT3_HIP(denoise_launch(L, stream));
-    return leave(ctx, stream);
-}
-
-int rt3_denoise(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* colour, const rt3_aov* aov, const rt3_denoise_params* p, float* out) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = denoise_checks(ctx, w, h, colour, aov, p, out);
-    if (rc) return rc;
-    const size_t npix = (size_t)w * h;
-    return staged(ctx, { stage_in(colour, npix * sizeof(float4)), stage_in(aov, npix * sizeof(rt3_aov)), stage_out(out, npix * sizeof(float4)) },
-                  [&](void* const* d) { return rt3_denoise_device(ctx, w, h, d[0], d[1], p, d[2], ctx->stream); });
-}
-static_assert(sizeof(rt3_denoise_params) == 16, "rt3.h: rt3_denoise_params");
-
-// ---- The temporal denoiser
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
-// h x v, written out: (hy vz - hz vy, hz vx - hx vz, hx vy - hy vx)
-static void cross3(const float* h, const float* v, float* out) {
-    out[0] = h[1] * v[2] - h[2] * v[1];
-    out[1] = h[2] * v[0] - h[0] * v[2];
-    out[2] = h[0] * v[1] - h[1] * v[0];
-}
-
-static float dot3h(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-// A camera the reprojection can use: finite fields, horizontal x vertical != 0, and an image plane that misses the origin.
-static bool camera_ok(const rt3_camera* c) {
-    for (int i = 0; i < 3; i++)
-        if (!std::isfinite(c->origin[i]) || !std::isfinite(c->horizontal[i]) || !std::isfinite(c->vertical[i]) || !std::isfinite(c->lower_left_corner[i]))
-            return false;
-    float n[3], l[3];
-    cross3(c->horizontal, c->vertical, n);
-    if (n[0] == 0.0f && n[1] == 0.0f && n[2] == 0.0f) return false;
-    for (int i = 0; i < 3; i++) l[i] = c->lower_left_corner[i] - c->origin[i];
-    return dot3h(l, n) != 0.0f;
-}
-
-// What every form checks.  view / prev_view: the cameras, or the lenses (what = "cam" / "lens"); views_ok refuses them (0: fine).
-static int temporal_checks_of(rt3_ctx* ctx, uint32_t w, uint32_t h, const char* what, const void* view, const void* colour, const void* aov,
-                              const void* prev_view, const void* prev_history, const void* motion, const rt3_temporal_params* p,
-                              const void* out, const void* out_history, const std::function<int()>& views_ok) {
-    if (!p || !view) return fail(ctx, RT3_E_ARG, std::string("p / ") + what + " is NULL");
-    if (!colour || !aov || !out || !out_history) return fail(ctx, RT3_E_ARG, "colour / aov / out / out_history is NULL");
-    if (!prev_view != !prev_history) return fail(ctx, RT3_E_ARG, std::string("prev_") + what + " and prev_history must both be NULL or both be non-NULL");
-    if (w < 2 || h < 2 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must be at least 2 x 2 and have at most 2^26 pixels");
-    int rc = denoise_checks(ctx, w, h, colour, aov, &p->spatial, out);
-    if (rc) return rc;
-    if (!(p->alpha > 0.0f && p->alpha <= 1.0f) || !(p->moments_alpha > 0.0f && p->moments_alpha <= 1.0f))
-        return fail(ctx, RT3_E_ARG, "alpha and moments_alpha must be in (0, 1]");
-    if (!std::isfinite(p->depth_tolerance) || !(p->depth_tolerance > 0.0f)) return fail(ctx, RT3_E_ARG, "depth_tolerance must be finite and > 0");
-    if (!(p->normal_tolerance >= -1.0f && p->normal_tolerance <= 1.0f)) return fail(ctx, RT3_E_ARG, "normal_tolerance must be in [-1, 1]");
-    if ((rc = views_ok())) return rc;
-    const size_t npix = (size_t)w * h, nf = npix * sizeof(float4), nh = npix * sizeof(rt3_history);
-    const struct { const void* ptr; size_t n; } in[4] = { { colour, nf }, { aov, npix * sizeof(rt3_aov) }, { prev_history, nh }, { motion, nf } };
-    for (const auto& i : in)
-        if (i.ptr && (ranges_overlap(out, nf, i.ptr, i.n) || ranges_overlap(out_history, nh, i.ptr, i.n)))
-            return fail(ctx, RT3_E_ARG, "an output overlaps an input");
-    if (ranges_overlap(out, nf, out_history, nh)) return fail(ctx, RT3_E_ARG, "out_rgba and out_history overlap");
-    return 0;
-}
-
-static int temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* colour, const void* aov,
-                           const rt3_camera* prev_cam, const void* prev_history, const void* motion, const rt3_temporal_params* p,
-                           const void* out, const void* out_history) {
-    return temporal_checks_of(ctx, w, h, "cam", cam, colour, aov, prev_cam, prev_history, motion, p, out, out_history, [&]() {
-        if (!camera_ok(cam) || (prev_cam && !camera_ok(prev_cam)))
-            return fail(ctx, RT3_E_ARG, "a camera has a non-finite field, horizontal x vertical = 0, or an image plane through its origin");
-        return 0;
-    });
-}
-
-// k_temporal_reproject -> k_denoise_moments<true> -> the passes (pass 0 also writes the history colour); the same scratch as rt3_denoise.
-// The projection constants of DESIGN.md 4.12 step 3, in f32 in this order: L = llc' - o', n = h x v, a_u = (v x n) / (h . (v x n)),
-// a_v = (n x h) / (v . (n x h)) component by component, then L . n.
-// d_motion: the plane rt3_motion wrote, or NULL; without a previous frame it is checked and not read.
-int rt3_denoise_temporal_motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_colour, const void* d_aov,
-                                       const rt3_camera* prev_cam, const void* d_prev_history, const void* d_motion,
-                                       const rt3_temporal_params* p, void* d_out, void* d_out_history, void* stream_) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = temporal_checks(ctx, w, h, cam, d_colour, d_aov, prev_cam, d_prev_history, d_motion, p, d_out, d_out_history);
-    if (rc) return rc;
-    if (((uintptr_t)d_colour | (uintptr_t)d_aov | (uintptr_t)d_prev_history | (uintptr_t)d_motion | (uintptr_t)d_out | (uintptr_t)d_out_history) % 16u != 0)
-        return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
-    const size_t npix = (size_t)w * h;
-    TemporalLaunch T{};
-    T.base = DenoiseLaunch{ w, h, p->spatial.iterations, p->spatial.normal_power, p->spatial.sigma_luminance, p->spatial.sigma_depth,
-                            d_colour, d_aov, d_out, nullptr };
-    std::memcpy(T.cam, cam, sizeof(rt3_camera));
-    if (prev_cam) {
-        const float* hh = prev_cam->horizontal;
-        const float* vv = prev_cam->vertical;
-        float vn[3], nh[3];
-        for (int i = 0; i < 3; i++) { T.prev_o[i] = prev_cam->origin[i]; T.prev_l[i] = prev_cam->lower_left_corner[i] - prev_cam->origin[i]; }
-        cross3(hh, vv, T.prev_n);
-        cross3(vv, T.prev_n, vn);
-        const float du = dot3h(hh, vn);
-        for (int i = 0; i < 3; i++) T.a_u[i] = vn[i] / du;
-        cross3(T.prev_n, hh, nh);
-        const float dv = dot3h(vv, nh);
-        for (int i = 0; i < 3; i++) T.a_v[i] = nh[i] / dv;
-        T.ln = dot3h(T.prev_l, T.prev_n);
-        T.has_prev = 1;
-        T.same_cam = std::memcmp(prev_cam, cam, sizeof(rt3_camera)) == 0;
-    }
-    T.alpha = p->alpha; T.moments_alpha = p->moments_alpha; T.depth_tolerance = p->depth_tolerance; T.normal_tolerance = p->normal_tolerance;
-    T.prev_history = d_prev_history;
-    T.out_history = d_out_history;
-    T.motion = prev_cam ? d_motion : nullptr;
-    hipStream_t stream;
-    if ((rc = enter(ctx, stream_, &stream)) || (rc = ctx->d_dn.ensure(ctx, 3 * npix + (npix + 3) / 4))) return rc;     // the scratch is the context's
-    T.base.scratch = ctx->d_dn;
-    RT3_HIP(temporal_launch(T, stream));
-    return leave(ctx, stream);
-}
-
-int rt3_denoise_temporal_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_colour, const void* d_aov,
-                                const rt3_camera* prev_cam, const void* d_prev_history, const rt3_temporal_params* p, void* d_out,
-                                void* d_out_history, void* stream_) {
-    return rt3_denoise_temporal_motion_device(ctx, w, h, cam, d_colour, d_aov, prev_cam, d_prev_history, nullptr, p, d_out, d_out_history, stream_);
-}
-
-int rt3_denoise_temporal_motion(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
-                                const rt3_camera* prev_cam, const rt3_history* prev_history, const float* motion,
-                                const rt3_temporal_params* p, float* out, rt3_history* out_history) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = temporal_checks(ctx, w, h, cam, colour, aov, prev_cam, prev_history, motion, p, out, out_history);
-    if (rc) return rc;
-    const size_t npix = (size_t)w * h;
-    return staged(ctx, { stage_in(colour, npix * sizeof(float4)), stage_in(aov, npix * sizeof(rt3_aov)),
-                         stage_in(prev_history, npix * sizeof(rt3_history)), stage_in(motion, npix * sizeof(float4)),
-                         stage_out(out, npix * sizeof(float4)), stage_out(out_history, npix * sizeof(rt3_history)) },
-                  [&](void* const* d) { return rt3_denoise_temporal_motion_device(ctx, w, h, cam, d[0], d[1], prev_cam, d[2], d[3], p, d[4], d[5], ctx->stream); });
-}
-
-int rt3_denoise_temporal(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const float* colour, const rt3_aov* aov,
-                         const rt3_camera* prev_cam, const rt3_history* prev_history, const rt3_temporal_params* p, float* out,
-                         rt3_history* out_history) {
-    return rt3_denoise_temporal_motion(ctx, w, h, cam, colour, aov, prev_cam, prev_history, nullptr, p, out, out_history);
-}
-static_assert(sizeof(rt3_history) == 48, "rt3.h: rt3_history");
-static_assert(sizeof(rt3_temporal_params) == 32, "rt3.h: rt3_temporal_params");
-
-// ---- The motion plane
-// What both forms check: the frame, the camera, and the previous arrays against the scene on the context.
-// cam or lens: the frame's view, exactly one of them.
-static int motion_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_lens* lens, const void* aov, const void* prev_sph,
-                         uint32_t n_prev_sph, const void* prev_verts, uint32_t n_prev_verts, const void* out) {
-    if ((!cam && !lens) || !aov || !out) return fail(ctx, RT3_E_ARG, "cam / lens / aov / out_motion is NULL");
-    if (w < 2 || h < 2 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must be at least 2 x 2 and have at most 2^26 pixels");
-    if (cam && !camera_ok(cam))
-        return fail(ctx, RT3_E_ARG, "the camera has a non-finite field, horizontal x vertical = 0, or an image plane through its origin");
-    if (lens)
-        if (const char* why = rt3lens::refusal(lens, w, h)) return fail(ctx, RT3_E_ARG, why);
-    if ((!prev_sph && n_prev_sph) || (!prev_verts && n_prev_verts)) return fail(ctx, RT3_E_ARG, "a NULL previous array must have a count of 0");
-    if (prev_sph && ctx->n_sph == 0) return fail(ctx, RT3_E_STATE, "previous spheres were given, but the context has no spheres");
-    if (prev_verts && ctx->n_faces == 0) return fail(ctx, RT3_E_STATE, "previous vertices were given, but the context has no committed mesh");
-    if (prev_verts && !ctx->mesh_in_sync)
-        return fail(ctx, RT3_E_STATE, "the merged entity buffers were changed after the last rt3_mesh_commit (rt3_mesh_begin / rt3_mesh_put without a commit)");
-    if (prev_sph && n_prev_sph != ctx->n_sph) return fail(ctx, RT3_E_ARG, "n_prev_spheres must equal the context's sphere count");
-    if (prev_verts && n_prev_verts != ctx->d_verts.size()) return fail(ctx, RT3_E_ARG, "n_prev_vertices must equal the vertex count of the merged entity buffers");
-    const size_t npix = (size_t)w * h, no = npix * sizeof(float4);
-    const struct { const void* ptr; size_t n; } in[3] = { { aov, npix * sizeof(rt3_aov) }, { prev_sph, (size_t)n_prev_sph * sizeof(float4) },
-                                                          { prev_verts, (size_t)n_prev_verts * sizeof(float4) } };
-    for (const auto& i : in)
-        if (i.ptr && ranges_overlap(out, no, i.ptr, i.n)) return fail(ctx, RT3_E_ARG, "out_motion overlaps an input");
-    return 0;
-}
-
-// The device form for either view (cam or lens, exactly one).
-static int motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_lens* lens, const void* d_aov, const void* d_prev_sph,
-                         uint32_t n_prev_sph, const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
-    int rc = motion_checks(ctx, w, h, cam, lens, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out);
-    if (rc) return rc;
-    if (((uintptr_t)d_aov | (uintptr_t)d_prev_sph | (uintptr_t)d_prev_verts | (uintptr_t)d_out) % 16u != 0)
-        return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
-    MotionLaunch L{};
-    L.width = w; L.height = h;
-    if (cam) std::memcpy(L.cam, cam, sizeof(rt3_camera));
-    L.lens = lens;
-    L.aov = d_aov;
-    // a class without a previous array is never gathered: its buffers and counts stay out of the launch
-    if (d_prev_sph) { L.sph = ctx->d_sph_cr; L.sph_invr = ctx->d_sph_invr; L.prev_sph = d_prev_sph; L.n_sph = ctx->n_sph; }
-    if (d_prev_verts) {
-        L.gfaces = ctx->d_gfaces; L.verts = ctx->d_verts; L.prev_verts = d_prev_verts;
-        L.n_faces = ctx->n_faces; L.n_verts = (uint32_t)ctx->d_verts.size();
-    }
-    L.out = d_out;
-    hipStream_t stream;
-    if ((rc = enter(ctx, stream_, &stream))) return rc;
-    RT3_HIP(motion_launch(L, stream));
-    return leave(ctx, stream);
-}
-
-int rt3_motion_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const void* d_aov, const void* d_prev_sph, uint32_t n_prev_sph,
-                      const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
-    if (!ctx) return RT3_E_ARG;
-    return motion_device(ctx, w, h, cam, nullptr, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out, stream_);
-}
-
-int rt3_motion(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_camera* cam, const rt3_aov* aov, const float* prev_sph, uint32_t n_prev_sph,
-               const float* prev_verts, uint32_t n_prev_verts, float* out) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = motion_checks(ctx, w, h, cam, nullptr, aov, prev_sph, n_prev_sph, prev_verts, n_prev_verts, out);
-    if (rc) return rc;
-    const size_t npix = (size_t)w * h;
-    return staged(ctx, { stage_in(aov, npix * sizeof(rt3_aov)), stage_in(prev_sph, (size_t)n_prev_sph * sizeof(float4)),
-                     stage_in(prev_verts, (size_t)n_prev_verts * sizeof(float4)), stage_out(out, npix * sizeof(float4)) },
-                  [&](void* const* d) { return rt3_motion_device(ctx, w, h, cam, d[0], d[1], n_prev_sph, d[2], n_prev_verts, d[3], ctx->stream); });
-}
-
-// ---- Lens sequences: the two calls above for a frame rendered through a lens.  The lens forms of k_temporal_reproject and
-// k_motion take the lenses by value; nothing is worked out here but the checks.
-static int optic_temporal_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const void* colour, const void* aov,
-                                 const rt3_lens* prev_lens, const void* prev_history, const void* motion, const rt3_temporal_params* p,
-                                 const void* out, const void* out_history) {
-    return temporal_checks_of(ctx, w, h, "lens", lens, colour, aov, prev_lens, prev_history, motion, p, out, out_history, [&]() {
-        if (const char* why = rt3lens::refusal(lens, w, h)) return fail(ctx, RT3_E_ARG, why);
-        if (prev_lens) {
-            if (const char* why = rt3lens::refusal(prev_lens, w, h)) return fail(ctx, RT3_E_ARG, std::string("prev_") + why);
-            if (prev_lens->model != lens->model) return fail(ctx, RT3_E_ARG, "prev_lens must have the model of lens");
-        }
-        return 0;
-    });
-}
-
-int rt3_denoise_temporal_optic_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const void* d_colour, const void* d_aov,
-                                      const rt3_lens* prev_lens, const void* d_prev_history, const void* d_motion,
-                                      const rt3_temporal_params* p, void* d_out, void* d_out_history, void* stream_) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = optic_temporal_checks(ctx, w, h, lens, d_colour, d_aov, prev_lens, d_prev_history, d_motion, p, d_out, d_out_history);
-    if (rc) return rc;
-    if (((uintptr_t)d_colour | (uintptr_t)d_aov | (uintptr_t)d_prev_history | (uintptr_t)d_motion | (uintptr_t)d_out | (uintptr_t)d_out_history) % 16u != 0)
-        return fail(ctx, RT3_E_ARG, "device buffers must be 16-byte aligned");
-    const size_t npix = (size_t)w * h;
-    TemporalLaunch T{};
-    T.base = DenoiseLaunch{ w, h, p->spatial.iterations, p->spatial.normal_power, p->spatial.sigma_luminance, p->spatial.sigma_depth,
-                            d_colour, d_aov, d_out, nullptr };
-    T.lens = lens;
-    T.prev_lens = prev_lens;
-    T.has_prev = prev_lens ? 1u : 0u;
-    T.alpha = p->alpha; T.moments_alpha = p->moments_alpha; T.depth_tolerance = p->depth_tolerance; T.normal_tolerance = p->normal_tolerance;
-    T.prev_history = d_prev_history;
-    T.out_history = d_out_history;
-    T.motion = prev_lens ? d_motion : nullptr;
-    hipStream_t stream;
-    if ((rc = enter(ctx, stream_, &stream)) || (rc = ctx->d_dn.ensure(ctx, 3 * npix + (npix + 3) / 4))) return rc;     // the scratch is the context's
-    T.base.scratch = ctx->d_dn;
-    RT3_HIP(temporal_launch(T, stream));
-    return leave(ctx, stream);
-}
-
-int rt3_denoise_temporal_optic(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const float* colour, const rt3_aov* aov,
-                               const rt3_lens* prev_lens, const rt3_history* prev_history, const float* motion,
-                               const rt3_temporal_params* p, float* out, rt3_history* out_history) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = optic_temporal_checks(ctx, w, h, lens, colour, aov, prev_lens, prev_history, motion, p, out, out_history);
-    if (rc) return rc;
-    const size_t npix = (size_t)w * h;
-    return staged(ctx, { stage_in(colour, npix * sizeof(float4)), stage_in(aov, npix * sizeof(rt3_aov)),
-                         stage_in(prev_history, npix * sizeof(rt3_history)), stage_in(motion, npix * sizeof(float4)),
-                         stage_out(out, npix * sizeof(float4)), stage_out(out_history, npix * sizeof(rt3_history)) },
-                  [&](void* const* d) { return rt3_denoise_temporal_optic_device(ctx, w, h, lens, d[0], d[1], prev_lens, d[2], d[3], p, d[4], d[5], ctx->stream); });
-}
-
-int rt3_motion_optic_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const void* d_aov, const void* d_prev_sph, uint32_t n_prev_sph,
-                            const void* d_prev_verts, uint32_t n_prev_verts, void* d_out, void* stream_) {
-    if (!ctx) return RT3_E_ARG;
-    if (!lens) return fail(ctx, RT3_E_ARG, "lens / aov / out_motion is NULL");
-    return motion_device(ctx, w, h, nullptr, lens, d_aov, d_prev_sph, n_prev_sph, d_prev_verts, n_prev_verts, d_out, stream_);
-}
-
-int rt3_motion_optic(rt3_ctx* ctx, uint32_t w, uint32_t h, const rt3_lens* lens, const rt3_aov* aov, const float* prev_sph, uint32_t n_prev_sph,
-                     const float* prev_verts, uint32_t n_prev_verts, float* out) {
-    if (!ctx) return RT3_E_ARG;
-    if (!lens) return fail(ctx, RT3_E_ARG, "lens / aov / out_motion is NULL");
-    int rc = motion_checks(ctx, w, h, nullptr, lens, aov, prev_sph, n_prev_sph, prev_verts, n_prev_verts, out);
-    if (rc) return rc;
-    const size_t npix = (size_t)w * h;
-    return staged(ctx, { stage_in(aov, npix * sizeof(rt3_aov)), stage_in(prev_sph, (size_t)n_prev_sph * sizeof(float4)),
-                     stage_in(prev_verts, (size_t)n_prev_verts * sizeof(float4)), stage_out(out, npix * sizeof(float4)) },
-                  [&](void* const* d) { return rt3_motion_optic_device(ctx, w, h, lens, d[0], d[1], n_prev_sph, d[2], n_prev_verts, d[3], ctx->stream); });
-}
-
 // ---- Radiance along caller-supplied rays: the rays form of the kernel a query would take on the scene, over the items
 // (sample in batch, ray), through radiance_pass with the caller's rays and the caller's output as the sum buffer.
 static_assert(sizeof(rt3_radiance_params) == 24, "rt3.h: rt3_radiance_params");
@@ -3236,138 +2705,6 @@ int rt3_debug_light_table(rt3_ctx* ctx, uint32_t* q_out, uint64_t* cdf_out, uint
     *n_entries = (uint32_t)n;
     if (capacity < n) return fail(ctx, RT3_E_ARG, "capacity is smaller than the table (one entry per face and per sphere)");
     return download_table(ctx, ensure_light_table, ctx->d_light_q, ctx->d_light_cdf, n, q_out, cdf_out);
-}
-
-// ---- The display transform
-static int display_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* rgba, const rt3_display_params* p, const void* out) {
-    if (!p) return fail(ctx, RT3_E_ARG, "p is NULL");
-    if (!rgba || !out) return fail(ctx, RT3_E_ARG, "rgba / out_pixels is NULL");
-    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must have 1 .. 2^26 pixels");
-    if (const char* why = rt3disp::refusal(*p)) return fail(ctx, RT3_E_ARG, why);
-    const size_t npix = (size_t)w * h;
-    if (ranges_overlap(out, npix * sizeof(uint32_t), rgba, npix * sizeof(float4))) return fail(ctx, RT3_E_ARG, "out_pixels overlaps rgba");
-    return 0;
-}
-
-// Without the flag one launch, k_display_map with the uniform gain; with it the state zeroed on the stream, k_display_histogram, k_display_gain and
-// k_display_map reading the gain where k_display_gain left it.  Nothing here waits for the device, and nothing is timed: rt3_get_stats stays as it was.
-int rt3_display_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_rgba, const rt3_display_params* p, void* d_out, void* stream_) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = display_checks(ctx, w, h, d_rgba, p, d_out);
-    if (rc) return rc;
-    if ((uintptr_t)d_rgba % 16u != 0 || (uintptr_t)d_out % 4u != 0) return fail(ctx, RT3_E_ARG, "d_rgba must be 16-byte and d_out_pixels 4-byte aligned");
-    const bool auto_exposure = (p->flags & RT3_DISPLAY_AUTO_EXPOSURE) != 0;
-    hipStream_t stream;
-    if ((rc = enter(ctx, stream_, &stream))) return rc;
-    if (auto_exposure && (rc = ctx->d_display.ensure(ctx, rt3disp::kStateWords))) return rc;      // (the state is the context's: the first such call allocates it)
-    const DisplayLaunch L{ w * h, p->curve, p->transfer, auto_exposure, p->trim_low, p->trim_high, p->exposure, p->key, p->white, d_rgba, d_out,
-                           auto_exposure ? ctx->d_display.get() : nullptr };
-    RT3_HIP(display_launch(L, stream));
-    if (auto_exposure) ctx->display_auto = true;
-    return leave(ctx, stream);
-}
-
-int rt3_display(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* rgba, const rt3_display_params* p, uint32_t* out) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = display_checks(ctx, w, h, rgba, p, out);
-    if (rc) return rc;
-    const size_t npix = (size_t)w * h;
-    return staged(ctx, { stage_in(rgba, npix * sizeof(float4)), stage_out(out, npix * sizeof(uint32_t)) },
-                  [&](void* const* d) { return rt3_display_device(ctx, w, h, d[0], p, d[1], ctx->stream); });
-}
-
-int rt3_debug_display_state(rt3_ctx* ctx, uint32_t hist[512], uint32_t* dark, float* gain) {
-    if (!ctx) return RT3_E_ARG;
-    if (!ctx->display_auto) return fail(ctx, RT3_E_STATE, "no call with RT3_DISPLAY_AUTO_EXPOSURE on this context");
-    uint32_t state[rt3disp::kStateWords];
-    hipStream_t stream;
-    int rc;
-    if ((rc = enter(ctx, nullptr, &stream))) return rc;            // behind the call that wrote the state, whatever stream it ran on
-    RT3_HIP(hipMemcpyAsync(state, ctx->d_display.get(), sizeof state, hipMemcpyDeviceToHost, stream));
-    if ((rc = leave(ctx, stream))) return rc;
-    RT3_HIP(hipStreamSynchronize(stream));
-    if (hist) std::memcpy(hist, state, rt3disp::kBins * sizeof(uint32_t));
-    if (dark) *dark = state[rt3disp::kBins];
-    if (gain) *gain = rt3disp::float_of(state[rt3disp::kBins + 2]);
-    return 0;
-}
-
-// ---- Display sequences
-static int display_sequence_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* rgba, const rt3_display_sequence_params* p, const void* prev,
-                                   const void* out_exposure, const void* out) {
-    if (!p) return fail(ctx, RT3_E_ARG, "p is NULL");
-    if (!rgba || !out) return fail(ctx, RT3_E_ARG, "rgba / out_pixels is NULL");
-    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must have 1 .. 2^26 pixels");
-    if (const char* why = rt3dseq::refusal(*p)) return fail(ctx, RT3_E_ARG, why);
-    if (prev && !(p->display.flags & RT3_DISPLAY_AUTO_EXPOSURE)) return fail(ctx, RT3_E_ARG, "prev_exposure needs RT3_DISPLAY_AUTO_EXPOSURE");
-    const size_t npix = (size_t)w * h;
-    const struct { const void* at; size_t bytes; } buf[4] = { { rgba, npix * sizeof(float4) }, { out, npix * sizeof(uint32_t) },
-                                                              { prev, sizeof(rt3_exposure) }, { out_exposure, sizeof(rt3_exposure) } };
-    for (int a = 0; a < 4; a++)
-        for (int b = a + 1; b < 4; b++) {
-            if (!buf[a].at || !buf[b].at || (a == 2 && buf[a].at == buf[b].at)) continue;      // prev == out_exposure: one record serves a sequence
-            if (ranges_overlap(buf[a].at, buf[a].bytes, buf[b].at, buf[b].bytes)) return fail(ctx, RT3_E_ARG, "rgba, out_pixels and the exposure records must not overlap (prev_exposure == out_exposure apart)");
-        }
-    return 0;
-}
-
-// rt3_display_device's launches with k_display_gain_step in k_display_gain's place, and with bloom the pyramid's 2 L - 1 launches in front of a map that
-// composites.  Nothing here waits for the device, and nothing is timed: rt3_get_stats stays as it was.
-int rt3_display_sequence_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_rgba, const rt3_display_sequence_params* p, const void* d_prev,
-                                void* d_out_exposure, void* d_out, void* stream_) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = display_sequence_checks(ctx, w, h, d_rgba, p, d_prev, d_out_exposure, d_out);
-    if (rc) return rc;
-    if ((uintptr_t)d_rgba % 16u != 0 || (uintptr_t)d_out % 4u != 0 || (uintptr_t)d_prev % 4u != 0 || (uintptr_t)d_out_exposure % 4u != 0)
-        return fail(ctx, RT3_E_ARG, "d_rgba must be 16-byte, d_out_pixels and the exposure records 4-byte aligned");
-    const rt3_display_params& d = p->display;
-    const bool auto_exposure = (d.flags & RT3_DISPLAY_AUTO_EXPOSURE) != 0;
-    hipStream_t stream;
-    if ((rc = enter(ctx, stream_, &stream))) return rc;
-    if (auto_exposure && (rc = ctx->d_display.ensure(ctx, rt3disp::kStateWords))) return rc;
-    if (p->bloom_levels && (rc = ctx->d_bloom.ensure(ctx, rt3dseq::pyramid_texels(w, h, p->bloom_levels)))) return rc;
-    const DisplaySequenceLaunch S{ { w * h, d.curve, d.transfer, auto_exposure, d.trim_low, d.trim_high, d.exposure, d.key, d.white, d_rgba, d_out,
-                                     auto_exposure ? ctx->d_display.get() : nullptr },
-                                   w, h, p->adapt_brighter, p->adapt_darker, p->bloom_levels, p->bloom_threshold, p->bloom_intensity,
-                                   (const rt3_exposure*)d_prev, (rt3_exposure*)d_out_exposure, p->bloom_levels ? ctx->d_bloom.get() : nullptr };
-    RT3_HIP(display_sequence_launch(S, stream));
-    if (auto_exposure) ctx->display_auto = true;
-    if (p->bloom_levels) { ctx->bloom_w = w; ctx->bloom_h = h; ctx->bloom_levels = p->bloom_levels; }
-    return leave(ctx, stream);
-}
-
-int rt3_display_sequence(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* rgba, const rt3_display_sequence_params* p, const rt3_exposure* prev,
-                         rt3_exposure* out_exposure, uint32_t* out) {
-    if (!ctx) return RT3_E_ARG;
-    int rc = display_sequence_checks(ctx, w, h, rgba, p, prev, out_exposure, out);
-    if (rc) return rc;
-    if (prev && prev->level > rt3dseq::kMaxLevel) return fail(ctx, RT3_E_ARG, "prev_exposure->level is above 511 << 19");
-    const size_t npix = (size_t)w * h;
-    return staged(ctx, { stage_in(rgba, npix * sizeof(float4)), stage_in(prev, sizeof(rt3_exposure)), stage_out(out_exposure, sizeof(rt3_exposure)),
-                         stage_out(out, npix * sizeof(uint32_t)) },
-                  [&](void* const* d) { return rt3_display_sequence_device(ctx, w, h, d[0], p, d[1], d[2], d[3], ctx->stream); });
-}
-
-int rt3_debug_display_bloom(rt3_ctx* ctx, float* out_u1, float* out_bloom, uint64_t capacity_pixels, uint32_t* w_out, uint32_t* h_out) {
-    if (!ctx) return RT3_E_ARG;
-    if (!w_out || !h_out) return fail(ctx, RT3_E_ARG, "w / h is NULL");
-    if (ctx->bloom_levels == 0) return fail(ctx, RT3_E_STATE, "no rt3_display_sequence call with bloom_levels >= 1 on this context");
-    const uint32_t w = ctx->bloom_w, h = ctx->bloom_h, w1 = rt3dseq::half_of(w), h1 = rt3dseq::half_of(h);
-    const size_t npix = (size_t)w * h;
-    *w_out = w; *h_out = h;
-    if (capacity_pixels < npix) return fail(ctx, RT3_E_ARG, "capacity_pixels is smaller than the frame of the last bloom call");
-    hipStream_t stream;
-    int rc;
-    if ((rc = enter(ctx, nullptr, &stream))) return rc;            // behind the call that wrote the pyramid, whatever stream it ran on
-    if (out_u1) RT3_HIP(hipMemcpyAsync(out_u1, ctx->d_bloom.get(), (size_t)w1 * h1 * sizeof(float4), hipMemcpyDeviceToHost, stream));
-    if (out_bloom) {
-        if ((rc = ctx->d_bloom_plane.ensure(ctx, npix))) return rc;
-        RT3_HIP(bloom_plane_launch(ctx->d_bloom.get(), w1, h1, ctx->d_bloom_plane.get(), w, h, ctx->bloom_levels, stream));
-        RT3_HIP(hipMemcpyAsync(out_bloom, ctx->d_bloom_plane.get(), npix * sizeof(float4), hipMemcpyDeviceToHost, stream));
-    }
-    if ((rc = leave(ctx, stream))) return rc;
-    RT3_HIP(hipStreamSynchronize(stream));
-    return 0;
 }
 
 int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {

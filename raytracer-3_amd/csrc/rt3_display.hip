@@ -2,12 +2,14 @@
 // frame's trimmed log-average luminance), a tone curve, a transfer function.  A streaming pass: 16 bytes in and 4 out per pixel, 16 more in with
 // auto-exposure.  The law itself is rt3_display_law.hpp, shared with the host restatement; the auto-exposure adds up integers only (LDS and global
 // integer atomics), so the gain does not depend on the order the pixels arrive in and tests/display_ref.py reproduces every word.
-// A translation unit of its own (gfx950 only), as rt3_denoise.hip is: the kernels share nothing with the render path.  rt3_device.hip checks the
-// arguments, owns the state and calls display_launch().
+// A translation unit of its own (gfx950 only), as rt3_denoise.hip is: the kernels share nothing with the render path.  The entry points are below
+// the kernels: they check the arguments, take the state from the context (rt3_ctx.hpp) and launch.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 
+#include "rt3_ctx.hpp"
 #include "rt3_display_law.hpp"
 #include "rt3_display.hpp"
 
@@ -133,12 +135,64 @@ hipError_t display_map_launch(const DisplayLaunch& L, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t display_launch(const DisplayLaunch& L, hipStream_t stream) {
-    hipError_t e;
-    if (L.auto_exposure) {
-        if ((e = display_histogram_launch(L, stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_display_gain, dim3(1), dim3(kBins), 0, stream, L.state, L.trim_low, L.trim_high, L.exposure, L.key);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return display_map_launch(L, stream);
+// ---- The entry points (rt3.h)
+static int display_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* rgba, const rt3_display_params* p, const void* out) {
+    if (!p) return fail(ctx, RT3_E_ARG, "p is NULL");
+    if (!rgba || !out) return fail(ctx, RT3_E_ARG, "rgba / out_pixels is NULL");
+    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must have 1 .. 2^26 pixels");
+    if (const char* why = rt3disp::refusal(*p)) return fail(ctx, RT3_E_ARG, why);
+    const size_t npix = (size_t)w * h;
+    if (ranges_overlap(out, npix * sizeof(uint32_t), rgba, npix * sizeof(float4))) return fail(ctx, RT3_E_ARG, "out_pixels overlaps rgba");
+    return 0;
 }
+
+extern "C" {
+
+// Without the flag one launch, k_display_map with the uniform gain; with it the state zeroed on the stream, k_display_histogram, k_display_gain and
+// k_display_map reading the gain where k_display_gain left it.  Nothing here waits for the device, and nothing is timed: rt3_get_stats stays as it was.
+int rt3_display_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_rgba, const rt3_display_params* p, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = display_checks(ctx, w, h, d_rgba, p, d_out);
+    if (rc) return rc;
+    if ((uintptr_t)d_rgba % 16u != 0 || (uintptr_t)d_out % 4u != 0) return fail(ctx, RT3_E_ARG, "d_rgba must be 16-byte and d_out_pixels 4-byte aligned");
+    const bool auto_exposure = (p->flags & RT3_DISPLAY_AUTO_EXPOSURE) != 0;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    if (auto_exposure && (rc = ctx->d_display.ensure(ctx, kStateWords))) return rc;      // (the state is the context's: the first such call allocates it)
+    const DisplayLaunch L{ w * h, p->curve, p->transfer, auto_exposure, p->exposure, p->white, d_rgba, d_out, auto_exposure ? ctx->d_display.get() : nullptr };
+    if (auto_exposure) {
+        RT3_HIP(display_histogram_launch(L, stream));
+        hipLaunchKernelGGL(k_display_gain, dim3(1), dim3(kBins), 0, stream, L.state, p->trim_low, p->trim_high, p->exposure, p->key);
+        RT3_HIP(hipGetLastError());
+    }
+    RT3_HIP(display_map_launch(L, stream));
+    if (auto_exposure) ctx->display_auto = true;
+    return leave(ctx, stream);
+}
+
+int rt3_display(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* rgba, const rt3_display_params* p, uint32_t* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = display_checks(ctx, w, h, rgba, p, out);
+    if (rc) return rc;
+    const size_t npix = (size_t)w * h;
+    return staged(ctx, { stage_in(rgba, npix * sizeof(float4)), stage_out(out, npix * sizeof(uint32_t)) },
+                  [&](void* const* d) { return rt3_display_device(ctx, w, h, d[0], p, d[1], ctx->stream); });
+}
+
+int rt3_debug_display_state(rt3_ctx* ctx, uint32_t hist[512], uint32_t* dark, float* gain) {
+    if (!ctx) return RT3_E_ARG;
+    if (!ctx->display_auto) return fail(ctx, RT3_E_STATE, "no call with RT3_DISPLAY_AUTO_EXPOSURE on this context");
+    uint32_t state[kStateWords];
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, nullptr, &stream))) return rc;            // behind the call that wrote the state, whatever stream it ran on
+    RT3_HIP(hipMemcpyAsync(state, ctx->d_display.get(), sizeof state, hipMemcpyDeviceToHost, stream));
+    if ((rc = leave(ctx, stream))) return rc;
+    RT3_HIP(hipStreamSynchronize(stream));
+    if (hist) std::memcpy(hist, state, kBins * sizeof(uint32_t));
+    if (dark) *dark = state[kDarkSlot];
+    if (gain) *gain = float_of(state[kGainSlot]);
+    return 0;
+}
+
+}  // extern "C"

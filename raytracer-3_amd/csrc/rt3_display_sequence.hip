@@ -3,15 +3,15 @@
 // histogram and the map without bloom are rt3_display.hip's own kernels, launched through rt3_display.hpp.  Here: the gain kernel with the
 // adaptation step, the pyramid (bright pass fused into the first reduction, the reductions, the in-place up-sampling sums) and the map that
 // composites the bloom on the fly.  Every plane is float4 texels, one thread per texel, a capped grid with a grid-stride loop: streaming passes.
-// A translation unit of its own (gfx950 only), as rt3_display.hip is.  rt3_device.hip checks the arguments, owns the buffers and calls
-// display_sequence_launch().
+// A translation unit of its own (gfx950 only), as rt3_display.hip is.  The entry points are below the kernels: they check the arguments, take the
+// state and the pyramid from the context (rt3_ctx.hpp) and launch.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "rt3_ctx.hpp"
 #include "rt3_display_sequence_law.hpp"
 #include "rt3_display.hpp"
-#include "rt3_display_sequence.hpp"
 
 static_assert(sizeof(rt3_exposure) == 16, "rt3.h: rt3_exposure");
 static_assert(sizeof(rt3_display_sequence_params) == 64, "rt3.h: rt3_display_sequence_params");
@@ -29,8 +29,9 @@ uint32_t seq_grid(uint32_t n) {
     return want < kSeqMaxGrid ? want : kSeqMaxGrid;
 }
 
-__device__ inline Rgb rgb_of(const float4& v) { return Rgb{ v.x, v.y, v.z }; }
-__device__ inline float4 texel_of(const Rgb& c) { return make_float4(c.r, c.g, c.b, 0.0f); }
+// (rt3dseq::Rgb, the law's colour, spelled out: in this namespace a plain Rgb is the render path's radiance record, which rt3_ctx.hpp names)
+__device__ inline rt3dseq::Rgb rgb_of(const float4& v) { return rt3dseq::Rgb{ v.x, v.y, v.z }; }
+__device__ inline float4 texel_of(const rt3dseq::Rgb& c) { return make_float4(c.r, c.g, c.b, 0.0f); }
 __device__ inline Plane plane_of(const float4* p, uint32_t w, uint32_t h) { return Plane{ reinterpret_cast<const float*>(p), w, h }; }
 
 // k_display_gain with one more thread-0 tail: the frame's target P_t instead of its gain, then the step from prev's level towards it; the state after
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(kSeqBlock) void k_display_map_bloom(const float4* _
     for (uint32_t t = blockIdx.x * kSeqBlock + threadIdx.x; t < n; t += stride) {
         const uint32_t j = t / w0, i = t - j * w0;
         const float4 c = in[t];
-        const Rgb x = composite(exposed(c.x, c.y, c.z, gain), bloom_texel(u, i, j, weight), intensity);
+        const rt3dseq::Rgb x = composite(exposed(c.x, c.y, c.z, gain), bloom_texel(u, i, j, weight), intensity);
         out[t] = word_of(x.r, x.g, x.b, CURVE, TRANSFER, white, s_table);
     }
 }
@@ -162,52 +163,128 @@ __global__ __launch_bounds__(kSeqBlock) void k_bloom_plane(const float4* __restr
 
 }  // namespace
 
-hipError_t display_sequence_launch(const DisplaySequenceLaunch& S, hipStream_t stream) {
-    const DisplayLaunch& L = S.display;
-    hipError_t e;
-    if (L.auto_exposure) {
-        if ((e = display_histogram_launch(L, stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_display_gain_step, dim3(1), dim3(kBins), 0, stream, L.state, L.trim_low, L.trim_high, L.exposure, L.key, S.prev, S.out_exposure,
-                           S.adapt_brighter, S.adapt_darker);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    } else if (S.out_exposure) {
-        hipLaunchKernelGGL(k_exposure_given, dim3(1), dim3(64), 0, stream, S.out_exposure, L.exposure);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    if (S.bloom_levels == 0) return display_map_launch(L, stream);
-
-    const float4* in = (const float4*)L.rgba;
-    float4* plane[kMaxBloomLevels];
-    uint32_t w[kMaxBloomLevels + 1] = { S.width }, h[kMaxBloomLevels + 1] = { S.height };
-    float4* next = (float4*)S.pyramid;
-    for (uint32_t l = 1; l <= S.bloom_levels; l++) {
-        w[l] = half_of(w[l - 1]); h[l] = half_of(h[l - 1]);
-        plane[l - 1] = next;
-        next += (size_t)w[l] * h[l];
-    }
-    const dim3 block(kSeqBlock);
-    if (L.auto_exposure)
-        hipLaunchKernelGGL(k_bloom_down_first<true>, dim3(seq_grid(w[1] * h[1])), block, 0, stream, in, w[0], h[0], plane[0], w[1], h[1], L.exposure,
-                           (const uint32_t*)L.state, S.bloom_threshold);
-    else
-        hipLaunchKernelGGL(k_bloom_down_first<false>, dim3(seq_grid(w[1] * h[1])), block, 0, stream, in, w[0], h[0], plane[0], w[1], h[1], L.exposure,
-                           (const uint32_t*)L.state, S.bloom_threshold);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    for (uint32_t l = 2; l <= S.bloom_levels; l++) {
-        hipLaunchKernelGGL(k_bloom_down, dim3(seq_grid(w[l] * h[l])), block, 0, stream, (const float4*)plane[l - 2], w[l - 1], h[l - 1], plane[l - 1], w[l], h[l]);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    for (uint32_t l = S.bloom_levels - 1; l >= 1; l--) {
-        hipLaunchKernelGGL(k_bloom_up, dim3(seq_grid(w[l] * h[l])), block, 0, stream, (const float4*)plane[l], w[l + 1], h[l + 1], plane[l - 1], w[l], h[l]);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    const BloomMapKernel map = L.auto_exposure ? bloom_map_of<true>(L.curve, L.transfer) : bloom_map_of<false>(L.curve, L.transfer);
-    hipLaunchKernelGGL(map, dim3(seq_grid(L.npix)), block, 0, stream, in, (uint32_t*)L.out, w[0], h[0], (const float4*)plane[0], w[1], h[1], L.exposure,
-                       (const uint32_t*)L.state, L.white, S.bloom_intensity, level_weight(S.bloom_levels));
-    return hipGetLastError();
+// ---- The entry points (rt3.h)
+static int display_sequence_checks(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* rgba, const rt3_display_sequence_params* p, const void* prev,
+                                   const void* out_exposure, const void* out) {
+    if (!p) return fail(ctx, RT3_E_ARG, "p is NULL");
+    if (!rgba || !out) return fail(ctx, RT3_E_ARG, "rgba / out_pixels is NULL");
+    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 26)) return fail(ctx, RT3_E_ARG, "the frame must have 1 .. 2^26 pixels");
+    if (const char* why = rt3dseq::refusal(*p)) return fail(ctx, RT3_E_ARG, why);
+    if (prev && !(p->display.flags & RT3_DISPLAY_AUTO_EXPOSURE)) return fail(ctx, RT3_E_ARG, "prev_exposure needs RT3_DISPLAY_AUTO_EXPOSURE");
+    const size_t npix = (size_t)w * h;
+    const struct { const void* at; size_t bytes; } buf[4] = { { rgba, npix * sizeof(float4) }, { out, npix * sizeof(uint32_t) },
+                                                              { prev, sizeof(rt3_exposure) }, { out_exposure, sizeof(rt3_exposure) } };
+    for (int a = 0; a < 4; a++)
+        for (int b = a + 1; b < 4; b++) {
+            if (!buf[a].at || !buf[b].at || (a == 2 && buf[a].at == buf[b].at)) continue;      // prev == out_exposure: one record serves a sequence
+            if (ranges_overlap(buf[a].at, buf[a].bytes, buf[b].at, buf[b].bytes)) return fail(ctx, RT3_E_ARG, "rgba, out_pixels and the exposure records must not overlap (prev_exposure == out_exposure apart)");
+        }
+    return 0;
 }
 
-hipError_t bloom_plane_launch(const void* u1, uint32_t w1, uint32_t h1, void* out, uint32_t w0, uint32_t h0, uint32_t levels, hipStream_t stream) {
-    hipLaunchKernelGGL(k_bloom_plane, dim3(seq_grid(w0 * h0)), dim3(kSeqBlock), 0, stream, (const float4*)u1, w1, h1, (float4*)out, w0, h0, level_weight(levels));
-    return hipGetLastError();
+extern "C" {
+
+// Queued on the stream with no host wait, and nothing is timed: rt3_get_stats stays as it was.
+//   the exposure: with auto-exposure the state zeroed, k_display_histogram and k_display_gain_step (d_prev -> d_out_exposure, the gain left in the
+//   state); without it k_exposure_given if there is a d_out_exposure;
+//   bloom_levels == 0: k_display_map, one launch;
+//   bloom_levels == L: k_bloom_down_first, L - 1 x k_bloom_down, L - 1 x k_bloom_up, k_display_map_bloom: 2 L launches.
+// The pyramid (ctx->d_bloom): pyramid_texels(w, h, L) float4 texels, D_1 .. D_L one behind the other; after the call plane 1 holds U_1.
+int rt3_display_sequence_device(rt3_ctx* ctx, uint32_t w, uint32_t h, const void* d_rgba, const rt3_display_sequence_params* p, const void* d_prev,
+                                void* d_out_exposure, void* d_out, void* stream_) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = display_sequence_checks(ctx, w, h, d_rgba, p, d_prev, d_out_exposure, d_out);
+    if (rc) return rc;
+    if ((uintptr_t)d_rgba % 16u != 0 || (uintptr_t)d_out % 4u != 0 || (uintptr_t)d_prev % 4u != 0 || (uintptr_t)d_out_exposure % 4u != 0)
+        return fail(ctx, RT3_E_ARG, "d_rgba must be 16-byte, d_out_pixels and the exposure records 4-byte aligned");
+    const rt3_display_params& d = p->display;
+    const bool auto_exposure = (d.flags & RT3_DISPLAY_AUTO_EXPOSURE) != 0;
+    const uint32_t levels = p->bloom_levels;
+    hipStream_t stream;
+    if ((rc = enter(ctx, stream_, &stream))) return rc;
+    if (auto_exposure && (rc = ctx->d_display.ensure(ctx, rt3disp::kStateWords))) return rc;
+    if (levels && (rc = ctx->d_bloom.ensure(ctx, pyramid_texels(w, h, levels)))) return rc;
+    const DisplayLaunch L{ w * h, d.curve, d.transfer, auto_exposure, d.exposure, d.white, d_rgba, d_out, auto_exposure ? ctx->d_display.get() : nullptr };
+    rt3_exposure* const out_exposure = (rt3_exposure*)d_out_exposure;
+    if (auto_exposure) {
+        RT3_HIP(display_histogram_launch(L, stream));
+        hipLaunchKernelGGL(k_display_gain_step, dim3(1), dim3(kBins), 0, stream, L.state, d.trim_low, d.trim_high, d.exposure, d.key, (const rt3_exposure*)d_prev,
+                           out_exposure, p->adapt_brighter, p->adapt_darker);
+        RT3_HIP(hipGetLastError());
+    } else if (out_exposure) {
+        hipLaunchKernelGGL(k_exposure_given, dim3(1), dim3(64), 0, stream, out_exposure, d.exposure);
+        RT3_HIP(hipGetLastError());
+    }
+    if (levels == 0) {
+        RT3_HIP(display_map_launch(L, stream));
+    } else {
+        const float4* in = (const float4*)d_rgba;
+        const uint32_t* state = L.state;
+        float4* plane[kMaxBloomLevels];
+        uint32_t pw[kMaxBloomLevels + 1] = { w }, ph[kMaxBloomLevels + 1] = { h };
+        float4* next = ctx->d_bloom.get();
+        for (uint32_t l = 1; l <= levels; l++) {
+            pw[l] = half_of(pw[l - 1]); ph[l] = half_of(ph[l - 1]);
+            plane[l - 1] = next;
+            next += (size_t)pw[l] * ph[l];
+        }
+        const dim3 block(kSeqBlock);
+        hipLaunchKernelGGL(auto_exposure ? k_bloom_down_first<true> : k_bloom_down_first<false>, dim3(seq_grid(pw[1] * ph[1])), block, 0, stream, in, pw[0], ph[0],
+                           plane[0], pw[1], ph[1], d.exposure, state, p->bloom_threshold);
+        RT3_HIP(hipGetLastError());
+        for (uint32_t l = 2; l <= levels; l++) {
+            hipLaunchKernelGGL(k_bloom_down, dim3(seq_grid(pw[l] * ph[l])), block, 0, stream, (const float4*)plane[l - 2], pw[l - 1], ph[l - 1], plane[l - 1], pw[l], ph[l]);
+            RT3_HIP(hipGetLastError());
+        }
+        for (uint32_t l = levels - 1; l >= 1; l--) {
+            hipLaunchKernelGGL(k_bloom_up, dim3(seq_grid(pw[l] * ph[l])), block, 0, stream, (const float4*)plane[l], pw[l + 1], ph[l + 1], plane[l - 1], pw[l], ph[l]);
+            RT3_HIP(hipGetLastError());
+        }
+        const BloomMapKernel map = auto_exposure ? bloom_map_of<true>(d.curve, d.transfer) : bloom_map_of<false>(d.curve, d.transfer);
+        hipLaunchKernelGGL(map, dim3(seq_grid(L.npix)), block, 0, stream, in, (uint32_t*)d_out, pw[0], ph[0], (const float4*)plane[0], pw[1], ph[1], d.exposure,
+                           state, d.white, p->bloom_intensity, level_weight(levels));
+        RT3_HIP(hipGetLastError());
+    }
+    if (auto_exposure) ctx->display_auto = true;
+    if (levels) { ctx->bloom_w = w; ctx->bloom_h = h; ctx->bloom_levels = levels; }
+    return leave(ctx, stream);
 }
+
+int rt3_display_sequence(rt3_ctx* ctx, uint32_t w, uint32_t h, const float* rgba, const rt3_display_sequence_params* p, const rt3_exposure* prev,
+                         rt3_exposure* out_exposure, uint32_t* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = display_sequence_checks(ctx, w, h, rgba, p, prev, out_exposure, out);
+    if (rc) return rc;
+    if (prev && prev->level > kMaxLevel) return fail(ctx, RT3_E_ARG, "prev_exposure->level is above 511 << 19");
+    const size_t npix = (size_t)w * h;
+    return staged(ctx, { stage_in(rgba, npix * sizeof(float4)), stage_in(prev, sizeof(rt3_exposure)), stage_out(out_exposure, sizeof(rt3_exposure)),
+                         stage_out(out, npix * sizeof(uint32_t)) },
+                  [&](void* const* d) { return rt3_display_sequence_device(ctx, w, h, d[0], p, d[1], d[2], d[3], ctx->stream); });
+}
+
+// Tests only: U_1 of the last bloom call, and B = up(U_1) / levels stored at the frame's size.
+int rt3_debug_display_bloom(rt3_ctx* ctx, float* out_u1, float* out_bloom, uint64_t capacity_pixels, uint32_t* w_out, uint32_t* h_out) {
+    if (!ctx) return RT3_E_ARG;
+    if (!w_out || !h_out) return fail(ctx, RT3_E_ARG, "w / h is NULL");
+    if (ctx->bloom_levels == 0) return fail(ctx, RT3_E_STATE, "no rt3_display_sequence call with bloom_levels >= 1 on this context");
+    const uint32_t w = ctx->bloom_w, h = ctx->bloom_h, w1 = half_of(w), h1 = half_of(h);
+    const size_t npix = (size_t)w * h;
+    *w_out = w; *h_out = h;
+    if (capacity_pixels < npix) return fail(ctx, RT3_E_ARG, "capacity_pixels is smaller than the frame of the last bloom call");
+    hipStream_t stream;
+    int rc;
+    if ((rc = enter(ctx, nullptr, &stream))) return rc;            // behind the call that wrote the pyramid, whatever stream it ran on
+    if (out_u1) RT3_HIP(hipMemcpyAsync(out_u1, ctx->d_bloom.get(), (size_t)w1 * h1 * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    if (out_bloom) {
+        if ((rc = ctx->d_bloom_plane.ensure(ctx, npix))) return rc;
+        hipLaunchKernelGGL(k_bloom_plane, dim3(seq_grid(w * h)), dim3(kSeqBlock), 0, stream, (const float4*)ctx->d_bloom.get(), w1, h1, ctx->d_bloom_plane.get(), w, h,
+                           level_weight(ctx->bloom_levels));
+        RT3_HIP(hipGetLastError());
+        RT3_HIP(hipMemcpyAsync(out_bloom, ctx->d_bloom_plane.get(), npix * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    }
+    if ((rc = leave(ctx, stream))) return rc;
+    RT3_HIP(hipStreamSynchronize(stream));
+    return 0;
+}
+
+}  // extern "C"

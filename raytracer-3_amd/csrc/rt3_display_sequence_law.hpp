@@ -1,6 +1,6 @@
 // rt3_display_sequence_law.hpp — the law of display sequences (rt3.h "Display sequences"), one statement for the device and the host:
 // the exposure that follows a sequence (integers only) and the bloom pyramid (f32 operations rounded one by one; every file is compiled with
-// -ffp-contract=off).  Included by rt3_display_sequence.hip (the kernels), by rt3_device.hip (the parameter check, the pyramid's size) and by
+// -ffp-contract=off).  Included by rt3_display_sequence.hip (the kernels; the entry points' parameter check and the pyramid's size) and by
 // rt3_host.cpp (rt3_debug_exposure_step / rt3_debug_bloom, the serial restatement the tests compare with tests/display_sequence_ref.py).
 // The histogram, the trim, the curve and the transfer are rt3_display_law.hpp's.
 #pragma once

@@ -1,7 +1,7 @@
 // rt3_lens_law.hpp — the lens models' ray law (rt3.h "Lens models") and its inverse (rt3.h "Lens sequences"), one
 // statement for the device and the host.
 // Included by rt3_device.hip (k_lens_rays and the drivers' checks, rt3_lens.hpp), by rt3_denoise.hip (the lens forms of k_temporal_reproject and
-// k_motion) and by rt3_host.cpp (rt3_debug_lens_ray, rt3_lens_look_at, rt3_debug_turns, rt3_debug_optic_pixel: the serial restatement the tests
+// k_motion, their entry points' checks) and by rt3_host.cpp (rt3_debug_lens_ray, rt3_lens_look_at, rt3_debug_turns, rt3_debug_optic_pixel: the serial restatement the tests
 // compare with tests/lens_ref.py and tests/optic_ref.py).  Every float operation is an IEEE f32 operation rounded on its own (every file is compiled with
 // -ffp-contract=off); the fused multiply-adds of sincos2pi and of the validity rule's d.d are written out.  The hash, u01 and sincos2pi restate
 // rt3_kernel_common.hpp's, which exist for the device only.

@@ -1,0 +1,45 @@
+"""csrc/rt3_ctx.hpp — the device context and what every entry point shares — stands alone, and the launcher layer it replaced is gone.
+
+Every unit of the library that defines entry points includes the header (rt3_device.hip, rt3_denoise.hip, rt3_display.hip,
+rt3_display_sequence.hip), so it must compile where nothing but <hip/hip_runtime.h>, the standard headers it uses and rt3.h is at hand: none of
+the kernel headers.  The post-process entry points fill their kernels' arguments directly; the structs that carried the C ABI's parameters across the
+file boundary, and the two headers that held nothing else, must not come back.  No GPU."""
+import glob
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "raytracer-3_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+
+
+def test_header_stands_alone(tmp_path):
+    unit = tmp_path / "only_ctx.hip"
+    unit.write_text('#include "rt3_ctx.hpp"\n'
+                    "int probe(rt3_ctx* ctx) { return ctx->d_rad.get() == nullptr && ctx->tri.gfrag.size() == 0 ? fail(ctx, RT3_E_STATE, \"empty\") : 0; }\n")
+    # the Makefile's flags and include path (INC := -I../include from raytracer-3_amd/), the host side only, no output
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-Wno-unused-function",
+                           "--cuda-host-only", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), "-I", CSRC, str(unit)])
+    text = open(os.path.join(CSRC, "rt3_ctx.hpp")).read()
+    assert re.findall(r'#include "([^"]+)"', text) == ["rt3.h"]
+
+
+def test_launcher_layer_is_gone():
+    assert not os.path.exists(os.path.join(CSRC, "rt3_denoise.hpp"))
+    assert not os.path.exists(os.path.join(CSRC, "rt3_display_sequence.hpp"))
+    files = sorted(f for ext in ("hip", "hpp", "cpp") for f in glob.glob(os.path.join(CSRC, "*." + ext)))
+    text = {os.path.basename(f): open(f).read() for f in files}
+    for name in ("DenoiseLaunch", "TemporalLaunch", "MotionLaunch", "DisplaySequenceLaunch"):
+        assert [f for f, t in text.items() if re.search(r"\b%s\b" % name, t)] == [], name
+    # DisplayLaunch is what rt3_display.hpp keeps for rt3_display_sequence.hip: the arguments of the two steps a sequence call shares with
+    # rt3_display.hip, the histogram and the map — and nothing of the gain step between them, which each unit launches itself
+    users = sorted(f for f, t in text.items() if re.search(r"\bDisplayLaunch\b", t))
+    assert users == ["rt3_display.hip", "rt3_display.hpp", "rt3_display_sequence.hip"]
+    struct = re.search(r"struct DisplayLaunch \{(.*?)\n\};", text["rt3_display.hpp"], re.S).group(1)
+    for field in ("trim_low", "trim_high", "key"):
+        assert not re.search(r"\b%s\b" % field, struct), field
+    assert re.findall(r"hipError_t (\w+)\(", text["rt3_display.hpp"]) == ["display_histogram_launch", "display_map_launch"]
+    # nothing outside the unit that holds the kernels calls a launcher of it
+    for f, t in text.items():
+        assert not re.search(r"\b(denoise_launch|temporal_launch|motion_launch|display_launch|display_sequence_launch|bloom_plane_launch)\b", t), f
