@@ -26,11 +26,6 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_list(const Rgb* __restric
     counts[pix] = count_after;
 }
 
-__global__ __launch_bounds__(kBlock) void k_fill_words(uint32_t* __restrict__ out, uint32_t n, uint32_t value) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) out[i] = value;
-}
-
 // The rule of DESIGN.md 4.15 for every owned pixel, over its own count: all in f32, every operation rounded on its own (-ffp-contract=off), in the
 // order written there.  A NaN anywhere compares false: converged.
 __global__ __launch_bounds__(kBlock) void k_adaptive_flags(const float4* __restrict__ accum, const float4* __restrict__ accum_sq,
@@ -76,15 +71,7 @@ __device__ __forceinline__ bool adaptive_stays(const AdaptiveGeom& G, const uint
 // Compaction in ascending pixel order, in two passes over the same predicate: k_adaptive_count leaves the number of staying pixels of every block,
 // k_adaptive_select sums the counts of the blocks before its own (a few thousand words at 1080p), ranks its pixels by ballot and prefix count and
 // writes them; the last block also writes the list's length to *n_out, the one word the host reads back per round.
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* lds) {       // sum over the block of kBlock threads, in every thread
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = 0;
-    for (uint32_t w = 0; w < kBlock / 64; w++) t += lds[w];
-    __syncthreads();
-    return t;
-}
+// (block_sum: rt3_shared_kernels.hpp)
 __global__ __launch_bounds__(kBlock) void k_adaptive_count(const AdaptiveGeom G, const uint32_t* __restrict__ counts,
                                                           const uint8_t* __restrict__ unconverged, uint32_t npix, uint32_t done,
                                                           uint32_t* __restrict__ block_counts) {

@@ -1,5 +1,5 @@
 // rt3_ctx.hpp — the device context (struct rt3_ctx) and what every entry point shares, for every unit of the library that defines entry points:
-// rt3_device.hip, rt3_denoise.hip, rt3_display.hip and rt3_display_sequence.hip.  The owned device buffers (DevBuf), RT3_HIP and fail, the
+// rt3_device.hip, rt3_scene.hip, rt3_denoise.hip, rt3_display.hip and rt3_display_sequence.hip.  The owned device buffers (DevBuf), RT3_HIP and fail, the
 // stream convention and the event chain (stream_of, enter, leave), the host forms' round trip (staged) and ranges_overlap.  Needs
 // <hip/hip_runtime.h> and rt3.h only: none of the kernel headers.
 #pragma once
@@ -15,8 +15,8 @@
 
 #include "rt3.h"
 
-// The kernel-side types the context's buffers hold, by name only (a DevBuf<T> member needs no more than T*): they belong to rt3_device.hip's
-// unnamed namespace (rt3_kernel_common.hpp, rt3_matrix_filter.hpp), where the unit that allocates and reads those buffers completes them.
+// The kernel-side types the context's buffers hold, by name only (a DevBuf<T> member needs no more than T*): they belong to the unnamed
+// namespace of the units that allocate and read those buffers (rt3_kernel_common.hpp, rt3_filter_frags.hpp), which complete them.
 namespace {
 struct Rgb;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

@@ -1,5 +1,5 @@
 // rt3_env_sample.hpp — the environment map's sampling table and sampling law (rt3.h), one statement for the device and the host.
-// Included by rt3_device.hip (the table kernels, shade_lane of the sampling forms) and by rt3_host.cpp (rt3_debug_environment_sample, the serial
+// Included by rt3_scene.hip (the table kernels), by rt3_device.hip (shade_lane of the sampling forms) and by rt3_host.cpp (rt3_debug_environment_sample, the serial
 // restatement the tests compare with tests/environment_sample_ref.py).  Integers wherever a sum is taken, so the table does not depend on the order
 // it was built in; every float operation is an IEEE f32 operation rounded on its own (both files are compiled with -ffp-contract=off), the one fused
 // multiply-add — the dot product under the normalisation, as shade_lane normalises a scattered direction — is written out.

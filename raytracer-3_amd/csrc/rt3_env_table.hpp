@@ -1,5 +1,5 @@
 // rt3_env_table.hpp — the kernels that build the environment map's sampling table (RT3_FLAG_ENV_SAMPLING; rt3_env_sample.hpp)
-// Part of rt3_device.hip (one translation unit, gfx950 only); included from there, in this order.
+// Part of rt3_scene.hip (one translation unit, gfx950 only); included from there, in this order.
 #pragma once
 
 namespace {

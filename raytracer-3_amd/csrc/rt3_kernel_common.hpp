@@ -1,5 +1,5 @@
 // rt3_kernel_common.hpp — constants, arithmetic helpers (hash RNG, sky, pixel packing, sin/cos), Mode-X launch arguments and start_path()
-// Part of rt3_device.hip (one translation unit, gfx950 only); included from there, in this order.
+// No kernel.  Included by rt3_device.hip (all of it) and by rt3_scene.hip (the constants and the arithmetic helpers its kernels use), gfx950 only.
 #pragma once
 
 namespace {
@@ -207,7 +207,7 @@ struct TraceArgs {
     float tcx, tcy, tcz;     // faces (the faces' pass of k_trace_mfma_tiled)
     // Spheres that nearly every ray is a candidate for (a ground sphere; a sphere around the middle of the scene) gain nothing from the
     // filter and cost the pair list 64 entries per ray cast each: they are tested directly, every lane its own ray, and their fragment
-    // rows can never be candidates (sphere_direct_list in rt3_device.hip).  Matrix-filter kernels only.
+    // rows can never be candidates (sphere_direct_list, rt3_sphere_plan.hpp).  Matrix-filter kernels only.
     uint32_t n_direct; uint32_t direct[4];
     // Two-level filter of k_trace_mfma_tiled: with a group size G > 1 a row of the matrix filter is the bounding sphere of G
     // primitives, grouped in the order of a spatial median split (rt3_set_spheres / rt3_mesh_commit): *_grp holds the members' (cx, cy, cz, r^2)

@@ -1,7 +1,7 @@
 // rt3_level_filter.hpp — k_trace_levels: the multi-level candidate filter of DESIGN.md 5.2e as ONE loop over its stages
-// Part of rt3_device.hip (one translation unit, gfx950 only); included after rt3_matrix_filter.hpp, whose scan / push / pair-list pieces it uses.
+// Part of rt3_device.hip (one translation unit, gfx950 only); included after rt3_matrix_filter.hpp, whose scan / push / pair-list pieces it uses (kLevFan: rt3_filter_frags.hpp).
 //
-// Levels (8 children per node; primitives in the order of the spatial median split of rt3_device.hip):
+// Levels (8 children per node; primitives in the order of the spatial median split of rt3_scene.hip):
 //   top     what the matrix cores scan (K = 32 filter, mfma32k_scan_tile): LEVELS == 3: a row = 64 primitives; LEVELS == 4: a super-row = 512
 //   rows    LEVELS == 4 only: the 8 rows of a candidate super-row, their bounds tested in f32                       (A.*_rowb)
 //   leaves  the 8 leaf groups of a candidate row, bounds in f32                                                      (A.*_leaf)
@@ -20,7 +20,6 @@
 
 namespace {
 
-constexpr uint32_t kLevFan = 8;                                     // children per node at every level (kGroupTri = kGroupSph = kSuper = 8)
 constexpr uint32_t kLevListCap = 31u + 32u * kLevFan + 1u;          // a list below its consumer's threshold (32) + one batch's worst case: 288
 constexpr uint32_t kLevExactCap = 63u + 32u * kLevFan + 1u;         // the exact stage takes 64 at a time: 320
 constexpr uint32_t kLevBmBlocks = 4;                                // row blocks per push (resident rows) ...

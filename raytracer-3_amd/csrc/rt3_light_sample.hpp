@@ -1,5 +1,5 @@
 // rt3_light_sample.hpp — the emitters' sampling table and sampling law (rt3.h "Emitters: sampling"), one statement for the device and the host.
-// Included by rt3_device.hip (the table kernels of rt3_light_table.hpp, shade_lane of the light sampling forms) and by rt3_host.cpp
+// Included by rt3_scene.hip (the table kernels of rt3_light_table.hpp), by rt3_device.hip (shade_lane of the light sampling forms) and by rt3_host.cpp
 // (rt3_debug_light_sample, the serial restatement the tests compare with tests/light_sample_ref.py).  As in rt3_env_sample.hpp: integers wherever a sum
 // is taken, every float operation an IEEE f32 operation rounded on its own (both files are compiled with -ffp-contract=off), every fused multiply-add
 // written out.

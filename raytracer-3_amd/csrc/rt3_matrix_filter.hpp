@@ -3,7 +3,7 @@
 // k_trace_mfma (round 1's K = 64 kernel, the A/B reference).
 // Order of the file: the K = 64 form on v_mfma_f32_32x32x16_bf16 (the derivation; k_trace_mfma only), its 16x16x32 variant (A/B reference
 // for faces), the K = 32 form on v_mfma_f32_16x16x32_bf16 that every default kernel runs, the pair list, the kernels.
-// Part of rt3_device.hip (one translation unit, gfx950 only); included from there, in this order.
+// Part of rt3_device.hip (one translation unit, gfx950 only); included from there, behind rt3_filter_frags.hpp (the sphere side).
 #pragma once
 
 namespace {
@@ -29,11 +29,9 @@ namespace {
 constexpr int      kMB        = 1024;      // threads per workgroup of the matrix-filter kernels (one workgroup per CU, 4 waves per SIMD)
 constexpr uint32_t kMfmaSphMax = 512;      // 16 row blocks x 4 operand fragments x 1 KiB = 64 KiB of LDS
 constexpr uint32_t kBitmapBytes = 16 * kMB * 4;   // candidate words: [16 row blocks][kMB lanes]
-constexpr float    kFilterEps = 2e-5f;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // K-slot layout.  Operand q (0..3) of the chain holds 16 K-elements, lane half hh supplies elements 8 hh .. 8 hh + 7 as four
 // dwords i = 0..3 of two bf16 each.  With x_t / y_t the ray / sphere factor of term t (t = 0..8), E and K the two constants:
@@ -43,49 +41,8 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 //     (q = 3;     hh = 0)  ray (H x_8, 1) x3, (M x_8, H E)             sphere (H y_8, H K), (M y_8, M K), (L y_8, L K), (H y_8, 1)
 //     (q = 3;     hh = 1)  ray (M x_8, M E), (L x_8, L E), 0, 0        sphere (M y_8, 1), (H y_8, 1), 0, 0
 // so a lane needs only three distinct ray-side register quads per column set (operands 0 and 1 share one).
-// row of the A operand that holds sphere b (0..31) of a row block
-__host__ __device__ constexpr uint32_t frag_row_of(uint32_t b) { return ((15u - (b & 15u)) & 3u) + 8u * ((15u - (b & 15u)) >> 2) + 4u * (b >> 4); }
-
-__host__ __device__ inline uint32_t bf16_rn(float x) {            // round to nearest even, finite inputs
-    uint32_t u = __builtin_bit_cast(uint32_t, x);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__host__ __device__ inline float bf16_up(uint32_t h) { return __builtin_bit_cast(float, h << 16); }
-__host__ __device__ inline void split3(float x, uint32_t* parts /*[3]*/) {
-    parts[0] = bf16_rn(x);
-    const float r1 = x - bf16_up(parts[0]);
-    parts[1] = bf16_rn(r1);
-    parts[2] = bf16_rn(r1 - bf16_up(parts[1]));
-}
-
-// Sphere-side (A operand) fragment of one bounding sphere: out[q][hh][dword] = K elements 8 hh .. 8 hh + 7 of MFMA operand q.
-// kj = filter_kj(|C|^2, r^2); a padding row uses C = 0, kj = -1e30 (never a candidate), an unbounded one kj = +1e30 (always).
-__host__ __device__ inline void bound_frag_row(float cx, float cy, float cz, float kj, uint32_t out[4][2][4]) {
-    uint32_t y[9][3], k[3];                                         // [term][part]
-    const double x = cx, yy = cy, z = cz;
-    split3((float)(x * x), y[0]); split3((float)(yy * yy), y[1]); split3((float)(z * z), y[2]);
-    split3((float)(x * yy), y[3]); split3((float)(x * z), y[4]); split3((float)(yy * z), y[5]);
-    split3(cx, y[6]); split3(cy, y[7]); split3(cz, y[8]);
-    split3(kj, k);
-    const uint32_t one = 0x3F80u;
-    auto pk = [](uint32_t lo, uint32_t hi) { return lo | (hi << 16); };
-    for (int i = 0; i < 4; i++) {
-        for (int q = 0; q < 3; q++) out[q][0][i] = pk(y[2 * i][q], y[2 * i + 1][q]);
-        for (int q = 0; q < 2; q++) out[q][1][i] = pk(y[2 * i][q], y[2 * i + 1][q]);
-        out[2][1][i] = pk(y[2 * i][0], y[2 * i + 1][0]);
-    }
-    for (int i = 0; i < 3; i++) out[3][0][i] = pk(y[8][i], k[i]);
-    out[3][0][3] = pk(y[8][0], one);
-    out[3][1][0] = pk(y[8][1], one);
-    out[3][1][1] = pk(y[8][0], one);
-    out[3][1][2] = 0u; out[3][1][3] = 0u;
-}
-__host__ __device__ inline float filter_kj(double c2, double r2) { return (float)((r2 - c2) + (double)kFilterEps * (c2 + r2)); }
-constexpr float kNeverCandidate = -1e30f, kAlwaysCandidate = 1e30f;
-#ifndef RT3_FACE_K32
-#define RT3_FACE_K32 1                                               // 1: faces go through the K = 32 form like the spheres (fragments: k_commit_mesh);
-#endif                                                              // 0: the K = 64 16x16x32 form (A/B reference; tools/filter_probe measures both)
+// The sphere side of all three forms — frag_row_of, bound_frag_row, bound_frag16_row, bound_frag32_row, filter_kj, filter_kj32, the margins —
+// is rt3_filter_frags.hpp: the scene build encodes with it.
 
 // Ray-side (B operand) fragments of the 64 rays of a wave: [column set (rays 0..31 / 32..63)][operands 0 and 1, operand 2, operand 3].
 struct RayOperands { u32x4 b[2][3]; };
@@ -241,31 +198,6 @@ __device__ __forceinline__ void mfma_flush(uint32_t nz, uint32_t n_blocks, const
 struct RayOperands16 { u32x4 b[4][2]; };                            // [ray group G][q]: K-slice of this lane's group for ray 16 G + c
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
-// Sphere side: out[q][g][dword] = K-slots 32 q + 8 g .. + 7 of one row (kj, never / always: as bound_frag_row).
-__host__ __device__ inline void bound_frag16_row(float cx, float cy, float cz, float kj, uint32_t out[2][4][4]) {
-    uint32_t y[9][3], k[3];                                         // [term][part]
-    const double x = cx, yy = cy, z = cz;
-    split3((float)(x * x), y[0]); split3((float)(yy * yy), y[1]); split3((float)(z * z), y[2]);
-    split3((float)(x * yy), y[3]); split3((float)(x * z), y[4]); split3((float)(yy * z), y[5]);
-    split3(cx, y[6]); split3(cy, y[7]); split3(cz, y[8]);
-    split3(kj, k);
-    const uint32_t one = 0x3F80u;
-    uint32_t slot[64];
-    const int part_of_group[6] = { 0, 1, 2, 0, 1, 0 };              // sphere part of groups A..F
-    for (int grp = 0; grp < 6; grp++) {
-        for (int t = 0; t < 9; t++) slot[10 * grp + t] = y[t][part_of_group[grp]];
-        slot[10 * grp + 9] = grp < 3 ? k[grp] : one;
-    }
-    for (int i = 60; i < 64; i++) slot[i] = 0u;
-    for (int q = 0; q < 2; q++)
-        for (int g = 0; g < 4; g++)
-            for (int d = 0; d < 4; d++) out[q][g][d] = slot[32 * q + 8 * g + 2 * d] | (slot[32 * q + 8 * g + 2 * d + 1] << 16);
-}
-// where the fragment of (row block, row b of it, q, lane group g) lives: [blk][operand 2 h + q][lane 16 g + c]
-__host__ __device__ constexpr size_t frag16_index(uint32_t blk, uint32_t b, uint32_t q, uint32_t g) {
-    return ((size_t)blk * 4 + 2u * (b >> 4) + q) * 64 + 16u * g + (b & 15u);
-}
-
 // v_permlane16_swap(x, y): x's odd 16-lane rows <-> y's even rows
 __device__ __forceinline__ void swap16(uint32_t x, uint32_t y, uint32_t& nx, uint32_t& ny) {
     const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
@@ -394,33 +326,7 @@ __device__ __forceinline__ uint32_t mfma16_scan_tile(const u32x4* s_frag, uint32
 // Faces take the same form: their exact test is dearer (a 64-byte gather, ~150 instructions) and K = 32 doubles their candidates (20 -> 39 per
 // ray cast in the 47 106-face box), but the K = 64 face scan was bound by the matrix pipe itself: x0.82 on that scene, x0.76 on Mode R
 // (profiles/r02_ab_face_k32.log).  -DRT3_FACE_K32=0 keeps the K = 64 form of this shape (mfma16_scan_tile) as the A/B reference.
-constexpr float kFilterEps32 = 2.2e-4f;
 struct RayOperands32 { u32x4 b[4]; };                               // [ray group G]: K-slots 8 g .. 8 g + 7 of ray 16 G + c
-__host__ __device__ inline float filter_kj32(double c2, double r2) { return (float)((r2 - c2) + (double)kFilterEps32 * (c2 + r2)); }
-__host__ __device__ inline uint32_t bf16_ceil(float x) {           // smallest bf16 >= x (finite x)
-    uint32_t u = __builtin_bit_cast(uint32_t, x) & 0xFFFF0000u;     // towards zero
-    if (x > 0.0f && __builtin_bit_cast(float, u) < x) u += 0x10000u;
-    return u >> 16;
-}
-// Sphere side: out[g][dword] = K-slots 8 g .. 8 g + 7 of one row; (cx, cy, cz) are already relative to the filter centre.
-__host__ __device__ inline void bound_frag32_row(float cx, float cy, float cz, float kj, uint32_t out[4][4]) {
-    uint32_t y[9][3], k[2];
-    const double x = cx, yy = cy, z = cz;
-    split3((float)(x * x), y[0]); split3((float)(yy * yy), y[1]); split3((float)(z * z), y[2]);
-    split3((float)(x * yy), y[3]); split3((float)(x * z), y[4]); split3((float)(yy * z), y[5]);
-    split3(cx, y[6]); split3(cy, y[7]); split3(cz, y[8]);
-    k[0] = bf16_rn(kj);
-    k[1] = bf16_ceil(kj - bf16_up(k[0]));                           // H K + M K >= kj: what the dropped low part would add stays on the safe side
-    const uint32_t one = 0x3F80u;
-    uint32_t slot[32];
-    for (int t = 0; t < 9; t++) { slot[t] = y[t][0]; slot[10 + t] = y[t][1]; slot[20 + t] = y[t][0]; }
-    slot[9] = k[0]; slot[19] = k[1]; slot[29] = one; slot[30] = one; slot[31] = one;
-    for (int g = 0; g < 4; g++)
-        for (int d = 0; d < 4; d++) out[g][d] = slot[8 * g + 2 * d] | (slot[8 * g + 2 * d + 1] << 16);
-}
-__host__ __device__ constexpr size_t frag32_index(uint32_t blk, uint32_t b, uint32_t g) {       // [blk][h][16 g + c]
-    return ((size_t)blk * 2 + (b >> 4)) * 64 + 16u * g + (b & 15u);
-}
 // Ray side (o relative to the filter centre).  16 dwords per ray: (ph0..3, h8) twice, (pm0..3, m8a), (M E, L E); lane (g, c) needs
 // dwords 4 g .. 4 g + 3 of the rays of lanes (G, c): the two-stage transpose of build_ray_operands16 on 4-dword pieces.
 __device__ __forceinline__ void build_ray_operands32(float ox, float oy, float oz, float dx, float dy, float dz, bool alive, RayOperands32& R) {
@@ -573,7 +479,6 @@ __device__ __forceinline__ uint32_t mfma32k_scan_tile(const u32x4* s_frag, uint3
 // (Running the tests of all 16 waves together, in a phase of the whole workgroup behind a tile's first barrier, instead of whenever a wave
 // has 64 pairs, was built and measured neutral — x1.001 / x0.990 / x0.993 on the three tiled workloads — and taken out again.)
 constexpr uint32_t kPairCap = 128;                                  // per wave: < 64 left over + one round of <= 64 new pairs
-constexpr uint32_t kPairLaneShift = 26;                             // pair = lane << 26 | primitive row (< 2^26)
 constexpr unsigned long long kKeyNone = 0x7F800000FFFFFFFFull;      // t = +inf: what a real hit (t < inf) always beats
 __device__ __forceinline__ unsigned long long hit_key(float t, uint32_t is_sphere, uint32_t idx) {
     const uint32_t tb = __float_as_uint(t);
@@ -1194,16 +1099,7 @@ __device__ __forceinline__ void fill_tile(u32x4* s_frag, const u32x4* __restrict
 // a row is the bounding sphere of G primitives, a candidate row expands into G member tests: for spheres the exact test itself, for faces
 // first the f32 test of the member's own bounding sphere (the vector-ALU kernels' scan arithmetic, 16-byte record) whose survivors are
 // compacted into a second pair list and get the reference's plane + three-edge test, 64 at a time).  Both must divide 64.
-#ifndef RT3_GROUP_TRI
-#define RT3_GROUP_TRI 8
-#endif
-#ifndef RT3_GROUP_SPH
-#define RT3_GROUP_SPH 8
-#endif
-#ifndef RT3_SUPER
-#define RT3_SUPER 8                                                 // leaf groups per row of the matrix filter (1: two levels, rows = leaf groups)
-#endif
-constexpr uint32_t kGroupTri = RT3_GROUP_TRI, kGroupSph = RT3_GROUP_SPH, kSuper = RT3_SUPER;
+// (kGroupTri, kGroupSph, kSuper: rt3_filter_frags.hpp)
 // SUP > 1 (with GT, GS > 1): three levels — a row bounds SUP consecutive leaf groups; a candidate row's ray is first tested, in f32, against the SUP
 // leaves' bounding spheres (A.*_leaf; scan_tile's arithmetic with a margin of 1e-4 c, which covers what the exact sphere test's own rounding lets
 // through: DESIGN.md 5.2e), the surviving (ray lane, leaf) pairs go through a list of their own to the members' tests described above.

@@ -1,5 +1,5 @@
 // rt3_regroup.hpp — the group order of the multi-level filter again, on the device (rt3_regroup*)
-// Part of rt3_device.hip (one translation unit, gfx950 only); included from there, after rt3_scene_kernels.hpp.
+// Part of rt3_scene.hip (one translation unit, gfx950 only); included from there, after rt3_scene_kernels.hpp.
 #pragma once
 
 namespace {

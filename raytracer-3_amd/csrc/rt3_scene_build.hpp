@@ -1,7 +1,7 @@
 // rt3_scene_build.hpp — a full scene upload from device arrays (rt3_set_spheres_device / rt3_set_mesh_device): what
 // rt3_set_spheres and rt3_mesh_commit decide on one host thread — validation, the filter centre, the direct list, which primitives take part in
 // the group order — as kernels over the caller's arrays, and the ordered compaction that writes the initial group order.
-// Part of rt3_device.hip (one translation unit, gfx950 only); included from there, after rt3_regroup.hpp.
+// Part of rt3_scene.hip (one translation unit, gfx950 only); included from there, after rt3_regroup.hpp.
 #pragma once
 
 namespace {

@@ -1,5 +1,5 @@
 // rt3_scene_kernels.hpp — device-side scene assembly: tessellated spheres and the merge into the render layout (k_commit_mesh)
-// Part of rt3_device.hip (one translation unit, gfx950 only); included from there, in this order.
+// Part of rt3_scene.hip (one translation unit, gfx950 only); included from there, in this order.
 #pragma once
 
 namespace {
@@ -94,7 +94,7 @@ __global__ void k_commit_mesh(const rt3_gface* __restrict__ faces, const float4*
                               float4* __restrict__ mat, uint32_t* __restrict__ kind, uint32_t* __restrict__ error_flag,
                               u32x4* __restrict__ frag, uint32_t n_frag_rows, const uint32_t* __restrict__ box, float centre_scale) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    float centre[3];                                                // centre_scale: 1 for the path tracer; 0.5: Mode R's fragments (rt3_device.hip),
+    float centre[3];                                                // centre_scale: 1 for the path tracer; 0.5: Mode R's fragments (render_layout),   
     box_centre(box, centre);                                        //   a later launch that writes `frag` only
     for (int a = 0; a < 3; a++) centre[a] *= centre_scale;
     const bool all = centre_scale == 1.0f;

@@ -1,5 +1,5 @@
 // rt3_sphere_plan.hpp — what a full sphere upload decides before it builds anything: the centre the filter's coordinates are taken about and the
-// spheres that are tested directly.  Plain host C++ (no HIP): rt3_device.hip includes it for rt3_set_spheres, rt3_host.cpp for
+// spheres that are tested directly.  Plain host C++ (no HIP): rt3_scene.hip includes it for rt3_set_spheres, rt3_host.cpp for
 // rt3_debug_sphere_plan, which is what the device form of the upload (rt3_set_spheres_device, rt3_scene_build.hpp) is compared with.
 #pragma once
 

@@ -1,7 +1,7 @@
 """csrc/rt3_ctx.hpp — the device context and what every entry point shares — stands alone, and the launcher layer it replaced is gone.
 
-Every unit of the library that defines entry points includes the header (rt3_device.hip, rt3_denoise.hip, rt3_display.hip,
-rt3_display_sequence.hip), so it must compile where nothing but <hip/hip_runtime.h>, the standard headers it uses and rt3.h is at hand: none of
+Every unit of the library that defines entry points includes the header (rt3_device.hip, rt3_scene.hip, rt3_denoise.hip,
+rt3_display.hip, rt3_display_sequence.hip), so it must compile where nothing but <hip/hip_runtime.h>, the standard headers it uses and rt3.h is at hand: none of
 the kernel headers.  The post-process entry points fill their kernels' arguments directly; the structs that carried the C ABI's parameters across the
 file boundary, and the two headers that held nothing else, must not come back.  No GPU."""
 import glob

@@ -1,5 +1,5 @@
 """Spheres that nearly every ray is a candidate for are taken out of the matrix filter and tested directly (TraceArgs::direct,
-sphere_direct_list in rt3_device.hip).  The nearest hit must not depend on which path found it: exact ties in t between a
+sphere_direct_list in rt3_sphere_plan.hpp, called by rt3_scene.hip).  The nearest hit must not depend on which path found it: exact ties in t between a
 direct sphere and a filtered one go to the lower index, as in the sequential loops.  Six coincident big spheres with different flat
 colours (four fit on the list, two stay in the filter), a sphere around the camera, small spheres in front — every matrix-filter kernel
 against the unfiltered one."""

@@ -1,5 +1,5 @@
-// device_stubs.cpp — the device half of the C ABI (raytracer-3_amd/csrc/rt3_device.hip and, for the post-process calls, rt3_denoise.hip, rt3_display.hip
-// and rt3_display_sequence.hip) as "no device" stubs, for the SANITIZER BUILD ONLY
+// device_stubs.cpp — the device half of the C ABI (raytracer-3_amd/csrc/rt3_device.hip, for the scene calls rt3_scene.hip and, for the post-process calls,
+// rt3_denoise.hip, rt3_display.hip and rt3_display_sequence.hip) as "no device" stubs, for the SANITIZER BUILD ONLY
 // (make -C raytracer-3_amd asan): the host code under test — rt3_host.cpp, SceneParser.cpp, HostApi.cpp, Main.cpp — is compiled with g++
 // -fsanitize=address,undefined and linked against these instead of librt3hip.so, so that it runs on a machine without a GPU and without the
 // HIP runtime inside the sanitizer.  Nothing in the product links this file; every entry point fails the way the library does when no

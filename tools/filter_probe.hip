@@ -5,6 +5,7 @@
 // |filter - (exact discriminant + margin)| relative to the margin.  Build + run on an MI355X:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -o tools/filter_probe tools/filter_probe.hip raytracer-3_amd/csrc/rt3_host.cpp
 #include "../raytracer-3_amd/csrc/rt3_device.hip"
+#include "../raytracer-3_amd/csrc/rt3_scene.hip"                    // (what rt3_device.hip calls across the unit boundary: one translation unit here)
 #include <random>
 
 namespace {

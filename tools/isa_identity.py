@@ -10,9 +10,13 @@ block every mangled symbol becomes a placeholder and the local labels lose the n
 Functions of equal hash are paired, several of one hash in the order of their sorted names.  Prints `tree's name <- parent's name` per function
 (demangled, without the parameter list, a name of more than 200 characters cut short; --enum NAME=A,B,.. spells the values of an enum template argument) and ends with the counts; exit code 1 if a
 function of either side has no partner.
+
+A side may be several listings, A.s,B.s — a unit that was split in two: their functions are taken together, and a function both listings hold (a kernel
+of a header both units include) counts once per listing, as `name @B.s` from the second on.
 """
 import collections
 import hashlib
+import os
 import re
 import shutil
 import subprocess
@@ -54,7 +58,7 @@ def functions(path):
 
 def demangled(names, enums):
     tool = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
-    text = subprocess.run([tool], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines() if tool and names else list(names)
+    text = subprocess.run([tool], input="\n".join(n.split(" @")[0] for n in names), capture_output=True, text=True, check=True).stdout.splitlines() if tool and names else list(names)
     out = {}
     for n, d in zip(names, text):
         d = re.sub(r"^void ", "", d.replace("(anonymous namespace)::", ""))
@@ -68,8 +72,22 @@ def demangled(names, enums):
             d = d[:i]
         for enum, values in enums.items():
             d = re.sub(r"\(%s\)(\d+)" % re.escape(enum), lambda m: "%s::%s" % (enum, values[int(m.group(1))]) if int(m.group(1)) < len(values) else m.group(0), d)
-        out[n] = d if len(d) <= 200 else "%s...[%d more characters]" % (d[:160], len(d) - 160)
+        d = d if len(d) <= 200 else "%s...[%d more characters]" % (d[:160], len(d) - 160)
+        out[n] = d + n[len(n.split(" @")[0]):]
     return out
+
+
+def listings(paths):
+    """functions() over the listings of one side, A.s,B.s,...: a name a later listing repeats becomes `name @listing`."""
+    table, kernels = {}, set()
+    for path in paths.split(","):
+        t, k = functions(path)
+        for n, h in t.items():
+            key = n if n not in table else "%s @%s" % (n, os.path.basename(path))
+            table[key] = h
+            if n in k:
+                kernels.add(key)
+    return table, kernels
 
 
 def main():
@@ -83,7 +101,7 @@ def main():
             args.append(a)
     if len(args) != 2:
         sys.exit(__doc__)
-    (pa, pa_k), (tr, tr_k) = functions(args[0]), functions(args[1])
+    (pa, pa_k), (tr, tr_k) = listings(args[0]), listings(args[1])
     by_hash = collections.defaultdict(lambda: ([], []))
     for side, table in enumerate((pa, tr)):
         for n, h in table.items():

@@ -42,7 +42,7 @@ def params(width, height, lens_radius=0.0, tile_rows=8, tile_index=0, tile_count
 
 
 def direct_list(cr):
-    """sphere_direct_list (rt3_device.hip): the at most four spheres with the largest r / max(|C - c0|, R) above 1/2."""
+    """sphere_direct_list (rt3_sphere_plan.hpp): the at most four spheres with the largest r / max(|C - c0|, R) above 1/2."""
     cr = np.asarray(cr, np.float64)
     if len(cr) == 0:
         return []
