@@ -36,7 +36,8 @@ extern "C" {
  * importance sampling (RT3_FLAG_ENV_SAMPLING: one flag bit and two test-only functions), with the emitters' (RT3_FLAG_LIGHT_SAMPLING: the same again)
  * with the display transform (rt3_display*: one new struct of its own), with the lens models (rt3_lens_rays*, rt3_render_lens*,
  * rt3_render_lens_aov*: one new struct of its own), with lens sequences (rt3_denoise_temporal_optic*, rt3_motion_optic*), with display
- * sequences (rt3_display_sequence*: two new structs of their own) and with image textures (rt3_set_texture*, rt3_bind_*_textures*: no struct):
+ * sequences (rt3_display_sequence*: two new structs of their own), with image textures (rt3_set_texture*, rt3_bind_*_textures*: no struct) and
+ * with specular-chain AOVs (rt3_render_aov_specular*, rt3_render_lens_aov_specular*: one new struct of its own):
  * functions were only added, no existing struct changed. */
 #define RT3_ABI_VERSION 3u
 uint32_t rt3_abi_version(void);
@@ -666,6 +667,64 @@ int  rt3_render_lens_aov_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_pa
 /* Host only, no device and no context: the law above in C for one (pixel, sample) of the whole frame.  RT3_E_ARG for a NULL pointer, a lens the
  * entry points refuse, width or height 0, spp 0, x >= width, y >= height or s >= spp.  tests/lens_ref.py restates it bit for bit. */
 int  rt3_debug_lens_ray(const rt3_lens* lens, const rt3_params* params, uint32_t x, uint32_t y, uint32_t s, rt3_ray* out);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Specular-chain AOVs  (DESIGN.md 4.27, 5.2v): guides taken at the first rough surface behind mirrors and glass
+ * ------------------------------------------------------------------------------------------------- */
+/* rt3_render_aov_specular* / rt3_render_lens_aov_specular* are rt3_render_aov* / rt3_render_lens_aov* with every sample's ray followed through ideal
+ * mirrors and glass.  Per sample, from the primary ray, throughput T = (1, 1, 1), length L = 0, bounces used b = 0:
+ *   trace with rt3_intersect's rule (t_min from params, t_max = +inf); an invalid primary ray is what it is there (albedo 0, no hit).
+ *   miss: the chain ends, albedo = T x the miss colour of rt3_render_aov (sky, map, or 0 under RT3_FLAG_BLACK_BACKGROUND), one rounded multiply per
+ *     channel; normal and L stay those of the last surface the chain hit (a primary miss: 0 and nothing).
+ *   hit: point, normal, material record and texture modulation as rt3_render_aov takes them; L = L + t; front = d.n < 0 before the normal is flipped
+ *     to face the ray.  The chain FOLLOWS when b < max_bounces and the material is RT3_MAT_METAL with param <= max_fuzz, or RT3_MAT_DIELECTRIC; else it
+ *     ENDS here: albedo = T x rgb (a dielectric: T x 1), normal = this normal.
+ *     metal: k = 2 (d.n); m = fma(-k, n, d); r = m * (1 / sqrt(m.m)); if !(r.n > 0) the chain ends here (the render's "absorbed"), else T = T x rgb
+ *       and the next direction is r * (1 / sqrt(r.r)).  The fuzz is ignored: a followed metal is an ideal mirror.
+ *     dielectric: ri = front ? 1 / ior : ior; c = min(-(d.n), 1); s = sqrt(max(fma(-c, c, 1), 0)); if ri s > 1 the direction is m (total internal
+ *       reflection), else e = fma(c, n, d) * ri, q = -sqrt(|1 - e.e|), direction fma(q, n, e); either is scaled by 1 / sqrt(of its own dot).  The chain
+ *       refracts whenever it can (no Fresnel choice); T is unchanged.
+ *     the next ray starts at the hit point with t_max = +inf, b = b + 1; were it INVALID under rt3_intersect's rule, the chain ends at this surface.
+ *   (a.b is the fused chain fma(az, bz, fma(ay, by, ax * bx)) throughout.)
+ * Per pixel the sums are rt3_render_aov's, in sample order: albedo and normal over all samples, L over the samples whose PRIMARY ray hit, coverage =
+ * those samples / spp (geometric); kind / index stay sample 0's FIRST hit, so an id mask still names the object on screen.  The output is an ordinary
+ * rt3_aov: albedo is what demodulation should divide by, normal the end surface's normal, depth the path length to it (the "virtual depth").
+ * max_bounces = 0 is rt3_render_aov* / rt3_render_lens_aov* byte for byte.
+ * Checks, streams, the event chain, shards and the refusal of RT3_FLAG_REFERENCE_PRIMARY are those of the first-hit twins; additionally RT3_E_ARG, with
+ * the context's state untouched, for chain == NULL, max_bounces > 16, a max_fuzz that is NaN, negative or infinite, flags != 0 and _pad != 0.
+ * rt3_get_stats afterwards: ray_casts = valid rays traced over all bounces, samples = pixels x spp, launches / trace_ms summed over the at most
+ * max_bounces + 1 queries of each sample batch (batches sized by rt3_set_sample_storage_cap at 96 bytes per pixel and sample; the result does not depend
+ * on them).  The device forms are ordered on `stream` like their twins but wait for it once per bounce: one word, the chains still running, is
+ * read back and the loop stops at 0.  The temporal denoisers and rt3_motion* rebuild the first-hit point from depth: give them first-hit AOVs, not
+ * these. */
+typedef struct rt3_aov_chain_params {   /* 16 bytes */
+    uint32_t max_bounces;   /* 0..16; 0: rt3_render_aov exactly */
+    float    max_fuzz;      /* finite, >= 0: metals with param <= max_fuzz are followed (as ideal mirrors) */
+    uint32_t flags;         /* 0 */
+    uint32_t _pad;          /* 0 */
+} rt3_aov_chain_params;
+/* RT3_CHECK_RESULT: the compiler warns where the caller drops the return code (a refused chain struct leaves out_aov unwritten). */
+#if defined(__GNUC__) || defined(__clang__)
+#define RT3_CHECK_RESULT __attribute__((warn_unused_result))
+#else
+#define RT3_CHECK_RESULT
+#endif
+int  rt3_render_aov_specular(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* params, const rt3_aov_chain_params* chain, rt3_aov* out_aov)
+     RT3_CHECK_RESULT;
+int  rt3_render_aov_specular_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* params, const rt3_aov_chain_params* chain,
+                                    void* d_out_aov, void* stream) RT3_CHECK_RESULT;
+int  rt3_render_lens_aov_specular(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* params, const rt3_aov_chain_params* chain, rt3_aov* out_aov)
+     RT3_CHECK_RESULT;
+int  rt3_render_lens_aov_specular_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* params, const rt3_aov_chain_params* chain,
+                                         void* d_out_aov, void* stream) RT3_CHECK_RESULT;
+/* Host only, no device and no context; for the tests: one hit of the law above in C.  d: the ray's unit direction, p: the hit point, n: the surface's
+ * normal before the flip, mat_kind / mat: the material's kind and DEVICE record (metal: rgb, fuzz; dielectric: 1 / ior, r0, r0', ior — only [0] and
+ * [3] are read), T: the throughput, bounces_used: b.  Writes *follow (1: the chain goes on), out_rgb (follow: the new throughput; else the end's albedo),
+ * out_normal (flipped to face the ray) and out_direction (follow: the next unit direction; else 0).  RT3_E_ARG for a NULL pointer or chain params the
+ * entry points refuse.  tests/aov_chain_ref.py restates it bit for bit. */
+int  rt3_debug_aov_bounce(const float d[3], const float p[3], const float n[3], uint32_t mat_kind, const float mat[4], const float T[3],
+                          uint32_t bounces_used, const rt3_aov_chain_params* chain, float out_rgb[3], float out_normal[3], float out_direction[3],
+                          uint32_t* follow);
 
 /* ---------------------------------------------------------------------------------------------------
  * Lens sequences  (DESIGN.md 4.24, 5.2s): the temporal denoiser and the motion plane for frames rendered through a lens

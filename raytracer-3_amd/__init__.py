@@ -87,6 +87,11 @@ class rt3_stats(C.Structure):
                 ("exact_tests", C.c_uint64), ("filter_tests", C.c_uint64), ("bound_tests", C.c_uint64)]
 
 
+class rt3_aov_chain_params(C.Structure):
+    """rt3_aov_chain_params (16 bytes): how far rt3_render_aov_specular* follows mirrors and glass."""
+    _fields_ = [("max_bounces", C.c_uint32), ("max_fuzz", C.c_float), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class rt3_ray(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("direction", C.c_float * 3), ("_pad", C.c_uint32)]
 
@@ -273,6 +278,8 @@ EXPORTS = [
     "rt3_set_texture", "rt3_set_texture_device", "rt3_clear_textures", "rt3_texture_size", "rt3_bind_sphere_textures",
     "rt3_bind_sphere_textures_device", "rt3_bind_mesh_textures", "rt3_bind_mesh_textures_device", "rt3_debug_texture_lookup",
     "rt3_debug_texture_sphere_uv", "rt3_debug_texture_face_uv",
+    "rt3_render_aov_specular", "rt3_render_aov_specular_device", "rt3_render_lens_aov_specular", "rt3_render_lens_aov_specular_device",
+    "rt3_debug_aov_bounce",
 ]
 TEX_MAX_TEXTURES = 256   # RT3_TEX_MAX_TEXTURES: texture slots per context
 TEX_MAX_SIDE = 8192      # RT3_TEX_MAX_SIDE
@@ -382,6 +389,9 @@ def lib():
         "rt3_bind_mesh_textures": (i32, [vp, vp, vp, u32]), "rt3_bind_mesh_textures_device": (i32, [vp, vp, vp, u32, vp]),
         "rt3_debug_texture_lookup": (i32, [vp, u32, u32, u32, vp, vp]), "rt3_debug_texture_sphere_uv": (i32, [vp, vp]),
         "rt3_debug_texture_face_uv": (i32, [vp, vp, vp, vp, vp, vp]),
+        "rt3_render_aov_specular": (i32, [vp, vp, vp, vp, vp]), "rt3_render_aov_specular_device": (i32, [vp, vp, vp, vp, vp, vp]),
+        "rt3_render_lens_aov_specular": (i32, [vp, vp, vp, vp, vp]), "rt3_render_lens_aov_specular_device": (i32, [vp, vp, vp, vp, vp, vp]),
+        "rt3_debug_aov_bounce": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -1397,6 +1407,22 @@ class HipRenderer(Renderer):
     def render_lens_aov_device(self, lens, params, d_out_ptr, stream_ptr=None):
         self._check(lib().rt3_render_lens_aov_device(self._ctx, C.byref(lens), C.byref(params), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
 
+    def render_lens_aov_specular(self, lens, params, max_bounces=8, max_fuzz=0.0, device=None):
+        """Specular-chain AOVs of the lens frame (rt3_render_lens_aov_specular): render_lens_aov with every ray followed through
+        glass and metals of fuzz <= max_fuzz; numpy, or with device a (rows_owned, width, 12) float32 tensor there, as render_lens_aov."""
+        rows = lib().rt3_rows_owned(C.byref(params))
+        chain = rt3_aov_chain_params(max_bounces, max_fuzz, 0, 0)
+        if device is not None and device is not False:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device()) if device is True else torch.device(device)
+            out = torch.empty((rows, params.width, 12), dtype=torch.float32, device=dev)
+            self._check(lib().rt3_render_lens_aov_specular_device(self._ctx, C.byref(lens), C.byref(params), C.byref(chain),
+                                                                  C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            return out
+        out = np.zeros((rows, params.width), AOV)
+        self._check(lib().rt3_render_lens_aov_specular(self._ctx, C.byref(lens), C.byref(params), C.byref(chain), _p(out)))
+        return out
+
     # -- image textures (rt3_set_texture*, rt3_bind_*_textures*; DESIGN.md 4.26) ---------------------------------------
     def set_texture(self, slot, image, wrap="repeat"):
         """Fills texture slot `slot` (< TEX_MAX_TEXTURES) with a copy of `image`: a numpy array (H, W, 3 | 4), row 0 on top, or a contiguous
@@ -1550,6 +1576,23 @@ class HipRenderer(Renderer):
         """Asynchronous AOVs into a device buffer of rows_owned * width * 48 bytes (e.g. a torch tensor's data_ptr())."""
         self._check(lib().rt3_render_aov_device(self._ctx, C.byref(camera_c), C.byref(params), C.c_void_p(d_out_ptr),
                                                 C.c_void_p(stream_ptr or 0)))
+
+    def render_aov_specular(self, camera_c, params, max_bounces=8, max_fuzz=0.0):
+        """Specular-chain AOVs (rt3_render_aov_specular): render_aov with every ray followed through glass and through metals of
+        fuzz <= max_fuzz, at most max_bounces times, to the first rough surface — albedo, normal and path length of that end; kind / index of the
+        first hit.  max_bounces = 0 is render_aov.  For denoise(), not for the temporal denoisers (they rebuild the first-hit point from depth)."""
+        rows = lib().rt3_rows_owned(C.byref(params))
+        out = np.zeros((rows, params.width), AOV)
+        chain = rt3_aov_chain_params(max_bounces, max_fuzz, 0, 0)
+        self._check(lib().rt3_render_aov_specular(self._ctx, C.byref(camera_c), C.byref(params), C.byref(chain), _p(out)))
+        return out
+
+    def render_aov_specular_device(self, camera_c, params, d_out_ptr, stream_ptr=None, max_bounces=8, max_fuzz=0.0):
+        """rt3_render_aov_specular_device into a device buffer of rows_owned * width * 48 bytes.  The call reads one word back per bounce (it
+        stops once every chain has ended), so it is ordered on the stream but waits for it."""
+        chain = rt3_aov_chain_params(max_bounces, max_fuzz, 0, 0)
+        self._check(lib().rt3_render_aov_specular_device(self._ctx, C.byref(camera_c), C.byref(params), C.byref(chain), C.c_void_p(d_out_ptr),
+                                                         C.c_void_p(stream_ptr or 0)))
 
     def accum_resolve(self, params):
         """The accumulation as a linear float frame (rt3_accum_resolve): float32 (rows_owned, width, 4), (r, g, b, 0)."""

@@ -124,7 +124,10 @@ struct rt3_ctx {
     DevBuf<float4> d_arays;                                         // first-hit AOVs (rt3_render_aov*): one batch's camera rays and their hits,
     DevBuf<uint4> d_ahits;                                          // and the per-pixel running sums (three planes; not d_accum, which belongs to
     DevBuf<float4> d_aacc;                                          // the progressive render)
-    DevBuf<uint32_t> d_lens_keys;                                   // a shard's frame pixel indices (rt3_render_lens*: the keys of its rays)
+    // specular-chain AOVs (rt3_render_aov_specular*): per item of a batch the bounce queries' hits (the primary ones stay in d_ahits),
+    // the chain's state (T, L) and its last normal; the count of chains still running, read back once per bounce
+    DevBuf<uint4> d_chits; DevBuf<float4> d_cstate, d_cnorm; DevBuf<uint32_t> d_calive;
+    DevBuf<uint32_t> d_lens_keys;                                  // a shard's frame pixel indices (rt3_render_lens*: the keys of its rays)
     DevBuf<float4> d_dn;                                            // denoiser scratch (rt3_denoise*): two (I, v) planes, the guide plane, the depth slopes
     // the display transform's auto-exposure (rt3_display*): hist[512], dark, n and the gain's bits, allocated by the first call with the flag and
     // zeroed at the start of each such call; display_auto: there has been one (rt3_debug_display_state)

@@ -51,6 +51,7 @@
 #include "rt3_light_sample.hpp"
 #include "rt3_lens_law.hpp"
 #include "rt3_texture_law.hpp"
+#include "rt3_aov_chain_law.hpp"
 #include "rt3_kernel_common.hpp"
 #include "rt3_filter_frags.hpp"
 #include "rt3_path.hpp"
@@ -1156,17 +1157,27 @@ int rt3_camera_rays(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, ui
 // trace kernel on that buffer -> k_aov_accumulate; then one k_aov_resolve.  The batches share one ev_begin / ev_end and one counter reset, as the
 // render's batch loop does.  A: what k_aov_accumulate reads — the scene's records and the flags.  The caller has checked its arguments and the scene
 // and is behind enter().
+// chain (rt3_render_aov_specular*): each ray is followed through mirrors and glass.  Per batch at most max_bounces + 1 rounds of
+// query -> k_aov_bounce on the same ray buffer (a finished chain's ray is INVALID to the query and costs no trace), the primary hits in d_ahits and
+// every later round's in d_chits; then k_aov_accumulate_chain.  After each round the host reads one word, the chains still running, and leaves the
+// loop at 0 (the adaptive render's precedent; RT3_AOV_CHAIN_NO_WAIT=1 queues every round without waiting — the A/B of DESIGN.md 5.2v).
 static int aov_pass(rt3_ctx* ctx, const rt3_params* p, const TraceArgs& A, void* d_out, hipStream_t stream,
-                    const std::function<int(uint32_t, uint32_t)>& make_rays) {
+                    const std::function<int(uint32_t, uint32_t)>& make_rays, const rt3_aov_chain_params* chain = nullptr) {
     const uint32_t npix = rt3_rows_owned(p) * p->width;
     ctx->rendered = false;
     int rc;
     if (npix == 0) return (rc = begin_timed(ctx, stream)) ? rc : end_timed(ctx, stream, 0, nullptr);
-    const uint32_t batch = sample_batch(ctx, p->spp, npix, sizeof(rt3_ray) + sizeof(rt3_hit));      // 48 B per (pixel, sample): the ray and its hit
+    // 48 B per (pixel, sample): the ray and its hit; a chain adds 48: the bounce queries' hit, the state, the normal
+    const uint32_t batch = sample_batch(ctx, p->spp, npix, sizeof(rt3_ray) + sizeof(rt3_hit) + (chain ? sizeof(rt3_hit) + 2 * sizeof(float4) : 0));
     if (batch == 0) return fail(ctx, RT3_E_ARG, "frame too large for one sample batch");
     if ((rc = ctx->d_arays.ensure(ctx, (size_t)npix * batch * 2u)) || (rc = ctx->d_ahits.ensure(ctx, (size_t)npix * batch)) ||
         (rc = ctx->d_aacc.ensure(ctx, (size_t)npix * 3u)))
         return rc;
+    if (chain && ((rc = ctx->d_chits.ensure(ctx, (size_t)npix * batch)) || (rc = ctx->d_cstate.ensure(ctx, (size_t)npix * batch)) ||
+                  (rc = ctx->d_cnorm.ensure(ctx, (size_t)npix * batch)) || (rc = ctx->d_calive.ensure(ctx, 1))))
+        return rc;
+    const char* no_wait = getenv("RT3_AOV_CHAIN_NO_WAIT");
+    const bool wait = !(no_wait && no_wait[0] == '1');
     TraceArgs Q = scene_args(ctx);                                  // the query launches, as query_device sets them up
     Q.t_min = p->t_min;
     Q.q_rays = ctx->d_arays; Q.q_out = ctx->d_ahits; Q.q_occluded = 0u;
@@ -1176,6 +1187,37 @@ static int aov_pass(rt3_ctx* ctx, const rt3_params* p, const TraceArgs& A, void*
         const uint32_t ns = std::min(batch, p->spp - s0);
         Q.total = npix * ns;
         if ((rc = make_rays(s0, ns))) return rc;
+        if (chain) {
+            TraceArgs B = A;                                        // the bounce kernel: the scene's records, the flags and the batch's item count
+            B.total = Q.total;
+            const dim3 bg((Q.total + kBlock - 1) / kBlock), bb(kBlock);
+            for (uint32_t b = 0; b <= chain->max_bounces; b++) {
+                Q.q_out = b ? ctx->d_chits.get() : ctx->d_ahits.get();
+                if ((rc = issue_trace(ctx, Q, T, Q.total, stream))) return rc;
+                const bool count = wait && b < chain->max_bounces;  // (the last round ends every chain)
+                if (count) {
+                    RT3_HIP(hipMemsetAsync(ctx->d_calive, 0, 4, stream));
+                    hipLaunchKernelGGL(k_aov_bounce<true>, bg, bb, 0, stream, B, ctx->d_arays.get(), (const uint4*)Q.q_out, ctx->d_cstate.get(),
+                                       ctx->d_cnorm.get(), b, chain->max_bounces, chain->max_fuzz, (const float4*)ctx->d_env, ctx->env_n,
+                                       tex_table(ctx), ctx->d_calive.get());
+                } else {
+                    hipLaunchKernelGGL(k_aov_bounce<false>, bg, bb, 0, stream, B, ctx->d_arays.get(), (const uint4*)Q.q_out, ctx->d_cstate.get(),
+                                       ctx->d_cnorm.get(), b, chain->max_bounces, chain->max_fuzz, (const float4*)ctx->d_env, ctx->env_n,
+                                       tex_table(ctx), (uint32_t*)nullptr);
+                }
+                RT3_HIP(hipGetLastError());
+                if (count) {
+                    uint32_t n_alive = 0;
+                    RT3_HIP(hipMemcpyAsync(&n_alive, ctx->d_calive.get(), 4, hipMemcpyDeviceToHost, stream));
+                    RT3_HIP(hipStreamSynchronize(stream));
+                    if (n_alive == 0) break;
+                }
+            }
+            hipLaunchKernelGGL(k_aov_accumulate_chain, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const uint4*)ctx->d_ahits,
+                               (const float4*)ctx->d_cstate, (const float4*)ctx->d_cnorm, ctx->d_aacc.get(), npix, ns, s0 == 0 ? 1 : 0);
+            RT3_HIP(hipGetLastError());
+            continue;
+        }
         if ((rc = issue_trace(ctx, Q, T, Q.total, stream))) return rc;
         hipLaunchKernelGGL(k_aov_accumulate, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, (const float4*)ctx->d_arays,
                            (const uint4*)ctx->d_ahits, ctx->d_aacc, npix, ns, s0 == 0 ? 1 : 0, (const float4*)ctx->d_env, ctx->env_n, tex_table(ctx));
@@ -1229,10 +1271,13 @@ static int radiance_pass(rt3_ctx* ctx, uint32_t n, const rt3_radiance_params& rp
     return end_timed(ctx, stream, (uint64_t)n * rp.sample_count, &T);
 }
 
-int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, void* d_out, void* stream_) {
+// rt3_render_aov_device (chain == nullptr) and rt3_render_aov_specular_device: the same checks and set-up, the chain's own refusals behind the common ones.
+static int render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, const rt3_aov_chain_params* chain, bool specular, void* d_out,
+                             void* stream_) {
     if (!ctx) return RT3_E_ARG;
     int rc = aov_common_checks(ctx, cam, p, d_out, "d_out_aov");
     if (rc) return rc;
+    if (specular) if (const char* why = rt3chain::refusal(chain)) return fail(ctx, RT3_E_ARG, std::string("rt3_render_aov_specular: ") + why);
     if ((rc = check_scene(ctx)) || (rc = check_textures(ctx, 0u))) return rc;       // (the AOVs draw no shadow rays: the sampling flags change nothing here)
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
@@ -1246,7 +1291,13 @@ int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params*
         hipLaunchKernelGGL(k_camera_rays, dim3((A.total + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, A, ctx->d_arays.get());
         RT3_HIP(hipGetLastError());
         return 0;
-    });
+    }, chain);
+}
+int rt3_render_aov_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, void* d_out, void* stream) {
+    return render_aov_device(ctx, cam, p, nullptr, false, d_out, stream);
+}
+int rt3_render_aov_specular_device(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, const rt3_aov_chain_params* chain, void* d_out, void* stream) {
+    return render_aov_device(ctx, cam, p, chain, true, d_out, stream);
 }
 
 int rt3_render_aov(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, rt3_aov* out) {
@@ -1256,6 +1307,15 @@ int rt3_render_aov(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, rt3
     if (rc) return rc;
     return staged(ctx, { stage_out(out, (size_t)rt3_rows_owned(p) * p->width * sizeof(rt3_aov)) },
                   [&](void* const* d) { return rt3_render_aov_device(ctx, cam, p, d[0], ctx->stream); });
+}
+int rt3_render_aov_specular(rt3_ctx* ctx, const rt3_camera* cam, const rt3_params* p, const rt3_aov_chain_params* chain, rt3_aov* out) {
+    if (!ctx) return RT3_E_ARG;
+    if (!out) return fail(ctx, RT3_E_ARG, "out_aov is NULL");
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    if (const char* why = rt3chain::refusal(chain)) return fail(ctx, RT3_E_ARG, std::string("rt3_render_aov_specular: ") + why);
+    return staged(ctx, { stage_out(out, (size_t)rt3_rows_owned(p) * p->width * sizeof(rt3_aov)) },
+                  [&](void* const* d) { return rt3_render_aov_specular_device(ctx, cam, p, chain, d[0], ctx->stream); });
 }
 
 int rt3_accum_resolve_device(rt3_ctx* ctx, void* d_out, void* stream_) {
@@ -1437,10 +1497,12 @@ static int lens_aov_checks(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params*
 }
 
 // aov_pass with k_lens_rays in k_camera_rays' place.
-int rt3_render_lens_aov_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, void* d_out, void* stream_) {
+static int render_lens_aov_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, const rt3_aov_chain_params* chain, bool specular, void* d_out,
+                                  void* stream_) {
     if (!ctx) return RT3_E_ARG;
     int rc = lens_aov_checks(ctx, lens, p, d_out, "d_out_aov", true);
     if (rc) return rc;
+    if (specular) if (const char* why = rt3chain::refusal(chain)) return fail(ctx, RT3_E_ARG, std::string("rt3_render_lens_aov_specular: ") + why);
     if ((rc = check_scene(ctx)) || (rc = check_textures(ctx, 0u))) return rc;
     hipStream_t stream;
     if ((rc = enter(ctx, stream_, &stream))) return rc;
@@ -1449,7 +1511,14 @@ int rt3_render_lens_aov_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_par
     A.flags = p->flags;
     return aov_pass(ctx, p, A, d_out, stream, [&](uint32_t s0, uint32_t ns) {
         return launch_lens_rays(ctx, lens, p, npix, s0, ns, ctx->d_arays, nullptr, stream);
-    });
+    }, chain);
+}
+int rt3_render_lens_aov_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, void* d_out, void* stream) {
+    return render_lens_aov_device(ctx, lens, p, nullptr, false, d_out, stream);
+}
+int rt3_render_lens_aov_specular_device(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, const rt3_aov_chain_params* chain, void* d_out,
+                                        void* stream) {
+    return render_lens_aov_device(ctx, lens, p, chain, true, d_out, stream);
 }
 
 int rt3_render_lens_aov(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, rt3_aov* out) {
@@ -1459,6 +1528,15 @@ int rt3_render_lens_aov(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p,
     if ((rc = check_scene(ctx))) return rc;
     return staged(ctx, { stage_out(out, (size_t)rt3_rows_owned(p) * p->width * sizeof(rt3_aov)) },
                   [&](void* const* d) { return rt3_render_lens_aov_device(ctx, lens, p, d[0], ctx->stream); });
+}
+int rt3_render_lens_aov_specular(rt3_ctx* ctx, const rt3_lens* lens, const rt3_params* p, const rt3_aov_chain_params* chain, rt3_aov* out) {
+    if (!ctx) return RT3_E_ARG;
+    int rc = lens_aov_checks(ctx, lens, p, out, "out_aov", false);
+    if (rc) return rc;
+    if (const char* why = rt3chain::refusal(chain)) return fail(ctx, RT3_E_ARG, std::string("rt3_render_lens_aov_specular: ") + why);
+    if ((rc = check_scene(ctx))) return rc;
+    return staged(ctx, { stage_out(out, (size_t)rt3_rows_owned(p) * p->width * sizeof(rt3_aov)) },
+                  [&](void* const* d) { return rt3_render_lens_aov_specular_device(ctx, lens, p, chain, d[0], ctx->stream); });
 }
 
 int rt3_get_stats(rt3_ctx* ctx, rt3_stats* out) {

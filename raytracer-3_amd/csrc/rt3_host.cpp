@@ -12,6 +12,7 @@
 #include "rt3_display_sequence_law.hpp"
 #include "rt3_lens_law.hpp"
 #include "rt3_texture_law.hpp"
+#include "rt3_aov_chain_law.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -668,6 +669,19 @@ extern "C" int rt3_debug_lens_ray(const rt3_lens* lens, const rt3_params* p, uin
     rt3lens::ray_of(*lens, f, x, y, s, out->origin, out->direction);
     out->t_max = __builtin_inff();
     out->_pad = 0u;
+    return 0;
+}
+// One hit of the specular-chain law (rt3.h "Specular-chain AOVs") on the host: the statement of rt3_aov_chain_law.hpp k_aov_bounce evaluates.
+extern "C" int rt3_debug_aov_bounce(const float d[3], const float p[3], const float n[3], uint32_t mat_kind, const float mat[4], const float T[3],
+                                    uint32_t bounces_used, const rt3_aov_chain_params* chain, float out_rgb[3], float out_normal[3],
+                                    float out_direction[3], uint32_t* follow) {
+    if (!d || !p || !n || !mat || !T || !out_rgb || !out_normal || !out_direction || !follow || rt3chain::refusal(chain)) return RT3_E_ARG;
+    const rt3chain::Step S = rt3chain::step(d[0], d[1], d[2], p[0], p[1], p[2], n[0], n[1], n[2], mat_kind, mat[0], mat[1], mat[2], mat[3],
+                                            T[0], T[1], T[2], bounces_used, chain->max_bounces, chain->max_fuzz);
+    out_rgb[0] = S.ax; out_rgb[1] = S.ay; out_rgb[2] = S.az;
+    out_normal[0] = S.nx; out_normal[1] = S.ny; out_normal[2] = S.nz;
+    out_direction[0] = S.dx; out_direction[1] = S.dy; out_direction[2] = S.dz;
+    *follow = S.follow;
     return 0;
 }
 // The inverse law (rt3.h "Lens sequences") on the host: the statements of rt3_lens_law.hpp k_temporal_reproject evaluates.

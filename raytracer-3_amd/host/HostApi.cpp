@@ -405,6 +405,20 @@ std::vector<rt3_aov> HipRenderer::aov(Camera& camera) const {
     return frame;
 }
 
+std::vector<rt3_aov> HipRenderer::aov_specular(Camera& camera, const rt3_aov_chain_params& chain) const {
+    if (path.spp == 0) throw Fatal("specular-chain AOVs need the path tracer (Mode X)");
+    const rt3_camera cam = camera.wire();
+    const uint32_t w = camera.w(), h = camera.h();
+    std::vector<rt3_aov> frame((size_t)w * h);
+    gather_shards<rt3_aov>((uint32_t)ctx.size(), w, [&](uint32_t i) { return shard_params(w, h, i); },
+                           [&](uint32_t i, const rt3_params& p, rt3_aov* tile, std::string& err) {
+                               if (rt3_render_aov_specular(ctx[i], &cam, &p, &chain, tile) == 0) return true;
+                               err = rt3_last_error(ctx[i]);
+                               return false;
+                           }, frame.data());
+    return frame;
+}
+
 std::vector<float> HipRenderer::hdr() const {
     if (path.spp == 0 || last_w == 0) throw Fatal("the linear frame needs a Mode-X render first");
     struct Rgba { float v[4]; };
@@ -501,6 +515,14 @@ std::vector<rt3_aov> HipRenderer::lens_aov(const rt3_lens& lens, uint32_t width,
     const rt3_params p = lens_params(path, width, height);
     std::vector<rt3_aov> out((size_t)width * height);
     if (rt3_render_lens_aov(ctx[0], &lens, &p, out.data()) != 0) throw Fatal(rt3_last_error(ctx[0]));
+    return out;
+}
+
+std::vector<rt3_aov> HipRenderer::lens_aov_specular(const rt3_lens& lens, uint32_t width, uint32_t height, const rt3_aov_chain_params& chain) const {
+    if (path.spp == 0) throw Fatal("a lens frame's AOVs need the path tracer (Mode X)");
+    const rt3_params p = lens_params(path, width, height);
+    std::vector<rt3_aov> out((size_t)width * height);
+    if (rt3_render_lens_aov_specular(ctx[0], &lens, &p, &chain, out.data()) != 0) throw Fatal(rt3_last_error(ctx[0]));
     return out;
 }
 

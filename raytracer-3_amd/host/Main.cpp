@@ -40,6 +40,8 @@ struct Options {
     uint32_t spp = 0, depth = 50, seed = 1, gpus = 1;
     bool gpu_prerender = false, dump_scene = false;
     std::string aov_prefix, hdr_path;                              // Mode X: first-hit AOVs / the linear beauty as PFM files
+    bool aov_specular = false;                                     // --aov-specular: --aov and the single-frame --denoise take specular-chain guides
+    rt3_aov_chain_params chain{ 0u, 0.0f, 0u, 0u };
     std::string denoise_path;                                      // Mode X: the denoised linear frame as a PFM file
     uint32_t frames = 1;                                           // Mode X: frames of a sequence (frame k renders with seed + k)
     float orbit = 0.0f;                                            // look-at scenes: degrees the look-from point turns per frame
@@ -92,6 +94,8 @@ void print_usage(const char* exe) {
               << "\t   --gpus\tNumber of GPUs to shard the frame over (default: 1).\n"
               << "\t   --gpu-prerender\tTessellate spheres on the GPU instead of the host (same arrays).\n"
               << "\t   --dump-scene\tParse the --scene file, print its entities and exit.\n"
+              << "\t   --aov-specular\tBOUNCES[,MAX_FUZZ]. Mode X: --aov and the single-frame --denoise take their guides at the first rough surface behind\n"
+              << "\t\t\tglass and metals of fuzz <= MAX_FUZZ (default 0), following at most BOUNCES (<= 16) bounces. Not with --frames or --lens-frames.\n"
               << "\t   --aov\tMode X: also write the first-hit AOVs as PREFIX.albedo.pfm, PREFIX.normal.pfm and PREFIX.depth.pfm.\n"
               << "\t   --hdr\tMode X: also write the linear (float) frame to this path as a 3-channel PFM.\n"
               << "\t   --denoise\tMode X: also write the denoised linear frame (a-trous, AOV-guided) to this path as a 3-channel PFM;\n"
@@ -197,7 +201,7 @@ int parse_cli(Options& opt, int argc, const char** argv) {
                            key == "--slide" || key == "--adaptive" || key == "--counts" || key == "--regroup" ||
                            key == "--rays" || key == "--radiance" || key == "--env" || key == "--display" || key == "--lens" || key == "--lens-fov" ||
                            key == "--lens-extent" || key == "--lens-frames" || key == "--display-frames" || key == "--adapt" || key == "--bloom" ||
-                           key == "--texture" || key == "--bind-sphere";
+                           key == "--texture" || key == "--bind-sphere" || key == "--aov-specular";
         if (!known) {
             std::cerr << "Unknown option '" << argv[i] << "'\n\n" << "Run '" << argv[0] << " -h' to see a list of valid options.\n\n";
             return -1;
@@ -220,6 +224,22 @@ int parse_cli(Options& opt, int argc, const char** argv) {
         else if (key == "--seed") { if (!parse_u32(value, "seed", "Seed", &opt.seed)) return -1; }
         else if (key == "--gpus") { if (!parse_u32(value, "gpus", "Gpus", &opt.gpus)) return -1; }
         else if (key == "--aov") opt.aov_prefix = value;
+        else if (key == "--aov-specular") {                          // BOUNCES[,MAX_FUZZ]
+            const size_t comma = value.find(',');
+            if (!parse_u32(value.substr(0, comma), "aov-specular", "Aov-specular", &opt.chain.max_bounces)) return -1;
+            if (comma != std::string::npos) {
+                const std::string fz = value.substr(comma + 1);
+                char* end = nullptr;
+                const double f = std::strtod(fz.c_str(), &end);
+                if (end == fz.c_str() || *end != '\0' || !(f >= 0.0) || !std::isfinite((float)f)) {
+                    std::cerr << "Invalid aov-specular fuzz '" << fz << "'" << std::endl;
+                    return -1;
+                }
+                opt.chain.max_fuzz = (float)f;
+            }
+            if (opt.chain.max_bounces > 16u) { std::cerr << "--aov-specular follows at most 16 bounces." << std::endl; return -1; }
+            opt.aov_specular = true;
+        }
         else if (key == "--hdr") opt.hdr_path = value;
         else if (key == "--denoise") opt.denoise_path = value;
         else if (key == "--frames") { if (!parse_u32(value, "frames", "Frames", &opt.frames)) return -1; }
@@ -378,6 +398,11 @@ int parse_cli(Options& opt, int argc, const char** argv) {
     const bool mode_r = opt.spp == 0 && (opt.scene == "builtin" || (opt.scene.size() > 6 && opt.scene.compare(opt.scene.size() - 6, 6, ".scene") == 0));
     if (mode_r && (!opt.aov_prefix.empty() || !opt.hdr_path.empty())) {
         std::cerr << "--aov and --hdr need the path tracer (Mode X): pass --spp." << std::endl;
+        return -1;
+    }
+    if (opt.aov_specular && mode_r) { std::cerr << "--aov-specular needs the path tracer (Mode X): pass --spp." << std::endl; return -1; }
+    if (opt.aov_specular && (opt.frames > 1 || opt.lens_frames > 1)) {
+        std::cerr << "--aov-specular is not available with --frames or --lens-frames: the temporal denoisers rebuild the first-hit point from depth." << std::endl;
         return -1;
     }
     if (mode_r && !opt.denoise_path.empty()) {
@@ -738,7 +763,8 @@ int main(int argc, const char** argv) {
             std::cerr << "rendered a lens frame of " << w << "x" << h << " x " << path.spp << " spp in " << st.total_ms << " ms on device 0: " << st.ray_casts
                       << " rays, " << st.launches << " launches\n";
             const bool need_aov = !opt.aov_prefix.empty() || (!opt.denoise_path.empty() && !temporal);
-            const std::vector<rt3_aov> aov = need_aov ? renderer.lens_aov(lens, w, h) : std::vector<rt3_aov>();
+            const std::vector<rt3_aov> aov = !need_aov ? std::vector<rt3_aov>()
+                                             : opt.aov_specular ? renderer.lens_aov_specular(lens, w, h, opt.chain) : renderer.lens_aov(lens, w, h);
             const rt3_denoise_params dp{ 5, 128, 4.0f, 1.0f };                       // the defaults of DESIGN.md 4.11
             const std::vector<float> denoised = opt.denoise_path.empty() || temporal ? std::vector<float>() : renderer.denoise(w, h, linear, aov, dp);
             // the image: --display's transform, or the one that reproduces the ordinary Mode-X pack (no curve, the scene's gamma)
@@ -787,9 +813,13 @@ int main(int argc, const char** argv) {
         std::cerr << "rendered " << opt.width << "x" << opt.height << (path.spp ? " x " + std::to_string(path.spp) + " spp" : " (mode R)")
                   << " in " << st.total_ms << " ms on device 0: " << st.ray_casts << " rays, " << st.prim_tests << " ray-primitive tests\n";
         const rt3_denoise_params dp{ 5, 128, 4.0f, 1.0f };                         // the defaults of DESIGN.md 4.11
+        // the single-frame denoiser: guided by the first-hit AOVs, or under --aov-specular by the chain's
+        const auto denoise_frame = [&]() {
+            return opt.aov_specular ? renderer.denoise(cam.w(), cam.h(), renderer.hdr(), renderer.aov_specular(cam, opt.chain), dp) : renderer.denoise(cam, dp);
+        };
         std::vector<float> denoised;                                 // --display with a single-frame --denoise: the frame both outputs come from
         if (opt.display) {                                           // the image becomes the display transform of the linear frame
-            if (!opt.denoise_path.empty() && !temporal) denoised = renderer.denoise(cam, dp);
+            if (!opt.denoise_path.empty() && !temporal) denoised = denoise_frame();
             display_image(denoised.empty() ? renderer.hdr() : denoised);
         }
         if (opt.png) cam.get_frame().to_png(opt.output_path);
@@ -809,7 +839,7 @@ int main(int argc, const char** argv) {
             if (rt3_frame_to_pfm(hdr.data(), w, h, 3, 4, opt.hdr_path.c_str()) != 0) throw Fatal("Could not write '" + opt.hdr_path + "'");
         }
         if (!opt.aov_prefix.empty()) {
-            const std::vector<rt3_aov> aov = renderer.aov(cam);
+            const std::vector<rt3_aov> aov = opt.aov_specular ? renderer.aov_specular(cam, opt.chain) : renderer.aov(cam);
             const float* base = reinterpret_cast<const float*>(aov.data());          // (rt3_aov: 12 floats and words, 48 bytes)
             const struct { const char* name; size_t offset; uint32_t channels; } planes[] = { { ".albedo.pfm", 0, 3 }, { ".normal.pfm", 4, 3 }, { ".depth.pfm", 7, 1 } };
             for (const auto& pl : planes) {
@@ -819,7 +849,7 @@ int main(int argc, const char** argv) {
             }
         }
         if (!opt.denoise_path.empty() && !temporal) {
-            const std::vector<float> out = denoised.empty() ? renderer.denoise(cam, dp) : denoised;
+            const std::vector<float> out = denoised.empty() ? denoise_frame() : denoised;
             if (rt3_frame_to_pfm(out.data(), w, h, 3, 4, opt.denoise_path.c_str()) != 0) throw Fatal("Could not write '" + opt.denoise_path + "'");
         }
         if (!opt.rays_path.empty()) {                                // last: it replaces the render's stats, and touches nothing the outputs above read

@@ -73,6 +73,9 @@ public:
     // Mode X only, full frames (row 0 on top) assembled from the device shards: the first-hit AOVs of the current options (rt3_render_aov),
     // and the linear (r, g, b, 0) frame of the last render (rt3_accum_resolve)
     std::vector<rt3_aov> aov(Camera& camera) const;
+    // ... and the specular-chain AOVs (rt3_render_aov_specular): every ray followed through glass and the metals `chain` admits to the
+    // first rough surface; guides for denoise(width, height, colour, guides, params), not for the temporal denoisers or motion()
+    std::vector<rt3_aov> aov_specular(Camera& camera, const rt3_aov_chain_params& chain) const;
     std::vector<float> hdr() const;
     // Mode X only: the linear frame of the last render denoised on device 0 (rt3_denoise), guided by aov(camera); (r, g, b, 0) per pixel
     std::vector<float> denoise(Camera& camera, const rt3_denoise_params& params) const;
@@ -98,6 +101,7 @@ public:
     // (rt3_render_lens_aov).  A cube lens's frame (width N, height 6 N) is the array set_environment takes.
     std::vector<float> render_lens(const rt3_lens& lens, uint32_t width, uint32_t height) const;
     std::vector<rt3_aov> lens_aov(const rt3_lens& lens, uint32_t width, uint32_t height) const;
+    std::vector<rt3_aov> lens_aov_specular(const rt3_lens& lens, uint32_t width, uint32_t height, const rt3_aov_chain_params& chain) const;   // (rt3_render_lens_aov_specular)
     // One frame of a sequence of lens frames through the temporal denoiser on device 0 (rt3_denoise_temporal_optic): colour and guides
     // are render_lens's and lens_aov's for `lens`; `history` is the previous frame's and is replaced by this frame's; motion: empty, or motion_lens's plane
     std::vector<float> denoise_temporal_lens(const rt3_lens& lens, uint32_t width, uint32_t height, const std::vector<float>& colour,

@@ -83,6 +83,10 @@ int rt3_camera_rays(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t, ui
 int rt3_camera_rays_device(rt3_ctx*, const rt3_camera*, const rt3_params*, uint32_t, uint32_t, void*, void*) { return RT3_E_DEVICE; }
 int rt3_render_aov(rt3_ctx*, const rt3_camera*, const rt3_params*, rt3_aov*) { return RT3_E_DEVICE; }
 int rt3_render_aov_device(rt3_ctx*, const rt3_camera*, const rt3_params*, void*, void*) { return RT3_E_DEVICE; }
+int rt3_render_aov_specular(rt3_ctx*, const rt3_camera*, const rt3_params*, const rt3_aov_chain_params*, rt3_aov*) { return RT3_E_DEVICE; }     // (rt3_debug_aov_bounce is host code)
+int rt3_render_aov_specular_device(rt3_ctx*, const rt3_camera*, const rt3_params*, const rt3_aov_chain_params*, void*, void*) { return RT3_E_DEVICE; }
+int rt3_render_lens_aov_specular(rt3_ctx*, const rt3_lens*, const rt3_params*, const rt3_aov_chain_params*, rt3_aov*) { return RT3_E_DEVICE; }
+int rt3_render_lens_aov_specular_device(rt3_ctx*, const rt3_lens*, const rt3_params*, const rt3_aov_chain_params*, void*, void*) { return RT3_E_DEVICE; }
 int rt3_accum_resolve(rt3_ctx*, float*) { return RT3_E_DEVICE; }
 int rt3_accum_resolve_device(rt3_ctx*, void*, void*) { return RT3_E_DEVICE; }
 int rt3_denoise(rt3_ctx*, uint32_t, uint32_t, const float*, const rt3_aov*, const rt3_denoise_params*, float*) { return RT3_E_DEVICE; }
